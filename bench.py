@@ -18,7 +18,9 @@ BASELINE.json's metric has two halves and the default workload follows N:
          also runs the whole job alone for a few steps, so that every line carries its own one-GPU reference.
 `--workload c2|c3|c4` overrides (c4 at N = 1: --batch alignments on the one GPU).
 
-Prints ONE JSON line on rank 0.  `value` = ICP iterations/s over all ranks (`alignments_per_sec` beside it for C4).
+Prints ONE JSON line on rank 0.  `value` = ICP iterations/s over all ranks (`alignments_per_sec` beside it for C4);
+`ms_per_step` = wall time of one of the --steps timed steps.  --dump-outputs DIR: rank 0 writes what the last timed step
+of the headline workload computed (the result record of every alignment of the job; C5: the solved poses) as DIR/*.npy.
 """
 import argparse
 import json
@@ -53,9 +55,16 @@ def parse():
     ap.add_argument("--c3-own-clouds", action="store_true", help="c3: every slice uploads its own copy of the clouds (round <= 3)")
     ap.add_argument("--dump-table", default=None, help="rank 0 saves the exchanged result table of the last step (.npy): tests")
     ap.add_argument("--print-launch", action="store_true", help="N > 1 without a launcher: print the command that would be run, and exit")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy (float32 / float64), so that two "
+                         "builds can be compared output for output on the same seeded inputs")
     a = ap.parse_args()
     if a.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if a.steps is not None and a.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if a.warmup is not None and a.warmup < 0:
+        raise SystemExit("bench.py: --warmup must be >= 0")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if "WORLD_SIZE" in os.environ and world != a.gpus:
         # (a launcher started `world` ranks for a command line that says --gpus N: the line would claim the wrong N)
@@ -69,9 +78,33 @@ def parse():
 
 def fill_defaults(a, world):
     if a.steps is None:
-        a.steps = 200 if a.workload == "c2" else (100 if a.workload == "c3" else 20)
+        a.steps = {"c2": 200, "c3": 100, "c5": 3}.get(a.workload, 20)
     if a.warmup is None:
-        a.warmup = 20 if a.workload != "c4" else 3
+        a.warmup = {"c4": 3, "c5": 1}.get(a.workload, 20)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array; integers are stored as float64 (exact below 2**53)"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def record_outputs(table, workload):
+    """the result records of the last timed step of every alignment of the job (distributed.py's layout: estimate,
+    status, statistics of the last iteration and, for the batch path, H) as named arrays"""
+    from srrg2_slam_interfaces_amd import distributed as D
+
+    out = {"moving_in_fixed": table[:, :12].astype(np.float32).reshape(-1, 3, 4),
+           "status": table[:, 12], "num_iterations": table[:, 13], "num_inliers": table[:, 14],
+           "num_outliers": table[:, 15], "num_correspondences": table[:, 16],
+           "chi_inliers": table[:, 17].astype(np.float32)}
+    if workload == "c4":  # (compute_batch returns H of the last Gauss-Newton iteration; compute() does not)
+        out["information"] = np.stack([D.unpack_record(r)["information"] for r in table])
+    return out
 
 
 def launch_command(gpus, argv, port):
@@ -270,6 +303,7 @@ def measure(args, init_dist=True):
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    recs = records(res)  # (what the last timed step computed, read before anything else runs on the handle)
     # the driver runs --steps 20, a 5 ms sample of C2.  `value` stays the K timed steps the contract asks for; a
     # second figure from a loop of >= 50 ms (>= 200 steps) rides beside it with its own min / median / max.
     long_run = None
@@ -290,10 +324,12 @@ def measure(args, init_dist=True):
                     "ms_per_step": dt_long / n_long * 1e3,
                     "step_ms_min_median_max": [min(long_s) * 1e3, float(np.median(long_s)) * 1e3, max(long_s) * 1e3]}
     gc.enable()
-    table = D.exchange_records(records(res), K_total, device=coll_device, mode=args.exchange)
+    table = D.exchange_records(recs, K_total, device=coll_device, mode=args.exchange)
     assert table.shape[0] == K_total
     if args.dump_table and rank == 0:
         np.save(args.dump_table, table)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, record_outputs(table, args.workload))
     all_success = bool(np.all(table[:, 12] == 0)) and bool(np.all(table[:, 13] == args.iterations))
     total_units = args.iterations * K_total if args.workload == "c4" else units_per_step * world
     if world > 1:
@@ -590,9 +626,10 @@ def measure_c4_distinct(iterations=10, n_align=8, points=50_000):
                                    "(set_fixed + set_moving + compute() per alignment, clouds resident in HBM)" % (n_align, points)}}
 
 
-def measure_c5(cpu_seconds=30.0, with_cpu=True):
+def measure_c5(cpu_seconds=30.0, with_cpu=True, steps=3, warmup=1, dump_dir=None):
     """C5: pose-graph Gauss-Newton solve, 50 000 SE(3) poses / 200 000 factors, 10 iterations, PCG tolerance 1e-6
-    (MultiGraphSLAM_::optimize -> global_solver->compute(), S/system/multi_graph_slam_impl.cpp:300-317)"""
+    (MultiGraphSLAM_::optimize -> global_solver->compute(), S/system/multi_graph_slam_impl.cpp:300-317).  A step is one
+    cold solve of the same initial graph; `steps` timed solves follow `warmup` untimed ones."""
     import srrg2_slam_interfaces_amd as pkg
     from srrg2_slam_interfaces_amd import _abi as abi
     from srrg2_slam_interfaces_amd import posegraph as pgm
@@ -604,13 +641,16 @@ def measure_c5(cpu_seconds=30.0, with_cpu=True):
     pg = pkg.PoseGraph(abi.SE3_QUAT_RIGHT)
     pg.set_tuning(keep_structure=0)  # COLD solves: every one builds the structure of the multigrid hierarchy (matching on the host, patterns on the device)
     times, st = [], None
-    for _ in range(4):
+    for _ in range(warmup + steps):
         pg.set_graph(g["poses_init"], g["ij"], g["Z"])
         t0 = time.perf_counter()
         st = pg.solve()
         times.append(time.perf_counter() - t0)
-    times = times[1:]  # (the first solve also pays for first-touch allocations: warm-up; the figure is the MEDIAN of three)
+    times = times[warmup:]  # (the first solve also pays for first-touch allocations: warm-up; the figure is the MEDIAN)
     best = float(np.median(times))
+    if dump_dir:  # the solved poses and the statistics of every Gauss-Newton iteration of the last timed solve
+        dump_outputs(dump_dir, {"poses": pg.poses(), "chi": [s_["chi"] for s_ in st],
+                                "pcg_iterations": [s_["pcg_iterations"] for s_ in st]})
     pcg = sum(s_["pcg_iterations"] for s_ in st)
     params = pgm.default_params()
     converged = all(s_["solver_status"] == 0 and s_["pcg_iterations"] < params.pcg_max_iterations and
@@ -711,8 +751,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     explicit = args.explicit_workload
     if args.workload == "c5":  # (replicas only: the pose graph does not shard)
-        r = measure_c5(with_cpu=not args.no_cpu_baseline)
-        line = {"metric": "posegraph_gauss_newton_iterations_per_sec", "n_gpus": 1, "steps": 3, "warmup": 0,
+        r = measure_c5(with_cpu=not args.no_cpu_baseline, steps=args.steps, warmup=args.warmup, dump_dir=args.dump_outputs)
+        line = {"metric": "posegraph_gauss_newton_iterations_per_sec", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic"}
         line.update(r)
         print(json.dumps(line))
@@ -728,6 +768,7 @@ def main():
         def nested(workload, **over):
             a = copy.copy(args)
             a.workload, a.no_cpu_baseline = workload, True
+            a.dump_outputs = None  # (the outputs are the headline's)
             a.steps, a.warmup = None, None
             for k, v in over.items():
                 setattr(a, k, v)

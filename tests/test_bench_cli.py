@@ -57,3 +57,45 @@ def test_bare_gpus_2_runs_two_ranks_or_fails_loudly():
     assert len(lines) == 1, out.stdout
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 2 and rec["shared_gpu_dry_run"] is True and rec["config"]["alignments_per_step_by_rank"] == [4, 4]
+
+
+@pytest.mark.gpu
+def test_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the result records of the last timed step as .npy files (float32 / float64, well under 64 MB),
+    equal to what one compute_batch of the same seeded job returns; --steps sets the number of timed steps and the line
+    carries ms_per_step"""
+    import numpy as np
+
+    out_dir = tmp_path / "outputs"
+    args = [sys.executable, BENCH, "--gpus", "1", "--workload", "c4", "--batch", "8", "--batch-points", "8000",
+            "--steps", "3", "--warmup", "1", "--dump-outputs", str(out_dir)]
+    out = subprocess.run(args, capture_output=True, text=True, timeout=600, env=_env(), cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and len(rec["step_ms_min_median_max"]) == 3 and rec["ms_per_step"] > 0
+    got = {f[:-len(".npy")]: np.load(out_dir / f) for f in os.listdir(out_dir)}
+    assert all(f.endswith(".npy") for f in os.listdir(out_dir))
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    # the same job in this process, through the host-memory entry point
+    import srrg2_slam_interfaces_amd as pkg
+    from srrg2_slam_interfaces_amd import _abi as abi
+    from srrg2_slam_interfaces_amd import synthetic as syn
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    probs = syn.batch_3d(K=8, n=8000, seed=4000, shared_fixed_group=1 << 30)
+    al = bench.make_aligner(lambda: pkg.MultiAligner(abi.SE3_QUAT_RIGHT, device=0), abi, 10)
+    al.set_fixed(0, probs[0]["fixed"], probs[0]["fixed_normals"])
+    res = al.compute_batch([p["moving"] for p in probs], [syn.identity(3)] * 8, [p["moving_normals"] for p in probs])
+    assert got["moving_in_fixed"].dtype == np.float32
+    assert got["moving_in_fixed"].tobytes() == np.ascontiguousarray(res.moving_in_fixed, np.float32).tobytes()
+    assert np.array_equal(got["status"], res.status.astype(np.float64)) and not got["status"].any()
+    assert np.array_equal(got["num_iterations"], res.num_iterations.astype(np.float64))
+    assert np.array_equal(got["num_inliers"], res.last["num_inliers"].astype(np.float64))
+    assert got["chi_inliers"].tobytes() == res.last["chi_inliers"].astype(np.float32).tobytes()
+    H = np.asarray(res.information, np.float32)
+    assert np.array_equal(got["information"], np.triu(H) + np.transpose(np.triu(H, 1), (0, 2, 1)))
