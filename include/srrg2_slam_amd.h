@@ -601,6 +601,46 @@ int srrg2_aligner_profile_get(srrg2_aligner_h h, double* step_kernel_ms, int64_t
 #define SRRG2_PATH_PRIORS_FUSED 32   /* prior slices linearised by the control wave                                        */
 int srrg2_aligner_last_compute_path(srrg2_aligner_h h, int32_t* flags_out);
 
+/* ---- binary descriptor database: the matching half of MultiLoopDetectorHBST_ -----------------------------------
+ * (S/registration/loop_detector/multi_loop_detector_hbst_impl.cpp:41-70 addPreviousQuery, :72-161
+ * computeCorrespondences, :163-197 _computeCorrespondencesFromMatches; PARAMs multi_loop_detector_hbst.h:45-74).
+ * The reference keeps srrg_hbst::BinaryTree256<uint64_t>; this database is that tree with a single leaf: the search is
+ * exhaustive and exact on the device ("Descriptor matching").
+ *  - a descriptor is 256 bits = SRRG2_DESCRIPTOR_BYTES bytes (the ORB/BRIEF row of the reference); the Hamming distance
+ *    does not depend on the bit order.
+ *  - valid: one byte per point, nonzero = POINT_STATUS::Valid (NULL = all valid).  Invalid points are not matchables
+ *    (:131-136) but keep their index: every index below is a POINT index of the caller's array, never compacted.
+ *  - add: only the valid descriptors enter; the map's database index is the number of maps before it (:57);
+ *    a map without valid descriptors is not added (*index_out = -1, :46-49).  The graph id -> index map is the caller's.
+ *  - match: a pair (valid query q, database descriptor j of map r) matches iff hamming(q, j) < max_distance (strict;
+ *    the float threshold against the integer distance).  Maps failing the age gate of :150-151 (unsigned indices:
+ *    a map passes iff (r < query_index and query_index - r > min_age) or r > query_index) are not searched; a map is a
+ *    candidate iff its number of matching pairs > min_matches (:152-154).  Per reference descriptor the query with the
+ *    smallest distance is kept, the smallest query index on a tie (:168-197) -> srrg2_correspondence{fixed_idx = query
+ *    point, moving_idx = reference point, response = distance}.  Candidates ascend in r, each one's correspondences in
+ *    moving_idx.  A query holds at most 2^23 points.
+ *  - getters (*n_inout: capacity on entry, number of entries on return; a NULL buffer queries the number):
+ *    get_candidates       reference index, pre-deduplication match count, offsets of each candidate's
+ *                         correspondences (corr_offsets has n + 1 entries)
+ *    get_correspondences  all candidates' correspondences, concatenated in candidate order
+ *    get_map_counts       the match count of EVERY map of the database, -1 for the maps the age gate skipped
+ *    last_match_ms        HIP-event time of the last match(): query upload + search + compaction, without the readback */
+#define SRRG2_DESCRIPTOR_BYTES 32
+typedef struct srrg2_descriptor_db* srrg2_descriptor_db_h;
+int srrg2_descriptor_db_create(int device, srrg2_descriptor_db_h* out);
+int srrg2_descriptor_db_destroy(srrg2_descriptor_db_h h);
+int srrg2_descriptor_db_add(srrg2_descriptor_db_h h, const uint8_t* descriptors, const uint8_t* valid, int n,
+                            int* index_out);
+int srrg2_descriptor_db_size(srrg2_descriptor_db_h h, int* maps, int64_t* descriptors);
+int srrg2_descriptor_db_match(srrg2_descriptor_db_h h, const uint8_t* descriptors, const uint8_t* valid, int n,
+                              int64_t query_index, float max_distance, uint32_t min_age, int64_t min_matches,
+                              int* K_out);
+int srrg2_descriptor_db_get_candidates(srrg2_descriptor_db_h h, int32_t* reference, int64_t* num_matches,
+                                       int64_t* corr_offsets, int* n_inout);
+int srrg2_descriptor_db_get_correspondences(srrg2_descriptor_db_h h, srrg2_correspondence* buf, int64_t* n_inout);
+int srrg2_descriptor_db_get_map_counts(srrg2_descriptor_db_h h, int64_t* counts, int* n_inout);
+int srrg2_descriptor_db_last_match_ms(srrg2_descriptor_db_h h, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

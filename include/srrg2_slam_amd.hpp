@@ -11,6 +11,7 @@
 //   AlignerSliceMotionModel         AlignerSliceMotionModel_               aligner_slice_motion_model.hpp:13-92
 //   AlignerSliceOdomPrior           AlignerSliceOdom{2,3}DPrior            aligner_slice_odometry_prior.{h,cpp}
 //   Scene / SceneClipperBall / MergerCorrespondenceHomo                    mapping/scene_clipper.h, merger_correspondence_homo.h
+//   DescriptorDatabase              srrg_hbst::BinaryTree256 in MultiLoopDetectorHBST_  multi_loop_detector_hbst_impl.cpp:41-197
 //   (loop-closure drivers and the pose graph: srrg2_slam_amd_loop_closure.hpp)
 #pragma once
 #include <array>
@@ -443,6 +444,76 @@ private:
   EstimateType _T = EstimateType::Identity();
   srrg2_merge_result _last{};
   Status _status = Error;
+};
+
+// ---- binary descriptor database: the matching half of MultiLoopDetectorHBST_ --------------------------------------
+// (S/registration/loop_detector/multi_loop_detector_hbst_impl.cpp:41-197; it stands where the reference keeps its
+// srrg_hbst::BinaryTree256<uint64_t>).  Exact, exhaustive matching on the device; semantics: srrg2_slam_amd.h.
+class DescriptorDatabase {
+public:
+  struct Candidate {
+    int32_t index;        // database index of the reference local map
+    int64_t num_matches;  // matching pairs before deduplication
+    CorrespondenceVector correspondences;  // fixed_idx = query point, moving_idx = reference point, response = distance
+  };
+  explicit DescriptorDatabase(int device = 0) { check(srrg2_descriptor_db_create(device, &_h)); }
+  ~DescriptorDatabase() { srrg2_descriptor_db_destroy(_h); }
+  DescriptorDatabase(const DescriptorDatabase&)            = delete;
+  DescriptorDatabase& operator=(const DescriptorDatabase&) = delete;
+  // n rows of SRRG2_DESCRIPTOR_BYTES bytes; valid: n bytes or nullptr.  Returns the database index, -1 if not added.
+  int add(const uint8_t* descriptors, const uint8_t* valid, int n) {
+    int index = -1;
+    check(srrg2_descriptor_db_add(_h, descriptors, valid, n, &index));
+    return index;
+  }
+  int size() const {
+    int maps = 0;
+    check(srrg2_descriptor_db_size(_h, &maps, nullptr));
+    return maps;
+  }
+  int64_t numDescriptors() const {
+    int64_t n = 0;
+    check(srrg2_descriptor_db_size(_h, nullptr, &n));
+    return n;
+  }
+  // computeCorrespondences (:117-161): the candidates ascending in database index
+  std::vector<Candidate> match(const uint8_t* descriptors, const uint8_t* valid, int n, int64_t query_index,
+                               float maximum_descriptor_distance = 25.0f, uint32_t minimum_age_difference = 0,
+                               int64_t min_matches = 0) {
+    int K = 0;
+    check(srrg2_descriptor_db_match(_h, descriptors, valid, n, query_index, maximum_descriptor_distance,
+                                    minimum_age_difference, min_matches, &K));
+    std::vector<int32_t> index(K);
+    std::vector<int64_t> count(K), offsets(K + 1);
+    check(srrg2_descriptor_db_get_candidates(_h, index.data(), count.data(), offsets.data(), &K));
+    int64_t total = offsets[K];
+    CorrespondenceVector all(total);
+    check(srrg2_descriptor_db_get_correspondences(_h, all.data(), &total));
+    std::vector<Candidate> out(K);
+    for (int k = 0; k < K; ++k) {
+      out[k].index       = index[k];
+      out[k].num_matches = count[k];
+      out[k].correspondences.assign(all.begin() + offsets[k], all.begin() + offsets[k + 1]);
+    }
+    return out;
+  }
+  // the pair count of every map in the last match(), -1 for maps the age gate skipped
+  std::vector<int64_t> mapCounts() const {
+    int n = 0;
+    check(srrg2_descriptor_db_get_map_counts(_h, nullptr, &n));
+    std::vector<int64_t> c(n);
+    check(srrg2_descriptor_db_get_map_counts(_h, c.data(), &n));
+    return c;
+  }
+  double lastMatchMs() const {
+    double ms = 0.0;
+    check(srrg2_descriptor_db_last_match_ms(_h, &ms));
+    return ms;
+  }
+  srrg2_descriptor_db_h handle() const { return _h; }
+
+private:
+  srrg2_descriptor_db_h _h = nullptr;
 };
 
 }  // namespace srrg2_slam_amd

@@ -26,3 +26,11 @@ def scene_binding(device=0):
 
     l = _capi.lib()
     return _Binding(l, "srrg2_scene_", l.srrg2_amd_last_error, device)
+
+
+def DescriptorDatabase(device=0):
+    """Device-resident database of 256-bit binary descriptors with exact matching (the matching half of the HBST loop
+    detector; raises if the library or a HIP device is missing)."""
+    from .descriptors import DescriptorDatabase as _DD
+
+    return _DD(device=device)

@@ -29,6 +29,19 @@ def lib():
         _LIB = C.CDLL(LIB_PATH)
         _LIB.srrg2_amd_last_error.restype = C.c_char_p
         _LIB.srrg2_aligner_profile_get.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]
+        # srrg2_descriptor_db_* (descriptors.DescriptorDatabase): float / int64 arguments need their types
+        u8p = C.POINTER(C.c_uint8)
+        _LIB.srrg2_descriptor_db_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        _LIB.srrg2_descriptor_db_destroy.argtypes = [C.c_void_p]
+        _LIB.srrg2_descriptor_db_add.argtypes = [C.c_void_p, u8p, u8p, C.c_int, C.POINTER(C.c_int)]
+        _LIB.srrg2_descriptor_db_size.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+        _LIB.srrg2_descriptor_db_match.argtypes = [C.c_void_p, u8p, u8p, C.c_int, C.c_int64, C.c_float, C.c_uint32,
+                                                   C.c_int64, C.POINTER(C.c_int)]
+        _LIB.srrg2_descriptor_db_get_candidates.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                                            C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+        _LIB.srrg2_descriptor_db_get_correspondences.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        _LIB.srrg2_descriptor_db_get_map_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+        _LIB.srrg2_descriptor_db_last_match_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     return _LIB
 
 

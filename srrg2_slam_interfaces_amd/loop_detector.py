@@ -241,23 +241,121 @@ class MultiRelocalizer:
 
 
 class MultiLoopDetectorHBST:
-    """The alignment half of MultiLoopDetectorHBST_ (S/registration/loop_detector/multi_loop_detector_hbst_impl.cpp):
-    ``_computeAlignments`` (:257-377) -- per reference local map with enough descriptor matches, a one-variable
-    Gauss-Newton solve with the matches kept locked, starting from the identity -- and the accept gates and closure
-    record of ``_addLoopClosure`` (:379-447).  Here all candidates go through ONE compute_batch_correspondences().
-    The descriptor tree that produces the matches (srrg_hbst) is out of scope: matches are an input.
-    PARAMs: loop_detector.h (relocalize_min_inliers / max_chi_inliers / min_inliers_ratio)."""
+    """MultiLoopDetectorHBST_ (S/registration/loop_detector/multi_loop_detector_hbst_impl.cpp).
+
+    The matching half -- ``addPreviousQuery`` (:41-70) and ``computeCorrespondences`` (:72-197) -- runs on a
+    ``descriptors.DescriptorDatabase``: exact, exhaustive matching of 256-bit descriptors on the GPU.  It is the HBST of
+    the reference with a single leaf: ``maximum_leaf_size``, ``maximum_partitioning`` and ``maximum_depth`` are accepted
+    under their reference names and have no effect, and descriptor merging (``maximum_distance_for_merge``, compiled out
+    of the reference by default: ``#ifdef SRRG_MERGE_DESCRIPTORS``, :96-98) is unsupported.  Because a tree search is
+    approximate and this one is not, the closures found can be a SUPERSET of what the reference's tree finds.
+
+    The alignment half -- ``_computeAlignments`` (:257-377): per reference local map with enough descriptor matches, a
+    one-variable Gauss-Newton solve with the matches kept locked, starting from the identity -- and the accept gates and
+    closure record of ``_addLoopClosure`` (:379-447) run all candidates through ONE compute_batch_correspondences().
+    ``compute()`` is the two in a row (:12-39); ``compute_alignments`` also takes matches from elsewhere.
+    PARAMs: loop_detector.h (relocalize_min_inliers / max_chi_inliers / min_inliers_ratio),
+    multi_loop_detector_hbst.h:45-74 (the descriptor ones).  The database is created on ``device`` at the first
+    compute_correspondences() unless one is given."""
 
     def __init__(self, relocalize_aligner, relocalize_min_inliers=500, relocalize_max_chi_inliers=0.005,
-                 relocalize_min_inliers_ratio=0.7):
+                 relocalize_min_inliers_ratio=0.7, maximum_descriptor_distance=25.0, maximum_leaf_size=100,
+                 maximum_partitioning=0.1, maximum_depth=16, maximum_distance_for_merge=0.0,
+                 minimum_age_difference_to_candidates=0, database=None, device=0):
         if relocalize_aligner is None:
             raise RuntimeError("MultiLoopDetectorHBST::computeAlignments|ERROR: aligner not set")  # :264-268
+        if maximum_distance_for_merge != 0:
+            raise NotImplementedError("MultiLoopDetectorHBST: maximum_distance_for_merge != 0 is unsupported "
+                                      "(descriptor merging is not implemented)")
+        from .descriptors import check_match_args
+
+        check_match_args(maximum_descriptor_distance, minimum_age_difference_to_candidates, 0)
         self.relocalize_aligner = relocalize_aligner
         self.relocalize_min_inliers = relocalize_min_inliers
         self.relocalize_max_chi_inliers = relocalize_max_chi_inliers
         self.relocalize_min_inliers_ratio = relocalize_min_inliers_ratio
+        self.maximum_descriptor_distance = maximum_descriptor_distance
+        self.maximum_leaf_size = maximum_leaf_size  # (no effect: one leaf)
+        self.maximum_partitioning = maximum_partitioning  # (no effect)
+        self.maximum_depth = maximum_depth  # (no effect)
+        self.maximum_distance_for_merge = maximum_distance_for_merge
+        self.minimum_age_difference_to_candidates = minimum_age_difference_to_candidates
+        self.database = database
+        self.device = device
         self.detected_closures = []
         self.drops = []
+        self._graph_id_to_database_index = {}
+        self._local_maps_in_database = []  # per database index: (graph id, points, normals)
+        self._query = None  # the last query local map: (graph id, descriptors, valid, points, normals)
+        self._indices = []
+        self._correspondences_per_reference = {}
+        self.last_match = None
+
+    def indices(self):
+        """database indices of the candidates of the last compute_correspondences(), ascending"""
+        return list(self._indices)
+
+    def correspondences(self, index):
+        """the correspondences (fixed_idx = query point, moving_idx = reference point, response = distance) of candidate
+        ``index`` (a database index)"""
+        return self._correspondences_per_reference[index]
+
+    def graph_id(self, index):
+        return self._local_maps_in_database[index][0]
+
+    def compute_correspondences(self, graph_id, descriptors, valid=None, points=None, normals=None):
+        """computeCorrespondences (:72-161) for the query local map ``graph_id``; points / normals are kept for a later
+        add_previous_query() (the reference map's cloud of future alignments).  Returns indices()."""
+        from .descriptors import as_descriptors, as_valid
+
+        d = as_descriptors(descriptors)
+        v = as_valid(valid, len(d))
+        self._indices, self._correspondences_per_reference, self.last_match = [], {}, None
+        if len(d) == 0:  # :86-91 (an empty query is not added either)
+            self._query = None
+            return self.indices()
+        self._query = (graph_id, d, v, points, normals)
+        if self.database is None:
+            from .descriptors import DescriptorDatabase
+
+            self.database = DescriptorDatabase(device=self.device)
+        # the query index: the database size for a new local map, its own index for a registered one (:117-128)
+        query_index = self._graph_id_to_database_index.get(graph_id, len(self._local_maps_in_database))
+        res = self.database.match(d, v, query_index, self.maximum_descriptor_distance,
+                                  self.minimum_age_difference_to_candidates, self.relocalize_min_inliers)
+        self.last_match = res
+        self._indices = [int(r) for r in res.indices]
+        self._correspondences_per_reference = {int(r): c for r, c in zip(res.indices, res.correspondences)}
+        return self.indices()
+
+    def add_previous_query(self):
+        """addPreviousQuery (:41-70): the last query local map enters the database unless it is registered already or
+        has no valid descriptor."""
+        if self._query is None:
+            return -1
+        graph_id, d, v, points, normals = self._query
+        if graph_id in self._graph_id_to_database_index:
+            return -1
+        index = self.database.add(d, v)
+        if index < 0:
+            return -1
+        assert index == len(self._local_maps_in_database)
+        self._graph_id_to_database_index[graph_id] = index
+        self._local_maps_in_database.append((graph_id, points, normals))
+        self._query = None
+        return index
+
+    def compute(self, graph_id, points, normals, descriptors, valid=None, pose_in_query=None):
+        """compute() (:12-39): computeCorrespondences, then the alignments of the candidates.  The fixed cloud is the
+        query local map's points, the moving cloud the reference map's (:333-334); a closure's target is the reference
+        map's graph id."""
+        self.compute_correspondences(graph_id, descriptors, valid, points, normals)
+        candidates = []
+        for r in self._indices:
+            gid, ref_points, ref_normals = self._local_maps_in_database[r]
+            candidates.append({"reference": gid, "moving": ref_points, "moving_normals": ref_normals,
+                               "correspondences": self._correspondences_per_reference[r]})
+        return self.compute_alignments(graph_id, points, normals, candidates, pose_in_query)
 
     def compute_alignments(self, query_id, fixed, fixed_normals, candidates, pose_in_query=None):
         """candidates: list of dicts {reference, moving, moving_normals or None, correspondences (fixed_idx = query
