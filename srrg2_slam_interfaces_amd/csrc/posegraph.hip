@@ -270,6 +270,7 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_vertices(int V, const uint8_t
 #define MG_FUSE_BLOCKS 1200   // ... and at most this many off-diagonal blocks
 #define MG_DOWN2_THREADS 256
 #define MG_FUSE_LAST_NODES 16  // coarsest levels of at most this many nodes are solved inside the last down launch (k_mg_down2_coarsest)
+constexpr int MG_LIST_LANE_PRODUCTS = 4;  // products per lane the set-up's list kernels aim at (k_mg_hp_list / k_mg_galerkin_list)
 
 struct MgLevel {  // device view of one level (level 0 = the pose graph without its Fixed variables' couplings)
   int n, ne, nc, nce, np, nq;
@@ -315,15 +316,7 @@ struct MgLevel {  // device view of one level (level 0 = the pose graph without 
   // H(y) * Ps[x] with y = -1: the row's diagonal block, else the incidence code (edge << 1) | side; coarse edge k of the Galerkin
   // product is the sum over gp_list[gp_start[k] ..) of Ps[x]^T * Q[y]; qdiag[e] = the entry of Q in the row and column of entry e
   // of Ps (the coarse diagonal blocks).  They are the sorted candidate lists of the pattern build with their origins as payload:
-  // k_mg_hp / k_mg_galerkin found every product by a binary search per (entry, incidence), five in six of them in vain.
-  // Column-ordered float32 copies of Ps and Q (round 6): block m of Psfc / Qfc is the block of entry pcsc2[m].x / qcsc2[m].x, so a
-  // column is ONE contiguous run -- the restriction (level 0) and the down phases read their columns as a stream instead of 144-byte
-  // blocks scattered over the row-ordered arrays (55.7 MB per restriction for 29 MB of blocks); pcsc_pos / qcsc_pos = where an entry's
-  // block goes (the inverse of the column lists).
-  float* Psfc;
-  float* Qfc;
-  const int* pcsc_pos;
-  const int* qcsc_pos;
+  // round 5's set-up kernels found every product by a binary search per (entry, incidence), five in six of them in vain.
   const int* qp_start;
   const int2* qp_list;
   const int* gp_start;
@@ -360,7 +353,6 @@ __device__ __forceinline__ MgLevel mg_level(const MgLevel* __restrict__ levels, 
   L.qcsc_start = mg_glob(L.qcsc_start); L.qcsc_ent = mg_glob(L.qcsc_ent); L.pcsc2 = mg_glob(L.pcsc2); L.qcsc2 = mg_glob(L.qcsc2);
   L.qp_start = mg_glob(L.qp_start); L.qp_list = mg_glob(L.qp_list); L.gp_start = mg_glob(L.gp_start); L.gp_list = mg_glob(L.gp_list);
   L.qdiag = mg_glob(L.qdiag);
-  L.Psfc = mg_glob(L.Psfc); L.Qfc = mg_glob(L.Qfc); L.pcsc_pos = mg_glob(L.pcsc_pos); L.qcsc_pos = mg_glob(L.qcsc_pos);
   L.x = mg_glob(L.x); L.r = mg_glob(L.r); L.res = mg_glob(L.res);
   return L;
 }
@@ -628,7 +620,7 @@ __device__ __forceinline__ void mg_down2_column(const MgLevel& L, int I, int tid
   for (int a = 0; a < D; ++a) s[a] = 0.0;
   for (int m = L.pcsc_start[I] + tid; m < L.pcsc_start[I + 1]; m += nth) {
     const int2 er = L.pcsc2[m];
-    mg_block_tmulsub<D>(L.Psfc ? L.Psfc + (size_t) m * D * D : L.Psf + (size_t) er.x * D * D, L.r + (size_t) er.y * D, 1.0, s);
+    mg_block_tmulsub<D>(L.Psf + (size_t) er.x * D * D, L.r + (size_t) er.y * D, 1.0, s);
   }
   const int qe = L.qcsc_start[I + 1];
   for (int m0 = L.qcsc_start[I] + tid; m0 < qe; m0 += 2 * nth) {
@@ -638,9 +630,8 @@ __device__ __forceinline__ void mg_down2_column(const MgLevel& L, int I, int tid
     double t[D];
 #pragma unroll
     for (int a = 0; a < D; ++a) t[a] = 0.0;
-    mg_block_tmulsub<D>(L.Qfc ? L.Qfc + (size_t) m0 * D * D : L.Qf + (size_t) e0.x * D * D, L.x + (size_t) e0.y * D, -1.0, s);
-    mg_block_tmulsub<D>(L.Qfc ? L.Qfc + (size_t) (two ? m0 + nth : m0) * D * D : L.Qf + (size_t) e1.x * D * D, L.x + (size_t) e1.y * D,
-                        two ? -1.0 : 0.0, t);
+    mg_block_tmulsub<D>(L.Qf + (size_t) e0.x * D * D, L.x + (size_t) e0.y * D, -1.0, s);
+    mg_block_tmulsub<D>(L.Qf + (size_t) e1.x * D * D, L.x + (size_t) e1.y * D, two ? -1.0 : 0.0, t);
 #pragma unroll
     for (int a = 0; a < D; ++a) s[a] = s[a] + t[a];
   }
@@ -934,13 +925,11 @@ __global__ __launch_bounds__(PG_THREADS) void k_mg_bottom_dense(MgPair LV, const
 }
 
 // x += Ps x_coarse with the coarse correction taken from the coarse level's `res` (a two-phase level below a six-phase one)
-// (xc_in_x: the coarse level ran its six phases -- its result is in its x)
 template <int D>
-__global__ __launch_bounds__(PG_THREADS) void k_mg_prolong_res(MgPair LV, int xc_in_x,
-                                                               const PgScalars* __restrict__ sc) {
+__global__ __launch_bounds__(PG_THREADS) void k_mg_prolong_res(MgPair LV, const PgScalars* __restrict__ sc) {
   if (sc->done || sc->bad) return;
   const MgLevel L = LV.L;
-  mg_prolong<D>(L, xc_in_x ? LV.C.x : LV.C.res, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+  mg_prolong<D>(L, LV.C.res, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 // levels lf .. nl-1 (small) + the coarsest level nl in ONE workgroup: down, coarsest solve, up
@@ -1119,96 +1108,15 @@ __global__ __launch_bounds__(PG_THREADS) void k_mg_psmooth(MgPair LV, double ome
   // are then the Galerkin products of exactly the interpolation the cycle uses, and the products fetch 144 instead of 288 bytes of it;
   // 16-byte stores: 36 scalar ones took this kernel from 132 to 223 us on level 0)
   if (L.Psf) {
-    const size_t ec = L.Psfc ? (size_t) L.pcsc_pos[e] : 0;  // (and the column-ordered copy)
     if constexpr (D == 6) {
       float4* of = reinterpret_cast<float4*>(L.Psf + (size_t) e * D * D);
-      float4* oc = reinterpret_cast<float4*>(L.Psfc + ec * D * D);
 #pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        const float4 v = make_float4((float) o[4 * k], (float) o[4 * k + 1], (float) o[4 * k + 2], (float) o[4 * k + 3]);
-        of[k] = v;
-        if (L.Psfc) oc[k] = v;
-      }
+      for (int k = 0; k < 9; ++k) of[k] = make_float4((float) o[4 * k], (float) o[4 * k + 1], (float) o[4 * k + 2], (float) o[4 * k + 3]);
     } else {
 #pragma unroll
-      for (int k = 0; k < D * D; ++k) {
-        L.Psf[(size_t) e * D * D + k]  = (float) o[k];
-        if (L.Psfc) L.Psfc[ec * D * D + k] = (float) o[k];
-      }
+      for (int k = 0; k < D * D; ++k) L.Psf[(size_t) e * D * D + k] = (float) o[k];
     }
   }
-}
-
-// Q = H Ps.  One thread per (entry of Q, part): the look-ups of Ps[j, B] over the incidences j of row i are the
-// expensive part (a binary search each), so a thread does them once for the whole D x D block; `row_parts` adjacent
-// lanes share the incidences and add their blocks with the fixed butterfly.
-template <int D>
-__global__ __launch_bounds__(PG_THREADS) void k_mg_hp(MgPair LV) {
-  const MgLevel L = LV.L;
-  const int parts = L.row_parts;
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= L.nq * parts) return;  // (whole groups: the bound is a multiple of `parts`)
-  const int part = t & (parts - 1), q = t / parts;
-  const int i = L.qrow_of[q], Bc = L.qcol[q];
-  double w[D * D];
-#pragma unroll
-  for (int k = 0; k < D * D; ++k) w[k] = 0.0;
-  if (part == 0) {
-    const int e = mg_find(L.pcol, L.prow_start[i], L.prow_start[i + 1], Bc);
-    if (e >= 0) mg_block_mac<D, false>(w, L.Hd + (size_t) i * D * D, L.Ps + (size_t) e * D * D);
-  }
-  for (int k = L.inc_start[i] + part; k < L.inc_start[i + 1]; k += parts) {
-    const int2 adj = L.inc_adj[k];
-    const int e    = mg_find(L.pcol, L.prow_start[adj.x], L.prow_start[adj.x + 1], Bc);
-    if (e < 0) continue;
-    const double* Pe = L.Ps + (size_t) e * D * D;
-    const double* B  = L.Ho + (size_t) (adj.y >> 1) * D * D;
-    if (adj.y & 1)
-      mg_block_mac<D, true>(w, B, Pe);
-    else
-      mg_block_mac<D, false>(w, B, Pe);
-  }
-  mg_group_sum<D * D>(w, parts);
-  if (part != 0) return;
-  double* out = L.Q + (size_t) q * D * D;
-#pragma unroll
-  for (int k = 0; k < D * D; ++k) out[k] = w[k];
-}
-
-// Galerkin product, second half: Hc[A, B] = sum_i Ps[i, A]^T Q[i, B] over the rows of column A; the diagonal blocks
-// and the blocks of the coarse edges (A < B).  One thread per (coarse block, part); fixed lists, fixed order: deterministic.
-template <int D>
-__global__ __launch_bounds__(PG_THREADS) void k_mg_galerkin(MgPair LV) {
-  const MgLevel L = LV.L;
-  const MgLevel C = LV.C;
-  const int parts = L.col_parts;
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (L.nc + L.nce) * parts) return;
-  const int part = t & (parts - 1), blk = t / parts;
-  int A, B;
-  double* out;
-  if (blk < L.nc) {
-    A = B = blk;
-    out = C.Hd + (size_t) blk * D * D;
-  } else {
-    const int2 ab = C.eij[blk - L.nc];
-    A = ab.x;
-    B = ab.y;
-    out = C.Ho + (size_t) (blk - L.nc) * D * D;
-  }
-  double acc[D * D];
-#pragma unroll
-  for (int k = 0; k < D * D; ++k) acc[k] = 0.0;
-  for (int m = L.pcsc_start[A] + part; m < L.pcsc_start[A + 1]; m += parts) {
-    const int e = L.pcsc_ent[m], i = L.prow_of[e];
-    const int q = mg_find(L.qcol, L.qrow_start[i], L.qrow_start[i + 1], B);
-    if (q < 0) continue;
-    mg_block_mac<D, true>(acc, L.Ps + (size_t) e * D * D, L.Q + (size_t) q * D * D);
-  }
-  mg_group_sum<D * D>(acc, parts);
-  if (part != 0) return;
-#pragma unroll
-  for (int k = 0; k < D * D; ++k) out[k] = acc[k];
 }
 
 // Q = H Ps and the Galerkin product over the product lists (MgLevel::qp_list / gp_list): `parts` adjacent lanes share an
@@ -1322,38 +1230,25 @@ __global__ __launch_bounds__(PG_THREADS) void k_mg_to_float(MgPair LV, int with_
     }
     if (k < no) L.Hof[k] = (float) L.Ho[k];
   }
-  // (Psf / Psfc: written by k_mg_psmooth; Qf / Qfc: k_mg_q_to_float below)
+  // (Psf: written by k_mg_psmooth; Qf: k_mg_q_to_float below)
   (void) with_p;
   (void) with_q;
 }
-// the float32 copies of Q = H Ps of a two-phase level: row-ordered (the up phase) and column-ordered (the down phase); one entry per thread
+// the float32 copy of Q = H Ps of a two-phase level (the down and the up phase read it); one entry per thread
 template <int D>
 __global__ __launch_bounds__(PG_THREADS) void k_mg_q_to_float(MgPair LV) {
   const MgLevel L = LV.L;
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= L.nq) return;
   const double* src = L.Q + (size_t) q * D * D;
-  const size_t qc   = L.Qfc ? (size_t) L.qcsc_pos[q] : 0;
   if constexpr (D == 6) {
     float4* of = reinterpret_cast<float4*>(L.Qf + (size_t) q * D * D);
-    float4* oc = reinterpret_cast<float4*>(L.Qfc + qc * D * D);
 #pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const float4 v = make_float4((float) src[4 * k], (float) src[4 * k + 1], (float) src[4 * k + 2], (float) src[4 * k + 3]);
-      of[k] = v;
-      if (L.Qfc) oc[k] = v;
-    }
+    for (int k = 0; k < 9; ++k) of[k] = make_float4((float) src[4 * k], (float) src[4 * k + 1], (float) src[4 * k + 2], (float) src[4 * k + 3]);
   } else {
 #pragma unroll
-    for (int k = 0; k < D * D; ++k) {
-      L.Qf[(size_t) q * D * D + k] = (float) src[k];
-      if (L.Qfc) L.Qfc[qc * D * D + k] = (float) src[k];
-    }
+    for (int k = 0; k < D * D; ++k) L.Qf[(size_t) q * D * D + k] = (float) src[k];
   }
-}
-__global__ __launch_bounds__(PG_THREADS) void k_st_invert(int m, const int* __restrict__ ent, int* __restrict__ pos) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < m) pos[ent[t]] = t;
 }
 
 // dense inverse of the coarsest operator: assemble, Cholesky in place, then one thread per column solves for the inverse
@@ -1685,7 +1580,7 @@ __global__ void k_pg_tail_up(int ntail, int V0, const int* __restrict__ parent, 
 // smoothing step x1 = omega Dinv r (now in the kernel that produces r), level 1's (in level 0's restriction), the cycle's last
 // update x += omega Dinv res (in the r.z kernel), and the convergence test (block 0 of the cycle's first residual pass: the sum
 // of update_xr's partials is complete behind the kernel boundary).  14 launches; same operations on the same operands in the same
-// order per entry, so the same numbers as the unfused sequence (SRRG2_AMD_PG_FUSED_CG=0 keeps that one).
+// order per entry, so the same numbers as the unfused sequence (which the six-phase cycle still runs).
 template <int D>
 __global__ __launch_bounds__(PG_THREADS) void k_pg_update_xr_smooth(int n, int nblocks, const double* __restrict__ p,
                                                                     const double* __restrict__ Ap, double* __restrict__ x,
@@ -1766,9 +1661,8 @@ __global__ __launch_bounds__(PG_THREADS) void k_mg_restrict_smooth(MgPair LV, in
       double u[D];
 #pragma unroll
       for (int a = 0; a < D; ++a) u[a] = 0.0;
-      mg_block_tmulsub<D>(L.Psfc ? L.Psfc + (size_t) m0 * D * D : L.Psf + (size_t) e0.x * D * D, L.res + (size_t) e0.y * D, 1.0, s);
-      mg_block_tmulsub<D>(L.Psfc ? L.Psfc + (size_t) (two ? m0 + NL : m0) * D * D : L.Psf + (size_t) e1.x * D * D, L.res + (size_t) e1.y * D,
-                          two ? 1.0 : 0.0, u);
+      mg_block_tmulsub<D>(L.Psf + (size_t) e0.x * D * D, L.res + (size_t) e0.y * D, 1.0, s);
+      mg_block_tmulsub<D>(L.Psf + (size_t) e1.x * D * D, L.res + (size_t) e1.y * D, two ? 1.0 : 0.0, u);
 #pragma unroll
       for (int a = 0; a < D; ++a) s[a] = s[a] + u[a];
     }
@@ -1846,14 +1740,11 @@ struct MgLevelBufs {
   DevBuf<int> qcsc_start, qcsc_ent;
   DevBuf<int2> pcsc2, qcsc2;
   DevBuf<double> Hd, Ho, Ps, Q, Dinv, x, r, res;
-  DevBuf<float> Psfc, Qfc;                      // column-ordered copies (MgLevel::Psfc)
-  DevBuf<int> pcsc_pos, qcsc_pos;
   DevBuf<unsigned long long> qp_list, gp_list;  // (int2 {x, y} = the low and the high word)
   DevBuf<int> qp_start, gp_start, qdiag;
   long long nqp = 0, ngp = 0;                   // products of Q = H Ps / of the coarse edges
   void release() {
     qp_list.release(); gp_list.release(); qp_start.release(); gp_start.release(); qdiag.release();
-    Psfc.release(); Qfc.release(); pcsc_pos.release(); qcsc_pos.release();
     eij.release(); inc_start.release(); inc_adj.release(); agg.release(); rep0.release(); prow_start.release();
     pcol.release(); prow_of.release(); pcsc_start.release(); pcsc_ent.release(); qrow_start.release(); qcol.release();
     qrow_of.release(); Hd.release(); Ho.release(); P.release(); Ps.release(); Q.release(); Dinv.release(); x.release();
@@ -1895,16 +1786,6 @@ struct srrg2_posegraph_s {
     bool debug = false;         // SRRG2_AMD_PG_DEBUG
     bool keep_structure = true; // the hierarchy's structure survives a set() with the same topology
     bool device_structure = true;  // SRRG2_AMD_PG_DEVICE_STRUCTURE: the sparsity patterns of a level are built on the device
-    bool product_lists = true;     // SRRG2_AMD_PG_PRODUCT_LISTS: the set-up products over the lists the pattern build leaves (round 6; 0: the searching kernels)
-    int list_lane_products = 4;    // SRRG2_AMD_PG_LIST_LANES: products per lane the list kernels aim at
-    bool column_copies = false;    // SRRG2_AMD_PG_COLUMN_COPIES (experiment, off): column-ordered float32 copies of Ps and Q for the down phases --
-                                   // k_mg_down2 20.0 -> 17.4 / 10.7 -> 9.9 us, the restriction unchanged, the solve 85.3-87.5 -> 90.0 ms: the second
-                                   // copy of Ps is 29 MB more per cycle and two more arrays to write per set-up (profiles/r9/r9s_*)
-    bool setup_f32_ps = true;      // SRRG2_AMD_PG_SETUP_F32_PS: the set-up products read the float32 copy of the interpolation (round 6)
-    bool l1_six = false;           // SRRG2_AMD_PG_L1_SIX (experiment): level 1 on six phases through H instead of two through Q
-    bool tree_positions = true;    // SRRG2_AMD_PG_TREE_POSITIONS: the matching's geometry from a spanning tree of the measurements (round 6)
-    bool fused_bottom = true;      // SRRG2_AMD_PG_FUSED_BOTTOM: the bottom of the cycle as one dense operator (k_mg_bottom_dense, round 6)
-    bool fused_cg = true;          // SRRG2_AMD_PG_FUSED_CG: 14 launches per CG iteration instead of 18 (round 6; an A/B switch: same numbers)
   } sw;
   // scratch of the device-side pattern build (pg_device_patterns)
   DevBuf<unsigned long long> st_keys_a, st_keys_b;
@@ -2493,7 +2374,6 @@ int build_hierarchy(srrg2_posegraph_s* g) {
   // positions from a BREADTH-FIRST spanning tree of the measurements, rooted at the Fixed variables -- every pose is its tree
   // parent's composed with the factor's Z, a path of ~100 factors instead of up to 50 000, so neighbours agree to centimetres
   // whatever the initial guess is; it depends on the topology and the measurements only, like the structure it is used for.
-  // (sw.tree_positions = false / SRRG2_AMD_PG_TREE_POSITIONS=0: the current poses, as before)
   auto position = [&](int v, float* out) {
     const float* X = poses.data() + (size_t) v * T;
     if (D == 6) { out[0] = X[3]; out[1] = X[7]; out[2] = X[11]; } else { out[0] = X[2]; out[1] = X[5]; out[2] = 0.f; }
@@ -2517,7 +2397,7 @@ int build_hierarchy(srrg2_posegraph_s* g) {
   if ((rc = upload(g->act_edge, act))) return rc;
   g->coarsest_dense = 1;
   const auto t_tree = std::chrono::steady_clock::now();
-  if (g->sw.tree_positions && E > 0) {
+  if (E > 0) {
     const std::vector<float>& hZ = g->h_Z;  // (the measurements' host mirror: set() / add_factor keep it)
     // adjacency of the free variables over level 0's edges (eij / act, above); the factors that touch a Fixed variable seed the tree
     const int ne0 = (int) (eij.size() / 2);
@@ -2960,13 +2840,8 @@ int build_hierarchy(srrg2_posegraph_s* g) {
       L->prow_parts = parts;
     }
     if ((rc = L->Ps.reserve((size_t) std::max(np, 1) * D * D)) || (rc = L->Q.reserve((size_t) std::max(nq, 1) * D * D)) ||
-        (rc = L->Psf.reserve((size_t) std::max(np, 1) * D * D)) || (rc = L->Qf.reserve((size_t) std::max(nq, 1) * D * D)) ||
-        (rc = L->Psfc.reserve((size_t) std::max(np, 1) * D * D)) || (rc = L->Qfc.reserve((size_t) std::max(nq, 1) * D * D)) ||
-        (rc = L->pcsc_pos.reserve((size_t) std::max(np, 1))) || (rc = L->qcsc_pos.reserve((size_t) std::max(nq, 1))))
+        (rc = L->Psf.reserve((size_t) std::max(np, 1) * D * D)) || (rc = L->Qf.reserve((size_t) std::max(nq, 1) * D * D)))
       return rc;
-    // (where an entry's block goes in the column-ordered copies: the inverse of the column lists, which are on the device either way)
-    if (np > 0) hipLaunchKernelGGL(k_st_invert, st_grid((size_t) np), dim3(PG_THREADS), 0, g->stream, np, L->pcsc_ent.p, L->pcsc_pos.p);
-    if (nq > 0) hipLaunchKernelGGL(k_st_invert, st_grid((size_t) nq), dim3(PG_THREADS), 0, g->stream, nq, L->qcsc_ent.p, L->qcsc_pos.p);
     ms_up += ms_since(t_up);
     // next level
     n = nc;
@@ -3002,9 +2877,6 @@ int build_hierarchy(srrg2_posegraph_s* g) {
     v.Hdf = L->Hdf.p; v.Hof = L->Hof.p; v.Dinvf = L->Dinvf.p;
     v.Psf = l + 1 < nl ? L->Psf.p : nullptr; v.Qf = l + 1 < nl ? L->Qf.p : nullptr;
     v.qcsc_start = L->qcsc_start.p; v.qcsc_ent = L->qcsc_ent.p; v.pcsc2 = L->pcsc2.p; v.qcsc2 = L->qcsc2.p;
-    v.Psfc = (l + 1 < nl && g->sw.column_copies) ? L->Psfc.p : nullptr;
-    v.Qfc  = (l + 1 < nl && g->sw.column_copies) ? L->Qfc.p : nullptr;
-    v.pcsc_pos = L->pcsc_pos.p; v.qcsc_pos = L->qcsc_pos.p;
     v.qp_start = L->qp_start.p; v.qp_list = reinterpret_cast<const int2*>(L->qp_list.p); v.gp_start = L->gp_start.p;
     v.gp_list = reinterpret_cast<const int2*>(L->gp_list.p); v.qdiag = L->qdiag.p;
     v.Hd = L->Hd.p; v.Ho = L->Ho.p; v.P = L->P.p; v.Ps = L->Ps.p; v.Q = L->Q.p; v.Dinv = L->Dinv.p; v.x = L->x.p;
@@ -3106,13 +2978,10 @@ int pg_solve_t(srrg2_posegraph_s* g, const srrg2_posegraph_params* p, srrg2_pose
     int p2 = down ? Lb->col_parts : std::max(Lb->row_parts, Lb->prow_parts);
     return std::min(std::max(p2, 1), 8);
   };
-  // (fused CG steps, k_pg_update_xr_smooth ...: `head` = level 0's x1 is already there, `check` = the first residual pass carries the
-  // convergence test, `tail` = the caller's k_pg_update_dot applies the last update; sw.fused_cg)
-  const bool fused_cg = g->sw.fused_cg && two_phase;
-  const double tol_d  = (double) p->pcg_tolerance;
+  const double tol_d = (double) p->pcg_tolerance;
   // the bottom of the cycle as one dense operator (k_bd_*, k_mg_bottom_dense): the conditions of k_mg_down2_coarsest and a level small
   // enough for an N x N matrix
-  const bool dense_bottom = g->sw.fused_bottom && two_phase && g->coarsest_dense && lf == nl && lf >= 2 && g->levels[(size_t) nl]->n <= MG_FUSE_LAST_NODES &&
+  const bool dense_bottom = two_phase && g->coarsest_dense && lf == nl && lf >= 2 && g->levels[(size_t) nl]->n <= MG_FUSE_LAST_NODES &&
                             g->levels[(size_t) nl]->n == g->levels[(size_t) nl - 1]->nc && g->levels[(size_t) nl - 1]->n * D <= 1024;
   if (dense_bottom) {
     const size_t Nb = (size_t) g->levels[(size_t) nl - 1]->n * D, Mb = (size_t) g->levels[(size_t) nl]->n * D;
@@ -3120,27 +2989,19 @@ int pg_solve_t(srrg2_posegraph_s* g, const srrg2_posegraph_params* p, srrg2_pose
         (rc = g->bottom_W.reserve(Nb * Mb)))
       return rc;
   }
-  // level 1 on its six phases (through H: C5 18 MB per residual pass) instead of the two phases through Q (31 MB each way), with the
-  // fused restriction: five launches for two, fewer bytes (experiment switch SRRG2_AMD_PG_L1_SIX; needs a two-phase level 2 below)
-  const bool l1_six = g->sw.l1_six && fused_cg && lf >= 3;
-  auto vcycle2 = [&](bool head, bool check, bool tail) {
+  // The two-phase cycle with the fused CG steps around it (k_pg_update_xr_smooth ... k_pg_update_dot): `head` = level 0's x1 is
+  // already there, `check` = the first residual pass carries the convergence test; the caller's k_pg_update_dot applies the last
+  // update.  14 launches per CG iteration instead of 18 with the CG steps launched on their own (round 6, the same numbers).
+  auto vcycle2 = [&](bool head, bool check) {
     const MgLevelBufs* L0b = g->levels[0];
-    const int bl0 = blocks_for(L0b->n * D), bc0 = blocks_for(L0b->nc * D * L0b->col_parts), br0 = blocks_for(L0b->n * D * L0b->row_parts);
+    const int bl0 = blocks_for(L0b->n * D), br0 = blocks_for(L0b->n * D * L0b->row_parts);
     if (!head) hipLaunchKernelGGL(k_mg_op<D>, dim3(bl0), dim3(PG_THREADS), 0, g->stream, (int) MG_OP_SMOOTH0, pair(0), g->sc.p);
-    if (fused_cg)
-      hipLaunchKernelGGL(k_mg_residual0<D>, dim3(br0), dim3(PG_THREADS), 0, g->stream, pair(0), check ? 1 : 0, nb, tol_d, g->part_rr.p,
-                         g->part_bb.p, g->sc.p);
-    else
-      hipLaunchKernelGGL(k_mg_op<D>, dim3(br0), dim3(PG_THREADS), 0, g->stream, (int) MG_OP_RESIDUAL, pair(0), g->sc.p);
-    if (fused_cg && L0b->nc > 0) {  // restriction + x1 of level 1 in one launch
+    hipLaunchKernelGGL(k_mg_residual0<D>, dim3(br0), dim3(PG_THREADS), 0, g->stream, pair(0), check ? 1 : 0, nb, tol_d, g->part_rr.p,
+                       g->part_bb.p, g->sc.p);
+    if (L0b->nc > 0) {  // restriction + x1 of level 1 in one launch
       const int pp = std::min(std::max(L0b->col_parts / 2, 1), 8);
       hipLaunchKernelGGL(k_mg_restrict_smooth<D>, dim3((unsigned) (((size_t) L0b->nc * 8 * pp + PG_THREADS - 1) / PG_THREADS)), dim3(PG_THREADS),
                          0, g->stream, pair(0), pp, g->sc.p);
-    } else {
-      hipLaunchKernelGGL(k_mg_op<D>, dim3(bc0), dim3(PG_THREADS), 0, g->stream, (int) MG_OP_RESTRICT, pair(0), g->sc.p);
-      if (lf > 1)  // x1 of level 1 (the levels below get theirs from k_mg_down2)
-        hipLaunchKernelGGL(k_mg_op<D>, dim3(blocks_for(g->levels[1]->n * D)), dim3(PG_THREADS), 0, g->stream, (int) MG_OP_SMOOTH0,
-                           pair(1), g->sc.p);
     }
     // (the last two-phase level's down phase and the dense coarsest solve share a launch when the coarsest level is tiny)
     const bool fuse_last = g->coarsest_dense && lf == nl && lf >= 2 && g->levels[(size_t) nl]->n <= MG_FUSE_LAST_NODES &&
@@ -3148,13 +3009,6 @@ int pg_solve_t(srrg2_posegraph_s* g, const srrg2_posegraph_params* p, srrg2_pose
     const bool bottom = dense_bottom;  // (k_mg_bottom_dense: that launch and the up phase of level lf - 1 as one dense operator)
     for (int l = 1; l < lf; ++l) {
       const MgLevelBufs* Lb = g->levels[(size_t) l];
-      if (l == 1 && l1_six) {  // level 1 through H instead of Q: residual, then restriction + x1 of level 2
-        hipLaunchKernelGGL(k_mg_op<D>, dim3(blocks_for(Lb->n * D * Lb->row_parts)), dim3(PG_THREADS), 0, g->stream, (int) MG_OP_RESIDUAL, pair(1), g->sc.p);
-        const int pp = std::min(std::max(Lb->col_parts / 2, 1), 8);
-        hipLaunchKernelGGL(k_mg_restrict_smooth<D>, dim3((unsigned) (((size_t) Lb->nc * 8 * pp + PG_THREADS - 1) / PG_THREADS)), dim3(PG_THREADS),
-                           0, g->stream, pair(1), pp, g->sc.p);
-        continue;
-      }
       if (l == lf - 1 && bottom)
         hipLaunchKernelGGL(k_mg_bottom_dense<D>, dim3((unsigned) (((size_t) Lb->n * D * 32 + PG_THREADS - 1) / PG_THREADS)), dim3(PG_THREADS), 0,
                            g->stream, pair(l), g->bottom_B.p, g->sc.p);
@@ -3168,30 +3022,20 @@ int pg_solve_t(srrg2_posegraph_s* g, const srrg2_posegraph_params* p, srrg2_pose
                          g->coarsest_dense, g->sc.p);
     for (int l = lf - 1 - (bottom ? 1 : 0); l >= 1; --l) {
       const MgLevelBufs* Lb = g->levels[(size_t) l];
-      if (l == 1 && l1_six) {  // x = x1 + Ps x_c (level 2's result is in its res), residual, update: the result in level 1's x
-        hipLaunchKernelGGL(k_mg_prolong_res<D>, dim3(blocks_for(Lb->n * D * Lb->prow_parts)), dim3(PG_THREADS), 0, g->stream, pair(1), 0, g->sc.p);
-        hipLaunchKernelGGL(k_mg_op<D>, dim3(blocks_for(Lb->n * D * Lb->row_parts)), dim3(PG_THREADS), 0, g->stream, (int) MG_OP_RESIDUAL, pair(1), g->sc.p);
-        hipLaunchKernelGGL(k_mg_op<D>, dim3(blocks_for(Lb->n * D)), dim3(PG_THREADS), 0, g->stream, (int) MG_OP_UPDATE, pair(1), g->sc.p);
-        continue;
-      }
       const int pp = parts2(Lb, false);
       hipLaunchKernelGGL(k_mg_up2<D>, dim3((unsigned) (((size_t) Lb->n * 8 * pp + PG_THREADS - 1) / PG_THREADS)), dim3(PG_THREADS), 0, g->stream, pair(l), pp,
                          l + 1 < lf ? 1 : 0, g->sc.p);
     }
     const int bp0 = blocks_for(L0b->n * D * L0b->prow_parts);
     if (lf > 1)
-      hipLaunchKernelGGL(k_mg_prolong_res<D>, dim3(bp0), dim3(PG_THREADS), 0, g->stream, pair(0), l1_six ? 1 : 0, g->sc.p);
+      hipLaunchKernelGGL(k_mg_prolong_res<D>, dim3(bp0), dim3(PG_THREADS), 0, g->stream, pair(0), g->sc.p);
     else
       hipLaunchKernelGGL(k_mg_op<D>, dim3(bp0), dim3(PG_THREADS), 0, g->stream, (int) MG_OP_PROLONG, pair(0), g->sc.p);
     hipLaunchKernelGGL(k_mg_op<D>, dim3(br0), dim3(PG_THREADS), 0, g->stream, (int) MG_OP_RESIDUAL, pair(0), g->sc.p);
-    if (!tail) hipLaunchKernelGGL(k_mg_op<D>, dim3(bl0), dim3(PG_THREADS), 0, g->stream, (int) MG_OP_UPDATE, pair(0), g->sc.p);
   };
-  const bool fused_path = fused_cg && lf >= 1 && nl >= 1;  // (the two-phase cycle runs, with the fused CG steps around it)
+  const bool fused_path = two_phase && lf >= 1 && nl >= 1;  // (the two-phase cycle runs, with the fused CG steps around it)
+  // the six-phase cycle (two_phase = 0, or a hierarchy too shallow for the two-phase one)
   auto vcycle = [&]() {
-    if (two_phase && lf >= 1 && nl >= 1) {
-      vcycle2(false, false, false);
-      return;
-    }
     for (int l = 0; l < lf; ++l) {
       const MgLevelBufs* Lb = g->levels[(size_t) l];
       const int bl = blocks_for(Lb->n * D), bc = blocks_for(Lb->nc * D * Lb->col_parts), br = blocks_for(Lb->n * D * Lb->row_parts);
@@ -3252,7 +3096,7 @@ int pg_solve_t(srrg2_posegraph_s* g, const srrg2_posegraph_params* p, srrg2_pose
         MgLevelBufs* L = g->levels[(size_t) l];
         auto grid_of = [](size_t items) { return dim3((unsigned) std::max<size_t>((items + PG_THREADS - 1) / PG_THREADS, 1)); };
         hipLaunchKernelGGL(k_mg_interp<D>, dim3(blocks_for(L->n)), dim3(PG_THREADS), 0, g->stream, pair(l), T, g->poses.p);
-        // Lanes per row of H in the two set-up products that walk rows (k_mg_psmooth, k_mg_hp): a quarter of the cycle's
+        // Lanes per row of H in the set-up product that walks rows (k_mg_psmooth): a quarter of the cycle's
         // `row_parts` where the launch stays above ~64 k lanes.  The cycle's kernels do a block-vector product per incidence and
         // want ~8 incidences per lane; these do a look-up and a block-BLOCK product per incidence into 36 accumulators, and the
         // butterfly that adds the lanes' blocks costs as much as several of them (C5's levels 1 / 2: Q 651 -> 557, 431 -> 381 us,
@@ -3264,29 +3108,23 @@ int pg_solve_t(srrg2_posegraph_s* g, const srrg2_posegraph_params* p, srrg2_pose
             if (sp.L.row_parts >= 2 && items * (size_t) (sp.L.row_parts / 2) >= 65536) sp.L.row_parts /= 2;
           return sp;
         };
-        const MgPair sp_p = setup_pair((size_t) L->np), sp_q = setup_pair((size_t) L->nq);
+        const MgPair sp_p = setup_pair((size_t) L->np);
         hipLaunchKernelGGL(k_mg_psmooth<D>, grid_of((size_t) L->np * sp_p.L.row_parts), dim3(PG_THREADS), 0, g->stream,
                            sp_p, L->smoothed ? omega_p : 0.0);
-        if (g->sw.product_lists) {
-          // lanes per output block: ~list_lane_products products each (C5: 3.3 / 14 / 60 products per entry of Q on levels 0 - 2)
-          auto lanes_for = [&](double per_block, int cap) {
-            int lanes = 1;
-            while (lanes < cap && per_block > (double) g->sw.list_lane_products * lanes) lanes *= 2;
-            return lanes;
-          };
-          const int lq = lanes_for(L->nq > 0 ? (double) L->nqp / L->nq : 0.0, 16);
-          const int lg = lanes_for(L->nc + L->nce > 0 ? (double) (L->ngp + L->np) / (L->nc + L->nce) : 0.0, 32);
-          if (g->sw.setup_f32_ps && pair(l).L.Psf) {  // (the interpolation as float32 operand: MgLevel::Psf, written by k_mg_psmooth)
-            hipLaunchKernelGGL((k_mg_hp_list<D, true>), grid_of((size_t) L->nq * lq), dim3(PG_THREADS), 0, g->stream, pair(l), lq);
-            hipLaunchKernelGGL((k_mg_galerkin_list<D, true>), grid_of((size_t) (L->nc + L->nce) * lg), dim3(PG_THREADS), 0, g->stream, pair(l), lg);
-          } else {
-            hipLaunchKernelGGL((k_mg_hp_list<D, false>), grid_of((size_t) L->nq * lq), dim3(PG_THREADS), 0, g->stream, pair(l), lq);
-            hipLaunchKernelGGL((k_mg_galerkin_list<D, false>), grid_of((size_t) (L->nc + L->nce) * lg), dim3(PG_THREADS), 0, g->stream, pair(l), lg);
-          }
+        // lanes per output block: ~MG_LIST_LANE_PRODUCTS products each (C5: 3.3 / 14 / 60 products per entry of Q on levels 0 - 2)
+        auto lanes_for = [&](double per_block, int cap) {
+          int lanes = 1;
+          while (lanes < cap && per_block > (double) MG_LIST_LANE_PRODUCTS * lanes) lanes *= 2;
+          return lanes;
+        };
+        const int lq = lanes_for(L->nq > 0 ? (double) L->nqp / L->nq : 0.0, 16);
+        const int lg = lanes_for(L->nc + L->nce > 0 ? (double) (L->ngp + L->np) / (L->nc + L->nce) : 0.0, 32);
+        if (pair(l).L.Psf) {  // (the interpolation as float32 operand: MgLevel::Psf, written by k_mg_psmooth; null on the last level)
+          hipLaunchKernelGGL((k_mg_hp_list<D, true>), grid_of((size_t) L->nq * lq), dim3(PG_THREADS), 0, g->stream, pair(l), lq);
+          hipLaunchKernelGGL((k_mg_galerkin_list<D, true>), grid_of((size_t) (L->nc + L->nce) * lg), dim3(PG_THREADS), 0, g->stream, pair(l), lg);
         } else {
-        hipLaunchKernelGGL(k_mg_hp<D>, grid_of((size_t) L->nq * sp_q.L.row_parts), dim3(PG_THREADS), 0, g->stream, sp_q);
-        hipLaunchKernelGGL(k_mg_galerkin<D>, grid_of((size_t) (L->nc + L->nce) * L->col_parts), dim3(PG_THREADS), 0, g->stream,
-                           pair(l));
+          hipLaunchKernelGGL((k_mg_hp_list<D, false>), grid_of((size_t) L->nq * lq), dim3(PG_THREADS), 0, g->stream, pair(l), lq);
+          hipLaunchKernelGGL((k_mg_galerkin_list<D, false>), grid_of((size_t) (L->nc + L->nce) * lg), dim3(PG_THREADS), 0, g->stream, pair(l), lg);
         }
         hipLaunchKernelGGL(k_mg_dinv<D>, dim3((unsigned) ((L->nc + PG_THREADS - 1) / PG_THREADS)), dim3(PG_THREADS), 0, g->stream,
                            pair(l + 1), g->sc.p);
@@ -3320,8 +3158,8 @@ int pg_solve_t(srrg2_posegraph_s* g, const srrg2_posegraph_params* p, srrg2_pose
         const size_t items   = std::max((size_t) L->n, (size_t) L->ne) * D * D;
         hipLaunchKernelGGL(k_mg_to_float<D>, dim3((unsigned) std::min<size_t>(std::max<size_t>((items + PG_THREADS - 1) / PG_THREADS, 1), 4096)),
                            dim3(PG_THREADS), 0, g->stream, pair(l), 1, 0);
-        // (Q in float32, row- and column-ordered: read by the two-phase levels only -- level 0's Q is 2.7 x its Ps)
-        const bool with_q = two_phase && l >= 1 && l < lf && !(l == 1 && g->sw.l1_six && g->sw.fused_cg && lf >= 3);
+        // (Q in float32: read by the two-phase levels only -- level 0's Q is 2.7 x its Ps)
+        const bool with_q = two_phase && l >= 1 && l < lf;
         if (with_q && L->nq > 0 && pair(l).L.Qf)
           hipLaunchKernelGGL(k_mg_q_to_float<D>, dim3((unsigned) ((L->nq + PG_THREADS - 1) / PG_THREADS)), dim3(PG_THREADS), 0, g->stream, pair(l));
       }
@@ -3332,7 +3170,7 @@ int pg_solve_t(srrg2_posegraph_s* g, const srrg2_posegraph_params* p, srrg2_pose
     hipLaunchKernelGGL(k_pg_pcg_init, dim3(nb), dim3(PG_THREADS), 0, g->stream, n, g->b.p, g->x.p, r, g->part_bb.p, g->sc.p,
                        g->part_chi.p, g->part_n.p, nchi);
     if (fused_path) {
-      vcycle2(false, false, true);
+      vcycle2(false, false);
       hipLaunchKernelGGL(k_pg_update_dot<D>, dim3(nb), dim3(PG_THREADS), 0, g->stream, n, pair(0), r, g->part_rz.p, g->sc.p);
     } else {
       vcycle();
@@ -3349,7 +3187,7 @@ int pg_solve_t(srrg2_posegraph_s* g, const srrg2_posegraph_params* p, srrg2_pose
         if (fused_path) {
           hipLaunchKernelGGL(k_pg_update_xr_smooth<D>, dim3(nb), dim3(PG_THREADS), 0, g->stream, n, nb, g->p.p, g->Ap.p, g->x.p, r, rz_cur,
                              g->part_pAp.p, g->part_rr.p, pair(0), g->sc.p);
-          vcycle2(true, true, true);
+          vcycle2(true, true);
           hipLaunchKernelGGL(k_pg_update_dot<D>, dim3(nb), dim3(PG_THREADS), 0, g->stream, n, pair(0), r, rz_nxt, g->sc.p);
         } else {
         hipLaunchKernelGGL(k_pg_update_xr, dim3(nb), dim3(PG_THREADS), 0, g->stream, n, nb, (double) p->pcg_tolerance, g->p.p,
@@ -3557,14 +3395,6 @@ int srrg2_posegraph_create(int variable_kind, int device, srrg2_posegraph_h* out
     getf("SRRG2_AMD_PG_OMEGA", t.omega);
     getf("SRRG2_AMD_PG_LAG", t.lag_below);
     if (std::getenv("SRRG2_AMD_PG_DEBUG")) t.debug = 1;
-    if (const char* e = std::getenv("SRRG2_AMD_PG_FUSED_CG")) g->sw.fused_cg = std::atoi(e) != 0;
-    if (const char* e = std::getenv("SRRG2_AMD_PG_COLUMN_COPIES")) g->sw.column_copies = std::atoi(e) != 0;
-    if (const char* e = std::getenv("SRRG2_AMD_PG_SETUP_F32_PS")) g->sw.setup_f32_ps = std::atoi(e) != 0;
-    if (const char* e = std::getenv("SRRG2_AMD_PG_L1_SIX")) g->sw.l1_six = std::atoi(e) != 0;
-    if (const char* e = std::getenv("SRRG2_AMD_PG_TREE_POSITIONS")) g->sw.tree_positions = std::atoi(e) != 0;
-    if (const char* e = std::getenv("SRRG2_AMD_PG_FUSED_BOTTOM")) g->sw.fused_bottom = std::atoi(e) != 0;
-    if (const char* e = std::getenv("SRRG2_AMD_PG_PRODUCT_LISTS")) g->sw.product_lists = std::atoi(e) != 0;
-    if (const char* e = std::getenv("SRRG2_AMD_PG_LIST_LANES")) g->sw.list_lane_products = std::max(1, std::atoi(e));
     if (const char* e = std::getenv("SRRG2_AMD_PG_OFFSET_LIMIT")) g->st_offset_limit = std::min<unsigned long long>(std::strtoull(e, nullptr, 10), 0x7fff0000ull);
     if (t.match_passes < 1) t.match_passes = 1;
     apply_tuning(g, t);

@@ -37,12 +37,14 @@ def test_matches_oracle(oracle, product, kind):
     assert sg[-1]["chi"] < 0.2 * sg[0]["chi"]
 
 
-def test_se2_matches_oracle_on_a_four_level_hierarchy(oracle, product):
+@pytest.mark.parametrize("two_phase", [1, 0])
+def test_se2_matches_oracle_on_a_four_level_hierarchy(oracle, product, two_phase):
     """3 000 SE(2) poses: 3 000 -> ~375 -> ~47 -> ~6 nodes, so the 3 x 3-block instances of the two-phase cycle kernels
     (k_mg_down2 / k_mg_up2 / k_mg_down2_coarsest: whole blocks per lane) all run; poses within 1e-5 of the oracle's
-    block-Jacobi PCG"""
+    block-Jacobi PCG.  two_phase = 0: the six-phase cycle with the unfused CG steps, the solver's only other cycle"""
     g = syn.pose_graph_2d(V=3000, E=9000)
     ref, gpu = oracle.OraclePoseGraph(abi.SE2_RIGHT), product.PoseGraph(abi.SE2_RIGHT)
+    gpu.set_tuning(two_phase=two_phase)
     for pg in (ref, gpu):
         pg.set_graph(g["poses_init"], g["ij"], g["Z"])
     sr, sg = ref.solve(_tight()), gpu.solve(_tight())
