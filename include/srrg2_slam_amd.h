@@ -455,6 +455,27 @@ int srrg2_posegraph_size(srrg2_posegraph_h h, int* num_variables, int* num_facto
  * factor between two older variables, a changed flag or keep_structure = 0 rebuild as before). */
 int srrg2_posegraph_structure_info(srrg2_posegraph_h h, int* hierarchy_builds, int* eliminated_leaves);
 
+/* Robust kernels on pose-graph factors (the reference robustifies its solver factors too: factor->setRobustifier,
+ * multi_loop_detector_hbst_impl.cpp:337).  A factor's weight is the aligner's formula (srrg2_robustifier_kind), in double:
+ * w = 1 for chi < thr; for chi >= thr CLAMP gives 0, SATURATED thr/chi, CAUCHY 1/(1 + chi/thr).
+ * Iteratively reweighted Gauss-Newton: every iteration of srrg2_posegraph_solve computes w from the chi at that iteration's
+ * linearisation point and adds w J^T Omega J and w J^T Omega e.  srrg2_posegraph_stats.chi stays the raw sum of e^T Omega e
+ * over the enabled factors.  Defaults: srrg2_posegraph_set resets every factor to NONE, add_factor starts one at NONE,
+ * remove_factor drops it; ids keep their meaning across remove_factor.  Robustifiers are numerics, not topology: setting
+ * one does not rebuild the multigrid hierarchy (structure_info's hierarchy_builds stays) nor disturb the elimination of
+ * appended leaves, which are eliminated with their weight.  A free variable whose factors are all weighted 0 (CLAMP) has a
+ * singular block: solver_status = 1, the poses are left as they were.
+ * Errors: a bad or removed id, an unknown kind, or a threshold that is not positive and finite (kind != NONE) return
+ * SRRG2_E_INVALID and leave the handle unchanged. */
+/* robustifier of one factor (kind: srrg2_robustifier_kind; chi_threshold > 0 and finite unless kind == NONE) */
+int srrg2_posegraph_set_factor_robustifier(srrg2_posegraph_h h, int factor_id, int kind, float chi_threshold);
+/* the same for every factor id 0..E-1 at once (like set_enabled: entries of removed ids are ignored);
+ * kinds == NULL: all NONE */
+int srrg2_posegraph_set_robustifiers(srrg2_posegraph_h h, const int32_t* kinds, const float* chi_thresholds);
+/* chi = e^T Omega e and the robust weight w(chi) of every factor id at the CURRENT poses, enabled or not (E floats each;
+ * either pointer may be NULL); a removed id gives chi = NaN, weight = 0.  Changes nothing in the graph. */
+int srrg2_posegraph_evaluate_factors(srrg2_posegraph_h h, float* chi_out, float* weight_out);
+
 /* ---- scene slices kept in HBM between frames: clipping and correspondence-based merging ------
  * the tracker-side steps either side of align()
  * (S/trackers/tracker_slice_processor_impl.cpp:111-205: merge(), clip()).  A scene is a point

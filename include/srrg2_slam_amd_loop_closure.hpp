@@ -414,11 +414,22 @@ public:
   int addFactor(int from, int to, const EstimateType& Z, const float* information /* D x D or null */, bool enabled) {
     int id = -1;
     check(srrg2_posegraph_add_factor(_h, from, to, Z.data(), information, enabled ? 1 : 0, &id));
+    _factor_ids = id + 1;
     return id;
   }
   void setFactorEnabled(int factor_id, bool enabled) { check(srrg2_posegraph_set_factor_enabled(_h, factor_id, enabled ? 1 : 0)); }
   void removeFactor(int factor_id) { check(srrg2_posegraph_remove_factor(_h, factor_id)); }
   void size(int& variables, int& factors, int& enabled_factors) const { check(srrg2_posegraph_size(_h, &variables, &factors, &enabled_factors)); }
+  // factor->setRobustifier (multi_loop_detector_hbst_impl.cpp:337): kind = srrg2_robustifier_kind, iteratively reweighted GN
+  void setFactorRobustifier(int factor_id, int kind, float chi_threshold) {
+    check(srrg2_posegraph_set_factor_robustifier(_h, factor_id, kind, chi_threshold));
+  }
+  // chi and robust weight of every factor id at the current estimates (removed ids: chi = NaN, weight = 0)
+  void evaluateFactors(std::vector<float>& chi, std::vector<float>& weight) const {
+    chi.assign((size_t) _factor_ids, 0.f);
+    weight.assign(chi.size(), 0.f);
+    if (!chi.empty()) check(srrg2_posegraph_evaluate_factors(_h, chi.data(), weight.data()));
+  }
   std::vector<srrg2_posegraph_stats> compute() {  // global_solver->compute(), blocking
     srrg2_posegraph_params p{param_max_iterations, param_pcg_max_iterations, param_pcg_tolerance, param_damping};
     std::vector<srrg2_posegraph_stats> st((size_t) std::max(param_max_iterations, 1));
@@ -439,6 +450,7 @@ public:
 
 private:
   srrg2_posegraph_h _h = nullptr;
+  int _factor_ids      = 0;  // ids handed out so far (removed ones included)
 };
 using PoseGraph2D = PoseGraph_<SRRG2_SE2_RIGHT>;
 using PoseGraph3D = PoseGraph_<SRRG2_SE3_QUAT_RIGHT>;
@@ -458,6 +470,9 @@ public:
   explicit GraphSLAMLifecycle(GraphType& graph) : _graph(graph) {
     for (int a = 0; a < D; ++a) _default_info[a * D + a] = 1.f;
   }
+  // robustifier put on every closure loopValidate adds (kind = srrg2_robustifier_kind; SRRG2_ROBUST_NONE = none, the default)
+  int param_closure_robustifier       = SRRG2_ROBUST_NONE;
+  float param_closure_robustifier_chi = 0.f;
   // a variable with the current robot pose; an odometry factor from the previous local map with measurement
   // robot_in_local_map and information default_info * info_scale; the very first local map is Fixed (:86)
   int makeNewMap(const EstimateType& robot_in_world, const EstimateType& robot_in_local_map, float info_scale = 1.f) {
@@ -474,8 +489,11 @@ public:
   // closures enter the graph disabled (:238-241); rejected ones are removed (:279-281), accepted ones enabled (:283-286)
   std::vector<LoopClosureType> loopValidate(std::vector<LoopClosureType> detected, const Validator& validator = nullptr) {
     _num_valid_closures = 0;
-    for (LoopClosureType& c : detected)
+    for (LoopClosureType& c : detected) {
       c.factor_id = _graph.addFactor(c.source_graph_id, c.target_graph_id, c.measurement, c.information, false);
+      if (param_closure_robustifier != SRRG2_ROBUST_NONE)
+        _graph.setFactorRobustifier(c.factor_id, param_closure_robustifier, param_closure_robustifier_chi);
+    }
     std::vector<LoopClosureType> accepted;
     if (detected.empty()) return accepted;
     std::vector<Verdict> verdicts(detected.size(), Accepted);

@@ -6,7 +6,9 @@
 // so there is nothing to Schur-eliminate: block-sparse H build + preconditioned CG.
 //
 //   k_pg_edges<D>     one thread per factor: e, Ji, Jj, Omega products -> Ho[e] = Ji^T W Jj and the factor's
-//                     contributions to H_ii, H_jj, b_i, b_j, chi (stored per factor: no atomics)
+//                     contributions to H_ii, H_jj, b_i, b_j, chi (stored per factor: no atomics); with robustifiers
+//                     (k_pg_edges<D, true>) the blocks and b carry the factor's weight w(chi), chi stays raw
+//   k_pg_factor_eval<D>  chi and w(chi) of every factor at the current poses (srrg2_posegraph_evaluate_factors)
 //   k_pg_vertices<D>  one thread per variable: gathers its factors' contributions in incidence order
 //                     (deterministic), adds damping, handles Fixed variables, inverts the 6x6 block (level-0 smoother)
 //   k_mg_*            the aggregation-multigrid preconditioner (see "Linear solver" below)
@@ -20,10 +22,12 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <set>
 #include <string>
 #include <thread>
@@ -122,8 +126,9 @@ __device__ void edge_linearize(const float* Xi, const float* Xj, const float* Z,
   }
 }
 
-template <int D>
-__device__ void atwb(const double* A, const double* W, const double* B, double* C) {
+// C = A^T W B, times the robust weight w when SCALE (the unweighted instance is the plain product, bit for bit)
+template <int D, bool SCALE = false>
+__device__ void atwb(const double* A, const double* W, const double* B, double* C, double w = 1.0) {
   double WB[D * D];
   for (int r = 0; r < D; ++r)
     for (int c = 0; c < D; ++c) {
@@ -135,15 +140,32 @@ __device__ void atwb(const double* A, const double* W, const double* B, double* 
     for (int c = 0; c < D; ++c) {
       double s = 0.0;
       for (int k = 0; k < D; ++k) s = s + A[k * D + r] * WB[k * D + c];
-      C[r * D + c] = s;
+      C[r * D + c] = SCALE ? w * s : s;
     }
 }
 
-template <int D>
+// Robustifier of one factor (srrg2_posegraph_set_factor_robustifier) and its weight: the aligner's formula (robust_weight,
+// kernels.hip) in double.  Iteratively reweighted Gauss-Newton: every iteration takes w from the chi at its own
+// linearisation point and adds w J^T Omega J, w J^T Omega e.
+struct PgRobust {
+  int32_t kind;  // srrg2_robustifier_kind
+  float thr;     // chi_threshold
+};
+
+__device__ __forceinline__ double pg_robust_weight(int kind, double thr, double chi) {
+  if (kind == SRRG2_ROBUST_NONE || chi < thr) return 1.0;
+  if (kind == SRRG2_ROBUST_CLAMP) return 0.0;
+  if (kind == SRRG2_ROBUST_SATURATED) return thr / chi;
+  return 1.0 / (1.0 + chi / thr);
+}
+
+// ROBUST = false (no factor of the handle has a robustifier): `robust` is not read and the blocks are those of plain GN
+template <int D, bool ROBUST>
 __global__ __launch_bounds__(PG_THREADS) void k_pg_edges(int E, int T, const float* __restrict__ poses,
                                                          const int2* __restrict__ ij, const float* __restrict__ Z,
                                                          const double* __restrict__ omega,
-                                                         const uint8_t* __restrict__ enabled, double* __restrict__ Ho,
+                                                         const uint8_t* __restrict__ enabled,
+                                                         const PgRobust* __restrict__ robust, double* __restrict__ Ho,
                                                          EdgeContrib<D>* __restrict__ contrib) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= E) return;
@@ -164,10 +186,16 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_edges(int E, int T, const flo
   }
   double chi = 0.0;
   for (int a = 0; a < D; ++a) chi = chi + err[a] * We[a];
-  C.chi = chi;
-  atwb<D>(Ji, W, Ji, C.Cii);
-  atwb<D>(Jj, W, Jj, C.Cjj);
-  atwb<D>(Ji, W, Jj, Ho + (size_t) e * D * D);
+  C.chi = chi;  // (raw: stats.chi keeps its meaning with robustifiers)
+  double w = 1.0;
+  if (ROBUST) {
+    const PgRobust rb = robust[e];
+    w = pg_robust_weight(rb.kind, (double) rb.thr, chi);
+    for (int a = 0; a < D; ++a) We[a] = w * We[a];
+  }
+  atwb<D, ROBUST>(Ji, W, Ji, C.Cii, w);
+  atwb<D, ROBUST>(Jj, W, Jj, C.Cjj, w);
+  atwb<D, ROBUST>(Ji, W, Jj, Ho + (size_t) e * D * D, w);
   for (int r = 0; r < D; ++r) {
     double s = 0.0, t = 0.0;
     for (int k = 0; k < D; ++k) {
@@ -177,6 +205,34 @@ __global__ __launch_bounds__(PG_THREADS) void k_pg_edges(int E, int T, const flo
     C.bi[r] = s;
     C.bj[r] = t;
   }
+}
+
+// chi = e^T Omega e and w(chi) of EVERY factor (enabled or not) at the current poses: out[e] = chi, out[E + e] = w
+// (srrg2_posegraph_evaluate_factors).  The Jacobians edge_linearize also forms are dead code here.
+template <int D>
+__global__ __launch_bounds__(PG_THREADS) void k_pg_factor_eval(int E, int T, const float* __restrict__ poses,
+                                                               const int2* __restrict__ ij, const float* __restrict__ Z,
+                                                               const double* __restrict__ omega,
+                                                               const PgRobust* __restrict__ robust, float* __restrict__ out) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  const int2 v = ij[e];
+  double err[D], Ji[D * D], Jj[D * D];
+  edge_linearize<D>(poses + (size_t) v.x * T, poses + (size_t) v.y * T, Z + (size_t) e * T, err, Ji, Jj);
+  const double* W = omega + (size_t) e * D * D;
+  double chi = 0.0;
+  for (int a = 0; a < D; ++a) {  // (the order of k_pg_edges: chi is the same number)
+    double s = 0.0;
+    for (int k = 0; k < D; ++k) s = s + W[a * D + k] * err[k];
+    chi = chi + err[a] * s;
+  }
+  double w = 1.0;
+  if (robust) {
+    const PgRobust rb = robust[e];
+    w = pg_robust_weight(rb.kind, (double) rb.thr, chi);
+  }
+  out[e]              = (float) chi;
+  out[(size_t) E + e] = (float) w;
 }
 
 template <int D>
@@ -1811,6 +1867,13 @@ struct srrg2_posegraph_s {
   std::vector<float> h_Z;  // the measurements (the spanning-tree geometry of the matching, build_hierarchy)
   std::vector<uint8_t> h_enabled, h_removed, h_fixed;
   bool inc_dirty = false;
+  // robustifiers (srrg2_posegraph_set_factor_robustifier): numerics, not topology -- the hierarchy is not marked dirty.  The host
+  // copy is the truth; the device copy is uploaded by the next solve / evaluation that reads it.
+  std::vector<PgRobust> h_robust;
+  int n_robust      = 0;     // factors whose kind is not NONE; 0: k_pg_edges<D, false>, which reads no robustifier
+  bool robust_dirty = false;
+  DevBuf<PgRobust> robust;
+  DevBuf<float> eval_out;    // k_pg_factor_eval: E chi, then E weights
 };
 
 namespace {
@@ -2898,6 +2961,15 @@ int build_hierarchy(srrg2_posegraph_s* g) {
   return 0;
 }
 
+// the device copy of the robustifiers, when the host's has changed since the last upload
+int pg_sync_robust(srrg2_posegraph_s* g) {
+  if (!g->robust_dirty) return 0;
+  int rc = upload(g->robust, g->h_robust);
+  if (rc) return rc;
+  g->robust_dirty = false;
+  return 0;
+}
+
 // The variables / factors appended since the hierarchy was built: a forest of leaves (every new variable free, with exactly one
 // factor to a variable of lower index, every new factor such a factor, enabled), at most 32 of them -> their parents and factor
 // codes on the device, g->ntail set.  Anything else -> false: the caller rebuilds the hierarchy.
@@ -2948,6 +3020,8 @@ int pg_solve_t(srrg2_posegraph_s* g, const srrg2_posegraph_params* p, srrg2_pose
   if ((rc = g->contrib.reserve((size_t) std::max(E, 1) * (sizeof(EdgeContrib<D>) / sizeof(double))))) return rc;
   for (DevBuf<double>* v : {&g->b, &g->x, &g->r, &g->p, &g->Ap})
     if ((rc = v->reserve((size_t) std::max(V * D, 1)))) return rc;
+  const bool robust = g->n_robust > 0;
+  if (robust && (rc = pg_sync_robust(g))) return rc;
   for (DevBuf<double>* v : {&g->part_rz, &g->part_rz_new, &g->part_pAp, &g->part_rr, &g->part_bb})
     if ((rc = v->reserve((size_t) nb))) return rc;
   if ((rc = g->part_chi.reserve((size_t) nchi))) return rc;
@@ -3068,9 +3142,12 @@ int pg_solve_t(srrg2_posegraph_s* g, const srrg2_posegraph_params* p, srrg2_pose
   } exec_guard{chunk_exec};
   for (int it = 0; it < p->max_iterations; ++it) {
     HIP_TRY(hipMemsetAsync(g->sc.p, 0, sizeof(PgScalars), g->stream));
-    if (E > 0)
-      hipLaunchKernelGGL(k_pg_edges<D>, dim3(nbe), dim3(PG_THREADS), 0, g->stream, E, T, g->poses.p, g->ij.p, g->Z.p,
-                         g->omega.p, g->enabled.p, g->Ho.p, contrib);
+    if (E > 0 && robust)
+      hipLaunchKernelGGL((k_pg_edges<D, true>), dim3(nbe), dim3(PG_THREADS), 0, g->stream, E, T, g->poses.p, g->ij.p, g->Z.p,
+                         g->omega.p, g->enabled.p, (const PgRobust*) g->robust.p, g->Ho.p, contrib);
+    else if (E > 0)
+      hipLaunchKernelGGL((k_pg_edges<D, false>), dim3(nbe), dim3(PG_THREADS), 0, g->stream, E, T, g->poses.p, g->ij.p, g->Z.p,
+                         g->omega.p, g->enabled.p, (const PgRobust*) nullptr, g->Ho.p, contrib);
     hipLaunchKernelGGL(k_pg_chi, dim3(nchi), dim3(PG_THREADS), 0, g->stream, E, g->enabled.p, (const void*) contrib,
                        cstride, chi_off, g->part_chi.p, g->part_n.p);
     hipLaunchKernelGGL(k_pg_vertices<D>, dim3(nbv), dim3(PG_THREADS), 0, g->stream, V, g->fixed.p, g->inc_start.p,
@@ -3422,6 +3499,7 @@ int srrg2_posegraph_destroy(srrg2_posegraph_h g) {
   g->st_keys_a.release(); g->st_keys_b.release(); g->st_cnt.release(); g->st_off.release(); g->st_slot.release();
   g->st_ia.release(); g->st_ib.release(); g->st_counts.release(); g->st_total.release(); g->st_temp.release();
   g->st_vals.release(); g->st_rle.release();
+  g->robust.release(); g->eval_out.release();
   for (MgLevelBufs* L : g->level_pool) {
     L->release();
     delete L;
@@ -3482,6 +3560,9 @@ int srrg2_posegraph_set(srrg2_posegraph_h g, int V, const float* poses, const ui
   g->V = V;
   g->E = E;
   g->h_Z.assign(Z, Z + (size_t) E * T);
+  g->h_robust.assign((size_t) E, PgRobust{SRRG2_ROBUST_NONE, 0.f});  // (every factor starts without a robustifier)
+  g->n_robust     = 0;
+  g->robust_dirty = true;
   if (same_topology) return 0;  // (incidence lists and hierarchy structure are still those of this topology)
   g->h_ij.assign(ij, ij + 2 * (size_t) E);
   g->h_enabled.assign(en.begin(), en.begin() + E);
@@ -3539,6 +3620,8 @@ int srrg2_posegraph_add_factor(srrg2_posegraph_h g, int i, int j, const float* Z
   g->h_Z.insert(g->h_Z.end(), Z, Z + T);
   g->h_enabled.push_back(en);
   g->h_removed.push_back(0);
+  g->h_robust.push_back(PgRobust{SRRG2_ROBUST_NONE, 0.f});
+  g->robust_dirty = true;
   if (id_out) *id_out = E;
   g->E         = E + 1;
   g->inc_dirty = true;
@@ -3568,7 +3651,81 @@ int srrg2_posegraph_remove_factor(srrg2_posegraph_h g, int factor_id) {
   if (g->h_enabled[(size_t) factor_id]) g->mg_dirty = true;
   g->h_enabled[(size_t) factor_id] = 0;
   g->h_removed[(size_t) factor_id] = 1;
+  if (g->h_robust[(size_t) factor_id].kind != SRRG2_ROBUST_NONE) {  // (a removed factor has no robustifier)
+    g->h_robust[(size_t) factor_id] = PgRobust{SRRG2_ROBUST_NONE, 0.f};
+    g->n_robust -= 1;
+    g->robust_dirty = true;
+  }
   HIP_TRY(hipMemcpy(g->enabled.p + factor_id, &en, 1, hipMemcpyHostToDevice));
+  return 0;
+}
+
+/* Robustifiers of the factors: numerics only (no hierarchy rebuild); see include/srrg2_slam_amd.h */
+static bool robust_args_ok(int kind, float chi_threshold) {
+  if (kind == SRRG2_ROBUST_NONE) return true;
+  if (kind != SRRG2_ROBUST_CLAMP && kind != SRRG2_ROBUST_SATURATED && kind != SRRG2_ROBUST_CAUCHY) return false;
+  return chi_threshold > 0.f && std::isfinite(chi_threshold);
+}
+
+int srrg2_posegraph_set_factor_robustifier(srrg2_posegraph_h g, int factor_id, int kind, float chi_threshold) {
+  if (!g || factor_id < 0 || factor_id >= g->E) return fail(SRRG2_E_INVALID, "posegraph_set_factor_robustifier: bad factor id");
+  if (g->h_removed[(size_t) factor_id]) return fail(SRRG2_E_INVALID, "posegraph_set_factor_robustifier: factor was removed");
+  if (!robust_args_ok(kind, chi_threshold))
+    return fail(SRRG2_E_INVALID, "posegraph_set_factor_robustifier: unknown kind or threshold not positive and finite");
+  PgRobust& r = g->h_robust[(size_t) factor_id];
+  g->n_robust += (kind != SRRG2_ROBUST_NONE ? 1 : 0) - (r.kind != SRRG2_ROBUST_NONE ? 1 : 0);
+  r               = PgRobust{kind, kind == SRRG2_ROBUST_NONE ? 0.f : chi_threshold};
+  g->robust_dirty = true;
+  return 0;
+}
+
+int srrg2_posegraph_set_robustifiers(srrg2_posegraph_h g, const int32_t* kinds, const float* chi_thresholds) {
+  if (!g) return fail(SRRG2_E_INVALID, "posegraph_set_robustifiers: null handle");
+  const int E = g->E;
+  if (kinds) {  // (every entry is checked before any is applied: an error leaves the handle as it was)
+    for (int e = 0; e < E; ++e) {
+      if (g->h_removed[(size_t) e] || kinds[e] == SRRG2_ROBUST_NONE) continue;
+      if (!chi_thresholds || !robust_args_ok(kinds[e], chi_thresholds[e]))
+        return fail(SRRG2_E_INVALID, "posegraph_set_robustifiers: unknown kind or threshold not positive and finite");
+    }
+  }
+  int n = 0;
+  for (int e = 0; e < E; ++e) {
+    const int k = (kinds && !g->h_removed[(size_t) e]) ? kinds[e] : SRRG2_ROBUST_NONE;
+    g->h_robust[(size_t) e] = PgRobust{k, k == SRRG2_ROBUST_NONE ? 0.f : chi_thresholds[e]};
+    n += k != SRRG2_ROBUST_NONE ? 1 : 0;
+  }
+  g->n_robust     = n;
+  g->robust_dirty = true;
+  return 0;
+}
+
+int srrg2_posegraph_evaluate_factors(srrg2_posegraph_h g, float* chi_out, float* weight_out) {
+  if (!g || (!chi_out && !weight_out)) return fail(SRRG2_E_INVALID, "posegraph_evaluate_factors: bad arguments");
+  const int E = g->E;
+  if (E == 0) return 0;
+  HIP_TRY(hipSetDevice(g->device));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  int rc;
+  if (g->n_robust > 0 && (rc = pg_sync_robust(g))) return rc;
+  if ((rc = g->eval_out.reserve((size_t) 2 * E))) return rc;
+  const PgRobust* rb = g->n_robust > 0 ? g->robust.p : nullptr;
+  const dim3 grid((unsigned) ((E + PG_THREADS - 1) / PG_THREADS));
+  if (g->D == 6)
+    hipLaunchKernelGGL(k_pg_factor_eval<6>, grid, dim3(PG_THREADS), 0, g->stream, E, g->T, g->poses.p, g->ij.p, g->Z.p, g->omega.p, rb,
+                       g->eval_out.p);
+  else
+    hipLaunchKernelGGL(k_pg_factor_eval<3>, grid, dim3(PG_THREADS), 0, g->stream, E, g->T, g->poses.p, g->ij.p, g->Z.p, g->omega.p, rb,
+                       g->eval_out.p);
+  HIP_TRY(hipGetLastError());
+  std::vector<float> h((size_t) 2 * E);
+  HIP_TRY(hipMemcpyAsync(h.data(), g->eval_out.p, sizeof(float) * h.size(), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  for (int e = 0; e < E; ++e) {
+    const bool removed = g->h_removed[(size_t) e] != 0;
+    if (chi_out) chi_out[e] = removed ? std::numeric_limits<float>::quiet_NaN() : h[(size_t) e];
+    if (weight_out) weight_out[e] = removed ? 0.f : h[(size_t) E + e];
+  }
   return 0;
 }
 

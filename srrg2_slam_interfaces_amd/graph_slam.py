@@ -11,8 +11,13 @@ REJECTED, ACCEPTED, PENDING = 0, 1, 2
 
 
 class GraphSLAMLifecycle:
-    def __init__(self, posegraph, default_information=None):
+    def __init__(self, posegraph, default_information=None, closure_robustifier=None):
+        """closure_robustifier: None or (kind, chi_threshold), put on every closure loop_validate adds (the reference
+        robustifies its closure factors, multi_loop_detector_hbst_impl.cpp:337): a wrong closure that slips through is
+        down-weighted by the solve instead of dragging the map toward it"""
         self.graph = posegraph
+        self.closure_robustifier = None if closure_robustifier is None else (int(closure_robustifier[0]),
+                                                                             float(closure_robustifier[1]))
         self.default_info = (np.eye(posegraph.D, dtype=np.float32) if default_information is None
                              else np.asarray(default_information, np.float32))  # _default_info
         self.current_local_map = None  # graph id
@@ -38,7 +43,7 @@ class GraphSLAMLifecycle:
         self.num_valid_closures = 0
         ids = []
         for (i, j, Z, info) in detected_closures:
-            fid = self.graph.add_factor(i, j, Z, info, enabled=False)
+            fid = self.graph.add_factor(i, j, Z, info, enabled=False, robustifier=self.closure_robustifier)
             self.closures[fid] = (i, j)
             ids.append(fid)
         if not ids:
@@ -64,3 +69,11 @@ class GraphSLAMLifecycle:
         if not self.num_valid_closures:
             return []
         return self.graph.solve(params)
+
+    def closure_weights(self):
+        """{factor id: (chi, weight)} of the closures still in the graph, at the current poses (evaluate_factors): the
+        per-closure value a caller can decide on (remove_factor) after optimize()"""
+        if not self.closures:
+            return {}
+        chi, w = self.graph.evaluate_factors()
+        return {fid: (float(chi[fid]), float(w[fid])) for fid in sorted(self.closures)}

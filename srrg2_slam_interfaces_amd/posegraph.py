@@ -120,7 +120,8 @@ class PoseGraph:
         self.V += 1
         return vid.value
 
-    def add_factor(self, i, j, Z, information=None, enabled=True):
+    def add_factor(self, i, j, Z, information=None, enabled=True, robustifier=None):
+        """robustifier: None or (kind, chi_threshold), applied right after the factor is added"""
         Z = np.ascontiguousarray(Z, np.float32).reshape(-1)
         assert Z.size == self.tsize
         info = None
@@ -131,7 +132,44 @@ class PoseGraph:
         self._check(self._fn("add_factor")(self._h, C.c_int(i), C.c_int(j), Z.ctypes.data_as(C.POINTER(C.c_float)), info,
                                            C.c_int(int(enabled)), C.byref(fid)))
         self.E += 1
+        if robustifier is not None:
+            self.set_factor_robustifier(fid.value, *robustifier)
         return fid.value
+
+    # -- robust kernels on the factors (srrg2_posegraph_set_factor_robustifier / set_robustifiers / evaluate_factors)
+    def _optional_fn(self, name):
+        try:
+            return self._fn(name)
+        except AttributeError:
+            raise NotImplementedError("%s%s: this pose-graph backend has no robust kernels" % (self._prefix, name)) from None
+
+    def set_factor_robustifier(self, factor_id, kind, chi_threshold=0.0):
+        """kind: abi.ROBUST_*; weight w(chi) per Gauss-Newton iteration (iteratively reweighted)"""
+        fn = self._optional_fn("set_factor_robustifier")
+        self._check(fn(self._h, C.c_int(factor_id), C.c_int(kind), C.c_float(chi_threshold)))
+
+    def set_robustifiers(self, kinds, chi_thresholds=None):
+        """kinds / chi_thresholds: one entry per factor id; kinds None = every factor without a robustifier"""
+        fn = self._optional_fn("set_robustifiers")
+        kp = tp = None
+        if kinds is not None:
+            kinds = np.ascontiguousarray(kinds, np.int32)
+            assert kinds.size == self.E
+            kp = kinds.ctypes.data_as(C.POINTER(C.c_int32))
+        if chi_thresholds is not None:
+            chi_thresholds = np.ascontiguousarray(chi_thresholds, np.float32)
+            assert chi_thresholds.size == self.E
+            tp = chi_thresholds.ctypes.data_as(C.POINTER(C.c_float))
+        self._check(fn(self._h, kp, tp))
+
+    def evaluate_factors(self):
+        """(chi, weight): e^T Omega e and w(chi) of every factor id at the current poses, enabled or not; removed ids give
+        chi = NaN and weight = 0"""
+        fn = self._optional_fn("evaluate_factors")
+        chi, w = np.zeros(max(self.E, 1), np.float32), np.zeros(max(self.E, 1), np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(fn(self._h, chi.ctypes.data_as(fp), w.ctypes.data_as(fp)))
+        return chi[:self.E], w[:self.E]
 
     def set_factor_enabled(self, factor_id, enabled):
         self._check(self._fn("set_factor_enabled")(self._h, C.c_int(factor_id), C.c_int(int(enabled))))
