@@ -130,6 +130,7 @@ __device__ __forceinline__ void block_add(int v, int* target) {
   __shared__ int red[4];
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  __syncthreads();  // (a call right after another: thread 0 must have read red[] before the wave leaders overwrite it)
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {

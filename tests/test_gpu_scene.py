@@ -102,7 +102,7 @@ def test_merge_parity_with_duplicates(oracle, product, target, with_corr):
     _same_scene(*scenes)
     if with_corr:
         assert res[1]["num_merged"] > 100
-        # a second merge into the grown scene (capacity growth keeps the old points)
+    # (merges into a grown scene, 2-D, clouds without normals, the launch caps: tests/test_gpu_scene_merge.py)
     with pytest.raises(RuntimeError):
         b = product.scene_binding(0)
         scene, meas = mapping.Scene(b, 3), mapping.Scene(b, 3)
