@@ -770,6 +770,12 @@ static inline float robust_weight(int kind, float thr, float chi, int* kernelize
   }
 }
 
+/* max |u - c| over the pixels u + 0.5 in [0, n) of a projected point: n while the principal point c lies in the image, more
+ * when it lies outside (float operations, the same in aligner_host.hip) */
+static float proj_extent(int n, float c) {
+  return fmaxf(fmaxf((float) n, fabsf(c + 0.5f)), fabsf(((float) n - 0.5f) - c));
+}
+
 static int slice_exponent(const o_aligner* a, const o_slice* s) {
   const int plane = s->cfg.kind == SRRG2_SLICE_P2PLANE;
   const int repro = s->cfg.kind == SRRG2_SLICE_REPROJECTION;
@@ -779,7 +785,8 @@ static int slice_exponent(const o_aligner* a, const o_slice* s) {
   double mb       = plane ? (1.7320508075688772 * (double) s->ninf) * 1.01 : 1.01;
   if (repro) {
     const double K0 = (double) s->cfg.camera_matrix[0], K4 = (double) s->cfg.camera_matrix[4];
-    const double tx = (double) s->cfg.image_cols / K0, ty = (double) s->cfg.image_rows / K4;
+    const double tx = (double) proj_extent(s->cfg.image_cols, s->cfg.camera_matrix[2]) / K0;
+    const double ty = (double) proj_extent(s->cfg.image_rows, s->cfg.camera_matrix[5]) / K4;
     const double gb = (((K0 > K4 ? K0 : K4) / (double) s->cfg.depth_min) * (1.0 + (tx > ty ? tx : ty))) * 1.01;
     mb              = (1.7320508075688772 * gb) * 1.01;
   }

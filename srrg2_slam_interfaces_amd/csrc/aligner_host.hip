@@ -208,6 +208,12 @@ void identity(int kind, float* T) {
   }
 }
 
+// max |u - c| over the pixels u + 0.5 in [0, n) of a projected point: n while the principal point c lies in the image, more when
+// it lies outside; sizes the reprojection slice's fixed-point exponent (float operations, the same as oracle/o_aligner.c)
+float proj_extent(int n, float c) {
+  return std::fmax(std::fmax((float) n, std::fabs(c + 0.5f)), std::fabs(((float) n - 0.5f) - c));
+}
+
 int set_device(srrg2_aligner* a) {
   HIP_TRY(hipSetDevice(a->device));
   return 0;
@@ -925,8 +931,8 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     sc.finder    = s->cfg.finder;
     sc.K0        = s->cfg.camera_matrix[0];
     sc.K4        = s->cfg.camera_matrix[4];
-    sc.rows      = s->cfg.image_rows;
-    sc.cols      = s->cfg.image_cols;
+    sc.umax      = proj_extent(s->cfg.image_cols, s->cfg.camera_matrix[2]);
+    sc.vmax      = proj_extent(s->cfg.image_rows, s->cfg.camera_matrix[5]);
     sc.depth_min = s->cfg.depth_min;
     sc.pinf_bits = nullptr;
     sc.ninf_bits = nullptr;

@@ -210,7 +210,7 @@ struct SliceCtl {
   float prior_info[6];
   int finder;               // srrg2_finder_kind
   float K0, K4;             // focal lengths (projective / reprojection bounds)
-  int rows, cols;
+  float umax, vmax;         // max |u - c_x|, |v - c_y| of a projected point (reprojection bound; host: proj_extent)
   float depth_min;
   int* qcount;              // deferred-search queue counters of the slice (reset by the control kernel), or null
   int* qprobe_host;         // pinned host copy of the counters of iteration probe_it ([problem][near, far]), or null

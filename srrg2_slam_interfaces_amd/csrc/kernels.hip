@@ -4850,7 +4850,7 @@ __device__ __forceinline__ int slice_exponent(const CtlParams& C, const SliceCtl
   double mb        = plane ? (1.7320508075688772 * (double) ninf) * 1.01 : 1.01;
   if (repro) {
     const double K0 = (double) s.K0, K4 = (double) s.K4;
-    const double tx = (double) s.cols / K0, ty = (double) s.rows / K4;
+    const double tx = (double) s.umax / K0, ty = (double) s.vmax / K4;
     const double gb = (((K0 > K4 ? K0 : K4) / (double) s.depth_min) * (1.0 + (tx > ty ? tx : ty))) * 1.01;
     mb              = (1.7320508075688772 * gb) * 1.01;
   }

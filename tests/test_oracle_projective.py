@@ -2,38 +2,12 @@
 import numpy as np
 import pytest
 
+import projective_restatement as pr
 from helpers import projective_config, setup_pair
 from srrg2_slam_interfaces_amd import _abi as abi
 from srrg2_slam_interfaces_amd import synthetic as syn
 
 KIND = abi.SE3_QUAT_RIGHT
-
-
-def _numpy_projective(data, X, gate):
-    """independent numpy restatement of the finder: float32 projection, z-buffer (min depth, min index)."""
-    F = np.float32
-    K = data["K"].astype(F)
-    P = data["moving"]
-    X = X.astype(F)
-    q = np.stack([((X[i, 0] * P[:, 0] + X[i, 1] * P[:, 1]) + X[i, 2] * P[:, 2]) + X[i, 3] for i in range(3)], 1)
-    with np.errstate(all="ignore"):
-        u = (K[0, 0] * q[:, 0]) / q[:, 2] + K[0, 2]
-        v = (K[1, 1] * q[:, 1]) / q[:, 2] + K[1, 2]
-    uf, vf = u + F(0.5), v + F(0.5)
-    ok = (q[:, 2] >= F(data["depth_min"])) & (q[:, 2] <= F(data["depth_max"])) & (uf >= 0) & (uf < data["cols"]) & \
-         (vf >= 0) & (vf < data["rows"])
-    pix = np.where(ok, np.floor(vf).astype(np.int64) * data["cols"] + np.floor(uf).astype(np.int64), -1)
-    order = np.lexsort((np.arange(P.shape[0]), q[:, 2], pix))  # by pixel, then depth, then index
-    order = order[pix[order] >= 0]
-    first = np.ones(order.size, bool)
-    first[1:] = pix[order][1:] != pix[order][:-1]
-    winners = np.sort(order[first])
-    f = data["fixed"][pix[winners]]
-    dd = np.abs(f[:, 2] - q[winners, 2])
-    d = f - q[winners]
-    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
-    keep = np.isfinite(f).all(1) & (dd <= F(gate)) & (d2 <= (F(2) * F(gate)) * (F(2) * F(gate)))
-    return pix[winners][keep].astype(np.int32), winners[keep].astype(np.int32), dd[keep].astype(F)
 
 
 @pytest.mark.parametrize("guess_id", [0, 1])
@@ -44,7 +18,7 @@ def test_projective_finder_matches_numpy(oracle, guess_id):
     setup_pair(al, d, projective_config(KIND, abi.SLICE_P2PLANE, d, gate=0.05), guess)
     al.linearize_once(0)
     c = al.correspondences(0)
-    fi, mi, resp = _numpy_projective(d, guess, 0.05)
+    fi, mi, resp = pr.associate(d, guess, 0.05)  # independent restatement: float32 projection, z-buffer (min depth, min index)
     assert len(c) > 5000
     assert np.array_equal(c["fixed_idx"], fi) and np.array_equal(c["moving_idx"], mi)
     assert c["response"].tobytes() == resp.tobytes()
