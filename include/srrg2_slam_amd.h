@@ -555,9 +555,17 @@ int srrg2_scene_merge_from_aligner(srrg2_scene_h scene, srrg2_scene_h measuremen
  * Every setting gives the SAME results (indices, estimates, statistics bit for bit): the knobs choose between exact
  * strategies of the finder / reduction / control step.  A handle starts from srrg2_aligner_default_tuning() overridden
  * by the SRRG2_AMD_* environment variables, which are read ONCE, in srrg2_aligner_create (never inside compute()).
- * Negative values of the `int32_t` switches mean "automatic" (the library picks by problem size). */
+ * Negative values of the `int32_t` switches mean "automatic" (the library picks by problem size).
+ * strategy_mask holds only the SRRG2_TUNE_* bits below: each forces, on any configuration, a path the library also takes
+ * by itself on others.  srrg2_aligner_set_tuning rejects any other bit with SRRG2_E_INVALID; SRRG2_AMD_TUNE has them
+ * masked off, as the environment's other out-of-range values are clamped. */
+#define SRRG2_TUNE_PROJ_SEPARATE_LAUNCHES (1 << 17) /* projective slices in launches of their own (taken anyway for one
+                                                       projective slice, mixed slices or more than four)              */
+#define SRRG2_TUNE_INIT_LAUNCH (1 << 23) /* the k_icp_init launch in front of every compute() (taken anyway on a handle's
+                                            first compute() and wherever the prologue cannot ride in the first pass)  */
+#define SRRG2_TUNE_KNOWN_BITS (SRRG2_TUNE_PROJ_SEPARATE_LAUNCHES | SRRG2_TUNE_INIT_LAUNCH)
 typedef struct srrg2_aligner_tuning {
-  int32_t strategy_mask;        /* SRRG2_AMD_TUNE bit mask (DESIGN.md "Strategy knobs"); 0 = defaults                 */
+  int32_t strategy_mask;        /* SRRG2_AMD_TUNE: SRRG2_TUNE_* bits (DESIGN.md "Strategy knobs"); 0 = defaults       */
   int32_t queue_probe_iteration;/* SRRG2_AMD_QPROBE: iteration whose deferred-search counters decide whether the
                                    deferred-search launch is kept (default 1; -1 = never drop it)                      */
   int32_t small_max_points;     /* SRRG2_AMD_SMALL_MAX: upper limit of the clouds the one-workgroup kernel may take

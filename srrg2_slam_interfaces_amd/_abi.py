@@ -96,6 +96,12 @@ class BatchResult(C.Structure):
     ]
 
 
+# srrg2_aligner_tuning.strategy_mask: the only bits srrg2_aligner_set_tuning accepts (each forces a path the library also
+# takes by itself on other configurations)
+TUNE_PROJ_SEPARATE_LAUNCHES = 1 << 17  # projective slices in launches of their own
+TUNE_INIT_LAUNCH = 1 << 23  # the k_icp_init launch in front of every compute()
+
+
 class AlignerTuning(C.Structure):
     """srrg2_aligner_tuning: strategy knobs, every setting gives the same results (include/srrg2_slam_amd.h)"""
     _fields_ = [

@@ -93,7 +93,6 @@ struct Slice {
   // set_fixed's bounding box: written into pinned memory by the last block of k_ingest_bbox, word 8 = the sequence number polled for
   unsigned* bbox_host = nullptr; size_t bbox_host_cap = 0;
   unsigned bbox_seq = 0;
-  bool bbox_polled = false;        // the last k_ingest_bbox writes its result into bbox_host
   bool scalars_self_init = false;  // the last set_fixed's k_ingest_bbox left the scalars as the next one needs them
   DevBuf<unsigned> bbox_rows;  // [INGEST_BBOX_MAX_BLOCKS][8]: the blocks' partial results of k_ingest_bbox
   DevBuf<unsigned long long> zbuf;  // projective finder: [problem][rows*cols]
@@ -298,7 +297,7 @@ int build_grid(srrg2_aligner* a, Slice* s, float force_h = 0.f, bool have_bbox =
   }
   unsigned back[8];
   bool polled = false;
-  if (have_bbox && s->bbox_host && s->bbox_polled) {  // (set_fixed: the last block of k_ingest_bbox has left box and count in pinned memory)
+  if (have_bbox) {  // (set_fixed: the last block of k_ingest_bbox has left box and count in pinned memory)
     volatile unsigned* flag = s->bbox_host + 8;
     int spins = 0;
     polled    = true;
@@ -450,8 +449,7 @@ int ensure_lists(srrg2_aligner* a, Slice* s, long long max_entries) {
   // but this is the SECOND compute() on the cloud (or a batch), and with lists the coarser grid wins by far: 200 k points
   // 0.34 -> 0.23 ms, 400 k 0.63 -> 0.36 ms (profiles/r7h).  The grid is rebuilt once with the smallest cells that keep the
   // radius at CNL_MAX_R; if the lists do not fit even then, the fine grid comes back.  (Any grid gives the same results.)
-  if (g.rmax > CNL_MAX_R && s->nf > 0 && s->nf <= 2000000 && !(s->cfg.finder_cell_size > 0.f) &&
-      !(a->tuning.strategy_mask & (1 << 28))) {
+  if (g.rmax > CNL_MAX_R && s->nf > 0 && s->nf <= 2000000 && !(s->cfg.finder_cell_size > 0.f)) {
     const float h_fine = g.h;
     const int computes = s->grid_computes;
     const float h_list = s->cfg.finder_max_distance * 1.25f / ((float) CNL_MAX_R - 0.011f);
@@ -576,6 +574,7 @@ void tuning_from_environment(srrg2_aligner_tuning* t) {
   getf("SRRG2_AMD_CELL_TARGET", t->cell_target);
   getf("SRRG2_AMD_RMAX_CAP", t->rmax_cap);
   // (the environment bypasses srrg2_aligner_set_tuning's range check: clamp to what that check accepts)
+  t->strategy_mask &= SRRG2_TUNE_KNOWN_BITS;
   if (t->fast_points_per_thread < 0) t->fast_points_per_thread = 0;
   if (t->fast_from_iteration < 1) t->fast_from_iteration = 1;  // (iteration 0 has no previous neighbours to certify)
   if (t->msort_key_bits > 18) t->msort_key_bits = 18;
@@ -654,8 +653,7 @@ int upload_moving(srrg2_aligner* a, int si, const float* coords, int cs, const f
   // small key spaces: one workgroup per problem sorts straight from the caller's (staged) layout, with the problem
   // table read from pinned host memory (no copies, memsets or waits on the stream); the ingest-order copy of the
   // clouds, which this path does not produce, is only read by given-correspondences slices
-  const bool local_sort = !(a->tuning.strategy_mask & (1 << 22));
-  if (local_sort && kbits <= 15 && s->cfg.finder != SRRG2_FINDER_CORRESPONDENCES) {
+  if (kbits <= 15 && s->cfg.finder != SRRG2_FINDER_CORRESPONDENCES) {
     if ((rc = ensure_pinned(s->ms_probs_host, s->ms_probs_host_cap, (size_t) K))) return rc;
     if (s->ms_pending) HIP_TRY(hipStreamSynchronize(a->stream));  // (set_moving twice without a compute() in between)
     s->ms_pending = false;
@@ -830,7 +828,6 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   if (C.seq <= 0) C.seq = a->seq = 1;
   for (int k = 0; k < K; ++k) a->outs_host[k].seq = 0;  // (never a sequence number: fresh pinned memory is not zeroed)
   const srrg2_aligner_tuning& tn = a->tuning;  // (read once at create / set_tuning: no environment look-ups in compute())
-  C.tune          = tn.strategy_mask;
   C.probe_it      = tn.queue_probe_iteration;
   if (a->params.max_iterations <= C.probe_it + 3 || K > 4) C.probe_it = -1;
   // Small problems (laser scans, landmark maps) with one nearest-neighbour cue slice (plus priors): one workgroup per
@@ -859,8 +856,8 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     // (aligners whose control steps stay launches -- a prior slice next to the cue slice: a laser tracker with odometry --:
     // the one-workgroup kernel up to ~640 points; 360 beams 0.126 against 0.165 ms, 1000 beams 0.246 against 0.19 ms, r7f)
     // (round 6, late: the control wave linearises prior slices too -- wave_prior --, such aligners follow the rule of the cue-only
-    // ones; fused_control = 2 / SRRG2_AMD_TUNE bit 24: prior + cue aligners on control launches, as before)
-    const bool priors_launch = nslices > ncue && (tn.fused_control == 2 || (tn.strategy_mask & (1 << 24)) || nslices - ncue > 2);
+    // ones; fused_control = 2: prior + cue aligners on control launches, as before)
+    const bool priors_launch = nslices > ncue && (tn.fused_control == 2 || nslices - ncue > 2);
     if (small && (priors_launch || tn.fused_control == 0 || a->params.max_iterations < 2)) small = max_nm <= 640;
     if (small && !(priors_launch || tn.fused_control == 0 || a->params.max_iterations < 2)) {
       const Slice* sfc = a->slices[fc];
@@ -954,8 +951,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
       if ((rc = ensure_lists(a, s, 96LL << 20))) return rc;
       cnl[(size_t) si] = s->grid.list_R > 0 ? 1 : 0;
     }
-    const bool use_queue = s->cfg.finder == SRRG2_FINDER_NN_GATED && !(C.tune & 512) && nm_max_s >= queue_min && K <= 4 && !small &&
-                           !cnl[(size_t) si];
+    const bool use_queue = s->cfg.finder == SRRG2_FINDER_NN_GATED && nm_max_s >= queue_min && K <= 4 && !small && !cnl[(size_t) si];
     // batches: the converged pass (k_icp_step_fast) hands the points whose certificate failed to the deferred-search
     // kernel; the first iterations (k_icp_step) finish their open points themselves
     const bool fast_queue = s->cfg.finder == SRRG2_FINDER_NN_GATED && K > 4 && !small && fast_batch_queue;
@@ -1063,7 +1059,6 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
       // both z-buffers start clean; afterwards every pass resets the buffer of the next one
       HIP_TRY(hipMemsetAsync(s->zbuf.p, 0xff, (size_t) 2 * K * d.rows * d.cols * sizeof(unsigned long long), a->stream));
     }
-    d.tune            = tn.strategy_mask;
     if (a->dim == 3)
       dm::se3_inverse(s->cfg.sensor_in_robot, d.Sinv);
     else
@@ -1084,7 +1079,8 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
       if (a->slices[si]->cfg.finder != SRRG2_FINDER_PROJECTIVE) all_proj = false;
       proj_group.push_back(si);
     }
-    if (!all_proj || proj_group.size() < 2 || proj_group.size() > 4 || (C.tune & 131072)) proj_group.clear();
+    if (!all_proj || proj_group.size() < 2 || proj_group.size() > 4 || (tn.strategy_mask & SRRG2_TUNE_PROJ_SEPARATE_LAUNCHES))
+      proj_group.clear();
   }
   // ... and when they all read the SAME clouds (srrg2_aligner_share_clouds) through the same finder parameters, their
   // associations are identical: one z-buffer pass and one step launch serve all of them (k_icp_step_proj_fused)
@@ -1123,7 +1119,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   }
   const bool cues_consecutive = first_cue >= 0 && last_cue - first_cue + 1 == ncue_all;
   // (at most two prior slices: the control wave keeps their linearisations in registers until the sums are in)
-  if (prior_mask && (tn.fused_control == 2 /* cue slices only, as before: A/B */ || (C.tune & (1 << 24)) || nslices - ncue_all > 2)) fuse = false;
+  if (prior_mask && (tn.fused_control == 2 /* cue slices only, as before: A/B */ || nslices - ncue_all > 2)) fuse = false;
   const bool fuse_proj = proj_fused && (int) proj_group.size() == ncue_all && K == 1;
   fuse = fuse && cues_consecutive && (ncue_all == 1 || fuse_proj);
   // A nearest-neighbour slice WITHOUT lists (the first compute() on a fixed cloud: a tracker's frame) or with the deferred-search
@@ -1135,7 +1131,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   if (first_cue >= 0)
     for (int k = 0; k < K; ++k) nm_max_cue = std::max(nm_max_cue, all[(size_t) first_cue * K + k].nm);
   auto fast_at = [&](int slot0, int it) {  // (the choice of run_phase below)
-    return (slot0 > 0 || (it >= fast_from && it >= 1)) && !(C.tune & 4) && nm_max_cue >= fast_min;
+    return (slot0 > 0 || (it >= fast_from && it >= 1)) && nm_max_cue >= fast_min;
   };
   for (int si = 0; si < nslices && fuse; ++si) {
     const Slice* s = a->slices[si];
@@ -1151,7 +1147,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     const int fused_grid_max = a->fused_grid_max;
     const bool last_overlapped = a->computed && K == 1 && (size_t) si < a->last_nm_max.size() && a->last_nm_max[(size_t) si] > 0 &&
                                  a->last_ncorr[si] >= (int) (0.9 * a->last_nm_max[(size_t) si]);
-    if (fuse && !fuse_proj && !cnl[(size_t) si] && !(lds_tile > 0) && !split && !(C.tune & (1 << 27)) &&
+    if (fuse && !fuse_proj && !cnl[(size_t) si] && !(lds_tile > 0) && !split &&
         (!sdev[si].queue || (nm_max_cue <= fused_grid_max && last_overlapped) || fused_grid_max < 0 /* forced: tests */)) {
       sdev[si].queue  = nullptr;  // (finished inside the step kernel)
       sdev[si].qcount = nullptr;
@@ -1162,8 +1158,8 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     }
     if (fuse && !fuse_proj && !(cnl[(size_t) si] && !sdev[si].queue)) {
       fused_all = false;
-      // (worth it when converged passes follow; SRRG2_AMD_TUNE bit 27: lists or nothing, as before)
-      fuse = !split && !(C.tune & (1 << 27)) &&
+      // (worth it when converged passes follow)
+      fuse = !split &&
              (fast_at(0, a->params.max_iterations - 1) || (a->params.enable_inlier_only_runs && fast_at(a->params.max_iterations, 0)));
     }
   }
@@ -1233,8 +1229,8 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   // a k_icp_init launch in front of it (9 us of a 100 k-point compute()'s 164): a single alignment whose every pass carries its
   // control step, on the list or the fused grid kernel, whose last step is k_icp_final_wave (it leaves the slot sets zeroed: the
   // one thing of the prologue the first pass cannot do for itself), on a handle whose previous compute() ended that way.
-  // (SRRG2_AMD_TUNE bit 23: always the launch)
-  const bool final_wave = fuse && !(C.tune & (1 << 25));
+  // (SRRG2_TUNE_INIT_LAUNCH: always the launch)
+  const bool init_launch = (tn.strategy_mask & SRRG2_TUNE_INIT_LAUNCH) != 0;
   bool fold_init = false;
   InitInline fold_inl{};
   std::vector<InitBatch> fold_bat;  // (one per part of a batch)
@@ -1243,7 +1239,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   // it, over PCIe -- 32 alignments lost 50 us where the launch costs 12: 0.545 -> 0.60 ms, profiles/r10/r10f)
   int part_max = 0;
   for (int h = 0; h < nhalves; ++h) part_max = std::max(part_max, hn[h]);
-  if (fuse && !fuse_proj && fused_all && final_wave && (K == 1 || (part_max <= INIT_BATCH_MAX && cnl[(size_t) first_cue])) && first_cue >= 0 && nm_max_cue > 0 && !(C.tune & (1 << 23)) &&
+  if (fuse && !fuse_proj && fused_all && (K == 1 || (part_max <= INIT_BATCH_MAX && cnl[(size_t) first_cue])) && first_cue >= 0 && nm_max_cue > 0 && !init_launch &&
       (cnl[(size_t) first_cue] || !(lds_tile > 0)) && !a->profile) {
     const Slice* s = a->slices[first_cue];
     fold_init = s->slots_zeroed >= 3 * K && s->slots_zeroed_at == (const void*) s->partials.p;
@@ -1270,7 +1266,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     }
   }
   // (a pack of projective slices: the prologue rides in the z-buffer pass of the first iteration, k_proj_zbuf_fz_init)
-  if (fuse && fuse_proj && final_wave && K == 1 && first_cue >= 0 && nm_max_cue > 0 && !(C.tune & (1 << 23)) && !a->profile) {
+  if (fuse && fuse_proj && K == 1 && first_cue >= 0 && nm_max_cue > 0 && !init_launch && !a->profile) {
     fold_init = true;
     for (int si : proj_group) {
       const Slice* s = a->slices[si];
@@ -1363,8 +1359,8 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
       // (the last step on one wave too, k_icp_final_wave.  Round 5's version let the finalize part read the state back from memory
       // and measured SLOWER than the 256-thread kernel, which has it staged in LDS (C2 0.191 against 0.188 ms, profiles/r6a);
       // round 6, late: post and finalize run from the step's REGISTERS and the record for the host is written by the lanes of the
-      // wave, one word each, behind one system-scope fence.  SRRG2_AMD_TUNE bit 25 switches back to the 256-thread kernel)
-      if (final_wave && fuse_proj) {  // (a pack of projective slices: the same wave, the parameters from their device copy)
+      // wave, one word each, behind one system-scope fence)
+      if (fuse && fuse_proj) {  // (a pack of projective slices: the same wave, the parameters from their device copy)
         SliceDev pack[4];
         const ProblemDev* pp[4];
         for (size_t z = 0; z < proj_group.size(); ++z) {
@@ -1379,7 +1375,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
         }
         srrg2amd::launch_icp_final_wave_pack(pack, pp, (int) proj_group.size(), a->states.p, a->stats.p, a->outs_host, a->stats_host,
                                              !a->params.enable_inlier_only_runs, hstream[h]);
-      } else if (final_wave) {
+      } else if (fuse) {
         SliceDev sd          = sdev[first_cue];
         sd.prob0             = h0[h];
         sd.fc.ctl            = a->ctl_dev.p + h;
@@ -1482,7 +1478,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
           // its launch costs more than finishing a few near points inside the step kernel (queue_on, decided below).
           SliceDev sd = sdev[si];
           // (it >= 1 in the first run whatever the knob says: iteration 0 has no previous neighbours)
-          const bool fast = (slot0 > 0 || (it >= fast_from && it >= 1)) && !(C.tune & 4) && nm_max >= fast_min;
+          const bool fast = (slot0 > 0 || (it >= fast_from && it >= 1)) && nm_max >= fast_min;
           if (!queue_on[si] || (s->fast_queue_only && !fast)) {
             sd.queue  = nullptr;
             sd.qcount = nullptr;
@@ -1628,10 +1624,10 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     for (int k = 0; k < K; ++k) a->last_nm_max[(size_t) si] = std::max(a->last_nm_max[(size_t) si], all[(size_t) si * K + k].nm);
   a->records_state = 1;
   a->last_path = (fuse ? SRRG2_PATH_FUSED_CONTROL : 0) | (fuse && fused_all ? SRRG2_PATH_ALL_PASSES_FUSED : 0) |
-                 (final_wave && final_launched && !small ? SRRG2_PATH_FINAL_WAVE : 0) | (fold_init ? SRRG2_PATH_PROLOGUE_IN_PASS : 0) |
+                 (fuse && final_launched && !small ? SRRG2_PATH_FINAL_WAVE : 0) | (fold_init ? SRRG2_PATH_PROLOGUE_IN_PASS : 0) |
                  (small ? SRRG2_PATH_ONE_WORKGROUP : 0) | (fuse && prior_mask ? SRRG2_PATH_PRIORS_FUSED : 0);
   // (k_icp_final_wave has left the slot sets of its problems zeroed: the next compute() of the handle may skip the k_icp_init launch)
-  if (final_wave && final_launched && first_cue >= 0 && !small) {
+  if (fuse && final_launched && first_cue >= 0 && !small) {
     for (int si = 0; si < nslices; ++si) {  // (the one nearest-neighbour cue slice, or every slice of the projective pack)
       if (si != first_cue && !(fuse_proj && std::find(proj_group.begin(), proj_group.end(), si) != proj_group.end())) continue;
       Slice* s           = a->slices[si];
@@ -1750,6 +1746,7 @@ int srrg2_aligner_set_tuning(srrg2_aligner_h a, const srrg2_aligner_tuning* t) {
   if (t->fast_points_per_thread < 0 || t->fast_from_iteration < 1 || !(t->cell_target > 0.f) || t->msort_key_bits > 18 ||
       t->msort_key_bits < -1 || t->msort_segments < 0 || t->search_team < 0)
     return fail(SRRG2_E_INVALID, "set_tuning: value out of range");
+  if (t->strategy_mask & ~SRRG2_TUNE_KNOWN_BITS) return fail(SRRG2_E_INVALID, "set_tuning: unknown strategy_mask bit");
   a->tuning = *t;
   return 0;
 }
@@ -1942,12 +1939,10 @@ int srrg2_aligner_set_fixed(srrg2_aligner_h a, int si, const float* coords, int 
     if ((rc = s->bbox_rows.reserve((size_t) INGEST_BBOX_MAX_BLOCKS * 8))) return rc;
     if (++s->bbox_seq == 0) s->bbox_seq = 1;
     s->bbox_host[8] = 0;
-    const bool rows = !(a->tuning.strategy_mask & (1 << 21));  // (SRRG2_AMD_TUNE bit 21: atomics + a copy + a wait, as before)
     srrg2amd::launch_ingest_bbox(dsrc, sf, n, a->dim, s->fixed_raw.p, s->scalars.p + 10, s->scalars.p, s->scalars.p + 3,
-                                 (int*) (s->scalars.p + 6), a->stream, rows ? s->scalars.p + 11 : nullptr, rows ? s->bbox_host : nullptr,
-                                 s->bbox_seq, rows ? s->bbox_rows.p : nullptr, s->scalars.p + 7);
-    s->scalars_self_init = rows && n > 0;
-    s->bbox_polled       = rows;
+                                 (int*) (s->scalars.p + 6), a->stream, s->scalars.p + 11, s->bbox_host, s->bbox_seq, s->bbox_rows.p,
+                                 s->scalars.p + 7);
+    s->scalars_self_init = n > 0;
   }
   else
     srrg2amd::launch_ingest(dsrc, sf, n, a->dim, s->fixed_raw.p, s->scalars.p + 10, 1, a->stream);  // [10] = |fixed|inf

@@ -23,15 +23,6 @@
 
 #include "det_math.h"
 
-// Timing knobs (SRRG2_AMD_TUNE bits 1, 2, 8, 16, 32, 64, 128, 256, 1024, 2048) switch parts of the kernels OFF to see what
-// they cost: WRONG results, so they only exist in profiling builds (make EXTRA=-DSRRG2_TIMING_KNOBS).  The other bits
-// choose between exact strategies and stay available.
-#ifdef SRRG2_TIMING_KNOBS
-#define KNOB(t, bit) (((t) & (bit)) != 0)
-#else
-#define KNOB(t, bit) false
-#endif
-
 #include "device_util.h"
 
 // ============================================================================================
@@ -251,35 +242,6 @@ __device__ __forceinline__ void scan_radius1(const GridDev& g, float qx, float q
   }
 }
 
-// radius-2 cube (trimmed to the ball of the best candidate so far), one z-layer (5 rows) at a time: the 10 range
-// fetches of a layer are independent, so a lane pays one fetch latency per layer instead of one per row.  Re-visits
-// the radius-1 block (harmless: the minimum is idempotent).
-template <int DIM>
-__device__ __forceinline__ void scan_radius2(const GridDev& g, float qx, float qy, float qz, int cx, int cy, int cz,
-                                             float r2box, unsigned long long& bkey, float& b2) {
-  const float rr = ball_radius(r2box);
-  int x0, x1, y0, y1, z0 = 0, z1 = 0;
-  axis_range(qx, rr, g.ox, g.inv_h, cx - 2, cx + 2, g.nx, x0, x1);
-  axis_range(qy, rr, g.oy, g.inv_h, cy - 2, cy + 2, g.ny, y0, y1);
-  if (DIM == 3) axis_range(qz, rr, g.oz, g.inv_h, cz - 2, cz + 2, g.nz, z0, z1);
-  if (x0 > x1) return;
-  for (int z = z0; z <= z1; ++z) {
-    int rs[5], re[5];
-#pragma unroll
-    for (int r = 0; r < 5; ++r) {
-      const int y   = cy + r - 2;
-      const bool ok = y >= y0 && y <= y1;
-      const int row = ok ? (z * g.ny + y) * g.nx : 0;
-      rs[r] = ok ? g.cell_start[row + x0] : 0;
-      re[r] = ok ? g.cell_start[row + x1 + 1] : 0;
-    }
-#pragma unroll
-    for (int r = 0; r < 5; ++r) {
-      scan_range2<DIM>(g.pts, rs[r], re[r], qx, qy, qz, bkey, b2);
-    }
-  }
-}
-
 // The SHELL of the radius-2 cube: the cells of the 5^DIM cube that are not in the 3^DIM block (which scan_radius1 has
 // seen, trimmed to its own ball), trimmed to the ball of squared radius r2box.  Continues the running (key, runner-up)
 // pair of the first phase: every fixed point of cube ∩ ball is met exactly once over both phases.  A lane that found a
@@ -390,8 +352,7 @@ __device__ __forceinline__ long long wave_transpose_reduce(long long (&v)[ACC_N]
 // terms of w J^T J and w J^T e, and the statistics.  Returns the srrg2_factor_status of the correspondence.
 template <int D, int ROWS>
 __device__ __forceinline__ uint8_t factor_accumulate(const float (&J)[ROWS][D], const float (&e)[ROWS], bool invalid,
-                                                     int rk, float thr, double scale, bool skip_terms,
-                                                     long long (&acc)[ACC_N]) {
+                                                     int rk, float thr, double scale, long long (&acc)[ACC_N]) {
   float chi = e[0] * e[0];
 #pragma unroll
   for (int r = 1; r < ROWS; ++r) chi = chi + e[r] * e[r];
@@ -409,7 +370,7 @@ __device__ __forceinline__ uint8_t factor_accumulate(const float (&J)[ROWS][D], 
   acc[ACC_CHI_OUT] += kernelized ? chi_fx : 0;
   acc[ACC_N_IN] += kernelized ? 0 : 1;
   acc[ACC_CHI_IN] += kernelized ? 0 : chi_fx;
-  if (w != 0.f && !skip_terms) {
+  if (w != 0.f) {
     // (w * 2^k) is exact, (w * 2^k) * J is exact (24 x 24 bits); the fma rounds each product once onto the grid
     const double ws = (double) w * scale;
 #pragma unroll
@@ -942,16 +903,15 @@ __device__ __forceinline__ void finish_point(const SliceDev& S, const float* T, 
   if (inrange) {
     if (active) {
       bool found = bidx != NO_MATCH && best <= g.gate2;
-      if (KNOB(S.tune, 8)) found = false;
       // (a kept neighbour comes with its normal, loaded together with the prior: one round trip less on the chain; the
       // normal of a neighbour beyond the gate is fetched too: it is stored with the neighbour for the next iteration)
       if (!kept && bidx != NO_MATCH) bpos = g.pos_of[bidx];  // (searches do not track positions: one 4-byte gather here)
       if (bidx != NO_MATCH && (PLANE || S.use_normal_gate))
-        nf = KNOB(S.tune, 32) ? make_float4(0.f, 0.f, 1.f, 0.f) : (kept ? kept_n : g.nrm[bpos]);
+        nf = kept ? kept_n : g.nrm[bpos];
       // (with nf: one round trip, not one after the normal gate; a kept neighbour comes with its coordinates)
       if (bidx != NO_MATCH) fm = kept ? kept_f : g.pts[bpos];
       if (found && S.use_normal_gate) {
-        const float4 nm = KNOB(S.tune, 128) ? make_float4(0.f, 0.f, 1.f, 0.f) : (have_nm ? early_nm : S.mnrm[gi]);
+        const float4 nm = have_nm ? early_nm : S.mnrm[gi];
         float dot;
         if constexpr (DIM == 3) {
           float rx = (T[0] * nm.x + T[1] * nm.y) + T[2] * nm.z;
@@ -1021,7 +981,7 @@ __device__ __forceinline__ void finish_point(const SliceDev& S, const float* T, 
             J[r][2] = m[r][1] * p.x - m[r][0] * p.y;
           }
         }
-        fstat = factor_accumulate<D, ROWS>(J, e, false, rk, thr, scale, KNOB(S.tune, 64), acc);
+        fstat = factor_accumulate<D, ROWS>(J, e, false, rk, thr, scale, acc);
       }
     }
     if (!kept) {  // (a skipped search keeps its neighbour: only the exclusion radius changes)
@@ -1076,15 +1036,15 @@ __device__ __forceinline__ void icp_step_body(const SliceDev& S, const ProblemDe
   const float kk     = S.variable_kind == SRRG2_SE3_QUAT_RIGHT ? 2.f : 1.f;
   const GridDev& g   = S.grid;
   const float b2_1   = bound2_of(1, g.h);
-  const bool use_prior = sv.prior && !(S.tune & 4);
+  const bool use_prior = sv.prior;
   // open points go to the deferred-search queue, or are finished here (no queue; or the control kernel saw that the
   // queue stays nearly empty: st->qmode, mirrored by the host which then drops the deferred-search launch)
   const bool use_q = S.queue != nullptr && sv.qmode;
   // Scans of points without a neighbour inside the gate reach 25% beyond it once a prior exists: what they find (a
   // point just outside the gate, or nothing) then certifies "no match" for the following iterations without a search.
-  const float gfar = (use_prior && !(S.tune & 65536)) ? g.gate2_ext : g.gate2;
+  const float gfar = use_prior ? g.gate2_ext : g.gate2;
   // cube radius that covers the ball of radius sqrt(gfar) (both computed by the host with the same bound)
-  const int rfar = (use_prior && !(S.tune & 65536)) ? g.rmax : g.rfar_gate;
+  const int rfar = use_prior ? g.rmax : g.rfar_gate;
   float Tprev[12];  // the finder transform of the previous iteration (its queries: q' = Tprev * p)
   load_T(sv.Tprev, Tprev);
 
@@ -1144,7 +1104,7 @@ __device__ __forceinline__ void icp_step_body(const SliceDev& S, const ProblemDe
   float pad       = PAD_MIN * g.h;  // margin of the scans beyond the nearest neighbour (grows with the motion)
   __shared__ int coop_lds[NW][288];  // (64-lane scans need 264 ints, four 16-lane teams 4 x 72)
   STAMP(tl, 1);  // moving point + prior loaded
-  if (active && !KNOB(S.tune, 16)) {
+  if (active) {
     transform_point<DIM>(T, p, qx, qy, qz);
     // Temporal coherence, exactly.  The previous iteration of this compute() left, per moving point, its nearest
     // neighbour f* and an exclusion radius m: no OTHER fixed point lies within m of the previous query q'.
@@ -1162,7 +1122,7 @@ __device__ __forceinline__ void icp_step_body(const SliceDev& S, const ProblemDe
       const float ex = qx - px, ey = qy - py, ez = qz - pz;
       const float dl = sqrtf((ex * ex + ey * ey) + ez * ez);
       const float d1 = sqrtf(key_best(k1));
-      if (d1 * 1.00001f + dl * 1.00001f < pm * 0.99999f && !(S.tune & 4096)) {
+      if (d1 * 1.00001f + dl * 1.00001f < pm * 0.99999f) {
         skipped = true;
         best    = key_best(k1);
         bidx    = key_idx(k1);
@@ -1176,7 +1136,7 @@ __device__ __forceinline__ void icp_step_body(const SliceDev& S, const ProblemDe
         const float rr = (d1 + pad) * 1.00001f;
         r2box          = fminf(rr * rr, gfar);
       }
-    } else if (use_prior && !has_prev && pm > 0.f && !(S.tune & (4096 | 65536))) {
+    } else if (use_prior && !has_prev && pm > 0.f) {
       // (c) no fixed point at all within m of q' (an empty scan left m behind): if gate + |q - q'| < m there is still
       //     none within the gate of q: no match, no search
       float px, py, pz;
@@ -1196,7 +1156,7 @@ __device__ __forceinline__ void icp_step_body(const SliceDev& S, const ProblemDe
   float b2                = INFINITY;
   float complete2         = INFINITY;
   bool straggler = false;
-  if (use_q && use_prior && rfar > 1 && !KNOB(S.tune, 16) && !(S.tune & 8192)) {
+  if (use_q && use_prior && rfar > 1) {
     const bool need  = active && !skipped;
     const int n_need = __popcll(__ballot(need));
     if (need && n_need <= 8) {
@@ -1209,15 +1169,15 @@ __device__ __forceinline__ void icp_step_body(const SliceDev& S, const ProblemDe
   // before convergence only a fraction of the lanes still needs the first phase (the rest hold a certificate), and ~40 %
   // of those the second.  The lanes that need a scan leave their query in LDS; the first n threads of the workgroup each
   // take one and hand the (key, runner-up, completeness) triple back through LDS: whole waves skip the phase.
-  // (everything here is uniform over the workgroup: use_q and the tune word are per problem)
-  const bool compact = !use_q && !(S.tune & 2097152);
+  // (everything here is uniform over the workgroup: use_q is per problem)
+  const bool compact = !use_q;
   constexpr int COMPACT_MAX = NW * 48;  // above this the scan runs in place (nothing to win, two barriers to lose)
   __shared__ float4 s_q[NW * 64];
   __shared__ unsigned long long s_key[NW * 64];
   __shared__ float s_b2[NW * 64], s_c2[NW * 64];
   __shared__ int s_wq[NW * 64], s_cnt1[NW], s_cnt2[NW];
   const unsigned long long below = (1ull << lane) - 1ull;
-  const bool need1 = active && !KNOB(S.tune, 16) && !skipped && !straggler;
+  const bool need1 = active && !skipped && !straggler;
   {
     bool in_lds = false;
     int n1 = 0;
@@ -1356,8 +1316,7 @@ __device__ __forceinline__ void icp_step_body(const SliceDev& S, const ProblemDe
     // radius-2 cube per lane, then the cooperative scan for what is still open
     // the shell of the radius-2 cube, continuing the first phase's (key, runner-up) pair: both phases together have met
     // every fixed point of cube(2) within min(ball, first phase's completeness radius) exactly once
-    // (SRRG2_AMD_TUNE bit 1048576: the whole cube from scratch, as round 1 did)
-    const bool need2 = r2 > 1 && rfar >= 2 && !KNOB(S.tune, 2);
+    const bool need2 = r2 > 1 && rfar >= 2;
     {
       bool in_lds = false;
       int n2 = 0;
@@ -1402,13 +1361,7 @@ __device__ __forceinline__ void icp_step_body(const SliceDev& S, const ProblemDe
         const int wcx = cell_coord(wqx, g.ox, g.inv_h);
         const int wcy = cell_coord(wqy, g.oy, g.inv_h);
         const int wcz = DIM == 3 ? cell_coord(wqz, g.oz, g.inv_h) : 0;
-        if (S.tune & 1048576) {
-          rkey = NO_KEY;
-          rb2  = INFINITY;
-          scan_radius2<DIM>(g, wqx, wqy, wqz, wcx, wcy, wcz, wball, rkey, rb2);
-        } else {
-          scan_shell2<DIM>(g, wqx, wqy, wqz, wcx, wcy, wcz, wball, rkey, rb2);
-        }
+        scan_shell2<DIM>(g, wqx, wqy, wqz, wcx, wcy, wcz, wball, rkey, rb2);
       }
       if (in_lds) {
         __syncthreads();  // (every worker has read its item: the slots may be overwritten)
@@ -1425,7 +1378,6 @@ __device__ __forceinline__ void icp_step_body(const SliceDev& S, const ProblemDe
       if (need2) {
         bkey = rkey;
         b2   = rb2;
-        if (S.tune & 1048576) complete2 = INFINITY;
         best = key_best(bkey);
         bidx = key_idx(bkey);
         const bool found2 = bidx != NO_MATCH && best <= gfar;
@@ -1445,12 +1397,11 @@ __device__ __forceinline__ void icp_step_body(const SliceDev& S, const ProblemDe
       }
     }
     unsigned long long need = __ballot(r2 > 1);
-    if (KNOB(S.tune, 1)) need = 0;
     // Four open points per pass, a team of 16 lanes each (the cost of a cooperative scan is its fixed part -- row ranges,
     // prefix sum, two LDS round trips -- not its candidates: on the misaligned first pass of a batch a wave has a dozen
     // such points, most of them with nothing inside the gate); one 64-lane scan at a time when a single point is left.
     while (need) {
-      if (__popcll(need) == 1 || (S.tune & 524288)) {
+      if (__popcll(need) == 1) {
         const int src = __ffsll((long long) need) - 1;
         need &= need - 1;
         float wbest, wexcl2;
@@ -1462,7 +1413,7 @@ __device__ __forceinline__ void icp_step_body(const SliceDev& S, const ProblemDe
           best = wbest;
           bidx = widx;
         }
-        continue;
+        break;  // (it was the last open point)
       }
       int src[4];
 #pragma unroll
@@ -1754,7 +1705,7 @@ template <int DIM, int CAP>
 __device__ __forceinline__ void scan_radius1_tile(const GridDev& g, WaveTile<CAP>& t, const TileBox& b, int lane, float qx,
                                                   float qy, float qz, int cx, int cy, int cz, float r2box, bool want, int x0,
                                                   int x1, int y0, int y1, int z0, int z1, unsigned long long& bkey, float& b2,
-                                                  float& complete2, bool centre_only = false) {
+                                                  float& complete2) {
   constexpr int NROWS = DIM == 3 ? 9 : 3;
   constexpr int RC    = DIM == 3 ? 4 : 1;
   complete2 = r2box;
@@ -1781,7 +1732,6 @@ __device__ __forceinline__ void scan_radius1_tile(const GridDev& g, WaveTile<CAP
       complete2      = fminf(complete2, rb * rb);
     }
   }
-  if (centre_only) return;  // (timing knob)
   // the other rows: every point of a row is at least (dy, dz) away -- three slab distances per axis instead of one
   // rectangle distance per row
   const bool prune = complete2 < 3.0e38f;
@@ -1870,9 +1820,9 @@ __global__ __launch_bounds__(256) void k_icp_step_tile(SliceDev S, const Problem
   const float kk     = S.variable_kind == SRRG2_SE3_QUAT_RIGHT ? 2.f : 1.f;
   const GridDev& g   = S.grid;
   const float b2_1   = bound2_of(1, g.h);
-  const bool use_prior = (st->nstats > 0 || st->phase == 1) && !(S.tune & 4);
-  const float gfar = (use_prior && !(S.tune & 65536)) ? g.gate2_ext : g.gate2;
-  const int rfar   = (use_prior && !(S.tune & 65536)) ? g.rmax : g.rfar_gate;
+  const bool use_prior = st->nstats > 0 || st->phase == 1;
+  const float gfar = use_prior ? g.gate2_ext : g.gate2;
+  const int rfar   = use_prior ? g.rmax : g.rfar_gate;
   float Tprev[12];
   load_T(st->Tfprev[S.slice_idx], Tprev);
 
@@ -1932,7 +1882,7 @@ __global__ __launch_bounds__(256) void k_icp_step_tile(SliceDev S, const Problem
       const float ex = qx - px, ey = qy - py, ez = qz - pz;
       const float dl = sqrtf((ex * ex + ey * ey) + ez * ez);
       const float d1 = sqrtf(key_best(k1));
-      if (d1 * 1.00001f + dl * 1.00001f < pm * 0.99999f && !(S.tune & 4096)) {
+      if (d1 * 1.00001f + dl * 1.00001f < pm * 0.99999f) {
         skipped = true;
         best    = key_best(k1);
         bidx    = key_idx(k1);
@@ -1942,7 +1892,7 @@ __global__ __launch_bounds__(256) void k_icp_step_tile(SliceDev S, const Problem
         const float rr = (d1 + pad) * 1.00001f;
         r2box          = fminf(rr * rr, gfar);
       }
-    } else if (use_prior && !has_prev && pm > 0.f && !(S.tune & (4096 | 65536))) {
+    } else if (use_prior && !has_prev && pm > 0.f) {
       float px, py, pz;
       transform_point<DIM>(Tprev, p, px, py, pz);
       const float ex = qx - px, ey = qy - py, ez = qz - pz;
@@ -1959,9 +1909,7 @@ __global__ __launch_bounds__(256) void k_icp_step_tile(SliceDev S, const Problem
   unsigned long long bkey = NO_KEY;
   float b2 = INFINITY, complete2 = INFINITY;
   // ---- first phase: the 3^DIM block, trimmed to the ball
-  // (timing knobs, profiling builds only: 16 = no search, 33554432 = stage the tiles without scanning them,
-  // 67108864 = the row through the query's cell only, 2 = no shell phase, 8 = no linearisation)
-  const bool need1 = active && !skipped && !KNOB(S.tune, 16);
+  const bool need1 = active && !skipped;
   if (__any(need1)) {
     const float rr = ball_radius(r2box);
     int x0, x1, y0, y1, z0 = 0, z1 = 0;
@@ -1975,9 +1923,9 @@ __global__ __launch_bounds__(256) void k_icp_step_tile(SliceDev S, const Problem
     TILE_STAT(st->nstats, 5, tb.total);
     TILE_STAT(st->nstats, 6, tb.nyb * tb.nzb);
     TILE_STAT(st->nstats, 7, __popcll(__ballot(need1)));
-    if (tb.ok && !KNOB(S.tune, 33554432))
+    if (tb.ok)
       scan_radius1_tile<DIM, CAP>(g, wlds[wid].tile, tb, lane, qx, qy, qz, cx, cy, cz, r2box, want, x0, x1, y0, y1, z0, z1, bkey,
-                                  b2, complete2, KNOB(S.tune, 67108864));
+                                  b2, complete2);
     else if (need1)
       scan_radius1<DIM>(g, qx, qy, qz, cx, cy, cz, r2box, bkey, b2, complete2);
     if (need1) {
@@ -1999,7 +1947,7 @@ __global__ __launch_bounds__(256) void k_icp_step_tile(SliceDev S, const Problem
     }
   }
   // ---- second phase: the shell of the radius-2 cube, continuing the (key, runner-up) pair of the first
-  const bool need2 = r2 > 1 && rfar >= 2 && !KNOB(S.tune, 2);
+  const bool need2 = r2 > 1 && rfar >= 2;
   if (__any(need2)) {
     wave_lds_sync();  // (the first phase's tile is dead)
     const float rr = ball_radius(ball2);
@@ -3336,25 +3284,6 @@ __device__ __forceinline__ void point_rows(const float* T, float kk, const float
 
 }  // namespace
 
-// (experiment, -DSRRG2_NT_LOADS: the per-point arrays of the converged pass -- read once per pass, 512 MB per pass of a
-// 256-batch -- loaded non-temporally so that they do not evict the shared fixed clouds from L2 / MALL)
-template <typename T>
-__device__ __forceinline__ T ld_stream(const T* p) {
-#ifdef SRRG2_NT_LOADS
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
-__device__ __forceinline__ float4 ld_stream(const float4* p) {
-#ifdef SRRG2_NT_LOADS
-  typedef float v4f __attribute__((ext_vector_type(4)));
-  const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-  return make_float4(v.x, v.y, v.z, v.w);
-#else
-  return *p;
-#endif
-}
 // GATHER: the previous neighbour and its normal are gathered from the fixed cloud through prev_pos (batches: the cloud
 // is shared by all alignments and stays in L2; 8 instead of 36 streamed bytes per point) instead of read from prev_f / prev_n
 // (single alignments: no dependent load on the chain).
@@ -3392,13 +3321,11 @@ __device__ __forceinline__ void icp_step_fast_body(const SliceDev& S, const Prob
   const float thr    = S.robust_thr;
   const float kk     = S.variable_kind == SRRG2_SE3_QUAT_RIGHT ? 2.f : 1.f;
   const GridDev& g   = S.grid;
-  const bool ext     = !(S.tune & 65536);
-  const float gfar   = ext ? g.gate2_ext : g.gate2;
-  const int rfar     = ext ? g.rmax : g.rfar_gate;
+  const float gfar   = g.gate2_ext;
+  const int rfar     = g.rmax;
   const float gate_r = S.gate * 1.000001f;  // (>= sqrt(gate2))
   const bool ngate   = S.use_normal_gate != 0;
   const bool use_q   = !FUSED && S.queue != nullptr && st->qmode[S.slice_idx] != 0;  // (fused control steps: no queue)
-  const bool cert_a  = !(S.tune & 4096), cert_c = !(S.tune & (4096 | 65536));
   const int lane     = threadIdx.x & 63;
   const int wid      = threadIdx.x >> 6;
   // (the row tables of the cooperative grid scans -- 64-lane scans need 264 ints, four 16-lane teams 4 x 72 -- or, when the
@@ -3446,18 +3373,18 @@ __device__ __forceinline__ void icp_step_fast_body(const SliceDev& S, const Prob
     inr[k]      = i < pd.nm;
     gi_[k]      = pd.moff + (inr[k] ? i : 0);  // (out of range: the loads below read point 0 of the problem, masked out later)
     int ppos    = -1;
-    p[k]        = ld_stream(S.mpts + gi_[k]);
-    pm[k]       = ld_stream(S.prev_m + gi_[k]);
+    p[k]        = S.mpts[gi_[k]];
+    pm[k]       = S.prev_m[gi_[k]];
     pf[k]       = make_float4(0.f, 0.f, 0.f, __int_as_float(NO_MATCH));
     pn[k]       = make_float4(0.f, 0.f, 0.f, 0.f);
     pnm[k]      = make_float4(0.f, 0.f, 0.f, 0.f);
     if (GATHER) {
-      ppos = ld_stream(S.prev_pos + gi_[k]);
+      ppos = S.prev_pos[gi_[k]];
     } else {
       pf[k] = S.prev_f[gi_[k]];
       if (PLANE || ngate) pn[k] = S.prev_n[gi_[k]];
     }
-    if (ngate) pnm[k] = ld_stream(S.mnrm + gi_[k]);
+    if (ngate) pnm[k] = S.mnrm[gi_[k]];
     if (GATHER && ppos >= 0 && ppos < g.n) {
       pf[k] = g.pts[ppos];
       if (PLANE || ngate) pn[k] = g.nrm[ppos];
@@ -3593,8 +3520,8 @@ __device__ __forceinline__ void icp_step_fast_body(const SliceDev& S, const Prob
     const float rhs  = pm[k] * 0.99999f;
     // (a) of icp_step_body: d(q, f*) + |q - q'| < m  =>  f* is still the unique nearest neighbour
     // (c): nothing within m of q'; gate + |q - q'| < m  =>  still no match
-    const bool ca   = hasp && cert_a && (d1 * 1.00001f + dl * 1.00001f < rhs);
-    const bool cc   = !hasp && cert_c && pm[k] > 0.f && (gate_r * 1.00001f + dl * 1.00001f < rhs);
+    const bool ca   = hasp && (d1 * 1.00001f + dl * 1.00001f < rhs);
+    const bool cc   = !hasp && pm[k] > 0.f && (gate_r * 1.00001f + dl * 1.00001f < rhs);
     const bool have = active && (ca || cc);
     const float excl = pm[k] * 0.9999999f - dl * 1.00001f;
     const float pad  = fminf(2.f * dl, PAD_CAP * g.h) + PAD_MIN * g.h;
@@ -3807,14 +3734,14 @@ __device__ __forceinline__ void cnl_pass_body(const SliceDev& S, const GridLists
     load_T(pv.Tprev, Tprev);
     scale     = dm::pow2(pv.kexp);
     rk        = (pv.phase1 && S.robust_kind != SRRG2_ROBUST_NONE) ? (int) SRRG2_ROBUST_CLAMP : S.robust_kind;
-    use_prior = pv.prior && !(S.tune & 4);
+    use_prior = pv.prior;
   } else {
-    use_prior = S.fc.prior != 0 && !(S.tune & 4);  // (the host knows: every pass but the first of the first run)
+    use_prior = S.fc.prior != 0;  // (the host knows: every pass but the first of the first run)
   }
   const float thr    = S.robust_thr;
   const float kk     = S.variable_kind == SRRG2_SE3_QUAT_RIGHT ? 2.f : 1.f;
   const GridDev& g   = S.grid;
-  const float gfar = (use_prior && !(S.tune & 65536)) ? g.gate2_ext : g.gate2;
+  const float gfar = use_prior ? g.gate2_ext : g.gate2;
 
   __shared__ CnlWave wlds[NW];
 
@@ -3879,7 +3806,7 @@ __device__ __forceinline__ void cnl_pass_body(const SliceDev& S, const GridLists
       const float ex = qx - px, ey = qy - py, ez = qz - pz;
       const float dl = sqrtf((ex * ex + ey * ey) + ez * ez);
       const float d1 = sqrtf(key_best(k1));
-      if (d1 * 1.00001f + dl * 1.00001f < pm * 0.99999f && !(S.tune & 4096)) {
+      if (d1 * 1.00001f + dl * 1.00001f < pm * 0.99999f) {
         skipped = true;
         best    = key_best(k1);
         bidx    = key_idx(k1);
@@ -3889,7 +3816,7 @@ __device__ __forceinline__ void cnl_pass_body(const SliceDev& S, const GridLists
         const float rr  = (d1 + pad) * 1.00001f;
         r2box           = fminf(rr * rr, gfar);
       }
-    } else if (use_prior && !has_prev && pm > 0.f && !(S.tune & (4096 | 65536))) {
+    } else if (use_prior && !has_prev && pm > 0.f) {
       float px, py, pz;
       transform_point<DIM>(Tprev, p, px, py, pz);
       const float ex = qx - px, ey = qy - py, ez = qz - pz;
@@ -3900,7 +3827,7 @@ __device__ __forceinline__ void cnl_pass_body(const SliceDev& S, const GridLists
       }
     }
   }
-  const bool need = active && !skipped && !KNOB(S.tune, 16);
+  const bool need = active && !skipped;
   if constexpr (TEAM == 1 && SRRG2_CNL_REDEAL != 0) {
     // (experiment, see SRRG2_CNL_REDEAL) The queries of the workgroup are RE-DEALT between phase 0 and the header walk.  A
     // wave walks the headers as long as its longest list lasts: 6.98 steps of four headers on the first pass of C4 with
@@ -4192,15 +4119,14 @@ __global__ __launch_bounds__(256) void k_icp_step_queue(SliceDev S, const Proble
       q.i = 0; q.r2 = -1; q.best = INFINITY; q.bidx = NO_MATCH; q.bpos = 0; q.qx = q.qy = q.qz = 0.f;
       q.ball2 = 0.f; q.pad_ = 0;
       if (live) q = queue[e];
-      const bool skip = KNOB(S.tune, 2048);
       const int cx = cell_coord(q.qx, g.ox, g.inv_h);
       const int cy = cell_coord(q.qy, g.oy, g.inv_h);
       const int cz = DIM == 3 ? cell_coord(q.qz, g.oz, g.inv_h) : 0;
       float wbest, wexcl2;
       int widx, wpos;
-      coop_scan<DIM, TW>(g, lane, coop_lds[wid], q.qx, q.qy, q.qz, cx, cy, cz, (live && !skip) ? q.r2 : -1, q.ball2, wbest,
+      coop_scan<DIM, TW>(g, lane, coop_lds[wid], q.qx, q.qy, q.qz, cx, cy, cz, live ? q.r2 : -1, q.ball2, wbest,
                          widx, wpos, wexcl2);
-      const float qexcl = skip ? 0.f : sqrtf(wexcl2) * 0.99999f;
+      const float qexcl = sqrtf(wexcl2) * 0.99999f;
       if (wbest < q.best || (wbest == q.best && widx < q.bidx)) {
         q.best = wbest;
         q.bidx = widx;
@@ -4226,7 +4152,6 @@ __global__ __launch_bounds__(256) void k_icp_step_queue(SliceDev S, const Proble
   }
   for (int e = blockIdx.x * 4 + wid; e < count_far; e += W) {
     const QEntry q  = queue[pd.nm - 1 - e];
-    const bool skip = KNOB(S.tune, 1024);
     const int cx = cell_coord(q.qx, g.ox, g.inv_h);
     const int cy = cell_coord(q.qy, g.oy, g.inv_h);
     const int cz = DIM == 3 ? cell_coord(q.qz, g.oz, g.inv_h) : 0;
@@ -4234,7 +4159,7 @@ __global__ __launch_bounds__(256) void k_icp_step_queue(SliceDev S, const Proble
     int widx, wpos;
     int sr      = q.r2;
     float ball2 = q.ball2;
-    if (q.bidx == NO_MATCH && q.r2 >= 5 && !skip && !(S.tune & 262144)) {  // (small cubes: one pass is cheaper)
+    if (q.bidx == NO_MATCH && q.r2 >= 5) {  // (small cubes: one pass is cheaper)
       // Nothing is known about this point's neighbourhood and the ball is the whole gate: in a dense cloud that is
       // thousands of candidates.  Grow the cube instead (radius 2, 4, 8, ...) until something turns up, then scan once
       // more with the ball of that candidate (+ pad, for the exclusion radius).  Every pass is exact inside
@@ -4251,11 +4176,10 @@ __global__ __launch_bounds__(256) void k_icp_step_queue(SliceDev S, const Proble
         }
       }
     }
-    coop_scan<DIM, 64>(g, lane, coop_lds[wid], q.qx, q.qy, q.qz, cx, cy, cz, skip ? -1 : sr, ball2, wbest, widx, wpos,
-                       wexcl2);
+    coop_scan<DIM, 64>(g, lane, coop_lds[wid], q.qx, q.qy, q.qz, cx, cy, cz, sr, ball2, wbest, widx, wpos, wexcl2);
     if (lane == parked) {
       have    = true;
-      my_excl = skip ? 0.f : sqrtf(wexcl2) * 0.99999f;
+      my_excl = sqrtf(wexcl2) * 0.99999f;
       my_i    = q.i;
       my_best = q.best;
       my_bidx = q.bidx;
@@ -4364,7 +4288,7 @@ __global__ __launch_bounds__(256) void k_icp_step_corr(SliceDev S, const Problem
       }
     }
     // (a pair with a non-finite point gives a non-finite chi: Suppressed)
-    S.gcorr_stat[c] = factor_accumulate<D, ROWS>(J, e, false, rk, S.robust_thr, scale, false, acc);
+    S.gcorr_stat[c] = factor_accumulate<D, ROWS>(J, e, false, rk, S.robust_thr, scale, acc);
   }
   block_reduce_store<4>(acc, S.partials, prob, blockIdx.x);
 }
@@ -5005,7 +4929,7 @@ __device__ void control_body(const CtlParams& C, ProblemState* st, srrg2_iterati
     st->ncorr[s] = nc;
     good |= nc > sc.min_num_correspondences;  // aligner_slice_processor_impl.cpp:77-79
   }
-  if (!good && !KNOB(C.tune, 256)) {
+  if (!good) {
     for (int s = 0; s < C.nslices; ++s)
       if (C.slices[s].qcount) C.slices[s].qcount[2 * prob] = C.slices[s].qcount[2 * prob + 1] = 0;
     st->status = SRRG2_NOT_ENOUGH_CORRESPONDENCES;  // multi_aligner_impl.cpp:107-111
@@ -5069,26 +4993,8 @@ __device__ void control_body(const CtlParams& C, ProblemState* st, srrg2_iterati
   cur.num_correspondences = num_correspondences(C, st);
   cur.chi_inliers         = (float) chi_in;
   cur.chi_outliers        = (float) chi_out;
-  // (timing, profiling builds: bits 27..29 of the mask select how far the step runs -- 1: without the solve and
-  // everything behind it, 2: up to and including the solve, 3: + the stores of H, b, dx, 5: + box-plus, 6: + the finder
-  // transforms, 4: everything but the termination criterion and the queue bookkeeping)
-#ifdef SRRG2_TIMING_KNOBS
-  const int stage = (C.tune >> 27) & 7;
-#else
-  constexpr int stage = 0;
-#endif
-  if (stage == 1) {
-    st->nstats++;
-    st->last_H[0] = H[0] + b[0];
-    return;
-  }
   int bad                 = dm::solve<D>(H, b, dx);
   cur.solver_status       = bad ? 1 : 0;
-  if (stage == 2) {
-    st->nstats++;
-    st->last_dx[0] = dx[0] + dx[D - 1];
-    return;
-  }
 #pragma unroll
   for (int i = 0; i < D * D; ++i) st->last_H[i] = H[i];
 #pragma unroll
@@ -5096,31 +5002,18 @@ __device__ void control_body(const CtlParams& C, ProblemState* st, srrg2_iterati
     st->last_b[i]  = b[i];
     st->last_dx[i] = bad ? 0.0 : dx[i];
   }
-  if (stage == 3) {
-    st->nstats++;
-    return;
-  }
   for (int i = 0; i < 12; ++i) st->Xprev[i] = st->X[i];  // the estimate this iteration's finder passes ran with
   if (!bad) dm::box_plus(C.variable_kind, st->X, dx);  // solver Success: multi_aligner_impl.cpp:118-121
-  if (stage == 5) {
-    st->nstats++;
-    return;
-  }
   for (int s = 0; s < C.nslices; ++s) {
     if (C.slices[s].kind == SRRG2_SLICE_PRIOR) continue;
     for (int i = 0; i < 12; ++i) st->Tfprev[s][i] = st->Tf[s][i];
     if (!bad) finder_transform_of(C.slices[s].Sinv, C.variable_kind == SRRG2_SE2_RIGHT ? 2 : 3, st->X, st->Tf[s]);
-  }
-  if (stage == 6) {
-    st->nstats++;
-    return;
   }
   for (int s = 0; s < C.nslices; ++s)  // the fixed-point scale of given-correspondences slices follows the estimate
     if (C.slices[s].finder == SRRG2_FINDER_CORRESPONDENCES && C.slices[s].kind != SRRG2_SLICE_PRIOR)
       st->kexp[s] = slice_exponent(C, C.slices[s], prob, 0, st->X);
   if (st->nstats < C.max_stats) stats[(size_t) prob * C.max_stats + st->nstats] = cur;
   st->nstats++;
-  if (stage == 4) return;  // (timing: without the termination criterion and the queue bookkeeping)
   if (C.has_term && has_to_stop(C, st, cur)) st->done = 1;  // :124-126
   for (int s = 0; s < C.nslices; ++s)
     if (C.slices[s].qcount) {
@@ -5317,10 +5210,6 @@ __device__ void icp_control_block(const CtlParams& C, ProblemState* st, srrg2_it
     __syncthreads();
   }
   if (threadIdx.x != 0) return;
-  if (KNOB(C.tune, 67108864)) {  // (timing: everything but the sequential part; the iteration counter must still advance)
-    st->nstats++;
-    return;
-  }
   if (C.variable_kind == SRRG2_SE2_RIGHT)
     control_body<3>(C, st, stats, prob, sums, scaled);
   else
@@ -5594,18 +5483,16 @@ void launch_icp_step(int dim, bool plane, const SliceDev& S, const ProblemDev* p
   }
   int bx = (max_nm + 255) / 256;  // one moving point per thread
   dim3 grid(bx, K);
-  // (experiment: SRRG2_AMD_STEP_LDS = bytes of unused dynamic LDS per workgroup, to lower the occupancy on purpose)
-  static const unsigned dyn = getenv("SRRG2_AMD_STEP_LDS") ? (unsigned) atoi(getenv("SRRG2_AMD_STEP_LDS")) : 0u;
   if (dim == 3) {
     if (plane)
-      hipLaunchKernelGGL((k_icp_step<3, true>), grid, dim3(256), dyn, s, S, probs, states);
+      hipLaunchKernelGGL((k_icp_step<3, true>), grid, dim3(256), 0, s, S, probs, states);
     else
-      hipLaunchKernelGGL((k_icp_step<3, false>), grid, dim3(256), dyn, s, S, probs, states);
+      hipLaunchKernelGGL((k_icp_step<3, false>), grid, dim3(256), 0, s, S, probs, states);
   } else {
     if (plane)
-      hipLaunchKernelGGL((k_icp_step<2, true>), grid, dim3(256), dyn, s, S, probs, states);
+      hipLaunchKernelGGL((k_icp_step<2, true>), grid, dim3(256), 0, s, S, probs, states);
     else
-      hipLaunchKernelGGL((k_icp_step<2, false>), grid, dim3(256), dyn, s, S, probs, states);
+      hipLaunchKernelGGL((k_icp_step<2, false>), grid, dim3(256), 0, s, S, probs, states);
   }
   if (S.queue) launch_icp_queue(dim, plane, S, probs, states, K, max_nm, s);
 }

@@ -78,14 +78,13 @@ __global__ void k_ingest_batch(const float* __restrict__ src, int stride_floats,
 // ============================================================================================
 // grid build
 // ============================================================================================
-// SRC != nullptr (k_ingest_bbox): the points are ingested on the way -- caller layout in, float4 out, max |coordinate| of the
+// INGEST (k_ingest_bbox): the points are ingested on the way -- caller layout in, float4 out, max |coordinate| of the
 // finite points -- a fixed cloud's set_fixed in one pass over the cloud instead of two launches (round 6: a tracker sets a new
-// fixed cloud every frame, multi_tracker_impl.cpp:97-98)
+// fixed cloud every frame, multi_tracker_impl.cpp:97-98); the block's eight values go to block_out, not into atomics
 template <bool INGEST>
 __device__ __forceinline__ void bbox_body(const float* __restrict__ src, int stride_floats, int dim, float4* __restrict__ dst,
-                                          unsigned* __restrict__ maxabs_bits, const float4* __restrict__ pts, int n,
-                                          unsigned* __restrict__ mn_out, unsigned* __restrict__ mx_out, int* __restrict__ nvalid,
-                                          unsigned* __restrict__ block_out = nullptr) {
+                                          const float4* __restrict__ pts, int n, unsigned* __restrict__ mn_out,
+                                          unsigned* __restrict__ mx_out, int* __restrict__ nvalid, unsigned* __restrict__ block_out) {
   unsigned mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
   int valid = 0;
   float amax = 0.f;
@@ -134,7 +133,7 @@ __device__ __forceinline__ void bbox_body(const float* __restrict__ src, int str
     red[threadIdx.x >> 6][7] = __float_as_uint(amax);  // (non-negative floats order like their bit patterns)
   }
   __syncthreads();
-  if (block_out) {  // (k_ingest_bbox: the block's eight values for the last block to reduce -- no atomics on shared words at all)
+  if constexpr (INGEST) {  // (the block's eight values for the last block to reduce -- no atomics on shared words at all)
     if (threadIdx.x < 8) {
       const int d = threadIdx.x;
       unsigned v = red[0][d];
@@ -144,10 +143,6 @@ __device__ __forceinline__ void bbox_body(const float* __restrict__ src, int str
     return;
   }
   // (minima / maxima: the atomic only when it would move the value -- a look first, an exact filter: same-address atomics serialise)
-  if (INGEST && threadIdx.x == 7 && maxabs_bits) {
-    const unsigned v = max(max(red[0][7], red[1][7]), max(red[2][7], red[3][7]));
-    if (v != 0u && v > __hip_atomic_load(maxabs_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(maxabs_bits, v);
-  }
   if (threadIdx.x < 7) {
     const int d = threadIdx.x;
     if (d < 3) {
@@ -164,7 +159,7 @@ __device__ __forceinline__ void bbox_body(const float* __restrict__ src, int str
 }
 __global__ void k_bbox(const float4* __restrict__ pts, int n, unsigned* __restrict__ mn_out, unsigned* __restrict__ mx_out,
                        int* __restrict__ nvalid) {
-  bbox_body<false>(nullptr, 0, 3, nullptr, nullptr, pts, n, mn_out, mx_out, nvalid);
+  bbox_body<false>(nullptr, 0, 3, nullptr, pts, n, mn_out, mx_out, nvalid, nullptr);
 }
 // (ticket / host_out / seq: the LAST block to finish copies the box and the count into pinned host memory and, behind a system-scope
 // fence, the caller's sequence number -- set_fixed polls that word instead of queueing a device-to-host copy and waiting for the
@@ -175,8 +170,7 @@ __global__ void k_ingest_bbox(const float* __restrict__ src, int stride_floats, 
                               unsigned* __restrict__ block_out, unsigned* __restrict__ clear_after) {
   // (block_out: [gridDim.x][8] -- every block leaves its minima, maxima, count and max |coordinate| there instead of in 8 atomics
   // on neighbouring words: 256 blocks finishing together serialised 2 048 of them, 20 of this kernel's 24 us on a 100 k-point cloud)
-  bbox_body<true>(src, stride_floats, dim, dst, maxabs_bits, nullptr, n, mn_out, mx_out, nvalid, block_out);
-  if (!host_out || !block_out) return;
+  bbox_body<true>(src, stride_floats, dim, dst, nullptr, n, mn_out, mx_out, nvalid, block_out);
   __shared__ int last_block;
   __shared__ unsigned fin[16][8];
   // (the row was written by threads 0 .. 7: their wave releases it, thread 0 of the same wave takes the ticket behind the fence.  A
@@ -216,13 +210,13 @@ __global__ void k_ingest_bbox(const float* __restrict__ src, int stride_floats, 
     if (d < 3) mn_out[d] = r;
     else if (d < 6) mx_out[d - 3] = r;
     else if (d == 6) *nvalid = (int) r;
-    else if (maxabs_bits) *maxabs_bits = r;
+    else *maxabs_bits = r;
     if (d < 7) host_out[d] = r;
   }
   // (what the NEXT call and the kernels behind this one start from: the ticket back at zero, the normals' norm -- the word behind the
   // count, accumulated by the normals' ingest that follows on the stream -- cleared: set_fixed queues no initialising copy)
   if (threadIdx.x == 8) *ticket = 0u;
-  if (threadIdx.x == 9 && clear_after) *clear_after = 0u;
+  if (threadIdx.x == 9) *clear_after = 0u;
   if (threadIdx.x < 64) {  // (the writers' wave)
     __threadfence_system();
     if (threadIdx.x == 0) *reinterpret_cast<volatile unsigned*>(host_out + 8) = seq;
@@ -742,9 +736,6 @@ __global__ __launch_bounds__(1024) void k_msort_local(const float* __restrict__ 
   // (any monotone cell assignment gives a valid sort: the keys only order the points)
   const KeySpec ks = kspec;
   auto key_of = [&](const float4 p) -> unsigned { return key_of_point(p, ks, kbits); };
-#if defined(SRRG2_MSORT_EXPERIMENT) && SRRG2_MSORT_EXPERIMENT == 3
-  if (kbits > 0) return;  // (timing experiment: bounding box pass only)
-#endif
   // ---- pass 2: histogram
   for (int i0 = tid; i0 < pd.nm; i0 += NPT * 1024) {
     float4 q[NPT];
@@ -780,9 +771,6 @@ __global__ __launch_bounds__(1024) void k_msort_local(const float* __restrict__ 
     for (int c = wid * seg + lane; c < min((wid + 1) * seg, ncell); c += 64) hist[c] += before;
   }
   __syncthreads();
-#if defined(SRRG2_MSORT_EXPERIMENT) && SRRG2_MSORT_EXPERIMENT == 2
-  if (kbits > 0) return;  // (timing experiment: no scatter pass at all)
-#endif
   // ---- pass 3: scatter (the caller's index travels in .w; the order inside a cell does not matter: see above)
   const float* nbase = nsrc ? nsrc + (size_t) pd.moff * nsf : nullptr;
   for (int i0 = tid; i0 < pd.nm; i0 += NPT * 1024) {
@@ -803,14 +791,8 @@ __global__ __launch_bounds__(1024) void k_msort_local(const float* __restrict__ 
       if (i >= pd.nm) continue;
       const int pos = atomicAdd(&hist[key_of(q[j])], 1);
       q[j].w        = __int_as_float(seg0 + i);  // the caller's index within its problem
-#if defined(SRRG2_MSORT_EXPERIMENT) && SRRG2_MSORT_EXPERIMENT == 1
-      if (pos < 0) {  // (timing experiment: the scatter without its stores; wrong results)
-#endif
       out_pts[pd.moff + pos] = q[j];
       if (nbase) out_nrm[pd.moff + pos] = nq[j];
-#if defined(SRRG2_MSORT_EXPERIMENT) && SRRG2_MSORT_EXPERIMENT == 1
-      }
-#endif
     }
   }
 }
@@ -843,17 +825,11 @@ void launch_ingest_bbox(const float* src, int stride_floats, int n, int dim, flo
   // (with the rows: few blocks -- every block ends in ONE atomic on the ticket word, and device-scope atomics on one address cost
   // ~80 ns each: on a 100 k-point cloud 48 .. 128 blocks of 256 threads take 9.6 - 10.5 us, 1 024-thread blocks 14 - 15 us; one block
   // per 8 Ki points between 64 and INGEST_BBOX_MAX_BLOCKS, so that a cloud of millions still has its loads in flight)
-  if (ticket && host_out && block_out) {
-    const int bx  = (n + 255) / 256;
-    int cap       = n / 8192;
-    cap           = cap < 64 ? 64 : (cap > INGEST_BBOX_MAX_BLOCKS ? INGEST_BBOX_MAX_BLOCKS : cap);
-    hipLaunchKernelGGL(k_ingest_bbox, dim3(bx < cap ? bx : cap), dim3(256), 0, s, src, stride_floats, n, dim, dst, maxabs_bits, mn, mx, nvalid,
-                       ticket, host_out, seq, block_out, clear_after);
-    return;
-  }
   const int bx = (n + 255) / 256;
-  hipLaunchKernelGGL(k_ingest_bbox, dim3(bx < 256 ? bx : 256), dim3(256), 0, s, src, stride_floats, n, dim, dst, maxabs_bits, mn, mx, nvalid,
-                     nullptr, nullptr, 0u, nullptr, nullptr);
+  int cap      = n / 8192;
+  cap          = cap < 64 ? 64 : (cap > INGEST_BBOX_MAX_BLOCKS ? INGEST_BBOX_MAX_BLOCKS : cap);
+  hipLaunchKernelGGL(k_ingest_bbox, dim3(bx < cap ? bx : cap), dim3(256), 0, s, src, stride_floats, n, dim, dst, maxabs_bits, mn, mx, nvalid,
+                     ticket, host_out, seq, block_out, clear_after);
 }
 void launch_bbox(const float4* pts, int n, unsigned* mn, unsigned* mx, int* nvalid, hipStream_t s) {
   if (n <= 0) return;

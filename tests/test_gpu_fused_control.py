@@ -398,7 +398,7 @@ def test_prologue_inside_the_first_pass(oracle, product, kind, slice_kind, monke
     buffer its control steps never got to), an inlier-only run, a new initial guess, a moving cloud of another size, an EMPTY moving
     cloud (Fail: no statistics) and the compute() after it, a guess so far off that iteration 0 finds nothing, a new fixed cloud (the
     grid kernel's first pass), a prior slice that overrides the guess (cue slice at index 1), the launch path forced in between
-    (SRRG2_AMD_TUNE bit 23) -- the oracle's bits after every compute(), and the path asserted where it must be taken."""
+    (SRRG2_TUNE_INIT_LAUNCH) -- the oracle's bits after every compute(), and the path asserted where it must be taken."""
     monkeypatch.setenv("SRRG2_AMD_FUSED_GRID_MAX", "-1")
     if kind == abi.SE2_RIGHT:
         d = syn.scan_pair_2d(beams=3000, sigma=0.01, seed=1234)
@@ -459,7 +459,7 @@ def test_prologue_inside_the_first_pass(oracle, product, kind, slice_kind, monke
 
     for with_prior in (False, True):
         for knobs in ({"search_lists": 2, "fused_control": 1}, {"search_lists": 0, "fused_control": 1},
-                      {"search_lists": 2, "fused_control": 1, "strategy_mask": 1 << 23}):
+                      {"search_lists": 2, "fused_control": 1, "strategy_mask": abi.TUNE_INIT_LAUNCH}):
             ref, got = oracle.OracleAligner(kind), product.MultiAligner(kind)
             got.set_tuning(**knobs)
             forced_launch = "strategy_mask" in knobs
@@ -512,7 +512,7 @@ def test_prologue_inside_the_first_pass_of_a_small_batch(oracle, product):
         return first, second, path1, path2, third, single, al.last_compute_path()
 
     want = run(oracle.OracleAligner(kind))
-    for knobs in (FUSED, dict(FUSED, batch_pipeline=0), dict(FUSED, strategy_mask=1 << 23)):
+    for knobs in (FUSED, dict(FUSED, batch_pipeline=0), dict(FUSED, strategy_mask=abi.TUNE_INIT_LAUNCH)):
         al = product.MultiAligner(kind)
         al.set_tuning(**knobs)
         got = run(al)
@@ -529,7 +529,7 @@ def test_prologue_inside_the_first_pass_of_a_small_batch(oracle, product):
 
 
 @pytest.mark.parametrize("with_prior", [False, True])
-def test_prologue_inside_the_z_buffer_pass_of_a_projective_pack(oracle, product, with_prior):
+def test_projective_pack_prologue_in_the_z_buffer_pass(oracle, product, with_prior):
     """... and for projective slices that share one association (C3's shape): from the handle's second compute() on the z-buffer pass
     of the first iteration carries the prologue (k_proj_zbuf_fz_init), and the last step of every compute() is one wave
     (k_icp_final_wave_pack).  Three computes with different guesses, an inlier-only run, optionally a motion-model prior that overrides
@@ -564,7 +564,7 @@ def test_prologue_inside_the_z_buffer_pass_of_a_projective_pack(oracle, product,
             al.compute()
             yield (first, first + 1)
 
-    for knobs in ({"fused_control": 1}, {"fused_control": 1, "strategy_mask": 1 << 23}, {"fused_control": 1, "strategy_mask": 1 << 25}):
+    for knobs in ({"fused_control": 1}, {"fused_control": 1, "strategy_mask": abi.TUNE_INIT_LAUNCH}):
         ref, got = oracle.OracleAligner(kind), product.MultiAligner(kind)
         got.set_tuning(**knobs)
         for k, (cues, _) in enumerate(zip(script(ref), script(got))):

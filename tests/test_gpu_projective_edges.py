@@ -1,7 +1,7 @@
 """GPU: the projective path on the edges of tests/test_oracle_projective_edges.py, through every launch shape the host picks
 (one slice, a pack of 2-4 unshared slices, 2-4 slices on one shared association, 5-8 slices launched one by one, the pack
-split by SRRG2_AMD_TUNE bit 17, fused control on and off, the k_icp_init launch in front, the 256-thread final kernel,
-prior slices either side), one handle over many compute() calls, and compute_batch with a projective cue slice.
+split by SRRG2_TUNE_PROJ_SEPARATE_LAUNCHES (bit 17), fused control on and off, the k_icp_init launch in front
+(SRRG2_TUNE_INIT_LAUNCH, bit 23), prior slices either side), one handle over many compute() calls, and compute_batch with a projective cue slice.
 Every run is the oracle's bit for bit; the first iteration is the float64 restatement's."""
 import numpy as np
 import pytest
@@ -60,12 +60,11 @@ SHAPES = {
     "fused4": dict(kinds=(P, R, R, P), shared=True),
     "separate5": dict(kinds=(P, R, P, R, P), shared=False),
     "separate8": dict(kinds=(P, R) * 4, shared=True),
-    "pack3_bit17": dict(kinds=(P, R, P), shared=False, knobs={"strategy_mask": 131072}),
-    "fused2_bit17": dict(kinds=(P, R), shared=True, knobs={"strategy_mask": 131072}),
+    "pack3_bit17": dict(kinds=(P, R, P), shared=False, knobs={"strategy_mask": abi.TUNE_PROJ_SEPARATE_LAUNCHES}),
+    "fused2_bit17": dict(kinds=(P, R), shared=True, knobs={"strategy_mask": abi.TUNE_PROJ_SEPARATE_LAUNCHES}),
     "fused2_control0": dict(kinds=(P, R), shared=True, knobs={"fused_control": 0}),
     "fused2_control1": dict(kinds=(P, R), shared=True, knobs={"fused_control": 1}),
-    "fused3_bit23": dict(kinds=(P, R, P), shared=True, knobs={"fused_control": 1, "strategy_mask": 1 << 23}),
-    "fused3_bit25": dict(kinds=(P, R, P), shared=True, knobs={"fused_control": 1, "strategy_mask": 1 << 25}),
+    "fused3_bit23": dict(kinds=(P, R, P), shared=True, knobs={"fused_control": 1, "strategy_mask": abi.TUNE_INIT_LAUNCH}),
     "prior_before_fused": dict(kinds=(P, R), shared=True, prior="before"),
     "prior_after_pack": dict(kinds=(P, R), shared=False, prior="after"),
     "prior_after_fused": dict(kinds=(P, R, P), shared=True, prior="after"),
@@ -76,7 +75,8 @@ def _fused_expected(sh):
     """the host fuses the control steps into the passes of projective slices that share one association (2-4 of them)"""
     knobs = sh.get("knobs", {})
     n = len(sh["kinds"])
-    return sh["shared"] and 2 <= n <= 4 and knobs.get("fused_control", 1) != 0 and not knobs.get("strategy_mask", 0) & 131072
+    return sh["shared"] and 2 <= n <= 4 and knobs.get("fused_control", 1) != 0 and not (
+        knobs.get("strategy_mask", 0) & abi.TUNE_PROJ_SEPARATE_LAUNCHES)
 
 
 @pytest.mark.parametrize("shape", sorted(SHAPES))
@@ -121,8 +121,8 @@ def test_launch_shapes(oracle, product, shape, case):
     for k, path in enumerate(paths):
         assert bool(path & abi.PATH_FUSED_CONTROL) == fused, (shape, path)
         if fused:
-            assert bool(path & abi.PATH_FINAL_WAVE) == (not knobs.get("strategy_mask", 0) & (1 << 25)), (shape, path)
-            prologue = k > 0 and not knobs.get("strategy_mask", 0) & ((1 << 23) | (1 << 25))
+            assert path & abi.PATH_FINAL_WAVE, (shape, path)
+            prologue = k > 0 and not knobs.get("strategy_mask", 0) & abi.TUNE_INIT_LAUNCH
             assert bool(path & abi.PATH_PROLOGUE_IN_PASS) == prologue, (shape, k, path)
             assert bool(path & abi.PATH_PRIORS_FUSED) == ("prior" in sh), (shape, path)
 

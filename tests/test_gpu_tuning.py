@@ -37,6 +37,18 @@ def test_tuning_defaults_and_round_trip(product, monkeypatch):
     assert (t0.fast_from_iteration, t0.msort_key_bits) == (1, 18)
     monkeypatch.delenv("SRRG2_AMD_FAST_FROM")
     monkeypatch.delenv("SRRG2_AMD_MSORT_BITS")
+    # strategy_mask holds the two named bits only: a retired bit is rejected, and masked off when it comes from the environment
+    named = abi.TUNE_PROJ_SEPARATE_LAUNCHES | abi.TUNE_INIT_LAUNCH
+    al.set_tuning(strategy_mask=named)
+    assert al.tuning().strategy_mask == named
+    for retired in (4, 1 << 21, 1 << 25, 1 << 28):
+        with pytest.raises(RuntimeError, match="strategy_mask"):
+            al.set_tuning(strategy_mask=abi.TUNE_INIT_LAUNCH | retired)
+        assert al.tuning().strategy_mask == named
+    al.set_tuning(strategy_mask=0)
+    monkeypatch.setenv("SRRG2_AMD_TUNE", str(abi.TUNE_INIT_LAUNCH | (1 << 21) | (1 << 25)))
+    assert product.MultiAligner(abi.SE3_QUAT_RIGHT).tuning().strategy_mask == abi.TUNE_INIT_LAUNCH
+    monkeypatch.delenv("SRRG2_AMD_TUNE")
     # the environment is read once, when a handle is created
     monkeypatch.setenv("SRRG2_AMD_LDS_TILE", "0")
     assert al.tuning().lds_tile == 2
