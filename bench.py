@@ -14,13 +14,21 @@ BASELINE.json's metric has two halves and the default workload follows N:
          multi_loop_detector_brute_force_impl.cpp:64-91 -- a FIXED job of --total-alignments (256) independent 50k-point
          alignments against one query map, sharded k -> k mod N (STRONG scaling: 32 per GPU at N = 8), one
          compute_batch() per rank per step, no collective on the data path; the result records (X, statistics, H) are
-         exchanged ONCE after the timed region by an all-reduce(sum) (distributed.py).  After the timed region rank 0
-         also runs the whole job alone for a few steps, so that every line carries its own one-GPU reference.
+         exchanged ONCE after the timed region by an all-reduce(sum) (distributed.py).  With --full, rank 0 then
+         also runs the whole job alone for a few steps, so that the line carries its own one-GPU reference.
 `--workload c2|c3|c4` overrides (c4 at N = 1: --batch alignments on the one GPU).
 
 Prints ONE JSON line on rank 0.  `value` = ICP iterations/s over all ranks (`alignments_per_sec` beside it for C4);
 `ms_per_step` = wall time of one of the --steps timed steps.  --dump-outputs DIR: rank 0 writes what the last timed step
 of the headline workload computed (the result record of every alignment of the job; C5: the solved poses) as DIR/*.npy.
+
+Without --full a run does what its headline figure needs and nothing else: set up, warm up, time the steps, write the
+outputs, print the line.  --full adds everything else the line has carried: at N = 1 with no --workload the other
+configurations as nested objects (c3, c4_256, c4_32, c4_8, c4_distinct_8, c5, tracker_frame, prior_cue,
+projected_8gpu_speedup); per workload the roofline (profiled steps of its own), `long_run` / `value_long`, C2's
+`c2_fresh_fixed` and CPU baseline (--no-cpu-baseline, --no-cpu-all-cores, --cpu-seconds), C4's one-GPU reference of the
+N-rank job (--no-one-gpu-reference) and C5's warm solves and CPU baseline.  C5's `roofline` stays on the plain line:
+it is computed from the timed solves and takes no runs of its own.
 """
 import argparse
 import json
@@ -58,6 +66,9 @@ def parse():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="rank 0 writes what the last timed step computed as DIR/<name>.npy (float32 / float64), so that two "
                          "builds can be compared output for output on the same seeded inputs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the other configurations, roofline, CPU baselines, "
+                         "references (see the module docstring)")
     a = ap.parse_args()
     if a.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
@@ -307,7 +318,7 @@ def measure(args, init_dist=True):
     # the driver runs --steps 20, a 5 ms sample of C2.  `value` stays the K timed steps the contract asks for; a
     # second figure from a loop of >= 50 ms (>= 200 steps) rides beside it with its own min / median / max.
     long_run = None
-    if world == 1 and args.workload in ("c2", "c3") and args.steps < 200:
+    if args.full and world == 1 and args.workload in ("c2", "c3") and args.steps < 200:
         n_long, long_s = 200, []
         while True:
             tl0 = time.perf_counter()
@@ -346,17 +357,18 @@ def measure(args, init_dist=True):
         per_rank = [int(v) for v in cnt.cpu().tolist()]
 
     # roofline of the dominant kernel (k_icp_step): HIP events on the launch stream around every launch
-    lib = _capi.lib()
-    import ctypes as C
+    if args.full:
+        lib = _capi.lib()
+        import ctypes as C
 
-    lib.srrg2_aligner_profile_enable(al._h, 1)
-    for _ in range(max(3, min(10, args.steps))):
-        step()
-    ms, launches = C.c_double(0), C.c_int64(0)
-    lib.srrg2_aligner_profile_get(al._h, C.byref(ms), C.byref(launches), 1)
-    lib.srrg2_aligner_profile_enable(al._h, 0)
-    kern_ms = ms.value / max(launches.value, 1)
-    achieved = alg_bytes_per_launch / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
+        lib.srrg2_aligner_profile_enable(al._h, 1)
+        for _ in range(max(3, min(10, args.steps))):
+            step()
+        ms, launches = C.c_double(0), C.c_int64(0)
+        lib.srrg2_aligner_profile_get(al._h, C.byref(ms), C.byref(launches), 1)
+        lib.srrg2_aligner_profile_enable(al._h, 0)
+        kern_ms = ms.value / max(launches.value, 1)
+        achieved = alg_bytes_per_launch / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
 
     if rank != 0:
         if world > 1:
@@ -366,7 +378,7 @@ def measure(args, init_dist=True):
     # N > 1: the same job on ONE GPU (rank 0 alone, after the timed region), so that the line carries its own reference
     # for the strong-scaling ratio
     one_gpu = None
-    if world > 1 and args.workload == "c4" and not args.no_one_gpu_reference:
+    if args.full and world > 1 and args.workload == "c4" and not args.no_one_gpu_reference:
         c1, n1, o1, g1 = resident(list(range(K_total)))
         for _ in range(2):
             al.compute_batch_device(c1.data_ptr(), 12, n1.data_ptr(), 12, o1, g1)
@@ -378,24 +390,6 @@ def measure(args, init_dist=True):
         torch.cuda.synchronize()
         one_gpu = args.iterations * K_total * reps / (time.perf_counter() - t1)
 
-    # HBM-side bytes per launch of the timed kernels: PMC counters cannot be read from inside this process, so the
-    # number comes from the committed rocprofv3 --pmc passes of this same command (tools/traffic_from_pmc.py: separate
-    # FETCH_SIZE / WRITE_SIZE passes, KiB -> bytes, FETCH_SIZE doubled on gfx950 as MI355X_MICROARCH.md prescribes); only
-    # reported when the passes were taken at the default problem size of the workload
-    # reported when the passes were taken at this very problem size (C4: the same number of alignments per launch)
-    traffic, traffic_source = None, None
-    tname = "traffic_%s.json" % args.workload
-    if args.workload == "c4" and len(mine) != 32:
-        tname = "traffic_c4_%d.json" % len(mine)
-    tpath = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", tname)
-    default_size = ((args.points == 100_000 and args.overlap == 1.0) if args.workload == "c2" else
-                    (args.batch_points == 50_000) if args.workload == "c4" else True)
-    if os.path.exists(tpath) and default_size:
-        with open(tpath) as fh:
-            tj = json.load(fh)
-        if args.workload != "c4" or tj.get("alignments_per_launch", 32) == len(mine):
-            traffic = tj["bytes_per_slice_pass"]
-            traffic_source = "profiles/" + tname
     out = {
         "metric": "icp_iterations_per_sec",
         "value": total_units * args.steps / dt,
@@ -436,7 +430,26 @@ def measure(args, init_dist=True):
             "parallelism": ("alignment k on rank k mod %d, no collective on the data path; result records (X, statistics, "
                             "H) exchanged once by %s after the timed region" % (world, args.exchange)) if world > 1 else "single GPU",
         },
-        "roofline": {
+    }
+    if args.full:
+        # HBM-side bytes per launch of the timed kernels: PMC counters cannot be read from inside this process, so the
+        # number comes from the committed rocprofv3 --pmc passes of this same command (tools/traffic_from_pmc.py: separate
+        # FETCH_SIZE / WRITE_SIZE passes, KiB -> bytes, FETCH_SIZE doubled on gfx950, whose FETCH_SIZE counter reports half the fetched bytes); only
+        # reported when the passes were taken at this very problem size (C4: the same number of alignments per launch)
+        traffic, traffic_source = None, None
+        tname = "traffic_%s.json" % args.workload
+        if args.workload == "c4" and len(mine) != 32:
+            tname = "traffic_c4_%d.json" % len(mine)
+        tpath = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", tname)
+        default_size = ((args.points == 100_000 and args.overlap == 1.0) if args.workload == "c2" else
+                        (args.batch_points == 50_000) if args.workload == "c4" else True)
+        if os.path.exists(tpath) and default_size:
+            with open(tpath) as fh:
+                tj = json.load(fh)
+            if args.workload != "c4" or tj.get("alignments_per_launch", 32) == len(mine):
+                traffic = tj["bytes_per_slice_pass"]
+                traffic_source = "profiles/" + tname
+        out["roofline"] = {
             "bound": "hbm",
             "kernel": ("k_icp_step_cnl_init<3,true,4> (the first pass: compute()'s prologue inside, no k_icp_init launch) / k_icp_step_cnl<3,true,1,fused> (search passes over the cell neighbour lists) / k_icp_step_fast<3,true,1,false,fused> (converged passes): one finder+factor pass of the slice; from the second pass on the launch carries the control step of the previous iteration in its prologue (fused control steps: no control launch between passes); the last step + finalize: k_icp_final_wave" if args.workload == "c2" else
                        "k_icp_step_cnl<3,true,1,fused> (search passes over the cell neighbour lists) / k_icp_step_fast<3,true,1|2,true,fused> (converged passes): one finder+factor pass over all alignments of the launch, the control steps of the previous iteration in its first workgroups" if args.workload == "c4" else "k_proj_zbuf_fz (+ the control step of the previous iteration) + k_icp_step_proj_fused (both slices share their clouds and their association: one z-buffer pass, one step launch)"),
@@ -452,8 +465,7 @@ def measure(args, init_dist=True):
             # the HIP-event brackets above hold a launch AND the gap to the next one (a launch-bound chain: C2 is ~12 dependent
             # launches of 10-25 us); rocprofv3's kernel durations of the same command, per pass kernel, from the committed summary
             **({"rocprofv3": rocprof_pass_split(args.workload)} if args.workload in ("c2", "c3") else {}),
-        },
-    }
+        }
 
     if args.workload == "c4":
         out["alignments_per_sec"] = K_total * args.steps / dt
@@ -461,7 +473,7 @@ def measure(args, init_dist=True):
             out["one_gpu_same_job"] = {"value": one_gpu, "unit": "iterations/s",
                                        "note": "rank 0 alone runs all %d alignments per step (after the timed region)" % K_total}
             out["strong_scaling_speedup"] = out["value"] / one_gpu
-    if world == 1 and args.workload == "c2" and args.overlap == 1.0:
+    if args.full and world == 1 and args.workload == "c2" and args.overlap == 1.0:
         # `value` is the steady state of a handle that aligns many clouds against ONE fixed cloud
         # (relocalizer, loop detector: the cell neighbour lists of the fixed cloud exist from the second compute() on).  A
         # tracker binds a NEW fixed cloud every frame (multi_tracker_impl.cpp:97-105): that compute() runs on the grid
@@ -482,7 +494,7 @@ def measure(args, init_dist=True):
                                          "control steps from the first converged pass on"}
         al.set_fixed(0, data["fixed"], data["fixed_normals"])
         step(); step()  # (back to the steady state for what follows)
-    if world == 1 and not args.no_cpu_baseline and args.workload == "c2":
+    if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "c2":
         # CPU baseline = the oracle (a port: the reference cannot be built here), single
         # thread like the reference, same clouds, same iteration count; bounded sample.
         # built for THIS host's cores (-march=native) from the committed oracle sources; the
@@ -626,10 +638,11 @@ def measure_c4_distinct(iterations=10, n_align=8, points=50_000):
                                    "(set_fixed + set_moving + compute() per alignment, clouds resident in HBM)" % (n_align, points)}}
 
 
-def measure_c5(cpu_seconds=30.0, with_cpu=True, steps=3, warmup=1, dump_dir=None):
+def measure_c5(cpu_seconds=30.0, with_cpu=True, steps=3, warmup=1, dump_dir=None, with_warm=True):
     """C5: pose-graph Gauss-Newton solve, 50 000 SE(3) poses / 200 000 factors, 10 iterations, PCG tolerance 1e-6
     (MultiGraphSLAM_::optimize -> global_solver->compute(), S/system/multi_graph_slam_impl.cpp:300-317).  A step is one
-    cold solve of the same initial graph; `steps` timed solves follow `warmup` untimed ones."""
+    cold solve of the same initial graph; `steps` timed solves follow `warmup` untimed ones.  with_warm: also the solves
+    that keep the hierarchy's structure and the solve after an append (`warm`)."""
     import srrg2_slam_interfaces_amd as pkg
     from srrg2_slam_interfaces_amd import _abi as abi
     from srrg2_slam_interfaces_amd import posegraph as pgm
@@ -658,18 +671,19 @@ def measure_c5(cpu_seconds=30.0, with_cpu=True, steps=3, warmup=1, dump_dir=None
     # What MultiGraphSLAM_::optimize() does over and over (multi_graph_slam_impl.cpp:300-317): the same graph again (the
     # hierarchy's structure is kept while the topology does not change), and the graph after makeNewMap appended one
     # variable and one factor (:52-90; the structure is rebuilt: that path is not incremental yet)
-    pg.set_tuning(keep_structure=1)
-    warm = []
-    for _ in range(3):
-        pg.set_graph(g["poses_init"], g["ij"], g["Z"])
+    if with_warm:
+        pg.set_tuning(keep_structure=1)
+        warm = []
+        for _ in range(3):
+            pg.set_graph(g["poses_init"], g["ij"], g["Z"])
+            t0 = time.perf_counter()
+            pg.solve()
+            warm.append(time.perf_counter() - t0)
+        vid = pg.add_variable(g["poses_init"][-1])
+        pg.add_factor(V - 1, vid, syn.identity(3))
         t0 = time.perf_counter()
-        pg.solve()
-        warm.append(time.perf_counter() - t0)
-    vid = pg.add_variable(g["poses_init"][-1])
-    pg.add_factor(V - 1, vid, syn.identity(3))
-    t0 = time.perf_counter()
-    st_app = pg.solve()
-    t_append = time.perf_counter() - t0
+        st_app = pg.solve()
+        t_append = time.perf_counter() - t0
     # 94.8 MB per linearisation, 48.8 MB per PCG iteration (float32 spec; the solver stores float64 blocks)
     alg = 94.8e6 * len(st) + 48.8e6 * pcg
     traffic, traffic_note, dom = None, None, None
@@ -694,12 +708,14 @@ def measure_c5(cpu_seconds=30.0, with_cpu=True, steps=3, warmup=1, dump_dir=None
                                                "achieved = algorithmic bytes of the whole solve / its wall time",
                      "achieved": alg / best / 1e9, "peak": 8000.0, "unit": "GB/s", "frac": alg / best / 1e9 / 8000.0,
                      "traffic": traffic, "traffic_source": traffic_note, "algorithmic_bytes": alg, "dominant_kernel": dom},
-        "warm": {"same_topology_ms": float(np.median(warm)) * 1e3,
-                 "after_appending_one_variable_and_factor_ms": t_append * 1e3,
-                 "pcg_iterations_after_append": [s_["pcg_iterations"] for s_ in st_app],
-                 "note": "ms_per_step is the COLD solve (hierarchy structure rebuilt every time: matching on the host, sparsity patterns on the device); same_topology = "
-                         "set_graph with unchanged edges keeps the structure; an append rebuilds it"},
     }
+    if with_warm:
+        out["warm"] = {"same_topology_ms": float(np.median(warm)) * 1e3,
+                       "after_appending_one_variable_and_factor_ms": t_append * 1e3,
+                       "pcg_iterations_after_append": [s_["pcg_iterations"] for s_ in st_app],
+                       "note": "ms_per_step is the COLD solve (hierarchy structure rebuilt every time: matching on the host, sparsity "
+                               "patterns on the device); same_topology = set_graph with unchanged edges keeps the structure; an append "
+                               "rebuilds it"}
     if with_cpu:
         # CPU baseline = the oracle's solver (block-Jacobi PCG, one thread) run to CONVERGENCE on a bounded sample: the
         # first Gauss-Newton iteration of the same graph with the iteration cap lifted (the full solve is ten such)
@@ -751,7 +767,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     explicit = args.explicit_workload
     if args.workload == "c5":  # (replicas only: the pose graph does not shard)
-        r = measure_c5(with_cpu=not args.no_cpu_baseline, steps=args.steps, warmup=args.warmup, dump_dir=args.dump_outputs)
+        r = measure_c5(with_cpu=args.full and not args.no_cpu_baseline, steps=args.steps, warmup=args.warmup,
+                       dump_dir=args.dump_outputs, with_warm=args.full)
         line = {"metric": "posegraph_gauss_newton_iterations_per_sec", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic"}
         line.update(r)
@@ -760,9 +777,9 @@ def main():
     out = measure(args)
     if out is None:
         return
-    if world == 1 and not explicit:
-        # the default line: C2 is `value`; every other BASELINE configuration rides along as a nested object with its own
-        # value / ms_per_step / roofline, measured in this same process
+    if args.full and world == 1 and not explicit:
+        # the default --full line: C2 is `value`; every other BASELINE configuration rides along as a nested object with its
+        # own value / ms_per_step / roofline, measured in this same process
         import copy
 
         def nested(workload, **over):

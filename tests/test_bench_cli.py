@@ -99,3 +99,48 @@ def test_dump_outputs_holds_the_last_timed_step(tmp_path):
     assert got["chi_inliers"].tobytes() == res.last["chi_inliers"].astype(np.float32).tobytes()
     H = np.asarray(res.information, np.float32)
     assert np.array_equal(got["information"], np.triu(H) + np.transpose(np.triu(H, 1), (0, 2, 1)))
+
+
+def _one_line(args, env=None):
+    out = subprocess.run(args, capture_output=True, text=True, timeout=600, env=env or _env(), cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    return json.loads(lines[0])
+
+
+def test_full_reaches_every_rank():
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--steps", "3", "--warmup", "1", "--full", "--print-launch"],
+                         capture_output=True, text=True, timeout=120, env=_env(), cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    cmd = json.loads(out.stdout.strip().splitlines()[-1])["launch"]
+    assert cmd[cmd.index(BENCH) + 1:] == ["--gpus", "4", "--steps", "3", "--warmup", "1", "--full"]
+
+
+@pytest.mark.gpu
+def test_plain_run_measures_the_headline_alone_and_full_the_rest():
+    """`bench.py --gpus 1 --steps K --warmup W` (no --workload: C2) prints the headline and nothing that takes runs of its
+    own; --full adds the long run, the profiled roofline, the fresh-fixed-cloud figure and the CPU baseline (small clouds)"""
+    plain = _one_line([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--points", "8000"])
+    assert set(plain) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "step_ms_min_median_max",
+                          "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"}
+    assert plain["metric"] == "icp_iterations_per_sec" and plain["unit"] == "iterations/s" and plain["dtype"] == "f32"
+    assert plain["higher_is_better"] is True and plain["steps"] == 3 and plain["warmup"] == 1
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["config"]["all_success"] is True
+    full = _one_line([sys.executable, BENCH, "--gpus", "1", "--workload", "c2", "--steps", "3", "--warmup", "1", "--points", "8000",
+                      "--full", "--cpu-seconds", "1", "--no-cpu-all-cores"])
+    assert set(plain) <= set(full)
+    assert full["long_run"]["steps"] >= 200 and full["value_long"] > 0
+    assert full["roofline"]["launches_timed"] > 0 and full["roofline"]["achieved"] > 0
+    assert full["c2_fresh_fixed"]["ms_per_step"] > 0
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["parity_indices_bit_exact_and_X_within_1e-5"] is True
+
+
+@pytest.mark.gpu
+def test_full_multi_rank_run_carries_the_one_gpu_reference():
+    """--full at N > 1 (two ranks on device 0 over gloo, the dry-run hook): rank 0 runs the whole job alone after the timed
+    region, and the line carries that reference and the strong-scaling ratio"""
+    rec = _one_line([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--total-alignments", "8",
+                     "--batch-points", "8000", "--full"], env=_env(SRRG2_BENCH_SHARE_GPU="1"))
+    assert rec["n_gpus"] == 2 and rec["config"]["all_success"] is True and rec["roofline"]["launches_timed"] > 0
+    assert rec["one_gpu_same_job"]["value"] > 0 and rec["strong_scaling_speedup"] > 0

@@ -9,8 +9,8 @@ d=json.loads(sys.stdin.read()); print('%-10s %-6s value %.0f  ms_per_step %.4f  
 for r in $(seq $REPS); do
   for which in base alt; do
     if [ $which = alt ]; then export SRRG2_AMD_LIB=$R/$ALT; else unset SRRG2_AMD_LIB; fi
-    python $R/bench.py --workload c4 --batch 256 --no-cpu-baseline 2>/dev/null | line c4_256 $which | tee -a $O/ab.txt
-    python $R/bench.py --workload c4 --no-cpu-baseline 2>/dev/null | line c4_32 $which | tee -a $O/ab.txt
-    python $R/bench.py --workload c2 --no-cpu-baseline 2>/dev/null | line c2 $which | tee -a $O/ab.txt
+    python $R/bench.py --full --workload c4 --batch 256 --no-cpu-baseline 2>/dev/null | line c4_256 $which | tee -a $O/ab.txt
+    python $R/bench.py --full --workload c4 --no-cpu-baseline 2>/dev/null | line c4_32 $which | tee -a $O/ab.txt
+    python $R/bench.py --full --workload c2 --no-cpu-baseline 2>/dev/null | line c2 $which | tee -a $O/ab.txt
   done
 done
