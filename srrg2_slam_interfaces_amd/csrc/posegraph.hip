@@ -3214,6 +3214,7 @@ int pg_solve_t(srrg2_posegraph_s* g, const srrg2_posegraph_params* p, srrg2_pose
         // 2: factor and L^-1 in LDS (row-sweep inverse); 1: factor in LDS; 0: everything in global memory
         const int in_lds = !lds_ok ? 0 : (2 * lds_need <= 150 * 1024 ? 2 : (lds_need <= 150 * 1024 ? 1 : 0));
         if (!lds_ok) (void) hipGetLastError();
+        if (g->sw.debug) std::fprintf(stderr, "posegraph: coarsest inverse of %zu unknowns, in_lds %d\n", Nc, in_lds);
         hipLaunchKernelGGL(k_mg_coarsest_inverse<D>, dim3(1), dim3(1024), (size_t) in_lds * lds_need, g->stream, pair(nl),
                            g->coarse_A.p, g->coarse_inv.p, g->sc.p, in_lds);
       }
