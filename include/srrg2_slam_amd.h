@@ -307,6 +307,35 @@ int srrg2_aligner_compute_batch_correspondences(srrg2_aligner_h h, int K, const 
                                                 const int32_t* corr_offsets, const float* guesses,
                                                 srrg2_batch_result* results);
 
+/* K independent alignments, alignment k = fixed cloud k against moving cloud k, in one call.  Result k is bit for bit
+ * what a handle with the same slices, params, termination and tuning returns from
+ *   set_fixed(0, F_k, NF_k); set_moving(0, M_k, NM_k); set_moving_in_fixed(G_k); compute()
+ * (the all-distinct C4 variant: closure hints between arbitrary pairs of local maps).  Fixed and moving
+ * clouds are given concatenated with offsets[K+1] (in points) each, normals optional (null: none), all in host memory or all
+ * in device memory (`mem`: SRRG2_MEM_HOST | SRRG2_MEM_DEVICE).  Each fixed cloud gets a search grid of its own, built with
+ * those of the other pairs; nothing of a pair but its bounding-box row goes through the host.
+ *   supported    slice 0 is the one cue slice: SRRG2_FINDER_NN_GATED, kind P2P or P2PLANE; prior slices may sit beside it
+ *                (with the handle's prior measurement, as in compute_batch); SE2_RIGHT, SE3_EULER_RIGHT, SE3_QUAT_RIGHT.
+ *   refused      SRRG2_E_UNSUPPORTED: projective, reprojection or given-correspondence slices, more than one cue slice, a
+ *                handle with set_point_shard.  SRRG2_E_INVALID, the handle unchanged: K < 0 or K > 65535, decreasing
+ *                offsets, null pointers where points exist, bad strides, SRRG2_MEM_DEVICE_KEPT, grids of more than 2^31
+ *                cells in all (checked from the fixed clouds' boxes, before the moving clouds are bound).  SRRG2_E_STATE: a
+ *                point-to-plane slice without fixed normals, a prior slice without measurement.  K = 0 returns 0.
+ *   returns      after it has finished reading the caller's buffers, on success and on error (as compute_batch).
+ *   handle after status, estimate, iteration stats and information are those of pair K-1 (as after compute_batch).  The
+ *                moving cloud of slice 0 is unbound: a plain compute() needs set_moving first (SRRG2_E_STATE otherwise).
+ *                get_correspondences / get_factor_status of the cue slice return SRRG2_E_STATE until the next compute():
+ *                pair records are not kept.  The slice's OWN fixed cloud, its grid and its neighbour lists are untouched
+ *                (pairs use buffers of their own): a loop detector may interleave compute_batch against its bound map with
+ *                pair calls. */
+int srrg2_align_pairs(srrg2_aligner_h h, int K,
+                      const float* fixed_coords, int fixed_stride_bytes,
+                      const float* fixed_normals, int fixed_normal_stride_bytes, const int32_t* fixed_offsets /* K+1 */,
+                      const float* moving_coords, int moving_stride_bytes,
+                      const float* moving_normals, int moving_normal_stride_bytes, const int32_t* moving_offsets /* K+1 */,
+                      int mem /* SRRG2_MEM_HOST | SRRG2_MEM_DEVICE */, const float* guesses /* K x 12 (or 9) */,
+                      srrg2_batch_result* results);
+
 /* ---- multi-GPU (no reference counterpart) ------------------------------------------
  * Loop-closure candidate alignments are independent: alignment k of K lives on rank k mod G, one process per GPU, one
  * aligner handle per process on its own device; there is no exchange while the alignments run.  The library does not

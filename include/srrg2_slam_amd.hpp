@@ -192,6 +192,46 @@ public:
                                         offsets.data(), SRRG2_MEM_HOST, g.data(), results.data()));
     return results;
   }
+  // K independent alignments, pair k = fixed cloud k against moving cloud k (srrg2_align_pairs): what K x { setFixed;
+  // setMoving; setMovingInFixed; compute() } returns, in one call, the slice's own fixed cloud untouched.
+  // fixed / moving: K pointers to packed Dim-float records with their sizes; normals may be empty (none) or K pointers.
+  std::vector<srrg2_batch_result> computeBatchPairs(const std::vector<const float*>& fixed, const std::vector<int>& fixed_sizes,
+                                                    const std::vector<const float*>& fixed_normals,
+                                                    const std::vector<const float*>& moving, const std::vector<int>& moving_sizes,
+                                                    const std::vector<const float*>& moving_normals,
+                                                    const std::vector<EstimateType>& guesses) {
+    const int K = (int) fixed.size();
+    if ((int) fixed_sizes.size() != K || (int) moving.size() != K || (int) moving_sizes.size() != K || (int) guesses.size() != K ||
+        (!fixed_normals.empty() && (int) fixed_normals.size() != K) || (!moving_normals.empty() && (int) moving_normals.size() != K))
+      throw std::runtime_error("MultiAligner_::computeBatchPairs|inconsistent argument sizes");
+    auto pack = [K](const std::vector<const float*>& clouds, const std::vector<const float*>& normals, const std::vector<int>& sizes,
+                    std::vector<int32_t>& offsets, std::vector<float>& coords, std::vector<float>& nrm) {
+      offsets.assign((size_t) K + 1, 0);
+      for (int k = 0; k < K; ++k) offsets[(size_t) k + 1] = offsets[(size_t) k] + sizes[(size_t) k];
+      coords.resize((size_t) offsets[(size_t) K] * Dim);
+      if (!normals.empty()) nrm.resize(coords.size());
+      for (int k = 0; k < K; ++k) {
+        const size_t off = (size_t) offsets[(size_t) k] * Dim, bytes = sizeof(float) * (size_t) sizes[(size_t) k] * Dim;
+        if (bytes) std::memcpy(coords.data() + off, clouds[(size_t) k], bytes);
+        if (bytes && !normals.empty()) std::memcpy(nrm.data() + off, normals[(size_t) k], bytes);
+      }
+    };
+    std::vector<int32_t> foff, moff;
+    std::vector<float> fc, fn, mc, mn;
+    pack(fixed, fixed_normals, fixed_sizes, foff, fc, fn);
+    pack(moving, moving_normals, moving_sizes, moff, mc, mn);
+    std::vector<float> g((size_t) K * EstimateType::N);
+    for (int k = 0; k < K; ++k) std::memcpy(g.data() + (size_t) k * EstimateType::N, guesses[(size_t) k].data(), sizeof(float) * EstimateType::N);
+    srrg2_aligner_params p{param_max_iterations, param_min_num_inliers, param_enable_inlier_only_runs ? 1 : 0,
+                           param_keep_only_inlier_correspondences ? 1 : 0};
+    check(srrg2_aligner_set_params(_h, &p));
+    std::vector<srrg2_batch_result> results((size_t) K);
+    if (K)
+      check(srrg2_align_pairs(_h, K, fc.data(), Dim * 4, fixed_normals.empty() ? nullptr : fn.data(), Dim * 4, foff.data(), mc.data(),
+                              Dim * 4, moving_normals.empty() ? nullptr : mn.data(), Dim * 4, moff.data(), SRRG2_MEM_HOST, g.data(),
+                              results.data()));
+    return results;
+  }
   // slice `slice` reads the clouds of slice `source` (two slices with the same fixed_slice_name / moving_slice_name bind to
   // the same clouds of the scene: aligner_slice_processor_base_impl.cpp:27-50); -1: clouds of its own again
   void shareClouds(int slice, int source) { check(srrg2_aligner_share_clouds(_h, slice, source)); }

@@ -428,3 +428,92 @@ class MultiAligner:
                                                 offsets.ctypes.data_as(C.POINTER(C.c_int32)),
                                                 C.c_int(abi.MEM_HOST), _fptr(g), res))
         return self._unpack_batch(res, K)
+
+    # -- pair batches (srrg2_align_pairs) ---------------------------------------------
+    def _pairs_fn(self):
+        """the library's pair-batch entry point, or None on a backend without it (the oracle binding)"""
+        if self._b.prefix != "srrg2_aligner_":
+            return None
+        try:
+            return self._b.lib.srrg2_align_pairs
+        except AttributeError:
+            return None
+
+    def _pairs_loop(self, fixed_clouds, moving_clouds, guesses, fixed_normals, moving_normals):
+        """the defining loop of a pair batch: set_fixed / set_moving / set_moving_in_fixed / compute() per pair (leaves the
+        last pair's clouds bound, as any such loop does)"""
+        K = len(fixed_clouds)
+        g = _as_f32(np.asarray(guesses)).reshape(K, self.tsize)
+        res = (abi.BatchResult * max(K, 1))()
+        D = 3 if self.dim == 2 else 6
+        for k in range(K):
+            self.set_fixed(0, np.asarray(fixed_clouds[k]).reshape(-1, self.dim),
+                           None if fixed_normals is None else np.asarray(fixed_normals[k]).reshape(-1, self.dim))
+            self.set_moving(0, np.asarray(moving_clouds[k]).reshape(-1, self.dim),
+                            None if moving_normals is None else np.asarray(moving_normals[k]).reshape(-1, self.dim))
+            self.set_moving_in_fixed(g[k])
+            r = res[k]
+            r.status = self.compute()
+            r.moving_in_fixed[:self.tsize] = self.moving_in_fixed().reshape(-1).tolist()
+            n = C.c_int(0)
+            self._check(self._b.fn("get_iteration_stats")(self._h, None, C.byref(n)))
+            r.num_iterations = n.value
+            if n.value > 0:
+                buf = (abi.IterationStats * n.value)()
+                self._check(self._b.fn("get_iteration_stats")(self._h, buf, C.byref(n)))
+                r.last = buf[n.value - 1]
+            r.num_correspondences = self.num_correspondences()
+            r.information[:D * D] = self.information().reshape(-1).tolist()
+        return self._unpack_batch(res, K)
+
+    def compute_batch_pairs(self, fixed_clouds, moving_clouds, guesses, fixed_normals=None, moving_normals=None):
+        """K independent alignments, fixed cloud k against moving cloud k (srrg2_align_pairs): bit for bit what
+        K x {set_fixed; set_moving; set_moving_in_fixed; compute()} returns, in one call; the slice's own fixed cloud stays bound.
+        On a backend without the entry point (the oracle) it runs that loop."""
+        K = len(fixed_clouds)
+        if len(moving_clouds) != K:
+            raise ValueError("compute_batch_pairs: %d fixed and %d moving clouds" % (K, len(moving_clouds)))
+        f = self._pairs_fn()
+        if f is None:
+            return self._pairs_loop(fixed_clouds, moving_clouds, guesses, fixed_normals, moving_normals)
+
+        def packed(clouds):
+            offsets = np.zeros(K + 1, dtype=np.int32)
+            offsets[1:] = np.cumsum([int(np.asarray(c).shape[0]) for c in clouds])
+            arr = (_as_f32(np.concatenate([_as_f32(c).reshape(-1, self.dim) for c in clouds], axis=0)) if K
+                   else np.zeros((0, self.dim), np.float32))
+            return arr, offsets
+
+        fc, foff = packed(fixed_clouds)
+        mc, moff = packed(moving_clouds)
+        fn = packed(fixed_normals)[0] if fixed_normals is not None else None
+        mn = packed(moving_normals)[0] if moving_normals is not None else None
+        g = _as_f32(np.asarray(guesses)).reshape(K, self.tsize)
+        res = (abi.BatchResult * max(K, 1))()
+        i32 = C.POINTER(C.c_int32)
+        self._check(f(self._h, C.c_int(K), _fptr(fc), C.c_int(self.dim * 4),
+                      _fptr(fn) if fn is not None else None, C.c_int(self.dim * 4), foff.ctypes.data_as(i32),
+                      _fptr(mc), C.c_int(self.dim * 4), _fptr(mn) if mn is not None else None, C.c_int(self.dim * 4),
+                      moff.ctypes.data_as(i32), C.c_int(abi.MEM_HOST), _fptr(g), res))
+        return self._unpack_batch(res, K)
+
+    def compute_batch_pairs_device(self, fixed_ptr, fixed_stride, fixed_normals_ptr, fixed_normal_stride, fixed_offsets,
+                                   moving_ptr, moving_stride, moving_normals_ptr, moving_normal_stride, moving_offsets, guesses):
+        """compute_batch_pairs on clouds already resident in HBM (raw device pointers as ints, strides in bytes, offsets[K+1]
+        in points)."""
+        f = self._pairs_fn()
+        if f is None:
+            raise RuntimeError("compute_batch_pairs_device: the backend has no srrg2_align_pairs")
+        foff = np.ascontiguousarray(fixed_offsets, dtype=np.int32)
+        moff = np.ascontiguousarray(moving_offsets, dtype=np.int32)
+        K = foff.size - 1
+        g = _as_f32(np.asarray(guesses)).reshape(K, self.tsize)
+        res = (abi.BatchResult * max(K, 1))()
+        fp = C.POINTER(C.c_float)
+        i32 = C.POINTER(C.c_int32)
+        self._check(f(self._h, C.c_int(K), C.cast(fixed_ptr, fp), C.c_int(fixed_stride),
+                      C.cast(fixed_normals_ptr, fp) if fixed_normals_ptr else None, C.c_int(fixed_normal_stride),
+                      foff.ctypes.data_as(i32), C.cast(moving_ptr, fp), C.c_int(moving_stride),
+                      C.cast(moving_normals_ptr, fp) if moving_normals_ptr else None, C.c_int(moving_normal_stride),
+                      moff.ctypes.data_as(i32), C.c_int(abi.MEM_DEVICE), _fptr(g), res))
+        return self._unpack_batch(res, K)

@@ -163,6 +163,19 @@ struct srrg2_aligner_s {
   DevBuf<unsigned> pub_epoch;
   DevBuf<CtlParams> ctl_dev;
   DevBuf<char> staging;  // raw strided input staged on the device
+  // pair batches (srrg2_align_pairs): the K fixed clouds of the last call and their grids (GridDev table + the concatenated arrays
+  // its records point into), in buffers of their own -- the slices' fixed clouds, grids and lists stay as they are
+  DevBuf<float4> pair_raw, pair_nrm_raw, pair_sorted, pair_nrm_sorted;
+  DevBuf<int> pair_cell_start, pair_cursor, pair_scan_sums, pair_pos_of;
+  DevBuf<unsigned> pair_rows;      // [K][PAIR_ROW_WORDS]: box, finite points, normals' norm per pair (k_pairs_ingest)
+  DevBuf<ProblemDev> pair_fprobs;  // [K] {offset, count} of the fixed clouds
+  DevBuf<GridDev> pair_grids;      // [K]
+  DevBuf<char> pair_staging;       // the fixed clouds staged (host input; the moving ones use `staging`)
+  unsigned* pair_rows_host = nullptr; size_t pair_rows_host_cap = 0;  // pinned: the rows, read back once per call
+  ProblemDev* pair_fprobs_host = nullptr; size_t pair_fprobs_host_cap = 0;
+  GridDev* pair_grids_host = nullptr; size_t pair_grids_host_cap = 0;
+  bool pair_normals  = false;         // the fixed clouds of the pair batch at hand have normals
+  bool pairs_computed = false;        // the last compute was a pair batch: it left no correspondence records
   // pinned host mirrors
   ProblemOut* outs_host = nullptr; size_t outs_host_cap = 0;
   int seq = 0;  // sequence number of the last compute() (completion flags in outs_host)
@@ -241,9 +254,10 @@ int ensure_pinned(T*& p, size_t& cap, size_t n) {
 // stage `n` records of `dim` floats, `stride_bytes` apart, from host or device memory; returns a device
 // pointer to floats and the stride in floats
 int stage_input(srrg2_aligner* a, const float* src, int stride_bytes, int n, int dim, int mem, const float** dev_ptr,
-                int* stride_floats, size_t staging_offset) {
+                int* stride_floats, size_t staging_offset, DevBuf<char>* staging = nullptr) {
+  DevBuf<char>& stg = staging ? *staging : a->staging;
   if (n <= 0) {
-    *dev_ptr       = (const float*) a->staging.p;
+    *dev_ptr       = (const float*) stg.p;
     *stride_floats = dim;
     return 0;
   }
@@ -254,7 +268,7 @@ int stage_input(srrg2_aligner* a, const float* src, int stride_bytes, int n, int
     return 0;
   }
   if (mem != SRRG2_MEM_HOST) return fail(SRRG2_E_INVALID, "bad mem kind");
-  char* dst = a->staging.p + staging_offset;
+  char* dst = stg.p + staging_offset;
   if (stride_bytes == dim * 4) {
     HIP_TRY(hipMemcpyAsync(dst, src, (size_t) n * dim * 4, hipMemcpyHostToDevice, a->stream));
   } else {
@@ -432,6 +446,79 @@ int build_grid(srrg2_aligner* a, Slice* s, float force_h = 0.f, bool have_bbox =
   g.pos_of     = s->pos_of.p;
   HIP_TRY(hipGetLastError());
   return 0;
+}
+
+// The grid of one fixed cloud of a pair batch (srrg2_align_pairs), from its row (PAIR_ROW_WORDS: box, finite points): build_grid's
+// rules without the occupancy probe and with a cap that suits many small grids -- <= 2048 cells per axis and <= max(16 n, 4096)
+// cells (build_grid's floor of 4 Mi cells would cost 16 MB of cell starts per pair).  The automatic cell size is a density rule
+// instead of a probe: ~cell_target points per occupied cell of a surface (a curve in 2-D) whose area is taken as half the box's
+// surface (its length as half the box's perimeter), in [gate / 8, gate].  Results do not depend on h: the rule
+// only decides speed.  Returns the cells of the grid (the cell starts it needs: ncell + 1).
+long long pair_grid_of(const srrg2_aligner* a, const Slice* s, const unsigned* row, int n, GridDev& g) {
+  const int nvalid = (int) row[6];
+  const int dim    = a->dim;
+  float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
+  if (nvalid > 0) {
+    for (int d = 0; d < 3; ++d) {
+      mn[d] = key_to_float(~row[d]);
+      mx[d] = key_to_float(row[3 + d]);
+    }
+  }
+  const float gate      = s->cfg.finder_max_distance;
+  const double cell_cap = std::max(4096.0, 16.0 * (double) n);
+  auto fit_cell = [&](float h0) {
+    float h = h0 > 0.f ? h0 : 1.f;
+    for (;;) {
+      double cells = 1.0;
+      bool ok      = true;
+      for (int d = 0; d < dim; ++d) {
+        double nd = std::floor(((double) mx[d] - (double) mn[d]) / (double) h) + 1.0;
+        if (nd > 2048.0) ok = false;
+        cells *= nd;
+      }
+      if (ok && cells <= cell_cap) return h;
+      h *= 1.25f;
+    }
+  };
+  float h0 = s->cfg.finder_cell_size > 0.f ? s->cfg.finder_cell_size : gate * 0.25f;
+  if (!(s->cfg.finder_cell_size > 0.f) && nvalid > 0) {
+    const double target = a->tuning.cell_target > 0.f ? (double) a->tuning.cell_target : 8.0;
+    double e[3] = {0, 0, 0};
+    for (int d = 0; d < dim; ++d) e[d] = std::max((double) mx[d] - (double) mn[d], 0.0);
+    const double hd = dim == 3 ? std::sqrt(target * (e[0] * e[1] + e[1] * e[2] + e[0] * e[2]) / (double) nvalid)
+                               : target * (e[0] + e[1]) / (double) nvalid;
+    const float hh = (float) hd;
+    if (std::isfinite(hh) && hh > 0.f) h0 = std::fmin(std::fmax(hh, gate * 0.125f), gate);
+    // (2-D: the cube that covers the extended gate at radius <= 3, as build_grid)
+    float rcap = dim == 2 ? 3.f : 0.f;
+    if (a->tuning.rmax_cap > 0.f) rcap = a->tuning.rmax_cap;
+    if (rcap > 1.f) h0 = std::fmax(h0, gate * 1.25f / (rcap - 0.011f));
+  }
+  const float h = fit_cell(h0);
+  g = GridDev{};
+  g.ox = mn[0]; g.oy = mn[1]; g.oz = dim == 3 ? mn[2] : 0.f;
+  g.h     = h;
+  g.inv_h = 1.0f / h;
+  auto ccoord = [&](float x, float o) {
+    float u = (x - o) * g.inv_h;
+    u       = std::fmin(std::fmax(u, -2048.f), 4096.f);
+    return (int) std::floor(u);
+  };
+  g.nx = nvalid > 0 ? ccoord(mx[0], g.ox) + 1 : 1;
+  g.ny = nvalid > 0 ? ccoord(mx[1], g.oy) + 1 : 1;
+  g.nz = (nvalid > 0 && dim == 3) ? ccoord(mx[2], g.oz) + 1 : 1;
+  g.gate2     = gate * gate;
+  g.gate2_ext = (gate * 1.25f) * (gate * 1.25f);
+  g.n         = n;
+  int r       = 1;
+  while (bound2_of_host(r, h) < g.gate2_ext && r < 4096) ++r;
+  g.rmax          = r;
+  int rg          = 1;
+  while (rg < r && bound2_of_host(rg, h) < g.gate2) ++rg;
+  g.rfar_gate     = rg;
+  g.list_R        = 0;
+  g.lists         = nullptr;
+  return (long long) g.nx * g.ny * g.nz;
 }
 
 // Cell neighbour lists of a slice's grid (k_icp_step_cnl; GridDev::list_*): once per grid, on the first compute() that wants
@@ -733,8 +820,12 @@ int upload_moving(srrg2_aligner* a, int si, const float* coords, int cs, const f
   return 0;
 }
 
-int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null for K == 1 */, const float* guesses) {
+// pair_grids != null: a pair batch (srrg2_align_pairs) -- problem k searches the grid pair_grids[k] of its own fixed cloud (device
+// table) instead of slice 0's grid, on the pair instantiations of the grid kernels with control launches
+int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null for K == 1 */, const float* guesses,
+                const GridDev* pair_grids = nullptr) {
   auto t_begin = std::chrono::steady_clock::now();
+  const bool pairs = pair_grids != nullptr;
   int rc;
   if ((rc = set_device(a))) return rc;
   // (a pipelined batch: upload_moving has already put the second half's sort on the second stream)
@@ -770,12 +861,12 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
       if (!s->has_prior) return fail(SRRG2_E_STATE, "compute: prior slice without measurement");
       continue;
     }
-    if (!s->has_fixed) return fail(SRRG2_E_STATE, "compute: cue slice| no fixed");
+    if (!s->has_fixed && !pairs) return fail(SRRG2_E_STATE, "compute: cue slice| no fixed");
     if (!s->has_moving) return fail(SRRG2_E_STATE, "compute: cue slice| no moving");
     if (K == 1 && s->moving_is_batch)
       return fail(SRRG2_E_STATE, "compute: the moving cloud bound to the cue slice is the concatenation of the last "
                                  "compute_batch (K > 1); bind one with set_moving first");
-    if (s->cfg.kind == SRRG2_SLICE_P2PLANE && !s->fixed_has_normals)
+    if (s->cfg.kind == SRRG2_SLICE_P2PLANE && !(pairs ? a->pair_normals : s->fixed_has_normals))
       return fail(SRRG2_E_STATE, "compute: point-to-plane slice needs fixed normals");
     if (s->cfg.finder == SRRG2_FINDER_PROJECTIVE && s->nf != s->cfg.image_rows * s->cfg.image_cols)
       return fail(SRRG2_E_STATE, "compute: projective finder needs an organised fixed cloud of rows x cols points");
@@ -857,9 +948,11 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     // the one-workgroup kernel up to ~640 points; 360 beams 0.126 against 0.165 ms, 1000 beams 0.246 against 0.19 ms, r7f)
     // (round 6, late: the control wave linearises prior slices too -- wave_prior --, such aligners follow the rule of the cue-only
     // ones; fused_control = 2: prior + cue aligners on control launches, as before)
+    // (pair batches: every cloud up to small_max_points on the one-workgroup kernel -- their passes run on the grid kernels with a
+    // control launch each, and a batch of small clouds leaves such launches nearly empty)
     const bool priors_launch = nslices > ncue && (tn.fused_control == 2 || nslices - ncue > 2);
-    if (small && (priors_launch || tn.fused_control == 0 || a->params.max_iterations < 2)) small = max_nm <= 640;
-    if (small && !(priors_launch || tn.fused_control == 0 || a->params.max_iterations < 2)) {
+    if (small && !pairs && (priors_launch || tn.fused_control == 0 || a->params.max_iterations < 2)) small = max_nm <= 640;
+    if (small && !pairs && !(priors_launch || tn.fused_control == 0 || a->params.max_iterations < 2)) {
       const Slice* sfc = a->slices[fc];
       const int sl     = tn.search_lists;
       const bool lists = sl >= 2 || (sl == 1 && K > 4) || (sl < 0 && (K > 4 || sfc->grid_computes >= 1 || sfc->lists_tried));
@@ -895,7 +988,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   // (automatic: batches of more than four alignments -- C4-256 374 -> 406 k it/s, C4-32 305 -> 322 k, C4-8 167 -> 171 k;
   // single alignments are launch / latency bound and neutral to 1.5 % slower with it: 30 k points 41.7 -> 41.1 k it/s,
   // profiles/archive/r3i_ab_tile_default.txt)
-  const int lds_tile = tn.lds_tile >= 0 ? tn.lds_tile : (K > 4 ? 1 : 0);
+  const int lds_tile = pairs ? 0 : (tn.lds_tile >= 0 ? tn.lds_tile : (K > 4 ? 1 : 0));
   // Search passes over the cell neighbour lists of the grid (k_icp_step_cnl, round 4): 0 = never, 1 = batches of more than
   // four alignments, 2 = every alignment (no deferred-search queue then).  -1 = automatic: batches always (the build --
   // two kernels, ~0.2 ms at 100 k points, two host waits -- is shared by all their alignments); single alignments from the
@@ -945,16 +1038,16 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     const int queue_min = tn.queue_min_points;
     const bool want_lists = search_lists >= 2 || (search_lists == 1 && K > 4) ||
                             (search_lists < 0 && (K > 4 || s->grid_computes >= 1 || s->lists_tried));
-    s->grid_computes++;
-    if (s->cfg.finder == SRRG2_FINDER_NN_GATED && !small && want_lists) {
+    if (!pairs) s->grid_computes++;  // (a pair batch does not search the slice's grid)
+    if (s->cfg.finder == SRRG2_FINDER_NN_GATED && !small && want_lists && !pairs) {
       // (the lists are built once per grid; the guard: 96 Mi entries = 1.5 GB -- C2: 3 M entries, a 2 M-point cloud: ~60 M)
       if ((rc = ensure_lists(a, s, 96LL << 20))) return rc;
       cnl[(size_t) si] = s->grid.list_R > 0 ? 1 : 0;
     }
-    const bool use_queue = s->cfg.finder == SRRG2_FINDER_NN_GATED && nm_max_s >= queue_min && K <= 4 && !small && !cnl[(size_t) si];
+    const bool use_queue = s->cfg.finder == SRRG2_FINDER_NN_GATED && nm_max_s >= queue_min && K <= 4 && !small && !cnl[(size_t) si] && !pairs;
     // batches: the converged pass (k_icp_step_fast) hands the points whose certificate failed to the deferred-search
     // kernel; the first iterations (k_icp_step) finish their open points themselves
-    const bool fast_queue = s->cfg.finder == SRRG2_FINDER_NN_GATED && K > 4 && !small && fast_batch_queue;
+    const bool fast_queue = s->cfg.finder == SRRG2_FINDER_NN_GATED && K > 4 && !small && fast_batch_queue && !pairs;
     s->fast_queue_only = fast_queue && !use_queue;
     const int nblocks    = PARTIAL_SLOTS;
     {
@@ -978,12 +1071,13 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     // (k_icp_init zeroes the slot sets and the queue counters; afterwards the control kernel resets them each iteration)
     sc.partials  = s->partials.p;
     sc.pinf_bits = s->pinf.p;
-    sc.ninf_bits = s->scalars.p + 7;
+    // (a pair's exponent is sized by ITS normals, as its own compute()'s: the rows, PAIR_ROW_WORDS apart -- k_icp_init_pairs)
+    sc.ninf_bits = pairs ? a->pair_rows.p + PAIR_ROW_NINF : s->scalars.p + 7;
     sc.finf_bits = s->scalars.p + 10;
     sc.gcorr_off = nullptr;
     sc.nm_global = (a->reduce_fn && s->cfg.kind != SRRG2_SLICE_PRIOR) ? (int) a->shard_total : 0;
     SliceDev& d       = sdev[si];
-    d.grid            = s->grid;
+    d.grid            = pairs ? GridDev{} : s->grid;  // (pair batches: the kernels take pair_grids[problem])
     d.mpts            = s->moving.p;
     d.mnrm            = s->moving_has_normals ? s->moving_nrm.p : nullptr;
     d.corr_fixed      = s->corr_fixed.p;
@@ -1007,7 +1101,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     d.robust_kind     = s->cfg.robustifier;
     d.robust_thr      = s->cfg.robustifier_chi_threshold;
     d.normal_cos      = s->cfg.finder_normal_cos;
-    d.use_normal_gate = (s->cfg.finder_normal_cos > -1.f && s->fixed_has_normals && s->moving_has_normals) ? 1 : 0;
+    d.use_normal_gate = (s->cfg.finder_normal_cos > -1.f && (pairs ? a->pair_normals : s->fixed_has_normals) && s->moving_has_normals) ? 1 : 0;
     // (batches: every pass re-reads the previous neighbour through its position in the shared, L2-resident fixed cloud; the
     // search passes then stream 48 instead of 112 bytes per point -- the algorithmic figure)
     d.gather_prev     = (s->cfg.finder == SRRG2_FINDER_NN_GATED && fast_gather) ? 1 : 0;
@@ -1103,7 +1197,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   // walks the problems first, so the control steps of all problems run in its first workgroups, and the workgroups of the
   // later rounds read the published records through the L2.)
   fuse = tn.fused_control != 0 && !small && !a->reduce_fn && a->timeline_path.empty() && first_cue >= 0 &&
-         a->params.max_iterations >= 2;
+         a->params.max_iterations >= 2 && !pairs;
   // (one nearest-neighbour cue slice, or projective slices that share one association -- k_proj_zbuf_fz --; no prior slices:
   // the step finds everything in the slices' records)
   // (round 6, late: prior slices next to them -- an odometry prior or a motion model: what a tracker configures, S/instances.cpp:35-38
@@ -1282,14 +1376,19 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   for (Slice* sl : a->slices) sl->slots_zeroed = 0;  // (until this compute() has ended the same way)
   if (!fold_init)
     for (int h = 0; h < nhalves; ++h)
-      srrg2amd::launch_icp_init(Ch[h], a->probs_host, a->probs.p, a->states.p, a->guesses_host, a->tsize, hstream[h]);
+      srrg2amd::launch_icp_init(Ch[h], a->probs_host, a->probs.p, a->states.p, a->guesses_host, a->tsize, hstream[h], pairs);
   auto t_init = std::chrono::steady_clock::now();
 
   if (small) {
     Slice* s = a->slices[first_cue];
-    srrg2amd::launch_icp_small(a->dim, s->cfg.kind == SRRG2_SLICE_P2PLANE, sdev[first_cue], C,
-                               a->probs.p + (size_t) first_cue * K, a->states.p, a->stats.p, a->outs_host, a->stats_host,
-                               a->stream);
+    if (pairs)
+      srrg2amd::launch_icp_small_pairs(a->dim, s->cfg.kind == SRRG2_SLICE_P2PLANE, sdev[first_cue], pair_grids, C,
+                                       a->probs.p + (size_t) first_cue * K, a->states.p, a->stats.p, a->outs_host, a->stats_host,
+                                       a->stream);
+    else
+      srrg2amd::launch_icp_small(a->dim, s->cfg.kind == SRRG2_SLICE_P2PLANE, sdev[first_cue], C,
+                                 a->probs.p + (size_t) first_cue * K, a->states.p, a->stats.p, a->outs_host, a->stats_host,
+                                 a->stream);
   }
   // Adaptive use of the deferred-search kernel.  After iteration `probe_it` the control kernel looks at what that
   // iteration deferred: few entries, none of them far (a far entry is a whole-wave scan: expensive when a wave has to do
@@ -1503,7 +1602,12 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
             hipStream_t hs = hstream[h];
             const int Kh   = hn[h];
             const bool first_pass_init = fold_init && slot0 == 0 && it == 0 && si == first_cue;  // (the prologue rides in this pass)
-            if (fast)
+            if (pairs && fast)
+              srrg2amd::launch_icp_step_fast_pairs(a->dim, plane, sd, pair_grids, pt, a->states.p, Kh, nm_max, fast_ppt_of(Kh),
+                                                   fast_gather, hs);
+            else if (pairs)
+              srrg2amd::launch_icp_step_pairs(a->dim, plane, sd, pair_grids, pt, a->states.p, Kh, nm_max, hs);
+            else if (fast)
               srrg2amd::launch_icp_step_fast(a->dim, plane, sd, pt, a->states.p, Kh, nm_max, fast_ppt_of(Kh), fast_gather, hs);
             else if (cnl[(size_t) si] && !sd.queue)
               srrg2amd::launch_icp_step_cnl(a->dim, plane, sd, s->lists_host, pt, a->states.p, Kh, nm_max,
@@ -1622,7 +1726,8 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   a->last_nm_max.assign((size_t) nslices, 0);
   for (int si = 0; si < nslices; ++si)
     for (int k = 0; k < K; ++k) a->last_nm_max[(size_t) si] = std::max(a->last_nm_max[(size_t) si], all[(size_t) si * K + k].nm);
-  a->records_state = 1;
+  a->records_state  = pairs ? 2 : 1;  // (a pair batch's records cannot be derived: its fixed clouds are not the slice's)
+  a->pairs_computed = pairs;
   a->last_path = (fuse ? SRRG2_PATH_FUSED_CONTROL : 0) | (fuse && fused_all ? SRRG2_PATH_ALL_PASSES_FUSED : 0) |
                  (fuse && final_launched && !small ? SRRG2_PATH_FINAL_WAVE : 0) | (fold_init ? SRRG2_PATH_PROLOGUE_IN_PASS : 0) |
                  (small ? SRRG2_PATH_ONE_WORKGROUP : 0) | (fuse && prior_mask ? SRRG2_PATH_PRIORS_FUSED : 0);
@@ -1636,6 +1741,56 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     }
   }
   return 0;
+}
+
+// the parts of a pipelined batch (compute_batch, align_pairs): 0 = one launch sequence, else parts [pbegin[p], pbegin[p + 1])
+int plan_batch_parts(srrg2_aligner* a, int K, const int32_t* offsets, int* pbegin) {
+  int nparts = 0;
+  {
+    const srrg2_aligner_tuning& tn = a->tuning;
+    int max_nm = 0;
+    for (int k = 0; k < K; ++k) max_nm = std::max(max_nm, offsets[k + 1] - offsets[k]);
+    bool one_cue = true;
+    for (size_t si = 1; si < a->slices.size(); ++si)
+      if (a->slices[si]->cfg.kind != SRRG2_SLICE_PRIOR) one_cue = false;
+    int want = tn.batch_pipeline == 0 ? 1 : (tn.batch_pipeline == 1 ? 2 : (tn.batch_pipeline > 1 ? tn.batch_pipeline : (K >= 8 ? 2 : 1)));
+    want     = std::min(std::min(want, (int) srrg2_aligner::MAX_PARTS), K);
+    if (want >= 2 && one_cue && a->slices[0]->cfg.finder == SRRG2_FINDER_NN_GATED && max_nm > tn.small_max_points &&
+        !tn.fast_batch_queue && !a->reduce_fn && !a->profile && a->timeline_path.empty()) {
+      nparts = want;
+      // (the parts' streams are created when a batch first wants them: an application with hundreds of aligners -- per-thread
+      // relocalisers -- that never runs pipelined batches owns one stream per aligner, not eight; ADVICE r5)
+      for (int p = 1; p < nparts; ++p)
+        if (!a->pstream[p] && hipStreamCreateWithFlags(&a->pstream[p], hipStreamNonBlocking) != hipSuccess) {
+          (void) hipGetLastError();
+          a->pstream[p] = nullptr;
+          nparts        = p >= 2 ? p : 0;  // (fewer parts, or none)
+          break;
+        }
+      for (int p = 0; p <= nparts; ++p) pbegin[p] = (int) ((long long) K * p / nparts);  // (contiguous, sizes differ by <= 1)
+    }
+  }
+  return nparts;
+}
+
+// the K result records of the batch run_compute has just delivered
+void fill_batch_results(const srrg2_aligner* a, int K, srrg2_batch_result* results) {
+  const int slots = a->max_stats;
+  for (int k = 0; k < K; ++k) {
+    const ProblemOut& o = a->outs_host[k];
+    std::memset(&results[k], 0, sizeof(results[k]));
+    std::memcpy(results[k].moving_in_fixed, o.X, sizeof(float) * a->tsize);
+    results[k].status         = o.status;
+    results[k].num_iterations = o.nstats;
+    if (o.nstats > 0) results[k].last = a->stats_host[(size_t) k * slots + std::min(o.nstats, slots) - 1];
+    int tot = 0;  // multi_aligner_impl.cpp:275-285, after pruning (k_icp_finalize)
+    for (size_t si = 0; si < a->slices.size(); ++si) {
+      const int c = a->slices[si]->cfg.kind == SRRG2_SLICE_PRIOR ? 1 : o.ncorr[si];
+      if (c >= 0) tot += c;
+    }
+    results[k].num_correspondences = tot;
+    std::memcpy(results[k].information, o.H, sizeof(o.H));
+  }
 }
 
 // correspondence records of the nearest-neighbour slices of the last compute(), derived on demand
@@ -1824,6 +1979,12 @@ int srrg2_aligner_destroy(srrg2_aligner_h a) {
   a->probs.release(); a->states.release(); a->outs.release(); a->stats.release(); a->guesses.release();
   a->pub.release(); a->pub_epoch.release(); a->ctl_dev.release();
   a->staging.release();
+  a->pair_raw.release(); a->pair_nrm_raw.release(); a->pair_sorted.release(); a->pair_nrm_sorted.release();
+  a->pair_cell_start.release(); a->pair_cursor.release(); a->pair_scan_sums.release(); a->pair_pos_of.release();
+  a->pair_rows.release(); a->pair_fprobs.release(); a->pair_grids.release(); a->pair_staging.release();
+  if (a->pair_rows_host) (void) hipHostFree(a->pair_rows_host);
+  if (a->pair_fprobs_host) (void) hipHostFree(a->pair_fprobs_host);
+  if (a->pair_grids_host) (void) hipHostFree(a->pair_grids_host);
   if (a->outs_host) (void) hipHostFree(a->outs_host);
   if (a->stats_host) (void) hipHostFree(a->stats_host);
   if (a->guesses_host) (void) hipHostFree(a->guesses_host);
@@ -2178,7 +2339,7 @@ int aligner_slice_view(srrg2_aligner_s* a, int si, AlignerSliceView* v) {
   int rc = check_slice(a, si, "aligner_slice_view");
   if (rc) return rc;
   Slice* s = a->slices[si];
-  if (!a->computed || a->K != 1 || s->cfg.kind == SRRG2_SLICE_PRIOR || !s->has_moving || !s->has_fixed)
+  if (!a->computed || a->K != 1 || s->cfg.kind == SRRG2_SLICE_PRIOR || !s->has_moving || !s->has_fixed || a->pairs_computed)
     return fail(SRRG2_E_STATE, "aligner_slice_view: needs a cue slice after a single-problem compute()");
   if (a->records_state == 2) return fail(SRRG2_E_STATE, "aligner_slice_view: the clouds changed since the last compute()");
   if ((rc = materialize_records(a, /*host_wait=*/false))) return rc;
@@ -2217,6 +2378,8 @@ int srrg2_aligner_get_correspondences(srrg2_aligner_h a, int si, srrg2_correspon
   int rc = check_slice(a, si, "get_correspondences");
   if (rc) return rc;
   if (!n) return fail(SRRG2_E_INVALID, "get_correspondences: null count");
+  if (a->pairs_computed && a->slices[si]->cfg.kind != SRRG2_SLICE_PRIOR)
+    return fail(SRRG2_E_STATE, "get_correspondences: the last compute was a pair batch (srrg2_align_pairs), which keeps no records");
   if (a->slices[si]->cfg.finder == SRRG2_FINDER_CORRESPONDENCES && a->slices[si]->cfg.kind != SRRG2_SLICE_PRIOR) {
     std::vector<srrg2_correspondence> pairs;
     std::vector<uint8_t> st;
@@ -2256,6 +2419,8 @@ int srrg2_aligner_get_factor_status(srrg2_aligner_h a, int si, uint8_t* buf, int
   int rc = check_slice(a, si, "get_factor_status");
   if (rc) return rc;
   if (!n) return fail(SRRG2_E_INVALID, "get_factor_status: null count");
+  if (a->pairs_computed && a->slices[si]->cfg.kind != SRRG2_SLICE_PRIOR)
+    return fail(SRRG2_E_STATE, "get_factor_status: the last compute was a pair batch (srrg2_align_pairs), which keeps no records");
   if (a->slices[si]->cfg.finder == SRRG2_FINDER_CORRESPONDENCES && a->slices[si]->cfg.kind != SRRG2_SLICE_PRIOR) {
     std::vector<srrg2_correspondence> pairs;
     std::vector<uint8_t> st;
@@ -2311,31 +2476,8 @@ int srrg2_aligner_compute_batch(srrg2_aligner_h a, int K, const float* coords, i
   // control step (one workgroup per alignment on an otherwise idle chip, ~10 us per iteration, + the kernel boundaries) and
   // Morton sort pass, the other parts' pass kernels have the chip.  Same kernels on the same data: the same bits.
   // tuning.batch_pipeline: 0 = never, 1 = two halves for every batch of >= 2, P >= 2: P parts (batches of >= P), -1 = automatic
-  int nparts = 0, pbegin[srrg2_aligner::MAX_PARTS + 1] = {0};
-  {
-    const srrg2_aligner_tuning& tn = a->tuning;
-    int max_nm = 0;
-    for (int k = 0; k < K; ++k) max_nm = std::max(max_nm, offsets[k + 1] - offsets[k]);
-    bool one_cue = true;
-    for (size_t si = 1; si < a->slices.size(); ++si)
-      if (a->slices[si]->cfg.kind != SRRG2_SLICE_PRIOR) one_cue = false;
-    int want = tn.batch_pipeline == 0 ? 1 : (tn.batch_pipeline == 1 ? 2 : (tn.batch_pipeline > 1 ? tn.batch_pipeline : (K >= 8 ? 2 : 1)));
-    want     = std::min(std::min(want, (int) srrg2_aligner::MAX_PARTS), K);
-    if (want >= 2 && one_cue && a->slices[0]->cfg.finder == SRRG2_FINDER_NN_GATED && max_nm > tn.small_max_points &&
-        !tn.fast_batch_queue && !a->reduce_fn && !a->profile && a->timeline_path.empty()) {
-      nparts = want;
-      // (the parts' streams are created when a batch first wants them: an application with hundreds of aligners -- per-thread
-      // relocalisers -- that never runs pipelined batches owns one stream per aligner, not eight; ADVICE r5)
-      for (int p = 1; p < nparts; ++p)
-        if (!a->pstream[p] && hipStreamCreateWithFlags(&a->pstream[p], hipStreamNonBlocking) != hipSuccess) {
-          (void) hipGetLastError();
-          a->pstream[p] = nullptr;
-          nparts        = p >= 2 ? p : 0;  // (fewer parts, or none)
-          break;
-        }
-      for (int p = 0; p <= nparts; ++p) pbegin[p] = (int) ((long long) K * p / nparts);  // (contiguous, sizes differ by <= 1)
-    }
-  }
+  int pbegin[srrg2_aligner::MAX_PARTS + 1] = {0};
+  const int nparts = plan_batch_parts(a, K, offsets, pbegin);
   if ((rc = upload_moving(a, 0, coords, cs, normals, ns, offsets, K, mem, /*wait=*/false, nparts, pbegin))) return rc;
   if (a->hosttime)
     std::fprintf(stderr, "compute_batch: upload_moving (enqueue) %.1f us\n",
@@ -2347,22 +2489,7 @@ int srrg2_aligner_compute_batch(srrg2_aligner_h a, int K, const float* coords, i
     for (Slice* sl : a->slices) sl->ms_pending = false;
     return rc;
   }
-  const int slots = a->max_stats;
-  for (int k = 0; k < K; ++k) {
-    const ProblemOut& o = a->outs_host[k];
-    std::memset(&results[k], 0, sizeof(results[k]));
-    std::memcpy(results[k].moving_in_fixed, o.X, sizeof(float) * a->tsize);
-    results[k].status         = o.status;
-    results[k].num_iterations = o.nstats;
-    if (o.nstats > 0) results[k].last = a->stats_host[(size_t) k * slots + std::min(o.nstats, slots) - 1];
-    int tot = 0;  // multi_aligner_impl.cpp:275-285, after pruning (k_icp_finalize)
-    for (size_t si = 0; si < a->slices.size(); ++si) {
-      const int c = a->slices[si]->cfg.kind == SRRG2_SLICE_PRIOR ? 1 : o.ncorr[si];
-      if (c >= 0) tot += c;
-    }
-    results[k].num_correspondences = tot;
-    std::memcpy(results[k].information, o.H, sizeof(o.H));
-  }
+  fill_batch_results(a, K, results);
   // The handle's observable state is that of the LAST alignment (K x {set_moving; set_moving_in_fixed; compute()}):
   // status, estimate, statistics, correspondences and factor status of problem K - 1 stay readable.  The bound moving
   // cloud, however, is the concatenation of the batch (Slice::moving_is_batch): a later plain compute() must bind its
@@ -2399,6 +2526,150 @@ int srrg2_aligner_compute_batch_correspondences(srrg2_aligner_h a, int K, const 
   s->h_gcorr_off.resize((size_t) K + 1);
   for (int k = 0; k <= K; ++k) s->h_gcorr_off[(size_t) k] = corr_offsets[k] - corr_offsets[0];
   return srrg2_aligner_compute_batch(a, K, coords, cs, normals, ns, offsets, mem, guesses, results);
+}
+
+int srrg2_align_pairs(srrg2_aligner_h a, int K, const float* fixed_coords, int fcs, const float* fixed_normals, int fns,
+                      const int32_t* fixed_offsets, const float* moving_coords, int mcs, const float* moving_normals, int mns,
+                      const int32_t* moving_offsets, int mem, const float* guesses, srrg2_batch_result* results) {
+  // (everything that can be refused is refused before the handle is touched)
+  if (!a) return fail(SRRG2_E_INVALID, "align_pairs: null handle");
+  if (K < 0 || K > 65535) return fail(SRRG2_E_INVALID, "align_pairs: K must be in [0, 65535] (grid.y)");
+  if (K == 0) return 0;
+  if (!fixed_offsets || !moving_offsets || !guesses || !results) return fail(SRRG2_E_INVALID, "align_pairs: bad arguments");
+  if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE)
+    return fail(SRRG2_E_INVALID, "align_pairs: mem must be SRRG2_MEM_HOST or SRRG2_MEM_DEVICE");
+  for (const int32_t* off : {fixed_offsets, moving_offsets}) {
+    if (off[0] < 0) return fail(SRRG2_E_INVALID, "align_pairs: negative offset");
+    for (int k = 0; k < K; ++k)
+      if (off[k + 1] < off[k]) return fail(SRRG2_E_INVALID, "align_pairs: offsets must not decrease");
+  }
+  const int nf_all = fixed_offsets[K] - fixed_offsets[0], nm_all = moving_offsets[K] - moving_offsets[0];
+  if ((nf_all > 0 && !fixed_coords) || (nm_all > 0 && !moving_coords))
+    return fail(SRRG2_E_INVALID, "align_pairs: null cloud");
+  const int dim = a->dim;
+  auto bad_stride = [&](const void* p, int st, int n) { return p && n > 0 && (st % 4 != 0 || st < dim * 4); };
+  if (bad_stride(fixed_coords, fcs, nf_all) || bad_stride(fixed_normals, fns, nf_all) || bad_stride(moving_coords, mcs, nm_all) ||
+      bad_stride(moving_normals, mns, nm_all))
+    return fail(SRRG2_E_INVALID, "align_pairs: stride must be a multiple of 4 and >= dim*4");
+  if (a->slices.empty()) return fail(SRRG2_E_STATE, "align_pairs: no slices");
+  Slice* s = a->slices[0];
+  if (s->cfg.kind == SRRG2_SLICE_PRIOR) return fail(SRRG2_E_UNSUPPORTED, "align_pairs: slice 0 must be the cue slice");
+  if (s->cfg.finder != SRRG2_FINDER_NN_GATED || (s->cfg.kind != SRRG2_SLICE_P2P && s->cfg.kind != SRRG2_SLICE_P2PLANE))
+    return fail(SRRG2_E_UNSUPPORTED, "align_pairs: the cue slice must be a point-to-point or point-to-plane slice with the "
+                                     "nearest-neighbour finder");
+  for (size_t si = 1; si < a->slices.size(); ++si) {
+    if (a->slices[si]->cfg.kind != SRRG2_SLICE_PRIOR)
+      return fail(SRRG2_E_UNSUPPORTED, "align_pairs: one cue slice (slice 0) plus prior slices");
+    if (!a->slices[si]->has_prior) return fail(SRRG2_E_STATE, "align_pairs: prior slice without measurement");
+  }
+  if (a->reduce_fn) return fail(SRRG2_E_UNSUPPORTED, "align_pairs: not on a point-sharded handle (set_point_shard)");
+  if (s->cfg.kind == SRRG2_SLICE_P2PLANE && !fixed_normals)
+    return fail(SRRG2_E_STATE, "align_pairs: point-to-plane slice needs fixed normals");
+  int rc;
+  if ((rc = set_device(a))) return rc;
+  if ((rc = quiesce_stream2(a))) return rc;
+  // (from here on every error path waits for the stream: the call returns only after the caller's buffers have been read)
+  auto drain = [&](int code) {
+    (void) hipStreamSynchronize(a->stream);
+    for (int p = 1; p < srrg2_aligner::MAX_PARTS; ++p)
+      if (a->pstream[p]) (void) hipStreamSynchronize(a->pstream[p]);
+    s->ms_pending = false;
+    return code;
+  };
+  // 1. the fixed clouds: one ingest for all of them, with the per-pair rows, read back with ONE copy and one wait
+  const size_t nfa = (size_t) std::max(nf_all, 1);
+  int max_nf = 0;
+  if ((rc = ensure_pinned(a->pair_fprobs_host, a->pair_fprobs_host_cap, (size_t) K)) ||
+      (rc = ensure_pinned(a->pair_rows_host, a->pair_rows_host_cap, (size_t) K * PAIR_ROW_WORDS)) ||
+      (rc = ensure_pinned(a->pair_grids_host, a->pair_grids_host_cap, (size_t) K)))
+    return rc;
+  for (int k = 0; k < K; ++k) {
+    a->pair_fprobs_host[k] = ProblemDev{fixed_offsets[k] - fixed_offsets[0], fixed_offsets[k + 1] - fixed_offsets[k]};
+    max_nf                 = std::max(max_nf, a->pair_fprobs_host[k].nm);
+  }
+  if ((rc = a->pair_raw.reserve(nfa)) || (fixed_normals && (rc = a->pair_nrm_raw.reserve(nfa))) ||
+      (rc = a->pair_rows.reserve((size_t) K * PAIR_ROW_WORDS)) || (rc = a->pair_fprobs.reserve((size_t) K)) ||
+      (rc = a->pair_grids.reserve((size_t) K)))
+    return rc;
+  const size_t bytes_c = (size_t) nf_all * dim * 4;
+  if (mem == SRRG2_MEM_HOST && (rc = a->pair_staging.reserve(2 * bytes_c + 64))) return rc;
+  const float* fsrc = nullptr;
+  const float* nsrc = nullptr;
+  int fsf = dim, nsf = dim;
+  // (a HIP call that fails once the caller's buffers may be read: wait for the streams before returning)
+#define PAIRS_TRY(expr)                                                                              \
+  do {                                                                                               \
+    hipError_t _e = (expr);                                                                          \
+    if (_e != hipSuccess) return drain(fail(SRRG2_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); \
+  } while (0)
+  const float* fbase = fixed_coords ? (const float*) ((const char*) fixed_coords + (size_t) fixed_offsets[0] * fcs) : nullptr;
+  if ((rc = stage_input(a, fbase, fcs, nf_all, dim, mem, &fsrc, &fsf, 0, &a->pair_staging))) return drain(rc);
+  if (fixed_normals) {
+    const float* nbase = (const float*) ((const char*) fixed_normals + (size_t) fixed_offsets[0] * fns);
+    if ((rc = stage_input(a, nbase, fns, nf_all, dim, mem, &nsrc, &nsf, (bytes_c + 63) / 64 * 64, &a->pair_staging)))
+      return drain(rc);
+  }
+  PAIRS_TRY(hipMemcpyAsync(a->pair_fprobs.p, a->pair_fprobs_host, sizeof(ProblemDev) * (size_t) K, hipMemcpyHostToDevice, a->stream));
+  PAIRS_TRY(hipMemsetAsync(a->pair_rows.p, 0, sizeof(unsigned) * (size_t) K * PAIR_ROW_WORDS, a->stream));
+  srrg2amd::launch_pairs_ingest(fsrc, fsf, nsrc, nsf, a->pair_fprobs.p, K, max_nf, dim, a->pair_raw.p,
+                                fixed_normals ? a->pair_nrm_raw.p : nullptr, a->pair_rows.p, a->stream);
+  PAIRS_TRY(hipMemcpyAsync(a->pair_rows_host, a->pair_rows.p, sizeof(unsigned) * (size_t) K * PAIR_ROW_WORDS, hipMemcpyDeviceToHost,
+                           a->stream));
+  PAIRS_TRY(hipStreamSynchronize(a->stream));
+  // 2. the grids' records on the host from the rows (before the slice's moving cloud is touched: a batch whose grids do not fit
+  // is refused with the handle unchanged)
+  long long total = 0;
+  int max_cells   = 0;
+  std::vector<long long> coff((size_t) K);
+  for (int k = 0; k < K; ++k) {
+    const long long nc = pair_grid_of(a, s, a->pair_rows_host + (size_t) k * PAIR_ROW_WORDS, a->pair_fprobs_host[k].nm,
+                                      a->pair_grids_host[k]);
+    coff[(size_t) k] = total;
+    total += nc + 1;  // (+ the cell of the non-finite points)
+    max_cells = (int) std::max((long long) max_cells, nc);
+  }
+  if (total >= 0x7fffffffLL - 1) return fail(SRRG2_E_INVALID, "align_pairs: the pairs' grids exceed 2^31 cells");
+  if ((rc = a->pair_cell_start.reserve((size_t) total + 1)) || (rc = a->pair_cursor.reserve((size_t) total + 1)) ||
+      (rc = a->pair_scan_sums.reserve((size_t) srrg2amd::scan_num_blocks((int) total) + 2)) ||
+      (rc = a->pair_sorted.reserve(nfa + 8)) ||  // (scan_range over-reads <= 3 entries)
+      (fixed_normals && (rc = a->pair_nrm_sorted.reserve(nfa + 8))) || (rc = a->pair_pos_of.reserve(nfa)))
+    return rc;
+  for (int k = 0; k < K; ++k) {
+    GridDev& g     = a->pair_grids_host[k];
+    const int foff = a->pair_fprobs_host[k].moff;
+    g.cell_start   = a->pair_cell_start.p + coff[(size_t) k];
+    g.pts          = a->pair_sorted.p + foff;
+    g.nrm          = fixed_normals ? a->pair_nrm_sorted.p + foff : nullptr;
+    g.pos_of       = a->pair_pos_of.p + foff;
+  }
+  // 3. the moving clouds (Morton sort per problem, pipelined parts as compute_batch)
+  int pbegin[srrg2_aligner::MAX_PARTS + 1] = {0};
+  const int nparts = plan_batch_parts(a, K, moving_offsets, pbegin);
+  if ((rc = upload_moving(a, 0, moving_coords, mcs, moving_normals, mns, moving_offsets, K, mem, /*wait=*/false, nparts, pbegin)))
+    return drain(rc);
+  // 4. the segmented grid build (count, scan, localise, scatter) in one launch each
+  PAIRS_TRY(hipMemcpyAsync(a->pair_grids.p, a->pair_grids_host, sizeof(GridDev) * (size_t) K, hipMemcpyHostToDevice, a->stream));
+  PAIRS_TRY(hipMemsetAsync(a->pair_cell_start.p, 0, sizeof(int) * ((size_t) total + 1), a->stream));
+  srrg2amd::launch_pairs_grid_build(a->pair_grids.p, a->pair_fprobs.p, K, max_nf, max_cells, (int) total, a->pair_raw.p,
+                                    fixed_normals ? a->pair_nrm_raw.p : nullptr, a->pair_cell_start.p, a->pair_cursor.p,
+                                    a->pair_scan_sums.p, a->pair_scan_sums.p + a->pair_scan_sums.cap - 1, a->pair_sorted.p,
+                                    fixed_normals ? a->pair_nrm_sorted.p : nullptr, a->pair_pos_of.p, a->stream);
+  PAIRS_TRY(hipGetLastError());
+  // (the parts of a pipelined batch search the grids built on `stream`)
+  if (a->batch_parts >= 2) {
+    PAIRS_TRY(hipEventRecord(a->ev_staged, a->stream));
+    for (int p = 1; p < a->batch_parts; ++p) PAIRS_TRY(hipStreamWaitEvent(a->pstream[p], a->ev_staged, 0));
+  }
+#undef PAIRS_TRY
+  // 5. the alignments
+  a->pair_normals = fixed_normals != nullptr;
+  rc              = run_compute(a, K, moving_offsets, guesses, a->pair_grids.p);
+  // (the moving cloud of the slice is unbound: a plain compute() needs set_moving first)
+  s->has_moving      = false;
+  s->moving_is_batch = false;
+  if (rc) return drain(rc);
+  fill_batch_results(a, K, results);
+  return 0;
 }
 
 int srrg2_multi_gpu_init(int local_rank, int* device_out) {

@@ -216,11 +216,19 @@ struct SliceCtl {
   int nm_global;            // > 0: moving points of the alignment over ALL ranks (point-sharded alignment: sizes the exponent)
   const long long* partials;  // [3][problem][PARTIAL_SLOTS][ACC_N] (null for priors; buffers 1 and 2 are used by fused control steps)
   const unsigned* pinf_bits;      // [problem] max |coord| of the finite moving points (float bits)
-  const unsigned* ninf_bits;      // [1] max |component| of the fixed normals
+  const unsigned* ninf_bits;      // [1] max |component| of the fixed normals (pair batches: [problem * PAIR_ROW_WORDS])
   const unsigned* finf_bits;      // [1] max |coordinate| of the fixed cloud (given-correspondences slices)
   const int* gcorr_off;           // [K + 1] offsets of the given correspondences (or null)
   float Sinv[12];                 // robot_in_sensor = sensor_in_robot^-1 (SliceDev::Sinv)
 };
+
+// Pair batches (srrg2_align_pairs): every alignment has a fixed cloud and a grid of its own.  The fixed clouds are concatenated;
+// their grids are segments of concatenated cell_start / sorted points / sorted normals / pos_of arrays, each GridDev of the table
+// pointing at its pair's segments, so that positions (pos_of, prev_pos) stay pair-local.  Per pair one row of PAIR_ROW_WORDS words,
+// written by the ingest: [0, 3) complemented bounding-box minimum keys (~fkey: zero-initialised and raised with atomicMax like the
+// maxima), [3, 6) maximum keys, [6] finite points, [7] max |component| of the fixed normals (float bits).
+#define PAIR_ROW_WORDS 8
+#define PAIR_ROW_NINF 7
 
 // a single alignment's initial guess and per-slice problem table, carried in k_icp_init's arguments
 struct InitInline {

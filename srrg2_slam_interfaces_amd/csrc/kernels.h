@@ -65,8 +65,9 @@ void launch_corr_step(int dim, bool plane, const SliceDev& S, const ProblemDev* 
                       int max_ncorr, hipStream_t s);
 void launch_proj_step(bool repro, const SliceDev& S, const ProblemDev* probs, ProblemState* states, int K, int max_nm,
                       hipStream_t s);
+// (pairs: a pair batch, srrg2_align_pairs -- every problem's exponent from its own fixed normals: SliceCtl::ninf_bits[problem * PAIR_ROW_WORDS])
 void launch_icp_init(const CtlParams& C, const ProblemDev* probs_host, ProblemDev* probs, ProblemState* states,
-                     const float* guesses_host, int tsize, hipStream_t s);
+                     const float* guesses_host, int tsize, hipStream_t s, bool pairs = false);
 // what k_icp_init gets of a single alignment in its arguments (guess, problem table); false: a batch (read from pinned memory)
 bool make_init_inline(const CtlParams& C, const ProblemDev* probs_host, const float* guesses_host, int tsize, InitInline* inl);
 void launch_icp_control(const CtlParams& C, ProblemState* states, srrg2_iteration_stats* stats, hipStream_t s);
@@ -77,6 +78,23 @@ void launch_icp_final_wave_pack(const SliceDev* slices, const ProblemDev* const*
                                 bool with_post, hipStream_t s);
 void launch_icp_small(int dim, bool plane, const SliceDev& S, const CtlParams& C, const ProblemDev* probs, ProblemState* states,
                       srrg2_iteration_stats* stats, ProblemOut* outs_host, srrg2_iteration_stats* stats_host, hipStream_t s);
+// pair batches (srrg2_align_pairs): k_icp_step / k_icp_step_fast / k_icp_small with grids[problem], the problem's own grid, in place
+// of S.grid (control launches, no lists, tiles or deferred-search queue)
+void launch_icp_step_pairs(int dim, bool plane, const SliceDev& S, const GridDev* grids, const ProblemDev* probs,
+                           ProblemState* states, int K, int max_nm, hipStream_t s);
+void launch_icp_step_fast_pairs(int dim, bool plane, const SliceDev& S, const GridDev* grids, const ProblemDev* probs,
+                                ProblemState* states, int K, int max_nm, int ppt, bool gather, hipStream_t s);
+void launch_icp_small_pairs(int dim, bool plane, const SliceDev& S, const GridDev* grids, const CtlParams& C, const ProblemDev* probs,
+                            ProblemState* states, srrg2_iteration_stats* stats, ProblemOut* outs_host,
+                            srrg2_iteration_stats* stats_host, hipStream_t s);
+// pair batches, fixed side: the K concatenated clouds (fprobs: {offset, count} per pair) ingested in one launch with the per-pair rows
+// (PAIR_ROW_WORDS each, zeroed by the caller); then the segmented grid build over the table of the pairs' grids (cell segments of
+// ncell + 1 entries: the last counts the non-finite points, so that every segment's scan starts at its pair's offset)
+void launch_pairs_ingest(const float* src, int sf, const float* nsrc, int nsf, const ProblemDev* fprobs, int K, int max_nf, int dim,
+                         float4* dst, float4* dst_nrm, unsigned* rows, hipStream_t s);
+void launch_pairs_grid_build(const GridDev* grids, const ProblemDev* fprobs, int K, int max_nf, int max_cells, int total_cells,
+                             const float4* pts, const float4* nrm, int* cell_start, int* cursor, int* scan_sums, int* scan_total,
+                             float4* out_pts, float4* out_nrm, int* pos_of, hipStream_t s);
 // the last control step of a compute() with fused control steps (one nearest-neighbour cue slice): one wave per problem
 void launch_icp_final_wave(const CtlParams& C, const SliceDev& S, ProblemState* states, srrg2_iteration_stats* stats,
                            ProblemOut* outs_host, srrg2_iteration_stats* stats_host, bool with_post, hipStream_t s);

@@ -1466,6 +1466,21 @@ __global__ __launch_bounds__(256) void k_icp_step(SliceDev S, const ProblemDev* 
   icp_step_body<DIM, PLANE, 4>(S, probs[prob], sv, prob, blockIdx.x, gridDim.x, gridDim.y, nullptr);
 }
 
+// Pair batches (srrg2_align_pairs): the same pass with the grid of the problem's OWN fixed cloud, grids[prob], in place of the
+// slice's.  No neighbour lists, no LDS tiles, no deferred-search queue: a cloud aligned against once does not
+// repay their build.
+template <int DIM, bool PLANE>
+__global__ __launch_bounds__(256) void k_icp_step_pairs(SliceDev S, const GridDev* __restrict__ grids,
+                                                        const ProblemDev* __restrict__ probs, ProblemState* __restrict__ states) {
+  const int prob   = blockIdx.y + S.prob0;
+  ProblemState* st = &states[prob];
+  if (st->done || st->finished) return;
+  S.grid = grids[prob];
+  StepView sv;
+  step_view_of_state(S, st, sv);
+  icp_step_body<DIM, PLANE, 4>(S, probs[prob], sv, prob, blockIdx.x, gridDim.x, gridDim.y, nullptr);
+}
+
 // ============================================================================================
 // Search passes of batches with the neighbourhood of every WAVE staged in LDS (k_icp_step_tile).
 //
@@ -2097,8 +2112,10 @@ __device__ unsigned long long g_pass_ts[16 * 512 * 8];  // [epoch][workgroup (ti
 namespace {
 
 __device__ float robust_weight(int kind, float thr, float chi, bool& kernelized);  // (defined with the control kernels below)
+// (PAIRS: a pair batch, srrg2_align_pairs -- every problem's fixed cloud has its own normals' norm, s.ninf_bits[prob * PAIR_ROW_WORDS])
+template <bool PAIRS = false>
 __device__ __forceinline__ int slice_exponent(const CtlParams& C, const SliceCtl& s, int prob, int nm, const float* X);
-template <bool ONLY_INLINE>
+template <bool ONLY_INLINE, bool PAIRS = false>
 __device__ __forceinline__ void init_problem_thread0(const CtlParams& C, int prob, const ProblemDev* probs_host, ProblemDev* probs,
                                                      ProblemState* states, const float* guesses_host, int tsize,
                                                      const InitInline& inl, unsigned (*init_gran)[PUB_SLICE_GRANULES]);
@@ -3689,6 +3706,13 @@ __global__ __launch_bounds__(256) void k_icp_step_fast(SliceDev S, const Problem
                                                        ProblemState* __restrict__ states) {
   icp_step_fast_body<DIM, PLANE, PPT, GATHER, FUSED>(S, probs, states);
 }
+// ... of a pair batch (k_icp_step_pairs): control launches, the problem's own grid
+template <int DIM, bool PLANE, int PPT, bool GATHER>
+__global__ __launch_bounds__(256) void k_icp_step_fast_pairs(SliceDev S, const GridDev* __restrict__ grids,
+                                                             const ProblemDev* __restrict__ probs, ProblemState* __restrict__ states) {
+  S.grid = grids[blockIdx.y + S.prob0];
+  icp_step_fast_body<DIM, PLANE, PPT, GATHER, 0>(S, probs, states);
+}
 // ============================================================================================
 // The search pass over the cell neighbour lists (cnl_search above): TEAM lanes per moving point.
 // ============================================================================================
@@ -4762,6 +4786,7 @@ __global__ __launch_bounds__(256) void k_icp_step_proj_pack(SlicePack P, Problem
 // ============================================================================================
 namespace {
 
+template <bool PAIRS>
 __device__ __forceinline__ int slice_exponent(const CtlParams& C, const SliceCtl& s, int prob, int nm, const float* X) {
   const bool plane = s.kind == SRRG2_SLICE_P2PLANE;
   const bool repro = s.kind == SRRG2_SLICE_REPROJECTION;
@@ -4770,7 +4795,7 @@ __device__ __forceinline__ int slice_exponent(const CtlParams& C, const SliceCtl
   const int dim    = C.variable_kind == SRRG2_SE2_RIGHT ? 2 : 3;
   const int rows   = plane ? 1 : (repro ? 2 : dim);
   const float pinf = __uint_as_float(s.pinf_bits[prob]);
-  const float ninf = __uint_as_float(s.ninf_bits[0]);
+  const float ninf = __uint_as_float(s.ninf_bits[PAIRS ? prob * PAIR_ROW_WORDS : 0]);  // (a pair's own rows: k_pairs_ingest)
   double mb        = plane ? (1.7320508075688772 * (double) ninf) * 1.01 : 1.01;
   if (repro) {
     const double K0 = (double) s.K0, K4 = (double) s.K4;
@@ -5036,7 +5061,7 @@ __device__ void control_body(const CtlParams& C, ProblemState* st, srrg2_iterati
 // records of epoch 0, staged in `init_gran` for the wave that publishes them (k_icp_init; fused_init_tail inside a first pass)
 namespace {
 // (ONLY_INLINE: guess and problem table from `inl` whatever inl.use says -- the pinned tables are not even passed)
-template <bool ONLY_INLINE>
+template <bool ONLY_INLINE, bool PAIRS>
 __device__ __forceinline__ void init_problem_thread0(const CtlParams& C, int prob, const ProblemDev* probs_host, ProblemDev* probs,
                                      ProblemState* states, const float* guesses_host, int tsize, const InitInline& inl,
                                      unsigned (*init_gran)[PUB_SLICE_GRANULES]) {
@@ -5078,7 +5103,7 @@ __device__ __forceinline__ void init_problem_thread0(const CtlParams& C, int pro
     if (C.slices[s].kind == SRRG2_SLICE_PRIOR) continue;
     float Xloc[12], Tloc[12];
     for (int i = 0; i < 12; ++i) Xloc[i] = st->X[i];
-    const int kx = slice_exponent(C, C.slices[s], prob, nm_of[s], Xloc);
+    const int kx = slice_exponent<PAIRS>(C, C.slices[s], prob, nm_of[s], Xloc);
     finder_transform_of(C.slices[s].Sinv, C.variable_kind == SRRG2_SE2_RIGHT ? 2 : 3, Xloc, Tloc);
     st->kexp[s] = kx;
     for (int i = 0; i < 12; ++i) st->Tf[s][i] = st->Tfprev[s][i] = Tloc[i];
@@ -5101,9 +5126,10 @@ __device__ __forceinline__ void init_problem_thread0(const CtlParams& C, int pro
 // the stream), the partial-sum slots and queue counters are zeroed here (no memsets on the stream).
 // (inl.use: a single alignment's guess and problem table travel in the kernel arguments -- 116 bytes -- instead of being read
 // from pinned host memory: one PCIe round trip less at the head of every compute(); batches keep the pinned tables)
-__global__ __launch_bounds__(64) void k_icp_init(CtlParams C, const ProblemDev* __restrict__ probs_host,
-                                                 ProblemDev* __restrict__ probs, ProblemState* __restrict__ states,
-                                                 const float* __restrict__ guesses_host, int tsize, InitInline inl) {
+template <bool PAIRS>
+__device__ __forceinline__ void icp_init_body(const CtlParams& C, const ProblemDev* __restrict__ probs_host,
+                                              ProblemDev* __restrict__ probs, ProblemState* __restrict__ states,
+                                              const float* __restrict__ guesses_host, int tsize, const InitInline& inl) {
   const int prob = blockIdx.x + C.prob0;
   for (int s = 0; s < C.nslices; ++s) {
     const SliceCtl& sc = C.slices[s];
@@ -5122,13 +5148,24 @@ __global__ __launch_bounds__(64) void k_icp_init(CtlParams C, const ProblemDev* 
   // (fused control steps: the records of epoch 0 are written by all 64 lanes from a staged copy of what thread 0 computes;
   // one thread storing 64 granules per slice one after the other took k_icp_init from 6 to 25 us)
   __shared__ unsigned init_gran[SRRG2_MAX_SLICES][PUB_SLICE_GRANULES];
-  if (threadIdx.x == 0) init_problem_thread0<false>(C, prob, probs_host, probs, states, guesses_host, tsize, inl, init_gran);
+  if (threadIdx.x == 0) init_problem_thread0<false, PAIRS>(C, prob, probs_host, probs, states, guesses_host, tsize, inl, init_gran);
   if (!C.pub) return;
   __syncthreads();
   for (int s = 0; s < C.nslices; ++s)
     if (C.slices[s].kind != SRRG2_SLICE_PRIOR)
       pub_store(C.pub + ((size_t) prob * SRRG2_MAX_SLICES + s) * PUB_SLICE_GRANULES + threadIdx.x, (unsigned long long) init_gran[s][threadIdx.x]);
   pub_write_epoch(C.pub_epoch, prob, threadIdx.x, 0u);
+}
+__global__ __launch_bounds__(64) void k_icp_init(CtlParams C, const ProblemDev* __restrict__ probs_host,
+                                                 ProblemDev* __restrict__ probs, ProblemState* __restrict__ states,
+                                                 const float* __restrict__ guesses_host, int tsize, InitInline inl) {
+  icp_init_body<false>(C, probs_host, probs, states, guesses_host, tsize, inl);
+}
+// ... of a pair batch (srrg2_align_pairs): the exponents from every pair's own fixed normals
+__global__ __launch_bounds__(64) void k_icp_init_pairs(CtlParams C, const ProblemDev* __restrict__ probs_host,
+                                                       ProblemDev* __restrict__ probs, ProblemState* __restrict__ states,
+                                                       const float* __restrict__ guesses_host, int tsize, InitInline inl) {
+  icp_init_body<true>(C, probs_host, probs, states, guesses_host, tsize, inl);
 }
 
 constexpr int STATE_WORDS = (int) (sizeof(ProblemState) / sizeof(int));
@@ -5360,11 +5397,60 @@ __global__ __launch_bounds__(256) void k_icp_control_final(CtlParams C, ProblemS
 // problem's tiles, thread 0 runs the control step between them -- the same per-point and control code as the
 // launch-per-pass path, so the same bits.  A batch of small problems runs one workgroup per problem.
 // ============================================================================================
+// (TWIN: k_icp_small_pairs below repeats this body statement for statement -- a change here is a change there; the pair-batch tests
+// compare the two bit for bit, tests/test_gpu_align_pairs.py)
 template <int DIM, bool PLANE>
 __global__ __launch_bounds__(512) void k_icp_small(SliceDev S, CtlParams C, const ProblemDev* __restrict__ probs,
                                                    ProblemState* __restrict__ states, srrg2_iteration_stats* __restrict__ stats,
                                                    ProblemOut* __restrict__ outs_host,
                                                    srrg2_iteration_stats* __restrict__ stats_host) {
+  constexpr int NW = 8;  // (16 waves would cap the registers at 128 per lane: the SE(3) control step spills, measured slower)
+  constexpr int D  = DIM == 3 ? 6 : 3;
+  const int prob   = blockIdx.x;
+  __shared__ ProblemState sst;
+  __shared__ long long sums[SRRG2_MAX_SLICES][ACC_N];
+  __shared__ double scaled[SRRG2_MAX_SLICES][ACC_N];
+  state_to_lds(&sst, &states[prob]);
+  __syncthreads();
+  const ProblemDev pd = probs[prob];
+  const int ntiles    = (pd.nm + NW * 64 - 1) / (NW * 64);
+  const int nrun      = C.params.enable_inlier_only_runs ? 2 : 1;
+  for (int run = 0; run < nrun; ++run) {
+    for (int it = 0; it < C.params.max_iterations; ++it) {
+      if (sst.done || sst.finished) break;  // (uniform: LDS)
+      if (threadIdx.x < ACC_N) sums[S.slice_idx][threadIdx.x] = 0;
+      __syncthreads();
+      for (int tile = 0; tile < ntiles; ++tile) {
+        StepView sv;
+        step_view_of_state(S, &sst, sv);
+        icp_step_body<DIM, PLANE, NW>(S, pd, sv, prob, tile, ntiles, C.K, sums[S.slice_idx]);
+        __syncthreads();  // (the body's shared scratch is reused by the next tile)
+      }
+      if (threadIdx.x < ACC_N)
+        scaled[S.slice_idx][threadIdx.x] = (double) sums[S.slice_idx][threadIdx.x] * dm::pow2(-sst.kexp[S.slice_idx]);
+      __syncthreads();
+      if (threadIdx.x == 0) control_body<D>(C, &sst, stats, prob, sums, scaled);
+      __syncthreads();
+    }
+    if (run == 0 && nrun == 2) {  // multi_aligner_impl.cpp:75-85, then the inlier-only run
+      if (threadIdx.x == 0) icp_post_one(C, &sst, stats, prob);
+      __syncthreads();
+    }
+  }
+  __threadfence();  // (the statistics thread 0 wrote are read back by the whole workgroup below)
+  __syncthreads();
+  icp_finalize_block(C, &sst, stats, outs_host, stats_host, prob, nrun == 1);
+  __syncthreads();
+  state_from_lds(&states[prob], &sst);
+}
+// ... of a pair batch: the problem's own grid (k_icp_step_pairs).  The body is k_icp_small's, statement for statement: moved into a
+// shared function, k_icp_small itself came out with another register count (existing kernels stay as they are).
+template <int DIM, bool PLANE>
+__global__ __launch_bounds__(512) void k_icp_small_pairs(SliceDev S, const GridDev* __restrict__ grids, CtlParams C,
+                                                         const ProblemDev* __restrict__ probs, ProblemState* __restrict__ states,
+                                                         srrg2_iteration_stats* __restrict__ stats, ProblemOut* __restrict__ outs_host,
+                                                         srrg2_iteration_stats* __restrict__ stats_host) {
+  S.grid = grids[blockIdx.x];
   constexpr int NW = 8;  // (16 waves would cap the registers at 128 per lane: the SE(3) control step spills, measured slower)
   constexpr int D  = DIM == 3 ? 6 : 3;
   const int prob   = blockIdx.x;
@@ -5811,11 +5897,15 @@ bool make_init_inline(const CtlParams& C, const ProblemDev* probs_host, const fl
   return true;
 }
 void launch_icp_init(const CtlParams& C, const ProblemDev* probs_host, ProblemDev* probs, ProblemState* states,
-                     const float* guesses_host, int tsize, hipStream_t s) {
+                     const float* guesses_host, int tsize, hipStream_t s, bool pairs) {
   InitInline inl{};
   (void) make_init_inline(C, probs_host, guesses_host, tsize, &inl);
-  hipLaunchKernelGGL(k_icp_init, dim3(C.nprob > 0 ? C.nprob : C.K), dim3(64), 0, s, C, probs_host, probs, states, guesses_host,
-                     tsize, inl);
+  if (pairs)
+    hipLaunchKernelGGL(k_icp_init_pairs, dim3(C.nprob > 0 ? C.nprob : C.K), dim3(64), 0, s, C, probs_host, probs, states, guesses_host,
+                       tsize, inl);
+  else
+    hipLaunchKernelGGL(k_icp_init, dim3(C.nprob > 0 ? C.nprob : C.K), dim3(64), 0, s, C, probs_host, probs, states, guesses_host,
+                       tsize, inl);
 }
 void launch_icp_control(const CtlParams& C, ProblemState* states, srrg2_iteration_stats* stats, hipStream_t s) {
   hipLaunchKernelGGL(k_icp_control, dim3(C.nprob > 0 ? C.nprob : C.K), dim3(256), 0, s, C, states, stats);
@@ -5835,6 +5925,65 @@ void launch_icp_small(int dim, bool plane, const SliceDev& S, const CtlParams& C
       hipLaunchKernelGGL((k_icp_small<2, false>), dim3(C.K), dim3(512), 0, s, S, C, probs, states, stats, outs_host, stats_host);
   }
 }
+
+// pair batches (srrg2_align_pairs): the launchers above with the table of the problems' own grids
+// (INST: the instantiation for <dim, plane> and the kernel's remaining template arguments)
+#define PAIRS_LAUNCH(INST, GRID, BLOCK, ...)                                      \
+  do {                                                                            \
+    if (dim == 3) {                                                               \
+      if (plane)                                                                  \
+        hipLaunchKernelGGL((INST(3, true)), GRID, BLOCK, 0, s, S, grids, __VA_ARGS__);  \
+      else                                                                        \
+        hipLaunchKernelGGL((INST(3, false)), GRID, BLOCK, 0, s, S, grids, __VA_ARGS__); \
+    } else {                                                                      \
+      if (plane)                                                                  \
+        hipLaunchKernelGGL((INST(2, true)), GRID, BLOCK, 0, s, S, grids, __VA_ARGS__);  \
+      else                                                                        \
+        hipLaunchKernelGGL((INST(2, false)), GRID, BLOCK, 0, s, S, grids, __VA_ARGS__); \
+    }                                                                             \
+  } while (0)
+void launch_icp_step_pairs(int dim, bool plane, const SliceDev& S, const GridDev* grids, const ProblemDev* probs,
+                           ProblemState* states, int K, int max_nm, hipStream_t s) {
+  if (K <= 0 || max_nm <= 0) return;
+  const dim3 grid((max_nm + 255) / 256, K);
+#define INST(D, P) k_icp_step_pairs<D, P>
+  PAIRS_LAUNCH(INST, grid, dim3(256), probs, states);
+#undef INST
+}
+void launch_icp_step_fast_pairs(int dim, bool plane, const SliceDev& S, const GridDev* grids, const ProblemDev* probs,
+                                ProblemState* states, int K, int max_nm, int ppt, bool gather, hipStream_t s) {
+  if (K <= 0 || max_nm <= 0) return;
+  const int p = ppt >= 2 ? 2 : 1;  // (two points per thread from 64 alignments per launch on: run_compute's fast_ppt_of)
+  const dim3 grid((max_nm + 256 * p - 1) / (256 * p), K);
+#define INST_2G(D, P) k_icp_step_fast_pairs<D, P, 2, true>
+#define INST_2N(D, P) k_icp_step_fast_pairs<D, P, 2, false>
+#define INST_1G(D, P) k_icp_step_fast_pairs<D, P, 1, true>
+#define INST_1N(D, P) k_icp_step_fast_pairs<D, P, 1, false>
+  if (p == 2) {
+    if (gather)
+      PAIRS_LAUNCH(INST_2G, grid, dim3(256), probs, states);
+    else
+      PAIRS_LAUNCH(INST_2N, grid, dim3(256), probs, states);
+  } else {
+    if (gather)
+      PAIRS_LAUNCH(INST_1G, grid, dim3(256), probs, states);
+    else
+      PAIRS_LAUNCH(INST_1N, grid, dim3(256), probs, states);
+  }
+#undef INST_2G
+#undef INST_2N
+#undef INST_1G
+#undef INST_1N
+}
+void launch_icp_small_pairs(int dim, bool plane, const SliceDev& S, const GridDev* grids, const CtlParams& C, const ProblemDev* probs,
+                            ProblemState* states, srrg2_iteration_stats* stats, ProblemOut* outs_host,
+                            srrg2_iteration_stats* stats_host, hipStream_t s) {
+  if (C.K <= 0) return;
+#define INST(D, P) k_icp_small_pairs<D, P>
+  PAIRS_LAUNCH(INST, dim3(C.K), dim3(512), C, probs, states, stats, outs_host, stats_host);
+#undef INST
+}
+#undef PAIRS_LAUNCH
 // The LAST control step of a compute() with fused control steps, on one wave (wave_control) with the post / finalize steps
 // behind it: the 256-thread k_icp_control_final stages the 3.4 KB state through LDS around a 238-register body; this one reads
 // the record + the slot sets, runs the lane-distributed step and finalizes from what that step left in its registers

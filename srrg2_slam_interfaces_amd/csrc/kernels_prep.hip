@@ -362,6 +362,112 @@ __global__ void k_grid_scatter(GridDev g, const float4* __restrict__ pts, const 
 }
 
 // ============================================================================================
+// Pair batches (srrg2_align_pairs): K fixed clouds, one grid each, built together.  blockIdx.y = pair, its points
+// [moff, moff + nm) of the concatenation (fprobs); the pairs' grids come from the host's table (derived from the rows below).
+// ============================================================================================
+// ingest of coordinates and normals (what set_fixed's k_ingest_bbox and k_ingest do for one cloud) + the pair's row: bounding box,
+// finite points, max |component| of the normals (PAIR_ROW_WORDS, device_types.h)
+__global__ __launch_bounds__(256) void k_pairs_ingest(const float* __restrict__ src, int sf, const float* __restrict__ nsrc, int nsf,
+                                                      const ProblemDev* __restrict__ fprobs, int dim, float4* __restrict__ dst,
+                                                      float4* __restrict__ dst_nrm, unsigned* __restrict__ rows) {
+  const ProblemDev pd = fprobs[blockIdx.y];
+  unsigned v[PAIR_ROW_WORDS] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // (~min keys, max keys, count, normal norm: all start at 0)
+  float namax = 0.f;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < pd.nm; i += gridDim.x * blockDim.x) {
+    const float* q = src + (size_t) (pd.moff + i) * sf;
+    const float4 p = make_float4(q[0], q[1], dim == 3 ? q[2] : 0.f, 0.f);
+    dst[pd.moff + i] = p;
+    if (finite3(p.x, p.y, p.z)) {
+      v[6] += 1u;
+      const unsigned k[3] = {fkey(p.x), fkey(p.y), fkey(p.z)};
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        v[d]     = max(v[d], ~k[d]);
+        v[3 + d] = max(v[3 + d], k[d]);
+      }
+    }
+    if (nsrc) {  // (every component that is finite, as k_ingest with finite_per_point = 0)
+      const float* r = nsrc + (size_t) (pd.moff + i) * nsf;
+      const float nx = r[0], ny = r[1], nz = dim == 3 ? r[2] : 0.f;
+      dst_nrm[pd.moff + i] = make_float4(nx, ny, nz, 0.f);
+      if (isfinite(nx)) namax = fmaxf(namax, fabsf(nx));
+      if (isfinite(ny)) namax = fmaxf(namax, fabsf(ny));
+      if (isfinite(nz)) namax = fmaxf(namax, fabsf(nz));
+    }
+  }
+  v[PAIR_ROW_NINF] = __float_as_uint(namax);  // (non-negative floats order like their bit patterns)
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+    for (int d = 0; d < PAIR_ROW_WORDS; ++d) {
+      const unsigned x = (unsigned) __shfl_xor((int) v[d], off);
+      v[d]             = d == 6 ? v[d] + x : max(v[d], x);
+    }
+  __shared__ unsigned red[4][PAIR_ROW_WORDS];
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int d = 0; d < PAIR_ROW_WORDS; ++d) red[threadIdx.x >> 6][d] = v[d];
+  __syncthreads();
+  if (threadIdx.x < PAIR_ROW_WORDS) {  // (one atomic per block and word, none for a zero)
+    const int d = threadIdx.x;
+    unsigned* row = rows + (size_t) blockIdx.y * PAIR_ROW_WORDS;
+    if (d == 6) {
+      const unsigned t = (red[0][6] + red[1][6]) + (red[2][6] + red[3][6]);
+      if (t) atomicAdd(row + 6, t);
+    } else {
+      const unsigned t = max(max(red[0][d], red[1][d]), max(red[2][d], red[3][d]));
+      if (t) atomicMax(row + d, t);
+    }
+  }
+}
+
+// counting pass: non-finite points into the segment's last cell (ncell), which no search reads
+__global__ __launch_bounds__(256) void k_pairs_grid_count(const GridDev* __restrict__ grids, const ProblemDev* __restrict__ fprobs,
+                                                          const float4* __restrict__ pts) {
+  const ProblemDev pd = fprobs[blockIdx.y];
+  const GridDev g     = grids[blockIdx.y];
+  int* counts         = const_cast<int*>(g.cell_start);
+  const int sink      = g.nx * g.ny * g.nz;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < pd.nm; i += gridDim.x * blockDim.x) {
+    const float4 p = pts[pd.moff + i];
+    atomicAdd(&counts[finite3(p.x, p.y, p.z) ? grid_cell_of(g, p) : sink], 1);
+  }
+}
+
+// after the scan over all segments: the cell starts of segment k begin at the pair's offset; make them pair-local (entries
+// [0, ncell], the last = the pair's finite points, as cell_start[ncell] of set_fixed's grid)
+__global__ __launch_bounds__(256) void k_pairs_localize(const GridDev* __restrict__ grids, const ProblemDev* __restrict__ fprobs) {
+  const int off   = fprobs[blockIdx.y].moff;
+  const GridDev g = grids[blockIdx.y];
+  int* cs         = const_cast<int*>(g.cell_start);
+  const int ncell = g.nx * g.ny * g.nz;
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c <= ncell; c += gridDim.x * blockDim.x) cs[c] -= off;
+}
+
+// scatter (k_grid_scatter per pair): cursors of the whole concatenation, positions written pair-local
+__global__ __launch_bounds__(256) void k_pairs_grid_scatter(const GridDev* __restrict__ grids, const ProblemDev* __restrict__ fprobs,
+                                                            const float4* __restrict__ pts, const float4* __restrict__ nrm,
+                                                            const int* __restrict__ cs_base, int* __restrict__ cursor,
+                                                            float4* __restrict__ out_pts, float4* __restrict__ out_nrm,
+                                                            int* __restrict__ pos_of) {
+  const ProblemDev pd = fprobs[blockIdx.y];
+  const GridDev g     = grids[blockIdx.y];
+  int* cur            = cursor + (g.cell_start - cs_base);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < pd.nm; i += gridDim.x * blockDim.x) {
+    float4 p = pts[pd.moff + i];
+    if (!finite3(p.x, p.y, p.z)) {
+      pos_of[pd.moff + i] = 0;
+      continue;
+    }
+    const int pos = atomicAdd(&cur[grid_cell_of(g, p)], 1);  // (in [moff, moff + finite points of the pair))
+    p.w           = __int_as_float(i);
+    out_pts[pos]  = p;
+    pos_of[pd.moff + i] = pos - pd.moff;
+    if (nrm) out_nrm[pos] = nrm[pd.moff + i];
+  }
+}
+
+// ============================================================================================
 // Cell neighbour lists (GridDev::list_*; the search passes of k_icp_step_cnl walk them).  One thread per cell of the
 // extended grid walks the offset table (host-built: the offsets d with cls_b2[class(d)] <= extended gate^2, sorted by
 // (class, centre distance)) and emits one entry per CNL_ENTRY_MAX points of every occupied target cell -- k_cnl_count counts them,
@@ -864,6 +970,30 @@ void launch_grid_scatter(const GridDev& g, const float4* pts, const float4* nrm,
                          float4* out_nrm, int* pos_of, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(k_grid_scatter, dim3((n + 255) / 256), dim3(256), 0, s, g, pts, nrm, n, cursor, out_pts, out_nrm, pos_of);
+}
+
+static int pairs_blocks(int n) {
+  const int b = (n + 255) / 256;
+  return b < 1 ? 1 : (b > 256 ? 256 : b);
+}
+
+void launch_pairs_ingest(const float* src, int sf, const float* nsrc, int nsf, const ProblemDev* fprobs, int K, int max_nf, int dim,
+                         float4* dst, float4* dst_nrm, unsigned* rows, hipStream_t s) {
+  if (K <= 0 || max_nf <= 0) return;
+  hipLaunchKernelGGL(k_pairs_ingest, dim3(pairs_blocks(max_nf), K), dim3(256), 0, s, src, sf, nsrc, nsf, fprobs, dim, dst, dst_nrm,
+                     rows);
+}
+
+void launch_pairs_grid_build(const GridDev* grids, const ProblemDev* fprobs, int K, int max_nf, int max_cells, int total_cells,
+                             const float4* pts, const float4* nrm, int* cell_start, int* cursor, int* scan_sums, int* scan_total,
+                             float4* out_pts, float4* out_nrm, int* pos_of, hipStream_t s) {
+  if (K <= 0) return;
+  if (max_nf > 0) hipLaunchKernelGGL(k_pairs_grid_count, dim3(pairs_blocks(max_nf), K), dim3(256), 0, s, grids, fprobs, pts);
+  launch_exclusive_scan(cell_start, total_cells, scan_sums, scan_total, s, cursor);
+  hipLaunchKernelGGL(k_pairs_localize, dim3(pairs_blocks(max_cells + 1), K), dim3(256), 0, s, grids, fprobs);
+  if (max_nf > 0)
+    hipLaunchKernelGGL(k_pairs_grid_scatter, dim3(pairs_blocks(max_nf), K), dim3(256), 0, s, grids, fprobs, pts, nrm, cell_start,
+                       cursor, out_pts, out_nrm, pos_of);
 }
 
 void launch_msort(const float4* pts, const float4* nrm, const ProblemDev* probs, int K, int max_nm, int kbits, int aniso,
