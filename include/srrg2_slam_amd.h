@@ -336,6 +336,43 @@ int srrg2_align_pairs(srrg2_aligner_h h, int K,
                       int mem /* SRRG2_MEM_HOST | SRRG2_MEM_DEVICE */, const float* guesses /* K x 12 (or 9) */,
                       srrg2_batch_result* results);
 
+/* The K moving clouds of one cue slice in a srrg2_align_batch_slices call: concatenated, offsets[K+1] in points.  A prior slice
+ * or a slice that shares another slice's clouds (share_clouds) has an all-null entry. */
+typedef struct srrg2_batch_slice_clouds {
+  const float*   coords;  int coord_stride_bytes;
+  const float*   normals; int normal_stride_bytes;   /* null: none */
+  const int32_t* offsets;                            /* K+1 (in points); null: no entry */
+} srrg2_batch_slice_clouds;
+
+/* K independent alignments against the bound fixed clouds, every cue slice with a moving cloud of its own per alignment
+ * (the loop of MultiLoopDetectorBruteForce_ / MultiRelocalizer_, which bind a whole property container per candidate:
+ * every slice picks its moving cloud by name).  Result k is bit for bit what a handle with the same slices, params,
+ * termination and tuning returns from
+ *   set_moving(s, M[s][k], N[s][k]) for every cue slice s that owns its clouds; set_moving_in_fixed(G_k); compute()
+ * Slices bound by share_clouds take their source's cloud k; prior slices use the handle's prior measurement and fixed clouds
+ * are the ones bound with set_fixed (as in compute_batch).  A slice's cloud k may be empty: the result is then what compute()
+ * gives with that empty cloud bound.  Every (slice, alignment) sizes its fixed-point exponent from its own cloud.
+ *   clouds       [nslices], one entry per slice of the handle; all clouds in host memory or all in device memory (`mem`).
+ *   supported    any number of cue slices up to SRRG2_MAX_SLICES: nearest-neighbour P2P / P2PLANE slices with clouds of their
+ *                own, projective slices (shared clouds too: the RGB-D pack of a point-to-plane and a reprojection slice),
+ *                mixtures of the two, prior slices anywhere; SE2_RIGHT, SE3_EULER_RIGHT, SE3_QUAT_RIGHT (projective and
+ *                reprojection slices: SE(3) only, as everywhere).
+ *   refused      before anything is bound, the handle unchanged.  SRRG2_E_INVALID: nslices differs from the handle's slice
+ *                count, K < 0 or K > 65535, a cue slice that owns its clouds without offsets, a prior or sharing slice with a
+ *                non-empty entry, decreasing offsets, null pointers where points exist, bad strides, SRRG2_MEM_DEVICE_KEPT.
+ *                SRRG2_E_UNSUPPORTED: a given-correspondences slice (compute_batch_correspondences is its batch), a handle
+ *                with set_point_shard.  SRRG2_E_STATE: a cue slice without a fixed cloud, P2PLANE without fixed normals, a
+ *                projective slice whose fixed cloud is not rows x cols, a prior slice without measurement.  K = 0 returns 0.
+ *   memory       a projective slice that owns its association reserves 2 K rows cols 64-bit z-buffer words (VGA: 157 MB at
+ *                K = 32, 1.26 GB at K = 256); the batch runs as one launch sequence (no pipelined parts).
+ *   returns      after it has finished reading the caller's buffers, on success and on error (as compute_batch).
+ *   handle after status, estimate, iteration stats and information are those of alignment K-1 (as after compute_batch);
+ *                every cue slice's get_correspondences / get_factor_status returns alignment K-1's records.  The moving
+ *                clouds of the batch stay bound as a batch: a plain compute() needs set_moving first (SRRG2_E_STATE). */
+int srrg2_align_batch_slices(srrg2_aligner_h h, int K, int nslices, const srrg2_batch_slice_clouds* clouds /* [nslices] */,
+                             int mem /* SRRG2_MEM_HOST | SRRG2_MEM_DEVICE */, const float* guesses /* K x 12 (or 9) */,
+                             srrg2_batch_result* results);
+
 /* ---- multi-GPU (no reference counterpart) ------------------------------------------
  * Loop-closure candidate alignments are independent: alignment k of K lives on rank k mod G, one process per GPU, one
  * aligner handle per process on its own device; there is no exchange while the alignments run.  The library does not

@@ -14,6 +14,7 @@
 //   DescriptorDatabase              srrg_hbst::BinaryTree256 in MultiLoopDetectorHBST_  multi_loop_detector_hbst_impl.cpp:41-197
 //   (loop-closure drivers and the pose graph: srrg2_slam_amd_loop_closure.hpp)
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstring>
 #include <deque>
@@ -110,8 +111,10 @@ public:
   int addSlice(const srrg2_slice_config& c) {
     int idx = -1;
     check(srrg2_aligner_add_slice(_h, &c, &idx));
+    _nslices = idx + 1;
     return idx;
   }
+  int numSlices() const { return _nslices; }
   static srrg2_slice_config defaultSliceConfig() {
     srrg2_slice_config c;
     srrg2_slice_default_config(&c, VARIABLE_KIND);
@@ -232,6 +235,53 @@ public:
                               results.data()));
     return results;
   }
+  // one cue slice's K moving clouds in a computeBatchSlices call: K pointers to packed Dim-float records with their sizes,
+  // normals empty (none) or K pointers
+  struct SliceClouds {
+    int slice = 0;
+    std::vector<const float*> clouds;
+    std::vector<int> sizes;
+    std::vector<const float*> normals;
+  };
+  // K independent alignments against the bound fixed clouds, every cue slice with a moving cloud of its own per alignment
+  // (srrg2_align_batch_slices): what K x { setMoving per slice; setMovingInFixed; compute() } returns, in one call.  `slices`:
+  // the cue slices that own their clouds (a slice bound by shareClouds takes its source's; prior slices have no entry).
+  std::vector<srrg2_batch_result> computeBatchSlices(const std::vector<SliceClouds>& slices, const std::vector<EstimateType>& guesses) {
+    const int K = (int) guesses.size();
+    std::vector<srrg2_batch_slice_clouds> entries((size_t) std::max(_nslices, 1));
+    std::memset(entries.data(), 0, sizeof(srrg2_batch_slice_clouds) * entries.size());
+    std::vector<std::vector<int32_t>> offsets(slices.size());
+    std::vector<std::vector<float>> coords(slices.size()), nrm(slices.size());
+    for (size_t i = 0; i < slices.size(); ++i) {
+      const SliceClouds& sc = slices[i];
+      if (sc.slice < 0 || sc.slice >= _nslices) throw std::runtime_error("MultiAligner_::computeBatchSlices|bad slice index");
+      if ((int) sc.clouds.size() != K || (int) sc.sizes.size() != K || (!sc.normals.empty() && (int) sc.normals.size() != K))
+        throw std::runtime_error("MultiAligner_::computeBatchSlices|inconsistent argument sizes");
+      offsets[i].assign((size_t) K + 1, 0);
+      for (int k = 0; k < K; ++k) offsets[i][(size_t) k + 1] = offsets[i][(size_t) k] + sc.sizes[(size_t) k];
+      coords[i].resize((size_t) offsets[i][(size_t) K] * Dim);
+      if (!sc.normals.empty()) nrm[i].resize(coords[i].size());
+      for (int k = 0; k < K; ++k) {
+        const size_t off = (size_t) offsets[i][(size_t) k] * Dim, bytes = sizeof(float) * (size_t) sc.sizes[(size_t) k] * Dim;
+        if (bytes) std::memcpy(coords[i].data() + off, sc.clouds[(size_t) k], bytes);
+        if (bytes && !sc.normals.empty()) std::memcpy(nrm[i].data() + off, sc.normals[(size_t) k], bytes);
+      }
+      srrg2_batch_slice_clouds& e = entries[(size_t) sc.slice];
+      e.coords              = coords[i].data();
+      e.coord_stride_bytes  = Dim * 4;
+      e.normals             = sc.normals.empty() ? nullptr : nrm[i].data();
+      e.normal_stride_bytes = Dim * 4;
+      e.offsets             = offsets[i].data();
+    }
+    std::vector<float> g((size_t) K * EstimateType::N);
+    for (int k = 0; k < K; ++k) std::memcpy(g.data() + (size_t) k * EstimateType::N, guesses[(size_t) k].data(), sizeof(float) * EstimateType::N);
+    srrg2_aligner_params p{param_max_iterations, param_min_num_inliers, param_enable_inlier_only_runs ? 1 : 0,
+                           param_keep_only_inlier_correspondences ? 1 : 0};
+    check(srrg2_aligner_set_params(_h, &p));
+    std::vector<srrg2_batch_result> results((size_t) K);
+    if (K) check(srrg2_align_batch_slices(_h, K, _nslices, entries.data(), SRRG2_MEM_HOST, g.data(), results.data()));
+    return results;
+  }
   // slice `slice` reads the clouds of slice `source` (two slices with the same fixed_slice_name / moving_slice_name bind to
   // the same clouds of the scene: aligner_slice_processor_base_impl.cpp:27-50); -1: clouds of its own again
   void shareClouds(int slice, int source) { check(srrg2_aligner_share_clouds(_h, slice, source)); }
@@ -266,6 +316,7 @@ public:
 
 private:
   srrg2_aligner_h _h = nullptr;
+  int _nslices       = 0;
   Status _status     = Fail;  // aligner.h:56
   mutable EstimateType _X = EstimateType::Identity();
   IterationStatsVector _iteration_stats;

@@ -62,6 +62,60 @@ struct LoopClosure {
   float aligner_information[D * D] = {};
 };
 
+// ---- SliceCloud: one slice's cloud of a local map -------------------------------------------------------------------------
+// (an aligner with several cue slices: the reference binds a local map's whole property container and every slice picks its
+// cloud by name, multi_loop_detector_brute_force_impl.cpp:63-79, multi_relocalizer_impl.cpp:74-87)
+struct SliceCloud {
+  int slice            = 0;
+  const float* coords  = nullptr;  // packed DIM-float records
+  const float* normals = nullptr;  // null: none
+  int size             = 0;
+};
+
+// the moving clouds of a detector's / relocaliser's candidates as computeBatchSlices entries: every candidate names the same
+// slices in the same order
+template <typename SliceClouds>
+std::vector<SliceClouds> gatherSliceClouds(const std::vector<const std::vector<SliceCloud>*>& per_candidate, const char* who) {
+  std::vector<SliceClouds> out;
+  if (per_candidate.empty()) return out;
+  const std::vector<SliceCloud>& first = *per_candidate[0];
+  out.resize(first.size());
+  for (size_t i = 0; i < first.size(); ++i) out[i].slice = first[i].slice;
+  std::vector<char> with_normals(first.size(), 1);
+  for (const std::vector<SliceCloud>* c : per_candidate) {
+    if (c->size() != first.size()) throw std::runtime_error(std::string(who) + "| candidates carry different slices");
+    for (size_t i = 0; i < first.size(); ++i) {
+      if ((*c)[i].slice != first[i].slice) throw std::runtime_error(std::string(who) + "| candidates carry different slices");
+      if (!(*c)[i].normals) with_normals[i] = 0;
+    }
+  }
+  for (size_t i = 0; i < first.size(); ++i) {
+    bool any_normals = false;
+    for (const std::vector<SliceCloud>* c : per_candidate) {
+      out[i].clouds.push_back((*c)[i].coords);
+      out[i].sizes.push_back((*c)[i].size);
+      out[i].normals.push_back((*c)[i].normals);
+      any_normals = any_normals || (*c)[i].normals;
+    }
+    if (!with_normals[i]) {
+      if (any_normals) throw std::runtime_error(std::string(who) + "| some candidates carry normals and some do not");
+      out[i].normals.clear();
+    }
+  }
+  return out;
+}
+
+// aligner->setFixed(container) on every handle: slice 0's cloud, or every slice's of `fixed_slices`
+template <typename Sharded>
+void setFixedOn(Sharded& sharded, const std::vector<SliceCloud>& fixed_slices, const float* coords, const float* normals, int n) {
+  constexpr int DIM = Sharded::Dim;
+  if (fixed_slices.empty()) {
+    sharded.setFixed(0, coords, DIM * 4, normals, DIM * 4, n);
+    return;
+  }
+  for (const SliceCloud& f : fixed_slices) sharded.setFixed(f.slice, f.coords, DIM * 4, f.normals, DIM * 4, f.size);
+}
+
 // ---- ClosureHint: a candidate local map with the initial guess of target-in-source -----------------------------------------
 template <int DIM>
 struct ClosureHint {
@@ -72,6 +126,8 @@ struct ClosureHint {
   const float* moving         = nullptr;
   const float* moving_normals = nullptr;
   int size = 0;
+  // not empty: the candidate's cloud per slice (an aligner with several cue slices; `moving` is not read then)
+  std::vector<SliceCloud> moving_slices;
 };
 
 // ---- LocalMapSelectorBreadthFirst_ ----------------------------------------------------------------------------------------
@@ -161,7 +217,10 @@ public:
   // the fixed side: the current local map's slice (aligner->setFixed once, _impl.cpp:63)
   void setFixed(const float* coords, const float* normals, int n) {
     _fixed = coords; _fixed_normals = normals; _nfixed = n;
+    _fixed_slices.clear();
   }
+  // ... or its cloud per slice (an aligner with several cue slices)
+  void setFixed(const std::vector<SliceCloud>& fixed) { _fixed_slices = fixed; }
   // one independent alignment per hint (:64-79) -- ONE compute_batch call -- then the accept gates (:80-112) and the
   // closure record (:120-131)
   const std::vector<LoopClosureType>& compute(int source_local_map_id, const std::vector<ClosureHint<DIM>>& hints,
@@ -173,10 +232,12 @@ public:
     std::vector<const float*> clouds, normals;
     std::vector<int> sizes, ids;
     std::vector<EstimateType> guesses;
+    std::vector<const std::vector<SliceCloud>*> per_slice;
     bool all_normals = true;
     for (const ClosureHint<DIM>& h : hints) {
-      if (!h.moving) continue;  // :71-75: a hint without the slice is skipped
+      if (!h.moving && h.moving_slices.empty()) continue;  // :71-75: a hint without the slice is skipped
       _attempted_closures.push_back(h.local_map_id);
+      if (!h.moving_slices.empty()) per_slice.push_back(&h.moving_slices);
       clouds.push_back(h.moving);
       normals.push_back(h.moving_normals);
       all_normals = all_normals && h.moving_normals != nullptr;
@@ -185,7 +246,9 @@ public:
       guesses.push_back(h.initial_guess);
     }
     if (clouds.empty()) return _detected_closures;
-    if (!all_normals) {
+    if (!per_slice.empty() && per_slice.size() != clouds.size())
+      throw std::runtime_error("MultiLoopDetectorBruteForce_::compute| some hints carry per-slice clouds and some do not");
+    if (!all_normals && per_slice.empty()) {
       for (const float* nm : normals)
         if (nm) throw std::runtime_error("MultiLoopDetectorBruteForce_::compute| some hints carry normals and some do not");
       normals.clear();
@@ -193,8 +256,12 @@ public:
     std::vector<AlignerType*> handles{param_relocalize_aligner};
     handles.insert(handles.end(), param_relocalize_aligners.begin(), param_relocalize_aligners.end());
     ShardedAligners<AlignerType> sharded(handles);
-    sharded.setFixed(0, _fixed, DIM * 4, _fixed_normals, DIM * 4, _nfixed);  // aligner->setFixed, once per handle (:63)
-    const std::vector<srrg2_batch_result> results = sharded.computeBatch(clouds, sizes, normals, guesses);
+    setFixedOn(sharded, _fixed_slices, _fixed, _fixed_normals, _nfixed);  // aligner->setFixed, once per handle (:63)
+    const std::vector<srrg2_batch_result> results =
+        per_slice.empty() ? sharded.computeBatch(clouds, sizes, normals, guesses)
+                          : sharded.computeBatchSlices(
+                                gatherSliceClouds<typename AlignerType::SliceClouds>(per_slice, "MultiLoopDetectorBruteForce_::compute"),
+                                guesses);
     for (size_t k = 0; k < results.size(); ++k) {
       const srrg2_batch_result& r = results[k];
       if (r.status != AlignerBase::Success) {  // :80-84
@@ -239,6 +306,7 @@ private:
   const float* _fixed         = nullptr;
   const float* _fixed_normals = nullptr;
   int _nfixed                 = 0;
+  std::vector<SliceCloud> _fixed_slices;
   std::vector<int> _attempted_closures;
   std::vector<LoopClosureType> _detected_closures;
   std::vector<std::pair<int, std::string>> _drops;
@@ -264,11 +332,15 @@ public:
     const float* moving         = nullptr;
     const float* moving_normals = nullptr;
     int size                    = 0;
+    std::vector<SliceCloud> moving_slices;  // not empty: the target's cloud per slice (`moving` is not read then)
   };
   // the current measurement (aligner->setFixed(&tracker->measurementContainer()), _impl.cpp:78)
   void setFixed(const float* coords, const float* normals, int n) {
     _fixed = coords; _fixed_normals = normals; _nfixed = n;
+    _fixed_slices.clear();
   }
+  // ... or its cloud per slice (an aligner with several cue slices)
+  void setFixed(const std::vector<SliceCloud>& fixed) { _fixed_slices = fixed; }
   // returns the id of the relocalization map or -1
   int compute(const std::vector<Candidate>& candidates) {
     _relocalization_map = -1;
@@ -309,7 +381,7 @@ public:
     {  // a candidate whose local map does not carry the slice cannot be aligned: dropped like a hint without one
       std::vector<const Candidate*> with_cloud;
       for (const Candidate* c : near) {
-        if (c->moving && c->size > 0)
+        if ((c->moving && c->size > 0) || !c->moving_slices.empty())
           with_cloud.push_back(c);
         else
           _drops.emplace_back(c->closure.target_graph_id, "NO_SLICE DROP");
@@ -320,8 +392,10 @@ public:
     std::vector<const float*> clouds, normals;
     std::vector<int> sizes;
     std::vector<EstimateType> guesses;
+    std::vector<const std::vector<SliceCloud>*> per_slice;
     bool all_normals = true, any_normals = false;
     for (const Candidate* c : near) {
+      if (!c->moving_slices.empty()) per_slice.push_back(&c->moving_slices);
       clouds.push_back(c->moving);
       normals.push_back(c->moving_normals);
       all_normals = all_normals && c->moving_normals != nullptr;
@@ -329,15 +403,20 @@ public:
       sizes.push_back(c->size);
       guesses.push_back(c->closure.pose_in_target.inverse());  // :91
     }
-    if (!all_normals) {
+    if (!per_slice.empty() && per_slice.size() != near.size())
+      throw std::runtime_error("MultiRelocalizer_::compute| some candidates carry per-slice clouds and some do not");
+    if (!all_normals && per_slice.empty()) {
       if (any_normals) throw std::runtime_error("MultiRelocalizer_::compute| some candidates carry normals and some do not");
       normals.clear();
     }
     std::vector<AlignerType*> handles{param_aligner};
     handles.insert(handles.end(), param_aligners.begin(), param_aligners.end());
     ShardedAligners<AlignerType> sharded(handles);
-    sharded.setFixed(0, _fixed, DIM * 4, _fixed_normals, DIM * 4, _nfixed);
-    const std::vector<srrg2_batch_result> results = sharded.computeBatch(clouds, sizes, normals, guesses);
+    setFixedOn(sharded, _fixed_slices, _fixed, _fixed_normals, _nfixed);
+    const std::vector<srrg2_batch_result> results =
+        per_slice.empty() ? sharded.computeBatch(clouds, sizes, normals, guesses)
+                          : sharded.computeBatchSlices(
+                                gatherSliceClouds<typename AlignerType::SliceClouds>(per_slice, "MultiRelocalizer_::compute"), guesses);
     float best_chi_average = std::numeric_limits<float>::max();
     for (size_t k = 0; k < results.size(); ++k) {
       const srrg2_batch_result& r = results[k];
@@ -382,6 +461,7 @@ private:
   const float* _fixed         = nullptr;
   const float* _fixed_normals = nullptr;
   int _nfixed                 = 0;
+  std::vector<SliceCloud> _fixed_slices;
   int _relocalization_map     = -1;
   bool _relocalized           = false;
   LoopClosureType _relocalized_closure;

@@ -82,6 +82,34 @@ public:
     return results;
   }
 
+  // the same for an aligner with several cue slices (computeBatchSlices): alignment k -> handle k mod G, every slice's cloud k
+  // with it
+  using SliceClouds = typename AlignerType::SliceClouds;
+  std::vector<srrg2_batch_result> computeBatchSlices(const std::vector<SliceClouds>& slices, const std::vector<EstimateType>& guesses) {
+    const int K = (int) guesses.size(), G = size();
+    for (const SliceClouds& sc : slices)
+      if ((int) sc.clouds.size() != K || (int) sc.sizes.size() != K || (!sc.normals.empty() && (int) sc.normals.size() != K))
+        throw std::runtime_error("ShardedAligners::computeBatchSlices|inconsistent argument sizes");
+    std::vector<srrg2_batch_result> results((size_t) K);
+    forEach([&](int g) {
+      std::vector<SliceClouds> mine(slices.size());
+      std::vector<EstimateType> gs;
+      for (int k = g; k < K; k += G) {
+        for (size_t i = 0; i < slices.size(); ++i) {
+          mine[i].slice = slices[i].slice;
+          mine[i].clouds.push_back(slices[i].clouds[(size_t) k]);
+          mine[i].sizes.push_back(slices[i].sizes[(size_t) k]);
+          if (!slices[i].normals.empty()) mine[i].normals.push_back(slices[i].normals[(size_t) k]);
+        }
+        gs.push_back(guesses[(size_t) k]);
+      }
+      if (gs.empty()) return;
+      const std::vector<srrg2_batch_result> r = _a[(size_t) g]->computeBatchSlices(mine, gs);
+      for (size_t j = 0; j < r.size(); ++j) results[(size_t) g + j * (size_t) G] = r[j];
+    });
+    return results;
+  }
+
   // The K x SRRG2_RECORD_FLOATS table of SURVEY.md 8e: handle g packs ITS rows (srrg2_multi_gpu_pack_record) into a
   // zero table, the G tables are added.  x + 0 = x: the sum holds every record unchanged, H included -- what the
   // multi-process path obtains with ONE all-reduce(sum) over RCCL.

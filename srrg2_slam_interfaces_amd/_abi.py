@@ -96,6 +96,17 @@ class BatchResult(C.Structure):
     ]
 
 
+class BatchSliceClouds(C.Structure):
+    """srrg2_batch_slice_clouds: one slice's K moving clouds in a srrg2_align_batch_slices call (all null: no entry)"""
+    _fields_ = [
+        ("coords", C.POINTER(C.c_float)),
+        ("coord_stride_bytes", C.c_int32),
+        ("normals", C.POINTER(C.c_float)),
+        ("normal_stride_bytes", C.c_int32),
+        ("offsets", C.POINTER(C.c_int32)),
+    ]
+
+
 # srrg2_aligner_tuning.strategy_mask: the only bits srrg2_aligner_set_tuning accepts (each forces a path the library also
 # takes by itself on other configurations)
 TUNE_PROJ_SEPARATE_LAUNCHES = 1 << 17  # projective slices in launches of their own

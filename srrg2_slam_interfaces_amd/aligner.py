@@ -445,26 +445,30 @@ class MultiAligner:
         K = len(fixed_clouds)
         g = _as_f32(np.asarray(guesses)).reshape(K, self.tsize)
         res = (abi.BatchResult * max(K, 1))()
-        D = 3 if self.dim == 2 else 6
         for k in range(K):
             self.set_fixed(0, np.asarray(fixed_clouds[k]).reshape(-1, self.dim),
                            None if fixed_normals is None else np.asarray(fixed_normals[k]).reshape(-1, self.dim))
             self.set_moving(0, np.asarray(moving_clouds[k]).reshape(-1, self.dim),
                             None if moving_normals is None else np.asarray(moving_normals[k]).reshape(-1, self.dim))
             self.set_moving_in_fixed(g[k])
-            r = res[k]
-            r.status = self.compute()
-            r.moving_in_fixed[:self.tsize] = self.moving_in_fixed().reshape(-1).tolist()
-            n = C.c_int(0)
-            self._check(self._b.fn("get_iteration_stats")(self._h, None, C.byref(n)))
-            r.num_iterations = n.value
-            if n.value > 0:
-                buf = (abi.IterationStats * n.value)()
-                self._check(self._b.fn("get_iteration_stats")(self._h, buf, C.byref(n)))
-                r.last = buf[n.value - 1]
-            r.num_correspondences = self.num_correspondences()
-            r.information[:D * D] = self.information().reshape(-1).tolist()
+            self._compute_into(res[k])
         return self._unpack_batch(res, K)
+
+    def _compute_into(self, r):
+        """compute() and the handle's result, as one srrg2_batch_result record (the defining loops of the batch calls)"""
+        D = 3 if self.dim == 2 else 6
+        r.status = self.compute()
+        r.moving_in_fixed[:self.tsize] = self.moving_in_fixed().reshape(-1).tolist()
+        n = C.c_int(0)
+        self._check(self._b.fn("get_iteration_stats")(self._h, None, C.byref(n)))
+        r.num_iterations = n.value
+        if n.value > 0:
+            buf = (abi.IterationStats * n.value)()
+            self._check(self._b.fn("get_iteration_stats")(self._h, buf, C.byref(n)))
+            r.last = buf[n.value - 1]
+        r.num_correspondences = self.num_correspondences()
+        if n.value > 0:  # (a compute() without an iteration has no H of its own: zeros, as in the batch records)
+            r.information[:D * D] = self.information().reshape(-1).tolist()
 
     def compute_batch_pairs(self, fixed_clouds, moving_clouds, guesses, fixed_normals=None, moving_normals=None):
         """K independent alignments, fixed cloud k against moving cloud k (srrg2_align_pairs): bit for bit what
@@ -516,4 +520,96 @@ class MultiAligner:
                       foff.ctypes.data_as(i32), C.cast(moving_ptr, fp), C.c_int(moving_stride),
                       C.cast(moving_normals_ptr, fp) if moving_normals_ptr else None, C.c_int(moving_normal_stride),
                       moff.ctypes.data_as(i32), C.c_int(abi.MEM_DEVICE), _fptr(g), res))
+        return self._unpack_batch(res, K)
+
+    # -- multi-cue batches (srrg2_align_batch_slices) -------------------------------------
+    def _batch_slices_fn(self):
+        """the library's multi-cue batch entry point, or None on a backend without it (the oracle binding)"""
+        if self._b.prefix != "srrg2_aligner_":
+            return None
+        try:
+            return self._b.lib.srrg2_align_batch_slices
+        except AttributeError:
+            return None
+
+    def _slices_loop(self, moving, guesses, moving_normals):
+        """the defining loop of a multi-cue batch: set_moving of every slice in ``moving`` / set_moving_in_fixed / compute() per
+        alignment (leaves the last alignment's clouds bound, as any such loop does)"""
+        K = len(guesses)
+        g = _as_f32(np.asarray(guesses)).reshape(K, self.tsize)
+        res = (abi.BatchResult * max(K, 1))()
+        for k in range(K):
+            for si in sorted(moving):
+                nrm = None if not moving_normals or moving_normals.get(si) is None else moving_normals[si][k]
+                self.set_moving(si, np.asarray(moving[si][k]).reshape(-1, self.dim),
+                                None if nrm is None else np.asarray(nrm).reshape(-1, self.dim))
+            self.set_moving_in_fixed(g[k])
+            self._compute_into(res[k])
+        return self._unpack_batch(res, K)
+
+    def _slices_entries(self, K, moving, moving_normals, keep):
+        """srrg2_batch_slice_clouds[nslices] from {slice: [K clouds]} (the arrays it points into appended to ``keep``)"""
+        entries = (abi.BatchSliceClouds * max(len(self.slices), 1))()
+        for si, clouds in moving.items():
+            if not 0 <= si < len(self.slices):
+                raise ValueError("compute_batch_slices: no slice %d" % si)
+            if len(clouds) != K:
+                raise ValueError("compute_batch_slices: slice %d has %d clouds for %d guesses" % (si, len(clouds), K))
+            parts = [_as_f32(c).reshape(-1, self.dim) for c in clouds]
+            offsets = np.zeros(K + 1, dtype=np.int32)
+            offsets[1:] = np.cumsum([p.shape[0] for p in parts])
+            coords = _as_f32(np.concatenate(parts, axis=0)) if K else np.zeros((0, self.dim), np.float32)
+            e = entries[si]
+            e.coords, e.coord_stride_bytes = _fptr(coords), self.dim * 4
+            e.offsets = offsets.ctypes.data_as(C.POINTER(C.c_int32))
+            keep += [coords, offsets]
+            if moving_normals and moving_normals.get(si) is not None:
+                normals = _as_f32(np.concatenate([_as_f32(n).reshape(-1, self.dim) for n in moving_normals[si]], axis=0))
+                if normals.shape != coords.shape:
+                    raise ValueError("compute_batch_slices: slice %d: normals and clouds differ in size" % si)
+                e.normals, e.normal_stride_bytes = _fptr(normals), self.dim * 4
+                keep.append(normals)
+        return entries
+
+    def compute_batch_slices(self, moving, guesses, moving_normals=None):
+        """K independent alignments against the bound fixed clouds, every cue slice with a moving cloud of its own per
+        alignment (srrg2_align_batch_slices).  ``moving``: {slice_idx: [K clouds]} for the cue slices that own their clouds
+        (a slice bound by share_clouds takes its source's), ``moving_normals`` the same form or None.  Bit for bit what
+        K x {set_moving per slice; set_moving_in_fixed; compute()} returns; on a backend without the entry point (the oracle)
+        it runs that loop."""
+        K = len(guesses)
+        moving = {int(si): list(c) for si, c in moving.items()}
+        moving_normals = None if moving_normals is None else {int(si): (None if c is None else list(c))
+                                                              for si, c in moving_normals.items()}
+        f = self._batch_slices_fn()
+        if f is None:
+            return self._slices_loop(moving, guesses, moving_normals)
+        keep = []
+        entries = self._slices_entries(K, moving, moving_normals, keep)
+        g = _as_f32(np.asarray(guesses)).reshape(K, self.tsize)
+        res = (abi.BatchResult * max(K, 1))()
+        self._check(f(self._h, C.c_int(K), C.c_int(len(self.slices)), entries, C.c_int(abi.MEM_HOST), _fptr(g), res))
+        return self._unpack_batch(res, K)
+
+    def compute_batch_slices_device(self, entries, guesses):
+        """compute_batch_slices on clouds already resident in HBM: ``entries`` = {slice_idx: (coords_ptr, coord_stride,
+        normals_ptr or 0, normal_stride, offsets[K+1])} with raw device pointers as ints, strides in bytes, offsets in points."""
+        f = self._batch_slices_fn()
+        if f is None:
+            raise RuntimeError("compute_batch_slices_device: the backend has no srrg2_align_batch_slices")
+        K = len(guesses)
+        arr = (abi.BatchSliceClouds * max(len(self.slices), 1))()
+        keep = []
+        fp = C.POINTER(C.c_float)
+        for si, (cp, cs, npt, nst, off) in entries.items():
+            off = np.ascontiguousarray(off, dtype=np.int32)
+            keep.append(off)
+            e = arr[si]
+            e.coords, e.coord_stride_bytes = C.cast(cp, fp), cs
+            if npt:
+                e.normals, e.normal_stride_bytes = C.cast(npt, fp), nst
+            e.offsets = off.ctypes.data_as(C.POINTER(C.c_int32))
+        g = _as_f32(np.asarray(guesses)).reshape(K, self.tsize)
+        res = (abi.BatchResult * max(K, 1))()
+        self._check(f(self._h, C.c_int(K), C.c_int(len(self.slices)), arr, C.c_int(abi.MEM_DEVICE), _fptr(g), res))
         return self._unpack_batch(res, K)

@@ -64,7 +64,8 @@ struct Slice {
   DevBuf<unsigned> pinf;  // per problem
   int nm_total            = 0;
   bool has_moving         = false;
-  bool moving_is_batch    = false;  // the bound moving cloud is the concatenation of a compute_batch with K > 1
+  bool moving_is_batch    = false;  // the bound moving cloud is the concatenation of a compute_batch with K > 1 (or of any
+                                    // align_batch_slices)
   bool moving_has_normals = false;
   // outputs
   DevBuf<int> corr_fixed;
@@ -822,8 +823,10 @@ int upload_moving(srrg2_aligner* a, int si, const float* coords, int cs, const f
 
 // pair_grids != null: a pair batch (srrg2_align_pairs) -- problem k searches the grid pair_grids[k] of its own fixed cloud (device
 // table) instead of slice 0's grid, on the pair instantiations of the grid kernels with control launches
+// slice_offsets != null: a multi-cue batch (srrg2_align_batch_slices) -- slice si's problem table from slice_offsets[si] (a slice
+// that shares clouds: its source's), any number of cue slices; null: every cue slice on `offsets` (compute_batch: one cue slice)
 int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null for K == 1 */, const float* guesses,
-                const GridDev* pair_grids = nullptr) {
+                const GridDev* pair_grids = nullptr, const int32_t* const* slice_offsets = nullptr) {
   auto t_begin = std::chrono::steady_clock::now();
   const bool pairs = pair_grids != nullptr;
   int rc;
@@ -871,7 +874,8 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     if (s->cfg.finder == SRRG2_FINDER_PROJECTIVE && s->nf != s->cfg.image_rows * s->cfg.image_cols)
       return fail(SRRG2_E_STATE, "compute: projective finder needs an organised fixed cloud of rows x cols points");
   }
-  // problems: all cue slices share the problem layout of slice 0's batch; for K == 1 each slice has its own nm
+  // problems: all cue slices share the problem layout of slice 0's batch (a multi-cue batch: each its own, slice_offsets); for
+  // K == 1 each slice has its own nm
   const int slots = 2 * std::max(a->params.max_iterations, 1);
   a->max_stats    = slots;
   if ((rc = a->probs.reserve((size_t) K * std::max(nslices, 1)))) return rc;
@@ -890,6 +894,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   std::vector<ProblemDev> all((size_t) K * std::max(nslices, 1));
   for (int si = 0; si < nslices; ++si) {
     Slice* s = a->slices[si];
+    const int32_t* off = slice_offsets ? slice_offsets[s->alias_of >= 0 ? s->alias_of : si] : offsets;
     for (int k = 0; k < K; ++k) {
       ProblemDev pd{0, 0};
       if (s->cfg.kind != SRRG2_SLICE_PRIOR) {
@@ -897,8 +902,8 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
           pd.moff = 0;
           pd.nm   = s->nm_total;
         } else {
-          pd.moff = offsets[k] - offsets[0];
-          pd.nm   = offsets[k + 1] - offsets[k];
+          pd.moff = off[k] - off[0];
+          pd.nm   = off[k + 1] - off[k];
         }
         max_nm = std::max(max_nm, pd.nm);
       }
@@ -1159,7 +1164,10 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
       dm::se2_inverse(s->cfg.sensor_in_robot, d.Sinv);
     std::memcpy(sc.Sinv, d.Sinv, sizeof(sc.Sinv));
   }
-  if (K > 1 && first_cue >= 0) {
+  // (a multi-cue batch, slice_offsets: every slice's passes read its own table; the launch-path decisions that look at one cue
+  // slice only -- small, fuse, fold_init, the pipelined parts -- never pick a multi-cue batch with K > 1: those need one cue slice
+  // or, fuse_proj, K == 1.  It runs on control launches, every slice's passes on the kernels its own size and lists choose.)
+  if (K > 1 && first_cue >= 0 && !slice_offsets) {
     for (int si = 0; si < nslices; ++si)
       if (a->slices[si]->cfg.kind != SRRG2_SLICE_PRIOR && si != first_cue)
         return fail(SRRG2_E_UNSUPPORTED, "compute_batch supports one cue slice (plus prior slices)");
@@ -2667,6 +2675,95 @@ int srrg2_align_pairs(srrg2_aligner_h a, int K, const float* fixed_coords, int f
   // (the moving cloud of the slice is unbound: a plain compute() needs set_moving first)
   s->has_moving      = false;
   s->moving_is_batch = false;
+  if (rc) return drain(rc);
+  fill_batch_results(a, K, results);
+  return 0;
+}
+
+int srrg2_align_batch_slices(srrg2_aligner_h a, int K, int nslices, const srrg2_batch_slice_clouds* clouds, int mem,
+                             const float* guesses, srrg2_batch_result* results) {
+  // (everything that can be refused is refused before the handle is touched)
+  if (!a) return fail(SRRG2_E_INVALID, "align_batch_slices: null handle");
+  if (K < 0 || K > 65535) return fail(SRRG2_E_INVALID, "align_batch_slices: K must be in [0, 65535] (grid.y)");
+  if (K == 0) return 0;
+  if (!clouds || !guesses || !results) return fail(SRRG2_E_INVALID, "align_batch_slices: bad arguments");
+  if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE)
+    return fail(SRRG2_E_INVALID, "align_batch_slices: mem must be SRRG2_MEM_HOST or SRRG2_MEM_DEVICE");
+  const int ns_handle = (int) a->slices.size();
+  if (nslices != ns_handle) return fail(SRRG2_E_INVALID, "align_batch_slices: nslices differs from the handle's slice count");
+  if (nslices == 0) return fail(SRRG2_E_STATE, "align_batch_slices: no slices");
+  const int dim = a->dim;
+  auto bad_stride = [&](const void* p, int st, int n) { return p && n > 0 && (st % 4 != 0 || st < dim * 4); };
+  // 1. the entries: one per slice, clouds for the cue slices that own theirs, nothing for the others
+  std::vector<int> owners;
+  for (int si = 0; si < nslices; ++si) {
+    const Slice* s                   = a->slices[si];
+    const srrg2_batch_slice_clouds& e = clouds[si];
+    const bool owns = s->cfg.kind != SRRG2_SLICE_PRIOR && s->alias_of < 0;
+    if (!owns) {
+      if (e.coords || e.normals || e.offsets)
+        return fail(SRRG2_E_INVALID, "align_batch_slices: a prior slice or a slice that shares clouds has a non-empty entry");
+      continue;
+    }
+    if (s->cfg.finder == SRRG2_FINDER_CORRESPONDENCES) continue;  // (refused below)
+    if (!e.offsets) return fail(SRRG2_E_INVALID, "align_batch_slices: a cue slice that owns its clouds has no offsets");
+    if (e.offsets[0] < 0) return fail(SRRG2_E_INVALID, "align_batch_slices: negative offset");
+    for (int k = 0; k < K; ++k)
+      if (e.offsets[k + 1] < e.offsets[k]) return fail(SRRG2_E_INVALID, "align_batch_slices: offsets must not decrease");
+    const int n = e.offsets[K] - e.offsets[0];
+    if (n > 0 && !e.coords) return fail(SRRG2_E_INVALID, "align_batch_slices: null cloud");
+    if (bad_stride(e.coords, e.coord_stride_bytes, n) || bad_stride(e.normals, e.normal_stride_bytes, n))
+      return fail(SRRG2_E_INVALID, "align_batch_slices: stride must be a multiple of 4 and >= dim*4");
+    owners.push_back(si);
+  }
+  // 2. what the batch does not cover
+  for (int si = 0; si < nslices; ++si)
+    if (a->slices[si]->cfg.finder == SRRG2_FINDER_CORRESPONDENCES && a->slices[si]->cfg.kind != SRRG2_SLICE_PRIOR)
+      return fail(SRRG2_E_UNSUPPORTED, "align_batch_slices: given-correspondences slices (compute_batch_correspondences is their batch)");
+  if (a->reduce_fn) return fail(SRRG2_E_UNSUPPORTED, "align_batch_slices: not on a point-sharded handle (set_point_shard)");
+  // 3. the bound state every alignment needs (run_compute's checks, made here so that a refusal leaves the moving clouds alone)
+  for (int si = 0; si < nslices; ++si) {
+    const Slice* s = a->slices[si];
+    if (s->cfg.kind == SRRG2_SLICE_PRIOR) {
+      if (!s->has_prior) return fail(SRRG2_E_STATE, "align_batch_slices: prior slice without measurement");
+      continue;
+    }
+    const Slice* o = s;
+    if (s->alias_of >= 0) {
+      if (s->alias_of >= nslices || a->slices[s->alias_of]->alias_of >= 0 || a->slices[s->alias_of]->cfg.kind == SRRG2_SLICE_PRIOR)
+        return fail(SRRG2_E_STATE, "align_batch_slices: a slice shares the clouds of a slice that is gone");
+      o = a->slices[s->alias_of];
+      if (s->cfg.finder != SRRG2_FINDER_PROJECTIVE || o->cfg.finder != SRRG2_FINDER_PROJECTIVE)
+        return fail(SRRG2_E_UNSUPPORTED, "align_batch_slices: shared clouds are for slices with the projective finder");
+    }
+    if (!o->has_fixed) return fail(SRRG2_E_STATE, "align_batch_slices: cue slice without a fixed cloud");
+    if (s->cfg.kind == SRRG2_SLICE_P2PLANE && !o->fixed_has_normals)
+      return fail(SRRG2_E_STATE, "align_batch_slices: point-to-plane slice needs fixed normals");
+    if (s->cfg.finder == SRRG2_FINDER_PROJECTIVE && o->nf != s->cfg.image_rows * s->cfg.image_cols)
+      return fail(SRRG2_E_STATE, "align_batch_slices: projective finder needs an organised fixed cloud of rows x cols points");
+  }
+  int rc;
+  if ((rc = set_device(a))) return rc;
+  auto drain = [&](int code) {
+    (void) hipStreamSynchronize(a->stream);
+    for (Slice* sl : a->slices) sl->ms_pending = false;
+    return code;
+  };
+  // 4. the moving clouds, slice by slice (each upload but the last waits for its ingest: the slices share the staging buffer, which
+  // the next upload may re-allocate); the last one's sort overlaps the launches of the alignments, as in compute_batch
+  std::vector<const int32_t*> soff((size_t) nslices, nullptr);
+  for (size_t i = 0; i < owners.size(); ++i) {
+    const int si                      = owners[i];
+    const srrg2_batch_slice_clouds& e = clouds[si];
+    soff[(size_t) si]                 = e.offsets;
+    if ((rc = upload_moving(a, si, e.coords, e.coord_stride_bytes, e.normals, e.normal_stride_bytes, e.offsets, K, mem,
+                            /*wait=*/i + 1 < owners.size())))
+      return drain(rc);
+  }
+  // 5. the alignments: every slice's problem table from its own offsets
+  rc = run_compute(a, K, owners.empty() ? nullptr : soff[(size_t) owners[0]], guesses, nullptr, soff.data());
+  // (the moving clouds are the batch's: a plain compute() must bind its own first, whatever K was)
+  for (int si : owners) a->slices[si]->moving_is_batch = true;
   if (rc) return drain(rc);
   fill_batch_results(a, K, results);
   return 0;

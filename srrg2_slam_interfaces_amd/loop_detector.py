@@ -13,8 +13,37 @@ from . import _abi as abi
 from . import slices as sl
 
 
+def _set_fixed(al, fixed, fixed_normals):
+    """aligner->setFixed(container): one cloud for slice 0, or {slice_idx: cloud} (normals the same form) for every slice
+    that reads a cloud of its own"""
+    if not isinstance(fixed, dict):
+        al.set_fixed(0, fixed, fixed_normals)
+        return
+    for si in sorted(fixed):
+        al.set_fixed(si, fixed[si], fixed_normals.get(si) if isinstance(fixed_normals, dict) else None)
+
+
+def _align(al, movings, normals, guesses):
+    """one batch for the candidates' moving clouds: arrays -> compute_batch (slice 0), {slice_idx: cloud} per candidate ->
+    compute_batch_slices (the reference binds the candidate's whole property container, every slice picks its cloud by name:
+    multi_loop_detector_brute_force_impl.cpp:63-79, multi_relocalizer_impl.cpp:74-87)"""
+    if not any(isinstance(m, dict) for m in movings):
+        return al.compute_batch(movings, guesses, normals if all(n is not None for n in normals) else None)
+    keys = {tuple(sorted(m)) if isinstance(m, dict) else None for m in movings}
+    if len(keys) != 1 or None in keys:
+        raise ValueError("per-slice moving clouds: every candidate needs a dict with the same slices")
+    slices = sorted(movings[0])
+    moving = {si: [m[si] for m in movings] for si in slices}
+    moving_normals = {}
+    for si in slices:
+        per = [n.get(si) if isinstance(n, dict) else None for n in normals]
+        moving_normals[si] = per if all(x is not None for x in per) else None
+    return al.compute_batch_slices(moving, guesses, moving_normals)
+
+
 class ClosureHint:
-    """LocalMapSelector_::ClosureHint: a candidate local map and the initial guess of moving-in-fixed."""
+    """LocalMapSelector_::ClosureHint: a candidate local map and the initial guess of moving-in-fixed.  ``moving`` /
+    ``moving_normals``: a cloud for slice 0, or {slice_idx: cloud} for an aligner with several cue slices."""
 
     def __init__(self, local_map_id, moving, moving_normals=None, initial_guess=None):
         self.local_map_id = local_map_id
@@ -45,11 +74,9 @@ class MultiLoopDetectorBruteForce:
         hints = [h for h in hints if h.moving is not None]
         if not hints:
             return self.detected_closures
-        al.set_fixed(0, fixed, fixed_normals)  # aligner->setFixed(...) once, :63
+        _set_fixed(al, fixed, fixed_normals)  # aligner->setFixed(...) once, :63
         guesses = [sl.identity(dim) if h.initial_guess is None else h.initial_guess for h in hints]
-        normals = [h.moving_normals for h in hints]
-        results = al.compute_batch([h.moving for h in hints], guesses,
-                                   normals if all(n is not None for n in normals) else None)
+        results = _align(al, [h.moving for h in hints], [h.moving_normals for h in hints], guesses)
         for h, r in zip(hints, results):
             if r["status"] != abi.SUCCESS:  # :80-84
                 self.drops.append((h.local_map_id, "ALIGNER DROP [code: %d]" % r["status"]))
@@ -157,7 +184,8 @@ class MultiRelocalizer:
     aligner branch, the target local map's cloud).  Without an aligner the best closure is chosen on the detector's
     statistics (:27-66); with one every candidate within max_translation is re-aligned against the current measurement
     -- here in ONE compute_batch() instead of the sequential loop -- gated like the detector (:104-121) and the lowest
-    chi per inlier wins (:128-137).  PARAMs: multi_relocalizer.h:29-43, relocalizer.h:22."""
+    chi per inlier wins (:128-137).  A candidate's ``moving`` / ``moving_normals`` and ``fixed`` / ``fixed_normals`` may be
+    {slice_idx: cloud} dicts for an aligner with several cue slices (one compute_batch_slices() then).  PARAMs: multi_relocalizer.h:29-43, relocalizer.h:22."""
 
     def __init__(self, aligner=None, max_translation=3.0, relocalize_min_inliers=500, relocalize_max_chi_inliers=0.005,
                  relocalize_min_inliers_ratio=0.7):
@@ -209,11 +237,9 @@ class MultiRelocalizer:
         if not near:
             return None
         al = self.aligner
-        al.set_fixed(0, fixed, fixed_normals)  # aligner->setFixed(&tracker->measurementContainer()), :78
+        _set_fixed(al, fixed, fixed_normals)  # aligner->setFixed(&tracker->measurementContainer()), :78
         guesses = [sl.inverse(np.asarray(c["pose_in_target"], np.float32)) for c in near]  # :91
-        normals = [c.get("moving_normals") for c in near]
-        results = al.compute_batch([c["moving"] for c in near], guesses,
-                                   normals if all(n is not None for n in normals) else None)
+        results = _align(al, [c["moving"] for c in near], [c.get("moving_normals") for c in near], guesses)
         best_chi_average = np.float32(np.finfo(np.float32).max)
         for c, r in zip(near, results):
             if r["status"] != abi.SUCCESS:  # :93-97
