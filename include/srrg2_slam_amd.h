@@ -589,6 +589,36 @@ int srrg2_scene_get(srrg2_scene_h h, float* coords_out, float* normals_out, int 
  * until the scene is next modified. */
 int srrg2_scene_device_arrays(srrg2_scene_h h, const float** coords, const float** normals, int* n);
 
+/* Per-point features: a 256-bit descriptor (SRRG2_DESCRIPTOR_BYTES bytes) and a float intensity, the extra fields of
+ * PointIntensityDescriptor2f / 3f -- the cloud type of the reference's second merger (S/mapping/
+ * merger_correspondence_homo.h:36-40) and of its HBST detector, which reads the descriptors back from the local map's cloud
+ * (multi_loop_detector_hbst_impl.cpp:84-85, :131-136).  They travel with the point through every scene operation:
+ *   set_features   n must equal the scene's size (else SRRG2_E_INVALID, scene unchanged).  Either pointer may be NULL: that
+ *                  field is then absent; both NULL drops the features.  Strides in bytes: descriptors >= 32 (any alignment),
+ *                  intensity >= 4 and a multiple of 4 (else SRRG2_E_INVALID).  mem: SRRG2_MEM_HOST | SRRG2_MEM_DEVICE.
+ *   srrg2_scene_set replaces the content and so drops the features.  A scene that never got features behaves as before.
+ *   validity       unchanged: a point is Valid iff its coordinates are finite; an invalid point keeps its features and index.
+ *   clip_ball      `clipped` receives the features of the points it keeps (clipped[k] = full[global_indices[k]]) and
+ *                  the feature presence of `full`.
+ *   merge / merge_from_aligner
+ *                  a merged scene point takes the measurement point's descriptor and intensity (point_scene = point_meas,
+ *                  merger_correspondence_homo_impl.cpp:71); of several correspondences onto one scene point the last one that
+ *                  passed both gates, in correspondence order, decides.  Appended points carry their features unchanged
+ *                  (:35-40, :103-115).  An EMPTY scene adopts the measurement's feature presence; otherwise scene and
+ *                  measurement must agree field by field: SRRG2_E_STATE, both handles unchanged.
+ *   get_features   like srrg2_scene_get: up to `capacity` points, descriptors as packed 32-byte rows; an absent field is
+ *                  not written (either pointer may be NULL).
+ *   device_features  like srrg2_scene_device_arrays: descriptors as rows of 32 bytes (16-byte aligned), intensities as
+ *                  floats; NULL for an absent field.  Valid until the scene is next modified. */
+#ifndef SRRG2_DESCRIPTOR_BYTES
+#define SRRG2_DESCRIPTOR_BYTES 32
+#endif
+int srrg2_scene_set_features(srrg2_scene_h h, const uint8_t* descriptors, int descriptor_stride_bytes, const float* intensity,
+                             int intensity_stride_bytes, int n, int mem);
+int srrg2_scene_has_features(srrg2_scene_h h, int* has_descriptors, int* has_intensity);
+int srrg2_scene_get_features(srrg2_scene_h h, uint8_t* descriptors_out, float* intensity_out, int capacity, int* n);
+int srrg2_scene_device_features(srrg2_scene_h h, const uint8_t** descriptors, const float** intensity, int* n);
+
 /* SceneClipper_::compute() (S/mapping/scene_clipper.h:17-122; the reference ships the interface
  * only, concrete clippers live in the SLAM pipelines): ball policy -- keeps the Valid points of
  * `full` within `range` of the robot, in scene order, expressed in the robot frame
@@ -720,7 +750,9 @@ int srrg2_aligner_last_compute_path(srrg2_aligner_h h, int32_t* flags_out);
  *    get_correspondences  all candidates' correspondences, concatenated in candidate order
  *    get_map_counts       the match count of EVERY map of the database, -1 for the maps the age gate skipped
  *    last_match_ms        HIP-event time of the last match(): query upload + search + compaction, without the readback */
+#ifndef SRRG2_DESCRIPTOR_BYTES
 #define SRRG2_DESCRIPTOR_BYTES 32
+#endif
 typedef struct srrg2_descriptor_db* srrg2_descriptor_db_h;
 int srrg2_descriptor_db_create(int device, srrg2_descriptor_db_h* out);
 int srrg2_descriptor_db_destroy(srrg2_descriptor_db_h h);
@@ -735,6 +767,17 @@ int srrg2_descriptor_db_get_candidates(srrg2_descriptor_db_h h, int32_t* referen
 int srrg2_descriptor_db_get_correspondences(srrg2_descriptor_db_h h, srrg2_correspondence* buf, int64_t* n_inout);
 int srrg2_descriptor_db_get_map_counts(srrg2_descriptor_db_h h, int64_t* counts, int* n_inout);
 int srrg2_descriptor_db_last_match_ms(srrg2_descriptor_db_h h, double* ms);
+/* add / match with the descriptors of a scene that carries them (srrg2_scene_set_features), read on the device: EXACTLY
+ * srrg2_descriptor_db_add / _match called with the scene's descriptors and valid[i] = (point i is Valid, i.e. has finite
+ * coordinates) -- same database index, candidates, counts and correspondences (fixed_idx = the scene's point index, never
+ * compacted), same getters afterwards.  The database keeps a copy: later changes of the scene do not reach it.  Only counts
+ * cross to the host.  A scene without descriptors: SRRG2_E_STATE; a scene on another device than the database:
+ * SRRG2_E_INVALID; both leave the database as it was.  An empty scene or one without Valid points behaves as n = 0 / no valid
+ * descriptor does (*index_out = -1, K = 0).  The call is ordered behind the work queued on the scene's stream and returns
+ * when the database no longer reads the scene. */
+int srrg2_descriptor_db_add_scene(srrg2_descriptor_db_h h, srrg2_scene_h scene, int* index_out);
+int srrg2_descriptor_db_match_scene(srrg2_descriptor_db_h h, srrg2_scene_h scene, int64_t query_index, float max_distance,
+                                    uint32_t min_age, int64_t min_matches, int* K_out);
 
 #ifdef __cplusplus
 }

@@ -419,7 +419,8 @@ private:
 };
 
 // ---- scene slices in device memory: SceneClipper_ / MergerCorrespondenceHomo_ ------
-//   Scene                       a PointNormal{2,3}f cloud living in HBM (LocalMap scene slice / measurement)
+//   Scene                       a PointNormal{2,3}f cloud living in HBM (LocalMap scene slice / measurement); with setFeatures
+//                               a PointIntensityDescriptor{2,3}f one: descriptor + intensity travel through clip and merge
 //   SceneClipperBall            SceneClipper_<Estimate, Scene>              S/mapping/scene_clipper.h:17-122
 //   MergerCorrespondenceHomo    MergerCorrespondenceHomo_<Estimate, Scene>  S/mapping/merger_correspondence_homo.h
 template <int DIM>
@@ -448,6 +449,34 @@ public:
   // device float4 arrays (stride 16 bytes), e.g. for MultiAligner_::setMoving(..., SRRG2_MEM_DEVICE)
   void deviceArrays(const float*& coords, const float*& normals, int& n) const {
     check(srrg2_scene_device_arrays(_h, &coords, &normals, &n));
+  }
+  // per-point features: rows of SRRG2_DESCRIPTOR_BYTES bytes and / or floats, nullptr = that field is absent (both: dropped);
+  // n must be size().  Strides in bytes.
+  void setFeatures(const uint8_t* descriptors, int descriptor_stride_bytes, const float* intensity, int intensity_stride_bytes,
+                   int n, int mem = SRRG2_MEM_HOST) {
+    check(srrg2_scene_set_features(_h, descriptors, descriptor_stride_bytes, intensity, intensity_stride_bytes, n, mem));
+  }
+  bool hasDescriptors() const {
+    int d = 0;
+    check(srrg2_scene_has_features(_h, &d, nullptr));
+    return d != 0;
+  }
+  bool hasIntensity() const {
+    int i = 0;
+    check(srrg2_scene_has_features(_h, nullptr, &i));
+    return i != 0;
+  }
+  // packed rows of 32 bytes / floats; a field the scene does not carry comes back empty
+  void getFeatures(std::vector<uint8_t>& descriptors, std::vector<float>& intensity) const {
+    int n = size();
+    descriptors.assign(hasDescriptors() ? (size_t) n * SRRG2_DESCRIPTOR_BYTES : 0, 0);
+    intensity.assign(hasIntensity() ? (size_t) n : 0, 0.f);
+    check(srrg2_scene_get_features(_h, descriptors.empty() ? nullptr : descriptors.data(),
+                                   intensity.empty() ? nullptr : intensity.data(), n, &n));
+  }
+  // device arrays (nullptr for an absent field), valid until the scene is next modified
+  void deviceFeatures(const uint8_t*& descriptors, const float*& intensity, int& n) const {
+    check(srrg2_scene_device_features(_h, &descriptors, &intensity, &n));
   }
   srrg2_scene_h handle() const { return _h; }
 
@@ -574,6 +603,11 @@ public:
     int K = 0;
     check(srrg2_descriptor_db_match(_h, descriptors, valid, n, query_index, maximum_descriptor_distance,
                                     minimum_age_difference, min_matches, &K));
+    return candidates(K);
+  }
+
+private:
+  std::vector<Candidate> candidates(int K) {
     std::vector<int32_t> index(K);
     std::vector<int64_t> count(K), offsets(K + 1);
     check(srrg2_descriptor_db_get_candidates(_h, index.data(), count.data(), offsets.data(), &K));
@@ -587,6 +621,23 @@ public:
       out[k].correspondences.assign(all.begin() + offsets[k], all.begin() + offsets[k + 1]);
     }
     return out;
+  }
+
+public:
+  // add / match with the descriptors of a scene that carries them, read on the device; valid = finite coordinates
+  template <int DIM>
+  int add(const Scene<DIM>& scene) {
+    int index = -1;
+    check(srrg2_descriptor_db_add_scene(_h, scene.handle(), &index));
+    return index;
+  }
+  template <int DIM>
+  std::vector<Candidate> match(const Scene<DIM>& scene, int64_t query_index, float maximum_descriptor_distance = 25.0f,
+                               uint32_t minimum_age_difference = 0, int64_t min_matches = 0) {
+    int K = 0;
+    check(srrg2_descriptor_db_match_scene(_h, scene.handle(), query_index, maximum_descriptor_distance,
+                                          minimum_age_difference, min_matches, &K));
+    return candidates(K);
   }
   // the pair count of every map in the last match(), -1 for maps the age gate skipped
   std::vector<int64_t> mapCounts() const {

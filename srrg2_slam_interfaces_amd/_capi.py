@@ -42,6 +42,9 @@ def lib():
         _LIB.srrg2_descriptor_db_get_correspondences.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         _LIB.srrg2_descriptor_db_get_map_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
         _LIB.srrg2_descriptor_db_last_match_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        _LIB.srrg2_descriptor_db_add_scene.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        _LIB.srrg2_descriptor_db_match_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_uint32, C.c_int64,
+                                                         C.POINTER(C.c_int)]
     return _LIB
 
 

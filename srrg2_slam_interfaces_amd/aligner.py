@@ -394,6 +394,26 @@ class MultiAligner:
             coffsets.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(g), res))
         return self._unpack_batch(res, K)
 
+    def compute_batch_correspondences_device(self, coords_ptr, coord_stride, normals_ptr, normal_stride, offsets,
+                                             correspondences, guesses):
+        """compute_batch_correspondences on moving clouds already resident in HBM (raw device pointers as ints,
+        concatenated with ``offsets``); the correspondences stay host arrays."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        K = offsets.size - 1
+        coffsets = np.zeros(K + 1, dtype=np.int32)
+        coffsets[1:] = np.cumsum([len(c) for c in correspondences])
+        parts = [self._corr_array(cs)[1][: len(cs)] for cs in correspondences]
+        cptr, keep = self._corr_array(np.concatenate([q.view(np.int32) for q in parts]).view(self._CORR_DTYPE)
+                                      if parts else np.zeros(0, self._CORR_DTYPE))
+        g = _as_f32(np.asarray(guesses)).reshape(K, self.tsize)
+        res = (abi.BatchResult * max(K, 1))()
+        self._check(self._b.fn("compute_batch_correspondences")(
+            self._h, C.c_int(K), C.cast(coords_ptr, C.POINTER(C.c_float)), C.c_int(coord_stride),
+            C.cast(normals_ptr, C.POINTER(C.c_float)) if normals_ptr else None, C.c_int(normal_stride),
+            offsets.ctypes.data_as(C.POINTER(C.c_int32)), C.c_int(abi.MEM_DEVICE), cptr,
+            coffsets.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(g), res))
+        return self._unpack_batch(res, K)
+
     def compute_batch_device(self, coords_ptr, coord_stride, normals_ptr, normal_stride, offsets, guesses):
         """compute_batch on clouds already resident in HBM (raw device pointers as ints)."""
         offsets = np.ascontiguousarray(offsets, dtype=np.int32)

@@ -19,6 +19,11 @@
 //                     correspondences, ascending in the reference point index.
 // The host reads the per-map statistics once, picks the candidates (count gate, :152-154) and reads the
 // correspondences once.
+// A scene that carries descriptors (srrg2_scene_set_features) is added / matched without its descriptors leaving the
+// device (the reference reads them from the local map's cloud: :84-85, :131-136): k_scene_flag marks the Valid points,
+// an exclusive scan numbers them, k_scene_stage scatters descriptors and point indices -- ascending point index, the
+// order stage() produces on the host -- into the database tail (add) or the query buffers (match); one count crosses to
+// the host.  The three kernels above then run unchanged.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,7 +32,9 @@
 #include <string>
 #include <vector>
 
+#include "device_types.h"
 #include "host_util.h"
+#include "kernels.h"
 
 using srrg2amd::DevBuf;
 using srrg2amd::fail;
@@ -183,6 +190,31 @@ __global__ void __launch_bounds__(THREADS) k_desc_emit(const Candidate* __restri
   }
 }
 
+// ---- staging from a scene ---------------------------------------------------------------------------------------------
+// Valid <=> finite coordinates (scene.hip's valid_point)
+__global__ void k_scene_flag(int dim, const float4* __restrict__ pts, int n, int* __restrict__ flags) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const float4 p = pts[i];
+    flags[i]       = (isfinite(p.x) && isfinite(p.y) && (dim == 2 || isfinite(p.z))) ? 1 : 0;
+  }
+}
+
+// offset: the exclusive scan of the flags (offset[n] is not read: a point is valid iff its coordinates are, tested again)
+__global__ void k_scene_stage(int dim, const float4* __restrict__ pts, const uint4* __restrict__ desc, int n,
+                              const int* __restrict__ offset, int cap, uint4* __restrict__ out_desc,
+                              int32_t* __restrict__ out_idx) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const float4 p = pts[i];
+    if (!(isfinite(p.x) && isfinite(p.y) && (dim == 2 || isfinite(p.z)))) continue;
+    const int k = offset[i];
+    if (k >= cap) continue;  // (cannot happen: cap is the scan's total; a guard against writing past the buffers)
+    const uint4 a = desc[2 * (size_t) i], b = desc[2 * (size_t) i + 1];
+    out_desc[2 * (size_t) k]     = a;
+    out_desc[2 * (size_t) k + 1] = b;
+    out_idx[k]                   = i;
+  }
+}
+
 // a device buffer that keeps its first `used` elements when it grows (capacity doubles)
 template <typename T>
 int grow_keep(DevBuf<T>& buf, size_t need, size_t used, hipStream_t s) {
@@ -245,6 +277,9 @@ struct srrg2_descriptor_db {
   DevBuf<srrg2_correspondence> corr;
   void* staging = nullptr;  // pinned
   size_t staging_cap = 0;
+  // staging from a scene: flags -> offsets, the scan's block sums, the event that orders this stream behind the scene's
+  DevBuf<int> sflags, sscan;
+  hipEvent_t ev_scene = nullptr;
   // last match()
   std::vector<MapStat> h_stats;
   std::vector<int64_t> map_counts;
@@ -279,6 +314,49 @@ int stage(srrg2_descriptor_db* h, const uint8_t* d, const uint8_t* valid, int n,
   *nv_out  = nv;
   *idx_off = off;
   return 0;
+}
+
+int scene_blocks(int n) {
+  int b = (n + THREADS - 1) / THREADS;
+  return b < 1 ? 1 : (b > 2048 ? 2048 : b);
+}
+
+// the checks shared by add_scene / match_scene
+int scene_view(srrg2_descriptor_db* h, srrg2_scene_h scene, const char* who, srrg2amd::SceneFeatureView* v) {
+  if (!h || !scene) return fail(SRRG2_E_INVALID, std::string(who) + ": NULL handle");
+  int rc;
+  if ((rc = srrg2amd::scene_feature_view(scene, v))) return rc;
+  if (v->device != h->device) return fail(SRRG2_E_INVALID, std::string(who) + ": the scene lives on another device");
+  if (!v->desc) return fail(SRRG2_E_STATE, std::string(who) + ": the scene carries no descriptors (srrg2_scene_set_features)");
+  if (v->n > MAX_QUERY) return fail(SRRG2_E_INVALID, std::string(who) + ": a scene holds at most 2^23 points here");
+  return 0;
+}
+
+// number the Valid points of the scene: h->sflags = exclusive scan of the flags, *nv_out = their count (one pinned int).
+// The database's stream first waits for what is queued on the scene's.
+int scene_count(srrg2_descriptor_db* h, const srrg2amd::SceneFeatureView& v, int* nv_out) {
+  *nv_out = 0;
+  if (v.n == 0) return 0;
+  int rc;
+  if (!h->ev_scene) HIP_TRY(hipEventCreateWithFlags(&h->ev_scene, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(h->ev_scene, v.stream));
+  HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_scene, 0));
+  if ((rc = h->sflags.reserve((size_t) v.n + 1))) return rc;
+  if ((rc = h->sscan.reserve((size_t) srrg2amd::scan_num_blocks(v.n) + 2))) return rc;
+  if ((rc = host_reserve(&h->staging, &h->staging_cap, 64))) return rc;
+  hipLaunchKernelGGL(k_scene_flag, dim3(scene_blocks(v.n)), dim3(THREADS), 0, h->stream, v.dim, v.pts, v.n, h->sflags.p);
+  int* dtotal = h->sscan.p + h->sscan.cap - 1;
+  srrg2amd::launch_exclusive_scan(h->sflags.p, v.n, h->sscan.p, dtotal, h->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h->staging, dtotal, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  *nv_out = *(const int*) h->staging;
+  return 0;
+}
+
+void scene_scatter(srrg2_descriptor_db* h, const srrg2amd::SceneFeatureView& v, int nv, uint4* out_desc, int32_t* out_idx) {
+  hipLaunchKernelGGL(k_scene_stage, dim3(scene_blocks(v.n)), dim3(THREADS), 0, h->stream, v.dim, v.pts, v.desc, v.n,
+                     h->sflags.p, nv, out_desc, out_idx);
 }
 
 }  // namespace
@@ -316,7 +394,9 @@ int srrg2_descriptor_db_destroy(srrg2_descriptor_db_h h) {
   if (h->stream) (void) hipStreamSynchronize(h->stream);
   h->desc.release(); h->ref_idx.release(); h->starts.release(); h->best.release(); h->count.release();
   h->query.release(); h->query_idx.release(); h->stats.release(); h->cands.release(); h->corr.release();
+  h->sflags.release(); h->sscan.release();
   if (h->staging) (void) hipHostFree(h->staging);
+  if (h->ev_scene) (void) hipEventDestroy(h->ev_scene);
   if (h->ev0) (void) hipEventDestroy(h->ev0);
   if (h->ev1) (void) hipEventDestroy(h->ev1);
   if (h->stream) (void) hipStreamDestroy(h->stream);
@@ -324,14 +404,21 @@ int srrg2_descriptor_db_destroy(srrg2_descriptor_db_h h) {
   return 0;
 }
 
-int srrg2_descriptor_db_add(srrg2_descriptor_db_h h, const uint8_t* d, const uint8_t* valid, int n, int* index_out) {
-  if (!h || n < 0 || (n > 0 && !d)) return fail(SRRG2_E_INVALID, "descriptor_db_add: bad arguments");
+namespace {
+
+// add() behind the argument checks.  sv: the descriptors come from a scene on the device, else from d / valid on the host
+int add_impl(srrg2_descriptor_db* h, const uint8_t* d, const uint8_t* valid, int n, const srrg2amd::SceneFeatureView* sv,
+             int* index_out) {
   int rc;
   if ((rc = db_device(h))) return rc;
   if (index_out) *index_out = -1;
   int nv       = 0;
   size_t off   = 0;
-  if ((rc = stage(h, d, valid, n, &nv, &off))) return rc;
+  if (sv) {
+    if ((rc = scene_count(h, *sv, &nv))) return rc;
+  } else if ((rc = stage(h, d, valid, n, &nv, &off))) {
+    return rc;
+  }
   if (nv == 0) return 0;  // addPreviousQuery skips an empty request (:46-49)
   const int maps      = (int) h->h_starts.size() - 1;
   const long long old = h->h_starts.back(), now = old + nv;
@@ -339,15 +426,34 @@ int srrg2_descriptor_db_add(srrg2_descriptor_db_h h, const uint8_t* d, const uin
   if ((rc = grow_keep(h->ref_idx, (size_t) now, (size_t) old, h->stream))) return rc;
   if ((rc = grow_keep(h->starts, (size_t) maps + 2, (size_t) maps + 1, h->stream))) return rc;
   h->h_starts.push_back(now);
-  HIP_TRY(hipMemcpyAsync(h->desc.p + 2 * old, h->staging, (size_t) nv * SRRG2_DESCRIPTOR_BYTES, hipMemcpyHostToDevice,
-                         h->stream));
-  HIP_TRY(hipMemcpyAsync(h->ref_idx.p + old, (uint8_t*) h->staging + off, (size_t) nv * 4, hipMemcpyHostToDevice,
-                         h->stream));
+  if (sv) {
+    scene_scatter(h, *sv, nv, h->desc.p + 2 * old, h->ref_idx.p + old);
+    HIP_TRY(hipGetLastError());
+  } else {
+    HIP_TRY(hipMemcpyAsync(h->desc.p + 2 * old, h->staging, (size_t) nv * SRRG2_DESCRIPTOR_BYTES, hipMemcpyHostToDevice,
+                           h->stream));
+    HIP_TRY(hipMemcpyAsync(h->ref_idx.p + old, (uint8_t*) h->staging + off, (size_t) nv * 4, hipMemcpyHostToDevice,
+                           h->stream));
+  }
   HIP_TRY(hipMemcpyAsync(h->starts.p + maps + 1, &h->h_starts.back(), sizeof(long long), hipMemcpyHostToDevice,
                          h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));  // (the staging buffer is reused by the next call)
+  HIP_TRY(hipStreamSynchronize(h->stream));  // (the staging buffer is reused by the next call; a scene is no longer read)
   if (index_out) *index_out = maps;
   return 0;
+}
+
+}  // namespace
+
+int srrg2_descriptor_db_add(srrg2_descriptor_db_h h, const uint8_t* d, const uint8_t* valid, int n, int* index_out) {
+  if (!h || n < 0 || (n > 0 && !d)) return fail(SRRG2_E_INVALID, "descriptor_db_add: bad arguments");
+  return add_impl(h, d, valid, n, nullptr, index_out);
+}
+
+int srrg2_descriptor_db_add_scene(srrg2_descriptor_db_h h, srrg2_scene_h scene, int* index_out) {
+  srrg2amd::SceneFeatureView v;
+  int rc;
+  if ((rc = scene_view(h, scene, "descriptor_db_add_scene", &v))) return rc;
+  return add_impl(h, nullptr, nullptr, v.n, &v, index_out);
 }
 
 int srrg2_descriptor_db_size(srrg2_descriptor_db_h h, int* maps, int64_t* descriptors) {
@@ -357,12 +463,11 @@ int srrg2_descriptor_db_size(srrg2_descriptor_db_h h, int* maps, int64_t* descri
   return 0;
 }
 
-int srrg2_descriptor_db_match(srrg2_descriptor_db_h h, const uint8_t* d, const uint8_t* valid, int n,
-                              int64_t query_index, float max_distance, uint32_t min_age, int64_t min_matches,
-                              int* K_out) {
-  if (!h || n < 0 || (n > 0 && !d) || std::isnan(max_distance) || query_index < 0 || min_matches < 0)
-    return fail(SRRG2_E_INVALID, "descriptor_db_match: bad arguments");
-  if (n > MAX_QUERY) return fail(SRRG2_E_INVALID, "descriptor_db_match: a query holds at most 2^23 descriptors");
+namespace {
+
+// match() behind the argument checks; sv as in add_impl
+int match_impl(srrg2_descriptor_db* h, const uint8_t* d, const uint8_t* valid, int n, const srrg2amd::SceneFeatureView* sv,
+               int64_t query_index, float max_distance, uint32_t min_age, int64_t min_matches, int* K_out) {
   int rc;
   if ((rc = db_device(h))) return rc;
   h->cand_ref.clear();
@@ -385,7 +490,11 @@ int srrg2_descriptor_db_match(srrg2_descriptor_db_h h, const uint8_t* d, const u
   for (int r = map_lo; r < map_lo + map_skip; ++r) h->map_counts[r] = -1;
   int nv     = 0;
   size_t off = 0;
-  if ((rc = stage(h, d, valid, n, &nv, &off))) return rc;
+  if (sv) {
+    if ((rc = scene_count(h, *sv, &nv))) return rc;
+  } else if ((rc = stage(h, d, valid, n, &nv, &off))) {
+    return rc;
+  }
   if (nv == 0 || nactive == 0 || searched == 0) return 0;  // no pair: every searched map counts 0
   if ((rc = grow_keep(h->query, (size_t) nv * 2, 0, h->stream))) return rc;
   if ((rc = grow_keep(h->query_idx, (size_t) nv, 0, h->stream))) return rc;
@@ -393,8 +502,13 @@ int srrg2_descriptor_db_match(srrg2_descriptor_db_h h, const uint8_t* d, const u
   if ((rc = grow_keep(h->count, (size_t) h->h_starts.back(), 0, h->stream))) return rc;
   if ((rc = grow_keep(h->stats, (size_t) maps, 0, h->stream))) return rc;
   HIP_TRY(hipEventRecord(h->ev0, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->query.p, h->staging, (size_t) nv * SRRG2_DESCRIPTOR_BYTES, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->query_idx.p, (uint8_t*) h->staging + off, (size_t) nv * 4, hipMemcpyHostToDevice, h->stream));
+  if (sv) {
+    scene_scatter(h, *sv, nv, h->query.p, h->query_idx.p);
+    HIP_TRY(hipGetLastError());
+  } else {
+    HIP_TRY(hipMemcpyAsync(h->query.p, h->staging, (size_t) nv * SRRG2_DESCRIPTOR_BYTES, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->query_idx.p, (uint8_t*) h->staging + off, (size_t) nv * 4, hipMemcpyHostToDevice, h->stream));
+  }
   const long long blocks = (nactive + THREADS * DPT - 1) / (THREADS * DPT);
   hipLaunchKernelGGL(k_desc_match, dim3((unsigned) blocks), dim3(THREADS), 0, h->stream, h->desc.p, lo, skip, nactive,
                      h->query.p, nv, L, h->best.p, h->count.p);
@@ -441,6 +555,27 @@ int srrg2_descriptor_db_match(srrg2_descriptor_db_h h, const uint8_t* d, const u
   h->last_ms = ms;
   if (K_out) *K_out = K;
   return 0;
+}
+
+}  // namespace
+
+int srrg2_descriptor_db_match(srrg2_descriptor_db_h h, const uint8_t* d, const uint8_t* valid, int n,
+                              int64_t query_index, float max_distance, uint32_t min_age, int64_t min_matches,
+                              int* K_out) {
+  if (!h || n < 0 || (n > 0 && !d) || std::isnan(max_distance) || query_index < 0 || min_matches < 0)
+    return fail(SRRG2_E_INVALID, "descriptor_db_match: bad arguments");
+  if (n > MAX_QUERY) return fail(SRRG2_E_INVALID, "descriptor_db_match: a query holds at most 2^23 descriptors");
+  return match_impl(h, d, valid, n, nullptr, query_index, max_distance, min_age, min_matches, K_out);
+}
+
+int srrg2_descriptor_db_match_scene(srrg2_descriptor_db_h h, srrg2_scene_h scene, int64_t query_index, float max_distance,
+                                    uint32_t min_age, int64_t min_matches, int* K_out) {
+  if (std::isnan(max_distance) || query_index < 0 || min_matches < 0)
+    return fail(SRRG2_E_INVALID, "descriptor_db_match_scene: bad arguments");
+  srrg2amd::SceneFeatureView v;
+  int rc;
+  if ((rc = scene_view(h, scene, "descriptor_db_match_scene", &v))) return rc;
+  return match_impl(h, nullptr, nullptr, v.n, &v, query_index, max_distance, min_age, min_matches, K_out);
 }
 
 int srrg2_descriptor_db_get_candidates(srrg2_descriptor_db_h h, int32_t* reference, int64_t* num_matches,

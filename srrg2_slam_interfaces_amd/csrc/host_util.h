@@ -61,6 +61,15 @@ struct AlignerSliceView {
 };
 int aligner_slice_view(srrg2_aligner_s* a, int slice_idx, AlignerSliceView* v);
 
+// what descriptors.hip needs to see of a scene: the points (validity), the descriptors (null: the scene has none), its stream
+struct SceneFeatureView {
+  const float4* pts;
+  const uint4* desc;  // two per point
+  int n, dim, device;
+  hipStream_t stream;
+};
+int scene_feature_view(srrg2_scene* s, SceneFeatureView* v);
+
 }  // namespace srrg2amd
 
 #define HIP_TRY(expr)                                                                              \

@@ -4,7 +4,11 @@
 //   SceneClipper_::compute() (interface)   S/mapping/scene_clipper.h:17-122
 //   the index flip + local->global mapping of TrackerSliceProcessor_::merge()
 //                                          S/trackers/tracker_slice_processor_impl.cpp:160-186
-// A scene is two float4 arrays (points {x, y, z, 0}, normals) with spare capacity.  All kernels are one thread per
+// A scene is two float4 arrays (points {x, y, z, 0}, normals) with spare capacity and, for the clouds of a visual pipeline
+// (PointIntensityDescriptor2f / 3f, the second instantiation of the merger: merger_correspondence_homo.h:36-40), a 256-bit
+// descriptor (two uint4) and a float intensity per point, each allocated only when present.  The features travel with the point:
+// the kernels that move points (k_clip_scatter, merge_one, k_append_scatter) have a feature-carrying instantiation, chosen on the
+// host, so a scene without features runs the code it ran before they existed.  All kernels are one thread per
 // point or correspondence, coalesced, HBM bound: clip = 2 passes over the scene (flag+count, scatter) around an
 // exclusive scan; merge = one pass over the correspondences + (if the merge target was not reached) flag/scan/scatter
 // of the measurement.  The reference merges sequentially; results are identical because
@@ -36,6 +40,11 @@ struct srrg2_scene {
   DevBuf<float4> pts, nrm;
   int n            = 0;
   bool has_normals = false;
+  // per-point features (absent unless set_features / a merge or clip brought them): 2 uint4 per point, 1 float per point;
+  // when present their capacity follows pts.cap
+  DevBuf<uint4> desc;
+  DevBuf<float> inten;
+  bool has_desc = false, has_inten = false;
   DevBuf<int> gidx;  // local -> global indices of the last clip into this scene
   int ng = 0;
   // scratch
@@ -111,9 +120,28 @@ __global__ void k_clip_flag(int dim, Xf L, float range2, const float4* __restric
   }
 }
 
+// what a feature-carrying kernel needs: source (measurement / full scene) and destination (scene / clipped scene) arrays; a
+// null pair = that field is absent.  Descriptor halves move as 16-byte vectors.
+struct Feat {
+  const uint4* src_desc;
+  const float* src_inten;
+  uint4* dst_desc;
+  float* dst_inten;
+};
+
+__device__ __forceinline__ void move_features(const Feat& f, int from, int to) {
+  if (f.dst_desc) {
+    const uint4 a = f.src_desc[2 * (size_t) from], b = f.src_desc[2 * (size_t) from + 1];
+    f.dst_desc[2 * (size_t) to]     = a;
+    f.dst_desc[2 * (size_t) to + 1] = b;
+  }
+  if (f.dst_inten) f.dst_inten[to] = f.src_inten[from];
+}
+
+template <bool FEAT>
 __global__ void k_clip_scatter(int dim, Xf L, float range2, const float4* __restrict__ pts, const float4* __restrict__ nrm,
                                int n, const int* __restrict__ offset, float4* __restrict__ out_pts,
-                               float4* __restrict__ out_nrm, int* __restrict__ gidx, int cap) {
+                               float4* __restrict__ out_nrm, int* __restrict__ gidx, int cap, Feat f) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     float4 q;
     if (!clip_keep(dim, L, range2, pts[i], q)) continue;
@@ -122,6 +150,7 @@ __global__ void k_clip_scatter(int dim, Xf L, float range2, const float4* __rest
     out_pts[k]  = q;
     out_nrm[k]  = nrm ? rotate_normal(dim, L, nrm[i]) : make_float4(0.f, 0.f, 0.f, 0.f);
     gidx[k]     = i;
+    if (FEAT) move_features(f, i, k);
   }
 }
 
@@ -141,9 +170,10 @@ __device__ __forceinline__ void block_add(int v, int* target) {
 
 // ---- merge --------------------------------------------------------------------------------------------------
 // one correspondence: merger_correspondence_homo_impl.cpp:55-76.  Returns true if merged.
+template <bool FEAT>
 __device__ __forceinline__ bool merge_one(int dim, const Xf& M, float max_response, float max_d2, float4* scene_pts,
                                           float4* scene_nrm, const float4* meas_pts, const float4* meas_nrm, int s, int m,
-                                          float response) {
+                                          float response, const Feat& f) {
   if (!(response < max_response)) return false;  // :60
   const float4 ps = scene_pts[s];
   const float4 q  = xform_point(dim, M, meas_pts[m]);  // :62-63
@@ -154,6 +184,7 @@ __device__ __forceinline__ bool merge_one(int dim, const Xf& M, float max_respon
   if (scene_nrm) scene_nrm[s] = meas_nrm ? meas_nrm[m] : make_float4(0.f, 0.f, 0.f, 0.f);
   float4 r = make_float4((q.x + ps.x) * 0.5f, (q.y + ps.y) * 0.5f, dim == 3 ? (q.z + ps.z) * 0.5f : 0.f, 0.f);
   scene_pts[s] = r;
+  if (FEAT) move_features(f, m, s);  // :71 again: descriptor and intensity are fields of the measurement point
   return true;
 }
 
@@ -170,16 +201,17 @@ __global__ void k_merge_count(const srrg2_correspondence* __restrict__ corr, int
 }
 
 // scene points hit exactly once: independent of every other correspondence
+template <bool FEAT>
 __global__ void k_merge_apply(int dim, Xf M, float max_response, float max_d2, const srrg2_correspondence* __restrict__ corr,
                               int ncorr, const int* __restrict__ counts, float4* scene_pts, float4* scene_nrm,
                               const float4* __restrict__ meas_pts, const float4* __restrict__ meas_nrm,
-                              unsigned char* __restrict__ merged, int* __restrict__ dup_flags) {
+                              unsigned char* __restrict__ merged, int* __restrict__ dup_flags, Feat f) {
   for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < ncorr; c += gridDim.x * blockDim.x) {
     const srrg2_correspondence k = corr[c];
     const bool dup               = counts[k.fixed_idx] > 1;
     if (dup_flags) dup_flags[c] = dup ? 1 : 0;
     if (dup) continue;
-    if (merge_one(dim, M, max_response, max_d2, scene_pts, scene_nrm, meas_pts, meas_nrm, k.fixed_idx, k.moving_idx, k.response))
+    if (merge_one<FEAT>(dim, M, max_response, max_d2, scene_pts, scene_nrm, meas_pts, meas_nrm, k.fixed_idx, k.moving_idx, k.response, f))
       merged[k.moving_idx] = 1;
   }
 }
@@ -202,16 +234,17 @@ __global__ void k_dup_keys(const srrg2_correspondence* __restrict__ corr, const 
   }
 }
 
+template <bool FEAT>
 __global__ void k_merge_dups(int dim, Xf M, float max_response, float max_d2, const srrg2_correspondence* __restrict__ corr,
                              const unsigned long long* __restrict__ keys, int ndup, float4* scene_pts, float4* scene_nrm,
                              const float4* __restrict__ meas_pts, const float4* __restrict__ meas_nrm,
-                             unsigned char* __restrict__ merged) {
+                             unsigned char* __restrict__ merged, Feat f) {
   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < ndup; t += gridDim.x * blockDim.x) {
     const unsigned s = (unsigned) (keys[t] >> 32);
     if (t > 0 && (unsigned) (keys[t - 1] >> 32) == s) continue;  // not the first of its group
     for (int j = t; j < ndup && (unsigned) (keys[j] >> 32) == s; ++j) {
       const srrg2_correspondence k = corr[(unsigned) keys[j]];
-      if (merge_one(dim, M, max_response, max_d2, scene_pts, scene_nrm, meas_pts, meas_nrm, k.fixed_idx, k.moving_idx, k.response))
+      if (merge_one<FEAT>(dim, M, max_response, max_d2, scene_pts, scene_nrm, meas_pts, meas_nrm, k.fixed_idx, k.moving_idx, k.response, f))
         merged[k.moving_idx] = 1;
     }
   }
@@ -220,13 +253,14 @@ __global__ void k_merge_dups(int dim, Xf M, float max_response, float max_d2, co
 // the tracker's path: correspondences straight from the aligner's per-point arrays (sorted order of its moving cloud =
 // the clipped scene), flipped and mapped to the global scene (tracker_slice_processor_impl.cpp:175-181).  The map is
 // injective, so every scene point is hit at most once: no ordering to respect.
+template <bool FEAT>
 __global__ void k_merge_from_aligner(int dim, Xf M, float max_response, float max_d2, const float4* __restrict__ moving_sorted,
                                      const int* __restrict__ corr_fixed, const float* __restrict__ corr_resp,
                                      const unsigned char* __restrict__ corr_stat, int prune, int nm,
                                      const int* __restrict__ gidx, int n_scene, int n_meas, float4* scene_pts,
                                      float4* scene_nrm, const float4* __restrict__ meas_pts,
                                      const float4* __restrict__ meas_nrm, unsigned char* __restrict__ merged,
-                                     int* __restrict__ scalars) {
+                                     int* __restrict__ scalars, Feat f) {
   int ncorr = 0, nmerged = 0;
   for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < nm; g += gridDim.x * blockDim.x) {
     const int m = corr_fixed[g];  // aligner "fixed" = the measurement
@@ -239,7 +273,7 @@ __global__ void k_merge_from_aligner(int dim, Xf M, float max_response, float ma
       continue;
     }
     ++ncorr;
-    if (merge_one(dim, M, max_response, max_d2, scene_pts, scene_nrm, meas_pts, meas_nrm, s, m, corr_resp[g])) {
+    if (merge_one<FEAT>(dim, M, max_response, max_d2, scene_pts, scene_nrm, meas_pts, meas_nrm, s, m, corr_resp[g], f)) {
       // (several scene points may merge into one measurement point: its flag byte is set through an atomic OR on the word that
       // holds it, and whoever finds it clear counts it -- the number of DISTINCT merged points without a second pass over the
       // flags, k_count_merged, and its launch, copy and wait: a tracker's merge 0.088 -> ~0.07 ms)
@@ -265,16 +299,31 @@ __global__ void k_append_flag(int dim, const float4* __restrict__ meas_pts, cons
     flags[i] = (!(merged && merged[i]) && valid_point(dim, meas_pts[i])) ? 1 : 0;
 }
 
+template <bool FEAT>
 __global__ void k_append_scatter(int dim, Xf M, const float4* __restrict__ meas_pts, const float4* __restrict__ meas_nrm,
                                  const unsigned char* __restrict__ merged, int n, const int* __restrict__ offset, int base,
-                                 float4* __restrict__ scene_pts, float4* __restrict__ scene_nrm) {
+                                 float4* __restrict__ scene_pts, float4* __restrict__ scene_nrm, Feat f) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const float4 p = meas_pts[i];
     if ((merged && merged[i]) || !valid_point(dim, p)) continue;
     const int k  = base + offset[i];
     scene_pts[k] = xform_point(dim, M, p);  // transformInPlace: coordinates and normal
     scene_nrm[k] = meas_nrm ? rotate_normal(dim, M, meas_nrm[i]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (FEAT) move_features(f, i, k);  // (descriptors and intensities are frame-free: appended unchanged)
   }
+}
+
+// set_features: descriptor rows of any stride and alignment -> two uint4 per point.  One thread per 32-bit word, read as bytes.
+__global__ void k_ingest_descriptors(const unsigned char* __restrict__ src, size_t stride, int n, unsigned* __restrict__ dst) {
+  const size_t words = (size_t) n * 8;
+  for (size_t w = (size_t) blockIdx.x * blockDim.x + threadIdx.x; w < words; w += (size_t) gridDim.x * blockDim.x) {
+    const unsigned char* b = src + (w >> 3) * stride + (w & 7) * 4;
+    dst[w] = (unsigned) b[0] | ((unsigned) b[1] << 8) | ((unsigned) b[2] << 16) | ((unsigned) b[3] << 24);
+  }
+}
+
+__global__ void k_ingest_intensity(const float* __restrict__ src, size_t stride_floats, int n, float* __restrict__ dst) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[i] = src[(size_t) i * stride_floats];
 }
 
 int blocks_for(int n) {
@@ -287,9 +336,65 @@ int scene_device(srrg2_scene* s) {
   return 0;
 }
 
-// grow the point arrays to hold n points, keeping the first `keep`
+// the feature-carrying instantiation of a kernel when the call moves features, else the plain one
+#define LAUNCH_FEAT(kernel, feat, grid, stream, ...)                                    \
+  do {                                                                                  \
+    if (feat)                                                                           \
+      hipLaunchKernelGGL(kernel<true>, grid, dim3(256), 0, stream, __VA_ARGS__);        \
+    else                                                                                \
+      hipLaunchKernelGGL(kernel<false>, grid, dim3(256), 0, stream, __VA_ARGS__);       \
+  } while (0)
+
+// features of `src` points written into `dst` (the fields `dst` carries; the callers have made both agree)
+Feat feat_of(const srrg2_scene* src, const srrg2_scene* dst) {
+  return Feat{dst->has_desc ? src->desc.p : nullptr, dst->has_inten ? src->inten.p : nullptr,
+              dst->has_desc ? dst->desc.p : nullptr, dst->has_inten ? dst->inten.p : nullptr};
+}
+
+bool moves_features(const Feat& f) { return f.dst_desc || f.dst_inten; }
+
+// a feature array follows the capacity of the point arrays (per_point elements each), keeping the first `keep` points' entries
+template <typename T>
+int grow_feature(srrg2_scene* s, DevBuf<T>& buf, size_t per_point, int keep) {
+  const size_t want = s->pts.cap * per_point;
+  if (want <= buf.cap) return 0;
+  DevBuf<T> nb;
+  int rc;
+  if ((rc = nb.reserve(want))) return rc;
+  const size_t kept = std::min((size_t) (keep > 0 ? keep : 0) * per_point, buf.cap);
+  if (kept > 0) {
+    HIP_TRY(hipMemcpyAsync(nb.p, buf.p, sizeof(T) * kept, hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+  }
+  buf.release();
+  buf = nb;
+  return 0;
+}
+
+int features_reserve(srrg2_scene* s, int keep) {
+  int rc;
+  if (s->has_desc && (rc = grow_feature(s, s->desc, 2, keep))) return rc;
+  if (s->has_inten && (rc = grow_feature(s, s->inten, 1, keep))) return rc;
+  return 0;
+}
+
+// "homo": scene and measurement are clouds of ONE point type.  An empty scene takes the measurement's; otherwise the fields
+// must agree.  Called before a merge changes anything.
+int bind_features(srrg2_scene* scene, const srrg2_scene* meas, const char* who) {
+  if (scene->n == 0) {
+    scene->has_desc  = meas->has_desc;
+    scene->has_inten = meas->has_inten;
+    return features_reserve(scene, 0);
+  }
+  if (scene->has_desc != meas->has_desc || scene->has_inten != meas->has_inten)
+    return fail(SRRG2_E_STATE, std::string(who) + ": scene and measurement disagree on descriptors / intensity (one point type "
+                                                  "per merger: merger_correspondence_homo.h:36-40)");
+  return 0;
+}
+
+// grow the point arrays (and the feature arrays that are present) to hold n points, keeping the first `keep`
 int scene_reserve(srrg2_scene* s, int n, int keep) {
-  if ((size_t) n <= s->pts.cap && (size_t) n <= s->nrm.cap) return 0;
+  if ((size_t) n <= s->pts.cap && (size_t) n <= s->nrm.cap) return features_reserve(s, keep);
   DevBuf<float4> np, nn;
   int rc;
   const size_t want = (size_t) n + (size_t) n / 2 + 1024;
@@ -304,7 +409,7 @@ int scene_reserve(srrg2_scene* s, int n, int keep) {
   s->nrm.release();
   s->pts = np;
   s->nrm = nn;
-  return 0;
+  return features_reserve(s, keep);
 }
 
 // flags[0..n) -> exclusive scan in place; total in scalars[0] (host value returned)
@@ -357,9 +462,10 @@ int finish_merge(srrg2_scene* scene, srrg2_scene* meas, const Xf& M, bool have_c
       if ((rc = scan_flags(scene, n_meas, &total))) return rc;
       if (total > 0) {
         if ((rc = scene_reserve(scene, scene->n + total, scene->n))) return rc;
-        hipLaunchKernelGGL(k_append_scatter, dim3(blocks_for(n_meas)), dim3(256), 0, scene->stream, scene->dim, M,
-                           meas->pts.p, meas->has_normals ? meas->nrm.p : nullptr, mg, n_meas, scene->flags.p, scene->n,
-                           scene->pts.p, scene->nrm.p);
+        const Feat f = feat_of(meas, scene);
+        LAUNCH_FEAT(k_append_scatter, moves_features(f), dim3(blocks_for(n_meas)), scene->stream, scene->dim, M, meas->pts.p,
+                    meas->has_normals ? meas->nrm.p : nullptr, mg, n_meas, scene->flags.p, scene->n, scene->pts.p,
+                    scene->nrm.p, f);
         scene->n += total;
       }
       out->num_added = total;
@@ -408,7 +514,7 @@ int srrg2_scene_destroy(srrg2_scene_h s) {
   if (!s) return 0;
   (void) hipSetDevice(s->device);
   if (s->stream) (void) hipStreamSynchronize(s->stream);
-  s->pts.release(); s->nrm.release(); s->gidx.release(); s->flags.release(); s->scan_sums.release();
+  s->pts.release(); s->nrm.release(); s->desc.release(); s->inten.release(); s->gidx.release(); s->flags.release(); s->scan_sums.release();
   s->counts.release(); s->dup_list.release(); s->dup_keys.release(); s->sort_tmp.release(); s->merged.release(); s->corr.release(); s->staging.release(); s->dscalars.release();
   if (s->scalars) (void) hipHostFree(s->scalars);
   if (s->stream) (void) hipStreamDestroy(s->stream);
@@ -423,6 +529,7 @@ int srrg2_scene_set(srrg2_scene_h s, const float* coords, int cs, const float* n
     return fail(SRRG2_E_INVALID, "scene_set: strides must be multiples of 4 bytes and >= dim floats");
   int rc;
   if ((rc = scene_device(s))) return rc;
+  s->has_desc = s->has_inten = false;  // the content is replaced: features of the old points go with them
   if ((rc = scene_reserve(s, n > 0 ? n : 1, 0))) return rc;
   s->n           = n;
   s->ng          = 0;
@@ -492,6 +599,73 @@ int srrg2_scene_device_arrays(srrg2_scene_h s, const float** coords, const float
   return 0;
 }
 
+int srrg2_scene_set_features(srrg2_scene_h s, const uint8_t* descriptors, int ds, const float* intensity, int is, int n,
+                             int mem) {
+  if (!s) return fail(SRRG2_E_INVALID, "scene_set_features: null scene");
+  if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, "scene_set_features: bad mem");
+  if (n != s->n) return fail(SRRG2_E_INVALID, "scene_set_features: n differs from the scene's size");
+  if ((descriptors && ds < SRRG2_DESCRIPTOR_BYTES) || (intensity && (is < 4 || is % 4)))
+    return fail(SRRG2_E_INVALID, "scene_set_features: descriptor stride >= 32 bytes, intensity stride a multiple of 4 bytes, >= 4");
+  int rc;
+  if ((rc = scene_device(s))) return rc;
+  s->has_desc  = descriptors != nullptr;
+  s->has_inten = intensity != nullptr;
+  if ((rc = features_reserve(s, 0))) return rc;
+  if (n == 0 || (!descriptors && !intensity)) return 0;
+  const unsigned char* dd = descriptors;
+  const float* di         = intensity;
+  if (mem == SRRG2_MEM_HOST) {
+    const size_t bd    = descriptors ? (size_t) (n - 1) * ds + SRRG2_DESCRIPTOR_BYTES : 0;
+    const size_t bi    = intensity ? (size_t) (n - 1) * is + 4 : 0;
+    const size_t off_i = (bd + 63) / 64 * 64;
+    if ((rc = s->staging.reserve(off_i + bi + 64))) return rc;
+    if (descriptors) {
+      HIP_TRY(hipMemcpyAsync(s->staging.p, descriptors, bd, hipMemcpyHostToDevice, s->stream));
+      dd = (const unsigned char*) s->staging.p;
+    }
+    if (intensity) {
+      HIP_TRY(hipMemcpyAsync(s->staging.p + off_i, intensity, bi, hipMemcpyHostToDevice, s->stream));
+      di = (const float*) (s->staging.p + off_i);
+    }
+  }
+  if (descriptors)
+    hipLaunchKernelGGL(k_ingest_descriptors, dim3(blocks_for(n)), dim3(256), 0, s->stream, dd, (size_t) ds, n,
+                       reinterpret_cast<unsigned*>(s->desc.p));
+  if (intensity)
+    hipLaunchKernelGGL(k_ingest_intensity, dim3(blocks_for(n)), dim3(256), 0, s->stream, di, (size_t) (is / 4), n, s->inten.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return 0;
+}
+
+int srrg2_scene_has_features(srrg2_scene_h s, int* has_descriptors, int* has_intensity) {
+  if (!s) return fail(SRRG2_E_INVALID, "scene_has_features: null scene");
+  if (has_descriptors) *has_descriptors = s->has_desc ? 1 : 0;
+  if (has_intensity) *has_intensity = s->has_inten ? 1 : 0;
+  return 0;
+}
+
+int srrg2_scene_get_features(srrg2_scene_h s, uint8_t* descriptors_out, float* intensity_out, int capacity, int* n) {
+  if (!s || !n || capacity < 0) return fail(SRRG2_E_INVALID, "scene_get_features: bad arguments");
+  int rc;
+  if ((rc = scene_device(s))) return rc;
+  const int m = s->n < capacity ? s->n : capacity;
+  if (m > 0 && descriptors_out && s->has_desc)
+    HIP_TRY(hipMemcpy(descriptors_out, s->desc.p, (size_t) m * SRRG2_DESCRIPTOR_BYTES, hipMemcpyDeviceToHost));
+  if (m > 0 && intensity_out && s->has_inten)
+    HIP_TRY(hipMemcpy(intensity_out, s->inten.p, (size_t) m * sizeof(float), hipMemcpyDeviceToHost));
+  *n = s->n;
+  return 0;
+}
+
+int srrg2_scene_device_features(srrg2_scene_h s, const uint8_t** descriptors, const float** intensity, int* n) {
+  if (!s || !n) return fail(SRRG2_E_INVALID, "scene_device_features: bad arguments");
+  if (descriptors) *descriptors = s->has_desc ? (const uint8_t*) s->desc.p : nullptr;
+  if (intensity) *intensity = s->has_inten ? s->inten.p : nullptr;
+  *n = s->n;
+  return 0;
+}
+
 int srrg2_scene_clip_ball(srrg2_scene_h full, const float* robot_in_local_map, float range, srrg2_scene_h clipped,
                           int* status) {
   if (!full || !clipped || !robot_in_local_map || full == clipped || full->dim != clipped->dim ||
@@ -508,6 +682,8 @@ int srrg2_scene_clip_ball(srrg2_scene_h full, const float* robot_in_local_map, f
   const float range2 = range * range;
   const int n        = full->n;
   clipped->has_normals = full->has_normals;
+  clipped->has_desc    = full->has_desc;
+  clipped->has_inten   = full->has_inten;
   clipped->n = clipped->ng = 0;
   if (status) *status = n == 0 ? SRRG2_CLIPPER_READY : SRRG2_CLIPPER_SUCCESSFUL;  // :24-28
   if (n == 0) return 0;
@@ -518,15 +694,17 @@ int srrg2_scene_clip_ball(srrg2_scene_h full, const float* robot_in_local_map, f
   // A clipped scene that has room from the call before (a tracker clips around a pose that moves a little per frame): the scatter
   // is launched BEHIND the scan without the host having seen the total -- one wait per clip instead of two (0.046 -> ~0.03 ms for a
   // 100 k-point map); a total beyond the room repeats the scatter the slow way.
+  if ((rc = features_reserve(clipped, 0))) return rc;  // (room for features wherever there is room for points)
   const int room = (int) std::min<size_t>(std::min(clipped->pts.cap, clipped->nrm.cap), clipped->gidx.cap);
   bool speculated = false;
   if (room > 0) {
     if ((rc = full->scan_sums.reserve((size_t) srrg2amd::scan_num_blocks(n) + 2))) return rc;
     int* dtotal = full->scan_sums.p + full->scan_sums.cap - 1;
     srrg2amd::launch_exclusive_scan(full->flags.p, n, full->scan_sums.p, dtotal, st);
-    hipLaunchKernelGGL(k_clip_scatter, dim3(blocks_for(n)), dim3(256), 0, st, full->dim, L, range2, full->pts.p,
-                       full->has_normals ? full->nrm.p : nullptr, n, full->flags.p, clipped->pts.p, clipped->nrm.p,
-                       clipped->gidx.p, room);
+    const Feat f = feat_of(full, clipped);
+    LAUNCH_FEAT(k_clip_scatter, moves_features(f), dim3(blocks_for(n)), st, full->dim, L, range2, full->pts.p,
+                full->has_normals ? full->nrm.p : nullptr, n, full->flags.p, clipped->pts.p, clipped->nrm.p, clipped->gidx.p,
+                room, f);
     HIP_TRY(hipMemcpyAsync(&full->scalars[0], dtotal, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
@@ -538,10 +716,12 @@ int srrg2_scene_clip_ball(srrg2_scene_h full, const float* robot_in_local_map, f
   if (!speculated) {
     if ((rc = scene_reserve(clipped, total > 0 ? total : 1, 0))) return rc;
     if ((rc = clipped->gidx.reserve((size_t) (total > 0 ? total : 1)))) return rc;
-    if (total > 0)
-      hipLaunchKernelGGL(k_clip_scatter, dim3(blocks_for(n)), dim3(256), 0, st, full->dim, L, range2, full->pts.p,
-                         full->has_normals ? full->nrm.p : nullptr, n, full->flags.p, clipped->pts.p, clipped->nrm.p,
-                         clipped->gidx.p, total);
+    if (total > 0) {
+      const Feat f = feat_of(full, clipped);
+      LAUNCH_FEAT(k_clip_scatter, moves_features(f), dim3(blocks_for(n)), st, full->dim, L, range2, full->pts.p,
+                  full->has_normals ? full->nrm.p : nullptr, n, full->flags.p, clipped->pts.p, clipped->nrm.p, clipped->gidx.p,
+                  total, f);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
   }
@@ -569,6 +749,7 @@ int srrg2_scene_merge(srrg2_scene_h scene, srrg2_scene_h meas, const float* meas
   int rc;
   if ((rc = check_params(p))) return rc;
   if ((rc = scene_device(scene))) return rc;
+  if ((rc = bind_features(scene, meas, "scene_merge"))) return rc;
   std::memset(out, 0, sizeof(*out));
   out->status  = SRRG2_MERGER_INITIALIZING;  // :15
   const Xf M   = load_transform(scene->dim, measurement_in_scene);
@@ -594,9 +775,11 @@ int srrg2_scene_merge(srrg2_scene_h scene, srrg2_scene_h meas, const float* meas
       if (dups && (rc = scene->flags.reserve((size_t) ncorr + 1))) return rc;
       float4* snrm       = scene->nrm.p;  // (always allocated; written like the oracle's)
       const float4* mnrm = meas->has_normals ? meas->nrm.p : nullptr;
-      hipLaunchKernelGGL(k_merge_apply, dim3(blocks_for(ncorr)), dim3(256), 0, st, scene->dim, M, p->maximum_response,
-                         p->maximum_distance_geometry_squared, scene->corr.p, ncorr, scene->counts.p, scene->pts.p, snrm,
-                         meas->pts.p, mnrm, scene->merged.p, dups ? scene->flags.p : nullptr);
+      const Feat f       = feat_of(meas, scene);
+      const bool feat    = moves_features(f);
+      LAUNCH_FEAT(k_merge_apply, feat, dim3(blocks_for(ncorr)), st, scene->dim, M, p->maximum_response,
+                  p->maximum_distance_geometry_squared, scene->corr.p, ncorr, scene->counts.p, scene->pts.p, snrm, meas->pts.p,
+                  mnrm, scene->merged.p, dups ? scene->flags.p : nullptr, f);
       if (dups) {
         int ndup = 0;
         if ((rc = scan_flags(scene, ncorr, &ndup))) return rc;
@@ -612,9 +795,9 @@ int srrg2_scene_merge(srrg2_scene_h scene, srrg2_scene_h meas, const float* meas
           HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, kin, kout, ndup, 0, 64, st));
           if ((rc = scene->sort_tmp.reserve(std::max<size_t>(tmp_bytes, 1)))) return rc;
           HIP_TRY(hipcub::DeviceRadixSort::SortKeys(scene->sort_tmp.p, tmp_bytes, kin, kout, ndup, 0, 64, st));
-          hipLaunchKernelGGL(k_merge_dups, dim3(blocks_for(ndup)), dim3(256), 0, st, scene->dim, M, p->maximum_response,
-                             p->maximum_distance_geometry_squared, scene->corr.p, kout, ndup, scene->pts.p, snrm, meas->pts.p,
-                             mnrm, scene->merged.p);
+          LAUNCH_FEAT(k_merge_dups, feat, dim3(blocks_for(ndup)), st, scene->dim, M, p->maximum_response,
+                      p->maximum_distance_geometry_squared, scene->corr.p, kout, ndup, scene->pts.p, snrm, meas->pts.p, mnrm,
+                      scene->merged.p, f);
         }
       }
     }
@@ -637,6 +820,7 @@ int srrg2_scene_merge_from_aligner(srrg2_scene_h scene, srrg2_scene_h meas, cons
   if (v.nm != clipped->ng || v.nm != clipped->n)
     return fail(SRRG2_E_STATE, "scene_merge_from_aligner: the aligner's moving cloud is not the clipped scene");
   if (v.nf != meas->n) return fail(SRRG2_E_STATE, "scene_merge_from_aligner: the aligner's fixed cloud is not the measurement");
+  if ((rc = bind_features(scene, meas, "scene_merge_from_aligner"))) return rc;
   if (v.ready_event) HIP_TRY(hipStreamWaitEvent(scene->stream, (hipEvent_t) v.ready_event, 0));  // (no host wait in between)
   std::memset(out, 0, sizeof(*out));
   out->status = SRRG2_MERGER_INITIALIZING;
@@ -650,11 +834,11 @@ int srrg2_scene_merge_from_aligner(srrg2_scene_h scene, srrg2_scene_h meas, cons
   int* const counters         = reinterpret_cast<int*>(scene->merged.p);
   unsigned char* const flags_ = scene->merged.p + 64;
   if (v.nm > 0) {
-    hipLaunchKernelGGL(k_merge_from_aligner, dim3(std::min(blocks_for(v.nm), 256)), dim3(256), 0, st, scene->dim, M, p->maximum_response,
-                       p->maximum_distance_geometry_squared, v.moving_sorted, v.corr_fixed, v.corr_resp, v.corr_stat,
-                       v.prune ? 1 : 0, v.nm, clipped->gidx.p, n_scene, n_meas, scene->pts.p,
-                       scene->nrm.p, meas->pts.p, meas->has_normals ? meas->nrm.p : nullptr,
-                       flags_, counters);
+    const Feat f = feat_of(meas, scene);
+    LAUNCH_FEAT(k_merge_from_aligner, moves_features(f), dim3(std::min(blocks_for(v.nm), 256)), st, scene->dim, M,
+                p->maximum_response, p->maximum_distance_geometry_squared, v.moving_sorted, v.corr_fixed, v.corr_resp,
+                v.corr_stat, v.prune ? 1 : 0, v.nm, clipped->gidx.p, n_scene, n_meas, scene->pts.p, scene->nrm.p, meas->pts.p,
+                meas->has_normals ? meas->nrm.p : nullptr, flags_, counters, f);
     if ((rc = read_scalars(scene, counters))) return rc;
     if (scene->scalars[2]) return fail(SRRG2_E_STATE, "scene_merge_from_aligner: index out of range");
   }
@@ -665,3 +849,15 @@ int srrg2_scene_merge_from_aligner(srrg2_scene_h scene, srrg2_scene_h meas, cons
 }
 
 }  // extern "C"
+
+// what descriptors.hip sees of a scene (srrg2_descriptor_db_add_scene / _match_scene)
+int srrg2amd::scene_feature_view(srrg2_scene* s, srrg2amd::SceneFeatureView* v) {
+  if (!s || !v) return fail(SRRG2_E_INVALID, "scene_feature_view: bad arguments");
+  v->pts    = s->pts.p;
+  v->desc   = s->has_desc ? s->desc.p : nullptr;
+  v->n      = s->n;
+  v->dim    = s->dim;
+  v->device = s->device;
+  v->stream = s->stream;
+  return 0;
+}

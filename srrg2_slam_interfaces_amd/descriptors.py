@@ -8,6 +8,8 @@ Semantics (include/srrg2_slam_amd.h, DESIGN.md section 5 "Descriptor matching"):
     point indices of the caller's arrays, never compacted.
   - ``add`` appends the valid descriptors of one local map and returns its database index (-1: nothing valid, not added).
   - ``match`` returns the candidate maps (age gate, count gate) with their deduplicated correspondences.
+  - ``add_scene`` / ``match_scene`` are ``add`` / ``match`` fed on the device with the descriptors of a ``mapping.Scene``
+    that carries them and valid = the points with finite coordinates.
 There is no CPU fallback: without the library or a HIP device, construction raises.
 """
 import ctypes as C
@@ -114,6 +116,28 @@ class DescriptorDatabase:
         self._check(self._lib.srrg2_descriptor_db_add(self._h, _u8p(d), _u8p(v), C.c_int(len(d)), C.byref(idx)))
         return idx.value
 
+    def _scene_handle(self, scene):
+        if getattr(scene, "_b", None) is None or scene._b.lib is not self._lib:
+            raise ValueError("add_scene / match_scene need a Scene of the HIP library (mapping.Scene on scene_binding())")
+        return scene._h
+
+    def add_scene(self, scene):
+        """add() with the descriptors of ``scene`` (Scene.set_features) read on the device; valid = finite coordinates."""
+        idx = C.c_int(-1)
+        self._check(self._lib.srrg2_descriptor_db_add_scene(self._h, self._scene_handle(scene), C.byref(idx)))
+        return idx.value
+
+    def match_scene(self, scene, query_index=None, max_distance=25.0, min_age=0, min_matches=0):
+        """match() with the descriptors of ``scene`` read on the device; fixed_idx are the scene's point indices."""
+        if query_index is None:
+            query_index = self.size()[0]
+        check_match_args(max_distance, min_age, min_matches, query_index)
+        K = C.c_int(0)
+        self._check(self._lib.srrg2_descriptor_db_match_scene(self._h, self._scene_handle(scene), C.c_int64(int(query_index)),
+                                                              C.c_float(max_distance), C.c_uint32(int(min_age)),
+                                                              C.c_int64(int(min_matches)), C.byref(K)))
+        return self._result(K.value)
+
     def match(self, descriptors, valid=None, query_index=None, max_distance=25.0, min_age=0, min_matches=0):
         """query_index: the query map's database index (None: a new map, index = number of maps)."""
         d = as_descriptors(descriptors)
@@ -126,7 +150,10 @@ class DescriptorDatabase:
                                                         C.c_int64(int(query_index)), C.c_float(max_distance),
                                                         C.c_uint32(int(min_age)), C.c_int64(int(min_matches)),
                                                         C.byref(K)))
-        K = K.value
+        return self._result(K.value)
+
+    def _result(self, K):
+        """the getters after a match"""
         ref = np.zeros(K, np.int32)
         cnt = np.zeros(K, np.int64)
         off = np.zeros(K + 1, np.int64)

@@ -282,7 +282,13 @@ class MultiLoopDetectorHBST:
     ``compute()`` is the two in a row (:12-39); ``compute_alignments`` also takes matches from elsewhere.
     PARAMs: loop_detector.h (relocalize_min_inliers / max_chi_inliers / min_inliers_ratio),
     multi_loop_detector_hbst.h:45-74 (the descriptor ones).  The database is created on ``device`` at the first
-    compute_correspondences() unless one is given."""
+    compute_correspondences() unless one is given.
+
+    The query may be a ``mapping.Scene`` that carries descriptors (``Scene.set_features``) in place of the host arrays --
+    the local map's cloud the reference reads its descriptors from (:84-85, :131-136).  Then nothing but counts, matches
+    and results crosses to the host: the database matches and adds the scene on the device (valid = finite coordinates),
+    the detector remembers the scene by graph id, and the alignments bind the scenes' device arrays.  A remembered scene
+    must stay alive and unchanged while it can be a candidate, as the reference's local maps do."""
 
     def __init__(self, relocalize_aligner, relocalize_min_inliers=500, relocalize_max_chi_inliers=0.005,
                  relocalize_min_inliers_ratio=0.7, maximum_descriptor_distance=25.0, maximum_leaf_size=100,
@@ -329,11 +335,43 @@ class MultiLoopDetectorHBST:
     def graph_id(self, index):
         return self._local_maps_in_database[index][0]
 
+    @staticmethod
+    def _is_scene(x):
+        from .mapping import Scene
+
+        return isinstance(x, Scene)
+
+    def _database(self):
+        if self.database is None:
+            from .descriptors import DescriptorDatabase
+
+            self.database = DescriptorDatabase(device=self.device)
+        return self.database
+
+    def _correspondences_from_scene(self, graph_id, scene):
+        self._indices, self._correspondences_per_reference, self.last_match = [], {}, None
+        if scene.size() == 0:  # :86-91
+            self._query = None
+            return self.indices()
+        self._query = (graph_id, scene, None, scene, None)
+        query_index = self._graph_id_to_database_index.get(graph_id, len(self._local_maps_in_database))
+        res = self._database().match_scene(scene, query_index, self.maximum_descriptor_distance,
+                                           self.minimum_age_difference_to_candidates, self.relocalize_min_inliers)
+        self.last_match = res
+        self._indices = [int(r) for r in res.indices]
+        self._correspondences_per_reference = {int(r): c for r, c in zip(res.indices, res.correspondences)}
+        return self.indices()
+
     def compute_correspondences(self, graph_id, descriptors, valid=None, points=None, normals=None):
         """computeCorrespondences (:72-161) for the query local map ``graph_id``; points / normals are kept for a later
-        add_previous_query() (the reference map's cloud of future alignments).  Returns indices()."""
+        add_previous_query() (the reference map's cloud of future alignments).  ``descriptors`` may be a Scene with
+        descriptors: it is the whole query (valid, points and normals are its own).  Returns indices()."""
         from .descriptors import as_descriptors, as_valid
 
+        if self._is_scene(descriptors):
+            if valid is not None or points is not None or normals is not None:
+                raise ValueError("a Scene is the whole query: valid / points / normals come from it")
+            return self._correspondences_from_scene(graph_id, descriptors)
         d = as_descriptors(descriptors)
         v = as_valid(valid, len(d))
         self._indices, self._correspondences_per_reference, self.last_match = [], {}, None
@@ -362,7 +400,7 @@ class MultiLoopDetectorHBST:
         graph_id, d, v, points, normals = self._query
         if graph_id in self._graph_id_to_database_index:
             return -1
-        index = self.database.add(d, v)
+        index = self.database.add_scene(d) if self._is_scene(d) else self.database.add(d, v)
         if index < 0:
             return -1
         assert index == len(self._local_maps_in_database)
@@ -371,11 +409,18 @@ class MultiLoopDetectorHBST:
         self._query = None
         return index
 
-    def compute(self, graph_id, points, normals, descriptors, valid=None, pose_in_query=None):
+    def compute(self, graph_id, points, normals=None, descriptors=None, valid=None, pose_in_query=None):
         """compute() (:12-39): computeCorrespondences, then the alignments of the candidates.  The fixed cloud is the
         query local map's points, the moving cloud the reference map's (:333-334); a closure's target is the reference
-        map's graph id."""
-        self.compute_correspondences(graph_id, descriptors, valid, points, normals)
+        map's graph id.  ``points`` may be a Scene with descriptors (then normals / descriptors / valid stay None)."""
+        if self._is_scene(points):
+            if normals is not None or descriptors is not None or valid is not None:
+                raise ValueError("a Scene is the whole query: normals / descriptors / valid come from it")
+            self.compute_correspondences(graph_id, points)
+        else:
+            if descriptors is None:
+                raise ValueError("compute: descriptors missing")
+            self.compute_correspondences(graph_id, descriptors, valid, points, normals)
         candidates = []
         for r in self._indices:
             gid, ref_points, ref_normals = self._local_maps_in_database[r]
@@ -383,9 +428,49 @@ class MultiLoopDetectorHBST:
                                "correspondences": self._correspondences_per_reference[r]})
         return self.compute_alignments(graph_id, points, normals, candidates, pose_in_query)
 
+    def _align_scenes(self, fixed, todo):
+        """the batched locked solve on device-resident clouds: the query scene's arrays are the fixed cloud, the candidates'
+        (float4 records, stride 16) are concatenated device to device into one buffer for the call"""
+        import ctypes as C
+
+        from . import _capi
+
+        lib = _capi.lib()
+        lib.srrg2_amd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        lib.srrg2_amd_device_malloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
+        lib.srrg2_amd_device_free.argtypes = [C.c_void_p]
+        al = self.relocalize_aligner
+        addr = lambda p: C.cast(p, C.c_void_p).value  # noqa: E731
+        fp, fn, n = fixed.device_arrays()
+        al.set_cloud_device("set_fixed", 0, addr(fp), 16, addr(fn) if fn is not None else None, 16, n)
+        arrays = [c["moving"].device_arrays() for c in todo]
+        with_normals = all(a[1] is not None for a in arrays)
+        offsets = np.zeros(len(todo) + 1, np.int32)
+        offsets[1:] = np.cumsum([a[2] for a in arrays])
+        total = max(int(offsets[-1]), 1)
+        bufs = []
+        try:
+            for _ in range(2 if with_normals else 1):
+                p = C.c_void_p()
+                if lib.srrg2_amd_device_malloc(C.c_size_t(16 * total), C.byref(p)):
+                    raise RuntimeError("srrg2_amd_device_malloc failed")
+                bufs.append(p.value)
+            for k, (cp, cn, m) in enumerate(arrays):
+                for buf, src in zip(bufs, (cp, cn)):
+                    if m and lib.srrg2_amd_memcpy(C.c_void_p(buf + 16 * int(offsets[k])), C.c_void_p(addr(src)),
+                                                  C.c_size_t(16 * m), 2, None):
+                        raise RuntimeError("srrg2_amd_memcpy (device -> device) failed")
+            return al.compute_batch_correspondences_device(
+                bufs[0], 16, bufs[1] if with_normals else None, 16, offsets, [c["correspondences"] for c in todo],
+                [sl.identity(al.dim)] * len(todo))  # :335
+        finally:
+            for b in bufs:
+                lib.srrg2_amd_device_free(C.c_void_p(b))
+
     def compute_alignments(self, query_id, fixed, fixed_normals, candidates, pose_in_query=None):
         """candidates: list of dicts {reference, moving, moving_normals or None, correspondences (fixed_idx = query
-        point, moving_idx = reference point)}"""
+        point, moving_idx = reference point)}.  With a Scene as ``fixed`` every candidate's ``moving`` must be a Scene too:
+        the clouds are bound from their device arrays."""
         al = self.relocalize_aligner
         dim = al.dim
         pose_in_query = sl.identity(dim) if pose_in_query is None else np.asarray(pose_in_query, np.float32)
@@ -398,11 +483,16 @@ class MultiLoopDetectorHBST:
             todo.append(c)
         if not todo:
             return self.detected_closures
-        al.set_fixed(0, fixed, fixed_normals)
-        normals = [c.get("moving_normals") for c in todo]
-        results = al.compute_batch_correspondences(
-            [c["moving"] for c in todo], [c["correspondences"] for c in todo], [sl.identity(dim)] * len(todo),  # :335
-            normals if all(n is not None for n in normals) else None)
+        if self._is_scene(fixed) or any(self._is_scene(c["moving"]) for c in todo):
+            if not (self._is_scene(fixed) and all(self._is_scene(c["moving"]) for c in todo)):
+                raise ValueError("compute_alignments: scenes and host arrays cannot be mixed")
+            results = self._align_scenes(fixed, todo)
+        else:
+            al.set_fixed(0, fixed, fixed_normals)
+            normals = [c.get("moving_normals") for c in todo]
+            results = al.compute_batch_correspondences(
+                [c["moving"] for c in todo], [c["correspondences"] for c in todo], [sl.identity(dim)] * len(todo),  # :335
+                normals if all(n is not None for n in normals) else None)
         for c, r in zip(todo, results):
             if r["status"] != abi.SUCCESS:  # :346-356
                 self.drops.append((c["reference"], "ALIGNER DROP [code: %d]" % r["status"]))

@@ -1,6 +1,8 @@
 """Python mirror of the tracker-side scene steps over the C ABI (srrg2_scene_*).
 
-``Scene``                      a point(+normal) cloud kept in device memory (a LocalMap scene slice / a measurement)
+``Scene``                      a point(+normal) cloud kept in device memory (a LocalMap scene slice / a measurement); with
+                               ``set_features`` also a 256-bit descriptor and an intensity per point (PointIntensityDescriptor2f / 3f
+                               clouds), which clipper and merger move with the points
 ``SceneClipperBall``           ``SceneClipper_`` (S/mapping/scene_clipper.h:17-122) with the ball policy
 ``MergerCorrespondenceHomo``   ``MergerCorrespondenceHomo_`` (S/mapping/merger_correspondence_homo_impl.cpp:11-125)
 
@@ -56,6 +58,25 @@ class _Binding:
             raise RuntimeError("%s (code %d)" % (msg.decode() if msg else "", rc))
 
 
+def as_scene_features(descriptors, intensity, n):
+    """argument checking of Scene.set_features: (descriptors as (n, 32) uint8 or None, intensity as (n,) float32 or None)"""
+    d = i = None
+    if descriptors is not None:
+        from .descriptors import as_descriptors
+
+        d = as_descriptors(descriptors)
+        if d.shape[0] != n:
+            raise ValueError("descriptors: %d rows for a scene of %d points" % (d.shape[0], n))
+    if intensity is not None:
+        i = np.asarray(intensity)
+        if i.dtype.kind not in "fiub":
+            raise ValueError("intensity: numbers expected, got %s" % i.dtype)
+        if i.shape not in ((n,), (n, 1)):
+            raise ValueError("intensity: expected %d values, got shape %s" % (n, i.shape))
+        i = np.ascontiguousarray(i, dtype=np.float32).reshape(n)
+    return d, i
+
+
 class Scene:
     def __init__(self, binding, dim=3):
         self._b = binding
@@ -100,6 +121,48 @@ class Scene:
         k = C.c_int(0)
         self._b.check(self._b.fn("get")(self._h, _fp(c), _fp(m), C.c_int(n), C.byref(k)))
         return c[:n], m[:n]
+
+    def _feature_fn(self, name):
+        """the feature entry points exist in the HIP library only"""
+        f = getattr(self._b.lib, self._b.prefix + name, None)
+        if f is None:
+            raise NotImplementedError("%s%s: this binding has no per-point features (product library only)"
+                                      % (self._b.prefix, name))
+        return f
+
+    def set_features(self, descriptors=None, intensity=None):
+        """one 256-bit descriptor ((n, 32) uint8 rows) and / or one intensity per point; None = that field is absent
+        (both None drops the features).  They follow the points through clip and merge."""
+        d, i = as_scene_features(descriptors, intensity, self.size())
+        f = self._feature_fn("set_features")
+        n = self.size()
+        self._b.check(f(self._h, None if d is None else d.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_int(32),
+                        None if i is None else _fp(i), C.c_int(4), C.c_int(n), C.c_int(abi.MEM_HOST)))
+
+    def has_features(self):
+        """(has descriptors, has intensity)"""
+        d, i = C.c_int(0), C.c_int(0)
+        self._b.check(self._feature_fn("has_features")(self._h, C.byref(d), C.byref(i)))
+        return bool(d.value), bool(i.value)
+
+    def features(self):
+        """(descriptors as (n, 32) uint8 or None, intensity as (n,) float32 or None)"""
+        hd, hi = self.has_features()
+        n = self.size()
+        d = np.zeros((max(n, 1), 32), np.uint8) if hd else None
+        i = np.zeros(max(n, 1), np.float32) if hi else None
+        k = C.c_int(0)
+        self._b.check(self._feature_fn("get_features")(
+            self._h, None if d is None else d.ctypes.data_as(C.POINTER(C.c_uint8)), None if i is None else _fp(i),
+            C.c_int(n), C.byref(k)))
+        return (None if d is None else d[:n]), (None if i is None else i[:n])
+
+    def device_features(self):
+        """(descriptors_ptr or None, intensity_ptr or None, n): device arrays, rows of 32 bytes / floats; valid until the
+        scene is next modified"""
+        d, i, n = C.POINTER(C.c_uint8)(), C.POINTER(C.c_float)(), C.c_int(0)
+        self._b.check(self._feature_fn("device_features")(self._h, C.byref(d), C.byref(i), C.byref(n)))
+        return (d if d else None), (i if i else None), n.value
 
     def global_indices(self):
         n = C.c_int(0)

@@ -3,7 +3,8 @@
 one JSON line with the database and query sizes, the median match() time (HIP events: upload + search + compaction;
 wall clock: the whole call with the readback), pairs/s and the share of the VALU bound, the numpy restatement on a
 sample of maps scaled to the whole database (numpy, not HBST), and one MultiLoopDetectorHBST.compute() end to end.
-  usage: python tools/bench_descriptors.py [--maps 1000] [--per-map 1000] [--query 2000] [--reps 20] [--sample 16]"""
+--from-scene adds the same query matched from a Scene that carries the descriptors (match_scene: staged on the device).
+  usage: python tools/bench_descriptors.py [--maps 1000] [--per-map 1000] [--query 2000] [--reps 20] [--sample 16] [--from-scene]"""
 import argparse
 import json
 import os
@@ -40,6 +41,7 @@ def main():
     ap.add_argument("--query", type=int, default=2000)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--sample", type=int, default=16)
+    ap.add_argument("--from-scene", action="store_true")
     a = ap.parse_args()
     rng = np.random.default_rng(7)
     maps = [hr.random_descriptors(rng, a.per_map) for _ in range(a.maps)]
@@ -63,6 +65,22 @@ def main():
         wall.append((time.perf_counter() - t0) * 1e3)
         dev.append(res.device_ms)
     dev_ms, wall_ms = float(np.median(dev)), float(np.median(wall))
+    scene_ms = None
+    if a.from_scene:
+        from srrg2_slam_interfaces_amd import mapping
+
+        qs = mapping.Scene(pkg.scene_binding(0), 3)
+        qs.set(rng.uniform(-5, 5, (a.query, 3)).astype(np.float32))
+        qs.set_features(q)
+        ref = db.match_scene(qs, min_matches=min_matches)  # warm-up
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(ref.correspondences, res.correspondences))
+        sdev, swall = [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            r = db.match_scene(qs, min_matches=min_matches)
+            swall.append((time.perf_counter() - t0) * 1e3)
+            sdev.append(r.device_ms)
+        scene_ms = {"match_scene_ms_events": round(float(np.median(sdev)), 4), "match_scene_ms_wall": round(float(np.median(swall)), 4)}
     pairs = float(ndesc) * a.query
     bound_ms = pairs * OPS_PER_PAIR / VALU_LANE_OPS * 1e3
 
@@ -99,7 +117,7 @@ def main():
         "fraction_of_valu_bound": round(bound_ms / dev_ms, 3),
         "numpy_restatement_ms_scaled": round(numpy_ms, 1), "numpy_sample_maps": len(sample),
         "compute_ms": round(compute_ms, 3), "compute_candidates": len(det.indices()),
-        "compute_closures": len(closures_found)}))
+        "compute_closures": len(closures_found), **(scene_ms or {})}))
 
 
 if __name__ == "__main__":

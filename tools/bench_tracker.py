@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Frame rate of the tracker cycle with everything resident in HBM: clip the local map around the last estimate, align the
 new measurement against it (set_fixed builds the grid, set_moving sorts the clipped scene), merge.  One JSON line with the
-per-stage milliseconds (host wall clock around blocking C-ABI calls)."""
+per-stage milliseconds (host wall clock around blocking C-ABI calls).  --features: every measurement carries a 256-bit
+descriptor and an intensity per point (Scene.set_features; their upload is counted under "upload"), which clip and merge
+move with the points."""
 import argparse
 import json
 import os
@@ -23,7 +25,7 @@ KEPT = os.environ.get("SRRG2_TRACKER_KEPT", "1") != "0"
 FIXED_FIRST = os.environ.get("SRRG2_TRACKER_FIXED_FIRST", "0") != "0"  # 1: set_fixed before set_moving, as MultiTrackerBase_::align does (the same frame time: set_fixed 0.15 -> 0.10 ms, compute 0.19 -> 0.25 -- the sort it then waits for)
 
 
-def run(points=100_000, frames=30):
+def run(points=100_000, frames=30, features=False):
     """the tracker cycle of multi_tracker_impl.cpp:83-123 with everything resident in HBM; returns the JSON object"""
     import types
 
@@ -43,13 +45,22 @@ def run(points=100_000, frames=30):
         P, N = syn.scene_3d(args.points, 900 + k)
         Xi = syn.se3_inv(poses[k])
         frames.append((np.ascontiguousarray(P @ Xi[:, :3].T + Xi[:, 3], np.float32), np.ascontiguousarray(N @ Xi[:, :3].T, np.float32)))
+    feats = None
+    if features:
+        rng = np.random.default_rng(5)
+        feats = [(rng.integers(0, 256, (len(f[0]), 32), dtype=np.uint8), rng.random(len(f[0]), dtype=np.float32)) for f in frames]
     meas.set(*frames[0])
+    if feats:
+        meas.set_features(*feats[0])
     mg.set_scene(scene); mg.set_measurement(meas); mg.set_measurement_in_scene(syn.identity(3))
     mg.compute()
     est = syn.identity(3).astype(np.float32)
     t = {"upload": 0.0, "clip": 0.0, "set_moving": 0.0, "set_fixed": 0.0, "compute": 0.0, "merge": 0.0}
     for k in range(1, args.frames + 1):
-        t0 = time.perf_counter(); meas.set(*frames[k]); t1 = time.perf_counter()
+        t0 = time.perf_counter(); meas.set(*frames[k])
+        if feats:
+            meas.set_features(*feats[k])
+        t1 = time.perf_counter()
         cl.set_full_scene(scene); cl.set_clipped_scene_in_robot(clipped); cl.set_robot_in_local_map(est)
         cl.compute(); t2 = time.perf_counter()
         cp, cn, n = clipped.device_arrays()
@@ -75,7 +86,7 @@ def run(points=100_000, frames=30):
     ms = {k: 1e3 * v / nf for k, v in t.items()}
     on_device = sum(v for k, v in ms.items() if k != "upload")
     err = float(np.max(np.abs(est - poses[args.frames][:3].astype(np.float32))))
-    return {"points_per_frame": args.points, "scene_points": scene.size(), "ms": ms, "ms_per_frame_on_device": on_device,
+    return {"points_per_frame": args.points, "features": list(scene.has_features()), "scene_points": scene.size(), "ms": ms, "ms_per_frame_on_device": on_device,
             "frames_per_s_on_device": 1e3 / on_device, "pose_error_after_%d_frames" % args.frames: err, "status": al.status()}
 
 
@@ -83,8 +94,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=100_000)
     ap.add_argument("--frames", type=int, default=30)
+    ap.add_argument("--features", action="store_true", help="measurements carry a descriptor and an intensity per point")
     args = ap.parse_args()
-    print(json.dumps(run(args.points, args.frames)))
+    print(json.dumps(run(args.points, args.frames, args.features)))
 
 
 if __name__ == "__main__":
