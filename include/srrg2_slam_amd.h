@@ -647,6 +647,76 @@ int srrg2_scene_merge_from_aligner(srrg2_scene_h scene, srrg2_scene_h measuremen
                                    srrg2_aligner_h aligner, int slice_idx, srrg2_scene_h clipped,
                                    const srrg2_merger_params* p, srrg2_merge_result* out);
 
+/* ---- measurement adaptors: raw sensor data -> measurement scene, on the device ---------------------------------
+ * The adapt step of MultiTrackerBase_::compute() (S/trackers/multi_tracker_impl.cpp:57-80 ->
+ * S/trackers/tracker_slice_processor_base_impl.cpp:32-49 -> RawDataPreprocessor_::compute(),
+ * S/raw_data_preprocessors/raw_data_preprocessor.h:13-88).  The reference ships the interface only; the two concrete
+ * adaptors here are defined from first principles (DESIGN.md section 4 "Measurement adaptors" is the arithmetic contract):
+ *   depth image -> PointNormal3f cloud   pinhole unprojection, normals from the cross product of two central differences
+ *   laser scan  -> PointNormal2f cloud   polar -> Cartesian, normals from the chord between beams k-w and k+w
+ * Both write straight into a scene (replacing its content like srrg2_scene_set; global indices and descriptors are
+ * dropped), so the frame is adapt -> clip -> align -> merge on device handles. */
+
+/* RawDataPreprocessor_::Status, raw_data_preprocessor.h:22 (values identical) */
+enum srrg2_adaptor_status { SRRG2_ADAPTOR_READY = 0, SRRG2_ADAPTOR_INITIALIZING = 1, SRRG2_ADAPTOR_ERROR = 2 };
+enum srrg2_image_type { SRRG2_IMAGE_NONE = 0, SRRG2_IMAGE_U8 = 1, SRRG2_IMAGE_U16 = 2, SRRG2_IMAGE_F32 = 3 };
+
+typedef struct srrg2_depth_adaptor_params {
+  float camera_matrix[9];            /* row-major K; fx, fy finite and non-zero; K[0][1] != 0 -> SRRG2_E_UNSUPPORTED */
+  int32_t rows, cols;
+  float depth_scale;                 /* metres per count of a U16 image (default 0.001); F32 images are metres */
+  float depth_min, depth_max;        /* accepted z, both inclusive */
+  int32_t normal_col_gap, normal_row_gap; /* pixels; both 0 = no normals (a scene without normals) */
+  float normal_max_distance_squared; /* gate on each of the two difference vectors */
+  int32_t drop_points_without_normal; /* default 1: a depth-valid pixel that gets no normal becomes invalid;
+                                         0: it stays Valid with a NaN normal */
+  int32_t compact;                   /* 0: organised, rows*cols points, invalid = NaN (what the projective finder reads);
+                                        1: only the Valid points, in row-major pixel order (nearest-neighbour finder) */
+} srrg2_depth_adaptor_params;
+
+typedef struct srrg2_scan_adaptor_params {
+  double angle_min, angle_increment; /* bearing of beam k = angle_min + k * angle_increment (radians) */
+  float range_min, range_max;        /* accepted range, both inclusive */
+  int32_t normal_half_window;        /* w: normal from beams k-w and k+w; 0 = no normals */
+  float normal_max_distance_squared; /* gate on the chord p[k+w] - p[k-w] */
+  int32_t drop_points_without_normal;
+  int32_t compact;
+} srrg2_scan_adaptor_params;
+
+typedef struct srrg2_adapt_result {
+  int32_t status;       /* srrg2_adaptor_status */
+  int32_t num_raw;      /* pixels / beams */
+  int32_t num_in_range; /* finite and inside [min, max] */
+  int32_t num_valid;    /* points left Valid in dst */
+  int32_t scene_size;   /* srrg2_scene_size(dst) afterwards */
+} srrg2_adapt_result;
+
+/* defaults: identity-free (camera_matrix / rows / cols / bearings are the caller's); depth_scale 0.001, depth 0.4 .. 8 m,
+ * gaps 1 / 1, normal_max_distance_squared 0.0625, drop 1, organised; scan: range 0.05 .. 30 m, half window 1, 0.01, drop 1,
+ * organised */
+void srrg2_adapt_default_depth_params(srrg2_depth_adaptor_params* p);
+void srrg2_adapt_default_scan_params(srrg2_scan_adaptor_params* p);
+/* dst: a scene of dim 3.  depth / intensity: images with a row stride in bytes (a multiple of the element size, the pointer
+ * aligned to it), both in `mem` = SRRG2_MEM_HOST | SRRG2_MEM_DEVICE.  depth_type: U16 (raw counts, 0 = no reading) or F32
+ * (metres).  intensity_type NONE: dst has no features afterwards; U8 / F32: dst gets the intensity feature (the value as
+ * float, U8 not rescaled), moved with its point in compact mode.
+ *   refused   SRRG2_E_INVALID, dst unchanged: wrong dim, null params, a null image of more than zero pixels, rows or cols
+ *             < 0 or rows*cols beyond int32, a gap < 0 or exactly one of the two gaps 0, depth_type NONE / U8, intensity_type
+ *             U16, a stride smaller than a row or misaligned, fx or fy zero / not finite, bad mem.
+ *   status    an image of zero pixels leaves an empty scene, INITIALIZING; otherwise READY (also when no point is Valid).
+ *   compact   srrg2_scene_global_indices(dst) gives every point's pixel index r*cols + c.
+ *   waits     organised mode with out == NULL queues its work on the scene's stream and returns: the size (rows*cols) is
+ *             known on the host, so srrg2_scene_device_arrays + set_fixed(..., SRRG2_MEM_DEVICE_KEPT) can follow at once
+ *             (a SRRG2_MEM_HOST image in pageable memory is consumed before the call returns, as for any upload).
+ *             With out != NULL, and always in compact mode, the call returns when dst is complete. */
+int srrg2_adapt_depth_image(srrg2_scene_h dst, const void* depth, int depth_type, int depth_row_stride_bytes,
+                            const void* intensity, int intensity_type, int intensity_row_stride_bytes, int mem,
+                            const srrg2_depth_adaptor_params* p, srrg2_adapt_result* out /* may be NULL */);
+/* dst: a scene of dim 2; ranges: num_beams floats (metres), 4-byte aligned.  Refusals, status and waits as above
+ * (num_beams < 0, normal_half_window < 0); compact: global indices = beam indices. */
+int srrg2_adapt_laser_scan(srrg2_scene_h dst, const float* ranges, int num_beams, int mem,
+                           const srrg2_scan_adaptor_params* p, srrg2_adapt_result* out /* may be NULL */);
+
 /* ---- strategy knobs (no reference counterpart) ----------------------------------------------------------------
  * Every setting gives the SAME results (indices, estimates, statistics bit for bit): the knobs choose between exact
  * strategies of the finder / reduction / control step.  A handle starts from srrg2_aligner_default_tuning() overridden

@@ -566,6 +566,86 @@ private:
   Status _status = Error;
 };
 
+// ---- measurement adaptors: RawDataPreprocessor_ (S/raw_data_preprocessors/raw_data_preprocessor.h:13-88) -------------
+//   DepthImageAdaptor   depth image (+ intensity image) -> Scene<3>, organised or compact, with normals
+//   LaserScanAdaptor    ranges -> Scene<2> with normals
+// setRawData / setMeas / compute / status / reset; status() is Error after setRawData until compute() (:67-72).  The raw
+// data is borrowed until compute() has run.  compute(false) asks for no counts: an organised adapt then only queues its work.
+class AdaptorBase_ {
+public:
+  enum Status { Ready = 0, Initializing = 1, Error = 2 };  // raw_data_preprocessor.h:22
+  Status status() const { return _status; }
+  const srrg2_adapt_result& last() const { return _last; }
+
+protected:
+  void finish(int rc, bool want_result) {
+    _status = Error;
+    check(rc);
+    _status = want_result ? static_cast<Status>(_last.status) : Ready;
+  }
+  srrg2_adapt_result _last{};
+  Status _status = Initializing;
+};
+
+class DepthImageAdaptor : public AdaptorBase_ {
+public:
+  using MeasurementType = Scene<3>;
+  srrg2_depth_adaptor_params param;
+  DepthImageAdaptor() { srrg2_adapt_default_depth_params(&param); }
+  // images with a row stride in bytes; intensity may be nullptr with SRRG2_IMAGE_NONE; param.rows / cols say the size
+  void setRawData(const void* depth, int depth_type, int depth_row_stride_bytes, const void* intensity = nullptr,
+                  int intensity_type = SRRG2_IMAGE_NONE, int intensity_row_stride_bytes = 0, int mem = SRRG2_MEM_HOST) {
+    _depth = depth, _depth_type = depth_type, _depth_stride = depth_row_stride_bytes;
+    _inten = intensity, _inten_type = intensity_type, _inten_stride = intensity_row_stride_bytes;
+    _mem = mem, _has_raw = true;
+    _status = Error;
+  }
+  void setMeas(MeasurementType* meas) { _meas = meas; }
+  void reset() {
+    _has_raw = false;
+    _status  = Initializing;
+  }
+  void compute(bool want_result = true) {
+    if (!_meas || !_has_raw) throw std::runtime_error("DepthImageAdaptor::compute|raw data or measurement not set");
+    finish(srrg2_adapt_depth_image(_meas->handle(), _depth, _depth_type, _depth_stride, _inten, _inten_type, _inten_stride, _mem,
+                                   &param, want_result ? &_last : nullptr),
+           want_result);
+  }
+
+private:
+  MeasurementType* _meas = nullptr;
+  const void* _depth = nullptr;
+  const void* _inten = nullptr;
+  int _depth_type = SRRG2_IMAGE_NONE, _depth_stride = 0, _inten_type = SRRG2_IMAGE_NONE, _inten_stride = 0, _mem = SRRG2_MEM_HOST;
+  bool _has_raw = false;
+};
+
+class LaserScanAdaptor : public AdaptorBase_ {
+public:
+  using MeasurementType = Scene<2>;
+  srrg2_scan_adaptor_params param;
+  LaserScanAdaptor() { srrg2_adapt_default_scan_params(&param); }
+  void setRawData(const float* ranges, int num_beams, int mem = SRRG2_MEM_HOST) {
+    _ranges = ranges, _num_beams = num_beams, _mem = mem, _has_raw = true;
+    _status = Error;
+  }
+  void setMeas(MeasurementType* meas) { _meas = meas; }
+  void reset() {
+    _has_raw = false;
+    _status  = Initializing;
+  }
+  void compute(bool want_result = true) {
+    if (!_meas || !_has_raw) throw std::runtime_error("LaserScanAdaptor::compute|raw data or measurement not set");
+    finish(srrg2_adapt_laser_scan(_meas->handle(), _ranges, _num_beams, _mem, &param, want_result ? &_last : nullptr), want_result);
+  }
+
+private:
+  MeasurementType* _meas = nullptr;
+  const float* _ranges   = nullptr;
+  int _num_beams = 0, _mem = SRRG2_MEM_HOST;
+  bool _has_raw = false;
+};
+
 // ---- binary descriptor database: the matching half of MultiLoopDetectorHBST_ --------------------------------------
 // (S/registration/loop_detector/multi_loop_detector_hbst_impl.cpp:41-197; it stands where the reference keeps its
 // srrg_hbst::BinaryTree256<uint64_t>).  Exact, exhaustive matching on the device; semantics: srrg2_slam_amd.h.

@@ -34,3 +34,17 @@ def DescriptorDatabase(device=0):
     from .descriptors import DescriptorDatabase as _DD
 
     return _DD(device=device)
+
+
+def MeasurementAdaptorDepthImage(params=None):
+    """Depth image -> measurement scene on the device (the adapt step of a tracker's frame); see ``adaptors``."""
+    from .adaptors import MeasurementAdaptorDepthImage as _A
+
+    return _A(params)
+
+
+def MeasurementAdaptorLaserScan(params=None):
+    """Laser scan -> measurement scene on the device; see ``adaptors``."""
+    from .adaptors import MeasurementAdaptorLaserScan as _A
+
+    return _A(params)

@@ -138,6 +138,51 @@ class AlignerTuning(C.Structure):
     ]
 
 
+# enum srrg2_adaptor_status (RawDataPreprocessor_::Status, raw_data_preprocessor.h:22), enum srrg2_image_type
+ADAPTOR_READY, ADAPTOR_INITIALIZING, ADAPTOR_ERROR = 0, 1, 2
+IMAGE_NONE, IMAGE_U8, IMAGE_U16, IMAGE_F32 = 0, 1, 2, 3
+
+
+class DepthAdaptorParams(C.Structure):
+    """srrg2_depth_adaptor_params"""
+    _fields_ = [
+        ("camera_matrix", C.c_float * 9),
+        ("rows", C.c_int32),
+        ("cols", C.c_int32),
+        ("depth_scale", C.c_float),
+        ("depth_min", C.c_float),
+        ("depth_max", C.c_float),
+        ("normal_col_gap", C.c_int32),
+        ("normal_row_gap", C.c_int32),
+        ("normal_max_distance_squared", C.c_float),
+        ("drop_points_without_normal", C.c_int32),
+        ("compact", C.c_int32),
+    ]
+
+
+class ScanAdaptorParams(C.Structure):
+    """srrg2_scan_adaptor_params"""
+    _fields_ = [
+        ("angle_min", C.c_double),
+        ("angle_increment", C.c_double),
+        ("range_min", C.c_float),
+        ("range_max", C.c_float),
+        ("normal_half_window", C.c_int32),
+        ("normal_max_distance_squared", C.c_float),
+        ("drop_points_without_normal", C.c_int32),
+        ("compact", C.c_int32),
+    ]
+
+
+class AdaptResult(C.Structure):
+    """srrg2_adapt_result"""
+    _fields_ = [("status", C.c_int32), ("num_raw", C.c_int32), ("num_in_range", C.c_int32), ("num_valid", C.c_int32),
+                ("scene_size", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 def transform_size(variable_kind):
     return 9 if variable_kind == SE2_RIGHT else 12
 

@@ -45,6 +45,17 @@ def lib():
         _LIB.srrg2_descriptor_db_add_scene.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         _LIB.srrg2_descriptor_db_match_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_uint32, C.c_int64,
                                                          C.POINTER(C.c_int)]
+        # srrg2_adapt_* (adaptors.MeasurementAdaptorDepthImage / MeasurementAdaptorLaserScan)
+        from . import _abi as abi
+
+        _LIB.srrg2_adapt_default_depth_params.argtypes = [C.POINTER(abi.DepthAdaptorParams)]
+        _LIB.srrg2_adapt_default_depth_params.restype = None
+        _LIB.srrg2_adapt_default_scan_params.argtypes = [C.POINTER(abi.ScanAdaptorParams)]
+        _LIB.srrg2_adapt_default_scan_params.restype = None
+        _LIB.srrg2_adapt_depth_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                 C.POINTER(abi.DepthAdaptorParams), C.POINTER(abi.AdaptResult)]
+        _LIB.srrg2_adapt_laser_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(abi.ScanAdaptorParams),
+                                                C.POINTER(abi.AdaptResult)]
     return _LIB
 
 

@@ -1,0 +1,423 @@
+// adaptor.hip -- measurement adaptors: raw sensor data -> measurement scene, on the device (srrg2_adapt_*).
+// Replaces, behind the C ABI of include/srrg2_slam_amd.h, the adapt step of a tracker's frame:
+//   MultiTrackerBase_::compute() -> proc->adapt()     S/trackers/multi_tracker_impl.cpp:57-80
+//   TrackerSliceProcessorBase_::adapt()               S/trackers/tracker_slice_processor_base_impl.cpp:32-49
+//   RawDataPreprocessor_::compute() (interface)       S/raw_data_preprocessors/raw_data_preprocessor.h:13-88
+// The reference ships the interface only; the two adaptors here (depth image -> organised PointNormal3f cloud, laser scan ->
+// PointNormal2f cloud) are defined from first principles: DESIGN.md section 4 "Measurement adaptors" is the arithmetic
+// contract, tests/adaptor_restatement.py restates it in numpy and the library must give the same bits.
+// Kernels: one thread per pixel / beam, grid-stride.  A thread reads its own raw value and its four (two) neighbours' and
+// RECOMPUTES the neighbours' points from them -- the same expression gives the same bits as the neighbour's own thread, so
+// there is no second pass and no dependency between threads -- and writes point and normal as 16-byte records, coalesced.
+// Organised output is one kernel; compact output is flag -> exclusive scan -> scatter like the ball clipper, the points
+// recomputed in the scatter rather than staged.  The counters of srrg2_adapt_result are summed per workgroup and added with
+// ONE 64-bit atomic per workgroup (both counts in one word), and read back only when the caller asks for them.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+
+#include "det_math.h"
+#include "host_util.h"
+#include "kernels.h"
+#include "scene_state.h"
+
+using srrg2amd::fail;
+
+namespace {
+
+enum { PX_IN_RANGE = 1, PX_VALID = 2 };
+
+__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
+
+__device__ __forceinline__ float sq3(float x, float y, float z) { return (x * x + y * y) + z * z; }
+
+// ---- depth image -----------------------------------------------------------------------------------------------------
+struct DepthArgs {
+  const unsigned char* depth;
+  const unsigned char* inten;  // null: no intensity
+  long long depth_stride, inten_stride;  // bytes per row
+  int inten_f32;                         // intensity is F32 (else U8)
+  int rows, cols;
+  int gc, gr;  // gaps; gc == 0: no normals
+  float ifx, ify, cx, cy, scale, zmin, zmax, maxd2;
+  int drop;
+};
+
+template <typename D>
+struct DepthSource {
+  DepthArgs a;
+
+  __device__ __forceinline__ bool depth_at(int r, int c, float& z) const {
+    const D raw = *reinterpret_cast<const D*>(a.depth + (long long) r * a.depth_stride + (long long) c * (long long) sizeof(D));
+    if (sizeof(D) == 2) {
+      if (raw == (D) 0) return false;
+      z = (float) raw * a.scale;
+    } else {
+      z = (float) raw;
+    }
+    return isfinite(z) && a.zmin <= z && z <= a.zmax;
+  }
+  __device__ __forceinline__ float3 point_at(int r, int c, float z) const {
+    return make_float3((((float) c - a.cx) * a.ifx) * z, (((float) r - a.cy) * a.ify) * z, z);
+  }
+  // point and normal of pixel i as they are stored; returns PX_* bits
+  __device__ __forceinline__ int eval(int i, float4& p, float4& n) const {
+    const int r = i / a.cols, c = i - r * a.cols;
+    const float qn = quiet_nan();
+    p = make_float4(qn, qn, qn, 0.f);
+    n = a.gc > 0 ? make_float4(qn, qn, qn, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    float z;
+    if (!depth_at(r, c, z)) return 0;
+    const float3 q = point_at(r, c, z);
+    bool has_normal = false;
+    if (a.gc > 0 && c >= a.gc && c < a.cols - a.gc && r >= a.gr && r < a.rows - a.gr) {
+      float zl, zr, zu, zd;
+      const bool okl = depth_at(r, c - a.gc, zl), okr = depth_at(r, c + a.gc, zr);
+      const bool oku = depth_at(r - a.gr, c, zu), okd = depth_at(r + a.gr, c, zd);
+      if (okl && okr && oku && okd) {
+        const float3 pr = point_at(r, c + a.gc, zr), pl = point_at(r, c - a.gc, zl);
+        const float3 pd = point_at(r + a.gr, c, zd), pu = point_at(r - a.gr, c, zu);
+        const float dcx = pr.x - pl.x, dcy = pr.y - pl.y, dcz = pr.z - pl.z;
+        const float drx = pd.x - pu.x, dry = pd.y - pu.y, drz = pd.z - pu.z;
+        if (!(sq3(dcx, dcy, dcz) > a.maxd2) && !(sq3(drx, dry, drz) > a.maxd2)) {
+          float nx = dcy * drz - dcz * dry;
+          float ny = dcz * drx - dcx * drz;
+          float nz = dcx * dry - dcy * drx;
+          const float len = sqrtf(sq3(nx, ny, nz));
+          if (len > 0.f) {
+            nx = nx / len;
+            ny = ny / len;
+            nz = nz / len;
+            if ((nx * q.x + ny * q.y) + nz * q.z > 0.f) {  // normals face the sensor
+              nx = -nx;
+              ny = -ny;
+              nz = -nz;
+            }
+            n          = make_float4(nx, ny, nz, 0.f);
+            has_normal = true;
+          }
+        }
+      }
+    }
+    const bool valid = a.gc == 0 || has_normal || !a.drop;
+    if (valid) p = make_float4(q.x, q.y, q.z, 0.f);
+    return PX_IN_RANGE | (valid ? PX_VALID : 0);
+  }
+  __device__ __forceinline__ float intensity(int i) const {
+    const int r = i / a.cols, c = i - r * a.cols;
+    const unsigned char* row = a.inten + (long long) r * a.inten_stride;
+    return a.inten_f32 ? reinterpret_cast<const float*>(row)[c] : (float) row[c];
+  }
+};
+
+// ---- laser scan ------------------------------------------------------------------------------------------------------
+struct ScanSource {
+  const float* ranges;
+  int n, w;  // w == 0: no normals
+  double amin, ainc;
+  float rmin, rmax, maxd2;
+  int drop;
+
+  __device__ __forceinline__ bool range_at(int k, float& r) const {
+    r = ranges[k];
+    return isfinite(r) && rmin <= r && r <= rmax;
+  }
+  __device__ __forceinline__ float2 point_at(int k, float r) const {
+    double s, c;
+    dm::sincos(amin + (double) k * ainc, s, c);
+    const float cf = (float) c, sf = (float) s;
+    return make_float2(cf * r, sf * r);
+  }
+  __device__ __forceinline__ int eval(int k, float4& p, float4& nrm) const {
+    const float qn = quiet_nan();
+    p   = make_float4(qn, qn, 0.f, 0.f);
+    nrm = w > 0 ? make_float4(qn, qn, 0.f, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    float r;
+    if (!range_at(k, r)) return 0;
+    const float2 q  = point_at(k, r);
+    bool has_normal = false;
+    if (w > 0 && k >= w && k < n - w) {
+      float ra, rb;
+      const bool oka = range_at(k - w, ra), okb = range_at(k + w, rb);
+      if (oka && okb) {
+        const float2 pa = point_at(k - w, ra), pb = point_at(k + w, rb);
+        const float tx = pb.x - pa.x, ty = pb.y - pa.y;
+        const float t2 = tx * tx + ty * ty;
+        if (t2 <= maxd2) {
+          const float len = sqrtf(t2);
+          if (len > 0.f) {
+            float nx = ty / len, ny = -tx / len;
+            if (nx * q.x + ny * q.y > 0.f) {
+              nx = -nx;
+              ny = -ny;
+            }
+            nrm        = make_float4(nx, ny, 0.f, 0.f);
+            has_normal = true;
+          }
+        }
+      }
+    }
+    const bool valid = w == 0 || has_normal || !drop;
+    if (valid) p = make_float4(q.x, q.y, 0.f, 0.f);
+    return PX_IN_RANGE | (valid ? PX_VALID : 0);
+  }
+  __device__ __forceinline__ float intensity(int) const { return 0.f; }
+};
+
+// ---- kernels ---------------------------------------------------------------------------------------------------------
+// both counts of a workgroup in one word (low: in range, high: Valid), ONE atomic per workgroup (blockDim = 256): same-address
+// atomics serialise
+__device__ __forceinline__ void block_add_counts(int flags_seen_in_range, int flags_seen_valid, unsigned long long* target) {
+  __shared__ unsigned long long red[4];
+  unsigned long long v = (unsigned long long) (unsigned) flags_seen_in_range | ((unsigned long long) (unsigned) flags_seen_valid << 32);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long t = (red[0] + red[1]) + (red[2] + red[3]);
+    if (t) atomicAdd(target, t);
+  }
+}
+
+template <typename S>
+__global__ __launch_bounds__(256) void k_adapt_organised(S src, int n, float4* __restrict__ pts, float4* __restrict__ nrm,
+                                                         float* __restrict__ inten, unsigned long long* __restrict__ counters) {
+  int in_range = 0, valid = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    float4 p, q;
+    const int f = src.eval(i, p, q);
+    pts[i] = p;
+    nrm[i] = q;
+    if (inten) inten[i] = src.intensity(i);
+    in_range += f & 1;
+    valid += f >> 1;
+  }
+  block_add_counts(in_range, valid, counters);
+}
+
+template <typename S>
+__global__ __launch_bounds__(256) void k_adapt_flag(S src, int n, int* __restrict__ flags, unsigned long long* __restrict__ counters) {
+  int in_range = 0, valid = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    float4 p, q;
+    const int f = src.eval(i, p, q);
+    flags[i]    = f >> 1;
+    in_range += f & 1;
+    valid += f >> 1;
+  }
+  block_add_counts(in_range, valid, counters);
+}
+
+template <typename S>
+__global__ __launch_bounds__(256) void k_adapt_scatter(S src, int n, const int* __restrict__ offset, int total,
+                                                       float4* __restrict__ pts, float4* __restrict__ nrm,
+                                                       float* __restrict__ inten, int* __restrict__ gidx) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    float4 p, q;
+    if (!(src.eval(i, p, q) & PX_VALID)) continue;
+    const int k = offset[i];
+    if (k < 0 || k >= total) continue;  // (cannot happen: flags and scatter evaluate the same expression)
+    pts[k]  = p;
+    nrm[k]  = q;
+    gidx[k] = i;
+    if (inten) inten[k] = src.intensity(i);
+  }
+}
+
+// few, fat workgroups: the work per pixel is a handful of flops and the counters cost one atomic per workgroup
+int adapt_blocks(int n) {
+  int b = (n + 255) / 256;
+  return b < 1 ? 1 : (b > 512 ? 512 : b);
+}
+
+// raw data in pageable or pinned host memory -> the scene's staging buffer at `offset`, on the scene's stream
+int stage(srrg2_scene* s, const void* host, size_t bytes, size_t offset, const unsigned char** dev) {
+  HIP_TRY(hipMemcpyAsync(s->staging.p + offset, host, bytes, hipMemcpyHostToDevice, s->stream));
+  *dev = reinterpret_cast<const unsigned char*>(s->staging.p + offset);
+  return 0;
+}
+
+// the part both adaptors share.  The source's device pointers are valid on the scene's stream; nothing of `s` has changed yet.
+template <typename S>
+int run_adapt(srrg2_scene* s, const S& src, int n, bool normals, bool intensity, bool compact, srrg2_adapt_result* out) {
+  int rc;
+  s->has_desc  = false;  // the content is replaced: features of the old points go with them
+  s->has_inten = intensity;
+  if (out) {
+    std::memset(out, 0, sizeof(*out));
+    out->status  = n == 0 ? SRRG2_ADAPTOR_INITIALIZING : SRRG2_ADAPTOR_READY;
+    out->num_raw = n;
+  }
+  if (n == 0) {
+    if ((rc = srrg2amd::scene_make_room(s, 1, 0))) return rc;
+    s->n = s->ng = 0;
+    s->has_normals = normals;
+    return 0;
+  }
+  hipStream_t st = s->stream;
+  unsigned long long* counters = reinterpret_cast<unsigned long long*>(s->dscalars.p + 8);
+  HIP_TRY(hipMemsetAsync(counters, 0, sizeof(unsigned long long), st));
+  const dim3 grid(adapt_blocks(n)), block(256);
+  if (!compact) {
+    if ((rc = srrg2amd::scene_make_room(s, n, 0))) return rc;
+    s->n           = n;
+    s->ng          = 0;
+    s->has_normals = normals;
+    hipLaunchKernelGGL(k_adapt_organised<S>, grid, block, 0, st, src, n, s->pts.p, s->nrm.p, intensity ? s->inten.p : nullptr,
+                       counters);
+    HIP_TRY(hipGetLastError());
+    s->pending = true;
+    if (!out) return 0;  // (queued: whoever reads the scene next from another stream or from the host settles it)
+  } else {
+    if ((rc = s->flags.reserve((size_t) n + 1))) return rc;
+    hipLaunchKernelGGL(k_adapt_flag<S>, grid, block, 0, st, src, n, s->flags.p, counters);
+    int total = 0;
+    if ((rc = srrg2amd::scene_scan_flags(s, n, &total))) return rc;
+    if (total < 0 || total > n) return fail(SRRG2_E_HIP, "adapt: the compaction scan returned a total out of range");
+    if ((rc = srrg2amd::scene_make_room(s, total > 0 ? total : 1, 0))) return rc;
+    if ((rc = s->gidx.reserve((size_t) (total > 0 ? total : 1)))) return rc;
+    s->n = s->ng = total;
+    s->has_normals = normals;
+    if (total > 0)
+      hipLaunchKernelGGL(k_adapt_scatter<S>, grid, block, 0, st, src, n, s->flags.p, total, s->pts.p, s->nrm.p,
+                         intensity ? s->inten.p : nullptr, s->gidx.p);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipMemcpyAsync(&s->scalars[8], counters, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  s->pending = false;
+  if (out) {
+    out->num_in_range = s->scalars[8];
+    out->num_valid    = s->scalars[9];
+    out->scene_size   = s->n;
+  }
+  return 0;
+}
+
+bool aligned_to(const void* p, long long stride, int elem) {
+  return reinterpret_cast<uintptr_t>(p) % (uintptr_t) elem == 0 && stride % elem == 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+void srrg2_adapt_default_depth_params(srrg2_depth_adaptor_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->camera_matrix[0] = p->camera_matrix[4] = p->camera_matrix[8] = 1.f;
+  p->depth_scale                 = 0.001f;
+  p->depth_min                   = 0.4f;
+  p->depth_max                   = 8.f;
+  p->normal_col_gap              = 1;
+  p->normal_row_gap              = 1;
+  p->normal_max_distance_squared = 0.0625f;
+  p->drop_points_without_normal  = 1;
+  p->compact                     = 0;
+}
+
+void srrg2_adapt_default_scan_params(srrg2_scan_adaptor_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->range_min                   = 0.05f;
+  p->range_max                   = 30.f;
+  p->normal_half_window          = 1;
+  p->normal_max_distance_squared = 0.01f;
+  p->drop_points_without_normal  = 1;
+  p->compact                     = 0;
+}
+
+int srrg2_adapt_depth_image(srrg2_scene_h dst, const void* depth, int depth_type, int depth_stride, const void* intensity,
+                            int intensity_type, int intensity_stride, int mem, const srrg2_depth_adaptor_params* p,
+                            srrg2_adapt_result* out) {
+  if (!dst || !p) return fail(SRRG2_E_INVALID, "adapt_depth_image: null scene or params");
+  if (dst->dim != 3) return fail(SRRG2_E_INVALID, "adapt_depth_image: the scene must have dim 3");
+  if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, "adapt_depth_image: bad mem");
+  if (depth_type != SRRG2_IMAGE_U16 && depth_type != SRRG2_IMAGE_F32)
+    return fail(SRRG2_E_INVALID, "adapt_depth_image: depth_type must be SRRG2_IMAGE_U16 or SRRG2_IMAGE_F32");
+  if (intensity_type != SRRG2_IMAGE_NONE && intensity_type != SRRG2_IMAGE_U8 && intensity_type != SRRG2_IMAGE_F32)
+    return fail(SRRG2_E_INVALID, "adapt_depth_image: intensity_type must be NONE, U8 or F32");
+  if (p->rows < 0 || p->cols < 0 || (long long) p->rows * (long long) p->cols > 0x7fffffffLL)
+    return fail(SRRG2_E_INVALID, "adapt_depth_image: rows, cols >= 0 and rows*cols within int32");
+  if (p->normal_col_gap < 0 || p->normal_row_gap < 0 || (p->normal_col_gap == 0) != (p->normal_row_gap == 0))
+    return fail(SRRG2_E_INVALID, "adapt_depth_image: normal gaps >= 0, and both or neither 0");
+  const float fx = p->camera_matrix[0], fy = p->camera_matrix[4];
+  if (!std::isfinite(fx) || !std::isfinite(fy) || fx == 0.f || fy == 0.f)
+    return fail(SRRG2_E_INVALID, "adapt_depth_image: fx and fy must be finite and non-zero");
+  if (p->camera_matrix[1] != 0.f) return fail(SRRG2_E_UNSUPPORTED, "adapt_depth_image: a camera matrix with skew (K[0][1] != 0)");
+  const int n  = p->rows * p->cols;
+  const int de = depth_type == SRRG2_IMAGE_U16 ? 2 : 4, ie = intensity_type == SRRG2_IMAGE_F32 ? 4 : 1;
+  const bool with_inten = intensity_type != SRRG2_IMAGE_NONE;
+  if (n > 0) {
+    if (!depth || (with_inten && !intensity)) return fail(SRRG2_E_INVALID, "adapt_depth_image: null image");
+    if ((long long) depth_stride < (long long) p->cols * de || !aligned_to(depth, depth_stride, de))
+      return fail(SRRG2_E_INVALID, "adapt_depth_image: depth row stride smaller than a row, or image not aligned to its element");
+    if (with_inten && ((long long) intensity_stride < (long long) p->cols * ie || !aligned_to(intensity, intensity_stride, ie)))
+      return fail(SRRG2_E_INVALID, "adapt_depth_image: intensity row stride smaller than a row, or image not aligned to its element");
+  }
+  int rc;
+  HIP_TRY(hipSetDevice(dst->device));
+  DepthArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.depth        = static_cast<const unsigned char*>(depth);
+  a.inten        = with_inten ? static_cast<const unsigned char*>(intensity) : nullptr;
+  a.depth_stride = depth_stride;
+  a.inten_stride = intensity_stride;
+  a.inten_f32    = intensity_type == SRRG2_IMAGE_F32;
+  a.rows = p->rows, a.cols = p->cols;
+  a.gc = p->normal_col_gap, a.gr = p->normal_row_gap;
+  a.ifx = 1.0f / fx, a.ify = 1.0f / fy;
+  a.cx = p->camera_matrix[2], a.cy = p->camera_matrix[5];
+  a.scale = p->depth_scale, a.zmin = p->depth_min, a.zmax = p->depth_max;
+  a.maxd2 = p->normal_max_distance_squared;
+  a.drop  = p->drop_points_without_normal != 0;
+  if (n > 0 && mem == SRRG2_MEM_HOST) {  // rows up to the last pixel of the last row, as they lie
+    const size_t bd    = (size_t) (p->rows - 1) * (size_t) depth_stride + (size_t) p->cols * de;
+    const size_t bi    = with_inten ? (size_t) (p->rows - 1) * (size_t) intensity_stride + (size_t) p->cols * ie : 0;
+    const size_t off_i = (bd + 63) / 64 * 64;
+    if ((rc = dst->staging.reserve(off_i + bi + 64))) return rc;
+    if ((rc = stage(dst, depth, bd, 0, &a.depth))) return rc;
+    if (with_inten && (rc = stage(dst, intensity, bi, off_i, &a.inten))) return rc;
+  }
+  const bool normals = a.gc > 0;
+  if (depth_type == SRRG2_IMAGE_U16) return run_adapt(dst, DepthSource<uint16_t>{a}, n, normals, with_inten, p->compact != 0, out);
+  return run_adapt(dst, DepthSource<float>{a}, n, normals, with_inten, p->compact != 0, out);
+}
+
+int srrg2_adapt_laser_scan(srrg2_scene_h dst, const float* ranges, int num_beams, int mem, const srrg2_scan_adaptor_params* p,
+                           srrg2_adapt_result* out) {
+  if (!dst || !p) return fail(SRRG2_E_INVALID, "adapt_laser_scan: null scene or params");
+  if (dst->dim != 2) return fail(SRRG2_E_INVALID, "adapt_laser_scan: the scene must have dim 2");
+  if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, "adapt_laser_scan: bad mem");
+  if (num_beams < 0 || p->normal_half_window < 0) return fail(SRRG2_E_INVALID, "adapt_laser_scan: num_beams, normal_half_window >= 0");
+  if (num_beams > 0 && (!ranges || reinterpret_cast<uintptr_t>(ranges) % 4 != 0))
+    return fail(SRRG2_E_INVALID, "adapt_laser_scan: null or misaligned ranges");
+  // (the bearings go through a fixed argument reduction: keep them where it is exact enough and its integer part fits)
+  if (!std::isfinite(p->angle_min) || !std::isfinite(p->angle_increment) ||
+      std::fabs(p->angle_min) + (double) num_beams * std::fabs(p->angle_increment) > 1.0e6)
+    return fail(SRRG2_E_INVALID, "adapt_laser_scan: bearings must be finite and within 1e6 rad");
+  int rc;
+  HIP_TRY(hipSetDevice(dst->device));
+  ScanSource src;
+  std::memset(&src, 0, sizeof(src));
+  src.ranges = ranges;
+  src.n      = num_beams;
+  src.w      = p->normal_half_window;
+  src.amin = p->angle_min, src.ainc = p->angle_increment;
+  src.rmin = p->range_min, src.rmax = p->range_max;
+  src.maxd2 = p->normal_max_distance_squared;
+  src.drop  = p->drop_points_without_normal != 0;
+  if (num_beams > 0 && mem == SRRG2_MEM_HOST) {
+    const unsigned char* d = nullptr;
+    if ((rc = dst->staging.reserve((size_t) num_beams * 4 + 64))) return rc;
+    if ((rc = stage(dst, ranges, (size_t) num_beams * 4, 0, &d))) return rc;
+    src.ranges = reinterpret_cast<const float*>(d);
+  }
+  return run_adapt(dst, src, num_beams, src.w > 0, false, p->compact != 0, out);
+}
+
+}  // extern "C"

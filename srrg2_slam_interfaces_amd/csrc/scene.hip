@@ -30,33 +30,10 @@
 #include "device_types.h"
 #include "host_util.h"
 #include "kernels.h"
+#include "scene_state.h"
 
 using srrg2amd::DevBuf;
 using srrg2amd::fail;
-
-struct srrg2_scene {
-  int dim = 3, device = 0;
-  hipStream_t stream = nullptr;
-  DevBuf<float4> pts, nrm;
-  int n            = 0;
-  bool has_normals = false;
-  // per-point features (absent unless set_features / a merge or clip brought them): 2 uint4 per point, 1 float per point;
-  // when present their capacity follows pts.cap
-  DevBuf<uint4> desc;
-  DevBuf<float> inten;
-  bool has_desc = false, has_inten = false;
-  DevBuf<int> gidx;  // local -> global indices of the last clip into this scene
-  int ng = 0;
-  // scratch
-  DevBuf<int> flags, scan_sums, counts, dup_list;
-  DevBuf<unsigned char> merged;
-  DevBuf<srrg2_correspondence> corr;
-  DevBuf<unsigned long long> dup_keys;  // (scene index << 32 | correspondence index) of the duplicates: unsorted, sorted
-  DevBuf<char> sort_tmp;
-  DevBuf<char> staging;
-  int* scalars = nullptr;  // pinned host mirror of dscalars
-  DevBuf<int> dscalars;    // device: [0] scan total, [1] num_merged, [2] error flag, [3] duplicates seen, [4] ncorr
-};
 
 namespace {
 
@@ -331,8 +308,14 @@ int blocks_for(int n) {
   return b < 1 ? 1 : (b > 2048 ? 2048 : b);
 }
 
+// the device of the scene made current, and whatever an adaptor left queued on its stream finished: every entry point that reads
+// or rewrites a scene starts here (several of them read it on another scene's stream or through the null stream)
 int scene_device(srrg2_scene* s) {
   HIP_TRY(hipSetDevice(s->device));
+  if (s->pending) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->pending = false;
+  }
   return 0;
 }
 
@@ -593,6 +576,8 @@ int srrg2_scene_get(srrg2_scene_h s, float* coords_out, float* normals_out, int 
 
 int srrg2_scene_device_arrays(srrg2_scene_h s, const float** coords, const float** normals, int* n) {
   if (!s || !coords || !n) return fail(SRRG2_E_INVALID, "scene_device_arrays: bad arguments");
+  int rc;
+  if ((rc = scene_device(s))) return rc;  // (the arrays go to another stream: an adaptor's queued work has to be done)
   *coords = (const float*) s->pts.p;
   if (normals) *normals = s->has_normals ? (const float*) s->nrm.p : nullptr;
   *n = s->n;
@@ -660,6 +645,8 @@ int srrg2_scene_get_features(srrg2_scene_h s, uint8_t* descriptors_out, float* i
 
 int srrg2_scene_device_features(srrg2_scene_h s, const uint8_t** descriptors, const float** intensity, int* n) {
   if (!s || !n) return fail(SRRG2_E_INVALID, "scene_device_features: bad arguments");
+  int rc;
+  if ((rc = scene_device(s))) return rc;
   if (descriptors) *descriptors = s->has_desc ? (const uint8_t*) s->desc.p : nullptr;
   if (intensity) *intensity = s->has_inten ? s->inten.p : nullptr;
   *n = s->n;
@@ -672,7 +659,7 @@ int srrg2_scene_clip_ball(srrg2_scene_h full, const float* robot_in_local_map, f
       full->device != clipped->device)
     return fail(SRRG2_E_INVALID, "scene_clip_ball: bad arguments");
   int rc;
-  if ((rc = scene_device(full))) return rc;
+  if ((rc = scene_device(clipped)) || (rc = scene_device(full))) return rc;
   float Linv[12];
   if (full->dim == 3)
     dm::se3_inverse(robot_in_local_map, Linv);  // scene_clipper.h:64-68
@@ -748,7 +735,7 @@ int srrg2_scene_merge(srrg2_scene_h scene, srrg2_scene_h meas, const float* meas
   if (ncorr > 0 && !correspondences) return fail(SRRG2_E_INVALID, "scene_merge: null correspondences");
   int rc;
   if ((rc = check_params(p))) return rc;
-  if ((rc = scene_device(scene))) return rc;
+  if ((rc = scene_device(meas)) || (rc = scene_device(scene))) return rc;
   if ((rc = bind_features(scene, meas, "scene_merge"))) return rc;
   std::memset(out, 0, sizeof(*out));
   out->status  = SRRG2_MERGER_INITIALIZING;  // :15
@@ -813,7 +800,7 @@ int srrg2_scene_merge_from_aligner(srrg2_scene_h scene, srrg2_scene_h meas, cons
     return fail(SRRG2_E_INVALID, "scene_merge_from_aligner: bad arguments");
   int rc;
   if ((rc = check_params(p))) return rc;
-  if ((rc = scene_device(scene))) return rc;
+  if ((rc = scene_device(meas)) || (rc = scene_device(clipped)) || (rc = scene_device(scene))) return rc;
   srrg2amd::AlignerSliceView v;
   if ((rc = srrg2amd::aligner_slice_view(aligner, slice_idx, &v))) return rc;
   if (v.device != scene->device) return fail(SRRG2_E_INVALID, "scene_merge_from_aligner: aligner lives on another device");
@@ -850,9 +837,15 @@ int srrg2_scene_merge_from_aligner(srrg2_scene_h scene, srrg2_scene_h meas, cons
 
 }  // extern "C"
 
+int srrg2amd::scene_make_room(srrg2_scene* s, int n, int keep) { return scene_reserve(s, n, keep); }
+
+int srrg2amd::scene_scan_flags(srrg2_scene* s, int n, int* total) { return scan_flags(s, n, total); }
+
 // what descriptors.hip sees of a scene (srrg2_descriptor_db_add_scene / _match_scene)
 int srrg2amd::scene_feature_view(srrg2_scene* s, srrg2amd::SceneFeatureView* v) {
   if (!s || !v) return fail(SRRG2_E_INVALID, "scene_feature_view: bad arguments");
+  int rc;
+  if ((rc = scene_device(s))) return rc;
   v->pts    = s->pts.p;
   v->desc   = s->has_desc ? s->desc.p : nullptr;
   v->n      = s->n;

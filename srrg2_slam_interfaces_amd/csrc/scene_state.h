@@ -1,0 +1,41 @@
+// scene_state.h -- what a scene handle holds (srrg2_scene_h), shared by the sources that write scenes: scene.hip (set, clip,
+// merge) and adaptor.hip (measurement adaptors).  Internal to the library.
+#pragma once
+#include "host_util.h"
+
+struct srrg2_scene {
+  int dim = 3, device = 0;
+  hipStream_t stream = nullptr;
+  srrg2amd::DevBuf<float4> pts, nrm;
+  int n            = 0;
+  bool has_normals = false;
+  // per-point features (absent unless set_features / a merge or clip brought them): 2 uint4 per point, 1 float per point;
+  // when present their capacity follows pts.cap
+  srrg2amd::DevBuf<uint4> desc;
+  srrg2amd::DevBuf<float> inten;
+  bool has_desc = false, has_inten = false;
+  srrg2amd::DevBuf<int> gidx;  // local -> global indices of the last clip into this scene
+  int ng = 0;
+  // an adaptor has queued work that writes this scene and returned without waiting (srrg2_adapt_*, organised mode without a
+  // result): scene.hip's entry points wait for it before the host, or a stream other than `stream`, reads or rewrites it
+  bool pending = false;
+  // scratch
+  srrg2amd::DevBuf<int> flags, scan_sums, counts, dup_list;
+  srrg2amd::DevBuf<unsigned char> merged;
+  srrg2amd::DevBuf<srrg2_correspondence> corr;
+  srrg2amd::DevBuf<unsigned long long> dup_keys;  // (scene index << 32 | correspondence index) of the duplicates: unsorted, sorted
+  srrg2amd::DevBuf<char> sort_tmp;
+  srrg2amd::DevBuf<char> staging;
+  int* scalars = nullptr;  // pinned host mirror of dscalars
+  // device: [0] scan total, [1] num_merged, [2] error flag, [3] duplicates seen, [4] ncorr (merge); [8] in range, [9] Valid (adapt)
+  srrg2amd::DevBuf<int> dscalars;
+};
+
+namespace srrg2amd {
+
+// grow the point arrays (and the feature arrays that are present) to hold n points, keeping the first `keep` (scene.hip)
+int scene_make_room(srrg2_scene* s, int n, int keep);
+// s->flags[0..n) -> exclusive scan in place; the total comes back on the host (one wait on the scene's stream)
+int scene_scan_flags(srrg2_scene* s, int n, int* total);
+
+}  // namespace srrg2amd
