@@ -598,7 +598,8 @@ int srrg2_scene_device_arrays(srrg2_scene_h h, const float** coords, const float
  *                  intensity >= 4 and a multiple of 4 (else SRRG2_E_INVALID).  mem: SRRG2_MEM_HOST | SRRG2_MEM_DEVICE.
  *   srrg2_scene_set replaces the content and so drops the features.  A scene that never got features behaves as before.
  *   validity       unchanged: a point is Valid iff its coordinates are finite; an invalid point keeps its features and index.
- *   clip_ball      `clipped` receives the features of the points it keeps (clipped[k] = full[global_indices[k]]) and
+ *   clip_ball / clip_projective
+ *                  `clipped` receives the features of the points it keeps (clipped[k] = full[global_indices[k]]) and
  *                  the feature presence of `full`.
  *   merge / merge_from_aligner
  *                  a merged scene point takes the measurement point's descriptor and intensity (point_scene = point_meas,
@@ -628,6 +629,40 @@ int srrg2_scene_device_features(srrg2_scene_h h, const uint8_t** descriptors, co
 int srrg2_scene_clip_ball(srrg2_scene_h full, const float* robot_in_local_map, float range, srrg2_scene_h clipped,
                           int* status);
 int srrg2_scene_global_indices(srrg2_scene_h clipped, int32_t* buf, int* n_inout);
+
+/* SceneClipper_::compute() with the projective policy (defined here from first principles, like the ball policy: the
+ * reference's concrete projective clipper lives in its RGB-D pipeline).  Keeps the Valid points of `full` that a pinhole camera
+ * mounted at sensor_in_robot (SceneClipper_::setSensorInRobot, scene_clipper.h:86-89) sees from robot_in_local_map:
+ *   r = robot_in_local_map^-1 * p, c = sensor_in_robot^-1 * r, projected exactly as the projective finder projects
+ *   (depth_min <= c.z <= depth_max, u = (K0*c.x)/c.z + K2, v = (K4*c.y)/c.z + K5, in view iff 0 <= u+0.5 < cols and
+ *   0 <= v+0.5 < rows, pixel = floor(v+0.5)*cols + floor(u+0.5));
+ *   occlusion_margin < 0: every in-view point is kept (frustum only); >= 0: only those with
+ *   c.z <= (minimum c.z over the in-view points of the pixel) + occlusion_margin -- 0 keeps every point that ties for the
+ *   minimum, +inf equals frustum only.  DESIGN.md section 4 "Projective clipping" is the arithmetic contract.
+ * Output as clip_ball: the kept points in scene order, in the ROBOT frame (r, bit for bit what clip_ball writes for the same
+ * point; the aligner applies robot_in_sensor itself), normals rotated, global indices, features and their presence.
+ *   refused   `clipped` unchanged.  SRRG2_E_INVALID: a null handle, pose or params; full == clipped; different devices or dims;
+ *             rows or cols <= 0 or rows*cols beyond int32; !(depth_min > 0) or !(depth_max >= depth_min); fx or fy zero / not
+ *             finite; a NaN margin.  SRRG2_E_UNSUPPORTED: scenes of dim 2 (a 2-D field-of-view clipper is not built), K with
+ *             skew.
+ *   status    Ready when `full` is empty, else Successful -- also when nothing is kept (`clipped` is then empty). */
+typedef struct srrg2_projective_clip_params {
+  float   camera_matrix[9];   /* row-major K; K[0][1] != 0 -> SRRG2_E_UNSUPPORTED (as the depth adaptor) */
+  int32_t image_rows, image_cols;
+  float   depth_min, depth_max;
+  float   sensor_in_robot[12];
+  float   occlusion_margin;   /* < 0: frustum only; >= 0: metres behind the nearest point of the pixel */
+} srrg2_projective_clip_params;
+typedef struct srrg2_clip_result {
+  int32_t status;        /* srrg2_clipper_status */
+  int32_t num_valid;     /* Valid points of full */
+  int32_t num_in_view;   /* of those, inside the depth range and the image */
+  int32_t num_kept;      /* == srrg2_scene_size(clipped) */
+} srrg2_clip_result;
+/* identity sensor, depth 0.4 .. 8 m, margin -1 (frustum only); camera_matrix (identity) / rows / cols (0) are the caller's */
+void srrg2_clip_default_projective_params(srrg2_projective_clip_params* p);
+int srrg2_scene_clip_projective(srrg2_scene_h full, const float* robot_in_local_map, const srrg2_projective_clip_params* p,
+                                srrg2_scene_h clipped, srrg2_clip_result* out /* may be NULL */);
 
 /* MergerCorrespondenceHomo_::compute() (S/mapping/merger_correspondence_homo_impl.cpp:11-125).
  * correspondences: fixed_idx = scene point, moving_idx = measurement point, processed in order

@@ -422,6 +422,7 @@ private:
 //   Scene                       a PointNormal{2,3}f cloud living in HBM (LocalMap scene slice / measurement); with setFeatures
 //                               a PointIntensityDescriptor{2,3}f one: descriptor + intensity travel through clip and merge
 //   SceneClipperBall            SceneClipper_<Estimate, Scene>              S/mapping/scene_clipper.h:17-122
+//   SceneClipperProjective      the same interface, projective policy (3-D): what a pinhole camera sees of the scene
 //   MergerCorrespondenceHomo    MergerCorrespondenceHomo_<Estimate, Scene>  S/mapping/merger_correspondence_homo.h
 template <int DIM>
 class Scene {
@@ -513,6 +514,44 @@ private:
   SceneType* _full    = nullptr;
   SceneType* _clipped = nullptr;
   EstimateType _robot_in_local_map = EstimateType::Identity();
+  Status _status = Error;
+};
+
+// the points of a 3-D scene that a pinhole camera at sensor_in_robot sees (srrg2_scene_clip_projective): param.camera_matrix,
+// image_rows / image_cols, depth range and occlusion_margin are the PARAMs; last() holds the counts of the last compute()
+class SceneClipperProjective {
+public:
+  enum Status { Error = 0, Successful = 1, Ready = 2 };  // scene_clipper.h:24-28
+  using EstimateType = Isometry<3>;
+  using SceneType    = Scene<3>;
+  srrg2_projective_clip_params param;
+  SceneClipperProjective() { srrg2_clip_default_projective_params(&param); }
+  void setFullScene(SceneType* s) { _full = s; }
+  void setClippedSceneInRobot(SceneType* s) { _clipped = s; }
+  void setRobotInLocalMap(const EstimateType& T) { _robot_in_local_map = T; }
+  void setSensorInRobot(const EstimateType& T) { std::memcpy(param.sensor_in_robot, T.data(), sizeof(param.sensor_in_robot)); }  // :86-89
+  void setCameraMatrix(const float* K_row_major) { std::memcpy(param.camera_matrix, K_row_major, sizeof(param.camera_matrix)); }
+  void compute() {
+    if (!_full || !_clipped) throw std::runtime_error("SceneClipperProjective::compute|scene not set");
+    _status = Error;
+    check(srrg2_scene_clip_projective(_full->handle(), _robot_in_local_map.data(), &param, _clipped->handle(), &_last));
+    _status = static_cast<Status>(_last.status);
+  }
+  Status status() const { return _status; }
+  const srrg2_clip_result& last() const { return _last; }
+  std::vector<int> globalIndices() const {  // :98-101
+    int n = 0;
+    check(srrg2_scene_global_indices(_clipped->handle(), nullptr, &n));
+    std::vector<int> v((size_t) n);
+    if (n) check(srrg2_scene_global_indices(_clipped->handle(), v.data(), &n));
+    return v;
+  }
+
+private:
+  SceneType* _full    = nullptr;
+  SceneType* _clipped = nullptr;
+  EstimateType _robot_in_local_map = EstimateType::Identity();
+  srrg2_clip_result _last{};
   Status _status = Error;
 };
 

@@ -56,6 +56,13 @@ def lib():
                                                  C.POINTER(abi.DepthAdaptorParams), C.POINTER(abi.AdaptResult)]
         _LIB.srrg2_adapt_laser_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(abi.ScanAdaptorParams),
                                                 C.POINTER(abi.AdaptResult)]
+        # srrg2_scene_clip_projective (mapping.SceneClipperProjective)
+        from . import mapping
+
+        _LIB.srrg2_clip_default_projective_params.argtypes = [C.POINTER(mapping.ProjectiveClipParams)]
+        _LIB.srrg2_clip_default_projective_params.restype = None
+        _LIB.srrg2_scene_clip_projective.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(mapping.ProjectiveClipParams),
+                                                     C.c_void_p, C.POINTER(mapping.ClipResult)]
     return _LIB
 
 

@@ -1,4 +1,4 @@
-// scene.hip -- scene slices kept in HBM between frames: ball clipping and correspondence-based merging
+// scene.hip -- scene slices kept in HBM between frames: ball and projective clipping, correspondence-based merging
 // (SURVEY.md section 8f row 2).  Replaces, behind the C ABI of include/srrg2_slam_amd.h:
 //   MergerCorrespondenceHomo_::compute()   S/mapping/merger_correspondence_homo_impl.cpp:11-125
 //   SceneClipper_::compute() (interface)   S/mapping/scene_clipper.h:17-122
@@ -10,7 +10,7 @@
 // the kernels that move points (k_clip_scatter, merge_one, k_append_scatter) have a feature-carrying instantiation, chosen on the
 // host, so a scene without features runs the code it ran before they existed.  All kernels are one thread per
 // point or correspondence, coalesced, HBM bound: clip = 2 passes over the scene (flag+count, scatter) around an
-// exclusive scan; merge = one pass over the correspondences + (if the merge target was not reached) flag/scan/scatter
+// exclusive scan (the projective clip with occlusion: one more in front, the per-pixel depth minimum); merge = one pass over the correspondences + (if the merge target was not reached) flag/scan/scatter
 // of the measurement.  The reference merges sequentially; results are identical because
 //   - a scene point hit by ONE correspondence is independent of all others (the common case: the tracker's
 //     correspondences come through an injective local->global map),
@@ -142,6 +142,76 @@ __device__ __forceinline__ void block_add(int v, int* target) {
   if (threadIdx.x == 0) {
     const int t = (red[0] + red[1]) + (red[2] + red[3]);
     if (t) atomicAdd(target, t);
+  }
+}
+
+// ---- projective clip (no reference counterpart: SceneClipper_ is an interface; DESIGN.md section 4 "Projective clipping") -------
+// keeps the Valid points a pinhole camera at sensor_in_robot sees: inside the depth range and the image, and -- margin >= 0 --
+// no further than `margin` behind the nearest point of their pixel.
+//   k_pclip_zmin     per pixel the minimum camera depth of the in-view points: positive floats order like their bit patterns,
+//                    so ONE 32-bit atomicMin per in-view point (no return value, order-free: deterministic)
+//   k_pclip_flag     keep flag per point + the Valid / in-view counts (one atomic per block and count)
+//   k_pclip_scatter  the points the scan kept (offset[i + 1] != offset[i]: the scan leaves the total in offset[n]), in the robot
+//                    frame: the same L and xform_point as k_clip_scatter, so the same bits
+struct ProjCam {
+  float K0, K2, K4, K5, depth_min, depth_max, margin;
+  int rows, cols;
+};
+
+// steps 1-4 of the contract: Valid, r = L p, c = S r, project_point of the projective finder (kernels.hip).  -1: not in view
+__device__ __forceinline__ int pclip_project(const Xf& L, const Xf& S, const ProjCam& C, const float4 p, bool& valid, float& cz) {
+  valid = valid_point(3, p);
+  if (!valid) return -1;
+  const float4 c = xform_point(3, S, xform_point(3, L, p));
+  if (!(isfinite(c.x) && isfinite(c.y) && isfinite(c.z))) return -1;
+  if (!(c.z >= C.depth_min) || !(c.z <= C.depth_max)) return -1;
+  const float u  = (C.K0 * c.x) / c.z + C.K2;
+  const float v  = (C.K4 * c.y) / c.z + C.K5;
+  const float uf = u + 0.5f, vf = v + 0.5f;
+  if (!(uf >= 0.f) || !(uf < (float) C.cols) || !(vf >= 0.f) || !(vf < (float) C.rows)) return -1;
+  cz = c.z;
+  return (int) floorf(vf) * C.cols + (int) floorf(uf);
+}
+
+__global__ void k_pclip_zmin(Xf L, Xf S, ProjCam C, const float4* __restrict__ pts, int n, unsigned* __restrict__ zmin) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    bool valid;
+    float cz;
+    const int pix = pclip_project(L, S, C, pts[i], valid, cz);
+    if (pix >= 0) atomicMin(&zmin[pix], __float_as_uint(cz));  // (pix < rows * cols: project_point's bounds)
+  }
+}
+
+// counters: [0] Valid points, [1] in-view points
+template <bool OCCLUSION>
+__global__ void k_pclip_flag(Xf L, Xf S, ProjCam C, const float4* __restrict__ pts, int n, const unsigned* __restrict__ zmin,
+                             int* __restrict__ flags, int* __restrict__ counters) {
+  int nvalid = 0, nview = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    bool valid;
+    float cz;
+    const int pix = pclip_project(L, S, C, pts[i], valid, cz);
+    bool keep     = pix >= 0;
+    nvalid += valid ? 1 : 0;
+    nview += keep ? 1 : 0;
+    if (OCCLUSION && keep) keep = cz <= __uint_as_float(zmin[pix]) + C.margin;
+    flags[i] = keep ? 1 : 0;
+  }
+  block_add(nvalid, &counters[0]);
+  block_add(nview, &counters[1]);
+}
+
+template <bool FEAT>
+__global__ void k_pclip_scatter(Xf L, const float4* __restrict__ pts, const float4* __restrict__ nrm, int n,
+                                const int* __restrict__ offset, float4* __restrict__ out_pts, float4* __restrict__ out_nrm,
+                                int* __restrict__ gidx, int cap, Feat f) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int k = offset[i];
+    if (offset[i + 1] == k || k >= cap) continue;  // not kept / no room yet (as k_clip_scatter: the caller repeats it)
+    out_pts[k] = xform_point(3, L, pts[i]);
+    out_nrm[k] = nrm ? rotate_normal(3, L, nrm[i]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    gidx[k]    = i;
+    if (FEAT) move_features(f, i, k);
   }
 }
 
@@ -498,7 +568,7 @@ int srrg2_scene_destroy(srrg2_scene_h s) {
   (void) hipSetDevice(s->device);
   if (s->stream) (void) hipStreamSynchronize(s->stream);
   s->pts.release(); s->nrm.release(); s->desc.release(); s->inten.release(); s->gidx.release(); s->flags.release(); s->scan_sums.release();
-  s->counts.release(); s->dup_list.release(); s->dup_keys.release(); s->sort_tmp.release(); s->merged.release(); s->corr.release(); s->staging.release(); s->dscalars.release();
+  s->counts.release(); s->dup_list.release(); s->dup_keys.release(); s->sort_tmp.release(); s->merged.release(); s->corr.release(); s->staging.release(); s->zmin.release(); s->dscalars.release();
   if (s->scalars) (void) hipHostFree(s->scalars);
   if (s->stream) (void) hipStreamDestroy(s->stream);
   delete s;
@@ -713,6 +783,103 @@ int srrg2_scene_clip_ball(srrg2_scene_h full, const float* robot_in_local_map, f
     HIP_TRY(hipStreamSynchronize(st));
   }
   clipped->n = clipped->ng = total;
+  return 0;
+}
+
+void srrg2_clip_default_projective_params(srrg2_projective_clip_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->camera_matrix[0] = p->camera_matrix[4] = p->camera_matrix[8] = 1.f;
+  p->depth_min = 0.4f;
+  p->depth_max = 8.f;
+  p->sensor_in_robot[0] = p->sensor_in_robot[5] = p->sensor_in_robot[10] = 1.f;
+  p->occlusion_margin = -1.f;
+}
+
+int srrg2_scene_clip_projective(srrg2_scene_h full, const float* robot_in_local_map, const srrg2_projective_clip_params* p,
+                                srrg2_scene_h clipped, srrg2_clip_result* out) {
+  if (!full || !clipped || !robot_in_local_map || !p) return fail(SRRG2_E_INVALID, "scene_clip_projective: null argument");
+  if (full == clipped || full->dim != clipped->dim || full->device != clipped->device)
+    return fail(SRRG2_E_INVALID, "scene_clip_projective: full and clipped must be two scenes of one dim on one device");
+  if (full->dim != 3)
+    return fail(SRRG2_E_UNSUPPORTED, "scene_clip_projective: 2-D scenes (a field-of-view clipper over bearings is not built)");
+  if (p->image_rows <= 0 || p->image_cols <= 0 || (long long) p->image_rows * (long long) p->image_cols > 0x7fffffffLL)
+    return fail(SRRG2_E_INVALID, "scene_clip_projective: image_rows, image_cols > 0 and rows*cols within int32");
+  if (!(p->depth_min > 0.f) || !(p->depth_max >= p->depth_min))
+    return fail(SRRG2_E_INVALID, "scene_clip_projective: 0 < depth_min <= depth_max");
+  const float fx = p->camera_matrix[0], fy = p->camera_matrix[4];
+  if (!std::isfinite(fx) || !std::isfinite(fy) || fx == 0.f || fy == 0.f)
+    return fail(SRRG2_E_INVALID, "scene_clip_projective: fx and fy must be finite and non-zero");
+  if (std::isnan(p->occlusion_margin)) return fail(SRRG2_E_INVALID, "scene_clip_projective: occlusion_margin is NaN");
+  if (p->camera_matrix[1] != 0.f)
+    return fail(SRRG2_E_UNSUPPORTED, "scene_clip_projective: a camera matrix with skew (K[0][1] != 0)");
+  int rc;
+  if ((rc = scene_device(clipped)) || (rc = scene_device(full))) return rc;
+  float Linv[12], Sinv[12];
+  dm::se3_inverse(robot_in_local_map, Linv);
+  dm::se3_inverse(p->sensor_in_robot, Sinv);
+  const Xf L = load_transform(3, Linv), S = load_transform(3, Sinv);
+  const ProjCam cam{fx, p->camera_matrix[2], fy, p->camera_matrix[5], p->depth_min, p->depth_max, p->occlusion_margin,
+                    p->image_rows, p->image_cols};
+  const bool occlusion = p->occlusion_margin >= 0.f;
+  const int n          = full->n;
+  clipped->has_normals = full->has_normals;
+  clipped->has_desc    = full->has_desc;
+  clipped->has_inten   = full->has_inten;
+  clipped->n = clipped->ng = 0;
+  // (arrays even for an empty result, as srrg2_scene_set leaves them: srrg2_scene_device_arrays then shows the normals' presence)
+  if ((rc = scene_reserve(clipped, 1, 0)) || (rc = clipped->gidx.reserve(1))) return rc;
+  if (out) {
+    std::memset(out, 0, sizeof(*out));
+    out->status = n == 0 ? SRRG2_CLIPPER_READY : SRRG2_CLIPPER_SUCCESSFUL;
+  }
+  if (n == 0) return 0;
+  hipStream_t st = full->stream;
+  if ((rc = full->flags.reserve((size_t) n + 1))) return rc;
+  // (the two counts in front of the scan's total at the tail of its scratch: one copy brings all three to the host)
+  if ((rc = full->scan_sums.reserve((size_t) srrg2amd::scan_num_blocks(n) + 4))) return rc;
+  int* const counters = full->scan_sums.p + full->scan_sums.cap - 3;
+  int* const dtotal   = counters + 2;
+  HIP_TRY(hipMemsetAsync(counters, 0, 2 * sizeof(int), st));
+  const dim3 grid(blocks_for(n));
+  if (occlusion) {
+    const size_t npix = (size_t) cam.rows * (size_t) cam.cols;
+    if ((rc = full->zmin.reserve(npix))) return rc;
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) full->zmin.p, 0x7f800000, npix, st));  // +inf
+    hipLaunchKernelGGL(k_pclip_zmin, grid, dim3(256), 0, st, L, S, cam, full->pts.p, n, full->zmin.p);
+    hipLaunchKernelGGL(k_pclip_flag<true>, grid, dim3(256), 0, st, L, S, cam, full->pts.p, n, full->zmin.p, full->flags.p, counters);
+  } else {
+    hipLaunchKernelGGL(k_pclip_flag<false>, grid, dim3(256), 0, st, L, S, cam, full->pts.p, n, (const unsigned*) nullptr,
+                       full->flags.p, counters);
+  }
+  srrg2amd::launch_exclusive_scan(full->flags.p, n, full->scan_sums.p, dtotal, st);
+  // as clip_ball: the scatter goes behind the scan into the room `clipped` has, before the host knows the total -- one wait per
+  // clip; a total beyond the room repeats the scatter with room for all
+  const int room = (int) std::min<size_t>(std::min(clipped->pts.cap, clipped->nrm.cap), clipped->gidx.cap);
+  {
+    const Feat f = feat_of(full, clipped);
+    LAUNCH_FEAT(k_pclip_scatter, moves_features(f), grid, st, L, full->pts.p, full->has_normals ? full->nrm.p : nullptr, n,
+                full->flags.p, clipped->pts.p, clipped->nrm.p, clipped->gidx.p, room, f);
+  }
+  HIP_TRY(hipMemcpyAsync(&full->scalars[0], counters, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  const int num_valid = full->scalars[0], num_in_view = full->scalars[1], total = full->scalars[2];
+  if (total > room) {
+    if ((rc = scene_reserve(clipped, total, 0))) return rc;
+    if ((rc = clipped->gidx.reserve((size_t) total))) return rc;
+    const Feat f = feat_of(full, clipped);
+    LAUNCH_FEAT(k_pclip_scatter, moves_features(f), grid, st, L, full->pts.p, full->has_normals ? full->nrm.p : nullptr, n,
+                full->flags.p, clipped->pts.p, clipped->nrm.p, clipped->gidx.p, total, f);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  clipped->n = clipped->ng = total;
+  if (out) {
+    out->num_valid   = num_valid;
+    out->num_in_view = num_in_view;
+    out->num_kept    = total;
+  }
   return 0;
 }
 
