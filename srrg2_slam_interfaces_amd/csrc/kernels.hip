@@ -5390,600 +5390,7 @@ __global__ __launch_bounds__(256) void k_icp_control_final(CtlParams C, ProblemS
   state_from_lds(&states[prob], &sst);
 }
 
-// ============================================================================================
-// Small alignments (laser scans, landmark maps: up to ~1000 moving points).  With one launch per pass such a compute()
-// is ~24 launch floors and little else (C1: 0.33 ms on the GPU against 0.66 ms on one CPU core; 0.23 ms here).  ONE
-// workgroup owns the problem for the whole compute(): the state and the sums live in LDS, the passes loop over the
-// problem's tiles, thread 0 runs the control step between them -- the same per-point and control code as the
-// launch-per-pass path, so the same bits.  A batch of small problems runs one workgroup per problem.
-// ============================================================================================
-// (TWIN: k_icp_small_pairs below repeats this body statement for statement -- a change here is a change there; the pair-batch tests
-// compare the two bit for bit, tests/test_gpu_align_pairs.py)
-template <int DIM, bool PLANE>
-__global__ __launch_bounds__(512) void k_icp_small(SliceDev S, CtlParams C, const ProblemDev* __restrict__ probs,
-                                                   ProblemState* __restrict__ states, srrg2_iteration_stats* __restrict__ stats,
-                                                   ProblemOut* __restrict__ outs_host,
-                                                   srrg2_iteration_stats* __restrict__ stats_host) {
-  constexpr int NW = 8;  // (16 waves would cap the registers at 128 per lane: the SE(3) control step spills, measured slower)
-  constexpr int D  = DIM == 3 ? 6 : 3;
-  const int prob   = blockIdx.x;
-  __shared__ ProblemState sst;
-  __shared__ long long sums[SRRG2_MAX_SLICES][ACC_N];
-  __shared__ double scaled[SRRG2_MAX_SLICES][ACC_N];
-  state_to_lds(&sst, &states[prob]);
-  __syncthreads();
-  const ProblemDev pd = probs[prob];
-  const int ntiles    = (pd.nm + NW * 64 - 1) / (NW * 64);
-  const int nrun      = C.params.enable_inlier_only_runs ? 2 : 1;
-  for (int run = 0; run < nrun; ++run) {
-    for (int it = 0; it < C.params.max_iterations; ++it) {
-      if (sst.done || sst.finished) break;  // (uniform: LDS)
-      if (threadIdx.x < ACC_N) sums[S.slice_idx][threadIdx.x] = 0;
-      __syncthreads();
-      for (int tile = 0; tile < ntiles; ++tile) {
-        StepView sv;
-        step_view_of_state(S, &sst, sv);
-        icp_step_body<DIM, PLANE, NW>(S, pd, sv, prob, tile, ntiles, C.K, sums[S.slice_idx]);
-        __syncthreads();  // (the body's shared scratch is reused by the next tile)
-      }
-      if (threadIdx.x < ACC_N)
-        scaled[S.slice_idx][threadIdx.x] = (double) sums[S.slice_idx][threadIdx.x] * dm::pow2(-sst.kexp[S.slice_idx]);
-      __syncthreads();
-      if (threadIdx.x == 0) control_body<D>(C, &sst, stats, prob, sums, scaled);
-      __syncthreads();
-    }
-    if (run == 0 && nrun == 2) {  // multi_aligner_impl.cpp:75-85, then the inlier-only run
-      if (threadIdx.x == 0) icp_post_one(C, &sst, stats, prob);
-      __syncthreads();
-    }
-  }
-  __threadfence();  // (the statistics thread 0 wrote are read back by the whole workgroup below)
-  __syncthreads();
-  icp_finalize_block(C, &sst, stats, outs_host, stats_host, prob, nrun == 1);
-  __syncthreads();
-  state_from_lds(&states[prob], &sst);
-}
-// ... of a pair batch: the problem's own grid (k_icp_step_pairs).  The body is k_icp_small's, statement for statement: moved into a
-// shared function, k_icp_small itself came out with another register count (DESIGN.md section 5: existing kernels stay as they are).
-template <int DIM, bool PLANE>
-__global__ __launch_bounds__(512) void k_icp_small_pairs(SliceDev S, const GridDev* __restrict__ grids, CtlParams C,
-                                                         const ProblemDev* __restrict__ probs, ProblemState* __restrict__ states,
-                                                         srrg2_iteration_stats* __restrict__ stats, ProblemOut* __restrict__ outs_host,
-                                                         srrg2_iteration_stats* __restrict__ stats_host) {
-  S.grid = grids[blockIdx.x];
-  constexpr int NW = 8;  // (16 waves would cap the registers at 128 per lane: the SE(3) control step spills, measured slower)
-  constexpr int D  = DIM == 3 ? 6 : 3;
-  const int prob   = blockIdx.x;
-  __shared__ ProblemState sst;
-  __shared__ long long sums[SRRG2_MAX_SLICES][ACC_N];
-  __shared__ double scaled[SRRG2_MAX_SLICES][ACC_N];
-  state_to_lds(&sst, &states[prob]);
-  __syncthreads();
-  const ProblemDev pd = probs[prob];
-  const int ntiles    = (pd.nm + NW * 64 - 1) / (NW * 64);
-  const int nrun      = C.params.enable_inlier_only_runs ? 2 : 1;
-  for (int run = 0; run < nrun; ++run) {
-    for (int it = 0; it < C.params.max_iterations; ++it) {
-      if (sst.done || sst.finished) break;  // (uniform: LDS)
-      if (threadIdx.x < ACC_N) sums[S.slice_idx][threadIdx.x] = 0;
-      __syncthreads();
-      for (int tile = 0; tile < ntiles; ++tile) {
-        StepView sv;
-        step_view_of_state(S, &sst, sv);
-        icp_step_body<DIM, PLANE, NW>(S, pd, sv, prob, tile, ntiles, C.K, sums[S.slice_idx]);
-        __syncthreads();  // (the body's shared scratch is reused by the next tile)
-      }
-      if (threadIdx.x < ACC_N)
-        scaled[S.slice_idx][threadIdx.x] = (double) sums[S.slice_idx][threadIdx.x] * dm::pow2(-sst.kexp[S.slice_idx]);
-      __syncthreads();
-      if (threadIdx.x == 0) control_body<D>(C, &sst, stats, prob, sums, scaled);
-      __syncthreads();
-    }
-    if (run == 0 && nrun == 2) {  // multi_aligner_impl.cpp:75-85, then the inlier-only run
-      if (threadIdx.x == 0) icp_post_one(C, &sst, stats, prob);
-      __syncthreads();
-    }
-  }
-  __threadfence();  // (the statistics thread 0 wrote are read back by the whole workgroup below)
-  __syncthreads();
-  icp_finalize_block(C, &sst, stats, outs_host, stats_host, prob, nrun == 1);
-  __syncthreads();
-  state_from_lds(&states[prob], &sst);
-}
-
-// ============================================================================================
-// launchers
-// ============================================================================================
-namespace srrg2amd {
-
-int icp_step_blocks(int max_nm) {
-  return (max_nm + 255) / 256;  // one moving point per thread
-}
-
-int icp_queue_blocks(int max_nm, int K) {
-  // waves that share the deferred searches of one problem: up to 4096 for a single alignment, fewer per problem in a batch
-  int b = icp_step_blocks(max_nm);
-  int cap = K <= 1 ? 1024 : (K <= 8 ? 256 : 64);
-  return b < cap ? b : cap;
-}
-
-static void launch_icp_queue(int dim, bool plane, const SliceDev& S, const ProblemDev* probs, ProblemState* states, int K,
-                             int max_nm, hipStream_t s) {
-  const int qb = icp_queue_blocks(max_nm, K);
-  dim3 qgrid(qb, K);
-  if (dim == 3) {
-    if (plane)
-      hipLaunchKernelGGL((k_icp_step_queue<3, true>), qgrid, dim3(256), 0, s, S, probs, states);
-    else
-      hipLaunchKernelGGL((k_icp_step_queue<3, false>), qgrid, dim3(256), 0, s, S, probs, states);
-  } else {
-    if (plane)
-      hipLaunchKernelGGL((k_icp_step_queue<2, true>), qgrid, dim3(256), 0, s, S, probs, states);
-    else
-      hipLaunchKernelGGL((k_icp_step_queue<2, false>), qgrid, dim3(256), 0, s, S, probs, states);
-  }
-}
-
-void launch_icp_step(int dim, bool plane, const SliceDev& S, const ProblemDev* probs, ProblemState* states, int K,
-                     int max_nm, hipStream_t s, const CtlParams* init_C, const InitInline* init_inl) {
-  if (K <= 0) return;
-  if (S.fc.pub && init_C) {  // the first pass of a single alignment with compute()'s prologue inside (even for an empty cloud)
-    dim3 fgrid(K, (max_nm + 255) / 256 + 1);  // (+ the workgroup that writes the rest of the prologue)
-    ProblemDev* pw = const_cast<ProblemDev*>(probs);
-    if (dim == 3) {
-      if (plane)
-        hipLaunchKernelGGL((k_icp_step_fused_init<3, true>), fgrid, dim3(256), 0, s, S, *init_C, *init_inl, pw, states);
-      else
-        hipLaunchKernelGGL((k_icp_step_fused_init<3, false>), fgrid, dim3(256), 0, s, S, *init_C, *init_inl, pw, states);
-    } else {
-      if (plane)
-        hipLaunchKernelGGL((k_icp_step_fused_init<2, true>), fgrid, dim3(256), 0, s, S, *init_C, *init_inl, pw, states);
-      else
-        hipLaunchKernelGGL((k_icp_step_fused_init<2, false>), fgrid, dim3(256), 0, s, S, *init_C, *init_inl, pw, states);
-    }
-    return;
-  }
-  if (max_nm <= 0) return;
-  if (S.fc.pub) {  // fused control steps: the record instead of ProblemState, no deferred-search queue
-    dim3 fgrid(K, (max_nm + 255) / 256);
-#define FUSED_GRID_LAUNCH(PRIORS)                                                                              \
-  do {                                                                                                         \
-    if (dim == 3) {                                                                                            \
-      if (plane)                                                                                               \
-        hipLaunchKernelGGL((k_icp_step_fused<3, true, PRIORS>), fgrid, dim3(256), 0, s, S, probs, states);     \
-      else                                                                                                     \
-        hipLaunchKernelGGL((k_icp_step_fused<3, false, PRIORS>), fgrid, dim3(256), 0, s, S, probs, states);    \
-    } else {                                                                                                   \
-      if (plane)                                                                                               \
-        hipLaunchKernelGGL((k_icp_step_fused<2, true, PRIORS>), fgrid, dim3(256), 0, s, S, probs, states);     \
-      else                                                                                                     \
-        hipLaunchKernelGGL((k_icp_step_fused<2, false, PRIORS>), fgrid, dim3(256), 0, s, S, probs, states);    \
-    }                                                                                                          \
-  } while (0)
-    if (S.fc.prior_mask)
-      FUSED_GRID_LAUNCH(true);
-    else
-      FUSED_GRID_LAUNCH(false);
-#undef FUSED_GRID_LAUNCH
-    return;
-  }
-  int bx = (max_nm + 255) / 256;  // one moving point per thread
-  dim3 grid(bx, K);
-  if (dim == 3) {
-    if (plane)
-      hipLaunchKernelGGL((k_icp_step<3, true>), grid, dim3(256), 0, s, S, probs, states);
-    else
-      hipLaunchKernelGGL((k_icp_step<3, false>), grid, dim3(256), 0, s, S, probs, states);
-  } else {
-    if (plane)
-      hipLaunchKernelGGL((k_icp_step<2, true>), grid, dim3(256), 0, s, S, probs, states);
-    else
-      hipLaunchKernelGGL((k_icp_step<2, false>), grid, dim3(256), 0, s, S, probs, states);
-  }
-  if (S.queue) launch_icp_queue(dim, plane, S, probs, states, K, max_nm, s);
-}
-
-#ifdef SRRG2_PASS_TIMELINE
-extern "C" int srrg2_amd_debug_pass_timeline(unsigned long long* out, int reset) {
-  const size_t bytes = sizeof(unsigned long long) * 16 * 512 * 8;
-  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pass_ts), bytes) != hipSuccess) return -1;
-  if (reset) {
-    static unsigned long long zero[16 * 512 * 8];
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_pass_ts), zero, bytes) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif
-
-#ifdef SRRG2_CNL_STATS
-extern "C" int srrg2_amd_debug_cnl_stats(unsigned long long* out, int reset) {
-  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_cnl_stats), sizeof(unsigned long long) * 64) != hipSuccess) return -1;
-  if (reset) {
-    static unsigned long long zero[64];
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_cnl_stats), zero, sizeof(zero)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif
-
-#ifdef SRRG2_TILE_STATS
-extern "C" int srrg2_amd_debug_tile_stats(unsigned long long* out, int reset) {
-  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tile_stats), sizeof(unsigned long long) * 64) != hipSuccess) return -1;
-  if (reset) {
-    static unsigned long long zero[64];
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_tile_stats), zero, sizeof(zero)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif
-
-// the search pass of a batch with wave tiles in LDS (cap: candidates per wave tile, 416: four workgroups per CU, 504: three)
-void launch_icp_step_tile(int dim, bool plane, const SliceDev& S, const ProblemDev* probs, ProblemState* states, int K,
-                          int max_nm, int cap, hipStream_t s) {
-  if (K <= 0 || max_nm <= 0) return;
-  dim3 grid((max_nm + 255) / 256, K);
-#define TILE_LAUNCH(D, P)                                                                            \
-  do {                                                                                               \
-    if (cap > 450)                                                                                   \
-      hipLaunchKernelGGL((k_icp_step_tile<D, P, 504>), grid, dim3(256), 0, s, S, probs, states);      \
-    else                                                                                             \
-      hipLaunchKernelGGL((k_icp_step_tile<D, P, 416>), grid, dim3(256), 0, s, S, probs, states);      \
-  } while (0)
-  if (dim == 3) {
-    if (plane) TILE_LAUNCH(3, true); else TILE_LAUNCH(3, false);
-  } else {
-    if (plane) TILE_LAUNCH(2, true); else TILE_LAUNCH(2, false);
-  }
-#undef TILE_LAUNCH
-}
-
-// the search pass over the cell neighbour lists of the grid (S.grid.list_R > 0); team = lanes per moving point (1 or 4)
-void launch_icp_step_cnl(int dim, bool plane, const SliceDev& S, const GridLists& GL, const ProblemDev* probs,
-                         ProblemState* states, int K, int max_nm, int team, hipStream_t s, const CtlParams* init_C,
-                         const InitInline* init_inl, const InitBatch* init_bat) {
-  if (K <= 0) return;
-  if (S.fc.pub && init_C && init_bat) {  // a part of a batch (K <= INIT_BATCH_MAX alignments) with the prologue in its first pass
-    ProblemDev* pw = const_cast<ProblemDev*>(probs);
-#define CNL_INITB_LAUNCH(TEAM)                                                                                                        \
-  do {                                                                                                                                \
-    dim3 grid(K, (max_nm * TEAM + 255) / 256 + 1);                                                                                    \
-    if (dim == 3) {                                                                                                                   \
-      if (plane)                                                                                                                      \
-        hipLaunchKernelGGL((k_icp_step_cnl_init_batch<3, true, TEAM>), grid, dim3(256), 0, s, S, GL, *init_C, *init_bat, pw, states);  \
-      else                                                                                                                            \
-        hipLaunchKernelGGL((k_icp_step_cnl_init_batch<3, false, TEAM>), grid, dim3(256), 0, s, S, GL, *init_C, *init_bat, pw, states); \
-    } else {                                                                                                                          \
-      if (plane)                                                                                                                      \
-        hipLaunchKernelGGL((k_icp_step_cnl_init_batch<2, true, TEAM>), grid, dim3(256), 0, s, S, GL, *init_C, *init_bat, pw, states);  \
-      else                                                                                                                            \
-        hipLaunchKernelGGL((k_icp_step_cnl_init_batch<2, false, TEAM>), grid, dim3(256), 0, s, S, GL, *init_C, *init_bat, pw, states); \
-    }                                                                                                                                 \
-  } while (0)
-    if (team >= 4)
-      CNL_INITB_LAUNCH(4);
-    else
-      CNL_INITB_LAUNCH(1);
-#undef CNL_INITB_LAUNCH
-    return;
-  }
-  if (S.fc.pub && init_C) {  // the first pass of a single alignment with compute()'s prologue inside (even for an empty cloud)
-    ProblemDev* pw = const_cast<ProblemDev*>(probs);
-#define CNL_INIT_LAUNCH(TEAM)                                                                                                   \
-  do {                                                                                                                          \
-    dim3 grid(K, (max_nm * TEAM + 255) / 256 + 1); /* (+ the workgroup that writes the rest of the prologue) */                  \
-    if (dim == 3) {                                                                                                             \
-      if (plane)                                                                                                                \
-        hipLaunchKernelGGL((k_icp_step_cnl_init<3, true, TEAM>), grid, dim3(256), 0, s, S, GL, *init_C, *init_inl, pw, states);  \
-      else                                                                                                                      \
-        hipLaunchKernelGGL((k_icp_step_cnl_init<3, false, TEAM>), grid, dim3(256), 0, s, S, GL, *init_C, *init_inl, pw, states); \
-    } else {                                                                                                                    \
-      if (plane)                                                                                                                \
-        hipLaunchKernelGGL((k_icp_step_cnl_init<2, true, TEAM>), grid, dim3(256), 0, s, S, GL, *init_C, *init_inl, pw, states);  \
-      else                                                                                                                      \
-        hipLaunchKernelGGL((k_icp_step_cnl_init<2, false, TEAM>), grid, dim3(256), 0, s, S, GL, *init_C, *init_inl, pw, states); \
-    }                                                                                                                           \
-  } while (0)
-    if (team >= 4)
-      CNL_INIT_LAUNCH(4);
-    else
-      CNL_INIT_LAUNCH(1);
-#undef CNL_INIT_LAUNCH
-    return;
-  }
-  if (max_nm <= 0) return;
-#define CNL_LAUNCH(TEAM, FUSED)                                                                                   \
-  do {                                                                                                            \
-    dim3 grid((max_nm * TEAM + 255) / 256, K);                                                                    \
-    if (FUSED) grid = dim3(K, (max_nm * TEAM + 255) / 256); /* x = problem, y = tile */                            \
-    if (dim == 3) {                                                                                               \
-      if (plane)                                                                                                  \
-        hipLaunchKernelGGL((k_icp_step_cnl<3, true, TEAM, FUSED>), grid, dim3(256), 0, s, S, GL, probs, states);  \
-      else                                                                                                        \
-        hipLaunchKernelGGL((k_icp_step_cnl<3, false, TEAM, FUSED>), grid, dim3(256), 0, s, S, GL, probs, states); \
-    } else {                                                                                                      \
-      if (plane)                                                                                                  \
-        hipLaunchKernelGGL((k_icp_step_cnl<2, true, TEAM, FUSED>), grid, dim3(256), 0, s, S, GL, probs, states);  \
-      else                                                                                                        \
-        hipLaunchKernelGGL((k_icp_step_cnl<2, false, TEAM, FUSED>), grid, dim3(256), 0, s, S, GL, probs, states); \
-    }                                                                                                             \
-  } while (0)
-  // (fused control steps -- S.fc.pub: the instantiations that read the state from the published record)
-  if (S.fc.pub && S.fc.prior_mask) {  // (... of an aligner with prior slices: the control wave linearises them, wave_prior)
-    if (team >= 4)
-      CNL_LAUNCH(4, 2);
-    else
-      CNL_LAUNCH(1, 2);
-  } else if (S.fc.pub) {
-    if (team >= 4)
-      CNL_LAUNCH(4, 1);
-    else
-      CNL_LAUNCH(1, 1);
-  } else {
-    if (team >= 4)
-      CNL_LAUNCH(4, 0);
-    else
-      CNL_LAUNCH(1, 0);
-  }
-#undef CNL_LAUNCH
-}
-template <int PPT, bool GATHER, int FUSED>
-static void launch_fast_ppt(int dim, bool plane, const SliceDev& S, const ProblemDev* probs, ProblemState* states, int K,
-                            int max_nm, hipStream_t s) {
-  dim3 grid((max_nm + 256 * PPT - 1) / (256 * PPT), K);
-  if (FUSED) grid = dim3(K, (max_nm + 256 * PPT - 1) / (256 * PPT));  // (x = problem, y = tile)
-  if (dim == 3) {
-    if (plane)
-      hipLaunchKernelGGL((k_icp_step_fast<3, true, PPT, GATHER, FUSED>), grid, dim3(256), 0, s, S, probs, states);
-    else
-      hipLaunchKernelGGL((k_icp_step_fast<3, false, PPT, GATHER, FUSED>), grid, dim3(256), 0, s, S, probs, states);
-  } else {
-    if (plane)
-      hipLaunchKernelGGL((k_icp_step_fast<2, true, PPT, GATHER, FUSED>), grid, dim3(256), 0, s, S, probs, states);
-    else
-      hipLaunchKernelGGL((k_icp_step_fast<2, false, PPT, GATHER, FUSED>), grid, dim3(256), 0, s, S, probs, states);
-  }
-}
-void launch_icp_step_fast(int dim, bool plane, const SliceDev& S, const ProblemDev* probs, ProblemState* states, int K,
-                          int max_nm, int ppt, bool gather, hipStream_t s) {
-  if (K <= 0 || max_nm <= 0) return;
-  if (S.fc.pub && S.fc.prior_mask) {  // ... of an aligner with prior slices (one point per thread: the instantiations that exist)
-    if (gather)
-      launch_fast_ppt<1, true, 2>(dim, plane, S, probs, states, K, max_nm, s);
-    else
-      launch_fast_ppt<1, false, 2>(dim, plane, S, probs, states, K, max_nm, s);
-    return;
-  }
-  if (S.fc.pub) {  // fused control steps (one or two points per thread)
-    if (gather) {
-      if (ppt >= 2)
-        launch_fast_ppt<2, true, 1>(dim, plane, S, probs, states, K, max_nm, s);
-      else
-        launch_fast_ppt<1, true, 1>(dim, plane, S, probs, states, K, max_nm, s);
-    } else {
-      if (ppt >= 2)
-        launch_fast_ppt<2, false, 1>(dim, plane, S, probs, states, K, max_nm, s);
-      else
-        launch_fast_ppt<1, false, 1>(dim, plane, S, probs, states, K, max_nm, s);
-    }
-    return;
-  }
-  if (gather) {
-    if (ppt >= 4)
-      launch_fast_ppt<4, true, 0>(dim, plane, S, probs, states, K, max_nm, s);
-    else if (ppt >= 2)
-      launch_fast_ppt<2, true, 0>(dim, plane, S, probs, states, K, max_nm, s);
-    else
-      launch_fast_ppt<1, true, 0>(dim, plane, S, probs, states, K, max_nm, s);
-  } else {
-    if (ppt >= 4)
-      launch_fast_ppt<4, false, 0>(dim, plane, S, probs, states, K, max_nm, s);
-    else if (ppt >= 2)
-      launch_fast_ppt<2, false, 0>(dim, plane, S, probs, states, K, max_nm, s);
-    else
-      launch_fast_ppt<1, false, 0>(dim, plane, S, probs, states, K, max_nm, s);
-  }
-  if (S.queue) launch_icp_queue(dim, plane, S, probs, states, K, max_nm, s);
-}
-
-void launch_icp_outputs(int dim, bool plane, const SliceDev& S, const ProblemDev* probs, const ProblemState* states, int K,
-                        int max_nm, hipStream_t s) {
-  if (K <= 0 || max_nm <= 0) return;
-  dim3 grid((max_nm + 255) / 256, K);
-  if (dim == 3) {
-    if (plane)
-      hipLaunchKernelGGL((k_icp_outputs<3, true>), grid, dim3(256), 0, s, S, probs, states);
-    else
-      hipLaunchKernelGGL((k_icp_outputs<3, false>), grid, dim3(256), 0, s, S, probs, states);
-  } else {
-    if (plane)
-      hipLaunchKernelGGL((k_icp_outputs<2, true>), grid, dim3(256), 0, s, S, probs, states);
-    else
-      hipLaunchKernelGGL((k_icp_outputs<2, false>), grid, dim3(256), 0, s, S, probs, states);
-  }
-}
-
-void launch_corr_step(int dim, bool plane, const SliceDev& S, const ProblemDev* probs, ProblemState* states, int K,
-                      int max_ncorr, hipStream_t s) {
-  if (K <= 0 || max_ncorr <= 0) return;
-  dim3 grid((max_ncorr + 255) / 256, K);
-  if (dim == 3) {
-    if (plane)
-      hipLaunchKernelGGL((k_icp_step_corr<3, true>), grid, dim3(256), 0, s, S, probs, states);
-    else
-      hipLaunchKernelGGL((k_icp_step_corr<3, false>), grid, dim3(256), 0, s, S, probs, states);
-  } else {
-    if (plane)
-      hipLaunchKernelGGL((k_icp_step_corr<2, true>), grid, dim3(256), 0, s, S, probs, states);
-    else
-      hipLaunchKernelGGL((k_icp_step_corr<2, false>), grid, dim3(256), 0, s, S, probs, states);
-  }
-}
-
-void launch_proj_step(bool repro, const SliceDev& S, const ProblemDev* probs, ProblemState* states, int K, int max_nm,
-                      hipStream_t s) {
-  if (K <= 0 || max_nm <= 0) return;
-  dim3 grid(icp_step_blocks(max_nm), K);
-  // (no memset: the z-buffers ping-pong, k_icp_step_proj resets the one the next pass will use)
-  hipLaunchKernelGGL(k_proj_zbuf, grid, dim3(256), 0, s, S, probs, states);
-  if (repro)
-    hipLaunchKernelGGL((k_icp_step_proj<true>), grid, dim3(256), 0, s, S, probs, states);
-  else
-    hipLaunchKernelGGL((k_icp_step_proj<false>), grid, dim3(256), 0, s, S, probs, states);
-}
-
-void launch_proj_step_pack(const SliceDev* slices, const ProblemDev* const* probs, int nslices, ProblemState* states, int K,
-                           int max_nm, hipStream_t s) {
-  if (K <= 0 || max_nm <= 0 || nslices <= 0 || nslices > 4) return;
-  SlicePack P;
-  for (int z = 0; z < nslices; ++z) {
-    P.s[z]     = slices[z];
-    P.probs[z] = probs[z];
-  }
-  for (int z = nslices; z < 4; ++z) {
-    P.s[z]     = slices[0];
-    P.probs[z] = probs[0];
-  }
-  dim3 grid(icp_step_blocks(max_nm), K, nslices);
-  hipLaunchKernelGGL(k_proj_zbuf_pack, grid, dim3(256), 0, s, P, states);
-  hipLaunchKernelGGL(k_icp_step_proj_pack, grid, dim3(256), 0, s, P, states);
-}
-
-// the projective slices of one aligner that share clouds and finder parameters: ONE z-buffer pass, ONE step launch
-void launch_proj_step_fused(const SliceDev* slices, const ProblemDev* const* probs, int nslices, ProblemState* states, int K,
-                            int max_nm, hipStream_t s, const CtlParams* init_C, const InitInline* init_inl, ProblemDev* probs_base) {
-  if (K <= 0 || max_nm <= 0 || nslices <= 0 || nslices > 4) return;
-  SlicePack P;
-  for (int z = 0; z < 4; ++z) {
-    P.s[z]     = slices[z < nslices ? z : 0];
-    P.probs[z] = probs[z < nslices ? z : 0];
-  }
-  dim3 grid(icp_step_blocks(max_nm), K);
-  if (P.s[0].fc.pub && init_C && init_inl && probs_base) {  // the first iteration of a compute() with the prologue inside
-    hipLaunchKernelGGL(k_proj_zbuf_fz_init, dim3(grid.x + 1, K), dim3(256), 0, s, P.s[0], *init_C, *init_inl, probs_base, states);
-    hipLaunchKernelGGL(k_icp_step_proj_fused<true>, grid, dim3(256), 0, s, P, nslices, states);
-    return;
-  }
-  if (P.s[0].fc.pub) {  // fused control steps
-    if (P.s[0].fc.prior_mask)
-      hipLaunchKernelGGL(k_proj_zbuf_fz<true>, grid, dim3(256), 0, s, P, nslices, states);
-    else
-      hipLaunchKernelGGL(k_proj_zbuf_fz<false>, grid, dim3(256), 0, s, P, nslices, states);
-    hipLaunchKernelGGL(k_icp_step_proj_fused<true>, grid, dim3(256), 0, s, P, nslices, states);
-    return;
-  }
-  hipLaunchKernelGGL(k_proj_zbuf, grid, dim3(256), 0, s, P.s[0], P.probs[0], states);
-  hipLaunchKernelGGL(k_icp_step_proj_fused<false>, grid, dim3(256), 0, s, P, nslices, states);
-}
-
-// the correspondence records of projective slice S after a compute(): the z-buffer of the last executed pass is rebuilt in
-// buffer 0 of the slice that owns the association (S0; once per owner: `rebuild`), then read by k_proj_records
-void launch_proj_records(const SliceDev& S0, const SliceDev& S, const ProblemDev* probs0, const ProblemDev* probs,
-                         ProblemState* states, int K, int max_nm, bool rebuild, hipStream_t s) {
-  if (K <= 0 || max_nm <= 0 || !S0.zbuf) return;
-  dim3 grid(icp_step_blocks(max_nm), K);
-  if (rebuild) {
-    (void) hipMemsetAsync(S0.zbuf, 0xff, (size_t) K * S0.rows * S0.cols * sizeof(unsigned long long), s);
-    hipLaunchKernelGGL(k_proj_zbuf_last, grid, dim3(256), 0, s, S0, probs0, states);
-  }
-  hipLaunchKernelGGL(k_proj_records, grid, dim3(256), 0, s, S0, S, probs, (const ProblemState*) states);
-}
-
-bool make_init_inline(const CtlParams& C, const ProblemDev* probs_host, const float* guesses_host, int tsize, InitInline* inl) {
-  *inl = InitInline{};
-  if (C.K != 1) return false;
-  inl->use = 1;  // (read on the host, sent with the launch)
-  for (int i = 0; i < 12; ++i) inl->guess[i] = i < tsize ? guesses_host[i] : 0.f;
-  for (int sl = 0; sl < C.nslices && sl < SRRG2_MAX_SLICES; ++sl) inl->pd[sl] = probs_host[sl];
-  return true;
-}
-void launch_icp_init(const CtlParams& C, const ProblemDev* probs_host, ProblemDev* probs, ProblemState* states,
-                     const float* guesses_host, int tsize, hipStream_t s, bool pairs) {
-  InitInline inl{};
-  (void) make_init_inline(C, probs_host, guesses_host, tsize, &inl);
-  if (pairs)
-    hipLaunchKernelGGL(k_icp_init_pairs, dim3(C.nprob > 0 ? C.nprob : C.K), dim3(64), 0, s, C, probs_host, probs, states, guesses_host,
-                       tsize, inl);
-  else
-    hipLaunchKernelGGL(k_icp_init, dim3(C.nprob > 0 ? C.nprob : C.K), dim3(64), 0, s, C, probs_host, probs, states, guesses_host,
-                       tsize, inl);
-}
-void launch_icp_control(const CtlParams& C, ProblemState* states, srrg2_iteration_stats* stats, hipStream_t s) {
-  hipLaunchKernelGGL(k_icp_control, dim3(C.nprob > 0 ? C.nprob : C.K), dim3(256), 0, s, C, states, stats);
-}
-void launch_icp_small(int dim, bool plane, const SliceDev& S, const CtlParams& C, const ProblemDev* probs, ProblemState* states,
-                      srrg2_iteration_stats* stats, ProblemOut* outs_host, srrg2_iteration_stats* stats_host, hipStream_t s) {
-  if (C.K <= 0) return;
-  if (dim == 3) {
-    if (plane)
-      hipLaunchKernelGGL((k_icp_small<3, true>), dim3(C.K), dim3(512), 0, s, S, C, probs, states, stats, outs_host, stats_host);
-    else
-      hipLaunchKernelGGL((k_icp_small<3, false>), dim3(C.K), dim3(512), 0, s, S, C, probs, states, stats, outs_host, stats_host);
-  } else {
-    if (plane)
-      hipLaunchKernelGGL((k_icp_small<2, true>), dim3(C.K), dim3(512), 0, s, S, C, probs, states, stats, outs_host, stats_host);
-    else
-      hipLaunchKernelGGL((k_icp_small<2, false>), dim3(C.K), dim3(512), 0, s, S, C, probs, states, stats, outs_host, stats_host);
-  }
-}
-
-// pair batches (srrg2_align_pairs): the launchers above with the table of the problems' own grids
-// (INST: the instantiation for <dim, plane> and the kernel's remaining template arguments)
-#define PAIRS_LAUNCH(INST, GRID, BLOCK, ...)                                      \
-  do {                                                                            \
-    if (dim == 3) {                                                               \
-      if (plane)                                                                  \
-        hipLaunchKernelGGL((INST(3, true)), GRID, BLOCK, 0, s, S, grids, __VA_ARGS__);  \
-      else                                                                        \
-        hipLaunchKernelGGL((INST(3, false)), GRID, BLOCK, 0, s, S, grids, __VA_ARGS__); \
-    } else {                                                                      \
-      if (plane)                                                                  \
-        hipLaunchKernelGGL((INST(2, true)), GRID, BLOCK, 0, s, S, grids, __VA_ARGS__);  \
-      else                                                                        \
-        hipLaunchKernelGGL((INST(2, false)), GRID, BLOCK, 0, s, S, grids, __VA_ARGS__); \
-    }                                                                             \
-  } while (0)
-void launch_icp_step_pairs(int dim, bool plane, const SliceDev& S, const GridDev* grids, const ProblemDev* probs,
-                           ProblemState* states, int K, int max_nm, hipStream_t s) {
-  if (K <= 0 || max_nm <= 0) return;
-  const dim3 grid((max_nm + 255) / 256, K);
-#define INST(D, P) k_icp_step_pairs<D, P>
-  PAIRS_LAUNCH(INST, grid, dim3(256), probs, states);
-#undef INST
-}
-void launch_icp_step_fast_pairs(int dim, bool plane, const SliceDev& S, const GridDev* grids, const ProblemDev* probs,
-                                ProblemState* states, int K, int max_nm, int ppt, bool gather, hipStream_t s) {
-  if (K <= 0 || max_nm <= 0) return;
-  const int p = ppt >= 2 ? 2 : 1;  // (two points per thread from 64 alignments per launch on: run_compute's fast_ppt_of)
-  const dim3 grid((max_nm + 256 * p - 1) / (256 * p), K);
-#define INST_2G(D, P) k_icp_step_fast_pairs<D, P, 2, true>
-#define INST_2N(D, P) k_icp_step_fast_pairs<D, P, 2, false>
-#define INST_1G(D, P) k_icp_step_fast_pairs<D, P, 1, true>
-#define INST_1N(D, P) k_icp_step_fast_pairs<D, P, 1, false>
-  if (p == 2) {
-    if (gather)
-      PAIRS_LAUNCH(INST_2G, grid, dim3(256), probs, states);
-    else
-      PAIRS_LAUNCH(INST_2N, grid, dim3(256), probs, states);
-  } else {
-    if (gather)
-      PAIRS_LAUNCH(INST_1G, grid, dim3(256), probs, states);
-    else
-      PAIRS_LAUNCH(INST_1N, grid, dim3(256), probs, states);
-  }
-#undef INST_2G
-#undef INST_2N
-#undef INST_1G
-#undef INST_1N
-}
-void launch_icp_small_pairs(int dim, bool plane, const SliceDev& S, const GridDev* grids, const CtlParams& C, const ProblemDev* probs,
-                            ProblemState* states, srrg2_iteration_stats* stats, ProblemOut* outs_host,
-                            srrg2_iteration_stats* stats_host, hipStream_t s) {
-  if (C.K <= 0) return;
-#define INST(D, P) k_icp_small_pairs<D, P>
-  PAIRS_LAUNCH(INST, dim3(C.K), dim3(512), C, probs, states, stats, outs_host, stats_host);
-#undef INST
-}
-#undef PAIRS_LAUNCH
+namespace srrg2amd {  // (the kernel symbols k_icp_final_wave* carry this namespace)
 // The LAST control step of a compute() with fused control steps, on one wave (wave_control) with the post / finalize steps
 // behind it: the 256-thread k_icp_control_final stages the 3.4 KB state through LDS around a 238-register body; this one reads
 // the record + the slot sets, runs the lane-distributed step and finalizes from what that step left in its registers
@@ -6110,49 +5517,479 @@ __global__ __launch_bounds__(64) void k_icp_final_wave_pack(SlicePack P, int ns,
                                                              srrg2_iteration_stats* __restrict__ stats_host, int with_post) {
   final_wave_body<6, 4, PRIORS>(*P.s[0].fc.ctl, P.s, ns, states, stats, outs_host, stats_host, with_post);
 }
-void launch_icp_final_wave(const CtlParams& C, const SliceDev& S, ProblemState* states, srrg2_iteration_stats* stats,
-                           ProblemOut* outs_host, srrg2_iteration_stats* stats_host, bool with_post, hipStream_t s) {
-  const dim3 grid(C.nprob > 0 ? C.nprob : C.K);
-#define FINAL_WAVE_LAUNCH(D_, PRIORS_) \
-  hipLaunchKernelGGL((k_icp_final_wave<D_, PRIORS_>), grid, dim3(64), 0, s, C, S, states, stats, outs_host, stats_host, with_post ? 1 : 0)
-  if (C.variable_kind == SRRG2_SE2_RIGHT) {
-    if (S.fc.prior_mask)
-      FINAL_WAVE_LAUNCH(3, true);
-    else
-      FINAL_WAVE_LAUNCH(3, false);
-  } else {
-    if (S.fc.prior_mask)
-      FINAL_WAVE_LAUNCH(6, true);
-    else
-      FINAL_WAVE_LAUNCH(6, false);
+}  // namespace srrg2amd
+
+// ============================================================================================
+// Small alignments (laser scans, landmark maps: up to ~1000 moving points).  With one launch per pass such a compute()
+// is ~24 launch floors and little else (C1: 0.33 ms on the GPU against 0.66 ms on one CPU core; 0.23 ms here).  ONE
+// workgroup owns the problem for the whole compute(): the state and the sums live in LDS, the passes loop over the
+// problem's tiles, thread 0 runs the control step between them -- the same per-point and control code as the
+// launch-per-pass path, so the same bits.  A batch of small problems runs one workgroup per problem.
+// ============================================================================================
+// (TWIN: k_icp_small_pairs below repeats this body statement for statement -- a change here is a change there; the pair-batch tests
+// compare the two bit for bit, tests/test_gpu_align_pairs.py)
+template <int DIM, bool PLANE>
+__global__ __launch_bounds__(512) void k_icp_small(SliceDev S, CtlParams C, const ProblemDev* __restrict__ probs,
+                                                   ProblemState* __restrict__ states, srrg2_iteration_stats* __restrict__ stats,
+                                                   ProblemOut* __restrict__ outs_host,
+                                                   srrg2_iteration_stats* __restrict__ stats_host) {
+  constexpr int NW = 8;  // (16 waves would cap the registers at 128 per lane: the SE(3) control step spills, measured slower)
+  constexpr int D  = DIM == 3 ? 6 : 3;
+  const int prob   = blockIdx.x;
+  __shared__ ProblemState sst;
+  __shared__ long long sums[SRRG2_MAX_SLICES][ACC_N];
+  __shared__ double scaled[SRRG2_MAX_SLICES][ACC_N];
+  state_to_lds(&sst, &states[prob]);
+  __syncthreads();
+  const ProblemDev pd = probs[prob];
+  const int ntiles    = (pd.nm + NW * 64 - 1) / (NW * 64);
+  const int nrun      = C.params.enable_inlier_only_runs ? 2 : 1;
+  for (int run = 0; run < nrun; ++run) {
+    for (int it = 0; it < C.params.max_iterations; ++it) {
+      if (sst.done || sst.finished) break;  // (uniform: LDS)
+      if (threadIdx.x < ACC_N) sums[S.slice_idx][threadIdx.x] = 0;
+      __syncthreads();
+      for (int tile = 0; tile < ntiles; ++tile) {
+        StepView sv;
+        step_view_of_state(S, &sst, sv);
+        icp_step_body<DIM, PLANE, NW>(S, pd, sv, prob, tile, ntiles, C.K, sums[S.slice_idx]);
+        __syncthreads();  // (the body's shared scratch is reused by the next tile)
+      }
+      if (threadIdx.x < ACC_N)
+        scaled[S.slice_idx][threadIdx.x] = (double) sums[S.slice_idx][threadIdx.x] * dm::pow2(-sst.kexp[S.slice_idx]);
+      __syncthreads();
+      if (threadIdx.x == 0) control_body<D>(C, &sst, stats, prob, sums, scaled);
+      __syncthreads();
+    }
+    if (run == 0 && nrun == 2) {  // multi_aligner_impl.cpp:75-85, then the inlier-only run
+      if (threadIdx.x == 0) icp_post_one(C, &sst, stats, prob);
+      __syncthreads();
+    }
   }
-#undef FINAL_WAVE_LAUNCH
+  __threadfence();  // (the statistics thread 0 wrote are read back by the whole workgroup below)
+  __syncthreads();
+  icp_finalize_block(C, &sst, stats, outs_host, stats_host, prob, nrun == 1);
+  __syncthreads();
+  state_from_lds(&states[prob], &sst);
 }
-void launch_icp_final_wave_pack(const SliceDev* slices, const ProblemDev* const* probs, int nslices, ProblemState* states,
-                                srrg2_iteration_stats* stats, ProblemOut* outs_host, srrg2_iteration_stats* stats_host,
-                                bool with_post, hipStream_t s) {
-  if (nslices <= 0 || nslices > 4) return;
+// ... of a pair batch: the problem's own grid (k_icp_step_pairs).  The body is k_icp_small's, statement for statement: moved into a
+// shared function, k_icp_small itself came out with another register count (DESIGN.md section 5: existing kernels stay as they are).
+template <int DIM, bool PLANE>
+__global__ __launch_bounds__(512) void k_icp_small_pairs(SliceDev S, const GridDev* __restrict__ grids, CtlParams C,
+                                                         const ProblemDev* __restrict__ probs, ProblemState* __restrict__ states,
+                                                         srrg2_iteration_stats* __restrict__ stats, ProblemOut* __restrict__ outs_host,
+                                                         srrg2_iteration_stats* __restrict__ stats_host) {
+  S.grid = grids[blockIdx.x];
+  constexpr int NW = 8;  // (16 waves would cap the registers at 128 per lane: the SE(3) control step spills, measured slower)
+  constexpr int D  = DIM == 3 ? 6 : 3;
+  const int prob   = blockIdx.x;
+  __shared__ ProblemState sst;
+  __shared__ long long sums[SRRG2_MAX_SLICES][ACC_N];
+  __shared__ double scaled[SRRG2_MAX_SLICES][ACC_N];
+  state_to_lds(&sst, &states[prob]);
+  __syncthreads();
+  const ProblemDev pd = probs[prob];
+  const int ntiles    = (pd.nm + NW * 64 - 1) / (NW * 64);
+  const int nrun      = C.params.enable_inlier_only_runs ? 2 : 1;
+  for (int run = 0; run < nrun; ++run) {
+    for (int it = 0; it < C.params.max_iterations; ++it) {
+      if (sst.done || sst.finished) break;  // (uniform: LDS)
+      if (threadIdx.x < ACC_N) sums[S.slice_idx][threadIdx.x] = 0;
+      __syncthreads();
+      for (int tile = 0; tile < ntiles; ++tile) {
+        StepView sv;
+        step_view_of_state(S, &sst, sv);
+        icp_step_body<DIM, PLANE, NW>(S, pd, sv, prob, tile, ntiles, C.K, sums[S.slice_idx]);
+        __syncthreads();  // (the body's shared scratch is reused by the next tile)
+      }
+      if (threadIdx.x < ACC_N)
+        scaled[S.slice_idx][threadIdx.x] = (double) sums[S.slice_idx][threadIdx.x] * dm::pow2(-sst.kexp[S.slice_idx]);
+      __syncthreads();
+      if (threadIdx.x == 0) control_body<D>(C, &sst, stats, prob, sums, scaled);
+      __syncthreads();
+    }
+    if (run == 0 && nrun == 2) {  // multi_aligner_impl.cpp:75-85, then the inlier-only run
+      if (threadIdx.x == 0) icp_post_one(C, &sst, stats, prob);
+      __syncthreads();
+    }
+  }
+  __threadfence();  // (the statistics thread 0 wrote are read back by the whole workgroup below)
+  __syncthreads();
+  icp_finalize_block(C, &sst, stats, outs_host, stats_host, prob, nrun == 1);
+  __syncthreads();
+  state_from_lds(&states[prob], &sst);
+}
+
+// ============================================================================================
+// launchers
+// ============================================================================================
+namespace srrg2amd {
+
+// The runtime values that choose a kernel instantiation become compile-time constants HERE, and nowhere else: with_value
+// calls the generic lambda f with std::integral_constant<.., A> if `first` holds and with <.., B> if not, with_dim_plane does
+// that for the pair (dim, plane) every ICP kernel is instantiated for.  Both inline to the launch they wrap (a single
+// alignment is launch-bound), and a lambda names only what exists: no instantiation that no path launches.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <auto A, auto B, class F>
+static __forceinline__ void with_value(bool first, F&& f) {
+  if (first)
+    f(std::integral_constant<decltype(A), A>{});
+  else
+    f(std::integral_constant<decltype(B), B>{});
+}
+template <class F>
+static __forceinline__ void with_dim_plane(int dim, bool plane, F&& f) {
+  with_value<3, 2>(dim == 3, [&](auto D) { with_value<true, false>(plane, [&](auto P) { f(D, P); }); });
+}
+
+// the problems of one control launch (CtlParams::nprob = 0: all K)
+static inline int ctl_problems(const CtlParams& C) {
+  return C.nprob > 0 ? C.nprob : C.K;
+}
+
+// up to four projective slices for one launch (the unused slots repeat slot 0)
+static SlicePack make_slice_pack(const SliceDev* slices, const ProblemDev* const* probs, int nslices) {
   SlicePack P;
   for (int z = 0; z < 4; ++z) {
     P.s[z]     = slices[z < nslices ? z : 0];
     P.probs[z] = probs[z < nslices ? z : 0];
   }
-  if (P.s[0].fc.prior_mask)
-    hipLaunchKernelGGL(k_icp_final_wave_pack<true>, dim3(1), dim3(64), 0, s, P, nslices, states, stats, outs_host, stats_host, with_post ? 1 : 0);
+  return P;
+}
+
+int icp_step_blocks(int max_nm) {
+  return (max_nm + 255) / 256;  // one moving point per thread
+}
+
+int icp_queue_blocks(int max_nm, int K) {
+  // waves that share the deferred searches of one problem: up to 4096 for a single alignment, fewer per problem in a batch
+  int b = icp_step_blocks(max_nm);
+  int cap = K <= 1 ? 1024 : (K <= 8 ? 256 : 64);
+  return b < cap ? b : cap;
+}
+
+static void launch_icp_queue(int dim, bool plane, const SliceDev& S, const ProblemDev* probs, ProblemState* states, int K,
+                             int max_nm, hipStream_t s) {
+  const dim3 qgrid(icp_queue_blocks(max_nm, K), K);
+  with_dim_plane(dim, plane, [&](auto D, auto P) {
+    hipLaunchKernelGGL((k_icp_step_queue<D(), P()>), qgrid, dim3(256), 0, s, S, probs, states);
+  });
+}
+
+void launch_icp_step(int dim, bool plane, const SliceDev& S, const ProblemDev* probs, ProblemState* states, int K,
+                     int max_nm, hipStream_t s, const CtlParams* init_C, const InitInline* init_inl) {
+  if (K <= 0) return;
+  const int tiles = icp_step_blocks(max_nm);
+  if (S.fc.pub && init_C) {  // the first pass of a single alignment with compute()'s prologue inside (even for an empty cloud)
+    const dim3 fgrid(K, tiles + 1);  // (+ the workgroup that writes the rest of the prologue)
+    ProblemDev* pw = const_cast<ProblemDev*>(probs);
+    with_dim_plane(dim, plane, [&](auto D, auto P) {
+      hipLaunchKernelGGL((k_icp_step_fused_init<D(), P()>), fgrid, dim3(256), 0, s, S, *init_C, *init_inl, pw, states);
+    });
+    return;
+  }
+  if (max_nm <= 0) return;
+  if (S.fc.pub) {  // fused control steps: the record instead of ProblemState, no deferred-search queue
+    const dim3 fgrid(K, tiles);
+    with_value<true, false>(S.fc.prior_mask != 0, [&](auto PRIORS) {
+      with_dim_plane(dim, plane, [&](auto D, auto P) {
+        hipLaunchKernelGGL((k_icp_step_fused<D(), P(), PRIORS()>), fgrid, dim3(256), 0, s, S, probs, states);
+      });
+    });
+    return;
+  }
+  const dim3 grid(tiles, K);
+  with_dim_plane(dim, plane, [&](auto D, auto P) {
+    hipLaunchKernelGGL((k_icp_step<D(), P()>), grid, dim3(256), 0, s, S, probs, states);
+  });
+  if (S.queue) launch_icp_queue(dim, plane, S, probs, states, K, max_nm, s);
+}
+
+// the counters of an instrumented build (tools/pass_timeline.py, cnl_stats.py, tile_stats.py): copied to `out` if given,
+// then zeroed if `reset`
+#if defined(SRRG2_PASS_TIMELINE) || defined(SRRG2_CNL_STATS) || defined(SRRG2_TILE_STATS)
+template <size_t N>
+static int debug_counters(unsigned long long (&counters)[N], unsigned long long* out, int reset) {
+  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(counters), sizeof(counters)) != hipSuccess) return -1;
+  if (reset) {
+    static unsigned long long zero[N];
+    if (hipMemcpyToSymbol(HIP_SYMBOL(counters), zero, sizeof(zero)) != hipSuccess) return -1;
+  }
+  return 0;
+}
+#endif
+#ifdef SRRG2_PASS_TIMELINE
+extern "C" int srrg2_amd_debug_pass_timeline(unsigned long long* out, int reset) {
+  return debug_counters(g_pass_ts, out, reset);
+}
+#endif
+#ifdef SRRG2_CNL_STATS
+extern "C" int srrg2_amd_debug_cnl_stats(unsigned long long* out, int reset) {
+  return debug_counters(g_cnl_stats, out, reset);
+}
+#endif
+#ifdef SRRG2_TILE_STATS
+extern "C" int srrg2_amd_debug_tile_stats(unsigned long long* out, int reset) {
+  return debug_counters(g_tile_stats, out, reset);
+}
+#endif
+
+// the search pass of a batch with wave tiles in LDS (cap: candidates per wave tile, 416: four workgroups per CU, 504: three)
+void launch_icp_step_tile(int dim, bool plane, const SliceDev& S, const ProblemDev* probs, ProblemState* states, int K,
+                          int max_nm, int cap, hipStream_t s) {
+  if (K <= 0 || max_nm <= 0) return;
+  const dim3 grid(icp_step_blocks(max_nm), K);
+  with_dim_plane(dim, plane, [&](auto D, auto P) {
+    with_value<504, 416>(cap > 450, [&](auto CAP) {
+      hipLaunchKernelGGL((k_icp_step_tile<D(), P(), CAP()>), grid, dim3(256), 0, s, S, probs, states);
+    });
+  });
+}
+
+// the search pass over the cell neighbour lists of the grid (S.grid.list_R > 0); team = lanes per moving point (1 or 4)
+void launch_icp_step_cnl(int dim, bool plane, const SliceDev& S, const GridLists& GL, const ProblemDev* probs,
+                         ProblemState* states, int K, int max_nm, int team, hipStream_t s, const CtlParams* init_C,
+                         const InitInline* init_inl, const InitBatch* init_bat) {
+  if (K <= 0) return;
+  ProblemDev* pw = const_cast<ProblemDev*>(probs);  // (a pass with the prologue inside writes the problems)
+  auto tiles_of = [&](auto TEAM) { return (max_nm * TEAM() + 255) / 256; };
+  if (S.fc.pub && init_C && init_bat) {  // a part of a batch (K <= INIT_BATCH_MAX alignments) with the prologue in its first pass
+    with_value<4, 1>(team >= 4, [&](auto TEAM) {
+      const dim3 grid(K, tiles_of(TEAM) + 1);
+      with_dim_plane(dim, plane, [&](auto D, auto P) {
+        hipLaunchKernelGGL((k_icp_step_cnl_init_batch<D(), P(), TEAM()>), grid, dim3(256), 0, s, S, GL, *init_C, *init_bat, pw,
+                           states);
+      });
+    });
+    return;
+  }
+  if (S.fc.pub && init_C) {  // the first pass of a single alignment with compute()'s prologue inside (even for an empty cloud)
+    with_value<4, 1>(team >= 4, [&](auto TEAM) {
+      const dim3 grid(K, tiles_of(TEAM) + 1);  // (+ the workgroup that writes the rest of the prologue)
+      with_dim_plane(dim, plane, [&](auto D, auto P) {
+        hipLaunchKernelGGL((k_icp_step_cnl_init<D(), P(), TEAM()>), grid, dim3(256), 0, s, S, GL, *init_C, *init_inl, pw,
+                           states);
+      });
+    });
+    return;
+  }
+  if (max_nm <= 0) return;
+  auto pass = [&](auto FUSED) __attribute__((always_inline)) {
+    with_value<4, 1>(team >= 4, [&](auto TEAM) {
+      const dim3 grid = FUSED() ? dim3(K, tiles_of(TEAM)) : dim3(tiles_of(TEAM), K);  // (fused: x = problem, y = tile)
+      with_dim_plane(dim, plane, [&](auto D, auto P) {
+        hipLaunchKernelGGL((k_icp_step_cnl<D(), P(), TEAM(), FUSED()>), grid, dim3(256), 0, s, S, GL, probs, states);
+      });
+    });
+  };
+  // (fused control steps -- S.fc.pub: the instantiations that read the state from the published record)
+  if (S.fc.pub && S.fc.prior_mask)  // (... of an aligner with prior slices: the control wave linearises them, wave_prior)
+    pass(int_c<2>{});
+  else if (S.fc.pub)
+    pass(int_c<1>{});
   else
-    hipLaunchKernelGGL(k_icp_final_wave_pack<false>, dim3(1), dim3(64), 0, s, P, nslices, states, stats, outs_host, stats_host, with_post ? 1 : 0);
+    pass(int_c<0>{});
+}
+
+// the pass of a converged alignment; ppt = moving points per thread
+void launch_icp_step_fast(int dim, bool plane, const SliceDev& S, const ProblemDev* probs, ProblemState* states, int K,
+                          int max_nm, int ppt, bool gather, hipStream_t s) {
+  if (K <= 0 || max_nm <= 0) return;
+  // (FUSED: 0 = control launches, 1 = fused control steps, 2 = ... of an aligner with prior slices)
+  auto pass = [&](auto PPT, auto GATHER, auto FUSED) __attribute__((always_inline)) {
+    const int tiles = (max_nm + 256 * PPT() - 1) / (256 * PPT());
+    const dim3 grid = FUSED() ? dim3(K, tiles) : dim3(tiles, K);  // (fused: x = problem, y = tile)
+    with_dim_plane(dim, plane, [&](auto D, auto P) {
+      hipLaunchKernelGGL((k_icp_step_fast<D(), P(), PPT(), GATHER(), FUSED()>), grid, dim3(256), 0, s, S, probs, states);
+    });
+  };
+  if (S.fc.pub && S.fc.prior_mask) {  // ... of an aligner with prior slices (one point per thread: the instantiations that exist)
+    with_value<true, false>(gather, [&](auto G) { pass(int_c<1>{}, G, int_c<2>{}); });
+    return;
+  }
+  if (S.fc.pub) {  // fused control steps (one or two points per thread)
+    with_value<true, false>(gather, [&](auto G) {
+      with_value<2, 1>(ppt >= 2, [&](auto PPT) { pass(PPT, G, int_c<1>{}); });
+    });
+    return;
+  }
+  with_value<true, false>(gather, [&](auto G) {
+    if (ppt >= 4)
+      pass(int_c<4>{}, G, int_c<0>{});
+    else
+      with_value<2, 1>(ppt >= 2, [&](auto PPT) { pass(PPT, G, int_c<0>{}); });
+  });
+  if (S.queue) launch_icp_queue(dim, plane, S, probs, states, K, max_nm, s);
+}
+
+void launch_icp_outputs(int dim, bool plane, const SliceDev& S, const ProblemDev* probs, const ProblemState* states, int K,
+                        int max_nm, hipStream_t s) {
+  if (K <= 0 || max_nm <= 0) return;
+  const dim3 grid(icp_step_blocks(max_nm), K);
+  with_dim_plane(dim, plane, [&](auto D, auto P) {
+    hipLaunchKernelGGL((k_icp_outputs<D(), P()>), grid, dim3(256), 0, s, S, probs, states);
+  });
+}
+
+void launch_corr_step(int dim, bool plane, const SliceDev& S, const ProblemDev* probs, ProblemState* states, int K,
+                      int max_ncorr, hipStream_t s) {
+  if (K <= 0 || max_ncorr <= 0) return;
+  const dim3 grid((max_ncorr + 255) / 256, K);
+  with_dim_plane(dim, plane, [&](auto D, auto P) {
+    hipLaunchKernelGGL((k_icp_step_corr<D(), P()>), grid, dim3(256), 0, s, S, probs, states);
+  });
+}
+
+void launch_proj_step(bool repro, const SliceDev& S, const ProblemDev* probs, ProblemState* states, int K, int max_nm,
+                      hipStream_t s) {
+  if (K <= 0 || max_nm <= 0) return;
+  const dim3 grid(icp_step_blocks(max_nm), K);
+  // (no memset: the z-buffers ping-pong, k_icp_step_proj resets the one the next pass will use)
+  hipLaunchKernelGGL(k_proj_zbuf, grid, dim3(256), 0, s, S, probs, states);
+  with_value<true, false>(repro, [&](auto REPRO) {
+    hipLaunchKernelGGL((k_icp_step_proj<REPRO()>), grid, dim3(256), 0, s, S, probs, states);
+  });
+}
+
+void launch_proj_step_pack(const SliceDev* slices, const ProblemDev* const* probs, int nslices, ProblemState* states, int K,
+                           int max_nm, hipStream_t s) {
+  if (K <= 0 || max_nm <= 0 || nslices <= 0 || nslices > 4) return;
+  const SlicePack P = make_slice_pack(slices, probs, nslices);
+  const dim3 grid(icp_step_blocks(max_nm), K, nslices);
+  hipLaunchKernelGGL(k_proj_zbuf_pack, grid, dim3(256), 0, s, P, states);
+  hipLaunchKernelGGL(k_icp_step_proj_pack, grid, dim3(256), 0, s, P, states);
+}
+
+// the projective slices of one aligner that share clouds and finder parameters: ONE z-buffer pass, ONE step launch
+void launch_proj_step_fused(const SliceDev* slices, const ProblemDev* const* probs, int nslices, ProblemState* states, int K,
+                            int max_nm, hipStream_t s, const CtlParams* init_C, const InitInline* init_inl, ProblemDev* probs_base) {
+  if (K <= 0 || max_nm <= 0 || nslices <= 0 || nslices > 4) return;
+  const SlicePack P = make_slice_pack(slices, probs, nslices);
+  const dim3 grid(icp_step_blocks(max_nm), K);
+  if (P.s[0].fc.pub && init_C && init_inl && probs_base) {  // the first iteration of a compute() with the prologue inside
+    hipLaunchKernelGGL(k_proj_zbuf_fz_init, dim3(grid.x + 1, K), dim3(256), 0, s, P.s[0], *init_C, *init_inl, probs_base, states);
+    hipLaunchKernelGGL(k_icp_step_proj_fused<true>, grid, dim3(256), 0, s, P, nslices, states);
+    return;
+  }
+  if (P.s[0].fc.pub) {  // fused control steps
+    with_value<true, false>(P.s[0].fc.prior_mask != 0, [&](auto PRIORS) {
+      hipLaunchKernelGGL(k_proj_zbuf_fz<PRIORS()>, grid, dim3(256), 0, s, P, nslices, states);
+    });
+    hipLaunchKernelGGL(k_icp_step_proj_fused<true>, grid, dim3(256), 0, s, P, nslices, states);
+    return;
+  }
+  hipLaunchKernelGGL(k_proj_zbuf, grid, dim3(256), 0, s, P.s[0], P.probs[0], states);
+  hipLaunchKernelGGL(k_icp_step_proj_fused<false>, grid, dim3(256), 0, s, P, nslices, states);
+}
+
+// the correspondence records of projective slice S after a compute(): the z-buffer of the last executed pass is rebuilt in
+// buffer 0 of the slice that owns the association (S0; once per owner: `rebuild`), then read by k_proj_records
+void launch_proj_records(const SliceDev& S0, const SliceDev& S, const ProblemDev* probs0, const ProblemDev* probs,
+                         ProblemState* states, int K, int max_nm, bool rebuild, hipStream_t s) {
+  if (K <= 0 || max_nm <= 0 || !S0.zbuf) return;
+  dim3 grid(icp_step_blocks(max_nm), K);
+  if (rebuild) {
+    (void) hipMemsetAsync(S0.zbuf, 0xff, (size_t) K * S0.rows * S0.cols * sizeof(unsigned long long), s);
+    hipLaunchKernelGGL(k_proj_zbuf_last, grid, dim3(256), 0, s, S0, probs0, states);
+  }
+  hipLaunchKernelGGL(k_proj_records, grid, dim3(256), 0, s, S0, S, probs, (const ProblemState*) states);
+}
+
+bool make_init_inline(const CtlParams& C, const ProblemDev* probs_host, const float* guesses_host, int tsize, InitInline* inl) {
+  *inl = InitInline{};
+  if (C.K != 1) return false;
+  inl->use = 1;  // (read on the host, sent with the launch)
+  for (int i = 0; i < 12; ++i) inl->guess[i] = i < tsize ? guesses_host[i] : 0.f;
+  for (int sl = 0; sl < C.nslices && sl < SRRG2_MAX_SLICES; ++sl) inl->pd[sl] = probs_host[sl];
+  return true;
+}
+void launch_icp_init(const CtlParams& C, const ProblemDev* probs_host, ProblemDev* probs, ProblemState* states,
+                     const float* guesses_host, int tsize, hipStream_t s, bool pairs) {
+  InitInline inl{};
+  (void) make_init_inline(C, probs_host, guesses_host, tsize, &inl);
+  const dim3 grid(ctl_problems(C));
+  if (pairs)
+    hipLaunchKernelGGL(k_icp_init_pairs, grid, dim3(64), 0, s, C, probs_host, probs, states, guesses_host, tsize, inl);
+  else
+    hipLaunchKernelGGL(k_icp_init, grid, dim3(64), 0, s, C, probs_host, probs, states, guesses_host, tsize, inl);
+}
+void launch_icp_control(const CtlParams& C, ProblemState* states, srrg2_iteration_stats* stats, hipStream_t s) {
+  hipLaunchKernelGGL(k_icp_control, dim3(ctl_problems(C)), dim3(256), 0, s, C, states, stats);
+}
+void launch_icp_small(int dim, bool plane, const SliceDev& S, const CtlParams& C, const ProblemDev* probs, ProblemState* states,
+                      srrg2_iteration_stats* stats, ProblemOut* outs_host, srrg2_iteration_stats* stats_host, hipStream_t s) {
+  if (C.K <= 0) return;
+  with_dim_plane(dim, plane, [&](auto D, auto P) {
+    hipLaunchKernelGGL((k_icp_small<D(), P()>), dim3(C.K), dim3(512), 0, s, S, C, probs, states, stats, outs_host, stats_host);
+  });
+}
+
+// pair batches (srrg2_align_pairs): the launchers above with the table of the problems' own grids
+void launch_icp_step_pairs(int dim, bool plane, const SliceDev& S, const GridDev* grids, const ProblemDev* probs,
+                           ProblemState* states, int K, int max_nm, hipStream_t s) {
+  if (K <= 0 || max_nm <= 0) return;
+  const dim3 grid(icp_step_blocks(max_nm), K);
+  with_dim_plane(dim, plane, [&](auto D, auto P) {
+    hipLaunchKernelGGL((k_icp_step_pairs<D(), P()>), grid, dim3(256), 0, s, S, grids, probs, states);
+  });
+}
+void launch_icp_step_fast_pairs(int dim, bool plane, const SliceDev& S, const GridDev* grids, const ProblemDev* probs,
+                                ProblemState* states, int K, int max_nm, int ppt, bool gather, hipStream_t s) {
+  if (K <= 0 || max_nm <= 0) return;
+  // (two points per thread from 64 alignments per launch on: run_compute's fast_ppt_of)
+  with_value<2, 1>(ppt >= 2, [&](auto PPT) {
+    const dim3 grid((max_nm + 256 * PPT() - 1) / (256 * PPT()), K);
+    with_value<true, false>(gather, [&](auto GATHER) {
+      with_dim_plane(dim, plane, [&](auto D, auto P) {
+        hipLaunchKernelGGL((k_icp_step_fast_pairs<D(), P(), PPT(), GATHER()>), grid, dim3(256), 0, s, S, grids, probs, states);
+      });
+    });
+  });
+}
+void launch_icp_small_pairs(int dim, bool plane, const SliceDev& S, const GridDev* grids, const CtlParams& C, const ProblemDev* probs,
+                            ProblemState* states, srrg2_iteration_stats* stats, ProblemOut* outs_host,
+                            srrg2_iteration_stats* stats_host, hipStream_t s) {
+  if (C.K <= 0) return;
+  with_dim_plane(dim, plane, [&](auto D, auto P) {
+    hipLaunchKernelGGL((k_icp_small_pairs<D(), P()>), dim3(C.K), dim3(512), 0, s, S, grids, C, probs, states, stats, outs_host,
+                       stats_host);
+  });
+}
+
+// the last control step of a compute() with fused control steps, on one wave (final_wave_body)
+void launch_icp_final_wave(const CtlParams& C, const SliceDev& S, ProblemState* states, srrg2_iteration_stats* stats,
+                           ProblemOut* outs_host, srrg2_iteration_stats* stats_host, bool with_post, hipStream_t s) {
+  const dim3 grid(ctl_problems(C));
+  with_value<3, 6>(C.variable_kind == SRRG2_SE2_RIGHT, [&](auto D) {
+    with_value<true, false>(S.fc.prior_mask != 0, [&](auto PRIORS) {
+      hipLaunchKernelGGL((k_icp_final_wave<D(), PRIORS()>), grid, dim3(64), 0, s, C, S, states, stats, outs_host, stats_host,
+                         with_post ? 1 : 0);
+    });
+  });
+}
+void launch_icp_final_wave_pack(const SliceDev* slices, const ProblemDev* const* probs, int nslices, ProblemState* states,
+                                srrg2_iteration_stats* stats, ProblemOut* outs_host, srrg2_iteration_stats* stats_host,
+                                bool with_post, hipStream_t s) {
+  if (nslices <= 0 || nslices > 4) return;
+  const SlicePack P = make_slice_pack(slices, probs, nslices);
+  with_value<true, false>(P.s[0].fc.prior_mask != 0, [&](auto PRIORS) {
+    hipLaunchKernelGGL(k_icp_final_wave_pack<PRIORS()>, dim3(1), dim3(64), 0, s, P, nslices, states, stats, outs_host, stats_host,
+                       with_post ? 1 : 0);
+  });
 }
 void launch_icp_control_final(const CtlParams& C, ProblemState* states, srrg2_iteration_stats* stats, ProblemOut* outs_host,
                                srrg2_iteration_stats* stats_host, bool with_post, hipStream_t s) {
-  hipLaunchKernelGGL(k_icp_control_final, dim3(C.nprob > 0 ? C.nprob : C.K), dim3(256), 0, s, C, states, stats, outs_host, stats_host,
+  hipLaunchKernelGGL(k_icp_control_final, dim3(ctl_problems(C)), dim3(256), 0, s, C, states, stats, outs_host, stats_host,
                      with_post ? 1 : 0);
 }
 void launch_icp_post(const CtlParams& C, ProblemState* states, const srrg2_iteration_stats* stats, hipStream_t s) {
-  hipLaunchKernelGGL(k_icp_post, dim3(C.nprob > 0 ? C.nprob : C.K), dim3(64), 0, s, C, states, stats);
+  hipLaunchKernelGGL(k_icp_post, dim3(ctl_problems(C)), dim3(64), 0, s, C, states, stats);
 }
 void launch_icp_finalize(const CtlParams& C, ProblemState* states, const srrg2_iteration_stats* stats,
                          ProblemOut* outs_host, srrg2_iteration_stats* stats_host, bool with_post, hipStream_t s) {
-  hipLaunchKernelGGL(k_icp_finalize, dim3(C.nprob > 0 ? C.nprob : C.K), dim3(64), 0, s, C, states, stats, outs_host, stats_host, with_post ? 1 : 0);
+  hipLaunchKernelGGL(k_icp_finalize, dim3(ctl_problems(C)), dim3(64), 0, s, C, states, stats, outs_host, stats_host,
+                     with_post ? 1 : 0);
 }
 
 }  // namespace srrg2amd
