@@ -598,7 +598,7 @@ int srrg2_scene_device_arrays(srrg2_scene_h h, const float** coords, const float
  *                  intensity >= 4 and a multiple of 4 (else SRRG2_E_INVALID).  mem: SRRG2_MEM_HOST | SRRG2_MEM_DEVICE.
  *   srrg2_scene_set replaces the content and so drops the features.  A scene that never got features behaves as before.
  *   validity       unchanged: a point is Valid iff its coordinates are finite; an invalid point keeps its features and index.
- *   clip_ball / clip_projective
+ *   clip_ball / clip_projective / clip_scan
  *                  `clipped` receives the features of the points it keeps (clipped[k] = full[global_indices[k]]) and
  *                  the feature presence of `full`.
  *   merge / merge_from_aligner
@@ -643,7 +643,7 @@ int srrg2_scene_global_indices(srrg2_scene_h clipped, int32_t* buf, int* n_inout
  * point; the aligner applies robot_in_sensor itself), normals rotated, global indices, features and their presence.
  *   refused   `clipped` unchanged.  SRRG2_E_INVALID: a null handle, pose or params; full == clipped; different devices or dims;
  *             rows or cols <= 0 or rows*cols beyond int32; !(depth_min > 0) or !(depth_max >= depth_min); fx or fy zero / not
- *             finite; a NaN margin.  SRRG2_E_UNSUPPORTED: scenes of dim 2 (a 2-D field-of-view clipper is not built), K with
+ *             finite; a NaN margin.  SRRG2_E_UNSUPPORTED: scenes of dim 2 (their clipper is srrg2_scene_clip_scan), K with
  *             skew.
  *   status    Ready when `full` is empty, else Successful -- also when nothing is kept (`clipped` is then empty). */
 typedef struct srrg2_projective_clip_params {
@@ -663,6 +663,35 @@ typedef struct srrg2_clip_result {
 void srrg2_clip_default_projective_params(srrg2_projective_clip_params* p);
 int srrg2_scene_clip_projective(srrg2_scene_h full, const float* robot_in_local_map, const srrg2_projective_clip_params* p,
                                 srrg2_scene_h clipped, srrg2_clip_result* out /* may be NULL */);
+
+/* SceneClipper_::compute() with the scan policy, the 2-D twin of the projective one (first principles as well).  Keeps the Valid
+ * points of a 2-D `full` that a planar laser scanner mounted at sensor_in_robot sees from robot_in_local_map:
+ *   r = robot_in_local_map^-1 * p, c = sensor_in_robot^-1 * r, rho = sqrtf(c.x*c.x + c.y*c.y), range_min <= rho <= range_max,
+ *   bearing dm::atan2(c.y, c.x) binned to the nearest beam of angle_min + k*angle_increment, k in [0, num_beams), after at most
+ *   one turn of 2 pi either way (the sector may cross +-pi; a clockwise scanner has a negative increment);
+ *   occlusion_margin < 0: every in-view point is kept (sector only); >= 0: only those with
+ *   rho <= (minimum rho over the in-view points of the beam) + occlusion_margin -- 0 keeps every point that ties for the
+ *   minimum, +inf equals sector only.  DESIGN.md section 4 "Scan clipping" is the arithmetic contract.
+ * Output as clip_ball: the kept points in scene order, in the ROBOT frame (r, bit for bit what clip_ball writes for the same
+ * point), normals rotated, global indices, features and their presence.  srrg2_clip_result.num_in_view: inside the range
+ * interval and the sector.
+ *   refused   `clipped` unchanged.  SRRG2_E_INVALID: a null handle, pose or params; full == clipped; different devices or dims;
+ *             num_beams <= 0; angle_increment zero or not finite; angle_min not finite or |angle_min| > 2 pi;
+ *             |angle_increment| * num_beams beyond 2 pi plus one increment (361 beams over 360 degrees are legal, two turns are
+ *             not; a relative slack of 2^-20 admits increments rounded to float32); !(range_min > 0) or
+ *             !(range_max >= range_min); a NaN margin.  SRRG2_E_UNSUPPORTED: scenes of dim 3 (3-D lidar rings are not built).
+ *   status    Ready when `full` is empty, else Successful -- also when nothing is kept (`clipped` is then empty). */
+typedef struct srrg2_scan_clip_params {
+  double  angle_min, angle_increment;   /* as srrg2_scan_adaptor_params: bearing of beam k = angle_min + k*angle_increment */
+  int32_t num_beams;
+  float   range_min, range_max;         /* accepted range in the SENSOR frame, both inclusive */
+  float   sensor_in_robot[9];           /* SE(2), row-major 3x3 */
+  float   occlusion_margin;             /* < 0: sector only; >= 0: metres behind the nearest point of the beam */
+} srrg2_scan_clip_params;
+/* identity sensor, range 0.05 .. 30 m (the scan adaptor's), margin -1 (sector only); bearings / num_beams (0) are the caller's */
+void srrg2_clip_default_scan_params(srrg2_scan_clip_params* p);
+int srrg2_scene_clip_scan(srrg2_scene_h full, const float* robot_in_local_map /* 3x3 */, const srrg2_scan_clip_params* p,
+                          srrg2_scene_h clipped, srrg2_clip_result* out /* may be NULL */);
 
 /* MergerCorrespondenceHomo_::compute() (S/mapping/merger_correspondence_homo_impl.cpp:11-125).
  * correspondences: fixed_idx = scene point, moving_idx = measurement point, processed in order

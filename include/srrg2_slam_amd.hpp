@@ -423,6 +423,7 @@ private:
 //                               a PointIntensityDescriptor{2,3}f one: descriptor + intensity travel through clip and merge
 //   SceneClipperBall            SceneClipper_<Estimate, Scene>              S/mapping/scene_clipper.h:17-122
 //   SceneClipperProjective      the same interface, projective policy (3-D): what a pinhole camera sees of the scene
+//   SceneClipperScan            the same interface, scan policy (2-D): what a planar laser scanner sees of the scene
 //   MergerCorrespondenceHomo    MergerCorrespondenceHomo_<Estimate, Scene>  S/mapping/merger_correspondence_homo.h
 template <int DIM>
 class Scene {
@@ -535,6 +536,43 @@ public:
     if (!_full || !_clipped) throw std::runtime_error("SceneClipperProjective::compute|scene not set");
     _status = Error;
     check(srrg2_scene_clip_projective(_full->handle(), _robot_in_local_map.data(), &param, _clipped->handle(), &_last));
+    _status = static_cast<Status>(_last.status);
+  }
+  Status status() const { return _status; }
+  const srrg2_clip_result& last() const { return _last; }
+  std::vector<int> globalIndices() const {  // :98-101
+    int n = 0;
+    check(srrg2_scene_global_indices(_clipped->handle(), nullptr, &n));
+    std::vector<int> v((size_t) n);
+    if (n) check(srrg2_scene_global_indices(_clipped->handle(), v.data(), &n));
+    return v;
+  }
+
+private:
+  SceneType* _full    = nullptr;
+  SceneType* _clipped = nullptr;
+  EstimateType _robot_in_local_map = EstimateType::Identity();
+  srrg2_clip_result _last{};
+  Status _status = Error;
+};
+
+// the points of a 2-D scene that a planar laser scanner at sensor_in_robot sees (srrg2_scene_clip_scan): param.angle_min,
+// angle_increment, num_beams, range interval and occlusion_margin are the PARAMs; last() holds the counts of the last compute()
+class SceneClipperScan {
+public:
+  enum Status { Error = 0, Successful = 1, Ready = 2 };  // scene_clipper.h:24-28
+  using EstimateType = Isometry<2>;
+  using SceneType    = Scene<2>;
+  srrg2_scan_clip_params param;
+  SceneClipperScan() { srrg2_clip_default_scan_params(&param); }
+  void setFullScene(SceneType* s) { _full = s; }
+  void setClippedSceneInRobot(SceneType* s) { _clipped = s; }
+  void setRobotInLocalMap(const EstimateType& T) { _robot_in_local_map = T; }
+  void setSensorInRobot(const EstimateType& T) { std::memcpy(param.sensor_in_robot, T.data(), sizeof(param.sensor_in_robot)); }  // :86-89
+  void compute() {
+    if (!_full || !_clipped) throw std::runtime_error("SceneClipperScan::compute|scene not set");
+    _status = Error;
+    check(srrg2_scene_clip_scan(_full->handle(), _robot_in_local_map.data(), &param, _clipped->handle(), &_last));
     _status = static_cast<Status>(_last.status);
   }
   Status status() const { return _status; }

@@ -63,6 +63,11 @@ def lib():
         _LIB.srrg2_clip_default_projective_params.restype = None
         _LIB.srrg2_scene_clip_projective.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(mapping.ProjectiveClipParams),
                                                      C.c_void_p, C.POINTER(mapping.ClipResult)]
+        # srrg2_scene_clip_scan (mapping.SceneClipperScan)
+        _LIB.srrg2_clip_default_scan_params.argtypes = [C.POINTER(mapping.ScanClipParams)]
+        _LIB.srrg2_clip_default_scan_params.restype = None
+        _LIB.srrg2_scene_clip_scan.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(mapping.ScanClipParams), C.c_void_p,
+                                               C.POINTER(mapping.ClipResult)]
     return _LIB
 
 

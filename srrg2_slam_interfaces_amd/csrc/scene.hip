@@ -1,4 +1,4 @@
-// scene.hip -- scene slices kept in HBM between frames: ball and projective clipping, correspondence-based merging
+// scene.hip -- scene slices kept in HBM between frames: ball, projective and scan clipping, correspondence-based merging
 // (SURVEY.md section 8f row 2).  Replaces, behind the C ABI of include/srrg2_slam_amd.h:
 //   MergerCorrespondenceHomo_::compute()   S/mapping/merger_correspondence_homo_impl.cpp:11-125
 //   SceneClipper_::compute() (interface)   S/mapping/scene_clipper.h:17-122
@@ -10,7 +10,7 @@
 // the kernels that move points (k_clip_scatter, merge_one, k_append_scatter) have a feature-carrying instantiation, chosen on the
 // host, so a scene without features runs the code it ran before they existed.  All kernels are one thread per
 // point or correspondence, coalesced, HBM bound: clip = 2 passes over the scene (flag+count, scatter) around an
-// exclusive scan (the projective clip with occlusion: one more in front, the per-pixel depth minimum); merge = one pass over the correspondences + (if the merge target was not reached) flag/scan/scatter
+// exclusive scan (the projective and the scan clip with occlusion: one more in front, the per-pixel depth / per-beam range minimum); merge = one pass over the correspondences + (if the merge target was not reached) flag/scan/scatter
 // of the measurement.  The reference merges sequentially; results are identical because
 //   - a scene point hit by ONE correspondence is independent of all others (the common case: the tracker's
 //     correspondences come through an injective local->global map),
@@ -201,18 +201,135 @@ __global__ void k_pclip_flag(Xf L, Xf S, ProjCam C, const float4* __restrict__ p
   block_add(nview, &counters[1]);
 }
 
+// (shared with the scan clip's k_sclip_scatter: DIM = 2)
+template <bool FEAT, int DIM>
+__device__ __forceinline__ void scatter_kept(const Xf& L, const float4* __restrict__ pts, const float4* __restrict__ nrm, int n,
+                                             const int* __restrict__ offset, float4* __restrict__ out_pts,
+                                             float4* __restrict__ out_nrm, int* __restrict__ gidx, int cap, const Feat& f) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int k = offset[i];
+    if (offset[i + 1] == k || k >= cap) continue;  // not kept / no room yet (as k_clip_scatter: the caller repeats it)
+    out_pts[k] = xform_point(DIM, L, pts[i]);
+    out_nrm[k] = nrm ? rotate_normal(DIM, L, nrm[i]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    gidx[k]    = i;
+    if (FEAT) move_features(f, i, k);
+  }
+}
+
 template <bool FEAT>
 __global__ void k_pclip_scatter(Xf L, const float4* __restrict__ pts, const float4* __restrict__ nrm, int n,
                                 const int* __restrict__ offset, float4* __restrict__ out_pts, float4* __restrict__ out_nrm,
                                 int* __restrict__ gidx, int cap, Feat f) {
+  scatter_kept<FEAT, 3>(L, pts, nrm, n, offset, out_pts, out_nrm, gidx, cap, f);
+}
+
+// ---- scan clip (no reference counterpart; DESIGN.md section 4 "Scan clipping") -------------------------------------------------
+// the 2-D twin of the projective clip: keeps the Valid points a planar laser scanner at sensor_in_robot sees -- inside the range
+// interval and the angular sector of its beams, and -- margin >= 0 -- no further than `margin` behind the nearest point of
+// their beam.
+//   k_sclip_rmin_lds  per beam the minimum range of the in-view points.  A scan has ~10^3 beams, a map 10^5..10^6 points: hundreds
+//                     of points per word, and same-address global atomics serialise (block_add above).  So every workgroup takes
+//                     the minimum in a private LDS table of num_beams words first (ds atomics, no return value) and sends ONE
+//                     global atomicMin per bin it touched.  Positive floats order like their bit patterns (range_min > 0).
+//   k_sclip_rmin      the same straight into global memory: tables beyond SRRG2_SCLIP_LDS_BINS, maps too small to give
+//                     SRRG2_SCLIP_LDS_MIN_WORKGROUPS workgroups their share, and the A/B build -DSRRG2_SCLIP_NO_LDS.
+//                     A minimum does not depend on who took it: both give the same bits.
+//   k_sclip_flag      keep flag per point + the Valid / in-view counts (one atomic per block and count)
+//   k_sclip_scatter   k_pclip_scatter's loop for dim 2: it reads the scan's neighbouring offsets and never computes a bearing
+struct ScanGeom {
+  double angle_min, angle_increment, wrap;  // wrap = copysign(2 pi, angle_increment)
+  float range_min, range_max, margin;
+  int num_beams;
+};
+
+// 8192 bins = 32 KB: four workgroups of 256 threads still share a CU's 160 KB of LDS, and every planar scanner in use
+// (360 .. 2 x 1440 beams) fits several times over
+#ifndef SRRG2_SCLIP_LDS_BINS
+#define SRRG2_SCLIP_LDS_BINS 8192
+#endif
+// points per workgroup and bin under which the table's initialisation and flush outweigh what it saves
+#ifndef SRRG2_SCLIP_POINTS_PER_BIN
+#define SRRG2_SCLIP_POINTS_PER_BIN 4
+#endif
+// ... and the workgroups that rule must leave for the table to pay: with fewer, the few that remain walk their points one
+// float64 atan2 after the other while most of the chip idles (measured, 1081 beams: 11 workgroups 0.067 ms against 0.060 ms
+// of global atomics for the whole clip, 23 workgroups equal, 46 and more ahead)
+#ifndef SRRG2_SCLIP_LDS_MIN_WORKGROUPS
+#define SRRG2_SCLIP_LDS_MIN_WORKGROUPS 20
+#endif
+
+// steps 1-5 of the contract: Valid, r = L p, c = S r, range, beam.  -1: not in view
+__device__ __forceinline__ int sclip_beam(const Xf& L, const Xf& S, const ScanGeom& G, const float4 p, bool& valid, float& rho) {
+  valid = valid_point(2, p);
+  if (!valid) return -1;
+  const float4 c = xform_point(2, S, xform_point(2, L, p));
+  if (!(isfinite(c.x) && isfinite(c.y))) return -1;
+  rho = sqrtf(c.x * c.x + c.y * c.y);
+  if (!(rho >= G.range_min) || !(rho <= G.range_max)) return -1;
+  const double beta = dm::atan2((double) c.y, (double) c.x);
+  const double d    = beta - G.angle_min;
+  double t          = d / G.angle_increment;
+  if (t < -0.5)
+    t = (d + G.wrap) / G.angle_increment;
+  else if (t >= (double) G.num_beams - 0.5)
+    t = (d - G.wrap) / G.angle_increment;
+  const double tf = t + 0.5;
+  if (!(tf >= 0.0) || !(tf < (double) G.num_beams)) return -1;
+  return (int) floor(tf);  // in [0, num_beams)
+}
+
+__global__ void k_sclip_rmin(Xf L, Xf S, ScanGeom G, const float4* __restrict__ pts, int n, unsigned* __restrict__ rmin) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const int k = offset[i];
-    if (offset[i + 1] == k || k >= cap) continue;  // not kept / no room yet (as k_clip_scatter: the caller repeats it)
-    out_pts[k] = xform_point(3, L, pts[i]);
-    out_nrm[k] = nrm ? rotate_normal(3, L, nrm[i]) : make_float4(0.f, 0.f, 0.f, 0.f);
-    gidx[k]    = i;
-    if (FEAT) move_features(f, i, k);
+    bool valid;
+    float rho;
+    const int beam = sclip_beam(L, S, G, pts[i], valid, rho);
+    if (beam >= 0) atomicMin(&rmin[beam], __float_as_uint(rho));
   }
+}
+
+// dynamic LDS: num_beams words (the host launches it only with num_beams <= SRRG2_SCLIP_LDS_BINS)
+__global__ void k_sclip_rmin_lds(Xf L, Xf S, ScanGeom G, const float4* __restrict__ pts, int n, unsigned* __restrict__ rmin) {
+  extern __shared__ unsigned table[];
+  const unsigned INF = 0x7f800000u;
+  for (int b = threadIdx.x; b < G.num_beams; b += blockDim.x) table[b] = INF;
+  __syncthreads();
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    bool valid;
+    float rho;
+    const int beam = sclip_beam(L, S, G, pts[i], valid, rho);
+    if (beam >= 0) atomicMin(&table[beam], __float_as_uint(rho));
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < G.num_beams; b += blockDim.x) {
+    const unsigned v = table[b];
+    if (v != INF) atomicMin(&rmin[b], v);
+  }
+}
+
+// counters: [0] Valid points, [1] in-view points
+template <bool OCCLUSION>
+__global__ void k_sclip_flag(Xf L, Xf S, ScanGeom G, const float4* __restrict__ pts, int n, const unsigned* __restrict__ rmin,
+                             int* __restrict__ flags, int* __restrict__ counters) {
+  int nvalid = 0, nview = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    bool valid;
+    float rho;
+    const int beam = sclip_beam(L, S, G, pts[i], valid, rho);
+    bool keep      = beam >= 0;
+    nvalid += valid ? 1 : 0;
+    nview += keep ? 1 : 0;
+    if (OCCLUSION && keep) keep = rho <= __uint_as_float(rmin[beam]) + G.margin;
+    flags[i] = keep ? 1 : 0;
+  }
+  block_add(nvalid, &counters[0]);
+  block_add(nview, &counters[1]);
+}
+
+template <bool FEAT>
+__global__ void k_sclip_scatter(Xf L, const float4* __restrict__ pts, const float4* __restrict__ nrm, int n,
+                                const int* __restrict__ offset, float4* __restrict__ out_pts, float4* __restrict__ out_nrm,
+                                int* __restrict__ gidx, int cap, Feat f) {
+  scatter_kept<FEAT, 2>(L, pts, nrm, n, offset, out_pts, out_nrm, gidx, cap, f);
 }
 
 // ---- merge --------------------------------------------------------------------------------------------------
@@ -568,7 +685,7 @@ int srrg2_scene_destroy(srrg2_scene_h s) {
   (void) hipSetDevice(s->device);
   if (s->stream) (void) hipStreamSynchronize(s->stream);
   s->pts.release(); s->nrm.release(); s->desc.release(); s->inten.release(); s->gidx.release(); s->flags.release(); s->scan_sums.release();
-  s->counts.release(); s->dup_list.release(); s->dup_keys.release(); s->sort_tmp.release(); s->merged.release(); s->corr.release(); s->staging.release(); s->zmin.release(); s->dscalars.release();
+  s->counts.release(); s->dup_list.release(); s->dup_keys.release(); s->sort_tmp.release(); s->merged.release(); s->corr.release(); s->staging.release(); s->zmin.release(); s->rmin.release(); s->dscalars.release();
   if (s->scalars) (void) hipHostFree(s->scalars);
   if (s->stream) (void) hipStreamDestroy(s->stream);
   delete s;
@@ -802,7 +919,7 @@ int srrg2_scene_clip_projective(srrg2_scene_h full, const float* robot_in_local_
   if (full == clipped || full->dim != clipped->dim || full->device != clipped->device)
     return fail(SRRG2_E_INVALID, "scene_clip_projective: full and clipped must be two scenes of one dim on one device");
   if (full->dim != 3)
-    return fail(SRRG2_E_UNSUPPORTED, "scene_clip_projective: 2-D scenes (a field-of-view clipper over bearings is not built)");
+    return fail(SRRG2_E_UNSUPPORTED, "scene_clip_projective: 2-D scenes (a laser scanner's view: srrg2_scene_clip_scan)");
   if (p->image_rows <= 0 || p->image_cols <= 0 || (long long) p->image_rows * (long long) p->image_cols > 0x7fffffffLL)
     return fail(SRRG2_E_INVALID, "scene_clip_projective: image_rows, image_cols > 0 and rows*cols within int32");
   if (!(p->depth_min > 0.f) || !(p->depth_max >= p->depth_min))
@@ -870,6 +987,115 @@ int srrg2_scene_clip_projective(srrg2_scene_h full, const float* robot_in_local_
     if ((rc = clipped->gidx.reserve((size_t) total))) return rc;
     const Feat f = feat_of(full, clipped);
     LAUNCH_FEAT(k_pclip_scatter, moves_features(f), grid, st, L, full->pts.p, full->has_normals ? full->nrm.p : nullptr, n,
+                full->flags.p, clipped->pts.p, clipped->nrm.p, clipped->gidx.p, total, f);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  clipped->n = clipped->ng = total;
+  if (out) {
+    out->num_valid   = num_valid;
+    out->num_in_view = num_in_view;
+    out->num_kept    = total;
+  }
+  return 0;
+}
+
+void srrg2_clip_default_scan_params(srrg2_scan_clip_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->range_min = 0.05f;
+  p->range_max = 30.f;
+  p->sensor_in_robot[0] = p->sensor_in_robot[4] = p->sensor_in_robot[8] = 1.f;
+  p->occlusion_margin = -1.f;
+}
+
+int srrg2_scene_clip_scan(srrg2_scene_h full, const float* robot_in_local_map, const srrg2_scan_clip_params* p,
+                          srrg2_scene_h clipped, srrg2_clip_result* out) {
+  if (!full || !clipped || !robot_in_local_map || !p) return fail(SRRG2_E_INVALID, "scene_clip_scan: null argument");
+  if (full == clipped || full->dim != clipped->dim || full->device != clipped->device)
+    return fail(SRRG2_E_INVALID, "scene_clip_scan: full and clipped must be two scenes of one dim on one device");
+  if (full->dim != 2)
+    return fail(SRRG2_E_UNSUPPORTED, "scene_clip_scan: 3-D scenes (lidar rings are not built; a camera: srrg2_scene_clip_projective)");
+  const double TWO_PI = 6.283185307179586;
+  const double inc    = std::fabs(p->angle_increment);
+  if (p->num_beams <= 0) return fail(SRRG2_E_INVALID, "scene_clip_scan: num_beams > 0");
+  if (!std::isfinite(p->angle_increment) || p->angle_increment == 0.0)
+    return fail(SRRG2_E_INVALID, "scene_clip_scan: angle_increment must be finite and non-zero");
+  if (!std::isfinite(p->angle_min) || std::fabs(p->angle_min) > TWO_PI)
+    return fail(SRRG2_E_INVALID, "scene_clip_scan: angle_min must be finite and within [-2 pi, 2 pi]");
+  // (a sector may close on itself once -- 361 beams over 360 degrees; the slack of 2^-20 admits an increment that went through
+  // float32 on its way here)
+  if (inc * (double) p->num_beams > (TWO_PI + inc) * (1.0 + 0x1p-20))
+    return fail(SRRG2_E_INVALID, "scene_clip_scan: |angle_increment| * num_beams beyond 2 pi plus one increment");
+  if (!(p->range_min > 0.f) || !(p->range_max >= p->range_min)) return fail(SRRG2_E_INVALID, "scene_clip_scan: 0 < range_min <= range_max");
+  if (std::isnan(p->occlusion_margin)) return fail(SRRG2_E_INVALID, "scene_clip_scan: occlusion_margin is NaN");
+  int rc;
+  if ((rc = scene_device(clipped)) || (rc = scene_device(full))) return rc;
+  float Linv[9], Sinv[9];
+  dm::se2_inverse(robot_in_local_map, Linv);
+  dm::se2_inverse(p->sensor_in_robot, Sinv);
+  const Xf L = load_transform(2, Linv), S = load_transform(2, Sinv);
+  const ScanGeom geom{p->angle_min, p->angle_increment, std::copysign(TWO_PI, p->angle_increment),
+                      p->range_min, p->range_max,       p->occlusion_margin,
+                      p->num_beams};
+  const bool occlusion = p->occlusion_margin >= 0.f;
+  const int n          = full->n;
+  clipped->has_normals = full->has_normals;
+  clipped->has_desc    = full->has_desc;
+  clipped->has_inten   = full->has_inten;
+  clipped->n = clipped->ng = 0;
+  // (arrays even for an empty result, as srrg2_scene_set leaves them: srrg2_scene_device_arrays then shows the normals' presence)
+  if ((rc = scene_reserve(clipped, 1, 0)) || (rc = clipped->gidx.reserve(1))) return rc;
+  if (out) {
+    std::memset(out, 0, sizeof(*out));
+    out->status = n == 0 ? SRRG2_CLIPPER_READY : SRRG2_CLIPPER_SUCCESSFUL;
+  }
+  if (n == 0) return 0;
+  hipStream_t st = full->stream;
+  if ((rc = full->flags.reserve((size_t) n + 1))) return rc;
+  // (the two counts in front of the scan's total at the tail of its scratch: one copy brings all three to the host)
+  if ((rc = full->scan_sums.reserve((size_t) srrg2amd::scan_num_blocks(n) + 4))) return rc;
+  int* const counters = full->scan_sums.p + full->scan_sums.cap - 3;
+  int* const dtotal   = counters + 2;
+  HIP_TRY(hipMemsetAsync(counters, 0, 2 * sizeof(int), st));
+  const dim3 grid(blocks_for(n));
+  if (occlusion) {
+    const int nb = geom.num_beams;
+    if ((rc = full->rmin.reserve((size_t) nb))) return rc;
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) full->rmin.p, 0x7f800000, (size_t) nb, st));  // +inf
+#ifndef SRRG2_SCLIP_NO_LDS
+    // every workgroup initialises and flushes num_beams words: give each at least SRRG2_SCLIP_POINTS_PER_BIN points per bin
+    const long long share = (long long) SRRG2_SCLIP_POINTS_PER_BIN * nb;
+    if (nb <= SRRG2_SCLIP_LDS_BINS && n / share >= SRRG2_SCLIP_LDS_MIN_WORKGROUPS) {
+      const int blocks = (int) std::min<long long>(grid.x, n / share);
+      hipLaunchKernelGGL(k_sclip_rmin_lds, dim3(blocks), dim3(256), (size_t) nb * sizeof(unsigned), st, L, S, geom, full->pts.p, n,
+                         full->rmin.p);
+    } else
+#endif
+      hipLaunchKernelGGL(k_sclip_rmin, grid, dim3(256), 0, st, L, S, geom, full->pts.p, n, full->rmin.p);
+    hipLaunchKernelGGL(k_sclip_flag<true>, grid, dim3(256), 0, st, L, S, geom, full->pts.p, n, full->rmin.p, full->flags.p, counters);
+  } else {
+    hipLaunchKernelGGL(k_sclip_flag<false>, grid, dim3(256), 0, st, L, S, geom, full->pts.p, n, (const unsigned*) nullptr,
+                       full->flags.p, counters);
+  }
+  srrg2amd::launch_exclusive_scan(full->flags.p, n, full->scan_sums.p, dtotal, st);
+  // as clip_ball: the scatter goes behind the scan into the room `clipped` has, before the host knows the total -- one wait per
+  // clip; a total beyond the room repeats the scatter with room for all
+  const int room = (int) std::min<size_t>(std::min(clipped->pts.cap, clipped->nrm.cap), clipped->gidx.cap);
+  {
+    const Feat f = feat_of(full, clipped);
+    LAUNCH_FEAT(k_sclip_scatter, moves_features(f), grid, st, L, full->pts.p, full->has_normals ? full->nrm.p : nullptr, n,
+                full->flags.p, clipped->pts.p, clipped->nrm.p, clipped->gidx.p, room, f);
+  }
+  HIP_TRY(hipMemcpyAsync(&full->scalars[0], counters, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  const int num_valid = full->scalars[0], num_in_view = full->scalars[1], total = full->scalars[2];
+  if (total > room) {
+    if ((rc = scene_reserve(clipped, total, 0))) return rc;
+    if ((rc = clipped->gidx.reserve((size_t) total))) return rc;
+    const Feat f = feat_of(full, clipped);
+    LAUNCH_FEAT(k_sclip_scatter, moves_features(f), grid, st, L, full->pts.p, full->has_normals ? full->nrm.p : nullptr, n,
                 full->flags.p, clipped->pts.p, clipped->nrm.p, clipped->gidx.p, total, f);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));

@@ -27,6 +27,7 @@ struct srrg2_scene {
   srrg2amd::DevBuf<char> sort_tmp;
   srrg2amd::DevBuf<char> staging;
   srrg2amd::DevBuf<unsigned> zmin;  // clip_projective with occlusion: per pixel the bits of the smallest camera depth seen
+  srrg2amd::DevBuf<unsigned> rmin;  // clip_scan with occlusion: per beam the bits of the smallest range seen
   int* scalars = nullptr;  // pinned host mirror of dscalars
   // device: [0] scan total, [1] num_merged, [2] error flag, [3] duplicates seen, [4] ncorr (merge); [8] in range, [9] Valid (adapt)
   srrg2amd::DevBuf<int> dscalars;

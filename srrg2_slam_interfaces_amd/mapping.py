@@ -5,6 +5,7 @@
                                clouds), which clipper and merger move with the points
 ``SceneClipperBall``           ``SceneClipper_`` (S/mapping/scene_clipper.h:17-122) with the ball policy
 ``SceneClipperProjective``     the same interface with the projective policy: what a pinhole camera sees (3-D, product library)
+``SceneClipperScan``           the same interface with the scan policy: what a planar laser scanner sees (2-D, product library)
 ``MergerCorrespondenceHomo``   ``MergerCorrespondenceHomo_`` (S/mapping/merger_correspondence_homo_impl.cpp:11-125)
 
 Method names follow the reference setters (snake_case).  Thin marshalling only; parametrised by
@@ -40,6 +41,12 @@ class ProjectiveClipParams(C.Structure):
                 ("occlusion_margin", C.c_float)]
 
 
+class ScanClipParams(C.Structure):
+    """srrg2_scan_clip_params"""
+    _fields_ = [("angle_min", C.c_double), ("angle_increment", C.c_double), ("num_beams", C.c_int32), ("range_min", C.c_float),
+                ("range_max", C.c_float), ("sensor_in_robot", C.c_float * 9), ("occlusion_margin", C.c_float)]
+
+
 class ClipResult(C.Structure):
     """srrg2_clip_result"""
     _fields_ = [("status", C.c_int32), ("num_valid", C.c_int32), ("num_in_view", C.c_int32), ("num_kept", C.c_int32)]
@@ -54,6 +61,16 @@ def default_projective_clip_params():
 
     p = ProjectiveClipParams()
     _capi.lib().srrg2_clip_default_projective_params(C.byref(p))
+    return p
+
+
+def default_scan_clip_params():
+    """identity sensor, range 0.05 .. 30 m, occlusion_margin < 0 (sector only); angle_min / angle_increment / num_beams are the
+    caller's"""
+    from . import _capi
+
+    p = ScanClipParams()
+    _capi.lib().srrg2_clip_default_scan_params(C.byref(p))
     return p
 
 
@@ -275,6 +292,52 @@ class SceneClipperProjective:
         self._status = CLIPPER_ERROR
         self._b.check(self._b.fn("clip_projective")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params),
                                                     self._clipped._h, C.byref(out) if want_result else None))
+        if want_result:
+            self._status, self.last = out.status, out.as_dict()
+        else:
+            self._status, self.last = (CLIPPER_SUCCESSFUL if self._full.size() else CLIPPER_READY), None
+        return self.last
+
+    def status(self):
+        return self._status
+
+    def global_indices(self):
+        return self._clipped.global_indices()
+
+
+class SceneClipperScan:
+    """setFullScene / setClippedSceneInRobot / setRobotInLocalMap / setSensorInRobot / compute / status / globalIndices for 2-D
+    scenes.  ``params``: ScanClipParams (angle_min, angle_increment, num_beams, range interval, occlusion_margin); ``last``: the
+    counts of the last compute() (``want_result=False`` passes no result struct: ``last`` is then None)."""
+
+    def __init__(self, binding, params=None):
+        self._b = binding
+        self.params = params or default_scan_clip_params()
+        self._full = self._clipped = None
+        self._robot_in_local_map = None
+        self._status = CLIPPER_ERROR
+        self.last = None
+
+    def set_full_scene(self, scene):
+        self._full = scene
+
+    def set_clipped_scene_in_robot(self, scene):
+        self._clipped = scene
+
+    def set_robot_in_local_map(self, T):
+        self._robot_in_local_map = _f32(T)
+
+    def set_sensor_in_robot(self, T):
+        for i, v in enumerate(_f32(T).reshape(9)):
+            self.params.sensor_in_robot[i] = float(v)
+
+    def compute(self, want_result=True):
+        if self._full is None or self._clipped is None or self._robot_in_local_map is None:
+            raise RuntimeError("SceneClipperScan::compute|scene, output or pose not set")
+        out = ClipResult()
+        self._status = CLIPPER_ERROR
+        self._b.check(self._b.fn("clip_scan")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params),
+                                              self._clipped._h, C.byref(out) if want_result else None))
         if want_result:
             self._status, self.last = out.status, out.as_dict()
         else:
