@@ -1,6 +1,7 @@
 """-m gpu: the incremental pose-graph interface (srrg2_posegraph_add_variable / add_factor / set_factor_enabled /
 remove_factor) against the one-shot interface and the CPU oracle, driven through the MultiGraphSLAM_ lifecycle mirror
-(S/system/multi_graph_slam_impl.cpp:52-90, :227-297, :300-317)."""
+(S/system/multi_graph_slam_impl.cpp:52-90, :227-297, :300-317).
+The eliminated leaves against float64, tail by tail: tests/test_gpu_posegraph_append.py."""
 import numpy as np
 import pytest
 

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import posegraph_restatement as PR
 import posegraph_robust_restatement as R
 from srrg2_slam_interfaces_amd import _abi as abi
 from srrg2_slam_interfaces_amd import posegraph as pgm
@@ -103,7 +104,10 @@ def test_outlier_story_on_the_gpu(product, kind):
 
 
 @pytest.mark.parametrize("kind", KINDS)
-def test_evaluate_factors_enabled_disabled_removed(oracle, product, kind):
+def test_evaluate_factors_enabled_disabled_removed(product, kind):
+    """against e^T Omega e of the float64 restatement at the poses read back: the read-back forms its residual in double
+    (edge_error_f64), where the oracle, like the solver, rounds three transforms to float32 -- 0.8 % of a chi on this SE(2)
+    graph, whose coordinates reach hundreds of metres"""
     g = _graph(kind)
     E = g["ij"].shape[0]
     om = R.information(kind, E)
@@ -125,9 +129,8 @@ def test_evaluate_factors_enabled_disabled_removed(oracle, product, kind):
     P0 = pg.poses().copy()
     chi, w = pg.evaluate_factors()
     assert np.array_equal(pg.poses(), P0)  # changes nothing
-    ref = oracle.OraclePoseGraph(kind)
-    ref.set_graph(P0, g["ij"], g["Z"], omega=om)
-    chi_ref = R.factor_chi(ref, om)
+    r, _, _, Om, _, _ = PR.linearise(kind, P0, g["ij"], g["Z"], om)
+    chi_ref = np.einsum("ea,eab,eb->e", r, Om, r)
     kinds[removed] = abi.ROBUST_NONE
     w_ref = R.weights(kinds, thrs, chi_ref)
     live = np.setdiff1d(np.arange(E), removed)
