@@ -693,6 +693,56 @@ void srrg2_clip_default_scan_params(srrg2_scan_clip_params* p);
 int srrg2_scene_clip_scan(srrg2_scene_h full, const float* robot_in_local_map /* 3x3 */, const srrg2_scan_clip_params* p,
                           srrg2_scene_h clipped, srrg2_clip_result* out /* may be NULL */);
 
+/* Normals for a scene that arrived as a plain list of points (a 3-D lidar sweep, a map from disk, srrg2_scene_set without
+ * normals, a merged map whose averaged normals have drifted): per point the PCA of its radius neighbourhood, on the device.
+ * No reference counterpart; DESIGN.md section 4 "Normals of unorganised scenes" is the arithmetic contract, bit for bit.
+ *   neighbours   j is a neighbour of i iff both have finite coordinates and d2 <= radius*radius (float32, the gated finder's
+ *                operation order, inclusive); i is its own neighbour.  Scenes of dim 2: the 2x2 problem, z ignored.
+ *   normal       the eigenvector of the smallest eigenvalue of the neighbourhood's covariance (float64, fixed Jacobi sweeps),
+ *                turned towards `viewpoint` (scene frame); a NaN in any of the three components of viewpoint = no viewpoint:
+ *                the component of largest magnitude is made positive.  curvature = lambda0 / (sum of lambdas).
+ *   no normal    a point with a non-finite coordinate; fewer than min_neighbours neighbours (too_few); all neighbours
+ *                coincident, trace <= 0 or not finite (degenerate); float32(curvature) > max_curvature (too_curved) -- counted in
+ *                the first that applies.  drop_points_without_normal = 1: such points leave the scene (stable compaction;
+ *                descriptor and intensity move with their point; srrg2_scene_global_indices gives every survivor's index before
+ *                the call, as the adaptors' compact mode).  0: order, size and global indices stay, their normal is NaN.
+ *   afterwards   the scene has normals (existing ones are replaced).  curvature_out[i] (host, capacity = the size before the
+ *                call, may be NULL) refers to index i BEFORE the call: the curvature where a covariance was formed and not
+ *                degenerate, else NaN.
+ *   refused      the scene unchanged.  SRRG2_E_INVALID: null handle or params; radius not finite or <= 0, or so large / small
+ *                that radius*radius is infinite / 0 in float32 (admissible: about 1e-22 .. 1.8e19); min_neighbours <
+ *                dim + 1; max_curvature NaN; drop_points_without_normal not 0 / 1.  SRRG2_E_UNSUPPORTED: the extent.  Points are
+ *                binned into cells floor((p - bbox_min) / h), h = radius * (1 + 2^-16), in float64; the 64-bit cell key holds at
+ *                most 2^30 cells per axis and 63 bits over the axes (an axis of c cells takes the bits of c - 1): two clusters
+ *                10^7 radii apart along one axis are fine, 10^7 radii apart along all three are refused.  Memory is O(n)
+ *                whatever the extent.
+ *   empty scene  succeeds, all-zero result.
+ *   waits        one host wait when out, curvature_out or the compaction needs a number.  With drop = 0 and both NULL the work
+ *                is queued on the scene's stream and the call returns (the next srrg2_scene_* call settles it, like an
+ *                organised adaptor write): srrg2_scene_device_arrays + set_fixed(..., SRRG2_MEM_DEVICE_KEPT) can follow at
+ *                once.  The extent cannot be refused from there: beyond the key range every normal comes out NaN. */
+typedef struct srrg2_normals_params {
+  float   radius;                 /* neighbourhood: d2 <= radius*radius, INCLUSIVE; finite, > 0 (default 0.1) */
+  int32_t min_neighbours;         /* neighbours counted INCLUDING the point itself; >= dim+1; default 5 (dim 3) / 3 (dim 2) */
+  float   max_curvature;          /* lambda0 / (sum of lambdas) above this -> no normal; default 1 (gate off) */
+  float   viewpoint[3];           /* in the scene's frame; normals face it (default: the origin); NaN = no viewpoint */
+  int32_t drop_points_without_normal; /* 1 (default): such points leave the scene; 0: they stay, normal = NaN */
+  int32_t reserved;               /* 0 (default_params sets it); not read: keeps the struct at 32 bytes */
+} srrg2_normals_params;
+
+typedef struct srrg2_normals_result {
+  int32_t num_points, num_finite, num_with_normal, num_too_few, num_degenerate, num_too_curved, scene_size;
+} srrg2_normals_result;
+
+void srrg2_normals_default_params(srrg2_normals_params* p, int dim);
+int  srrg2_scene_estimate_normals(srrg2_scene_h scene, const srrg2_normals_params* p,
+                                  float* curvature_out /* host, may be NULL, capacity = size before the call */,
+                                  srrg2_normals_result* out /* may be NULL */);
+/* the exponents of the fixed-point moment sums (first moments scaled by 2^e1, second by 2^e2): functions of the radius and
+ * the scene size alone -- with radius < 2^E (frexp) and n <= 2^L: e1 = min(61 - L - E, 50 - E), e2 = min(61 - L - 2E, 50 - 2E).
+ * No device needed. */
+void srrg2_normals_exponents(float radius, int n, int* e1, int* e2);
+
 /* MergerCorrespondenceHomo_::compute() (S/mapping/merger_correspondence_homo_impl.cpp:11-125).
  * correspondences: fixed_idx = scene point, moving_idx = measurement point, processed in order
  * (a scene point hit twice sees the first update, :55-73); n_correspondences < 0 = "no

@@ -480,6 +480,14 @@ public:
   void deviceFeatures(const uint8_t*& descriptors, const float*& intensity, int& n) const {
     check(srrg2_scene_device_features(_h, &descriptors, &intensity, &n));
   }
+  // normals from the PCA of every point's radius neighbourhood (srrg2_scene_estimate_normals; defaults:
+  // srrg2_normals_default_params(&p, DIM)).  curvature: per point as indexed BEFORE the call, NaN where none was formed.
+  srrg2_normals_result estimateNormals(const srrg2_normals_params& p, std::vector<float>* curvature = nullptr) {
+    srrg2_normals_result r;
+    if (curvature) curvature->assign((size_t) size(), 0.f);
+    check(srrg2_scene_estimate_normals(_h, &p, curvature && !curvature->empty() ? curvature->data() : nullptr, &r));
+    return r;
+  }
   srrg2_scene_h handle() const { return _h; }
 
 private:

@@ -183,6 +183,21 @@ class AdaptResult(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class NormalsParams(C.Structure):
+    """srrg2_normals_params"""
+    _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_int32), ("max_curvature", C.c_float), ("viewpoint", C.c_float * 3),
+                ("drop_points_without_normal", C.c_int32), ("reserved", C.c_int32)]
+
+
+class NormalsResult(C.Structure):
+    """srrg2_normals_result"""
+    _fields_ = [("num_points", C.c_int32), ("num_finite", C.c_int32), ("num_with_normal", C.c_int32), ("num_too_few", C.c_int32),
+                ("num_degenerate", C.c_int32), ("num_too_curved", C.c_int32), ("scene_size", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 def transform_size(variable_kind):
     return 9 if variable_kind == SE2_RIGHT else 12
 

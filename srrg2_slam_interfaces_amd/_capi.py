@@ -68,6 +68,13 @@ def lib():
         _LIB.srrg2_clip_default_scan_params.restype = None
         _LIB.srrg2_scene_clip_scan.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(mapping.ScanClipParams), C.c_void_p,
                                                C.POINTER(mapping.ClipResult)]
+        # srrg2_scene_estimate_normals (mapping.Scene.estimate_normals)
+        _LIB.srrg2_normals_default_params.argtypes = [C.POINTER(abi.NormalsParams), C.c_int]
+        _LIB.srrg2_normals_default_params.restype = None
+        _LIB.srrg2_normals_exponents.argtypes = [C.c_float, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _LIB.srrg2_normals_exponents.restype = None
+        _LIB.srrg2_scene_estimate_normals.argtypes = [C.c_void_p, C.POINTER(abi.NormalsParams), C.POINTER(C.c_float),
+                                                      C.POINTER(abi.NormalsResult)]
     return _LIB
 
 

@@ -686,6 +686,8 @@ int srrg2_scene_destroy(srrg2_scene_h s) {
   if (s->stream) (void) hipStreamSynchronize(s->stream);
   s->pts.release(); s->nrm.release(); s->desc.release(); s->inten.release(); s->gidx.release(); s->flags.release(); s->scan_sums.release();
   s->counts.release(); s->dup_list.release(); s->dup_keys.release(); s->sort_tmp.release(); s->merged.release(); s->corr.release(); s->staging.release(); s->zmin.release(); s->rmin.release(); s->dscalars.release();
+  s->alt_pts.release(); s->alt_nrm.release(); s->nrm_sorted.release(); s->nrm_tmp.release(); s->alt_desc.release(); s->alt_inten.release();
+  s->nrm_curv.release(); s->alt_gidx.release(); s->nrm_idx.release(); s->nrm_ctr.release(); s->nrm_keys.release();
   if (s->scalars) (void) hipHostFree(s->scalars);
   if (s->stream) (void) hipStreamDestroy(s->stream);
   delete s;

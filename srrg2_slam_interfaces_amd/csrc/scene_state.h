@@ -28,6 +28,14 @@ struct srrg2_scene {
   srrg2amd::DevBuf<char> staging;
   srrg2amd::DevBuf<unsigned> zmin;  // clip_projective with occlusion: per pixel the bits of the smallest camera depth seen
   srrg2amd::DevBuf<unsigned> rmin;  // clip_scan with occlusion: per beam the bits of the smallest range seen
+  // estimate_normals (normals.hip): the arrays the call writes in place of the scene's own -- swapped in once it has succeeded,
+  // so a refused call leaves the scene as it was -- and its scratch: cell keys and point indices (unsorted, sorted), the points
+  // in cell order, per-point normal and curvature, the bounding box / cell layout / counters block
+  srrg2amd::DevBuf<float4> alt_pts, alt_nrm, nrm_sorted, nrm_tmp;
+  srrg2amd::DevBuf<uint4> alt_desc;
+  srrg2amd::DevBuf<float> alt_inten, nrm_curv;
+  srrg2amd::DevBuf<int> alt_gidx, nrm_idx, nrm_ctr;
+  srrg2amd::DevBuf<unsigned long long> nrm_keys;
   int* scalars = nullptr;  // pinned host mirror of dscalars
   // device: [0] scan total, [1] num_merged, [2] error flag, [3] duplicates seen, [4] ncorr (merge); [8] in range, [9] Valid (adapt)
   srrg2amd::DevBuf<int> dscalars;

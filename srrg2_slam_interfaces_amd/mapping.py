@@ -214,6 +214,31 @@ class Scene:
         self._b.check(self._b.fn("global_indices")(self._h, buf.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(k)))
         return buf[:n.value]
 
+    def estimate_normals(self, radius, min_neighbours=None, max_curvature=1.0, viewpoint=(0.0, 0.0, 0.0), drop=True,
+                         return_curvature=False, want_result=True):
+        """normals from the PCA of every point's radius neighbourhood, on the device (srrg2_scene_estimate_normals; product
+        library only).  ``viewpoint`` None: no viewpoint (the largest component of a normal is made positive).  ``drop``:
+        points that get no normal leave the scene.  Returns the counts as a dict -- with ``return_curvature`` the pair
+        (counts, curvature per point as indexed BEFORE the call).  ``want_result=False`` with ``drop=False`` and no curvature
+        queues the work and returns None without waiting."""
+        f = self._feature_fn("estimate_normals")
+        p = abi.NormalsParams()
+        self._b.lib.srrg2_normals_default_params(C.byref(p), C.c_int(self.dim))
+        p.radius = float(radius)
+        if min_neighbours is not None:
+            p.min_neighbours = int(min_neighbours)
+        p.max_curvature = float(max_curvature)
+        vp = (np.nan,) * 3 if viewpoint is None else tuple(float(v) for v in viewpoint) + (0.0,) * (3 - len(viewpoint))
+        for k in range(3):
+            p.viewpoint[k] = vp[k]
+        p.drop_points_without_normal = int(drop)
+        out = abi.NormalsResult()
+        curv = np.zeros(max(self.size(), 1), np.float32) if return_curvature else None
+        n = self.size()
+        self._b.check(f(self._h, C.byref(p), _fp(curv) if return_curvature else None, C.byref(out) if want_result else None))
+        res = out.as_dict() if want_result else None
+        return (res, curv[:n]) if return_curvature else res
+
     def device_arrays(self):
         """(coords_ptr, normals_ptr or None, n): device float4 arrays (product backend only)."""
         c, m, n = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.c_int(0)
