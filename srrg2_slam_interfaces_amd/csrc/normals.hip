@@ -23,6 +23,7 @@
 #include "device_types.h"
 #include "host_util.h"
 #include "kernels.h"
+#include "scene_device.h"
 #include "scene_state.h"
 
 using srrg2amd::fail;
@@ -394,9 +395,7 @@ template <bool FEAT>
 __global__ __launch_bounds__(256) void k_nrm_scatter(const NrmSpec* __restrict__ spec, const float4* __restrict__ pts,
                                                      const float4* __restrict__ nrm, int n, const int* __restrict__ offset,
                                                      float4* __restrict__ out_pts, float4* __restrict__ out_nrm,
-                                                     int* __restrict__ gidx, const uint4* __restrict__ src_desc,
-                                                     const float* __restrict__ src_inten, uint4* __restrict__ dst_desc,
-                                                     float* __restrict__ dst_inten) {
+                                                     int* __restrict__ gidx, Feat f) {
   if (spec->unsupported) return;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const float4 q = nrm[i];
@@ -406,20 +405,8 @@ __global__ __launch_bounds__(256) void k_nrm_scatter(const NrmSpec* __restrict__
     out_pts[k] = pts[i];
     out_nrm[k] = q;
     gidx[k]    = i;
-    if (FEAT) {
-      if (dst_desc) {
-        const uint4 a = src_desc[2 * (size_t) i], b = src_desc[2 * (size_t) i + 1];
-        dst_desc[2 * (size_t) k]     = a;
-        dst_desc[2 * (size_t) k + 1] = b;
-      }
-      if (dst_inten) dst_inten[k] = src_inten[i];
-    }
+    if (FEAT) move_features(f, i, k);
   }
-}
-
-int blocks_for(int n) {
-  int b = (n + 255) / 256;
-  return b < 1 ? 1 : (b > 2048 ? 2048 : b);
 }
 
 int ceil_log2(int n) {
@@ -556,17 +543,14 @@ extern "C" int srrg2_scene_estimate_normals(srrg2_scene_h s, const srrg2_normals
     // the compaction goes behind the pass before the host knows how many survive: one wait per call
     hipLaunchKernelGGL(k_nrm_flag, grid, block, 0, st, spec, computed, n, s->flags.p);
     srrg2amd::launch_exclusive_scan(s->flags.p, n, s->scan_sums.p, ctr + C_TOTAL, st);
-    const bool feat = s->has_desc || s->has_inten;
-    const uint4* sd = s->has_desc ? s->desc.p : nullptr;
-    const float* si = s->has_inten ? s->inten.p : nullptr;
-    uint4* dd       = s->has_desc ? s->alt_desc.p : nullptr;
-    float* di       = s->has_inten ? s->alt_inten.p : nullptr;
-    if (feat)
+    const Feat f{s->has_desc ? s->desc.p : nullptr, s->has_inten ? s->inten.p : nullptr,
+                 s->has_desc ? s->alt_desc.p : nullptr, s->has_inten ? s->alt_inten.p : nullptr};
+    if (f.dst_desc || f.dst_inten)
       hipLaunchKernelGGL(k_nrm_scatter<true>, grid, block, 0, st, spec, s->pts.p, computed, n, s->flags.p, s->alt_pts.p,
-                         s->alt_nrm.p, s->alt_gidx.p, sd, si, dd, di);
+                         s->alt_nrm.p, s->alt_gidx.p, f);
     else
       hipLaunchKernelGGL(k_nrm_scatter<false>, grid, block, 0, st, spec, s->pts.p, computed, n, s->flags.p, s->alt_pts.p,
-                         s->alt_nrm.p, s->alt_gidx.p, sd, si, dd, di);
+                         s->alt_nrm.p, s->alt_gidx.p, f);
   }
   HIP_TRY(hipMemcpyAsync(s->scalars, ctr, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
   if (curvature_out) HIP_TRY(hipMemcpyAsync(curvature_out, s->nrm_curv.p, sizeof(float) * (size_t) n, hipMemcpyDeviceToHost, st));

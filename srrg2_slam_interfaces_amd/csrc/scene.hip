@@ -7,7 +7,7 @@
 // A scene is two float4 arrays (points {x, y, z, 0}, normals) with spare capacity and, for the clouds of a visual pipeline
 // (PointIntensityDescriptor2f / 3f, the second instantiation of the merger: merger_correspondence_homo.h:36-40), a 256-bit
 // descriptor (two uint4) and a float intensity per point, each allocated only when present.  The features travel with the point:
-// the kernels that move points (k_clip_scatter, merge_one, k_append_scatter) have a feature-carrying instantiation, chosen on the
+// the kernels that move points (k_scatter_kept, merge_one, k_append_scatter) have a feature-carrying instantiation, chosen on the
 // host, so a scene without features runs the code it ran before they existed.  All kernels are one thread per
 // point or correspondence, coalesced, HBM bound: clip = 2 passes over the scene (flag+count, scatter) around an
 // exclusive scan (the projective and the scan clip with occlusion: one more in front, the per-pixel depth / per-beam range minimum); merge = one pass over the correspondences + (if the merge target was not reached) flag/scan/scatter
@@ -30,6 +30,7 @@
 #include "device_types.h"
 #include "host_util.h"
 #include "kernels.h"
+#include "scene_device.h"
 #include "scene_state.h"
 
 using srrg2amd::DevBuf;
@@ -83,52 +84,47 @@ __device__ __forceinline__ float4 rotate_normal(int dim, const Xf& M, const floa
 }
 
 // ---- clip ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool clip_keep(int dim, const Xf& L, float range2, const float4 p, float4& q) {
+// words of a scene's dscalars a clip uses: what the projective and the scan clip's flag kernels count, and behind them the
+// scan's total, so that ONE copy brings all three to the host (compact_into)
+enum { CLIP_VALID = 0, CLIP_IN_VIEW = 1, CLIP_TOTAL = 2 };
+
+__device__ __forceinline__ bool clip_keep(int dim, const Xf& L, float range2, const float4 p) {
   if (!valid_point(dim, p)) return false;
-  q              = xform_point(dim, L, p);
+  const float4 q = xform_point(dim, L, p);
   const float d2 = (q.x * q.x + q.y * q.y) + q.z * q.z;
   return d2 <= range2;
 }
 
 __global__ void k_clip_flag(int dim, Xf L, float range2, const float4* __restrict__ pts, int n, int* __restrict__ flags) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    float4 q;
-    flags[i] = clip_keep(dim, L, range2, pts[i], q) ? 1 : 0;
-  }
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    flags[i] = clip_keep(dim, L, range2, pts[i]) ? 1 : 0;
 }
 
-// what a feature-carrying kernel needs: source (measurement / full scene) and destination (scene / clipped scene) arrays; a
-// null pair = that field is absent.  Descriptor halves move as 16-byte vectors.
-struct Feat {
-  const uint4* src_desc;
-  const float* src_inten;
-  uint4* dst_desc;
-  float* dst_inten;
-};
-
-__device__ __forceinline__ void move_features(const Feat& f, int from, int to) {
-  if (f.dst_desc) {
-    const uint4 a = f.src_desc[2 * (size_t) from], b = f.src_desc[2 * (size_t) from + 1];
-    f.dst_desc[2 * (size_t) to]     = a;
-    f.dst_desc[2 * (size_t) to + 1] = b;
+// the points the scan kept (offset[i + 1] != offset[i]: the scan leaves its total in offset[n]) into the robot frame, in scene
+// order: the scatter of all three clippers.  It evaluates no predicate, so whatever a flag kernel decided is what moves.
+template <bool FEAT, int DIM>
+__device__ __forceinline__ void scatter_kept(const Xf& L, const float4* __restrict__ pts, const float4* __restrict__ nrm, int n,
+                                             const int* __restrict__ offset, float4* __restrict__ out_pts,
+                                             float4* __restrict__ out_nrm, int* __restrict__ gidx, int cap, const Feat& f) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int k = offset[i];
+    // not kept / no room yet (a scatter launched before the host knew the total: compact_into repeats it with room for all)
+    if (offset[i + 1] == k || k >= cap) continue;
+    out_pts[k] = xform_point(DIM, L, pts[i]);
+    out_nrm[k] = nrm ? rotate_normal(DIM, L, nrm[i]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    gidx[k]    = i;
+    if (FEAT) move_features(f, i, k);
   }
-  if (f.dst_inten) f.dst_inten[to] = f.src_inten[from];
 }
 
 template <bool FEAT>
-__global__ void k_clip_scatter(int dim, Xf L, float range2, const float4* __restrict__ pts, const float4* __restrict__ nrm,
-                               int n, const int* __restrict__ offset, float4* __restrict__ out_pts,
-                               float4* __restrict__ out_nrm, int* __restrict__ gidx, int cap, Feat f) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    float4 q;
-    if (!clip_keep(dim, L, range2, pts[i], q)) continue;
-    const int k = offset[i];
-    if (k >= cap) continue;  // (a scatter launched before the host knew the total: the caller repeats it with room for all)
-    out_pts[k]  = q;
-    out_nrm[k]  = nrm ? rotate_normal(dim, L, nrm[i]) : make_float4(0.f, 0.f, 0.f, 0.f);
-    gidx[k]     = i;
-    if (FEAT) move_features(f, i, k);
-  }
+__global__ void k_scatter_kept(int dim, Xf L, const float4* __restrict__ pts, const float4* __restrict__ nrm, int n,
+                               const int* __restrict__ offset, float4* __restrict__ out_pts, float4* __restrict__ out_nrm,
+                               int* __restrict__ gidx, int cap, Feat f) {
+  if (dim == 3)
+    scatter_kept<FEAT, 3>(L, pts, nrm, n, offset, out_pts, out_nrm, gidx, cap, f);
+  else
+    scatter_kept<FEAT, 2>(L, pts, nrm, n, offset, out_pts, out_nrm, gidx, cap, f);
 }
 
 // block sum -> ONE atomic per block (same-address atomics serialise at tens of ns each; blockDim = 256)
@@ -151,8 +147,7 @@ __device__ __forceinline__ void block_add(int v, int* target) {
 //   k_pclip_zmin     per pixel the minimum camera depth of the in-view points: positive floats order like their bit patterns,
 //                    so ONE 32-bit atomicMin per in-view point (no return value, order-free: deterministic)
 //   k_pclip_flag     keep flag per point + the Valid / in-view counts (one atomic per block and count)
-//   k_pclip_scatter  the points the scan kept (offset[i + 1] != offset[i]: the scan leaves the total in offset[n]), in the robot
-//                    frame: the same L and xform_point as k_clip_scatter, so the same bits
+// and k_scatter_kept moves what the scan kept: the same L and xform_point as for the ball clip, so the same bits
 struct ProjCam {
   float K0, K2, K4, K5, depth_min, depth_max, margin;
   int rows, cols;
@@ -182,7 +177,7 @@ __global__ void k_pclip_zmin(Xf L, Xf S, ProjCam C, const float4* __restrict__ p
   }
 }
 
-// counters: [0] Valid points, [1] in-view points
+// counters: [CLIP_VALID], [CLIP_IN_VIEW]
 template <bool OCCLUSION>
 __global__ void k_pclip_flag(Xf L, Xf S, ProjCam C, const float4* __restrict__ pts, int n, const unsigned* __restrict__ zmin,
                              int* __restrict__ flags, int* __restrict__ counters) {
@@ -197,30 +192,8 @@ __global__ void k_pclip_flag(Xf L, Xf S, ProjCam C, const float4* __restrict__ p
     if (OCCLUSION && keep) keep = cz <= __uint_as_float(zmin[pix]) + C.margin;
     flags[i] = keep ? 1 : 0;
   }
-  block_add(nvalid, &counters[0]);
-  block_add(nview, &counters[1]);
-}
-
-// (shared with the scan clip's k_sclip_scatter: DIM = 2)
-template <bool FEAT, int DIM>
-__device__ __forceinline__ void scatter_kept(const Xf& L, const float4* __restrict__ pts, const float4* __restrict__ nrm, int n,
-                                             const int* __restrict__ offset, float4* __restrict__ out_pts,
-                                             float4* __restrict__ out_nrm, int* __restrict__ gidx, int cap, const Feat& f) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const int k = offset[i];
-    if (offset[i + 1] == k || k >= cap) continue;  // not kept / no room yet (as k_clip_scatter: the caller repeats it)
-    out_pts[k] = xform_point(DIM, L, pts[i]);
-    out_nrm[k] = nrm ? rotate_normal(DIM, L, nrm[i]) : make_float4(0.f, 0.f, 0.f, 0.f);
-    gidx[k]    = i;
-    if (FEAT) move_features(f, i, k);
-  }
-}
-
-template <bool FEAT>
-__global__ void k_pclip_scatter(Xf L, const float4* __restrict__ pts, const float4* __restrict__ nrm, int n,
-                                const int* __restrict__ offset, float4* __restrict__ out_pts, float4* __restrict__ out_nrm,
-                                int* __restrict__ gidx, int cap, Feat f) {
-  scatter_kept<FEAT, 3>(L, pts, nrm, n, offset, out_pts, out_nrm, gidx, cap, f);
+  block_add(nvalid, &counters[CLIP_VALID]);
+  block_add(nview, &counters[CLIP_IN_VIEW]);
 }
 
 // ---- scan clip (no reference counterpart; DESIGN.md section 4 "Scan clipping") -------------------------------------------------
@@ -235,7 +208,7 @@ __global__ void k_pclip_scatter(Xf L, const float4* __restrict__ pts, const floa
 //                     SRRG2_SCLIP_LDS_MIN_WORKGROUPS workgroups their share, and the A/B build -DSRRG2_SCLIP_NO_LDS.
 //                     A minimum does not depend on who took it: both give the same bits.
 //   k_sclip_flag      keep flag per point + the Valid / in-view counts (one atomic per block and count)
-//   k_sclip_scatter   k_pclip_scatter's loop for dim 2: it reads the scan's neighbouring offsets and never computes a bearing
+// and k_scatter_kept moves what the scan kept: it reads the scan's neighbouring offsets and never computes a bearing
 struct ScanGeom {
   double angle_min, angle_increment, wrap;  // wrap = copysign(2 pi, angle_increment)
   float range_min, range_max, margin;
@@ -306,7 +279,7 @@ __global__ void k_sclip_rmin_lds(Xf L, Xf S, ScanGeom G, const float4* __restric
   }
 }
 
-// counters: [0] Valid points, [1] in-view points
+// counters: [CLIP_VALID], [CLIP_IN_VIEW]
 template <bool OCCLUSION>
 __global__ void k_sclip_flag(Xf L, Xf S, ScanGeom G, const float4* __restrict__ pts, int n, const unsigned* __restrict__ rmin,
                              int* __restrict__ flags, int* __restrict__ counters) {
@@ -321,15 +294,8 @@ __global__ void k_sclip_flag(Xf L, Xf S, ScanGeom G, const float4* __restrict__ 
     if (OCCLUSION && keep) keep = rho <= __uint_as_float(rmin[beam]) + G.margin;
     flags[i] = keep ? 1 : 0;
   }
-  block_add(nvalid, &counters[0]);
-  block_add(nview, &counters[1]);
-}
-
-template <bool FEAT>
-__global__ void k_sclip_scatter(Xf L, const float4* __restrict__ pts, const float4* __restrict__ nrm, int n,
-                                const int* __restrict__ offset, float4* __restrict__ out_pts, float4* __restrict__ out_nrm,
-                                int* __restrict__ gidx, int cap, Feat f) {
-  scatter_kept<FEAT, 2>(L, pts, nrm, n, offset, out_pts, out_nrm, gidx, cap, f);
+  block_add(nvalid, &counters[CLIP_VALID]);
+  block_add(nview, &counters[CLIP_IN_VIEW]);
 }
 
 // ---- merge --------------------------------------------------------------------------------------------------
@@ -490,11 +456,6 @@ __global__ void k_ingest_intensity(const float* __restrict__ src, size_t stride_
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[i] = src[(size_t) i * stride_floats];
 }
 
-int blocks_for(int n) {
-  int b = (n + 255) / 256;
-  return b < 1 ? 1 : (b > 2048 ? 2048 : b);
-}
-
 // the device of the scene made current, and whatever an adaptor left queued on its stream finished: every entry point that reads
 // or rewrites a scene starts here (several of them read it on another scene's stream or through the null stream)
 int scene_device(srrg2_scene* s) {
@@ -596,6 +557,56 @@ int scan_flags(srrg2_scene* s, int n, int* total) {
 int read_scalars(srrg2_scene* s, const int* from = nullptr) {
   HIP_TRY(hipMemcpyAsync(s->scalars, from ? from : s->dscalars.p, 16 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
+  return 0;
+}
+
+// two distinct scenes of one dim on one device: what a clipper reads and what it writes
+bool clip_pair(const srrg2_scene* full, const srrg2_scene* clipped) {
+  return full && clipped && full != clipped && full->dim == clipped->dim && full->device == clipped->device;
+}
+
+// both scenes current and quiet; `clipped` takes the fields of `full` and is empty until the clip has succeeded
+int clip_begin(srrg2_scene* full, srrg2_scene* clipped) {
+  int rc;
+  if ((rc = scene_device(clipped)) || (rc = scene_device(full))) return rc;
+  clipped->has_normals = full->has_normals;
+  clipped->has_desc    = full->has_desc;
+  clipped->has_inten   = full->has_inten;
+  clipped->n = clipped->ng = 0;
+  return 0;
+}
+
+void launch_scatter_kept(srrg2_scene* full, srrg2_scene* clipped, const Xf& L, int n, int cap) {
+  const Feat f = feat_of(full, clipped);
+  LAUNCH_FEAT(k_scatter_kept, moves_features(f), dim3(blocks_for(n)), full->stream, full->dim, L, full->pts.p,
+              full->has_normals ? full->nrm.p : nullptr, n, full->flags.p, clipped->pts.p, clipped->nrm.p, clipped->gidx.p, cap, f);
+}
+
+// The tail of every clipper: the n > 0 keep flags a flag kernel has queued in full->flags (n + 1 words reserved) -> `clipped`,
+// the kept points by L in scene order; full->scalars[CLIP_VALID .. CLIP_TOTAL] on the host when it returns.
+// A clipped scene that has room from the call before (a tracker clips around a pose that moves a little per frame): the scatter
+// is launched BEHIND the scan without the host having seen the total -- one wait per clip instead of two (0.046 -> ~0.03 ms for a
+// 100 k-point map); the kernel's k >= cap guard keeps it inside the room, and a total beyond the room repeats it with room for
+// all (the scan runs once: its offsets still stand).
+int compact_into(srrg2_scene* full, srrg2_scene* clipped, const Xf& L, int n) {
+  int rc;
+  hipStream_t st = full->stream;
+  if ((rc = full->scan_sums.reserve((size_t) srrg2amd::scan_num_blocks(n)))) return rc;
+  srrg2amd::launch_exclusive_scan(full->flags.p, n, full->scan_sums.p, full->dscalars.p + CLIP_TOTAL, st);
+  if ((rc = features_reserve(clipped, 0))) return rc;  // (room for features wherever there is room for points)
+  const int room = (int) std::min({clipped->pts.cap, clipped->nrm.cap, clipped->gidx.cap});
+  if (room > 0) launch_scatter_kept(full, clipped, L, n, room);
+  HIP_TRY(hipMemcpyAsync(full->scalars, full->dscalars.p, (CLIP_TOTAL + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  const int total = full->scalars[CLIP_TOTAL];
+  if (total > room) {
+    if ((rc = scene_reserve(clipped, total, 0)) || (rc = clipped->gidx.reserve((size_t) total))) return rc;
+    launch_scatter_kept(full, clipped, L, n, total);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  clipped->n = clipped->ng = total;
   return 0;
 }
 
@@ -844,64 +855,24 @@ int srrg2_scene_device_features(srrg2_scene_h s, const uint8_t** descriptors, co
 
 int srrg2_scene_clip_ball(srrg2_scene_h full, const float* robot_in_local_map, float range, srrg2_scene_h clipped,
                           int* status) {
-  if (!full || !clipped || !robot_in_local_map || full == clipped || full->dim != clipped->dim ||
-      full->device != clipped->device)
-    return fail(SRRG2_E_INVALID, "scene_clip_ball: bad arguments");
+  if (!clip_pair(full, clipped) || !robot_in_local_map) return fail(SRRG2_E_INVALID, "scene_clip_ball: bad arguments");
   int rc;
-  if ((rc = scene_device(clipped)) || (rc = scene_device(full))) return rc;
+  if ((rc = clip_begin(full, clipped))) return rc;
   float Linv[12];
   if (full->dim == 3)
     dm::se3_inverse(robot_in_local_map, Linv);  // scene_clipper.h:64-68
   else
     dm::se2_inverse(robot_in_local_map, Linv);
-  const Xf L         = load_transform(full->dim, Linv);
-  const float range2 = range * range;
-  const int n        = full->n;
-  clipped->has_normals = full->has_normals;
-  clipped->has_desc    = full->has_desc;
-  clipped->has_inten   = full->has_inten;
-  clipped->n = clipped->ng = 0;
+  const Xf L  = load_transform(full->dim, Linv);
+  const int n = full->n;
   if (status) *status = n == 0 ? SRRG2_CLIPPER_READY : SRRG2_CLIPPER_SUCCESSFUL;  // :24-28
   if (n == 0) return 0;
-  hipStream_t st = full->stream;
   if ((rc = full->flags.reserve((size_t) n + 1))) return rc;
-  hipLaunchKernelGGL(k_clip_flag, dim3(blocks_for(n)), dim3(256), 0, st, full->dim, L, range2, full->pts.p, n, full->flags.p);
-  int total = 0;
-  // A clipped scene that has room from the call before (a tracker clips around a pose that moves a little per frame): the scatter
-  // is launched BEHIND the scan without the host having seen the total -- one wait per clip instead of two (0.046 -> ~0.03 ms for a
-  // 100 k-point map); a total beyond the room repeats the scatter the slow way.
-  if ((rc = features_reserve(clipped, 0))) return rc;  // (room for features wherever there is room for points)
-  const int room = (int) std::min<size_t>(std::min(clipped->pts.cap, clipped->nrm.cap), clipped->gidx.cap);
-  bool speculated = false;
-  if (room > 0) {
-    if ((rc = full->scan_sums.reserve((size_t) srrg2amd::scan_num_blocks(n) + 2))) return rc;
-    int* dtotal = full->scan_sums.p + full->scan_sums.cap - 1;
-    srrg2amd::launch_exclusive_scan(full->flags.p, n, full->scan_sums.p, dtotal, st);
-    const Feat f = feat_of(full, clipped);
-    LAUNCH_FEAT(k_clip_scatter, moves_features(f), dim3(blocks_for(n)), st, full->dim, L, range2, full->pts.p,
-                full->has_normals ? full->nrm.p : nullptr, n, full->flags.p, clipped->pts.p, clipped->nrm.p, clipped->gidx.p,
-                room, f);
-    HIP_TRY(hipMemcpyAsync(&full->scalars[0], dtotal, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    total      = full->scalars[0];
-    speculated = total <= room;
-  } else if ((rc = scan_flags(full, n, &total))) {
-    return rc;
-  }
-  if (!speculated) {
-    if ((rc = scene_reserve(clipped, total > 0 ? total : 1, 0))) return rc;
-    if ((rc = clipped->gidx.reserve((size_t) (total > 0 ? total : 1)))) return rc;
-    if (total > 0) {
-      const Feat f = feat_of(full, clipped);
-      LAUNCH_FEAT(k_clip_scatter, moves_features(f), dim3(blocks_for(n)), st, full->dim, L, range2, full->pts.p,
-                  full->has_normals ? full->nrm.p : nullptr, n, full->flags.p, clipped->pts.p, clipped->nrm.p, clipped->gidx.p,
-                  total, f);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-  }
-  clipped->n = clipped->ng = total;
+  hipLaunchKernelGGL(k_clip_flag, dim3(blocks_for(n)), dim3(256), 0, full->stream, full->dim, L, range * range, full->pts.p, n,
+                     full->flags.p);
+  if ((rc = compact_into(full, clipped, L, n))) return rc;
+  // (no arrays up front: a fresh handle has them only from here on, after a clip that kept nothing too)
+  if ((rc = scene_reserve(clipped, 1, 0)) || (rc = clipped->gidx.reserve(1))) return rc;
   return 0;
 }
 
@@ -918,7 +889,7 @@ void srrg2_clip_default_projective_params(srrg2_projective_clip_params* p) {
 int srrg2_scene_clip_projective(srrg2_scene_h full, const float* robot_in_local_map, const srrg2_projective_clip_params* p,
                                 srrg2_scene_h clipped, srrg2_clip_result* out) {
   if (!full || !clipped || !robot_in_local_map || !p) return fail(SRRG2_E_INVALID, "scene_clip_projective: null argument");
-  if (full == clipped || full->dim != clipped->dim || full->device != clipped->device)
+  if (!clip_pair(full, clipped))
     return fail(SRRG2_E_INVALID, "scene_clip_projective: full and clipped must be two scenes of one dim on one device");
   if (full->dim != 3)
     return fail(SRRG2_E_UNSUPPORTED, "scene_clip_projective: 2-D scenes (a laser scanner's view: srrg2_scene_clip_scan)");
@@ -933,7 +904,7 @@ int srrg2_scene_clip_projective(srrg2_scene_h full, const float* robot_in_local_
   if (p->camera_matrix[1] != 0.f)
     return fail(SRRG2_E_UNSUPPORTED, "scene_clip_projective: a camera matrix with skew (K[0][1] != 0)");
   int rc;
-  if ((rc = scene_device(clipped)) || (rc = scene_device(full))) return rc;
+  if ((rc = clip_begin(full, clipped))) return rc;
   float Linv[12], Sinv[12];
   dm::se3_inverse(robot_in_local_map, Linv);
   dm::se3_inverse(p->sensor_in_robot, Sinv);
@@ -942,10 +913,6 @@ int srrg2_scene_clip_projective(srrg2_scene_h full, const float* robot_in_local_
                     p->image_rows, p->image_cols};
   const bool occlusion = p->occlusion_margin >= 0.f;
   const int n          = full->n;
-  clipped->has_normals = full->has_normals;
-  clipped->has_desc    = full->has_desc;
-  clipped->has_inten   = full->has_inten;
-  clipped->n = clipped->ng = 0;
   // (arrays even for an empty result, as srrg2_scene_set leaves them: srrg2_scene_device_arrays then shows the normals' presence)
   if ((rc = scene_reserve(clipped, 1, 0)) || (rc = clipped->gidx.reserve(1))) return rc;
   if (out) {
@@ -955,11 +922,8 @@ int srrg2_scene_clip_projective(srrg2_scene_h full, const float* robot_in_local_
   if (n == 0) return 0;
   hipStream_t st = full->stream;
   if ((rc = full->flags.reserve((size_t) n + 1))) return rc;
-  // (the two counts in front of the scan's total at the tail of its scratch: one copy brings all three to the host)
-  if ((rc = full->scan_sums.reserve((size_t) srrg2amd::scan_num_blocks(n) + 4))) return rc;
-  int* const counters = full->scan_sums.p + full->scan_sums.cap - 3;
-  int* const dtotal   = counters + 2;
-  HIP_TRY(hipMemsetAsync(counters, 0, 2 * sizeof(int), st));
+  int* const counters = full->dscalars.p;  // (compact_into brings them to the host with the scan's total)
+  HIP_TRY(hipMemsetAsync(counters, 0, CLIP_TOTAL * sizeof(int), st));
   const dim3 grid(blocks_for(n));
   if (occlusion) {
     const size_t npix = (size_t) cam.rows * (size_t) cam.cols;
@@ -971,33 +935,11 @@ int srrg2_scene_clip_projective(srrg2_scene_h full, const float* robot_in_local_
     hipLaunchKernelGGL(k_pclip_flag<false>, grid, dim3(256), 0, st, L, S, cam, full->pts.p, n, (const unsigned*) nullptr,
                        full->flags.p, counters);
   }
-  srrg2amd::launch_exclusive_scan(full->flags.p, n, full->scan_sums.p, dtotal, st);
-  // as clip_ball: the scatter goes behind the scan into the room `clipped` has, before the host knows the total -- one wait per
-  // clip; a total beyond the room repeats the scatter with room for all
-  const int room = (int) std::min<size_t>(std::min(clipped->pts.cap, clipped->nrm.cap), clipped->gidx.cap);
-  {
-    const Feat f = feat_of(full, clipped);
-    LAUNCH_FEAT(k_pclip_scatter, moves_features(f), grid, st, L, full->pts.p, full->has_normals ? full->nrm.p : nullptr, n,
-                full->flags.p, clipped->pts.p, clipped->nrm.p, clipped->gidx.p, room, f);
-  }
-  HIP_TRY(hipMemcpyAsync(&full->scalars[0], counters, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
-  const int num_valid = full->scalars[0], num_in_view = full->scalars[1], total = full->scalars[2];
-  if (total > room) {
-    if ((rc = scene_reserve(clipped, total, 0))) return rc;
-    if ((rc = clipped->gidx.reserve((size_t) total))) return rc;
-    const Feat f = feat_of(full, clipped);
-    LAUNCH_FEAT(k_pclip_scatter, moves_features(f), grid, st, L, full->pts.p, full->has_normals ? full->nrm.p : nullptr, n,
-                full->flags.p, clipped->pts.p, clipped->nrm.p, clipped->gidx.p, total, f);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-  }
-  clipped->n = clipped->ng = total;
+  if ((rc = compact_into(full, clipped, L, n))) return rc;
   if (out) {
-    out->num_valid   = num_valid;
-    out->num_in_view = num_in_view;
-    out->num_kept    = total;
+    out->num_valid   = full->scalars[CLIP_VALID];
+    out->num_in_view = full->scalars[CLIP_IN_VIEW];
+    out->num_kept    = full->scalars[CLIP_TOTAL];
   }
   return 0;
 }
@@ -1014,7 +956,7 @@ void srrg2_clip_default_scan_params(srrg2_scan_clip_params* p) {
 int srrg2_scene_clip_scan(srrg2_scene_h full, const float* robot_in_local_map, const srrg2_scan_clip_params* p,
                           srrg2_scene_h clipped, srrg2_clip_result* out) {
   if (!full || !clipped || !robot_in_local_map || !p) return fail(SRRG2_E_INVALID, "scene_clip_scan: null argument");
-  if (full == clipped || full->dim != clipped->dim || full->device != clipped->device)
+  if (!clip_pair(full, clipped))
     return fail(SRRG2_E_INVALID, "scene_clip_scan: full and clipped must be two scenes of one dim on one device");
   if (full->dim != 2)
     return fail(SRRG2_E_UNSUPPORTED, "scene_clip_scan: 3-D scenes (lidar rings are not built; a camera: srrg2_scene_clip_projective)");
@@ -1032,7 +974,7 @@ int srrg2_scene_clip_scan(srrg2_scene_h full, const float* robot_in_local_map, c
   if (!(p->range_min > 0.f) || !(p->range_max >= p->range_min)) return fail(SRRG2_E_INVALID, "scene_clip_scan: 0 < range_min <= range_max");
   if (std::isnan(p->occlusion_margin)) return fail(SRRG2_E_INVALID, "scene_clip_scan: occlusion_margin is NaN");
   int rc;
-  if ((rc = scene_device(clipped)) || (rc = scene_device(full))) return rc;
+  if ((rc = clip_begin(full, clipped))) return rc;
   float Linv[9], Sinv[9];
   dm::se2_inverse(robot_in_local_map, Linv);
   dm::se2_inverse(p->sensor_in_robot, Sinv);
@@ -1042,10 +984,6 @@ int srrg2_scene_clip_scan(srrg2_scene_h full, const float* robot_in_local_map, c
                       p->num_beams};
   const bool occlusion = p->occlusion_margin >= 0.f;
   const int n          = full->n;
-  clipped->has_normals = full->has_normals;
-  clipped->has_desc    = full->has_desc;
-  clipped->has_inten   = full->has_inten;
-  clipped->n = clipped->ng = 0;
   // (arrays even for an empty result, as srrg2_scene_set leaves them: srrg2_scene_device_arrays then shows the normals' presence)
   if ((rc = scene_reserve(clipped, 1, 0)) || (rc = clipped->gidx.reserve(1))) return rc;
   if (out) {
@@ -1055,11 +993,8 @@ int srrg2_scene_clip_scan(srrg2_scene_h full, const float* robot_in_local_map, c
   if (n == 0) return 0;
   hipStream_t st = full->stream;
   if ((rc = full->flags.reserve((size_t) n + 1))) return rc;
-  // (the two counts in front of the scan's total at the tail of its scratch: one copy brings all three to the host)
-  if ((rc = full->scan_sums.reserve((size_t) srrg2amd::scan_num_blocks(n) + 4))) return rc;
-  int* const counters = full->scan_sums.p + full->scan_sums.cap - 3;
-  int* const dtotal   = counters + 2;
-  HIP_TRY(hipMemsetAsync(counters, 0, 2 * sizeof(int), st));
+  int* const counters = full->dscalars.p;  // (compact_into brings them to the host with the scan's total)
+  HIP_TRY(hipMemsetAsync(counters, 0, CLIP_TOTAL * sizeof(int), st));
   const dim3 grid(blocks_for(n));
   if (occlusion) {
     const int nb = geom.num_beams;
@@ -1080,33 +1015,11 @@ int srrg2_scene_clip_scan(srrg2_scene_h full, const float* robot_in_local_map, c
     hipLaunchKernelGGL(k_sclip_flag<false>, grid, dim3(256), 0, st, L, S, geom, full->pts.p, n, (const unsigned*) nullptr,
                        full->flags.p, counters);
   }
-  srrg2amd::launch_exclusive_scan(full->flags.p, n, full->scan_sums.p, dtotal, st);
-  // as clip_ball: the scatter goes behind the scan into the room `clipped` has, before the host knows the total -- one wait per
-  // clip; a total beyond the room repeats the scatter with room for all
-  const int room = (int) std::min<size_t>(std::min(clipped->pts.cap, clipped->nrm.cap), clipped->gidx.cap);
-  {
-    const Feat f = feat_of(full, clipped);
-    LAUNCH_FEAT(k_sclip_scatter, moves_features(f), grid, st, L, full->pts.p, full->has_normals ? full->nrm.p : nullptr, n,
-                full->flags.p, clipped->pts.p, clipped->nrm.p, clipped->gidx.p, room, f);
-  }
-  HIP_TRY(hipMemcpyAsync(&full->scalars[0], counters, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
-  const int num_valid = full->scalars[0], num_in_view = full->scalars[1], total = full->scalars[2];
-  if (total > room) {
-    if ((rc = scene_reserve(clipped, total, 0))) return rc;
-    if ((rc = clipped->gidx.reserve((size_t) total))) return rc;
-    const Feat f = feat_of(full, clipped);
-    LAUNCH_FEAT(k_sclip_scatter, moves_features(f), grid, st, L, full->pts.p, full->has_normals ? full->nrm.p : nullptr, n,
-                full->flags.p, clipped->pts.p, clipped->nrm.p, clipped->gidx.p, total, f);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-  }
-  clipped->n = clipped->ng = total;
+  if ((rc = compact_into(full, clipped, L, n))) return rc;
   if (out) {
-    out->num_valid   = num_valid;
-    out->num_in_view = num_in_view;
-    out->num_kept    = total;
+    out->num_valid   = full->scalars[CLIP_VALID];
+    out->num_in_view = full->scalars[CLIP_IN_VIEW];
+    out->num_kept    = full->scalars[CLIP_TOTAL];
   }
   return 0;
 }

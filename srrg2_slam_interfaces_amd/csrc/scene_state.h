@@ -37,7 +37,8 @@ struct srrg2_scene {
   srrg2amd::DevBuf<int> alt_gidx, nrm_idx, nrm_ctr;
   srrg2amd::DevBuf<unsigned long long> nrm_keys;
   int* scalars = nullptr;  // pinned host mirror of dscalars
-  // device: [0] scan total, [1] num_merged, [2] error flag, [3] duplicates seen, [4] ncorr (merge); [8] in range, [9] Valid (adapt)
+  // device: [1] num_merged, [2] error flag, [3] duplicates seen, [4] ncorr (merge); [0] Valid, [1] in view, [2] scan total (clip);
+  // [8] in range, [9] Valid (adapt)
   srrg2amd::DevBuf<int> dscalars;
 };
 

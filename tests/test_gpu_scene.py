@@ -50,19 +50,61 @@ def test_clip_ball_parity(oracle, product, dim):
     assert 1000 < s_gpu.size() < n
 
 
-def test_clip_into_a_scene_that_has_room_or_not(oracle, product):
+SCAN_TILE = 2048  # kernels_prep.hip: SCAN_THREADS * SCAN_ITEMS, the elements one workgroup of the exclusive scan takes
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, SCAN_TILE, SCAN_TILE + 1])
+@pytest.mark.parametrize("dim", [3, 2])
+def test_clip_ball_at_the_edges_of_the_scan(oracle, product, dim, n):
+    """The scatter keeps point i iff offset[i + 1] != offset[i]: for the LAST point that is the total the scan leaves in
+    offset[n], one word past the flags -- at sizes around the scatter's workgroup and the scan's tile.  The last point is inside
+    the ball and a NaN point sits right before it.  One clipped handle takes the clip twice (fresh: no room, the scatter waits
+    for the total; then with room: launched behind the scan) and a third with a radius that keeps nothing."""
+    rng = np.random.default_rng(1000 * dim + n)
+    sp = rng.uniform(-30, 30, (n, dim)).astype(f32)
+    sn = rng.normal(size=(n, dim)).astype(f32)
+    pose = (syn.se3(np.array([3.0, -2.0, 0.5]), np.deg2rad(np.array([10.0, 5.0, -20.0]))) if dim == 3
+            else syn.se2(3.0, -2.0, 0.7)).astype(f32)
+    sp[-1] = np.array([3.0, -2.0, 0.5], f32)[:dim] + f32(0.25)
+    if n > 1:
+        sp[-2] = np.nan
+    pairs = []
+    for b in _bindings(oracle, product):
+        full, clipped = mapping.Scene(b, dim), mapping.Scene(b, dim)
+        full.set(sp, sn)
+        pairs.append((b, full, clipped))
+    for r in (12.0, 12.0, 1e-3):
+        got = []
+        for b, full, clipped in pairs:
+            cl = mapping.SceneClipperBall(b, range_max=r)
+            cl.set_full_scene(full); cl.set_clipped_scene_in_robot(clipped); cl.set_robot_in_local_map(pose)
+            cl.compute()
+            got.append((cl.global_indices(), clipped))
+        (g_ref, s_ref), (g_gpu, s_gpu) = got
+        assert np.array_equal(g_ref, g_gpu), r
+        _same_scene(s_ref, s_gpu)
+        assert s_gpu.size() == s_ref.size() == len(g_gpu)
+        if r > 1.0:
+            assert g_gpu[-1] == n - 1 and n - 2 not in g_gpu
+        else:
+            assert s_gpu.size() == 0
+
+
+@pytest.mark.parametrize("dim", [3, 2])
+def test_clip_into_a_scene_that_has_room_or_not(oracle, product, dim):
     """Round 6, last: a clipped scene with room from the clip before gets its scatter launched behind the scan WITHOUT the host having
     seen the total (one wait per clip); a total beyond the room repeats the scatter.  One pair of scenes through a small clip, a larger
     one (beyond the room: repeated), a smaller one again (within the room: speculated), an empty one, and a full one."""
     rng = np.random.default_rng(77)
     n = 120_000
-    sp = rng.uniform(-30, 30, (n, 3)).astype(f32)
-    sn = rng.normal(size=(n, 3)).astype(f32)
+    sp = rng.uniform(-30, 30, (n, dim)).astype(f32)
+    sn = rng.normal(size=(n, dim)).astype(f32)
     sp[::1013] = np.nan
-    pose = syn.se3(np.array([3.0, -2.0, 0.5]), np.deg2rad(np.array([10.0, 5.0, -20.0]))).astype(f32)
+    pose = (syn.se3(np.array([3.0, -2.0, 0.5]), np.deg2rad(np.array([10.0, 5.0, -20.0]))) if dim == 3
+            else syn.se2(3.0, -2.0, 0.7)).astype(f32)
     pairs = []
     for b in _bindings(oracle, product):
-        full, clipped = mapping.Scene(b, 3), mapping.Scene(b, 3)
+        full, clipped = mapping.Scene(b, dim), mapping.Scene(b, dim)
         full.set(sp, sn)
         pairs.append((b, full, clipped))
     sizes = []
