@@ -743,6 +743,52 @@ int  srrg2_scene_estimate_normals(srrg2_scene_h scene, const srrg2_normals_param
  * No device needed. */
 void srrg2_normals_exponents(float radius, int n, int* e1, int* e2);
 
+/* Voxel-grid decimation: `dst` receives one point per occupied cell of a grid of `leaf_size` cubes (squares for dim 2), on the
+ * device.  No reference counterpart (the caller is srrg2_core's cloud voxelize); DESIGN.md section 4 "Voxel-grid decimation" is
+ * the contract and tests/voxel_restatement.py its executable form: the result is a function of the points and the parameters
+ * alone, bit for bit.  The call has a clipper's shape: two distinct scenes of one dim on one device, `src` untouched, `dst`
+ * replaced (it takes src's feature presence and has_normals), srrg2_scene_global_indices(dst) names each emitted point's
+ * representative in src.
+ *   cell            a point takes part iff its dim coordinates are finite; c_d = floor(((double) p_d - origin_d) / leaf) in
+ *                   float64 (dim 2: z ignored; a point on a face belongs to the upper cell; negative coordinates floor down).
+ *   representative  the cell's participating point with the lowest scene index.  A cell is emitted when it has at least
+ *                   min_points_per_voxel participating points; cells come out in ascending order of their representative:
+ *                   "the first point seen of every cell, in scene order".  A cloud with one point per cell comes back unchanged.
+ *   FIRST           the representative verbatim: coordinates, normal, descriptor, intensity.
+ *   CENTROID        coordinates: a cell of one point emits it verbatim; k > 1 points: about corner_d = origin_d + c_d * leaf the
+ *                   offsets are rounded to multiples of 2^-e (half to even), summed in int64, and
+ *                   float32(corner_d + (S_d * 2^-e) / k) comes out; e = e1 of srrg2_normals_exponents(leaf_size, size of src).
+ *                   Normals (src has normals): a normal contributes iff its dim components are finite and below 2 in magnitude;
+ *                   components rounded to multiples of 2^-en (en = e1 of srrg2_normals_exponents(1, size of src)), summed in
+ *                   int64, normalised in float64; NaN when none contributed or the sum is zero.
+ *                   Descriptor and intensity: the representative's (descriptors cannot be averaged).
+ *   counts_out[k]   (host, may be NULL, capacity = the size of src) participating points in the cell of emitted point k; words
+ *                   beyond the size of dst are zeroed.
+ *   result          num_occupied counts cells before the min_points gate, max_points_per_voxel is over the occupied cells,
+ *                   num_with_normal counts the emitted points whose normal has no NaN component (0 when src has no normals).
+ *   refused         `dst` keeps its content.  SRRG2_E_INVALID: a null handle or params; src == dst; different dims or devices; a
+ *                   leaf not finite or <= 0; an origin not finite; a mode outside the enum; min_points_per_voxel < 1; non-zero
+ *                   reserved.  SRRG2_E_UNSUPPORTED: the extent -- cell coordinates are keyed relative to the lowest occupied
+ *                   cell per axis; the 64-bit cell key holds at most 2^30 cells per axis and 63 bits over the axes (as
+ *                   srrg2_scene_estimate_normals).  Memory is O(n) whatever the extent.
+ *   empty src       succeeds, all-zero result, `dst` empty.
+ *   waits           one host wait (a `dst` without room for the result: a second one, as the clippers). */
+enum srrg2_voxel_mode { SRRG2_VOXEL_CENTROID = 0, SRRG2_VOXEL_FIRST = 1 };
+typedef struct srrg2_voxel_params {
+  float   leaf_size;             /* cell edge [m], finite, > 0; default 0.05 */
+  float   origin[3];             /* a grid corner, scene frame; default 0: the grid is anchored to the frame, not to the data */
+  int32_t mode;                  /* srrg2_voxel_mode; default CENTROID */
+  int32_t min_points_per_voxel;  /* >= 1; default 1; cells with fewer finite points emit nothing */
+  int32_t reserved[2];           /* 0; struct = 32 bytes */
+} srrg2_voxel_params;
+typedef struct srrg2_voxel_result {
+  int32_t num_points, num_finite, num_occupied, num_voxels /* emitted == size of dst */, num_with_normal, max_points_per_voxel;
+} srrg2_voxel_result;
+void srrg2_voxel_default_params(srrg2_voxel_params* p);
+int  srrg2_scene_voxelize(srrg2_scene_h src, const srrg2_voxel_params* p, srrg2_scene_h dst,
+                          int32_t* counts_out /* host, may be NULL, capacity = size of src */,
+                          srrg2_voxel_result* out /* may be NULL */);
+
 /* MergerCorrespondenceHomo_::compute() (S/mapping/merger_correspondence_homo_impl.cpp:11-125).
  * correspondences: fixed_idx = scene point, moving_idx = measurement point, processed in order
  * (a scene point hit twice sees the first update, :55-73); n_correspondences < 0 = "no

@@ -488,6 +488,23 @@ public:
     check(srrg2_scene_estimate_normals(_h, &p, curvature && !curvature->empty() ? curvature->data() : nullptr, &r));
     return r;
   }
+  // voxel-grid decimation into `dst` (srrg2_scene_voxelize; defaults: srrg2_voxel_default_params(&p)): this scene stays as it is,
+  // dst.globalIndices() names every emitted point's representative here.  counts: points per emitted cell.
+  srrg2_voxel_result voxelize(const srrg2_voxel_params& p, Scene<DIM>& dst, std::vector<int32_t>* counts = nullptr) {
+    srrg2_voxel_result r;
+    if (counts) counts->assign((size_t) size(), 0);
+    check(srrg2_scene_voxelize(_h, &p, dst._h, counts && !counts->empty() ? counts->data() : nullptr, &r));
+    if (counts) counts->resize((size_t) r.num_voxels);
+    return r;
+  }
+  // local -> global indices of the last clip / decimation INTO this scene
+  std::vector<int> globalIndices() const {
+    int n = 0;
+    check(srrg2_scene_global_indices(_h, nullptr, &n));
+    std::vector<int> g((size_t) n);
+    if (n > 0) check(srrg2_scene_global_indices(_h, g.data(), &n));
+    return g;
+  }
   srrg2_scene_h handle() const { return _h; }
 
 private:

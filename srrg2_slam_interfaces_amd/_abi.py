@@ -198,6 +198,24 @@ class NormalsResult(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+VOXEL_CENTROID, VOXEL_FIRST = 0, 1
+
+
+class VoxelParams(C.Structure):
+    """srrg2_voxel_params"""
+    _fields_ = [("leaf_size", C.c_float), ("origin", C.c_float * 3), ("mode", C.c_int32), ("min_points_per_voxel", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class VoxelResult(C.Structure):
+    """srrg2_voxel_result"""
+    _fields_ = [("num_points", C.c_int32), ("num_finite", C.c_int32), ("num_occupied", C.c_int32), ("num_voxels", C.c_int32),
+                ("num_with_normal", C.c_int32), ("max_points_per_voxel", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 def transform_size(variable_kind):
     return 9 if variable_kind == SE2_RIGHT else 12
 

@@ -75,6 +75,11 @@ def lib():
         _LIB.srrg2_normals_exponents.restype = None
         _LIB.srrg2_scene_estimate_normals.argtypes = [C.c_void_p, C.POINTER(abi.NormalsParams), C.POINTER(C.c_float),
                                                       C.POINTER(abi.NormalsResult)]
+        # srrg2_scene_voxelize (mapping.Scene.voxelize)
+        _LIB.srrg2_voxel_default_params.argtypes = [C.POINTER(abi.VoxelParams)]
+        _LIB.srrg2_voxel_default_params.restype = None
+        _LIB.srrg2_scene_voxelize.argtypes = [C.c_void_p, C.POINTER(abi.VoxelParams), C.c_void_p, C.POINTER(C.c_int32),
+                                              C.POINTER(abi.VoxelResult)]
     return _LIB
 
 

@@ -2,9 +2,8 @@
 // (a 3-D lidar sweep, a map from disk, a merged map whose averaged normals have drifted).  No reference counterpart; DESIGN.md
 // section 4 "Normals of unorganised scenes" is the arithmetic contract and tests/normals_restatement.py its executable form: the
 // result is a function of the points, the radius and the scene size alone, bit for bit.
-//   k_nrm_bbox      box of the finite points (dim coordinates) + their number
-//   k_nrm_spec      one thread: cells per axis and the bits each axis gets in the 64-bit cell key, or "beyond the key range"
-//   k_nrm_keys      cell key of every point (x fastest); non-finite points get the all-ones key and sort to the end
+//   k_grid_bbox / k_grid_spec / k_grid_keys   (cell_grid.h) box of the finite points, the cells' layout in the 64-bit key, a
+//                   cell key per point; non-finite points get the all-ones key and sort to the end
 //   (radix sort of (key, index) pairs: hipcub)
 //   k_nrm_gather    the points in cell order, .w = index in the scene
 //   k_nrm_neigh     THE pass: one wave per 64 consecutive sorted queries -- membership, fixed-point moments, covariance,
@@ -20,6 +19,7 @@
 #include <cstring>
 #include <string>
 
+#include "cell_grid.h"
 #include "device_types.h"
 #include "host_util.h"
 #include "kernels.h"
@@ -35,19 +35,11 @@ namespace {
 #define SRRG2_NRM_TILE 64
 // cyclic Jacobi sweeps over (0,1), (0,2), (1,2): DESIGN.md section 4
 #define SRRG2_NRM_SWEEPS 6
-// a cell coordinate has at most 30 bits, the three of them 63 in all
-#define SRRG2_NRM_AXIS_BITS 30
-#define SRRG2_NRM_KEY_BITS 63
+// counters block (ints): the grid's words (cell_grid.h: [0] finite points, [5] beyond the key range, [8, 14) the box) and, in
+// between, [1] with normal, [2] too few, [3] degenerate, [4] too curved, [6] scan total
+enum { C_FINITE = GRID_FINITE, C_NORMAL = 1, C_FEW = 2, C_DEGEN = 3, C_CURVED = 4, C_UNSUP = GRID_UNSUP, C_TOTAL = 6, C_WORDS = GRID_WORDS };
 
-// counters block (ints): [0] finite points, [1] with normal, [2] too few, [3] degenerate, [4] too curved, [5] beyond the key
-// range, [6] scan total; [8, 11) complemented keys of the box minimum, [11, 14) keys of the maximum (zero-initialised, atomicMax)
-enum { C_FINITE = 0, C_NORMAL = 1, C_FEW = 2, C_DEGEN = 3, C_CURVED = 4, C_UNSUP = 5, C_TOTAL = 6, C_MIN = 8, C_MAX = 11, C_WORDS = 16 };
-
-struct NrmSpec {  // written by k_nrm_spec
-  double mn[3], h;
-  int cmax[3], shift[3];
-  int unsupported, nfinite;
-};
+typedef GridSpec NrmSpec;
 
 struct NrmArgs {
   float r2;               // one float32 product
@@ -59,101 +51,6 @@ struct NrmArgs {
   double vp[3];
   int nan_if_unsupported;  // the call returns before the host knows: the normals become NaN instead of staying stale
 };
-
-__device__ __forceinline__ unsigned okey(float f) {
-  const unsigned b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float okey_inv(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-template <int DIM>
-__device__ __forceinline__ bool nrm_finite(const float4 p) {
-  return isfinite(p.x) && isfinite(p.y) && (DIM == 2 || isfinite(p.z));
-}
-
-template <int DIM>
-__global__ __launch_bounds__(256) void k_nrm_bbox(const float4* __restrict__ pts, int n, int* __restrict__ ctr) {
-  unsigned mn[3] = {0u, 0u, 0u}, mx[3] = {0u, 0u, 0u};  // (mn complemented: a maximum as well)
-  int valid = 0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float4 p = pts[i];
-    if (!nrm_finite<DIM>(p)) continue;
-    ++valid;
-    const float v[3] = {p.x, p.y, p.z};
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) {
-      const unsigned k = okey(v[d]);
-      mn[d] = max(mn[d], ~k);
-      mx[d] = max(mx[d], k);
-    }
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) {
-      mn[d] = max(mn[d], (unsigned) __shfl_xor((int) mn[d], off));
-      mx[d] = max(mx[d], (unsigned) __shfl_xor((int) mx[d], off));
-    }
-    valid += __shfl_xor(valid, off);
-  }
-  if ((threadIdx.x & 63) == 0 && valid) {  // one atomic per wave and word (a few grid-striding blocks)
-    unsigned* u = reinterpret_cast<unsigned*>(ctr);
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) {
-      atomicMax(&u[C_MIN + d], mn[d]);
-      atomicMax(&u[C_MAX + d], mx[d]);
-    }
-    atomicAdd(&ctr[C_FINITE], valid);
-  }
-}
-
-__device__ __forceinline__ int nrm_cell(double p, double mn, double h, int cmax) {
-  const double q = floor((p - mn) / h);
-  return q < 0.0 ? 0 : (q > (double) cmax ? cmax : (int) q);  // (inside by monotonicity; the clamp keeps a key's fields apart)
-}
-
-__global__ void k_nrm_spec(int dim, float radius, int* __restrict__ ctr, NrmSpec* __restrict__ spec) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  const unsigned* u = reinterpret_cast<const unsigned*>(ctr);
-  NrmSpec S;
-  S.h           = (double) radius * (1.0 + 0x1p-16);
-  S.nfinite     = ctr[C_FINITE];
-  S.unsupported = 0;
-  int bits_total = 0;
-  for (int d = 0; d < 3; ++d) {
-    S.mn[d] = 0.0, S.cmax[d] = 0, S.shift[d] = bits_total;
-    if (d >= dim || S.nfinite == 0) continue;
-    S.mn[d]        = (double) okey_inv(~u[C_MIN + d]);
-    const double q = floor(((double) okey_inv(u[C_MAX + d]) - S.mn[d]) / S.h);
-    if (!(q < (double) (1 << SRRG2_NRM_AXIS_BITS))) {  // (NaN included)
-      S.unsupported = 1;
-      continue;
-    }
-    S.cmax[d] = (int) q;
-    bits_total += 32 - __clz(S.cmax[d]);
-  }
-  if (bits_total > SRRG2_NRM_KEY_BITS) S.unsupported = 1;
-  ctr[C_UNSUP] = S.unsupported;
-  *spec        = S;
-}
-
-template <int DIM>
-__global__ __launch_bounds__(256) void k_nrm_keys(const NrmSpec* __restrict__ spec, const float4* __restrict__ pts, int n,
-                                                  unsigned long long* __restrict__ keys, int* __restrict__ idx) {
-  const NrmSpec S = *spec;
-  if (S.unsupported) return;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float4 p         = pts[i];
-    unsigned long long key = ~0ull;
-    if (nrm_finite<DIM>(p)) {
-      key = (unsigned long long) nrm_cell((double) p.x, S.mn[0], S.h, S.cmax[0]) |
-            ((unsigned long long) nrm_cell((double) p.y, S.mn[1], S.h, S.cmax[1]) << S.shift[1]);
-      if (DIM == 3) key |= (unsigned long long) nrm_cell((double) p.z, S.mn[2], S.h, S.cmax[2]) << S.shift[2];
-    }
-    keys[i] = key;
-    idx[i]  = i;
-  }
-}
 
 __global__ __launch_bounds__(256) void k_nrm_gather(const NrmSpec* __restrict__ spec, const float4* __restrict__ pts,
                                                     const int* __restrict__ sidx, int n, float4* __restrict__ sorted) {
@@ -238,7 +135,7 @@ __global__ __launch_bounds__(64) void k_nrm_neigh(const NrmSpec* __restrict__ sp
   const float4 me              = s < n ? sorted[s] : make_float4(0.f, 0.f, 0.f, 0.f);
   const unsigned long long key = active ? skeys[s] : ~0ull;
   const int NROWS              = DIM == 3 ? 9 : 3;
-  const unsigned long long row = key >> S.shift[1];  // (shifts <= 60: k_nrm_spec)
+  const unsigned long long row = key >> S.shift[1];  // (shifts <= 60: k_grid_spec)
   const int cx                 = (int) (key & ((1ull << S.shift[1]) - 1ull));
 
   unsigned long long sx = 0, sy = 0, sz = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0;
@@ -513,15 +410,18 @@ extern "C" int srrg2_scene_estimate_normals(srrg2_scene_h s, const srrg2_normals
 
   HIP_TRY(hipMemsetAsync(ctr, 0, C_WORDS * sizeof(int), st));
   const dim3 grid(blocks_for(n)), block(256);
+  GridAnchor anchor;  // cells from the box minimum
+  std::memset(&anchor, 0, sizeof(anchor));
+  anchor.h = (double) p->radius * (1.0 + 0x1p-16);
   if (dim == 3)
-    hipLaunchKernelGGL(k_nrm_bbox<3>, dim3(std::min<int>(grid.x, 64)), block, 0, st, s->pts.p, n, ctr);
+    hipLaunchKernelGGL(k_grid_bbox<3>, dim3(std::min<int>(grid.x, 64)), block, 0, st, s->pts.p, n, ctr);
   else
-    hipLaunchKernelGGL(k_nrm_bbox<2>, dim3(std::min<int>(grid.x, 64)), block, 0, st, s->pts.p, n, ctr);
-  hipLaunchKernelGGL(k_nrm_spec, dim3(1), dim3(64), 0, st, dim, p->radius, ctr, spec);
+    hipLaunchKernelGGL(k_grid_bbox<2>, dim3(std::min<int>(grid.x, 64)), block, 0, st, s->pts.p, n, ctr);
+  hipLaunchKernelGGL(k_grid_spec, dim3(1), dim3(64), 0, st, dim, anchor, ctr, spec);
   if (dim == 3)
-    hipLaunchKernelGGL(k_nrm_keys<3>, grid, block, 0, st, spec, s->pts.p, n, keys, idx);
+    hipLaunchKernelGGL(k_grid_keys<3>, grid, block, 0, st, spec, s->pts.p, n, keys, idx);
   else
-    hipLaunchKernelGGL(k_nrm_keys<2>, grid, block, 0, st, spec, s->pts.p, n, keys, idx);
+    hipLaunchKernelGGL(k_grid_keys<2>, grid, block, 0, st, spec, s->pts.p, n, keys, idx);
   size_t tmp_bytes = 0;
   HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, skeys, idx, sidx, n, 0, 64, st));
   if ((rc = s->sort_tmp.reserve(std::max<size_t>(tmp_bytes, 1)))) return rc;

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -588,26 +589,32 @@ void launch_scatter_kept(srrg2_scene* full, srrg2_scene* clipped, const Xf& L, i
 // is launched BEHIND the scan without the host having seen the total -- one wait per clip instead of two (0.046 -> ~0.03 ms for a
 // 100 k-point map); the kernel's k >= cap guard keeps it inside the room, and a total beyond the room repeats it with room for
 // all (the scan runs once: its offsets still stand).
-int compact_into(srrg2_scene* full, srrg2_scene* clipped, const Xf& L, int n) {
+int compact_scatter(srrg2_scene* full, srrg2_scene* clipped, int n, const std::function<void(int cap)>& scatter,
+                    const std::function<int()>& before_wait) {
   int rc;
   hipStream_t st = full->stream;
   if ((rc = full->scan_sums.reserve((size_t) srrg2amd::scan_num_blocks(n)))) return rc;
   srrg2amd::launch_exclusive_scan(full->flags.p, n, full->scan_sums.p, full->dscalars.p + CLIP_TOTAL, st);
   if ((rc = features_reserve(clipped, 0))) return rc;  // (room for features wherever there is room for points)
   const int room = (int) std::min({clipped->pts.cap, clipped->nrm.cap, clipped->gidx.cap});
-  if (room > 0) launch_scatter_kept(full, clipped, L, n, room);
+  if (room > 0) scatter(room);
+  if (before_wait && (rc = before_wait())) return rc;
   HIP_TRY(hipMemcpyAsync(full->scalars, full->dscalars.p, (CLIP_TOTAL + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
   const int total = full->scalars[CLIP_TOTAL];
   if (total > room) {
     if ((rc = scene_reserve(clipped, total, 0)) || (rc = clipped->gidx.reserve((size_t) total))) return rc;
-    launch_scatter_kept(full, clipped, L, n, total);
+    scatter(total);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
   }
   clipped->n = clipped->ng = total;
   return 0;
+}
+
+int compact_into(srrg2_scene* full, srrg2_scene* clipped, const Xf& L, int n) {
+  return compact_scatter(full, clipped, n, [&](int cap) { launch_scatter_kept(full, clipped, L, n, cap); }, nullptr);
 }
 
 int check_params(const srrg2_merger_params* p) {
@@ -699,6 +706,7 @@ int srrg2_scene_destroy(srrg2_scene_h s) {
   s->counts.release(); s->dup_list.release(); s->dup_keys.release(); s->sort_tmp.release(); s->merged.release(); s->corr.release(); s->staging.release(); s->zmin.release(); s->rmin.release(); s->dscalars.release();
   s->alt_pts.release(); s->alt_nrm.release(); s->nrm_sorted.release(); s->nrm_tmp.release(); s->alt_desc.release(); s->alt_inten.release();
   s->nrm_curv.release(); s->alt_gidx.release(); s->nrm_idx.release(); s->nrm_ctr.release(); s->nrm_keys.release();
+  s->vox_acc.release(); s->vox_rep.release(); s->vox_rank.release(); s->vox_cnt.release(); s->vox_counts.release(); s->vox_pts.release(); s->vox_nrm.release();
   if (s->scalars) (void) hipHostFree(s->scalars);
   if (s->stream) (void) hipStreamDestroy(s->stream);
   delete s;
@@ -1148,6 +1156,15 @@ int srrg2_scene_merge_from_aligner(srrg2_scene_h scene, srrg2_scene_h meas, cons
 int srrg2amd::scene_make_room(srrg2_scene* s, int n, int keep) { return scene_reserve(s, n, keep); }
 
 int srrg2amd::scene_scan_flags(srrg2_scene* s, int n, int* total) { return scan_flags(s, n, total); }
+
+bool srrg2amd::scene_clip_pair(const srrg2_scene* full, const srrg2_scene* clipped) { return clip_pair(full, clipped); }
+
+int srrg2amd::scene_clip_begin(srrg2_scene* full, srrg2_scene* clipped) { return clip_begin(full, clipped); }
+
+int srrg2amd::scene_compact_into(srrg2_scene* full, srrg2_scene* clipped, int n, const std::function<void(int cap)>& scatter,
+                                 const std::function<int()>& before_wait) {
+  return compact_scatter(full, clipped, n, scatter, before_wait);
+}
 
 // what descriptors.hip sees of a scene (srrg2_descriptor_db_add_scene / _match_scene)
 int srrg2amd::scene_feature_view(srrg2_scene* s, srrg2amd::SceneFeatureView* v) {

@@ -1,6 +1,8 @@
 // scene_state.h -- what a scene handle holds (srrg2_scene_h), shared by the sources that write scenes: scene.hip (set, clip,
 // merge) and adaptor.hip (measurement adaptors).  Internal to the library.
 #pragma once
+#include <functional>
+
 #include "host_util.h"
 
 struct srrg2_scene {
@@ -36,6 +38,12 @@ struct srrg2_scene {
   srrg2amd::DevBuf<float> alt_inten, nrm_curv;
   srrg2amd::DevBuf<int> alt_gidx, nrm_idx, nrm_ctr;
   srrg2amd::DevBuf<unsigned long long> nrm_keys;
+  // voxelize (voxel.hip; it sorts through the normals' key / index / counters scratch above): per cell the fixed-point sums and
+  // the two counts, the representative's scene index; per sorted entry the cell rank; per representative the emitted point,
+  // normal and count; per emitted point the count
+  srrg2amd::DevBuf<long long> vox_acc;
+  srrg2amd::DevBuf<int> vox_rep, vox_rank, vox_cnt, vox_counts;
+  srrg2amd::DevBuf<float4> vox_pts, vox_nrm;
   int* scalars = nullptr;  // pinned host mirror of dscalars
   // device: [1] num_merged, [2] error flag, [3] duplicates seen, [4] ncorr (merge); [0] Valid, [1] in view, [2] scan total (clip);
   // [8] in range, [9] Valid (adapt)
@@ -48,5 +56,15 @@ namespace srrg2amd {
 int scene_make_room(srrg2_scene* s, int n, int keep);
 // s->flags[0..n) -> exclusive scan in place; the total comes back on the host (one wait on the scene's stream)
 int scene_scan_flags(srrg2_scene* s, int n, int* total);
+// two distinct scenes of one dim on one device: what a clipper -- or the voxelizer -- reads and what it writes
+bool scene_clip_pair(const srrg2_scene* full, const srrg2_scene* clipped);
+// both scenes current and quiet; `clipped` takes the fields of `full` and is empty until the call has succeeded
+int scene_clip_begin(srrg2_scene* full, srrg2_scene* clipped);
+// The tail of every call that keeps some points of `full`, in scene order, in `clipped`: the n > 0 keep flags queued in
+// full->flags (n + 1 words reserved) are scanned in place; scatter(cap) launches, on full->stream, the kernel that moves a kept
+// point i to clipped's slot k = flags[i] when flags[i + 1] != k and k < cap; before_wait (may be empty) queues what else the one
+// host wait shall carry.  clipped->n = ng = the total when it returns (details at compact_into, scene.hip).
+int scene_compact_into(srrg2_scene* full, srrg2_scene* clipped, int n, const std::function<void(int cap)>& scatter,
+                       const std::function<int()>& before_wait);
 
 }  // namespace srrg2amd

@@ -74,6 +74,19 @@ def default_scan_clip_params():
     return p
 
 
+VoxelParams, VoxelResult = abi.VoxelParams, abi.VoxelResult
+VOXEL_MODES = {"centroid": abi.VOXEL_CENTROID, "first": abi.VOXEL_FIRST}
+
+
+def default_voxel_params():
+    """leaf 0.05 m, origin 0 (the grid is anchored to the frame), centroid mode, min_points_per_voxel 1"""
+    from . import _capi
+
+    p = VoxelParams()
+    _capi.lib().srrg2_voxel_default_params(C.byref(p))
+    return p
+
+
 def default_merger_params():
     """merger.h:126-131, merger_correspondence_homo.h:22-31"""
     return MergerParams(50.0, 0.25, 200)
@@ -238,6 +251,31 @@ class Scene:
         self._b.check(f(self._h, C.byref(p), _fp(curv) if return_curvature else None, C.byref(out) if want_result else None))
         res = out.as_dict() if want_result else None
         return (res, curv[:n]) if return_curvature else res
+
+    def voxelize(self, dst, leaf_size, origin=(0.0, 0.0, 0.0), mode="centroid", min_points=1, return_counts=False,
+                 want_result=True):
+        """voxel-grid decimation into the scene ``dst`` (srrg2_scene_voxelize; product library only): one point per occupied
+        cell of ``leaf_size``, in the order of each cell's first point; this scene is left untouched and
+        ``dst.global_indices()`` names every emitted point's representative here.  ``mode``: "centroid" (the cell's mean point
+        and mean normal, the representative's descriptor and intensity) or "first" (the representative verbatim).  Returns the
+        counts as a dict (None without ``want_result``) -- with ``return_counts`` the pair (counts, points per emitted cell)."""
+        f = self._feature_fn("voxelize")
+        p = VoxelParams()
+        self._b.lib.srrg2_voxel_default_params(C.byref(p))
+        p.leaf_size = float(leaf_size)
+        o = tuple(float(v) for v in origin) + (0.0,) * (3 - len(origin))
+        for k in range(3):
+            p.origin[k] = o[k]
+        if mode not in VOXEL_MODES:
+            raise ValueError("voxelize: mode is 'centroid' or 'first', got %r" % (mode,))
+        p.mode = VOXEL_MODES[mode]
+        p.min_points_per_voxel = int(min_points)
+        out = VoxelResult()
+        counts = np.zeros(max(self.size(), 1), np.int32) if return_counts else None
+        self._b.check(f(self._h, C.byref(p), dst._h, counts.ctypes.data_as(C.POINTER(C.c_int32)) if return_counts else None,
+                        C.byref(out) if want_result else None))
+        res = out.as_dict() if want_result else None
+        return (res, counts[:dst.size()]) if return_counts else res
 
     def device_arrays(self):
         """(coords_ptr, normals_ptr or None, n): device float4 arrays (product backend only)."""
