@@ -50,7 +50,7 @@ def test_clip_ball_parity(oracle, product, dim):
     assert 1000 < s_gpu.size() < n
 
 
-SCAN_TILE = 2048  # kernels_prep.hip: SCAN_THREADS * SCAN_ITEMS, the elements one workgroup of the exclusive scan takes
+from scene_large_cases import SCAN_TILE  # noqa: E402  (the scan beyond T * T elements: tests/test_gpu_scene_large.py)
 
 
 @pytest.mark.parametrize("n", [1, 255, 256, 257, SCAN_TILE, SCAN_TILE + 1])
