@@ -679,7 +679,8 @@ int srrg2_scene_clip_projective(srrg2_scene_h full, const float* robot_in_local_
  *             num_beams <= 0; angle_increment zero or not finite; angle_min not finite or |angle_min| > 2 pi;
  *             |angle_increment| * num_beams beyond 2 pi plus one increment (361 beams over 360 degrees are legal, two turns are
  *             not; a relative slack of 2^-20 admits increments rounded to float32); !(range_min > 0) or
- *             !(range_max >= range_min); a NaN margin.  SRRG2_E_UNSUPPORTED: scenes of dim 3 (3-D lidar rings are not built).
+ *             !(range_max >= range_min); a NaN margin.  SRRG2_E_UNSUPPORTED: scenes of dim 3 (a 3-D lidar's view:
+ *             srrg2_scene_clip_spherical; a camera's: srrg2_scene_clip_projective).
  *   status    Ready when `full` is empty, else Successful -- also when nothing is kept (`clipped` is then empty). */
 typedef struct srrg2_scan_clip_params {
   double  angle_min, angle_increment;   /* as srrg2_scan_adaptor_params: bearing of beam k = angle_min + k*angle_increment */
@@ -692,6 +693,53 @@ typedef struct srrg2_scan_clip_params {
 void srrg2_clip_default_scan_params(srrg2_scan_clip_params* p);
 int srrg2_scene_clip_scan(srrg2_scene_h full, const float* robot_in_local_map /* 3x3 */, const srrg2_scan_clip_params* p,
                           srrg2_scene_h clipped, srrg2_clip_result* out /* may be NULL */);
+
+/* The spherical sensor model of a spinning 3-D lidar: a range image of rows (rings, uniformly spaced in elevation) x cols
+ * (azimuth steps).  Shared by srrg2_adapt_lidar_sweep and srrg2_scene_clip_spherical, which project a sensor-frame point
+ * c = (x, y, z) the same way (DESIGN.md section 4 "Lidar sweeps" is the arithmetic contract):
+ *   rho = sqrtf((x*x + y*y) + z*z), range_min <= rho <= range_max;
+ *   azimuth dm::atan2(y, x) binned to the nearest column after at most one turn of 2 pi either way (as clip_scan bins a
+ *   bearing); elevation dm::atan2(z, sqrt(x*x + y*y)) binned to the nearest row, no wrap; pixel = row*cols + col.
+ *   invalid   (SRRG2_E_INVALID from both calls) rows or cols <= 0 or rows*cols beyond int32; an increment zero or not finite;
+ *             azimuth_min not finite or |azimuth_min| > 2 pi; |azimuth_increment| * cols beyond 2 pi plus one increment (slack
+ *             2^-20, as clip_scan); elevation_min not finite, or the first or last row's elevation outside [-pi/2, pi/2]
+ *             (slack 2^-20); !(range_min > 0) or !(range_max >= range_min).
+ *   wrap      the columns close the circle iff | |azimuth_increment| * cols - 2 pi | <= 2 pi * 2^-20 (the adaptor's normals). */
+typedef struct srrg2_spherical_model {
+  double  azimuth_min, azimuth_increment;     /* azimuth of column c = azimuth_min + c*azimuth_increment (radians; negative
+                                                 increment = clockwise) */
+  double  elevation_min, elevation_increment; /* elevation of row r = elevation_min + r*elevation_increment (negative increment
+                                                 = row 0 on top) */
+  int32_t rows, cols;
+  float   range_min, range_max;               /* accepted range, both inclusive */
+} srrg2_spherical_model;
+/* a full turn: azimuth_increment = 2 pi / cols, azimuth_min = -pi + pi / cols (the columns tile [-pi, pi)), elevation_min =
+ * elevation_first, elevation_increment = (elevation_last - elevation_first) / (rows - 1), range 0.5 .. 120 m.
+ * SRRG2_E_INVALID (m unchanged): null m, rows < 2, cols < 1, elevations not finite or equal. */
+int srrg2_spherical_model_full_turn(srrg2_spherical_model* m, int rows, int cols, double elevation_first, double elevation_last);
+
+/* SceneClipper_::compute() with the spherical policy, the 3-D twin of the scan one.  Keeps the Valid points of a 3-D `full`
+ * that a lidar mounted at sensor_in_robot sees from robot_in_local_map:
+ *   r = robot_in_local_map^-1 * p, c = sensor_in_robot^-1 * r (c finite), projected by the model above;
+ *   occlusion_margin < 0: every in-view point is kept (field of view only); >= 0: only those with
+ *   rho <= (minimum rho over the in-view points of the pixel) + occlusion_margin -- 0 keeps every point that ties for the
+ *   minimum, +inf equals field of view only.
+ * Output as clip_ball: the kept points in scene order, in the ROBOT frame (r, bit for bit what clip_ball writes for the same
+ * point), normals rotated, global indices, features and their presence.  srrg2_clip_result.num_in_view: inside the range
+ * interval and the image.
+ *   refused   `clipped` unchanged.  SRRG2_E_INVALID: a null handle, pose or params; full == clipped; different devices or dims;
+ *             an invalid model; a NaN margin; reserved != 0.  SRRG2_E_UNSUPPORTED: scenes of dim 2 (srrg2_scene_clip_scan).
+ *   status    Ready when `full` is empty, else Successful -- also when nothing is kept (`clipped` is then empty). */
+typedef struct srrg2_spherical_clip_params {
+  srrg2_spherical_model model;
+  float   sensor_in_robot[12];
+  float   occlusion_margin;   /* < 0: field of view only; >= 0: metres behind the nearest point of the pixel */
+  int32_t reserved;           /* 0 */
+} srrg2_spherical_clip_params;
+/* identity sensor, range 0.5 .. 120 m, margin -1 (field of view only); the model's angles / rows / cols (0) are the caller's */
+void srrg2_clip_default_spherical_params(srrg2_spherical_clip_params* p);
+int srrg2_scene_clip_spherical(srrg2_scene_h full, const float* robot_in_local_map, const srrg2_spherical_clip_params* p,
+                               srrg2_scene_h clipped, srrg2_clip_result* out /* may be NULL */);
 
 /* Normals for a scene that arrived as a plain list of points (a 3-D lidar sweep, a map from disk, srrg2_scene_set without
  * normals, a merged map whose averaged normals have drifted): per point the PCA of its radius neighbourhood, on the device.
@@ -810,11 +858,12 @@ int srrg2_scene_merge_from_aligner(srrg2_scene_h scene, srrg2_scene_h measuremen
 /* ---- measurement adaptors: raw sensor data -> measurement scene, on the device ---------------------------------
  * The adapt step of MultiTrackerBase_::compute() (S/trackers/multi_tracker_impl.cpp:57-80 ->
  * S/trackers/tracker_slice_processor_base_impl.cpp:32-49 -> RawDataPreprocessor_::compute(),
- * S/raw_data_preprocessors/raw_data_preprocessor.h:13-88).  The reference ships the interface only; the two concrete
+ * S/raw_data_preprocessors/raw_data_preprocessor.h:13-88).  The reference ships the interface only; the concrete
  * adaptors here are defined from first principles (DESIGN.md section 4 "Measurement adaptors" is the arithmetic contract):
  *   depth image -> PointNormal3f cloud   pinhole unprojection, normals from the cross product of two central differences
  *   laser scan  -> PointNormal2f cloud   polar -> Cartesian, normals from the chord between beams k-w and k+w
- * Both write straight into a scene (replacing its content like srrg2_scene_set; global indices and descriptors are
+ *   lidar sweep -> PointNormal3f cloud   point list -> range image (nearest point per pixel), normals as for the depth image
+ * All write straight into a scene (replacing its content like srrg2_scene_set; global indices and descriptors are
  * dropped), so the frame is adapt -> clip -> align -> merge on device handles. */
 
 /* RawDataPreprocessor_::Status, raw_data_preprocessor.h:22 (values identical) */
@@ -876,6 +925,39 @@ int srrg2_adapt_depth_image(srrg2_scene_h dst, const void* depth, int depth_type
  * (num_beams < 0, normal_half_window < 0); compact: global indices = beam indices. */
 int srrg2_adapt_laser_scan(srrg2_scene_h dst, const float* ranges, int num_beams, int mem,
                            const srrg2_scan_adaptor_params* p, srrg2_adapt_result* out /* may be NULL */);
+
+/* 3-D lidar sweep (a list of n points x, y, z in the sensor frame) -> organised or compact PointNormal3f cloud, through the
+ * range image of srrg2_spherical_model (declared with srrg2_scene_clip_spherical; DESIGN.md section 4 "Lidar sweeps").
+ *   bin       every point with finite coordinates is projected; of the points of one pixel the nearest wins, of equal ranges
+ *             the lowest input index: the result depends on the points alone.
+ *   scene     pixel by pixel, as the depth adaptor: an empty pixel is a NaN point; an occupied one stores its winner's input
+ *             coordinates verbatim.  Normal: the cross product of the central differences over c +- normal_col_gap (modulo cols
+ *             when the columns wrap) and r +- normal_row_gap, all four neighbours occupied and inside the image, each
+ *             difference within normal_max_distance_squared, normalised, turned towards the sensor.  Validity,
+ *             drop_points_without_normal and compact as srrg2_depth_adaptor_params.
+ *   intensity NULL: dst has no features afterwards; else dst gets the intensity feature, the winner's value (an empty pixel
+ *             of an organised scene: 0).  intensity = points + 3 with both strides 16 reads interleaved XYZI records.
+ *   result    num_raw = n, num_in_range = occupied pixels, num_valid, scene_size; status INITIALIZING when n == 0 (dst is then
+ *             an empty scene), else READY.
+ *   refused   SRRG2_E_INVALID, dst unchanged: wrong dim, null params, null points with n > 0, n < 0, a stride < 12 (intensity:
+ *             < 4) or no multiple of 4, a pointer not 4-byte aligned, bad mem, an invalid model, a gap < 0 or exactly one of
+ *             the two gaps 0, reserved != 0.
+ *   waits     as srrg2_adapt_depth_image: organised mode with out == NULL queues its work on the scene's stream and returns.
+ *             A SRRG2_MEM_HOST cloud is consumed before the call returns.  A SRRG2_MEM_DEVICE cloud must stay untouched until
+ *             the next srrg2_scene_* call on dst settles it. */
+typedef struct srrg2_lidar_adaptor_params {
+  srrg2_spherical_model model;
+  int32_t normal_col_gap, normal_row_gap; /* pixels; both 0 = no normals; exactly one 0 = SRRG2_E_INVALID */
+  float   normal_max_distance_squared;    /* gate on each of the two difference vectors; default 1.0 (untuned) */
+  int32_t drop_points_without_normal;     /* default 1 */
+  int32_t compact;                        /* 0: organised rows*cols, empty = NaN; 1: only the Valid points, pixel order */
+  int32_t reserved;                       /* 0 */
+} srrg2_lidar_adaptor_params;
+/* model zeroed except range 0.5 .. 120 m; gaps 1 / 1; normal_max_distance_squared 1.0; drop 1; organised */
+void srrg2_adapt_default_lidar_params(srrg2_lidar_adaptor_params* p);
+int srrg2_adapt_lidar_sweep(srrg2_scene_h dst /* dim 3 */, const float* points, int point_stride_bytes,
+                            const float* intensity /* may be NULL */, int intensity_stride_bytes, int n, int mem,
+                            const srrg2_lidar_adaptor_params* p, srrg2_adapt_result* out /* may be NULL */);
 
 /* ---- strategy knobs (no reference counterpart) ----------------------------------------------------------------
  * Every setting gives the SAME results (indices, estimates, statistics bit for bit): the knobs choose between exact

@@ -424,6 +424,7 @@ private:
 //   SceneClipperBall            SceneClipper_<Estimate, Scene>              S/mapping/scene_clipper.h:17-122
 //   SceneClipperProjective      the same interface, projective policy (3-D): what a pinhole camera sees of the scene
 //   SceneClipperScan            the same interface, scan policy (2-D): what a planar laser scanner sees of the scene
+//   SceneClipperSpherical       the same interface, spherical policy (3-D): what a spinning lidar sees of the scene
 //   MergerCorrespondenceHomo    MergerCorrespondenceHomo_<Estimate, Scene>  S/mapping/merger_correspondence_homo.h
 template <int DIM>
 class Scene {
@@ -618,6 +619,44 @@ private:
   Status _status = Error;
 };
 
+// the points of a 3-D scene that a spinning lidar at sensor_in_robot sees (srrg2_scene_clip_spherical): param.model (e.g. from
+// srrg2_spherical_model_full_turn) and occlusion_margin are the PARAMs; last() holds the counts of the last compute()
+class SceneClipperSpherical {
+public:
+  enum Status { Error = 0, Successful = 1, Ready = 2 };  // scene_clipper.h:24-28
+  using EstimateType = Isometry<3>;
+  using SceneType    = Scene<3>;
+  srrg2_spherical_clip_params param;
+  SceneClipperSpherical() { srrg2_clip_default_spherical_params(&param); }
+  void setFullScene(SceneType* s) { _full = s; }
+  void setClippedSceneInRobot(SceneType* s) { _clipped = s; }
+  void setRobotInLocalMap(const EstimateType& T) { _robot_in_local_map = T; }
+  void setSensorInRobot(const EstimateType& T) { std::memcpy(param.sensor_in_robot, T.data(), sizeof(param.sensor_in_robot)); }  // :86-89
+  void setModel(const srrg2_spherical_model& m) { param.model = m; }
+  void compute() {
+    if (!_full || !_clipped) throw std::runtime_error("SceneClipperSpherical::compute|scene not set");
+    _status = Error;
+    check(srrg2_scene_clip_spherical(_full->handle(), _robot_in_local_map.data(), &param, _clipped->handle(), &_last));
+    _status = static_cast<Status>(_last.status);
+  }
+  Status status() const { return _status; }
+  const srrg2_clip_result& last() const { return _last; }
+  std::vector<int> globalIndices() const {  // :98-101
+    int n = 0;
+    check(srrg2_scene_global_indices(_clipped->handle(), nullptr, &n));
+    std::vector<int> v((size_t) n);
+    if (n) check(srrg2_scene_global_indices(_clipped->handle(), v.data(), &n));
+    return v;
+  }
+
+private:
+  SceneType* _full    = nullptr;
+  SceneType* _clipped = nullptr;
+  EstimateType _robot_in_local_map = EstimateType::Identity();
+  srrg2_clip_result _last{};
+  Status _status = Error;
+};
+
 template <int DIM>
 class MergerCorrespondenceHomo {
 public:
@@ -671,6 +710,7 @@ private:
 // ---- measurement adaptors: RawDataPreprocessor_ (S/raw_data_preprocessors/raw_data_preprocessor.h:13-88) -------------
 //   DepthImageAdaptor   depth image (+ intensity image) -> Scene<3>, organised or compact, with normals
 //   LaserScanAdaptor    ranges -> Scene<2> with normals
+//   LidarSweepAdaptor   3-D lidar sweep (point list, + intensity) -> Scene<3>, organised or compact, with normals
 // setRawData / setMeas / compute / status / reset; status() is Error after setRawData until compute() (:67-72).  The raw
 // data is borrowed until compute() has run.  compute(false) asks for no counts: an organised adapt then only queues its work.
 class AdaptorBase_ {
@@ -745,6 +785,43 @@ private:
   MeasurementType* _meas = nullptr;
   const float* _ranges   = nullptr;
   int _num_beams = 0, _mem = SRRG2_MEM_HOST;
+  bool _has_raw = false;
+};
+
+class LidarSweepAdaptor : public AdaptorBase_ {
+public:
+  using MeasurementType = Scene<3>;
+  srrg2_lidar_adaptor_params param;
+  LidarSweepAdaptor() { srrg2_adapt_default_lidar_params(&param); }
+  // a full-turn sensor: srrg2_spherical_model_full_turn into param.model
+  void setFullTurnModel(int rows, int cols, double elevation_first, double elevation_last) {
+    check(srrg2_spherical_model_full_turn(&param.model, rows, cols, elevation_first, elevation_last));
+  }
+  // n records of x, y, z (sensor frame) with a stride in bytes; intensity may be nullptr (points + 3 with stride 16 reads XYZI)
+  void setRawData(const float* points, int point_stride_bytes, int n, const float* intensity = nullptr,
+                  int intensity_stride_bytes = 0, int mem = SRRG2_MEM_HOST) {
+    _points = points, _point_stride = point_stride_bytes, _n = n;
+    _inten = intensity, _inten_stride = intensity_stride_bytes;
+    _mem = mem, _has_raw = true;
+    _status = Error;
+  }
+  void setMeas(MeasurementType* meas) { _meas = meas; }
+  void reset() {
+    _has_raw = false;
+    _status  = Initializing;
+  }
+  void compute(bool want_result = true) {
+    if (!_meas || !_has_raw) throw std::runtime_error("LidarSweepAdaptor::compute|raw data or measurement not set");
+    finish(srrg2_adapt_lidar_sweep(_meas->handle(), _points, _point_stride, _inten, _inten_stride, _n, _mem, &param,
+                                   want_result ? &_last : nullptr),
+           want_result);
+  }
+
+private:
+  MeasurementType* _meas = nullptr;
+  const float* _points   = nullptr;
+  const float* _inten    = nullptr;
+  int _point_stride = 0, _inten_stride = 0, _n = 0, _mem = SRRG2_MEM_HOST;
   bool _has_raw = false;
 };
 

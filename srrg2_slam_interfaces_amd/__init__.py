@@ -48,3 +48,10 @@ def MeasurementAdaptorLaserScan(params=None):
     from .adaptors import MeasurementAdaptorLaserScan as _A
 
     return _A(params)
+
+
+def MeasurementAdaptorLidarSweep(params=None):
+    """3-D lidar sweep (point list) -> measurement scene with normals on the device; see ``adaptors``."""
+    from .adaptors import MeasurementAdaptorLidarSweep as _A
+
+    return _A(params)

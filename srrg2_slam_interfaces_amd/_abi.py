@@ -174,6 +174,26 @@ class ScanAdaptorParams(C.Structure):
     ]
 
 
+class SphericalModel(C.Structure):
+    """srrg2_spherical_model: the range image of a spinning 3-D lidar (rows = rings, cols = azimuth steps)"""
+    _fields_ = [("azimuth_min", C.c_double), ("azimuth_increment", C.c_double), ("elevation_min", C.c_double),
+                ("elevation_increment", C.c_double), ("rows", C.c_int32), ("cols", C.c_int32), ("range_min", C.c_float),
+                ("range_max", C.c_float)]
+
+
+class LidarAdaptorParams(C.Structure):
+    """srrg2_lidar_adaptor_params"""
+    _fields_ = [("model", SphericalModel), ("normal_col_gap", C.c_int32), ("normal_row_gap", C.c_int32),
+                ("normal_max_distance_squared", C.c_float), ("drop_points_without_normal", C.c_int32), ("compact", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class SphericalClipParams(C.Structure):
+    """srrg2_spherical_clip_params"""
+    _fields_ = [("model", SphericalModel), ("sensor_in_robot", C.c_float * 12), ("occlusion_margin", C.c_float),
+                ("reserved", C.c_int32)]
+
+
 class AdaptResult(C.Structure):
     """srrg2_adapt_result"""
     _fields_ = [("status", C.c_int32), ("num_raw", C.c_int32), ("num_in_range", C.c_int32), ("num_valid", C.c_int32),

@@ -56,6 +56,12 @@ def lib():
                                                  C.POINTER(abi.DepthAdaptorParams), C.POINTER(abi.AdaptResult)]
         _LIB.srrg2_adapt_laser_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(abi.ScanAdaptorParams),
                                                 C.POINTER(abi.AdaptResult)]
+        # srrg2_adapt_lidar_sweep (adaptors.MeasurementAdaptorLidarSweep), srrg2_spherical_model_full_turn
+        _LIB.srrg2_adapt_default_lidar_params.argtypes = [C.POINTER(abi.LidarAdaptorParams)]
+        _LIB.srrg2_adapt_default_lidar_params.restype = None
+        _LIB.srrg2_spherical_model_full_turn.argtypes = [C.POINTER(abi.SphericalModel), C.c_int, C.c_int, C.c_double, C.c_double]
+        _LIB.srrg2_adapt_lidar_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                 C.POINTER(abi.LidarAdaptorParams), C.POINTER(abi.AdaptResult)]
         # srrg2_scene_clip_projective (mapping.SceneClipperProjective)
         from . import mapping
 
@@ -68,6 +74,11 @@ def lib():
         _LIB.srrg2_clip_default_scan_params.restype = None
         _LIB.srrg2_scene_clip_scan.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(mapping.ScanClipParams), C.c_void_p,
                                                C.POINTER(mapping.ClipResult)]
+        # srrg2_scene_clip_spherical (mapping.SceneClipperSpherical)
+        _LIB.srrg2_clip_default_spherical_params.argtypes = [C.POINTER(abi.SphericalClipParams)]
+        _LIB.srrg2_clip_default_spherical_params.restype = None
+        _LIB.srrg2_scene_clip_spherical.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(abi.SphericalClipParams),
+                                                    C.c_void_p, C.POINTER(mapping.ClipResult)]
         # srrg2_scene_estimate_normals (mapping.Scene.estimate_normals)
         _LIB.srrg2_normals_default_params.argtypes = [C.POINTER(abi.NormalsParams), C.c_int]
         _LIB.srrg2_normals_default_params.restype = None

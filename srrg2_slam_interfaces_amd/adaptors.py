@@ -3,11 +3,13 @@
 ``MeasurementAdaptorDepthImage``   depth image (uint16 counts or float32 metres, + optional intensity image) -> organised
                                    or compact 3-D scene with normals
 ``MeasurementAdaptorLaserScan``    ranges -> 2-D scene with normals
+``MeasurementAdaptorLidarSweep``   3-D lidar sweep (a list of points, + optional intensity) -> organised or compact 3-D scene
+                                   with normals, through the range image of a spherical sensor model
 
 Method names follow ``RawDataPreprocessor_`` (S/raw_data_preprocessors/raw_data_preprocessor.h:13-88), snake_case:
 ``set_raw_data``, ``set_meas``, ``compute``, ``status``, ``reset``; ``status()`` is ERROR after ``set_raw_data`` until
 ``compute()`` (:67-72).  Thin marshalling only; product library only (the oracle has no adaptor: the parity target is
-tests/adaptor_restatement.py).
+tests/adaptor_restatement.py and tests/lidar_restatement.py).
 """
 import ctypes as C
 
@@ -32,6 +34,29 @@ def default_scan_params():
     p = abi.ScanAdaptorParams()
     _capi.lib().srrg2_adapt_default_scan_params(C.byref(p))
     return p
+
+
+def default_lidar_params():
+    """model zeroed except range 0.5 .. 120 m (fill it with ``spherical_model_full_turn`` or field by field); gaps 1 / 1,
+    normal_max_distance_squared 1.0, drop 1, organised"""
+    from . import _capi
+
+    p = abi.LidarAdaptorParams()
+    _capi.lib().srrg2_adapt_default_lidar_params(C.byref(p))
+    return p
+
+
+def spherical_model_full_turn(rows, cols, elevation_first, elevation_last, model=None):
+    """srrg2_spherical_model_full_turn: columns tiling [-pi, pi), rows from elevation_first to elevation_last, range
+    0.5 .. 120 m; fills ``model`` (e.g. ``params.model``) in place when given.  Raises on rows < 2, cols < 1, bad elevations."""
+    from . import _capi
+
+    m = abi.SphericalModel() if model is None else model
+    lib = _capi.lib()
+    if lib.srrg2_spherical_model_full_turn(C.byref(m), int(rows), int(cols), float(elevation_first), float(elevation_last)) != 0:
+        msg = lib.srrg2_amd_last_error()
+        raise ValueError(msg.decode() if msg else "spherical_model_full_turn")
+    return m
 
 
 def _image(img, image_type, what):
@@ -158,4 +183,58 @@ class MeasurementAdaptorLaserScan(_AdaptorBase):
         _, ptr, n, mem = self._raw
         self._check(self._lib.srrg2_adapt_laser_scan(self._meas._h, ptr, n, mem, C.byref(self.params),
                                                      C.byref(out) if want_result else None))
+        return self._finish(out, want_result)
+
+
+class MeasurementAdaptorLidarSweep(_AdaptorBase):
+    """params: abi.LidarAdaptorParams (model, gaps, gate, drop, compact).  In compact mode the scene's global indices are the
+    pixel indices row*cols + col of the range image."""
+
+    def __init__(self, params=None):
+        super().__init__()
+        self.params = params or default_lidar_params()
+        self._raw = None
+
+    def set_model(self, model):
+        """copy an abi.SphericalModel (e.g. from ``spherical_model_full_turn``) into the params"""
+        C.memmove(C.byref(self.params.model), C.byref(model), C.sizeof(abi.SphericalModel))
+
+    def set_raw_data(self, points, intensity=None):
+        """points: (n, 3) float32 array of x, y, z in the sensor frame, or (n, 4) of x, y, z, intensity (then ``intensity``
+        must be None), or a (device_pointer, stride_bytes, n) triple; intensity: (n,) floats, or a (device_pointer, stride_bytes)
+        pair next to device points.  The arrays are read at compute()."""
+        if isinstance(points, tuple):
+            ptr, stride, n = points
+            iptr, istride = (None, 0) if intensity is None else (C.c_void_p(int(intensity[0])), int(intensity[1]))
+            self._raw = (None, C.c_void_p(int(ptr)), int(stride), iptr, istride, int(n), abi.MEM_DEVICE)
+        else:
+            a = np.asarray(points)
+            if a.ndim != 2 or a.shape[1] not in (3, 4):
+                raise ValueError("points: an (n, 3) or (n, 4) array expected, got %s" % (a.shape,))
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            n, w = a.shape
+            keep, iptr, istride = (a,), None, 0
+            if w == 4:
+                if intensity is not None:
+                    raise ValueError("intensity: given twice (the points already have a fourth column)")
+                iptr, istride = C.c_void_p(a.ctypes.data + 12), 16
+            elif intensity is not None:
+                it = np.ascontiguousarray(intensity, dtype=np.float32).reshape(-1)
+                if it.shape[0] != n:
+                    raise ValueError("intensity: one value per point expected")
+                keep, iptr, istride = (a, it), C.c_void_p(it.ctypes.data), 4
+            self._raw = (keep, C.c_void_p(a.ctypes.data), 4 * w, iptr, istride, n, abi.MEM_HOST)
+        self._status = abi.ADAPTOR_ERROR
+
+    def reset(self):
+        self._raw = None
+        self._status = abi.ADAPTOR_INITIALIZING
+        self.last = None
+
+    def compute(self, want_result=True):
+        self._ready()
+        out = abi.AdaptResult()
+        _, ptr, stride, iptr, istride, n, mem = self._raw
+        self._check(self._lib.srrg2_adapt_lidar_sweep(self._meas._h, ptr, stride, iptr, istride, n, mem, C.byref(self.params),
+                                                      C.byref(out) if want_result else None))
         return self._finish(out, want_result)

@@ -3,9 +3,10 @@
 //   MultiTrackerBase_::compute() -> proc->adapt()     S/trackers/multi_tracker_impl.cpp:57-80
 //   TrackerSliceProcessorBase_::adapt()               S/trackers/tracker_slice_processor_base_impl.cpp:32-49
 //   RawDataPreprocessor_::compute() (interface)       S/raw_data_preprocessors/raw_data_preprocessor.h:13-88
-// The reference ships the interface only; the two adaptors here (depth image -> organised PointNormal3f cloud, laser scan ->
-// PointNormal2f cloud) are defined from first principles: DESIGN.md section 4 "Measurement adaptors" is the arithmetic
-// contract, tests/adaptor_restatement.py restates it in numpy and the library must give the same bits.
+// The reference ships the interface only; the adaptors here (depth image -> organised PointNormal3f cloud, laser scan ->
+// PointNormal2f cloud, lidar sweep -> PointNormal3f cloud through a range image) are defined from first principles: DESIGN.md
+// section 4 "Measurement adaptors" and "Lidar sweeps" are the arithmetic contract, tests/adaptor_restatement.py and
+// tests/lidar_restatement.py restate it in numpy and the library must give the same bits.
 // Kernels: one thread per pixel / beam, grid-stride.  A thread reads its own raw value and its four (two) neighbours' and
 // RECOMPUTES the neighbours' points from them -- the same expression gives the same bits as the neighbour's own thread, so
 // there is no second pass and no dependency between threads -- and writes point and normal as 16-byte records, coalesced.
@@ -23,6 +24,7 @@
 #include "host_util.h"
 #include "kernels.h"
 #include "scene_state.h"
+#include "spherical.h"
 
 using srrg2amd::fail;
 
@@ -167,6 +169,101 @@ struct ScanSource {
   __device__ __forceinline__ float intensity(int) const { return 0.f; }
 };
 
+// ---- lidar sweep (DESIGN.md section 4 "Lidar sweeps") ------------------------------------------------------------------
+// A sweep arrives as a list of points; the range image that organises it is built first: k_lidar_bin projects every point
+// (spherical.h) and takes, per pixel, the minimum of (range bits << 32 | input index) -- positive floats order like their bit
+// patterns, so the nearest point wins and, of equal ranges, the lowest index, whoever comes first.  ONE 64-bit atomicMin without
+// return value per in-view point, straight into global memory: the table of a 64 x 2048 sensor is 1 MB, far beyond a
+// workgroup's LDS, and a sweep puts about one point on each word, so there is nothing for a private table to combine.
+__global__ __launch_bounds__(256) void k_lidar_bin(const unsigned char* __restrict__ pts, long long stride, int n, sph::Geom G,
+                                                   unsigned long long* __restrict__ winner) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const float* q = reinterpret_cast<const float*>(pts + (long long) i * stride);
+    const float x = q[0], y = q[1], z = q[2];
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) continue;
+    float rho;
+    const int pix = sph::project(G, x, y, z, rho);  // (pix < rows * cols: project's bounds)
+    if (pix >= 0) atomicMin(&winner[pix], ((unsigned long long) __float_as_uint(rho) << 32) | (unsigned long long) (unsigned) i);
+  }
+}
+
+// the range image as a source of run_adapt: pixel -> its winner's input point, normals from the four neighbouring winners
+struct LidarSource {
+  const unsigned char* pts;
+  const unsigned char* inten;  // null: no intensity
+  long long pts_stride, inten_stride;
+  const unsigned long long* winner;
+  int rows, cols;
+  int gc, gr;  // gaps; gc == 0: no normals
+  int wrap;    // the columns close the circle
+  float maxd2;
+  int drop;
+
+  // the input index of the pixel's winner (< n by construction); false: the pixel is empty
+  __device__ __forceinline__ bool winner_at(int r, int c, unsigned& idx) const {
+    const unsigned long long w = winner[(long long) r * cols + c];
+    idx                        = (unsigned) w;
+    return w != ~0ull;
+  }
+  __device__ __forceinline__ float3 point_of(unsigned idx) const {
+    const float* q = reinterpret_cast<const float*>(pts + (long long) idx * pts_stride);
+    return make_float3(q[0], q[1], q[2]);
+  }
+  __device__ __forceinline__ int eval(int i, float4& p, float4& n) const {
+    const int r = i / cols, c = i - r * cols;
+    const float qn = quiet_nan();
+    p = make_float4(qn, qn, qn, 0.f);
+    n = gc > 0 ? make_float4(qn, qn, qn, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    unsigned iq;
+    if (!winner_at(r, c, iq)) return 0;
+    const float3 q  = point_of(iq);
+    bool has_normal = false;
+    if (gc > 0 && r >= gr && r < rows - gr && (wrap || (c >= gc && c < cols - gc))) {
+      int cl = c - gc, cr = c + gc;
+      if (wrap) {  // (gaps beyond one turn: modulo cols, like any other)
+        const int g = gc % cols;
+        cl          = c - g < 0 ? c - g + cols : c - g;
+        cr          = c + g >= cols ? c + g - cols : c + g;
+      }
+      unsigned il, ir, iu, id;
+      const bool okl = winner_at(r, cl, il), okr = winner_at(r, cr, ir);
+      const bool oku = winner_at(r - gr, c, iu), okd = winner_at(r + gr, c, id);
+      if (okl && okr && oku && okd) {
+        const float3 pr = point_of(ir), pl = point_of(il);
+        const float3 pd = point_of(id), pu = point_of(iu);
+        const float dcx = pr.x - pl.x, dcy = pr.y - pl.y, dcz = pr.z - pl.z;
+        const float drx = pd.x - pu.x, dry = pd.y - pu.y, drz = pd.z - pu.z;
+        if (!(sq3(dcx, dcy, dcz) > maxd2) && !(sq3(drx, dry, drz) > maxd2)) {
+          float nx = dcy * drz - dcz * dry;
+          float ny = dcz * drx - dcx * drz;
+          float nz = dcx * dry - dcy * drx;
+          const float len = sqrtf(sq3(nx, ny, nz));
+          if (len > 0.f) {
+            nx = nx / len;
+            ny = ny / len;
+            nz = nz / len;
+            if ((nx * q.x + ny * q.y) + nz * q.z > 0.f) {  // normals face the sensor
+              nx = -nx;
+              ny = -ny;
+              nz = -nz;
+            }
+            n          = make_float4(nx, ny, nz, 0.f);
+            has_normal = true;
+          }
+        }
+      }
+    }
+    const bool valid = gc == 0 || has_normal || !drop;
+    if (valid) p = make_float4(q.x, q.y, q.z, 0.f);
+    return PX_IN_RANGE | (valid ? PX_VALID : 0);
+  }
+  __device__ __forceinline__ float intensity(int i) const {
+    const unsigned long long w = winner[i];
+    if (w == ~0ull) return 0.f;
+    return *reinterpret_cast<const float*>(inten + (long long) (unsigned) w * inten_stride);
+  }
+};
+
 // ---- kernels ---------------------------------------------------------------------------------------------------------
 // both counts of a workgroup in one word (low: in range, high: Valid), ONE atomic per workgroup (blockDim = 256): same-address
 // atomics serialise
@@ -241,7 +338,7 @@ int stage(srrg2_scene* s, const void* host, size_t bytes, size_t offset, const u
   return 0;
 }
 
-// the part both adaptors share.  The source's device pointers are valid on the scene's stream; nothing of `s` has changed yet.
+// the part the adaptors share.  The source's device pointers are valid on the scene's stream; nothing of `s` has changed yet.
 template <typename S>
 int run_adapt(srrg2_scene* s, const S& src, int n, bool normals, bool intensity, bool compact, srrg2_adapt_result* out) {
   int rc;
@@ -418,6 +515,98 @@ int srrg2_adapt_laser_scan(srrg2_scene_h dst, const float* ranges, int num_beams
     src.ranges = reinterpret_cast<const float*>(d);
   }
   return run_adapt(dst, src, num_beams, src.w > 0, false, p->compact != 0, out);
+}
+
+void srrg2_adapt_default_lidar_params(srrg2_lidar_adaptor_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->model.range_min             = 0.5f;
+  p->model.range_max             = 120.f;
+  p->normal_col_gap              = 1;
+  p->normal_row_gap              = 1;
+  p->normal_max_distance_squared = 1.0f;
+  p->drop_points_without_normal  = 1;
+  p->compact                     = 0;
+}
+
+int srrg2_spherical_model_full_turn(srrg2_spherical_model* m, int rows, int cols, double elevation_first, double elevation_last) {
+  if (!m) return fail(SRRG2_E_INVALID, "spherical_model_full_turn: null model");
+  if (rows < 2 || cols < 1 || !std::isfinite(elevation_first) || !std::isfinite(elevation_last) || elevation_first == elevation_last)
+    return fail(SRRG2_E_INVALID, "spherical_model_full_turn: rows >= 2, cols >= 1, two finite and distinct elevations");
+  const double PI = 3.141592653589793;
+  std::memset(m, 0, sizeof(*m));
+  m->azimuth_increment   = (2.0 * PI) / (double) cols;
+  m->azimuth_min         = -PI + PI / (double) cols;
+  m->elevation_min       = elevation_first;
+  m->elevation_increment = (elevation_last - elevation_first) / (double) (rows - 1);
+  m->rows                = rows;
+  m->cols                = cols;
+  m->range_min           = 0.5f;
+  m->range_max           = 120.f;
+  return 0;
+}
+
+int srrg2_adapt_lidar_sweep(srrg2_scene_h dst, const float* points, int point_stride, const float* intensity, int intensity_stride,
+                            int n, int mem, const srrg2_lidar_adaptor_params* p, srrg2_adapt_result* out) {
+  if (!dst || !p) return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: null scene or params");
+  if (dst->dim != 3) return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: the scene must have dim 3");
+  if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: bad mem");
+  if (n < 0) return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: n >= 0");
+  if (p->reserved != 0) return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: reserved must be 0");
+  if (p->normal_col_gap < 0 || p->normal_row_gap < 0 || (p->normal_col_gap == 0) != (p->normal_row_gap == 0))
+    return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: normal gaps >= 0, and both or neither 0");
+  if (const char* why = sph::invalid(p->model)) return fail(SRRG2_E_INVALID, std::string("adapt_lidar_sweep: ") + why);
+  if (n > 0) {
+    if (!points) return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: null points");
+    if (point_stride < 12 || !aligned_to(points, point_stride, 4))
+      return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: point stride >= 12 and a multiple of 4, points 4-byte aligned");
+    if (intensity && (intensity_stride < 4 || !aligned_to(intensity, intensity_stride, 4)))
+      return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: intensity stride >= 4 and a multiple of 4, intensity 4-byte aligned");
+  }
+  int rc;
+  HIP_TRY(hipSetDevice(dst->device));
+  const bool with_inten = intensity != nullptr;
+  LidarSource src;
+  std::memset(&src, 0, sizeof(src));
+  src.rows = p->model.rows, src.cols = p->model.cols;
+  src.gc = p->normal_col_gap, src.gr = p->normal_row_gap;
+  src.wrap  = sph::columns_wrap(p->model);
+  src.maxd2 = p->normal_max_distance_squared;
+  src.drop  = p->drop_points_without_normal != 0;
+  const bool normals = src.gc > 0;
+  if (n == 0) return run_adapt(dst, src, 0, normals, with_inten, p->compact != 0, out);  // an empty scene, INITIALIZING
+  src.pts        = reinterpret_cast<const unsigned char*>(points);
+  src.inten      = reinterpret_cast<const unsigned char*>(intensity);
+  src.pts_stride = point_stride, src.inten_stride = intensity_stride;
+  hipStream_t st = dst->stream;
+  if (mem == SRRG2_MEM_HOST) {  // the records as they lie; interleaved intensities travel with their points, once
+    const unsigned char *pb = src.pts, *pe = pb + (size_t) (n - 1) * (size_t) point_stride + 12;
+    const unsigned char *ib = src.inten, *ie = with_inten ? ib + (size_t) (n - 1) * (size_t) intensity_stride + 4 : nullptr;
+    const unsigned char* d = nullptr;
+    if (with_inten && ib <= pe && pb <= ie) {
+      const unsigned char *lo = pb < ib ? pb : ib, *hi = pe > ie ? pe : ie;
+      if ((rc = dst->staging.reserve((size_t) (hi - lo) + 64))) return rc;
+      if ((rc = stage(dst, lo, (size_t) (hi - lo), 0, &d))) return rc;
+      src.pts   = d + (pb - lo);
+      src.inten = d + (ib - lo);
+    } else {
+      const size_t bp = (size_t) (pe - pb), bi = with_inten ? (size_t) (ie - ib) : 0, off_i = (bp + 63) / 64 * 64;
+      if ((rc = dst->staging.reserve(off_i + bi + 64))) return rc;
+      if ((rc = stage(dst, pb, bp, 0, &src.pts))) return rc;
+      if (with_inten && (rc = stage(dst, ib, bi, off_i, &src.inten))) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(st));  // the caller's cloud is consumed (pinned memory too) before anything is queued
+  }
+  const size_t npix = (size_t) src.rows * (size_t) src.cols;
+  if ((rc = dst->winner.reserve(npix))) return rc;
+  HIP_TRY(hipMemsetAsync(dst->winner.p, 0xff, npix * sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_lidar_bin, dim3(adapt_blocks(n)), dim3(256), 0, st, src.pts, src.pts_stride, n, sph::geom_of(p->model),
+                     dst->winner.p);
+  HIP_TRY(hipGetLastError());
+  src.winner = dst->winner.p;
+  if ((rc = run_adapt(dst, src, (int) npix, normals, with_inten, p->compact != 0, out))) return rc;
+  if (out) out->num_raw = n;  // (run_adapt counted the pixels it walked)
+  return 0;
 }
 
 }  // extern "C"

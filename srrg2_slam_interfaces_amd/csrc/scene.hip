@@ -1,4 +1,4 @@
-// scene.hip -- scene slices kept in HBM between frames: ball, projective and scan clipping, correspondence-based merging
+// scene.hip -- scene slices kept in HBM between frames: ball, projective, scan and spherical clipping, correspondence-based merging
 // (SURVEY.md section 8f row 2).  Replaces, behind the C ABI of include/srrg2_slam_amd.h:
 //   MergerCorrespondenceHomo_::compute()   S/mapping/merger_correspondence_homo_impl.cpp:11-125
 //   SceneClipper_::compute() (interface)   S/mapping/scene_clipper.h:17-122
@@ -33,6 +33,7 @@
 #include "kernels.h"
 #include "scene_device.h"
 #include "scene_state.h"
+#include "spherical.h"
 
 using srrg2amd::DevBuf;
 using srrg2amd::fail;
@@ -102,7 +103,7 @@ __global__ void k_clip_flag(int dim, Xf L, float range2, const float4* __restric
 }
 
 // the points the scan kept (offset[i + 1] != offset[i]: the scan leaves its total in offset[n]) into the robot frame, in scene
-// order: the scatter of all three clippers.  It evaluates no predicate, so whatever a flag kernel decided is what moves.
+// order: the scatter of all four clippers.  It evaluates no predicate, so whatever a flag kernel decided is what moves.
 template <bool FEAT, int DIM>
 __device__ __forceinline__ void scatter_kept(const Xf& L, const float4* __restrict__ pts, const float4* __restrict__ nrm, int n,
                                              const int* __restrict__ offset, float4* __restrict__ out_pts,
@@ -293,6 +294,73 @@ __global__ void k_sclip_flag(Xf L, Xf S, ScanGeom G, const float4* __restrict__ 
     nvalid += valid ? 1 : 0;
     nview += keep ? 1 : 0;
     if (OCCLUSION && keep) keep = rho <= __uint_as_float(rmin[beam]) + G.margin;
+    flags[i] = keep ? 1 : 0;
+  }
+  block_add(nvalid, &counters[CLIP_VALID]);
+  block_add(nview, &counters[CLIP_IN_VIEW]);
+}
+
+// ---- spherical clip (no reference counterpart; DESIGN.md section 4 "Lidar sweeps") ----------------------------------------------
+// the 3-D twin of the scan clip: keeps the Valid points a spinning lidar at sensor_in_robot sees -- inside the range interval
+// and the rows x cols range image of its spherical model (spherical.h, shared with the sweep adaptor), and -- margin >= 0 -- no
+// further than `margin` behind the nearest point of their pixel.
+//   k_spclip_rmin    per pixel the minimum range of the in-view points, ONE 32-bit atomicMin per point straight into global
+//                    memory: the image of a 64 x 2048 sensor has 131072 words, sixteen times SRRG2_SCLIP_LDS_BINS, and a map
+//                    puts a handful of points on each, so there is no LDS path.  It also counts, and leaves (pixel, range bits)
+//                    per point for the flag pass -- the projection is two float64 atan2, a square root and four divisions, more
+//                    than the 16 bytes per point of writing it down and reading it back (DESIGN.md has both timings;
+//                    -DSRRG2_SPCLIP_RECOMPUTE builds the variant whose flag pass projects again).
+//   k_spclip_flag    keep flag per point; without occlusion it projects and counts itself
+// and k_scatter_kept moves what the scan kept.
+__device__ __forceinline__ int spclip_project(const Xf& L, const Xf& S, const sph::Geom& G, const float4 p, bool& valid, float& rho) {
+  valid = valid_point(3, p);
+  if (!valid) return -1;
+  const float4 c = xform_point(3, S, xform_point(3, L, p));
+  if (!(isfinite(c.x) && isfinite(c.y) && isfinite(c.z))) return -1;
+  return sph::project(G, c.x, c.y, c.z, rho);
+}
+
+// counters: [CLIP_VALID], [CLIP_IN_VIEW]
+__global__ void k_spclip_rmin(Xf L, Xf S, sph::Geom G, const float4* __restrict__ pts, int n, unsigned* __restrict__ rmin,
+                              uint2* __restrict__ stage, int* __restrict__ counters) {
+  int nvalid = 0, nview = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    bool valid;
+    float rho     = 0.f;
+    const int pix = spclip_project(L, S, G, pts[i], valid, rho);
+    nvalid += valid ? 1 : 0;
+    nview += pix >= 0 ? 1 : 0;
+    if (pix >= 0) atomicMin(&rmin[pix], __float_as_uint(rho));  // (pix < rows * cols: project's bounds)
+    if (stage) stage[i] = make_uint2((unsigned) pix, __float_as_uint(rho));
+  }
+  if (stage) {
+    block_add(nvalid, &counters[CLIP_VALID]);
+    block_add(nview, &counters[CLIP_IN_VIEW]);
+  }
+}
+
+// the flag pass behind k_spclip_rmin: reads what that pass left per point
+__global__ void k_spclip_flag_staged(const uint2* __restrict__ stage, int n, const unsigned* __restrict__ rmin, float margin,
+                                     int* __restrict__ flags) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const uint2 s = stage[i];
+    const int pix = (int) s.x;
+    flags[i]      = pix >= 0 && __uint_as_float(s.y) <= __uint_as_float(rmin[pix]) + margin ? 1 : 0;
+  }
+}
+
+template <bool OCCLUSION>
+__global__ void k_spclip_flag(Xf L, Xf S, sph::Geom G, float margin, const float4* __restrict__ pts, int n,
+                              const unsigned* __restrict__ rmin, int* __restrict__ flags, int* __restrict__ counters) {
+  int nvalid = 0, nview = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    bool valid;
+    float rho     = 0.f;
+    const int pix = spclip_project(L, S, G, pts[i], valid, rho);
+    bool keep     = pix >= 0;
+    nvalid += valid ? 1 : 0;
+    nview += keep ? 1 : 0;
+    if (OCCLUSION && keep) keep = rho <= __uint_as_float(rmin[pix]) + margin;
     flags[i] = keep ? 1 : 0;
   }
   block_add(nvalid, &counters[CLIP_VALID]);
@@ -1021,6 +1089,72 @@ int srrg2_scene_clip_scan(srrg2_scene_h full, const float* robot_in_local_map, c
     hipLaunchKernelGGL(k_sclip_flag<true>, grid, dim3(256), 0, st, L, S, geom, full->pts.p, n, full->rmin.p, full->flags.p, counters);
   } else {
     hipLaunchKernelGGL(k_sclip_flag<false>, grid, dim3(256), 0, st, L, S, geom, full->pts.p, n, (const unsigned*) nullptr,
+                       full->flags.p, counters);
+  }
+  if ((rc = compact_into(full, clipped, L, n))) return rc;
+  if (out) {
+    out->num_valid   = full->scalars[CLIP_VALID];
+    out->num_in_view = full->scalars[CLIP_IN_VIEW];
+    out->num_kept    = full->scalars[CLIP_TOTAL];
+  }
+  return 0;
+}
+
+void srrg2_clip_default_spherical_params(srrg2_spherical_clip_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->model.range_min = 0.5f;
+  p->model.range_max = 120.f;
+  p->sensor_in_robot[0] = p->sensor_in_robot[5] = p->sensor_in_robot[10] = 1.f;
+  p->occlusion_margin = -1.f;
+}
+
+int srrg2_scene_clip_spherical(srrg2_scene_h full, const float* robot_in_local_map, const srrg2_spherical_clip_params* p,
+                               srrg2_scene_h clipped, srrg2_clip_result* out) {
+  if (!full || !clipped || !robot_in_local_map || !p) return fail(SRRG2_E_INVALID, "scene_clip_spherical: null argument");
+  if (!clip_pair(full, clipped))
+    return fail(SRRG2_E_INVALID, "scene_clip_spherical: full and clipped must be two scenes of one dim on one device");
+  if (full->dim != 3) return fail(SRRG2_E_UNSUPPORTED, "scene_clip_spherical: 2-D scenes (a laser scanner's view: srrg2_scene_clip_scan)");
+  if (const char* why = sph::invalid(p->model)) return fail(SRRG2_E_INVALID, std::string("scene_clip_spherical: ") + why);
+  if (std::isnan(p->occlusion_margin)) return fail(SRRG2_E_INVALID, "scene_clip_spherical: occlusion_margin is NaN");
+  if (p->reserved != 0) return fail(SRRG2_E_INVALID, "scene_clip_spherical: reserved must be 0");
+  int rc;
+  if ((rc = clip_begin(full, clipped))) return rc;
+  float Linv[12], Sinv[12];
+  dm::se3_inverse(robot_in_local_map, Linv);
+  dm::se3_inverse(p->sensor_in_robot, Sinv);
+  const Xf L = load_transform(3, Linv), S = load_transform(3, Sinv);
+  const sph::Geom geom = sph::geom_of(p->model);
+  const float margin   = p->occlusion_margin;
+  const bool occlusion = margin >= 0.f;
+  const int n          = full->n;
+  // (arrays even for an empty result, as srrg2_scene_set leaves them: srrg2_scene_device_arrays then shows the normals' presence)
+  if ((rc = scene_reserve(clipped, 1, 0)) || (rc = clipped->gidx.reserve(1))) return rc;
+  if (out) {
+    std::memset(out, 0, sizeof(*out));
+    out->status = n == 0 ? SRRG2_CLIPPER_READY : SRRG2_CLIPPER_SUCCESSFUL;
+  }
+  if (n == 0) return 0;
+  hipStream_t st = full->stream;
+  if ((rc = full->flags.reserve((size_t) n + 1))) return rc;
+  int* const counters = full->dscalars.p;  // (compact_into brings them to the host with the scan's total)
+  HIP_TRY(hipMemsetAsync(counters, 0, CLIP_TOTAL * sizeof(int), st));
+  const dim3 grid(blocks_for(n));
+  if (occlusion) {
+    const size_t npix = (size_t) geom.rows * (size_t) geom.cols;
+    if ((rc = full->rmin.reserve(npix))) return rc;
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) full->rmin.p, 0x7f800000, npix, st));  // +inf
+#ifndef SRRG2_SPCLIP_RECOMPUTE
+    if ((rc = full->sph_stage.reserve((size_t) n))) return rc;
+    hipLaunchKernelGGL(k_spclip_rmin, grid, dim3(256), 0, st, L, S, geom, full->pts.p, n, full->rmin.p, full->sph_stage.p, counters);
+    hipLaunchKernelGGL(k_spclip_flag_staged, grid, dim3(256), 0, st, full->sph_stage.p, n, full->rmin.p, margin, full->flags.p);
+#else
+    hipLaunchKernelGGL(k_spclip_rmin, grid, dim3(256), 0, st, L, S, geom, full->pts.p, n, full->rmin.p, (uint2*) nullptr, counters);
+    hipLaunchKernelGGL(k_spclip_flag<true>, grid, dim3(256), 0, st, L, S, geom, margin, full->pts.p, n, full->rmin.p, full->flags.p,
+                       counters);
+#endif
+  } else {
+    hipLaunchKernelGGL(k_spclip_flag<false>, grid, dim3(256), 0, st, L, S, geom, margin, full->pts.p, n, (const unsigned*) nullptr,
                        full->flags.p, counters);
   }
   if ((rc = compact_into(full, clipped, L, n))) return rc;

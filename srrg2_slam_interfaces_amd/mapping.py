@@ -6,6 +6,7 @@
 ``SceneClipperBall``           ``SceneClipper_`` (S/mapping/scene_clipper.h:17-122) with the ball policy
 ``SceneClipperProjective``     the same interface with the projective policy: what a pinhole camera sees (3-D, product library)
 ``SceneClipperScan``           the same interface with the scan policy: what a planar laser scanner sees (2-D, product library)
+``SceneClipperSpherical``      the same interface with the spherical policy: what a spinning 3-D lidar sees (3-D, product library)
 ``MergerCorrespondenceHomo``   ``MergerCorrespondenceHomo_`` (S/mapping/merger_correspondence_homo_impl.cpp:11-125)
 
 Method names follow the reference setters (snake_case).  Thin marshalling only; parametrised by
@@ -71,6 +72,19 @@ def default_scan_clip_params():
 
     p = ScanClipParams()
     _capi.lib().srrg2_clip_default_scan_params(C.byref(p))
+    return p
+
+
+SphericalModel, SphericalClipParams = abi.SphericalModel, abi.SphericalClipParams
+
+
+def default_spherical_clip_params():
+    """identity sensor, range 0.5 .. 120 m, occlusion_margin < 0 (field of view only); the model's angles / rows / cols are the
+    caller's (``adaptors.spherical_model_full_turn(rows, cols, first, last, model=p.model)`` fills a full turn)"""
+    from . import _capi
+
+    p = SphericalClipParams()
+    _capi.lib().srrg2_clip_default_spherical_params(C.byref(p))
     return p
 
 
@@ -401,6 +415,55 @@ class SceneClipperScan:
         self._status = CLIPPER_ERROR
         self._b.check(self._b.fn("clip_scan")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params),
                                               self._clipped._h, C.byref(out) if want_result else None))
+        if want_result:
+            self._status, self.last = out.status, out.as_dict()
+        else:
+            self._status, self.last = (CLIPPER_SUCCESSFUL if self._full.size() else CLIPPER_READY), None
+        return self.last
+
+    def status(self):
+        return self._status
+
+    def global_indices(self):
+        return self._clipped.global_indices()
+
+
+class SceneClipperSpherical:
+    """setFullScene / setClippedSceneInRobot / setRobotInLocalMap / setSensorInRobot / compute / status / globalIndices for 3-D
+    scenes seen by a spinning lidar.  ``params``: SphericalClipParams (model, occlusion_margin); ``last``: the counts of the last
+    compute() (``want_result=False`` passes no result struct: ``last`` is then None)."""
+
+    def __init__(self, binding, params=None):
+        self._b = binding
+        self.params = params or default_spherical_clip_params()
+        self._full = self._clipped = None
+        self._robot_in_local_map = None
+        self._status = CLIPPER_ERROR
+        self.last = None
+
+    def set_full_scene(self, scene):
+        self._full = scene
+
+    def set_clipped_scene_in_robot(self, scene):
+        self._clipped = scene
+
+    def set_robot_in_local_map(self, T):
+        self._robot_in_local_map = _f32(T)
+
+    def set_sensor_in_robot(self, T):
+        for i, v in enumerate(_f32(T).reshape(12)):
+            self.params.sensor_in_robot[i] = float(v)
+
+    def set_model(self, model):
+        C.memmove(C.byref(self.params.model), C.byref(model), C.sizeof(SphericalModel))
+
+    def compute(self, want_result=True):
+        if self._full is None or self._clipped is None or self._robot_in_local_map is None:
+            raise RuntimeError("SceneClipperSpherical::compute|scene, output or pose not set")
+        out = ClipResult()
+        self._status = CLIPPER_ERROR
+        self._b.check(self._b.fn("clip_spherical")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params),
+                                                   self._clipped._h, C.byref(out) if want_result else None))
         if want_result:
             self._status, self.last = out.status, out.as_dict()
         else:
