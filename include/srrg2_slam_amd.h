@@ -694,8 +694,8 @@ void srrg2_clip_default_scan_params(srrg2_scan_clip_params* p);
 int srrg2_scene_clip_scan(srrg2_scene_h full, const float* robot_in_local_map /* 3x3 */, const srrg2_scan_clip_params* p,
                           srrg2_scene_h clipped, srrg2_clip_result* out /* may be NULL */);
 
-/* The spherical sensor model of a spinning 3-D lidar: a range image of rows (rings, uniformly spaced in elevation) x cols
- * (azimuth steps).  Shared by srrg2_adapt_lidar_sweep and srrg2_scene_clip_spherical, which project a sensor-frame point
+/* The spherical sensor model of a spinning 3-D lidar: a range image of rows (rings, uniformly spaced in elevation; a per-ring
+ * table: srrg2_scene_clip_spherical_rings, srrg2_lidar_sweep_extras) x cols (azimuth steps).  Shared by srrg2_adapt_lidar_sweep and srrg2_scene_clip_spherical, which project a sensor-frame point
  * c = (x, y, z) the same way (DESIGN.md section 4 "Lidar sweeps" is the arithmetic contract):
  *   rho = sqrtf((x*x + y*y) + z*z), range_min <= rho <= range_max;
  *   azimuth dm::atan2(y, x) binned to the nearest column after at most one turn of 2 pi either way (as clip_scan bins a
@@ -740,6 +740,21 @@ typedef struct srrg2_spherical_clip_params {
 void srrg2_clip_default_spherical_params(srrg2_spherical_clip_params* p);
 int srrg2_scene_clip_spherical(srrg2_scene_h full, const float* robot_in_local_map, const srrg2_spherical_clip_params* p,
                                srrg2_scene_h clipped, srrg2_clip_result* out /* may be NULL */);
+
+/* srrg2_scene_clip_spherical for a sensor whose rings are not uniformly spaced: ring_elevations[r] (HOST memory, p->model.rows
+ * doubles, radians) is the elevation of row r, strictly ascending or strictly descending.  The model's elevation_min and
+ * elevation_increment are then neither read nor validated; everything else is srrg2_scene_clip_spherical's.
+ *   rows      boundaries in float64: b[0] = e[0] - (e[1] - e[0])*0.5, b[k] = (e[k-1] + e[k])*0.5, b[rows] = e[rows-1] +
+ *             (e[rows-1] - e[rows-2])*0.5; a point of elevation eps is in view iff it lies in [b[0], b[rows]) (descending
+ *             table: (b[rows], b[0]]) and takes the row whose interval holds it; a point on a boundary goes to the higher row
+ *             index.  The adaptor (srrg2_lidar_sweep_extras.ring_elevations) bins the same way.
+ *   NULL      ring_elevations == NULL is srrg2_scene_clip_spherical, bit for bit.
+ *   refused   `clipped` unchanged.  SRRG2_E_INVALID: rows < 2; an entry not finite or beyond (pi/2)(1 + 2^-20) in magnitude; a
+ *             table that is not strictly monotonic; whatever srrg2_scene_clip_spherical refuses.  SRRG2_E_UNSUPPORTED: rows > 256.
+ *   waits     the table is consumed before the call returns. */
+int srrg2_scene_clip_spherical_rings(srrg2_scene_h full, const float* robot_in_local_map, const srrg2_spherical_clip_params* p,
+                                     const double* ring_elevations /* HOST, p->model.rows entries; NULL = plain */,
+                                     srrg2_scene_h clipped, srrg2_clip_result* out /* may be NULL */);
 
 /* Normals for a scene that arrived as a plain list of points (a 3-D lidar sweep, a map from disk, srrg2_scene_set without
  * normals, a merged map whose averaged normals have drifted): per point the PCA of its radius neighbourhood, on the device.
@@ -958,6 +973,44 @@ void srrg2_adapt_default_lidar_params(srrg2_lidar_adaptor_params* p);
 int srrg2_adapt_lidar_sweep(srrg2_scene_h dst /* dim 3 */, const float* points, int point_stride_bytes,
                             const float* intensity /* may be NULL */, int intensity_stride_bytes, int n, int mem,
                             const srrg2_lidar_adaptor_params* p, srrg2_adapt_result* out /* may be NULL */);
+
+/* srrg2_adapt_lidar_sweep for real sensors: a per-ring elevation table and the de-skew of a sweep taken while the sensor moved
+ * (DESIGN.md section 4 "Lidar sweeps", contracts 1 and 2).  x == NULL, or the defaults, give srrg2_adapt_lidar_sweep bit for bit.
+ *   rings     ring_elevations as in srrg2_scene_clip_spherical_rings (same rows, same refusals; the model's elevation_min /
+ *             elevation_increment are then neither read nor validated).  A host table, consumed before the call returns.
+ *   de-skew   deskew != 0.  The image stays the sensor's firing grid: every point is projected and binned from its RAW
+ *             coordinates (nearest-wins with the raw range); what the scene stores for a winner, what its neighbours lend to a
+ *             normal and what turns the normal towards the sensor are the DE-SKEWED coordinates.
+ *             time     s = ((double) times[i] - time_begin) / (time_end - time_begin), not clamped: points outside the interval
+ *                      are extrapolated; a point whose time is not finite is treated as a point with a non-finite coordinate.
+ *                      times == NULL: s = tf / cols, tf the continuous column coordinate of the point's raw projection -- column 0
+ *                      is taken as the sweep's start, so the columns a sensor fires again past the seam get SMALL s (they are
+ *                      de-skewed as if fired at the start); give per-point times where that matters.
+ *             motion   3x4 [R|t], the sensor at s = 1 in the sensor frame at s = 0 (prev^-1 * curr of a constant-velocity
+ *                      model).  Constant rotation rate about the fixed axis of R, translation linear in s (not the SE(3) screw):
+ *                      q = Rot(axis, s*theta) * p + s*t, out = Rot(axis, reference*theta)^T * (q - reference*t), float64, each
+ *                      component rounded to float32 once.  reference = 1 expresses the scene in the sensor frame at the sweep's
+ *                      end, 0 at its start.  The result is specified for |s*theta| <= 1e6 rad.
+ *   refused   SRRG2_E_INVALID, dst unchanged: whatever srrg2_adapt_lidar_sweep refuses; reserved != 0; a bad ring table; with
+ *             deskew: motion or reference not finite; with deskew and times: time_begin or time_end not finite or equal, a
+ *             stride < 4 or no multiple of 4, times not 4-byte aligned.  SRRG2_E_UNSUPPORTED: a ring table with rows > 256.
+ *   waits     as srrg2_adapt_lidar_sweep; times live in the same `mem` as the points and follow the points' rules. */
+typedef struct srrg2_lidar_sweep_extras {
+  const double* ring_elevations;  /* HOST, model.rows entries (radians); NULL: the model's uniform rows */
+  const float*  times;            /* per point, in the same `mem` as the points; NULL with deskew != 0: time from the raw azimuth */
+  int32_t time_stride_bytes;      /* >= 4, multiple of 4 (20 with times = points + 4 reads XYZIT records) */
+  int32_t deskew;                 /* 0: off -- times, time_*, reference, motion are not looked at */
+  double  time_begin, time_end;   /* the times that mean s = 0 and s = 1; used only when times != NULL */
+  double  reference;              /* s of the frame the output is expressed in; default 1 (the sweep's end) */
+  float   motion[12];             /* 3x4 [R|t]: the sensor at s = 1 in the sensor frame at s = 0 */
+  int32_t reserved[2];            /* 0 */
+} srrg2_lidar_sweep_extras;
+/* all off: no table, no times, deskew 0, reference 1, motion identity */
+void srrg2_adapt_default_lidar_sweep_extras(srrg2_lidar_sweep_extras* x);
+int srrg2_adapt_lidar_sweep_ex(srrg2_scene_h dst /* dim 3 */, const float* points, int point_stride_bytes,
+                               const float* intensity /* may be NULL */, int intensity_stride_bytes, int n, int mem,
+                               const srrg2_lidar_adaptor_params* p, const srrg2_lidar_sweep_extras* x /* NULL = plain */,
+                               srrg2_adapt_result* out /* may be NULL */);
 
 /* ---- strategy knobs (no reference counterpart) ----------------------------------------------------------------
  * Every setting gives the SAME results (indices, estimates, statistics bit for bit): the knobs choose between exact

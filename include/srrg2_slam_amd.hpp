@@ -633,10 +633,20 @@ public:
   void setRobotInLocalMap(const EstimateType& T) { _robot_in_local_map = T; }
   void setSensorInRobot(const EstimateType& T) { std::memcpy(param.sensor_in_robot, T.data(), sizeof(param.sensor_in_robot)); }  // :86-89
   void setModel(const srrg2_spherical_model& m) { param.model = m; }
+  // one elevation (radians) per row of param.model, strictly ascending or descending, for sensors whose rings are not uniformly
+  // spaced (srrg2_scene_clip_spherical_rings; the model's elevation_min / elevation_increment are then ignored); a copy is kept.
+  // nullptr or rows == 0: back to the model's uniform rows
+  void setRingElevations(const double* elevations, int rows) {
+    _rings.assign(elevations, elevations + (elevations && rows > 0 ? rows : 0));
+  }
+  const std::vector<double>& ringElevations() const { return _rings; }
   void compute() {
     if (!_full || !_clipped) throw std::runtime_error("SceneClipperSpherical::compute|scene not set");
+    if (!_rings.empty() && (int) _rings.size() != param.model.rows)
+      throw std::runtime_error("SceneClipperSpherical::compute|one ring elevation per row of the model expected");
     _status = Error;
-    check(srrg2_scene_clip_spherical(_full->handle(), _robot_in_local_map.data(), &param, _clipped->handle(), &_last));
+    check(srrg2_scene_clip_spherical_rings(_full->handle(), _robot_in_local_map.data(), &param,
+                                           _rings.empty() ? nullptr : _rings.data(), _clipped->handle(), &_last));
     _status = static_cast<Status>(_last.status);
   }
   Status status() const { return _status; }
@@ -653,6 +663,7 @@ private:
   SceneType* _full    = nullptr;
   SceneType* _clipped = nullptr;
   EstimateType _robot_in_local_map = EstimateType::Identity();
+  std::vector<double> _rings;
   srrg2_clip_result _last{};
   Status _status = Error;
 };
@@ -792,7 +803,10 @@ class LidarSweepAdaptor : public AdaptorBase_ {
 public:
   using MeasurementType = Scene<3>;
   srrg2_lidar_adaptor_params param;
-  LidarSweepAdaptor() { srrg2_adapt_default_lidar_params(&param); }
+  LidarSweepAdaptor() {
+    srrg2_adapt_default_lidar_params(&param);
+    srrg2_adapt_default_lidar_sweep_extras(&_extras);
+  }
   // a full-turn sensor: srrg2_spherical_model_full_turn into param.model
   void setFullTurnModel(int rows, int cols, double elevation_first, double elevation_last) {
     check(srrg2_spherical_model_full_turn(&param.model, rows, cols, elevation_first, elevation_last));
@@ -805,6 +819,27 @@ public:
     _mem = mem, _has_raw = true;
     _status = Error;
   }
+  // srrg2_lidar_sweep_extras (srrg2_adapt_lidar_sweep_ex); with none of the three set, compute() is srrg2_adapt_lidar_sweep.
+  // one elevation (radians) per row of param.model, strictly monotonic; a copy is kept.  nullptr or rows == 0: uniform rows
+  void setRingElevations(const double* elevations, int rows) {
+    _rings.assign(elevations, elevations + (elevations && rows > 0 ? rows : 0));
+  }
+  // one float per point, in the memory of the points, borrowed like them; time_begin / time_end: the times that mean the sweep's
+  // start and end.  nullptr: with a motion set, the time comes from the raw azimuth
+  void setTimes(const float* times, int stride_bytes, double time_begin, double time_end) {
+    _extras.times = times, _extras.time_stride_bytes = stride_bytes;
+    _extras.time_begin = time_begin, _extras.time_end = time_end;
+  }
+  // de-skew: the sensor at the sweep's end in its frame at the sweep's start (prev^-1 * curr of a constant-velocity model);
+  // reference: the normalised time of the frame the scene is expressed in (1 = the end).  An identity motion gives the plain
+  // adapt's values
+  void setMotion(const Isometry<3>& motion, double reference = 1.0) {
+    std::memcpy(_extras.motion, motion.data(), sizeof(_extras.motion));
+    _extras.reference = reference;
+    _extras.deskew    = 1;
+  }
+  const srrg2_lidar_sweep_extras& extras() const { return _extras; }
+  const std::vector<double>& ringElevations() const { return _rings; }
   void setMeas(MeasurementType* meas) { _meas = meas; }
   void reset() {
     _has_raw = false;
@@ -812,8 +847,12 @@ public:
   }
   void compute(bool want_result = true) {
     if (!_meas || !_has_raw) throw std::runtime_error("LidarSweepAdaptor::compute|raw data or measurement not set");
-    finish(srrg2_adapt_lidar_sweep(_meas->handle(), _points, _point_stride, _inten, _inten_stride, _n, _mem, &param,
-                                   want_result ? &_last : nullptr),
+    if (!_rings.empty() && (int) _rings.size() != param.model.rows)
+      throw std::runtime_error("LidarSweepAdaptor::compute|one ring elevation per row of the model expected");
+    srrg2_lidar_sweep_extras x = _extras;
+    x.ring_elevations          = _rings.empty() ? nullptr : _rings.data();
+    finish(srrg2_adapt_lidar_sweep_ex(_meas->handle(), _points, _point_stride, _inten, _inten_stride, _n, _mem, &param, &x,
+                                      want_result ? &_last : nullptr),
            want_result);
   }
 
@@ -823,6 +862,8 @@ private:
   const float* _inten    = nullptr;
   int _point_stride = 0, _inten_stride = 0, _n = 0, _mem = SRRG2_MEM_HOST;
   bool _has_raw = false;
+  srrg2_lidar_sweep_extras _extras;
+  std::vector<double> _rings;
 };
 
 // ---- binary descriptor database: the matching half of MultiLoopDetectorHBST_ --------------------------------------

@@ -188,6 +188,13 @@ class LidarAdaptorParams(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class LidarSweepExtras(C.Structure):
+    """srrg2_lidar_sweep_extras: ring elevation table (host doubles) and motion de-skew of srrg2_adapt_lidar_sweep_ex"""
+    _fields_ = [("ring_elevations", C.POINTER(C.c_double)), ("times", C.c_void_p), ("time_stride_bytes", C.c_int32),
+                ("deskew", C.c_int32), ("time_begin", C.c_double), ("time_end", C.c_double), ("reference", C.c_double),
+                ("motion", C.c_float * 12), ("reserved", C.c_int32 * 2)]
+
+
 class SphericalClipParams(C.Structure):
     """srrg2_spherical_clip_params"""
     _fields_ = [("model", SphericalModel), ("sensor_in_robot", C.c_float * 12), ("occlusion_margin", C.c_float),

@@ -62,6 +62,11 @@ def lib():
         _LIB.srrg2_spherical_model_full_turn.argtypes = [C.POINTER(abi.SphericalModel), C.c_int, C.c_int, C.c_double, C.c_double]
         _LIB.srrg2_adapt_lidar_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                  C.POINTER(abi.LidarAdaptorParams), C.POINTER(abi.AdaptResult)]
+        _LIB.srrg2_adapt_default_lidar_sweep_extras.argtypes = [C.POINTER(abi.LidarSweepExtras)]
+        _LIB.srrg2_adapt_default_lidar_sweep_extras.restype = None
+        _LIB.srrg2_adapt_lidar_sweep_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                    C.POINTER(abi.LidarAdaptorParams), C.POINTER(abi.LidarSweepExtras),
+                                                    C.POINTER(abi.AdaptResult)]
         # srrg2_scene_clip_projective (mapping.SceneClipperProjective)
         from . import mapping
 
@@ -79,6 +84,8 @@ def lib():
         _LIB.srrg2_clip_default_spherical_params.restype = None
         _LIB.srrg2_scene_clip_spherical.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(abi.SphericalClipParams),
                                                     C.c_void_p, C.POINTER(mapping.ClipResult)]
+        _LIB.srrg2_scene_clip_spherical_rings.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(abi.SphericalClipParams),
+                                                          C.POINTER(C.c_double), C.c_void_p, C.POINTER(mapping.ClipResult)]
         # srrg2_scene_estimate_normals (mapping.Scene.estimate_normals)
         _LIB.srrg2_normals_default_params.argtypes = [C.POINTER(abi.NormalsParams), C.c_int]
         _LIB.srrg2_normals_default_params.restype = None

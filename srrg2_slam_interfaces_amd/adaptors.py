@@ -186,44 +186,87 @@ class MeasurementAdaptorLaserScan(_AdaptorBase):
         return self._finish(out, want_result)
 
 
+def default_lidar_sweep_extras():
+    """srrg2_lidar_sweep_extras with everything off: no ring table, no times, deskew 0, reference 1, identity motion"""
+    from . import _capi
+
+    x = abi.LidarSweepExtras()
+    _capi.lib().srrg2_adapt_default_lidar_sweep_extras(C.byref(x))
+    return x
+
+
 class MeasurementAdaptorLidarSweep(_AdaptorBase):
     """params: abi.LidarAdaptorParams (model, gaps, gate, drop, compact).  In compact mode the scene's global indices are the
-    pixel indices row*cols + col of the range image."""
+    pixel indices row*cols + col of the range image.  ``set_ring_elevations`` and ``set_motion`` switch on the per-ring table
+    and the de-skew of srrg2_adapt_lidar_sweep_ex; without them compute() is srrg2_adapt_lidar_sweep."""
 
     def __init__(self, params=None):
         super().__init__()
         self.params = params or default_lidar_params()
         self._raw = None
+        self._rings = None
+        self._motion = None  # (motion (12,) float32, reference, time_begin, time_end)
 
     def set_model(self, model):
         """copy an abi.SphericalModel (e.g. from ``spherical_model_full_turn``) into the params"""
         C.memmove(C.byref(self.params.model), C.byref(model), C.sizeof(abi.SphericalModel))
 
-    def set_raw_data(self, points, intensity=None):
+    def set_ring_elevations(self, elevations):
+        """one elevation (radians) per row of the model, strictly ascending or descending (the model's elevation_min /
+        elevation_increment are then ignored); None: the model's uniform rows.  A copy is kept."""
+        self._rings = None if elevations is None else np.array(elevations, dtype=np.float64).reshape(-1)
+
+    def set_motion(self, motion, reference=1.0, time_begin=None, time_end=None):
+        """de-skew the sweep: ``motion`` is the 3x4 [R|t] of the sensor at the sweep's end in its frame at the sweep's start
+        (prev^-1 * curr of a constant-velocity model), ``reference`` the normalised time of the frame the scene is expressed in
+        (1: the end).  ``time_begin`` / ``time_end`` say which per-point times (``set_raw_data(times=...)``) mean the start and
+        the end; without per-point times the time comes from the raw azimuth.  ``motion=None`` switches the de-skew off."""
+        if motion is None:
+            self._motion = None
+            return
+        m = np.ascontiguousarray(np.asarray(motion, np.float32).reshape(-1)[:12])
+        if m.shape[0] != 12:
+            raise ValueError("motion: a 3x4 (or 4x4) matrix expected")
+        self._motion = (m, float(reference), time_begin, time_end)
+
+    def set_raw_data(self, points, intensity=None, times=None):
         """points: (n, 3) float32 array of x, y, z in the sensor frame, or (n, 4) of x, y, z, intensity (then ``intensity``
-        must be None), or a (device_pointer, stride_bytes, n) triple; intensity: (n,) floats, or a (device_pointer, stride_bytes)
-        pair next to device points.  The arrays are read at compute()."""
+        must be None), or (n, 5) of x, y, z, intensity, time (then ``times`` must be None as well), or a
+        (device_pointer, stride_bytes, n) triple; intensity: (n,) floats, or a (device_pointer, stride_bytes) pair next to device
+        points; times: likewise, one float32 per point (read only when a motion is set).  The arrays are read at compute()."""
         if isinstance(points, tuple):
             ptr, stride, n = points
             iptr, istride = (None, 0) if intensity is None else (C.c_void_p(int(intensity[0])), int(intensity[1]))
-            self._raw = (None, C.c_void_p(int(ptr)), int(stride), iptr, istride, int(n), abi.MEM_DEVICE)
+            tptr, tstride = (None, 0) if times is None else (C.c_void_p(int(times[0])), int(times[1]))
+            self._raw = (None, C.c_void_p(int(ptr)), int(stride), iptr, istride, int(n), abi.MEM_DEVICE, tptr, tstride)
         else:
             a = np.asarray(points)
-            if a.ndim != 2 or a.shape[1] not in (3, 4):
-                raise ValueError("points: an (n, 3) or (n, 4) array expected, got %s" % (a.shape,))
+            if a.ndim != 2 or a.shape[1] not in (3, 4, 5):
+                raise ValueError("points: an (n, 3), (n, 4) or (n, 5) array expected, got %s" % (a.shape,))
             a = np.ascontiguousarray(a, dtype=np.float32)
             n, w = a.shape
-            keep, iptr, istride = (a,), None, 0
-            if w == 4:
+            keep, iptr, istride, tptr, tstride = [a], None, 0, None, 0
+            if w >= 4:
                 if intensity is not None:
                     raise ValueError("intensity: given twice (the points already have a fourth column)")
-                iptr, istride = C.c_void_p(a.ctypes.data + 12), 16
+                iptr, istride = C.c_void_p(a.ctypes.data + 12), 4 * w
             elif intensity is not None:
                 it = np.ascontiguousarray(intensity, dtype=np.float32).reshape(-1)
                 if it.shape[0] != n:
                     raise ValueError("intensity: one value per point expected")
-                keep, iptr, istride = (a, it), C.c_void_p(it.ctypes.data), 4
-            self._raw = (keep, C.c_void_p(a.ctypes.data), 4 * w, iptr, istride, n, abi.MEM_HOST)
+                keep.append(it)
+                iptr, istride = C.c_void_p(it.ctypes.data), 4
+            if w == 5:
+                if times is not None:
+                    raise ValueError("times: given twice (the points already have a fifth column)")
+                tptr, tstride = C.c_void_p(a.ctypes.data + 16), 20
+            elif times is not None:
+                tm = np.ascontiguousarray(times, dtype=np.float32).reshape(-1)
+                if tm.shape[0] != n:
+                    raise ValueError("times: one value per point expected")
+                keep.append(tm)
+                tptr, tstride = C.c_void_p(tm.ctypes.data), 4
+            self._raw = (tuple(keep), C.c_void_p(a.ctypes.data), 4 * w, iptr, istride, n, abi.MEM_HOST, tptr, tstride)
         self._status = abi.ADAPTOR_ERROR
 
     def reset(self):
@@ -231,10 +274,36 @@ class MeasurementAdaptorLidarSweep(_AdaptorBase):
         self._status = abi.ADAPTOR_INITIALIZING
         self.last = None
 
+    def _extras(self, tptr, tstride):
+        """the srrg2_lidar_sweep_extras of this compute(), or None for the plain call"""
+        if self._rings is None and self._motion is None:
+            return None
+        x = default_lidar_sweep_extras()
+        if self._rings is not None:
+            if self._rings.shape[0] != self.params.model.rows:
+                raise ValueError("ring elevations: %d entries for %d rows" % (self._rings.shape[0], self.params.model.rows))
+            x.ring_elevations = self._rings.ctypes.data_as(C.POINTER(C.c_double))
+        if self._motion is not None:
+            m, reference, t0, t1 = self._motion
+            x.deskew, x.reference = 1, reference
+            for i in range(12):
+                x.motion[i] = float(m[i])
+            if tptr is not None:
+                if t0 is None or t1 is None:
+                    raise ValueError("set_motion: time_begin and time_end are needed with per-point times")
+                x.times, x.time_stride_bytes, x.time_begin, x.time_end = tptr.value, tstride, float(t0), float(t1)
+        return x
+
     def compute(self, want_result=True):
         self._ready()
         out = abi.AdaptResult()
-        _, ptr, stride, iptr, istride, n, mem = self._raw
-        self._check(self._lib.srrg2_adapt_lidar_sweep(self._meas._h, ptr, stride, iptr, istride, n, mem, C.byref(self.params),
-                                                      C.byref(out) if want_result else None))
+        _, ptr, stride, iptr, istride, n, mem, tptr, tstride = self._raw
+        x = self._extras(tptr, tstride)
+        res = C.byref(out) if want_result else None
+        if x is None:
+            rc = self._lib.srrg2_adapt_lidar_sweep(self._meas._h, ptr, stride, iptr, istride, n, mem, C.byref(self.params), res)
+        else:
+            rc = self._lib.srrg2_adapt_lidar_sweep_ex(self._meas._h, ptr, stride, iptr, istride, n, mem, C.byref(self.params),
+                                                      C.byref(x), res)
+        self._check(rc)
         return self._finish(out, want_result)

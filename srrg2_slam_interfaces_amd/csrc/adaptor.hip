@@ -5,8 +5,8 @@
 //   RawDataPreprocessor_::compute() (interface)       S/raw_data_preprocessors/raw_data_preprocessor.h:13-88
 // The reference ships the interface only; the adaptors here (depth image -> organised PointNormal3f cloud, laser scan ->
 // PointNormal2f cloud, lidar sweep -> PointNormal3f cloud through a range image) are defined from first principles: DESIGN.md
-// section 4 "Measurement adaptors" and "Lidar sweeps" are the arithmetic contract, tests/adaptor_restatement.py and
-// tests/lidar_restatement.py restate it in numpy and the library must give the same bits.
+// section 4 "Measurement adaptors" and "Lidar sweeps" are the arithmetic contract, tests/adaptor_restatement.py,
+// tests/lidar_restatement.py and tests/lidar_motion_restatement.py restate it in numpy and the library must give the same bits.
 // Kernels: one thread per pixel / beam, grid-stride.  A thread reads its own raw value and its four (two) neighbours' and
 // RECOMPUTES the neighbours' points from them -- the same expression gives the same bits as the neighbour's own thread, so
 // there is no second pass and no dependency between threads -- and writes point and normal as 16-byte records, coalesced.
@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <utility>
 
 #include "det_math.h"
 #include "host_util.h"
@@ -184,6 +185,65 @@ __global__ __launch_bounds__(256) void k_lidar_bin(const unsigned char* __restri
     float rho;
     const int pix = sph::project(G, x, y, z, rho);  // (pix < rows * cols: project's bounds)
     if (pix >= 0) atomicMin(&winner[pix], ((unsigned long long) __float_as_uint(rho) << 32) | (unsigned long long) (unsigned) i);
+  }
+}
+
+// ---- ring tables and motion de-skew (srrg2_adapt_lidar_sweep_ex; DESIGN.md section 4 "Lidar sweeps", contracts 1 and 2) ----
+// what the de-skew of one point needs, prepared on the host in float64 (deskew_of): the sweep's motion as an angle about a
+// fixed axis plus a translation linear in s, the rotation at s = reference (Rref, row-major) and reference * t
+struct Deskew {
+  const unsigned char* times;  // null: s from the raw azimuth (tf / cols)
+  long long time_stride;
+  double t0, dt;  // time_begin, time_end - time_begin
+  double theta, a[3], t[3], rt[3], Rref[9];
+};
+
+// p (raw, sensor frame at its firing time s) -> the sensor frame at s = reference; each component rounded to float32 once
+__device__ __forceinline__ float4 deskew_point(const Deskew& K, double s, float x, float y, float z) {
+  const double px = (double) x, py = (double) y, pz = (double) z;
+  double sn, cs;
+  dm::sincos(s * K.theta, sn, cs);
+  const double omc = 1.0 - cs;
+  const double cx = K.a[1] * pz - K.a[2] * py, cy = K.a[2] * px - K.a[0] * pz, cz = K.a[0] * py - K.a[1] * px;
+  const double k  = ((K.a[0] * px + K.a[1] * py) + K.a[2] * pz) * omc;
+  const double qx = ((px * cs + cx * sn) + K.a[0] * k) + s * K.t[0];
+  const double qy = ((py * cs + cy * sn) + K.a[1] * k) + s * K.t[1];
+  const double qz = ((pz * cs + cz * sn) + K.a[2] * k) + s * K.t[2];
+  const double vx = qx - K.rt[0], vy = qy - K.rt[1], vz = qz - K.rt[2];
+  return make_float4((float) ((K.Rref[0] * vx + K.Rref[3] * vy) + K.Rref[6] * vz),
+                     (float) ((K.Rref[1] * vx + K.Rref[4] * vy) + K.Rref[7] * vz),
+                     (float) ((K.Rref[2] * vx + K.Rref[5] * vy) + K.Rref[8] * vz), 0.f);
+}
+
+// k_lidar_bin with a ring table (RINGS: staged into LDS once per workgroup) and / or the de-skew fused in (DESKEW): the point
+// is binned from its RAW coordinates -- the image stays the sensor's firing grid -- and what the image will read as its
+// coordinates, the de-skewed point, is written to dsk[i], 16 bytes per in-view point (only winners are ever read, and only
+// in-view points can win).  A point whose time is not finite is a point with a non-finite coordinate.
+template <bool RINGS, bool DESKEW>
+__global__ __launch_bounds__(256) void k_lidar_bin_ex(const unsigned char* __restrict__ pts, long long stride, int n, sph::Geom G,
+                                                      sph::Rings T, Deskew K, unsigned long long* __restrict__ winner,
+                                                      float4* __restrict__ dsk) {
+  __shared__ double sB[RINGS ? sph::MAX_RING_ROWS + 1 : 1];
+  if (RINGS) sph::stage_rings(T, sB);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const float* q = reinterpret_cast<const float*>(pts + (long long) i * stride);
+    const float x = q[0], y = q[1], z = q[2];
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) continue;
+    double s = 0.0;
+    if (DESKEW && K.times) {
+      const float tm = *reinterpret_cast<const float*>(K.times + (long long) i * K.time_stride);
+      if (!isfinite(tm)) continue;
+      s = ((double) tm - K.t0) / K.dt;
+    }
+    float rho;
+    double tf;
+    const int pix = sph::project_t<RINGS>(G, sB, T.descending, x, y, z, rho, tf);  // (pix < rows * cols: project's bounds)
+    if (pix < 0) continue;
+    atomicMin(&winner[pix], ((unsigned long long) __float_as_uint(rho) << 32) | (unsigned long long) (unsigned) i);
+    if (DESKEW) {
+      if (!K.times) s = tf / (double) G.cols;
+      dsk[i] = deskew_point(K, s, x, y, z);
+    }
   }
 }
 
@@ -399,6 +459,177 @@ bool aligned_to(const void* p, long long stride, int elem) {
   return reinterpret_cast<uintptr_t>(p) % (uintptr_t) elem == 0 && stride % elem == 0;
 }
 
+// the host side of the de-skew, float64 with det_math.h only: motion = [R|t] -> angle about a fixed axis (through the unit
+// quaternion, w >= 0), the rotation at s = reference by the per-point formula applied to the three unit vectors, reference * t
+void deskew_of(const srrg2_lidar_sweep_extras& x, Deskew& K) {
+  double R[9], q[4];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) R[i * 3 + j] = (double) x.motion[i * 4 + j];
+    K.t[i] = (double) x.motion[i * 4 + 3];
+  }
+  dm::R_to_quat(R, q);
+  const double vn = sqrt((q[1] * q[1] + q[2] * q[2]) + q[3] * q[3]);
+  if (vn == 0.0) {
+    K.theta = 0.0;
+    K.a[0] = 0.0, K.a[1] = 0.0, K.a[2] = 1.0;
+  } else {
+    K.theta = 2.0 * dm::atan2(vn, q[0]);
+    K.a[0] = q[1] / vn, K.a[1] = q[2] / vn, K.a[2] = q[3] / vn;
+  }
+  double sn, cs;
+  dm::sincos(x.reference * K.theta, sn, cs);
+  const double omc = 1.0 - cs;
+  for (int j = 0; j < 3; ++j) {  // column j = the rotation of e_j
+    const double e[3] = {j == 0 ? 1.0 : 0.0, j == 1 ? 1.0 : 0.0, j == 2 ? 1.0 : 0.0};
+    const double c[3] = {K.a[1] * e[2] - K.a[2] * e[1], K.a[2] * e[0] - K.a[0] * e[2], K.a[0] * e[1] - K.a[1] * e[0]};
+    const double k    = ((K.a[0] * e[0] + K.a[1] * e[1]) + K.a[2] * e[2]) * omc;
+    for (int i = 0; i < 3; ++i) K.Rref[i * 3 + j] = (e[i] * cs + c[i] * sn) + K.a[i] * k;
+  }
+  for (int i = 0; i < 3; ++i) K.rt[i] = x.reference * K.t[i];
+}
+
+// up to three strided host arrays -> the scene's staging buffer; arrays whose byte ranges touch or overlap (interleaved XYZI /
+// XYZIT records) travel together, once.  b[k] .. e[k] in, the device address of b[k] out (a null b[k] is skipped).
+int stage_ranges(srrg2_scene* s, int count, const unsigned char** b, const unsigned char* const* e) {
+  int order[3], m = 0;
+  for (int k = 0; k < count; ++k)
+    if (b[k]) order[m++] = k;
+  for (int i = 1; i < m; ++i)
+    for (int j = i; j > 0 && b[order[j]] < b[order[j - 1]]; --j) std::swap(order[j], order[j - 1]);
+  const unsigned char *lo[3], *hi[3];
+  int span_of[3], spans = 0;
+  for (int i = 0; i < m; ++i) {
+    const int k = order[i];
+    if (spans > 0 && b[k] <= hi[spans - 1]) {
+      if (e[k] > hi[spans - 1]) hi[spans - 1] = e[k];
+    } else {
+      lo[spans] = b[k], hi[spans] = e[k];
+      ++spans;
+    }
+    span_of[k] = spans - 1;
+  }
+  size_t off[3], total = 0;
+  for (int j = 0; j < spans; ++j) {
+    off[j] = total;
+    total  = (total + (size_t) (hi[j] - lo[j]) + 63) / 64 * 64;
+  }
+  int rc;
+  if ((rc = s->staging.reserve(total + 64))) return rc;
+  const unsigned char* d[3];
+  for (int j = 0; j < spans; ++j)
+    if ((rc = stage(s, lo[j], (size_t) (hi[j] - lo[j]), off[j], &d[j]))) return rc;
+  for (int i = 0; i < m; ++i) {
+    const int k = order[i];
+    b[k]        = d[span_of[k]] + (b[k] - lo[span_of[k]]);
+  }
+  return 0;
+}
+
+// srrg2_adapt_lidar_sweep (x == nullptr) and srrg2_adapt_lidar_sweep_ex; `who` opens every message
+int adapt_lidar_sweep(const std::string& who, srrg2_scene_h dst, const float* points, int point_stride, const float* intensity,
+                      int intensity_stride, int n, int mem, const srrg2_lidar_adaptor_params* p, const srrg2_lidar_sweep_extras* x,
+                      srrg2_adapt_result* out) {
+  if (!dst || !p) return fail(SRRG2_E_INVALID, who + "null scene or params");
+  if (dst->dim != 3) return fail(SRRG2_E_INVALID, who + "the scene must have dim 3");
+  if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, who + "bad mem");
+  if (n < 0) return fail(SRRG2_E_INVALID, who + "n >= 0");
+  if (p->reserved != 0) return fail(SRRG2_E_INVALID, who + "reserved must be 0");
+  if (p->normal_col_gap < 0 || p->normal_row_gap < 0 || (p->normal_col_gap == 0) != (p->normal_row_gap == 0))
+    return fail(SRRG2_E_INVALID, who + "normal gaps >= 0, and both or neither 0");
+  const bool rings  = x && x->ring_elevations;
+  const bool deskew = x && x->deskew != 0;
+  const bool timed  = deskew && x->times != nullptr;
+  if (const char* why = sph::invalid(p->model, rings)) return fail(SRRG2_E_INVALID, who + why);
+  sph::Rings table;
+  Deskew K;
+  std::memset(&K, 0, sizeof(K));
+  table.rows = table.descending = 0;
+  if (x) {
+    if (x->reserved[0] != 0 || x->reserved[1] != 0) return fail(SRRG2_E_INVALID, who + "extras: reserved must be 0");
+    if (rings) {
+      bool unsupported;
+      if (const char* why = sph::rings_of(p->model, x->ring_elevations, table, &unsupported))
+        return fail(unsupported ? SRRG2_E_UNSUPPORTED : SRRG2_E_INVALID, who + why);
+    }
+    if (deskew) {
+      bool finite = std::isfinite(x->reference);
+      for (int i = 0; i < 12; ++i) finite = finite && std::isfinite(x->motion[i]);
+      if (!finite) return fail(SRRG2_E_INVALID, who + "extras: motion and reference must be finite");
+      if (timed) {
+        if (!std::isfinite(x->time_begin) || !std::isfinite(x->time_end) || x->time_begin == x->time_end)
+          return fail(SRRG2_E_INVALID, who + "extras: time_begin and time_end must be finite and differ");
+        if (x->time_stride_bytes < 4 || !aligned_to(x->times, x->time_stride_bytes, 4))
+          return fail(SRRG2_E_INVALID, who + "extras: time stride >= 4 and a multiple of 4, times 4-byte aligned");
+      }
+    }
+  }
+  if (n > 0) {
+    if (!points) return fail(SRRG2_E_INVALID, who + "null points");
+    if (point_stride < 12 || !aligned_to(points, point_stride, 4))
+      return fail(SRRG2_E_INVALID, who + "point stride >= 12 and a multiple of 4, points 4-byte aligned");
+    if (intensity && (intensity_stride < 4 || !aligned_to(intensity, intensity_stride, 4)))
+      return fail(SRRG2_E_INVALID, who + "intensity stride >= 4 and a multiple of 4, intensity 4-byte aligned");
+  }
+  int rc;
+  HIP_TRY(hipSetDevice(dst->device));
+  const bool with_inten = intensity != nullptr;
+  LidarSource src;
+  std::memset(&src, 0, sizeof(src));
+  src.rows = p->model.rows, src.cols = p->model.cols;
+  src.gc = p->normal_col_gap, src.gr = p->normal_row_gap;
+  src.wrap  = sph::columns_wrap(p->model);
+  src.maxd2 = p->normal_max_distance_squared;
+  src.drop  = p->drop_points_without_normal != 0;
+  const bool normals = src.gc > 0;
+  if (n == 0) return run_adapt(dst, src, 0, normals, with_inten, p->compact != 0, out);  // an empty scene, INITIALIZING
+  src.pts        = reinterpret_cast<const unsigned char*>(points);
+  src.inten      = reinterpret_cast<const unsigned char*>(intensity);
+  src.pts_stride = point_stride, src.inten_stride = intensity_stride;
+  if (timed) {
+    K.times       = reinterpret_cast<const unsigned char*>(x->times);
+    K.time_stride = x->time_stride_bytes;
+    K.t0          = x->time_begin;
+    K.dt          = x->time_end - x->time_begin;
+  }
+  hipStream_t st = dst->stream;
+  if (mem == SRRG2_MEM_HOST) {  // the records as they lie; interleaved intensities and times travel with their points, once
+    const unsigned char* b[3] = {src.pts, src.inten, K.times};
+    const unsigned char* e[3] = {b[0] + (size_t) (n - 1) * (size_t) point_stride + 12,
+                                 with_inten ? b[1] + (size_t) (n - 1) * (size_t) intensity_stride + 4 : nullptr,
+                                 timed ? b[2] + (size_t) (n - 1) * (size_t) K.time_stride + 4 : nullptr};
+    if ((rc = stage_ranges(dst, 3, b, e))) return rc;
+    src.pts = b[0], src.inten = b[1], K.times = b[2];
+    HIP_TRY(hipStreamSynchronize(st));  // the caller's cloud is consumed (pinned memory too) before anything is queued
+  }
+  const size_t npix = (size_t) src.rows * (size_t) src.cols;
+  if ((rc = dst->winner.reserve(npix))) return rc;
+  if (deskew && (rc = dst->deskewed.reserve((size_t) n))) return rc;
+  HIP_TRY(hipMemsetAsync(dst->winner.p, 0xff, npix * sizeof(unsigned long long), st));
+  const dim3 grid(adapt_blocks(n)), block(256);
+  const sph::Geom geom = sph::geom_of(p->model);
+  if (!rings && !deskew) {
+    hipLaunchKernelGGL(k_lidar_bin, grid, block, 0, st, src.pts, src.pts_stride, n, geom, dst->winner.p);
+  } else {
+    if (deskew) deskew_of(*x, K);
+    float4* const dsk = deskew ? dst->deskewed.p : nullptr;
+    if (rings && deskew)
+      hipLaunchKernelGGL((k_lidar_bin_ex<true, true>), grid, block, 0, st, src.pts, src.pts_stride, n, geom, table, K, dst->winner.p, dsk);
+    else if (rings)
+      hipLaunchKernelGGL((k_lidar_bin_ex<true, false>), grid, block, 0, st, src.pts, src.pts_stride, n, geom, table, K, dst->winner.p, dsk);
+    else
+      hipLaunchKernelGGL((k_lidar_bin_ex<false, true>), grid, block, 0, st, src.pts, src.pts_stride, n, geom, table, K, dst->winner.p, dsk);
+    if (deskew) {  // the image reads the de-skewed points from here on
+      src.pts        = reinterpret_cast<const unsigned char*>(dsk);
+      src.pts_stride = 16;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  src.winner = dst->winner.p;
+  if ((rc = run_adapt(dst, src, (int) npix, normals, with_inten, p->compact != 0, out))) return rc;
+  if (out) out->num_raw = n;  // (run_adapt counted the pixels it walked)
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -546,67 +777,22 @@ int srrg2_spherical_model_full_turn(srrg2_spherical_model* m, int rows, int cols
   return 0;
 }
 
+void srrg2_adapt_default_lidar_sweep_extras(srrg2_lidar_sweep_extras* x) {
+  if (!x) return;
+  std::memset(x, 0, sizeof(*x));
+  x->reference = 1.0;
+  x->motion[0] = x->motion[5] = x->motion[10] = 1.f;
+}
+
 int srrg2_adapt_lidar_sweep(srrg2_scene_h dst, const float* points, int point_stride, const float* intensity, int intensity_stride,
                             int n, int mem, const srrg2_lidar_adaptor_params* p, srrg2_adapt_result* out) {
-  if (!dst || !p) return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: null scene or params");
-  if (dst->dim != 3) return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: the scene must have dim 3");
-  if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: bad mem");
-  if (n < 0) return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: n >= 0");
-  if (p->reserved != 0) return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: reserved must be 0");
-  if (p->normal_col_gap < 0 || p->normal_row_gap < 0 || (p->normal_col_gap == 0) != (p->normal_row_gap == 0))
-    return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: normal gaps >= 0, and both or neither 0");
-  if (const char* why = sph::invalid(p->model)) return fail(SRRG2_E_INVALID, std::string("adapt_lidar_sweep: ") + why);
-  if (n > 0) {
-    if (!points) return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: null points");
-    if (point_stride < 12 || !aligned_to(points, point_stride, 4))
-      return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: point stride >= 12 and a multiple of 4, points 4-byte aligned");
-    if (intensity && (intensity_stride < 4 || !aligned_to(intensity, intensity_stride, 4)))
-      return fail(SRRG2_E_INVALID, "adapt_lidar_sweep: intensity stride >= 4 and a multiple of 4, intensity 4-byte aligned");
-  }
-  int rc;
-  HIP_TRY(hipSetDevice(dst->device));
-  const bool with_inten = intensity != nullptr;
-  LidarSource src;
-  std::memset(&src, 0, sizeof(src));
-  src.rows = p->model.rows, src.cols = p->model.cols;
-  src.gc = p->normal_col_gap, src.gr = p->normal_row_gap;
-  src.wrap  = sph::columns_wrap(p->model);
-  src.maxd2 = p->normal_max_distance_squared;
-  src.drop  = p->drop_points_without_normal != 0;
-  const bool normals = src.gc > 0;
-  if (n == 0) return run_adapt(dst, src, 0, normals, with_inten, p->compact != 0, out);  // an empty scene, INITIALIZING
-  src.pts        = reinterpret_cast<const unsigned char*>(points);
-  src.inten      = reinterpret_cast<const unsigned char*>(intensity);
-  src.pts_stride = point_stride, src.inten_stride = intensity_stride;
-  hipStream_t st = dst->stream;
-  if (mem == SRRG2_MEM_HOST) {  // the records as they lie; interleaved intensities travel with their points, once
-    const unsigned char *pb = src.pts, *pe = pb + (size_t) (n - 1) * (size_t) point_stride + 12;
-    const unsigned char *ib = src.inten, *ie = with_inten ? ib + (size_t) (n - 1) * (size_t) intensity_stride + 4 : nullptr;
-    const unsigned char* d = nullptr;
-    if (with_inten && ib <= pe && pb <= ie) {
-      const unsigned char *lo = pb < ib ? pb : ib, *hi = pe > ie ? pe : ie;
-      if ((rc = dst->staging.reserve((size_t) (hi - lo) + 64))) return rc;
-      if ((rc = stage(dst, lo, (size_t) (hi - lo), 0, &d))) return rc;
-      src.pts   = d + (pb - lo);
-      src.inten = d + (ib - lo);
-    } else {
-      const size_t bp = (size_t) (pe - pb), bi = with_inten ? (size_t) (ie - ib) : 0, off_i = (bp + 63) / 64 * 64;
-      if ((rc = dst->staging.reserve(off_i + bi + 64))) return rc;
-      if ((rc = stage(dst, pb, bp, 0, &src.pts))) return rc;
-      if (with_inten && (rc = stage(dst, ib, bi, off_i, &src.inten))) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));  // the caller's cloud is consumed (pinned memory too) before anything is queued
-  }
-  const size_t npix = (size_t) src.rows * (size_t) src.cols;
-  if ((rc = dst->winner.reserve(npix))) return rc;
-  HIP_TRY(hipMemsetAsync(dst->winner.p, 0xff, npix * sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(k_lidar_bin, dim3(adapt_blocks(n)), dim3(256), 0, st, src.pts, src.pts_stride, n, sph::geom_of(p->model),
-                     dst->winner.p);
-  HIP_TRY(hipGetLastError());
-  src.winner = dst->winner.p;
-  if ((rc = run_adapt(dst, src, (int) npix, normals, with_inten, p->compact != 0, out))) return rc;
-  if (out) out->num_raw = n;  // (run_adapt counted the pixels it walked)
-  return 0;
+  return adapt_lidar_sweep("adapt_lidar_sweep: ", dst, points, point_stride, intensity, intensity_stride, n, mem, p, nullptr, out);
+}
+
+int srrg2_adapt_lidar_sweep_ex(srrg2_scene_h dst, const float* points, int point_stride, const float* intensity,
+                               int intensity_stride, int n, int mem, const srrg2_lidar_adaptor_params* p,
+                               const srrg2_lidar_sweep_extras* x, srrg2_adapt_result* out) {
+  return adapt_lidar_sweep("adapt_lidar_sweep_ex: ", dst, points, point_stride, intensity, intensity_stride, n, mem, p, x, out);
 }
 
 }  // extern "C"

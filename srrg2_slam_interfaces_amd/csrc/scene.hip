@@ -312,12 +312,16 @@ __global__ void k_sclip_flag(Xf L, Xf S, ScanGeom G, const float4* __restrict__ 
 //                    -DSRRG2_SPCLIP_RECOMPUTE builds the variant whose flag pass projects again).
 //   k_spclip_flag    keep flag per point; without occlusion it projects and counts itself
 // and k_scatter_kept moves what the scan kept.
-__device__ __forceinline__ int spclip_project(const Xf& L, const Xf& S, const sph::Geom& G, const float4 p, bool& valid, float& rho) {
+// RINGS: the rows of a ring table (B: the boundaries in LDS, sph::stage_rings) instead of the model's uniform rows
+template <bool RINGS>
+__device__ __forceinline__ int spclip_project(const Xf& L, const Xf& S, const sph::Geom& G, const double* B, int descending,
+                                              const float4 p, bool& valid, float& rho) {
   valid = valid_point(3, p);
   if (!valid) return -1;
   const float4 c = xform_point(3, S, xform_point(3, L, p));
   if (!(isfinite(c.x) && isfinite(c.y) && isfinite(c.z))) return -1;
-  return sph::project(G, c.x, c.y, c.z, rho);
+  double tf;
+  return sph::project_t<RINGS>(G, B, descending, c.x, c.y, c.z, rho, tf);
 }
 
 // counters: [CLIP_VALID], [CLIP_IN_VIEW]
@@ -327,7 +331,7 @@ __global__ void k_spclip_rmin(Xf L, Xf S, sph::Geom G, const float4* __restrict_
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     bool valid;
     float rho     = 0.f;
-    const int pix = spclip_project(L, S, G, pts[i], valid, rho);
+    const int pix = spclip_project<false>(L, S, G, nullptr, 0, pts[i], valid, rho);
     nvalid += valid ? 1 : 0;
     nview += pix >= 0 ? 1 : 0;
     if (pix >= 0) atomicMin(&rmin[pix], __float_as_uint(rho));  // (pix < rows * cols: project's bounds)
@@ -356,12 +360,49 @@ __global__ void k_spclip_flag(Xf L, Xf S, sph::Geom G, float margin, const float
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     bool valid;
     float rho     = 0.f;
-    const int pix = spclip_project(L, S, G, pts[i], valid, rho);
+    const int pix = spclip_project<false>(L, S, G, nullptr, 0, pts[i], valid, rho);
     bool keep     = pix >= 0;
     nvalid += valid ? 1 : 0;
     nview += keep ? 1 : 0;
     if (OCCLUSION && keep) keep = rho <= __uint_as_float(rmin[pix]) + margin;
     flags[i] = keep ? 1 : 0;
+  }
+  block_add(nvalid, &counters[CLIP_VALID]);
+  block_add(nview, &counters[CLIP_IN_VIEW]);
+}
+
+// the two projecting passes for a sensor with a ring table (srrg2_scene_clip_spherical_rings): the boundaries travel by value and
+// are staged into LDS once per workgroup; k_spclip_flag_staged is shared with the uniform model
+__global__ void k_spclip_rings_rmin(Xf L, Xf S, sph::Geom G, sph::Rings T, const float4* __restrict__ pts, int n,
+                                    unsigned* __restrict__ rmin, uint2* __restrict__ stage, int* __restrict__ counters) {
+  __shared__ double sB[sph::MAX_RING_ROWS + 1];
+  sph::stage_rings(T, sB);
+  int nvalid = 0, nview = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    bool valid;
+    float rho     = 0.f;
+    const int pix = spclip_project<true>(L, S, G, sB, T.descending, pts[i], valid, rho);
+    nvalid += valid ? 1 : 0;
+    nview += pix >= 0 ? 1 : 0;
+    if (pix >= 0) atomicMin(&rmin[pix], __float_as_uint(rho));  // (pix < rows * cols: project's bounds)
+    stage[i] = make_uint2((unsigned) pix, __float_as_uint(rho));
+  }
+  block_add(nvalid, &counters[CLIP_VALID]);
+  block_add(nview, &counters[CLIP_IN_VIEW]);
+}
+
+__global__ void k_spclip_rings_flag(Xf L, Xf S, sph::Geom G, sph::Rings T, const float4* __restrict__ pts, int n,
+                                    int* __restrict__ flags, int* __restrict__ counters) {
+  __shared__ double sB[sph::MAX_RING_ROWS + 1];
+  sph::stage_rings(T, sB);
+  int nvalid = 0, nview = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    bool valid;
+    float rho     = 0.f;
+    const int pix = spclip_project<true>(L, S, G, sB, T.descending, pts[i], valid, rho);
+    nvalid += valid ? 1 : 0;
+    nview += pix >= 0 ? 1 : 0;
+    flags[i] = pix >= 0 ? 1 : 0;
   }
   block_add(nvalid, &counters[CLIP_VALID]);
   block_add(nview, &counters[CLIP_IN_VIEW]);
@@ -1100,24 +1141,26 @@ int srrg2_scene_clip_scan(srrg2_scene_h full, const float* robot_in_local_map, c
   return 0;
 }
 
-void srrg2_clip_default_spherical_params(srrg2_spherical_clip_params* p) {
-  if (!p) return;
-  std::memset(p, 0, sizeof(*p));
-  p->model.range_min = 0.5f;
-  p->model.range_max = 120.f;
-  p->sensor_in_robot[0] = p->sensor_in_robot[5] = p->sensor_in_robot[10] = 1.f;
-  p->occlusion_margin = -1.f;
-}
+}  // extern "C"
 
-int srrg2_scene_clip_spherical(srrg2_scene_h full, const float* robot_in_local_map, const srrg2_spherical_clip_params* p,
-                               srrg2_scene_h clipped, srrg2_clip_result* out) {
-  if (!full || !clipped || !robot_in_local_map || !p) return fail(SRRG2_E_INVALID, "scene_clip_spherical: null argument");
+// srrg2_scene_clip_spherical (ring_elevations == nullptr) and srrg2_scene_clip_spherical_rings; `who` opens every message
+static int clip_spherical(const std::string& who, srrg2_scene_h full, const float* robot_in_local_map,
+                          const srrg2_spherical_clip_params* p, const double* ring_elevations, srrg2_scene_h clipped,
+                          srrg2_clip_result* out) {
+  if (!full || !clipped || !robot_in_local_map || !p) return fail(SRRG2_E_INVALID, who + "null argument");
   if (!clip_pair(full, clipped))
-    return fail(SRRG2_E_INVALID, "scene_clip_spherical: full and clipped must be two scenes of one dim on one device");
-  if (full->dim != 3) return fail(SRRG2_E_UNSUPPORTED, "scene_clip_spherical: 2-D scenes (a laser scanner's view: srrg2_scene_clip_scan)");
-  if (const char* why = sph::invalid(p->model)) return fail(SRRG2_E_INVALID, std::string("scene_clip_spherical: ") + why);
-  if (std::isnan(p->occlusion_margin)) return fail(SRRG2_E_INVALID, "scene_clip_spherical: occlusion_margin is NaN");
-  if (p->reserved != 0) return fail(SRRG2_E_INVALID, "scene_clip_spherical: reserved must be 0");
+    return fail(SRRG2_E_INVALID, who + "full and clipped must be two scenes of one dim on one device");
+  if (full->dim != 3) return fail(SRRG2_E_UNSUPPORTED, who + "2-D scenes (a laser scanner's view: srrg2_scene_clip_scan)");
+  if (const char* why = sph::invalid(p->model, ring_elevations != nullptr)) return fail(SRRG2_E_INVALID, who + why);
+  if (std::isnan(p->occlusion_margin)) return fail(SRRG2_E_INVALID, who + "occlusion_margin is NaN");
+  if (p->reserved != 0) return fail(SRRG2_E_INVALID, who + "reserved must be 0");
+  sph::Rings table;
+  table.rows = table.descending = 0;
+  if (ring_elevations) {
+    bool unsupported;
+    if (const char* why = sph::rings_of(p->model, ring_elevations, table, &unsupported))
+      return fail(unsupported ? SRRG2_E_UNSUPPORTED : SRRG2_E_INVALID, who + why);
+  }
   int rc;
   if ((rc = clip_begin(full, clipped))) return rc;
   float Linv[12], Sinv[12];
@@ -1144,6 +1187,12 @@ int srrg2_scene_clip_spherical(srrg2_scene_h full, const float* robot_in_local_m
     const size_t npix = (size_t) geom.rows * (size_t) geom.cols;
     if ((rc = full->rmin.reserve(npix))) return rc;
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) full->rmin.p, 0x7f800000, npix, st));  // +inf
+    if (ring_elevations) {
+      if ((rc = full->sph_stage.reserve((size_t) n))) return rc;
+      hipLaunchKernelGGL(k_spclip_rings_rmin, grid, dim3(256), 0, st, L, S, geom, table, full->pts.p, n, full->rmin.p,
+                         full->sph_stage.p, counters);
+      hipLaunchKernelGGL(k_spclip_flag_staged, grid, dim3(256), 0, st, full->sph_stage.p, n, full->rmin.p, margin, full->flags.p);
+    } else {
 #ifndef SRRG2_SPCLIP_RECOMPUTE
     if ((rc = full->sph_stage.reserve((size_t) n))) return rc;
     hipLaunchKernelGGL(k_spclip_rmin, grid, dim3(256), 0, st, L, S, geom, full->pts.p, n, full->rmin.p, full->sph_stage.p, counters);
@@ -1153,6 +1202,9 @@ int srrg2_scene_clip_spherical(srrg2_scene_h full, const float* robot_in_local_m
     hipLaunchKernelGGL(k_spclip_flag<true>, grid, dim3(256), 0, st, L, S, geom, margin, full->pts.p, n, full->rmin.p, full->flags.p,
                        counters);
 #endif
+    }
+  } else if (ring_elevations) {
+    hipLaunchKernelGGL(k_spclip_rings_flag, grid, dim3(256), 0, st, L, S, geom, table, full->pts.p, n, full->flags.p, counters);
   } else {
     hipLaunchKernelGGL(k_spclip_flag<false>, grid, dim3(256), 0, st, L, S, geom, margin, full->pts.p, n, (const unsigned*) nullptr,
                        full->flags.p, counters);
@@ -1164,6 +1216,27 @@ int srrg2_scene_clip_spherical(srrg2_scene_h full, const float* robot_in_local_m
     out->num_kept    = full->scalars[CLIP_TOTAL];
   }
   return 0;
+}
+
+extern "C" {
+
+void srrg2_clip_default_spherical_params(srrg2_spherical_clip_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->model.range_min = 0.5f;
+  p->model.range_max = 120.f;
+  p->sensor_in_robot[0] = p->sensor_in_robot[5] = p->sensor_in_robot[10] = 1.f;
+  p->occlusion_margin = -1.f;
+}
+
+int srrg2_scene_clip_spherical(srrg2_scene_h full, const float* robot_in_local_map, const srrg2_spherical_clip_params* p,
+                               srrg2_scene_h clipped, srrg2_clip_result* out) {
+  return clip_spherical("scene_clip_spherical: ", full, robot_in_local_map, p, nullptr, clipped, out);
+}
+
+int srrg2_scene_clip_spherical_rings(srrg2_scene_h full, const float* robot_in_local_map, const srrg2_spherical_clip_params* p,
+                                     const double* ring_elevations, srrg2_scene_h clipped, srrg2_clip_result* out) {
+  return clip_spherical("scene_clip_spherical_rings: ", full, robot_in_local_map, p, ring_elevations, clipped, out);
 }
 
 int srrg2_scene_global_indices(srrg2_scene_h s, int32_t* buf, int* n_inout) {

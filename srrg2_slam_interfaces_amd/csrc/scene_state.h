@@ -32,6 +32,8 @@ struct srrg2_scene {
   srrg2amd::DevBuf<unsigned> rmin;  // clip_scan / clip_spherical with occlusion: per beam / pixel the bits of the smallest range seen
   // adapt_lidar_sweep: per pixel of the range image (range bits << 32 | input index) of the nearest point, all ones = empty
   srrg2amd::DevBuf<unsigned long long> winner;
+  // adapt_lidar_sweep_ex with de-skew: per input point its de-skewed coordinates (written for in-view points, read for winners)
+  srrg2amd::DevBuf<float4> deskewed;
   srrg2amd::DevBuf<uint2> sph_stage;  // clip_spherical with occlusion: per point (pixel or -1, range bits) from the minimum pass
   // estimate_normals (normals.hip): the arrays the call writes in place of the scene's own -- swapped in once it has succeeded,
   // so a refused call leaves the scene as it was -- and its scratch: cell keys and point indices (unsorted, sorted), the points

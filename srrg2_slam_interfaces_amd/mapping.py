@@ -438,6 +438,7 @@ class SceneClipperSpherical:
         self.params = params or default_spherical_clip_params()
         self._full = self._clipped = None
         self._robot_in_local_map = None
+        self._rings = None
         self._status = CLIPPER_ERROR
         self.last = None
 
@@ -457,13 +458,26 @@ class SceneClipperSpherical:
     def set_model(self, model):
         C.memmove(C.byref(self.params.model), C.byref(model), C.sizeof(SphericalModel))
 
+    def set_ring_elevations(self, elevations):
+        """one elevation (radians) per row of the model, strictly ascending or descending, for sensors whose rings are not
+        uniformly spaced (the model's elevation_min / elevation_increment are then ignored); None: the model's uniform rows.
+        A copy is kept; its length must be ``params.model.rows`` at compute()."""
+        self._rings = None if elevations is None else np.array(elevations, dtype=np.float64).reshape(-1)
+
     def compute(self, want_result=True):
         if self._full is None or self._clipped is None or self._robot_in_local_map is None:
             raise RuntimeError("SceneClipperSpherical::compute|scene, output or pose not set")
         out = ClipResult()
         self._status = CLIPPER_ERROR
-        self._b.check(self._b.fn("clip_spherical")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params),
-                                                   self._clipped._h, C.byref(out) if want_result else None))
+        if self._rings is None:
+            self._b.check(self._b.fn("clip_spherical")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params),
+                                                       self._clipped._h, C.byref(out) if want_result else None))
+        else:
+            if self._rings.shape[0] != self.params.model.rows:
+                raise ValueError("ring elevations: %d entries for %d rows" % (self._rings.shape[0], self.params.model.rows))
+            self._b.check(self._b.fn("clip_spherical_rings")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params),
+                                                             self._rings.ctypes.data_as(C.POINTER(C.c_double)), self._clipped._h,
+                                                             C.byref(out) if want_result else None))
         if want_result:
             self._status, self.last = out.status, out.as_dict()
         else:

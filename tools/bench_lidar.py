@@ -9,9 +9,13 @@
 and per map (points sampled on the room's surfaces and on the wall next door, 100 k and 1 M)
   clip_ms           clip_spherical, field of view only and with a 0.1 m occlusion margin, against clip_ball (range_max of the
                     model), each with the kept count and the set_moving + compute() that follows it.
-One JSON line on stdout.
+Every *_ms figure has a twin *_minmax: [min, max] over the same calls, the run-to-run spread of that figure.
+Unless --plain-only is given, each sweep also gets "real_sensor": a sweep of the same shape taken by a MOVING sensor whose rings
+follow a two-block table (tests/lidar_motion_cases.py: 64 rows = an HDL-64's two blocks of 32), adapted with the table alone,
+with table + de-skew from per-point times (separate arrays, and XYZIT records from the host) and with table + de-skew from the
+raw azimuth; and each map "spherical_rings_*": the clip through the 64-entry table.  One JSON line on stdout.
 
-    python tools/bench_lidar.py [--calls 20] [--maps 100000,1000000] [--tag NAME]
+    python tools/bench_lidar.py [--calls 20] [--maps 100000,1000000] [--tag NAME] [--plain-only]
 """
 import argparse
 import json
@@ -35,7 +39,7 @@ F = np.float32
 POSE = lc.pose(3.2, 2.9, 1.1, yaw_deg=20.0, pitch_deg=1.5)
 
 
-def median_ms(fn, calls, warmup=3):
+def times_ms(fn, calls, warmup=3):
     for _ in range(warmup):
         fn()
     t = []
@@ -43,7 +47,17 @@ def median_ms(fn, calls, warmup=3):
         t0 = time.perf_counter()
         fn()
         t.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(t))
+    return t
+
+
+def median_ms(fn, calls, warmup=3):
+    return float(np.median(times_ms(fn, calls, warmup)))
+
+
+def stats_ms(fn, calls, warmup=3):
+    """-> (median, [min, max]), rounded"""
+    t = times_ms(fn, calls, warmup)
+    return round(float(np.median(t)), 4), [round(float(min(t)), 4), round(float(max(t)), 4)]
 
 
 def radius_for(pts, k, seed=1):
@@ -85,7 +99,7 @@ def bench_adaptor(b, rows, cols, calls):
     dev = torch.from_numpy(pts).cuda()
     torch.cuda.synchronize()
     scene, plain = mapping.Scene(b, 3), mapping.Scene(b, 3)
-    row = {"rows": rows, "cols": cols, "returns": n, "adapt_ms": {}}
+    row = {"rows": rows, "cols": cols, "returns": n, "adapt_ms": {}, "adapt_minmax": {}}
     for compact in (0, 1):
         for where in ("host", "device"):
             ad = adaptors.MeasurementAdaptorLidarSweep()
@@ -93,7 +107,8 @@ def bench_adaptor(b, rows, cols, calls):
             ad.params.compact = compact
             ad.set_meas(scene)
             ad.set_raw_data(pts if where == "host" else (dev.data_ptr(), 12, n))
-            row["adapt_ms"]["%s_%s" % ("compact" if compact else "organised", where)] = round(median_ms(ad.compute, calls), 4)
+            key = "%s_%s" % ("compact" if compact else "organised", where)
+            row["adapt_ms"][key], row["adapt_minmax"][key] = stats_ms(ad.compute, calls)
             row["adapt_result"] = dict(ad.last)
     al = pkg.MultiAligner(abi.SE3_QUAT_RIGHT, device=0)
     c = abi.default_slice_config(abi.SE3_QUAT_RIGHT)
@@ -120,7 +135,54 @@ def bench_adaptor(b, rows, cols, calls):
     return row, scene, m
 
 
-def bench_clipper(b, meas, m, n_map, calls):
+def ring_table(rows):
+    import lidar_motion_cases as mc
+
+    return mc.hdl64_table() if rows == 64 else mc.blocks_table(rows, descending=True, first_deg=-20.0)
+
+
+def bench_real_sensor(b, rows, cols, calls):
+    """the same shapes for a moving sensor with a two-block ring table: table alone, table + de-skew (times / XYZIT / azimuth)"""
+    import lidar_motion_cases as mc
+
+    e = ring_table(rows)
+    sweep = mc.moving_sweep(rows, cols, mc.START, mc.motion(), seed=rows, ring_elevations=e)
+    pts, inten, tm, m = sweep["points"], sweep["intensity"], sweep["times"], sweep["model"]
+    n = len(pts)
+    xyzit = np.ascontiguousarray(np.concatenate([pts, inten[:, None], tm[:, None]], axis=1), F)
+    dev, dev_t = torch.from_numpy(pts).cuda(), torch.from_numpy(tm).cuda()
+    torch.cuda.synchronize()
+    scene = mapping.Scene(b, 3)
+    row = {"rows": rows, "cols": cols, "returns": n, "table": "%d entries, %.2f .. %.2f deg" % (rows, np.degrees(e[0]), np.degrees(e[-1])),
+           "adapt_ms": {}, "adapt_minmax": {}, "adapt_result": {}}
+    variants = (("rings", False, "times"), ("rings_deskew_times", True, "times"), ("rings_deskew_xyzit", True, "xyzit"),
+                ("rings_deskew_azimuth", True, None), ("deskew_times_uniform_rows", True, "uniform"))
+    for name, deskew, times in variants:
+        for compact in (0, 1):
+            for where in ("host", "device"):
+                if times == "xyzit" and where == "device":
+                    continue
+                ad = adaptors.MeasurementAdaptorLidarSweep()
+                set_model(ad.params.model, m)
+                ad.params.compact = compact
+                ad.set_meas(scene)
+                if times != "uniform":
+                    ad.set_ring_elevations(e)
+                if deskew:
+                    ad.set_motion(sweep["motion"], 1.0, 0.0, 1.0)
+                if times == "xyzit":
+                    ad.set_raw_data(xyzit)
+                elif where == "host":
+                    ad.set_raw_data(pts, None, tm if times else None)
+                else:
+                    ad.set_raw_data((dev.data_ptr(), 12, n), None, (dev_t.data_ptr(), 4) if times else None)
+                key = "%s_%s_%s" % (name, "compact" if compact else "organised", where)
+                row["adapt_ms"][key], row["adapt_minmax"][key] = stats_ms(ad.compute, calls)
+                row["adapt_result"][name] = dict(ad.last)
+    return row
+
+
+def bench_clipper(b, meas, m, n_map, calls, rings=None):
     pts, nrm = room_map(n_map, n_map)
     full, clipped = mapping.Scene(b, 3), mapping.Scene(b, 3)
     full.set(pts, nrm)
@@ -145,10 +207,17 @@ def bench_clipper(b, meas, m, n_map, calls):
         cl.params.occlusion_margin = margin
         clippers[name] = cl
     clippers["ball"] = mapping.SceneClipperBall(b, range_max=float(m.range_max))
+    if rings is not None:
+        for name, margin in (("spherical_rings_fov", -1.0), ("spherical_rings_margin_0.1", 0.1)):
+            cl = mapping.SceneClipperSpherical(b)
+            set_model(cl.params.model, m)
+            cl.set_ring_elevations(rings)
+            cl.params.occlusion_margin = margin
+            clippers[name] = cl
     for name, cl in clippers.items():
         cl.set_full_scene(full); cl.set_clipped_scene_in_robot(clipped); cl.set_robot_in_local_map(POSE)
-        ms = median_ms(cl.compute, calls)
-        row["clip_ms"][name] = {"clip_ms": round(ms, 4), "kept": clipped.size(), "set_moving_compute_ms": round(median_ms(align, max(3, calls // 4)), 4),
+        ms, spread = stats_ms(cl.compute, calls)
+        row["clip_ms"][name] = {"clip_ms": ms, "clip_minmax": spread, "kept": clipped.size(), "set_moving_compute_ms": round(median_ms(align, max(3, calls // 4)), 4),
                                 "correspondences": al.iteration_stats()[-1]["num_correspondences"]}
     return row
 
@@ -158,17 +227,20 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--maps", default="100000,1000000")
     ap.add_argument("--tag", default="")
+    ap.add_argument("--plain-only", action="store_true", help="only the calls an idealised sensor makes (no table, no de-skew)")
     args = ap.parse_args()
     b = pkg.scene_binding(0)
     out = {"bench": "lidar", "tag": args.tag, "calls": args.calls, "sweeps": [], "maps": []}
     meas = model = None
     for rows, cols in ((64, 2048), (32, 1024)):
         row, scene, m = bench_adaptor(b, rows, cols, args.calls)
+        if not args.plain_only:
+            row["real_sensor"] = bench_real_sensor(b, rows, cols, args.calls)
         out["sweeps"].append(row)
         if meas is None:
             meas, model = scene, m  # (the 64 x 2048 measurement, compact, from the last adapt)
     for n_map in [int(s) for s in args.maps.split(",") if s]:
-        out["maps"].append(bench_clipper(b, meas, model, n_map, args.calls))
+        out["maps"].append(bench_clipper(b, meas, model, n_map, args.calls, None if args.plain_only else ring_table(model.rows)))
     print(json.dumps(out))
 
 
