@@ -512,22 +512,17 @@ private:
   srrg2_scene_h _h = nullptr;
 };
 
+// ---- scene clippers: SceneClipper_ (S/mapping/scene_clipper.h:17-122) with the ball policy and the three sensor views ----------
+// what the four share: the full scene, the clipped scene, the pose, status() and globalIndices()
 template <int DIM>
-class SceneClipperBall {
+class SceneClipperBase_ {
 public:
   enum Status { Error = 0, Successful = 1, Ready = 2 };  // scene_clipper.h:24-28
   using EstimateType = Isometry<DIM>;
   using SceneType    = Scene<DIM>;
-  float param_range  = 10.f;
   void setFullScene(SceneType* s) { _full = s; }
   void setClippedSceneInRobot(SceneType* s) { _clipped = s; }
   void setRobotInLocalMap(const EstimateType& T) { _robot_in_local_map = T; }
-  void compute() {
-    if (!_full || !_clipped) throw std::runtime_error("SceneClipperBall::compute|scene not set");
-    int st = Error;
-    check(srrg2_scene_clip_ball(_full->handle(), _robot_in_local_map.data(), param_range, _clipped->handle(), &st));
-    _status = static_cast<Status>(st);
-  }
   Status status() const { return _status; }
   std::vector<int> globalIndices() const {  // :98-101
     int n = 0;
@@ -537,101 +532,79 @@ public:
     return v;
   }
 
-private:
+protected:
+  void ready(const char* who) const {
+    if (!_full || !_clipped) throw std::runtime_error(std::string(who) + "::compute|scene not set");
+  }
   SceneType* _full    = nullptr;
   SceneType* _clipped = nullptr;
   EstimateType _robot_in_local_map = EstimateType::Identity();
   Status _status = Error;
+};
+
+template <int DIM>
+class SceneClipperBall : public SceneClipperBase_<DIM> {
+public:
+  using Status      = typename SceneClipperBase_<DIM>::Status;
+  float param_range = 10.f;
+  void compute() {
+    this->ready("SceneClipperBall");
+    int st = Status::Error;
+    check(srrg2_scene_clip_ball(this->_full->handle(), this->_robot_in_local_map.data(), param_range, this->_clipped->handle(), &st));
+    this->_status = static_cast<Status>(st);
+  }
+};
+
+// the clippers with a sensor: `param` (the PARAMs, sensor_in_robot among them), last() -- the counts of the last compute() --
+// and the frame of compute(): clip(who, call), where call(full, robot_in_local_map, clipped, &result) makes the C call
+template <int DIM, typename Params>
+class SceneViewClipperBase_ : public SceneClipperBase_<DIM> {
+public:
+  Params param;
+  void setSensorInRobot(const Isometry<DIM>& T) { std::memcpy(param.sensor_in_robot, T.data(), sizeof(param.sensor_in_robot)); }  // :86-89
+  const srrg2_clip_result& last() const { return _last; }
+
+protected:
+  template <typename Call>
+  void clip(const char* who, Call call) {
+    this->ready(who);
+    this->_status = SceneClipperBase_<DIM>::Error;
+    check(call(this->_full->handle(), this->_robot_in_local_map.data(), this->_clipped->handle(), &_last));
+    this->_status = static_cast<typename SceneClipperBase_<DIM>::Status>(_last.status);
+  }
+  srrg2_clip_result _last{};
 };
 
 // the points of a 3-D scene that a pinhole camera at sensor_in_robot sees (srrg2_scene_clip_projective): param.camera_matrix,
-// image_rows / image_cols, depth range and occlusion_margin are the PARAMs; last() holds the counts of the last compute()
-class SceneClipperProjective {
+// image_rows / image_cols, depth range and occlusion_margin are the PARAMs
+class SceneClipperProjective : public SceneViewClipperBase_<3, srrg2_projective_clip_params> {
 public:
-  enum Status { Error = 0, Successful = 1, Ready = 2 };  // scene_clipper.h:24-28
-  using EstimateType = Isometry<3>;
-  using SceneType    = Scene<3>;
-  srrg2_projective_clip_params param;
   SceneClipperProjective() { srrg2_clip_default_projective_params(&param); }
-  void setFullScene(SceneType* s) { _full = s; }
-  void setClippedSceneInRobot(SceneType* s) { _clipped = s; }
-  void setRobotInLocalMap(const EstimateType& T) { _robot_in_local_map = T; }
-  void setSensorInRobot(const EstimateType& T) { std::memcpy(param.sensor_in_robot, T.data(), sizeof(param.sensor_in_robot)); }  // :86-89
   void setCameraMatrix(const float* K_row_major) { std::memcpy(param.camera_matrix, K_row_major, sizeof(param.camera_matrix)); }
   void compute() {
-    if (!_full || !_clipped) throw std::runtime_error("SceneClipperProjective::compute|scene not set");
-    _status = Error;
-    check(srrg2_scene_clip_projective(_full->handle(), _robot_in_local_map.data(), &param, _clipped->handle(), &_last));
-    _status = static_cast<Status>(_last.status);
+    clip("SceneClipperProjective", [this](srrg2_scene_h full, const float* T, srrg2_scene_h clipped, srrg2_clip_result* out) {
+      return srrg2_scene_clip_projective(full, T, &param, clipped, out);
+    });
   }
-  Status status() const { return _status; }
-  const srrg2_clip_result& last() const { return _last; }
-  std::vector<int> globalIndices() const {  // :98-101
-    int n = 0;
-    check(srrg2_scene_global_indices(_clipped->handle(), nullptr, &n));
-    std::vector<int> v((size_t) n);
-    if (n) check(srrg2_scene_global_indices(_clipped->handle(), v.data(), &n));
-    return v;
-  }
-
-private:
-  SceneType* _full    = nullptr;
-  SceneType* _clipped = nullptr;
-  EstimateType _robot_in_local_map = EstimateType::Identity();
-  srrg2_clip_result _last{};
-  Status _status = Error;
 };
 
 // the points of a 2-D scene that a planar laser scanner at sensor_in_robot sees (srrg2_scene_clip_scan): param.angle_min,
-// angle_increment, num_beams, range interval and occlusion_margin are the PARAMs; last() holds the counts of the last compute()
-class SceneClipperScan {
+// angle_increment, num_beams, range interval and occlusion_margin are the PARAMs
+class SceneClipperScan : public SceneViewClipperBase_<2, srrg2_scan_clip_params> {
 public:
-  enum Status { Error = 0, Successful = 1, Ready = 2 };  // scene_clipper.h:24-28
-  using EstimateType = Isometry<2>;
-  using SceneType    = Scene<2>;
-  srrg2_scan_clip_params param;
   SceneClipperScan() { srrg2_clip_default_scan_params(&param); }
-  void setFullScene(SceneType* s) { _full = s; }
-  void setClippedSceneInRobot(SceneType* s) { _clipped = s; }
-  void setRobotInLocalMap(const EstimateType& T) { _robot_in_local_map = T; }
-  void setSensorInRobot(const EstimateType& T) { std::memcpy(param.sensor_in_robot, T.data(), sizeof(param.sensor_in_robot)); }  // :86-89
   void compute() {
-    if (!_full || !_clipped) throw std::runtime_error("SceneClipperScan::compute|scene not set");
-    _status = Error;
-    check(srrg2_scene_clip_scan(_full->handle(), _robot_in_local_map.data(), &param, _clipped->handle(), &_last));
-    _status = static_cast<Status>(_last.status);
+    clip("SceneClipperScan", [this](srrg2_scene_h full, const float* T, srrg2_scene_h clipped, srrg2_clip_result* out) {
+      return srrg2_scene_clip_scan(full, T, &param, clipped, out);
+    });
   }
-  Status status() const { return _status; }
-  const srrg2_clip_result& last() const { return _last; }
-  std::vector<int> globalIndices() const {  // :98-101
-    int n = 0;
-    check(srrg2_scene_global_indices(_clipped->handle(), nullptr, &n));
-    std::vector<int> v((size_t) n);
-    if (n) check(srrg2_scene_global_indices(_clipped->handle(), v.data(), &n));
-    return v;
-  }
-
-private:
-  SceneType* _full    = nullptr;
-  SceneType* _clipped = nullptr;
-  EstimateType _robot_in_local_map = EstimateType::Identity();
-  srrg2_clip_result _last{};
-  Status _status = Error;
 };
 
 // the points of a 3-D scene that a spinning lidar at sensor_in_robot sees (srrg2_scene_clip_spherical): param.model (e.g. from
-// srrg2_spherical_model_full_turn) and occlusion_margin are the PARAMs; last() holds the counts of the last compute()
-class SceneClipperSpherical {
+// srrg2_spherical_model_full_turn) and occlusion_margin are the PARAMs
+class SceneClipperSpherical : public SceneViewClipperBase_<3, srrg2_spherical_clip_params> {
 public:
-  enum Status { Error = 0, Successful = 1, Ready = 2 };  // scene_clipper.h:24-28
-  using EstimateType = Isometry<3>;
-  using SceneType    = Scene<3>;
-  srrg2_spherical_clip_params param;
   SceneClipperSpherical() { srrg2_clip_default_spherical_params(&param); }
-  void setFullScene(SceneType* s) { _full = s; }
-  void setClippedSceneInRobot(SceneType* s) { _clipped = s; }
-  void setRobotInLocalMap(const EstimateType& T) { _robot_in_local_map = T; }
-  void setSensorInRobot(const EstimateType& T) { std::memcpy(param.sensor_in_robot, T.data(), sizeof(param.sensor_in_robot)); }  // :86-89
   void setModel(const srrg2_spherical_model& m) { param.model = m; }
   // one elevation (radians) per row of param.model, strictly ascending or descending, for sensors whose rings are not uniformly
   // spaced (srrg2_scene_clip_spherical_rings; the model's elevation_min / elevation_increment are then ignored); a copy is kept.
@@ -641,31 +614,16 @@ public:
   }
   const std::vector<double>& ringElevations() const { return _rings; }
   void compute() {
-    if (!_full || !_clipped) throw std::runtime_error("SceneClipperSpherical::compute|scene not set");
+    ready("SceneClipperSpherical");
     if (!_rings.empty() && (int) _rings.size() != param.model.rows)
       throw std::runtime_error("SceneClipperSpherical::compute|one ring elevation per row of the model expected");
-    _status = Error;
-    check(srrg2_scene_clip_spherical_rings(_full->handle(), _robot_in_local_map.data(), &param,
-                                           _rings.empty() ? nullptr : _rings.data(), _clipped->handle(), &_last));
-    _status = static_cast<Status>(_last.status);
-  }
-  Status status() const { return _status; }
-  const srrg2_clip_result& last() const { return _last; }
-  std::vector<int> globalIndices() const {  // :98-101
-    int n = 0;
-    check(srrg2_scene_global_indices(_clipped->handle(), nullptr, &n));
-    std::vector<int> v((size_t) n);
-    if (n) check(srrg2_scene_global_indices(_clipped->handle(), v.data(), &n));
-    return v;
+    clip("SceneClipperSpherical", [this](srrg2_scene_h full, const float* T, srrg2_scene_h clipped, srrg2_clip_result* out) {
+      return srrg2_scene_clip_spherical_rings(full, T, &param, _rings.empty() ? nullptr : _rings.data(), clipped, out);
+    });
   }
 
 private:
-  SceneType* _full    = nullptr;
-  SceneType* _clipped = nullptr;
-  EstimateType _robot_in_local_map = EstimateType::Identity();
   std::vector<double> _rings;
-  srrg2_clip_result _last{};
-  Status _status = Error;
 };
 
 template <int DIM>

@@ -10,6 +10,7 @@
 // Kernels: one thread per pixel / beam, grid-stride.  A thread reads its own raw value and its four (two) neighbours' and
 // RECOMPUTES the neighbours' points from them -- the same expression gives the same bits as the neighbour's own thread, so
 // there is no second pass and no dependency between threads -- and writes point and normal as 16-byte records, coalesced.
+// The two image sources (depth image, lidar range image) take the normal from ONE image_normal over the four neighbours' points.
 // Organised output is one kernel; compact output is flag -> exclusive scan -> scatter like the ball clipper, the points
 // recomputed in the scatter rather than staged.  The counters of srrg2_adapt_result are summed per workgroup and added with
 // ONE 64-bit atomic per workgroup (both counts in one word), and read back only when the caller asks for them.
@@ -36,6 +37,30 @@ enum { PX_IN_RANGE = 1, PX_VALID = 2 };
 __device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
 
 __device__ __forceinline__ float sq3(float x, float y, float z) { return (x * x + y * y) + z * z; }
+
+// the normal of the image pixel whose point is q, from its right / left / lower / upper neighbours' points: the cross product of
+// the two central differences (neither longer than sqrt(maxd2)), normalised, facing the sensor.  false: the pixel has none
+__device__ __forceinline__ bool image_normal(const float3 q, const float3 pr, const float3 pl, const float3 pd, const float3 pu,
+                                             float maxd2, float4& n) {
+  const float dcx = pr.x - pl.x, dcy = pr.y - pl.y, dcz = pr.z - pl.z;
+  const float drx = pd.x - pu.x, dry = pd.y - pu.y, drz = pd.z - pu.z;
+  if (sq3(dcx, dcy, dcz) > maxd2 || sq3(drx, dry, drz) > maxd2) return false;
+  float nx = dcy * drz - dcz * dry;
+  float ny = dcz * drx - dcx * drz;
+  float nz = dcx * dry - dcy * drx;
+  const float len = sqrtf(sq3(nx, ny, nz));
+  if (!(len > 0.f)) return false;
+  nx = nx / len;
+  ny = ny / len;
+  nz = nz / len;
+  if ((nx * q.x + ny * q.y) + nz * q.z > 0.f) {  // normals face the sensor
+    nx = -nx;
+    ny = -ny;
+    nz = -nz;
+  }
+  n = make_float4(nx, ny, nz, 0.f);
+  return true;
+}
 
 // ---- depth image -----------------------------------------------------------------------------------------------------
 struct DepthArgs {
@@ -80,30 +105,9 @@ struct DepthSource {
       float zl, zr, zu, zd;
       const bool okl = depth_at(r, c - a.gc, zl), okr = depth_at(r, c + a.gc, zr);
       const bool oku = depth_at(r - a.gr, c, zu), okd = depth_at(r + a.gr, c, zd);
-      if (okl && okr && oku && okd) {
-        const float3 pr = point_at(r, c + a.gc, zr), pl = point_at(r, c - a.gc, zl);
-        const float3 pd = point_at(r + a.gr, c, zd), pu = point_at(r - a.gr, c, zu);
-        const float dcx = pr.x - pl.x, dcy = pr.y - pl.y, dcz = pr.z - pl.z;
-        const float drx = pd.x - pu.x, dry = pd.y - pu.y, drz = pd.z - pu.z;
-        if (!(sq3(dcx, dcy, dcz) > a.maxd2) && !(sq3(drx, dry, drz) > a.maxd2)) {
-          float nx = dcy * drz - dcz * dry;
-          float ny = dcz * drx - dcx * drz;
-          float nz = dcx * dry - dcy * drx;
-          const float len = sqrtf(sq3(nx, ny, nz));
-          if (len > 0.f) {
-            nx = nx / len;
-            ny = ny / len;
-            nz = nz / len;
-            if ((nx * q.x + ny * q.y) + nz * q.z > 0.f) {  // normals face the sensor
-              nx = -nx;
-              ny = -ny;
-              nz = -nz;
-            }
-            n          = make_float4(nx, ny, nz, 0.f);
-            has_normal = true;
-          }
-        }
-      }
+      if (okl && okr && oku && okd)
+        has_normal = image_normal(q, point_at(r, c + a.gc, zr), point_at(r, c - a.gc, zl), point_at(r + a.gr, c, zd),
+                                  point_at(r - a.gr, c, zu), a.maxd2, n);
     }
     const bool valid = a.gc == 0 || has_normal || !a.drop;
     if (valid) p = make_float4(q.x, q.y, q.z, 0.f);
@@ -176,6 +180,8 @@ struct ScanSource {
 // patterns, so the nearest point wins and, of equal ranges, the lowest index, whoever comes first.  ONE 64-bit atomicMin without
 // return value per in-view point, straight into global memory: the table of a 64 x 2048 sensor is 1 MB, far beyond a
 // workgroup's LDS, and a sweep puts about one point on each word, so there is nothing for a private table to combine.
+// (It is k_lidar_bin_ex<false, false> written out: launched through that template, with the 2.3 KB of table and de-skew block
+// it never reads in its kernel arguments, the plain adapt measured 1-2 us slower -- profiles/view_clip_refactor_ab.txt.)
 __global__ __launch_bounds__(256) void k_lidar_bin(const unsigned char* __restrict__ pts, long long stride, int n, sph::Geom G,
                                                    unsigned long long* __restrict__ winner) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -288,30 +294,7 @@ struct LidarSource {
       unsigned il, ir, iu, id;
       const bool okl = winner_at(r, cl, il), okr = winner_at(r, cr, ir);
       const bool oku = winner_at(r - gr, c, iu), okd = winner_at(r + gr, c, id);
-      if (okl && okr && oku && okd) {
-        const float3 pr = point_of(ir), pl = point_of(il);
-        const float3 pd = point_of(id), pu = point_of(iu);
-        const float dcx = pr.x - pl.x, dcy = pr.y - pl.y, dcz = pr.z - pl.z;
-        const float drx = pd.x - pu.x, dry = pd.y - pu.y, drz = pd.z - pu.z;
-        if (!(sq3(dcx, dcy, dcz) > maxd2) && !(sq3(drx, dry, drz) > maxd2)) {
-          float nx = dcy * drz - dcz * dry;
-          float ny = dcz * drx - dcx * drz;
-          float nz = dcx * dry - dcy * drx;
-          const float len = sqrtf(sq3(nx, ny, nz));
-          if (len > 0.f) {
-            nx = nx / len;
-            ny = ny / len;
-            nz = nz / len;
-            if ((nx * q.x + ny * q.y) + nz * q.z > 0.f) {  // normals face the sensor
-              nx = -nx;
-              ny = -ny;
-              nz = -nz;
-            }
-            n          = make_float4(nx, ny, nz, 0.f);
-            has_normal = true;
-          }
-        }
-      }
+      if (okl && okr && oku && okd) has_normal = image_normal(q, point_of(ir), point_of(il), point_of(id), point_of(iu), maxd2, n);
     }
     const bool valid = gc == 0 || has_normal || !drop;
     if (valid) p = make_float4(q.x, q.y, q.z, 0.f);
@@ -612,12 +595,8 @@ int adapt_lidar_sweep(const std::string& who, srrg2_scene_h dst, const float* po
   } else {
     if (deskew) deskew_of(*x, K);
     float4* const dsk = deskew ? dst->deskewed.p : nullptr;
-    if (rings && deskew)
-      hipLaunchKernelGGL((k_lidar_bin_ex<true, true>), grid, block, 0, st, src.pts, src.pts_stride, n, geom, table, K, dst->winner.p, dsk);
-    else if (rings)
-      hipLaunchKernelGGL((k_lidar_bin_ex<true, false>), grid, block, 0, st, src.pts, src.pts_stride, n, geom, table, K, dst->winner.p, dsk);
-    else
-      hipLaunchKernelGGL((k_lidar_bin_ex<false, true>), grid, block, 0, st, src.pts, src.pts_stride, n, geom, table, K, dst->winner.p, dsk);
+    const auto bin    = rings ? (deskew ? k_lidar_bin_ex<true, true> : k_lidar_bin_ex<true, false>) : k_lidar_bin_ex<false, true>;
+    hipLaunchKernelGGL(bin, grid, block, 0, st, src.pts, src.pts_stride, n, geom, table, K, dst->winner.p, dsk);
     if (deskew) {  // the image reads the de-skewed points from here on
       src.pts        = reinterpret_cast<const unsigned char*>(dsk);
       src.pts_stride = 16;

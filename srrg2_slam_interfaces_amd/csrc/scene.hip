@@ -10,7 +10,8 @@
 // the kernels that move points (k_scatter_kept, merge_one, k_append_scatter) have a feature-carrying instantiation, chosen on the
 // host, so a scene without features runs the code it ran before they existed.  All kernels are one thread per
 // point or correspondence, coalesced, HBM bound: clip = 2 passes over the scene (flag+count, scatter) around an
-// exclusive scan (the projective and the scan clip with occlusion: one more in front, the per-pixel depth / per-beam range minimum); merge = one pass over the correspondences + (if the merge target was not reached) flag/scan/scatter
+// exclusive scan (the view clips -- camera, scanner, lidar: ONE set of kernels over a View per sensor -- with occlusion: one more
+// in front, the per-bin depth / range minimum); merge = one pass over the correspondences + (if the merge target was not reached) flag/scan/scatter
 // of the measurement.  The reference merges sequentially; results are identical because
 //   - a scene point hit by ONE correspondence is independent of all others (the common case: the tracker's
 //     correspondences come through an injective local->global map),
@@ -143,13 +144,27 @@ __device__ __forceinline__ void block_add(int v, int* target) {
   }
 }
 
-// ---- projective clip (no reference counterpart: SceneClipper_ is an interface; DESIGN.md section 4 "Projective clipping") -------
-// keeps the Valid points a pinhole camera at sensor_in_robot sees: inside the depth range and the image, and -- margin >= 0 --
-// no further than `margin` behind the nearest point of their pixel.
-//   k_pclip_zmin     per pixel the minimum camera depth of the in-view points: positive floats order like their bit patterns,
-//                    so ONE 32-bit atomicMin per in-view point (no return value, order-free: deterministic)
-//   k_pclip_flag     keep flag per point + the Valid / in-view counts (one atomic per block and count)
-// and k_scatter_kept moves what the scan kept: the same L and xform_point as for the ball clip, so the same bits
+// ---- view clips (no reference counterpart: SceneClipper_ is an interface; DESIGN.md section 4 "Projective clipping", "Scan
+// clipping", "Lidar sweeps") --------------------------------------------------------------------------------------------------
+// keep the Valid points a sensor at sensor_in_robot sees: inside its depth / range interval and its image or sector, and --
+// margin >= 0 -- no further than `margin` behind the nearest point of their bin (a camera's or a lidar's pixel, a scanner's beam).
+// A sensor is a View: L, S, the geometry and the margin, by value as the first kernel argument, and ONE device function,
+// project(): point -> bin, or -1 when not in view, plus `valid` and the depth / range (written when it was computed).  RING_WORDS
+// doubles of LDS are the view's to fill once per workgroup (stage()) and to read in project().  The kernels over a view:
+//   k_view_min         per bin the minimum depth / range of the in-view points: positive floats order like their bit patterns,
+//                      so ONE 32-bit atomicMin per in-view point (no return value, order-free: deterministic)
+//   k_view_min_lds     the same through a workgroup's private LDS table (the scan clip, below)
+//   k_view_flag        keep flag per point + the Valid / in-view counts (one atomic per block and count)
+//   k_view_min_staged  k_view_min that also counts and leaves (bin, depth bits) per point for k_spclip_flag_staged (the lidar, below)
+// and k_scatter_kept moves what the scan kept: the same L and xform_point as for the ball clip, so the same bits; it reads the
+// scan's neighbouring offsets and never projects
+struct ViewBase {  // what every view has; no ring table
+  Xf L, S;
+  static constexpr int RING_WORDS = 1;
+  __device__ __forceinline__ void stage(double*) const {}
+};
+
+// -- pinhole camera
 struct ProjCam {
   float K0, K2, K4, K5, depth_min, depth_max, margin;
   int rows, cols;
@@ -170,47 +185,20 @@ __device__ __forceinline__ int pclip_project(const Xf& L, const Xf& S, const Pro
   return (int) floorf(vf) * C.cols + (int) floorf(uf);
 }
 
-__global__ void k_pclip_zmin(Xf L, Xf S, ProjCam C, const float4* __restrict__ pts, int n, unsigned* __restrict__ zmin) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    bool valid;
-    float cz;
-    const int pix = pclip_project(L, S, C, pts[i], valid, cz);
-    if (pix >= 0) atomicMin(&zmin[pix], __float_as_uint(cz));  // (pix < rows * cols: project_point's bounds)
+struct PinholeView : ViewBase {
+  ProjCam C;
+  __device__ __forceinline__ float margin() const { return C.margin; }
+  __device__ __forceinline__ int project(const double*, const float4 p, bool& valid, float& cz) const {
+    return pclip_project(L, S, C, p, valid, cz);
   }
-}
+};
 
-// counters: [CLIP_VALID], [CLIP_IN_VIEW]
-template <bool OCCLUSION>
-__global__ void k_pclip_flag(Xf L, Xf S, ProjCam C, const float4* __restrict__ pts, int n, const unsigned* __restrict__ zmin,
-                             int* __restrict__ flags, int* __restrict__ counters) {
-  int nvalid = 0, nview = 0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    bool valid;
-    float cz;
-    const int pix = pclip_project(L, S, C, pts[i], valid, cz);
-    bool keep     = pix >= 0;
-    nvalid += valid ? 1 : 0;
-    nview += keep ? 1 : 0;
-    if (OCCLUSION && keep) keep = cz <= __uint_as_float(zmin[pix]) + C.margin;
-    flags[i] = keep ? 1 : 0;
-  }
-  block_add(nvalid, &counters[CLIP_VALID]);
-  block_add(nview, &counters[CLIP_IN_VIEW]);
-}
-
-// ---- scan clip (no reference counterpart; DESIGN.md section 4 "Scan clipping") -------------------------------------------------
-// the 2-D twin of the projective clip: keeps the Valid points a planar laser scanner at sensor_in_robot sees -- inside the range
-// interval and the angular sector of its beams, and -- margin >= 0 -- no further than `margin` behind the nearest point of
-// their beam.
-//   k_sclip_rmin_lds  per beam the minimum range of the in-view points.  A scan has ~10^3 beams, a map 10^5..10^6 points: hundreds
-//                     of points per word, and same-address global atomics serialise (block_add above).  So every workgroup takes
-//                     the minimum in a private LDS table of num_beams words first (ds atomics, no return value) and sends ONE
-//                     global atomicMin per bin it touched.  Positive floats order like their bit patterns (range_min > 0).
-//   k_sclip_rmin      the same straight into global memory: tables beyond SRRG2_SCLIP_LDS_BINS, maps too small to give
-//                     SRRG2_SCLIP_LDS_MIN_WORKGROUPS workgroups their share, and the A/B build -DSRRG2_SCLIP_NO_LDS.
-//                     A minimum does not depend on who took it: both give the same bits.
-//   k_sclip_flag      keep flag per point + the Valid / in-view counts (one atomic per block and count)
-// and k_scatter_kept moves what the scan kept: it reads the scan's neighbouring offsets and never computes a bearing
+// -- planar laser scanner (2-D): the bins are the beams of its angular sector.
+// A scan has ~10^3 beams, a map 10^5..10^6 points: hundreds of points per word, and same-address global atomics serialise
+// (block_add above).  So with occlusion every workgroup takes the minimum in a private LDS table of num_beams words first
+// (k_view_min_lds: ds atomics, no return value) and sends ONE global atomicMin per bin it touched.  k_view_min, straight into
+// global memory, remains for tables beyond SRRG2_SCLIP_LDS_BINS and maps too small to give SRRG2_SCLIP_LDS_MIN_WORKGROUPS
+// workgroups their share.  A minimum does not depend on who took it: both give the same bits.
 struct ScanGeom {
   double angle_min, angle_increment, wrap;  // wrap = copysign(2 pi, angle_increment)
   float range_min, range_max, margin;
@@ -253,65 +241,19 @@ __device__ __forceinline__ int sclip_beam(const Xf& L, const Xf& S, const ScanGe
   return (int) floor(tf);  // in [0, num_beams)
 }
 
-__global__ void k_sclip_rmin(Xf L, Xf S, ScanGeom G, const float4* __restrict__ pts, int n, unsigned* __restrict__ rmin) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    bool valid;
-    float rho;
-    const int beam = sclip_beam(L, S, G, pts[i], valid, rho);
-    if (beam >= 0) atomicMin(&rmin[beam], __float_as_uint(rho));
+struct BeamView : ViewBase {
+  ScanGeom G;
+  __device__ __forceinline__ float margin() const { return G.margin; }
+  __device__ __forceinline__ int project(const double*, const float4 p, bool& valid, float& rho) const {
+    return sclip_beam(L, S, G, p, valid, rho);
   }
-}
+};
 
-// dynamic LDS: num_beams words (the host launches it only with num_beams <= SRRG2_SCLIP_LDS_BINS)
-__global__ void k_sclip_rmin_lds(Xf L, Xf S, ScanGeom G, const float4* __restrict__ pts, int n, unsigned* __restrict__ rmin) {
-  extern __shared__ unsigned table[];
-  const unsigned INF = 0x7f800000u;
-  for (int b = threadIdx.x; b < G.num_beams; b += blockDim.x) table[b] = INF;
-  __syncthreads();
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    bool valid;
-    float rho;
-    const int beam = sclip_beam(L, S, G, pts[i], valid, rho);
-    if (beam >= 0) atomicMin(&table[beam], __float_as_uint(rho));
-  }
-  __syncthreads();
-  for (int b = threadIdx.x; b < G.num_beams; b += blockDim.x) {
-    const unsigned v = table[b];
-    if (v != INF) atomicMin(&rmin[b], v);
-  }
-}
-
-// counters: [CLIP_VALID], [CLIP_IN_VIEW]
-template <bool OCCLUSION>
-__global__ void k_sclip_flag(Xf L, Xf S, ScanGeom G, const float4* __restrict__ pts, int n, const unsigned* __restrict__ rmin,
-                             int* __restrict__ flags, int* __restrict__ counters) {
-  int nvalid = 0, nview = 0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    bool valid;
-    float rho;
-    const int beam = sclip_beam(L, S, G, pts[i], valid, rho);
-    bool keep      = beam >= 0;
-    nvalid += valid ? 1 : 0;
-    nview += keep ? 1 : 0;
-    if (OCCLUSION && keep) keep = rho <= __uint_as_float(rmin[beam]) + G.margin;
-    flags[i] = keep ? 1 : 0;
-  }
-  block_add(nvalid, &counters[CLIP_VALID]);
-  block_add(nview, &counters[CLIP_IN_VIEW]);
-}
-
-// ---- spherical clip (no reference counterpart; DESIGN.md section 4 "Lidar sweeps") ----------------------------------------------
-// the 3-D twin of the scan clip: keeps the Valid points a spinning lidar at sensor_in_robot sees -- inside the range interval
-// and the rows x cols range image of its spherical model (spherical.h, shared with the sweep adaptor), and -- margin >= 0 -- no
-// further than `margin` behind the nearest point of their pixel.
-//   k_spclip_rmin    per pixel the minimum range of the in-view points, ONE 32-bit atomicMin per point straight into global
-//                    memory: the image of a 64 x 2048 sensor has 131072 words, sixteen times SRRG2_SCLIP_LDS_BINS, and a map
-//                    puts a handful of points on each, so there is no LDS path.  It also counts, and leaves (pixel, range bits)
-//                    per point for the flag pass -- the projection is two float64 atan2, a square root and four divisions, more
-//                    than the 16 bytes per point of writing it down and reading it back (DESIGN.md has both timings;
-//                    -DSRRG2_SPCLIP_RECOMPUTE builds the variant whose flag pass projects again).
-//   k_spclip_flag    keep flag per point; without occlusion it projects and counts itself
-// and k_scatter_kept moves what the scan kept.
+// -- spinning lidar (3-D): the bins are the pixels of the rows x cols range image of its spherical model (spherical.h, shared
+// with the sweep adaptor).  The image of a 64 x 2048 sensor has 131072 words, sixteen times SRRG2_SCLIP_LDS_BINS, and a map puts
+// a handful of points on each, so there is no LDS table.  With occlusion the minimum pass is k_view_min_staged and the flag pass
+// reads what it left -- the projection is two float64 atan2, a square root and four divisions, more than the 16 bytes per point
+// of writing it down and reading it back (docs/HISTORY.md has both timings).  Without, k_view_flag projects and counts itself.
 // RINGS: the rows of a ring table (B: the boundaries in LDS, sph::stage_rings) instead of the model's uniform rows
 template <bool RINGS>
 __device__ __forceinline__ int spclip_project(const Xf& L, const Xf& S, const sph::Geom& G, const double* B, int descending,
@@ -324,26 +266,103 @@ __device__ __forceinline__ int spclip_project(const Xf& L, const Xf& S, const sp
   return sph::project_t<RINGS>(G, B, descending, c.x, c.y, c.z, rho, tf);
 }
 
-// counters: [CLIP_VALID], [CLIP_IN_VIEW]
-__global__ void k_spclip_rmin(Xf L, Xf S, sph::Geom G, const float4* __restrict__ pts, int n, unsigned* __restrict__ rmin,
-                              uint2* __restrict__ stage, int* __restrict__ counters) {
-  int nvalid = 0, nview = 0;
+struct LidarView : ViewBase {  // the model's uniform rows: no 2 KB table in the kernel arguments
+  sph::Geom G;
+  float occlusion_margin;
+  __device__ __forceinline__ float margin() const { return occlusion_margin; }
+  __device__ __forceinline__ int project(const double*, const float4 p, bool& valid, float& rho) const {
+    return spclip_project<false>(L, S, G, nullptr, 0, p, valid, rho);
+  }
+};
+
+// a sensor with a ring table (srrg2_scene_clip_spherical_rings): the boundaries travel by value and are staged into LDS once per
+// workgroup
+struct RingLidarView : LidarView {
+  sph::Rings T;
+  static constexpr int RING_WORDS = sph::MAX_RING_ROWS + 1;
+  __device__ __forceinline__ void stage(double* B) const { sph::stage_rings(T, B); }
+  __device__ __forceinline__ int project(const double* B, const float4 p, bool& valid, float& rho) const {
+    return spclip_project<true>(L, S, G, B, T.descending, p, valid, rho);
+  }
+};
+
+// -- the kernels over a view (a view without a ring table leaves `rings` unused: the compiler drops it)
+template <typename V>
+__global__ void k_view_min(V v, const float4* __restrict__ pts, int n, unsigned* __restrict__ dmin) {
+  __shared__ double rings[V::RING_WORDS];
+  v.stage(rings);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     bool valid;
-    float rho     = 0.f;
-    const int pix = spclip_project<false>(L, S, G, nullptr, 0, pts[i], valid, rho);
-    nvalid += valid ? 1 : 0;
-    nview += pix >= 0 ? 1 : 0;
-    if (pix >= 0) atomicMin(&rmin[pix], __float_as_uint(rho));  // (pix < rows * cols: project's bounds)
-    if (stage) stage[i] = make_uint2((unsigned) pix, __float_as_uint(rho));
-  }
-  if (stage) {
-    block_add(nvalid, &counters[CLIP_VALID]);
-    block_add(nview, &counters[CLIP_IN_VIEW]);
+    float d;
+    const int bin = v.project(rings, pts[i], valid, d);
+    if (bin >= 0) atomicMin(&dmin[bin], __float_as_uint(d));  // (bin < the table's size: project's bounds)
   }
 }
 
-// the flag pass behind k_spclip_rmin: reads what that pass left per point
+// dynamic LDS: `bins` words (the host launches it only with bins <= SRRG2_SCLIP_LDS_BINS)
+template <typename V>
+__global__ void k_view_min_lds(V v, int bins, const float4* __restrict__ pts, int n, unsigned* __restrict__ dmin) {
+  extern __shared__ unsigned table[];
+  __shared__ double rings[V::RING_WORDS];
+  v.stage(rings);
+  const unsigned INF = 0x7f800000u;
+  for (int b = threadIdx.x; b < bins; b += blockDim.x) table[b] = INF;
+  __syncthreads();
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    bool valid;
+    float d;
+    const int bin = v.project(rings, pts[i], valid, d);
+    if (bin >= 0) atomicMin(&table[bin], __float_as_uint(d));
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < bins; b += blockDim.x) {
+    const unsigned m = table[b];
+    if (m != INF) atomicMin(&dmin[b], m);
+  }
+}
+
+// counters: [CLIP_VALID], [CLIP_IN_VIEW]
+template <typename V, bool OCCLUSION>
+__global__ void k_view_flag(V v, const float4* __restrict__ pts, int n, const unsigned* __restrict__ dmin, int* __restrict__ flags,
+                            int* __restrict__ counters) {
+  __shared__ double rings[V::RING_WORDS];
+  v.stage(rings);
+  int nvalid = 0, nview = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    bool valid;
+    float d;
+    const int bin = v.project(rings, pts[i], valid, d);
+    bool keep     = bin >= 0;
+    nvalid += valid ? 1 : 0;
+    nview += keep ? 1 : 0;
+    if (OCCLUSION && keep) keep = d <= __uint_as_float(dmin[bin]) + v.margin();
+    flags[i] = keep ? 1 : 0;
+  }
+  block_add(nvalid, &counters[CLIP_VALID]);
+  block_add(nview, &counters[CLIP_IN_VIEW]);
+}
+
+// counters: [CLIP_VALID], [CLIP_IN_VIEW]
+template <typename V>
+__global__ void k_view_min_staged(V v, const float4* __restrict__ pts, int n, unsigned* __restrict__ dmin, uint2* __restrict__ stage,
+                                  int* __restrict__ counters) {
+  __shared__ double rings[V::RING_WORDS];
+  v.stage(rings);
+  int nvalid = 0, nview = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    bool valid;
+    float d       = 0.f;
+    const int bin = v.project(rings, pts[i], valid, d);
+    nvalid += valid ? 1 : 0;
+    nview += bin >= 0 ? 1 : 0;
+    if (bin >= 0) atomicMin(&dmin[bin], __float_as_uint(d));  // (bin < the table's size: project's bounds)
+    stage[i] = make_uint2((unsigned) bin, __float_as_uint(d));
+  }
+  block_add(nvalid, &counters[CLIP_VALID]);
+  block_add(nview, &counters[CLIP_IN_VIEW]);
+}
+
+// the flag pass behind k_view_min_staged: reads what that pass left per point
 __global__ void k_spclip_flag_staged(const uint2* __restrict__ stage, int n, const unsigned* __restrict__ rmin, float margin,
                                      int* __restrict__ flags) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -353,60 +372,6 @@ __global__ void k_spclip_flag_staged(const uint2* __restrict__ stage, int n, con
   }
 }
 
-template <bool OCCLUSION>
-__global__ void k_spclip_flag(Xf L, Xf S, sph::Geom G, float margin, const float4* __restrict__ pts, int n,
-                              const unsigned* __restrict__ rmin, int* __restrict__ flags, int* __restrict__ counters) {
-  int nvalid = 0, nview = 0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    bool valid;
-    float rho     = 0.f;
-    const int pix = spclip_project<false>(L, S, G, nullptr, 0, pts[i], valid, rho);
-    bool keep     = pix >= 0;
-    nvalid += valid ? 1 : 0;
-    nview += keep ? 1 : 0;
-    if (OCCLUSION && keep) keep = rho <= __uint_as_float(rmin[pix]) + margin;
-    flags[i] = keep ? 1 : 0;
-  }
-  block_add(nvalid, &counters[CLIP_VALID]);
-  block_add(nview, &counters[CLIP_IN_VIEW]);
-}
-
-// the two projecting passes for a sensor with a ring table (srrg2_scene_clip_spherical_rings): the boundaries travel by value and
-// are staged into LDS once per workgroup; k_spclip_flag_staged is shared with the uniform model
-__global__ void k_spclip_rings_rmin(Xf L, Xf S, sph::Geom G, sph::Rings T, const float4* __restrict__ pts, int n,
-                                    unsigned* __restrict__ rmin, uint2* __restrict__ stage, int* __restrict__ counters) {
-  __shared__ double sB[sph::MAX_RING_ROWS + 1];
-  sph::stage_rings(T, sB);
-  int nvalid = 0, nview = 0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    bool valid;
-    float rho     = 0.f;
-    const int pix = spclip_project<true>(L, S, G, sB, T.descending, pts[i], valid, rho);
-    nvalid += valid ? 1 : 0;
-    nview += pix >= 0 ? 1 : 0;
-    if (pix >= 0) atomicMin(&rmin[pix], __float_as_uint(rho));  // (pix < rows * cols: project's bounds)
-    stage[i] = make_uint2((unsigned) pix, __float_as_uint(rho));
-  }
-  block_add(nvalid, &counters[CLIP_VALID]);
-  block_add(nview, &counters[CLIP_IN_VIEW]);
-}
-
-__global__ void k_spclip_rings_flag(Xf L, Xf S, sph::Geom G, sph::Rings T, const float4* __restrict__ pts, int n,
-                                    int* __restrict__ flags, int* __restrict__ counters) {
-  __shared__ double sB[sph::MAX_RING_ROWS + 1];
-  sph::stage_rings(T, sB);
-  int nvalid = 0, nview = 0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    bool valid;
-    float rho     = 0.f;
-    const int pix = spclip_project<true>(L, S, G, sB, T.descending, pts[i], valid, rho);
-    nvalid += valid ? 1 : 0;
-    nview += pix >= 0 ? 1 : 0;
-    flags[i] = pix >= 0 ? 1 : 0;
-  }
-  block_add(nvalid, &counters[CLIP_VALID]);
-  block_add(nview, &counters[CLIP_IN_VIEW]);
-}
 
 // ---- merge --------------------------------------------------------------------------------------------------
 // one correspondence: merger_correspondence_homo_impl.cpp:55-76.  Returns true if merged.
@@ -726,6 +691,49 @@ int compact_into(srrg2_scene* full, srrg2_scene* clipped, const Xf& L, int n) {
   return compact_scatter(full, clipped, n, [&](int cap) { launch_scatter_kept(full, clipped, L, n, cap); }, nullptr);
 }
 
+// The three view clippers between their validation and their return.  `passes(grid, counters)` queues on full->stream what
+// leaves the n keep flags in full->flags and the Valid / in-view counts in counters[CLIP_VALID], [CLIP_IN_VIEW] (cleared here).
+// `dmin`: the table of `bins` per-bin minima, reserved and filled with +inf here; null without occlusion.
+template <typename Passes>
+int clip_view(srrg2_scene* full, srrg2_scene* clipped, const Xf& L, DevBuf<unsigned>* dmin, size_t bins, srrg2_clip_result* out,
+              const Passes& passes) {
+  int rc;
+  if ((rc = clip_begin(full, clipped))) return rc;
+  const int n = full->n;
+  // (arrays even for an empty result, as srrg2_scene_set leaves them: srrg2_scene_device_arrays then shows the normals' presence)
+  if ((rc = scene_reserve(clipped, 1, 0)) || (rc = clipped->gidx.reserve(1))) return rc;
+  if (out) {
+    std::memset(out, 0, sizeof(*out));
+    out->status = n == 0 ? SRRG2_CLIPPER_READY : SRRG2_CLIPPER_SUCCESSFUL;
+  }
+  if (n == 0) return 0;
+  hipStream_t st = full->stream;
+  if ((rc = full->flags.reserve((size_t) n + 1))) return rc;
+  int* const counters = full->dscalars.p;  // (compact_into brings them to the host with the scan's total)
+  HIP_TRY(hipMemsetAsync(counters, 0, CLIP_TOTAL * sizeof(int), st));
+  if (dmin) {
+    if ((rc = dmin->reserve(bins))) return rc;
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) dmin->p, 0x7f800000, bins, st));  // +inf
+  }
+  if ((rc = passes(dim3(blocks_for(n)), counters))) return rc;
+  if ((rc = compact_into(full, clipped, L, n))) return rc;
+  if (out) {
+    out->num_valid   = full->scalars[CLIP_VALID];
+    out->num_in_view = full->scalars[CLIP_IN_VIEW];
+    out->num_kept    = full->scalars[CLIP_TOTAL];
+  }
+  return 0;
+}
+
+// the projecting flag pass of a view: behind a minimum pass that filled `dmin`, or -- null -- on its own
+template <typename V>
+void launch_view_flag(const V& view, srrg2_scene* full, dim3 grid, const unsigned* dmin, int* counters) {
+  if (dmin)
+    hipLaunchKernelGGL((k_view_flag<V, true>), grid, dim3(256), 0, full->stream, view, full->pts.p, full->n, dmin, full->flags.p, counters);
+  else
+    hipLaunchKernelGGL((k_view_flag<V, false>), grid, dim3(256), 0, full->stream, view, full->pts.p, full->n, dmin, full->flags.p, counters);
+}
+
 int check_params(const srrg2_merger_params* p) {
   if (!p) return fail(SRRG2_E_INVALID, "scene_merge: null params");
   if (p->target_number_of_merges < 0) return fail(SRRG2_E_INVALID, "scene_merge: target_number_of_merges < 0");
@@ -1020,45 +1028,21 @@ int srrg2_scene_clip_projective(srrg2_scene_h full, const float* robot_in_local_
   if (std::isnan(p->occlusion_margin)) return fail(SRRG2_E_INVALID, "scene_clip_projective: occlusion_margin is NaN");
   if (p->camera_matrix[1] != 0.f)
     return fail(SRRG2_E_UNSUPPORTED, "scene_clip_projective: a camera matrix with skew (K[0][1] != 0)");
-  int rc;
-  if ((rc = clip_begin(full, clipped))) return rc;
   float Linv[12], Sinv[12];
   dm::se3_inverse(robot_in_local_map, Linv);
   dm::se3_inverse(p->sensor_in_robot, Sinv);
-  const Xf L = load_transform(3, Linv), S = load_transform(3, Sinv);
-  const ProjCam cam{fx, p->camera_matrix[2], fy, p->camera_matrix[5], p->depth_min, p->depth_max, p->occlusion_margin,
-                    p->image_rows, p->image_cols};
+  const PinholeView view{{load_transform(3, Linv), load_transform(3, Sinv)},
+                         {fx, p->camera_matrix[2], fy, p->camera_matrix[5], p->depth_min, p->depth_max, p->occlusion_margin,
+                          p->image_rows, p->image_cols}};
   const bool occlusion = p->occlusion_margin >= 0.f;
-  const int n          = full->n;
-  // (arrays even for an empty result, as srrg2_scene_set leaves them: srrg2_scene_device_arrays then shows the normals' presence)
-  if ((rc = scene_reserve(clipped, 1, 0)) || (rc = clipped->gidx.reserve(1))) return rc;
-  if (out) {
-    std::memset(out, 0, sizeof(*out));
-    out->status = n == 0 ? SRRG2_CLIPPER_READY : SRRG2_CLIPPER_SUCCESSFUL;
-  }
-  if (n == 0) return 0;
-  hipStream_t st = full->stream;
-  if ((rc = full->flags.reserve((size_t) n + 1))) return rc;
-  int* const counters = full->dscalars.p;  // (compact_into brings them to the host with the scan's total)
-  HIP_TRY(hipMemsetAsync(counters, 0, CLIP_TOTAL * sizeof(int), st));
-  const dim3 grid(blocks_for(n));
-  if (occlusion) {
-    const size_t npix = (size_t) cam.rows * (size_t) cam.cols;
-    if ((rc = full->zmin.reserve(npix))) return rc;
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) full->zmin.p, 0x7f800000, npix, st));  // +inf
-    hipLaunchKernelGGL(k_pclip_zmin, grid, dim3(256), 0, st, L, S, cam, full->pts.p, n, full->zmin.p);
-    hipLaunchKernelGGL(k_pclip_flag<true>, grid, dim3(256), 0, st, L, S, cam, full->pts.p, n, full->zmin.p, full->flags.p, counters);
-  } else {
-    hipLaunchKernelGGL(k_pclip_flag<false>, grid, dim3(256), 0, st, L, S, cam, full->pts.p, n, (const unsigned*) nullptr,
-                       full->flags.p, counters);
-  }
-  if ((rc = compact_into(full, clipped, L, n))) return rc;
-  if (out) {
-    out->num_valid   = full->scalars[CLIP_VALID];
-    out->num_in_view = full->scalars[CLIP_IN_VIEW];
-    out->num_kept    = full->scalars[CLIP_TOTAL];
-  }
-  return 0;
+  return clip_view(full, clipped, view.L, occlusion ? &full->zmin : nullptr, (size_t) p->image_rows * (size_t) p->image_cols, out,
+                   [&](dim3 grid, int* counters) {
+                     if (occlusion)
+                       hipLaunchKernelGGL(k_view_min<PinholeView>, grid, dim3(256), 0, full->stream, view, full->pts.p, full->n,
+                                          full->zmin.p);
+                     launch_view_flag(view, full, grid, occlusion ? full->zmin.p : nullptr, counters);
+                     return 0;
+                   });
 }
 
 void srrg2_clip_default_scan_params(srrg2_scan_clip_params* p) {
@@ -1090,55 +1074,29 @@ int srrg2_scene_clip_scan(srrg2_scene_h full, const float* robot_in_local_map, c
     return fail(SRRG2_E_INVALID, "scene_clip_scan: |angle_increment| * num_beams beyond 2 pi plus one increment");
   if (!(p->range_min > 0.f) || !(p->range_max >= p->range_min)) return fail(SRRG2_E_INVALID, "scene_clip_scan: 0 < range_min <= range_max");
   if (std::isnan(p->occlusion_margin)) return fail(SRRG2_E_INVALID, "scene_clip_scan: occlusion_margin is NaN");
-  int rc;
-  if ((rc = clip_begin(full, clipped))) return rc;
   float Linv[9], Sinv[9];
   dm::se2_inverse(robot_in_local_map, Linv);
   dm::se2_inverse(p->sensor_in_robot, Sinv);
-  const Xf L = load_transform(2, Linv), S = load_transform(2, Sinv);
-  const ScanGeom geom{p->angle_min, p->angle_increment, std::copysign(TWO_PI, p->angle_increment),
-                      p->range_min, p->range_max,       p->occlusion_margin,
-                      p->num_beams};
+  const BeamView view{{load_transform(2, Linv), load_transform(2, Sinv)},
+                      {p->angle_min, p->angle_increment, std::copysign(TWO_PI, p->angle_increment), p->range_min, p->range_max,
+                       p->occlusion_margin, p->num_beams}};
   const bool occlusion = p->occlusion_margin >= 0.f;
-  const int n          = full->n;
-  // (arrays even for an empty result, as srrg2_scene_set leaves them: srrg2_scene_device_arrays then shows the normals' presence)
-  if ((rc = scene_reserve(clipped, 1, 0)) || (rc = clipped->gidx.reserve(1))) return rc;
-  if (out) {
-    std::memset(out, 0, sizeof(*out));
-    out->status = n == 0 ? SRRG2_CLIPPER_READY : SRRG2_CLIPPER_SUCCESSFUL;
-  }
-  if (n == 0) return 0;
-  hipStream_t st = full->stream;
-  if ((rc = full->flags.reserve((size_t) n + 1))) return rc;
-  int* const counters = full->dscalars.p;  // (compact_into brings them to the host with the scan's total)
-  HIP_TRY(hipMemsetAsync(counters, 0, CLIP_TOTAL * sizeof(int), st));
-  const dim3 grid(blocks_for(n));
-  if (occlusion) {
-    const int nb = geom.num_beams;
-    if ((rc = full->rmin.reserve((size_t) nb))) return rc;
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) full->rmin.p, 0x7f800000, (size_t) nb, st));  // +inf
-#ifndef SRRG2_SCLIP_NO_LDS
+  const int nb         = p->num_beams;
+  return clip_view(full, clipped, view.L, occlusion ? &full->rmin : nullptr, (size_t) nb, out, [&](dim3 grid, int* counters) {
+    hipStream_t st = full->stream;
+    const int n    = full->n;
     // every workgroup initialises and flushes num_beams words: give each at least SRRG2_SCLIP_POINTS_PER_BIN points per bin
     const long long share = (long long) SRRG2_SCLIP_POINTS_PER_BIN * nb;
-    if (nb <= SRRG2_SCLIP_LDS_BINS && n / share >= SRRG2_SCLIP_LDS_MIN_WORKGROUPS) {
+    if (occlusion && nb <= SRRG2_SCLIP_LDS_BINS && n / share >= SRRG2_SCLIP_LDS_MIN_WORKGROUPS) {
       const int blocks = (int) std::min<long long>(grid.x, n / share);
-      hipLaunchKernelGGL(k_sclip_rmin_lds, dim3(blocks), dim3(256), (size_t) nb * sizeof(unsigned), st, L, S, geom, full->pts.p, n,
-                         full->rmin.p);
-    } else
-#endif
-      hipLaunchKernelGGL(k_sclip_rmin, grid, dim3(256), 0, st, L, S, geom, full->pts.p, n, full->rmin.p);
-    hipLaunchKernelGGL(k_sclip_flag<true>, grid, dim3(256), 0, st, L, S, geom, full->pts.p, n, full->rmin.p, full->flags.p, counters);
-  } else {
-    hipLaunchKernelGGL(k_sclip_flag<false>, grid, dim3(256), 0, st, L, S, geom, full->pts.p, n, (const unsigned*) nullptr,
-                       full->flags.p, counters);
-  }
-  if ((rc = compact_into(full, clipped, L, n))) return rc;
-  if (out) {
-    out->num_valid   = full->scalars[CLIP_VALID];
-    out->num_in_view = full->scalars[CLIP_IN_VIEW];
-    out->num_kept    = full->scalars[CLIP_TOTAL];
-  }
-  return 0;
+      hipLaunchKernelGGL(k_view_min_lds<BeamView>, dim3(blocks), dim3(256), (size_t) nb * sizeof(unsigned), st, view, nb, full->pts.p,
+                         n, full->rmin.p);
+    } else if (occlusion) {
+      hipLaunchKernelGGL(k_view_min<BeamView>, grid, dim3(256), 0, st, view, full->pts.p, n, full->rmin.p);
+    }
+    launch_view_flag(view, full, grid, occlusion ? full->rmin.p : nullptr, counters);
+    return 0;
+  });
 }
 
 }  // extern "C"
@@ -1161,61 +1119,31 @@ static int clip_spherical(const std::string& who, srrg2_scene_h full, const floa
     if (const char* why = sph::rings_of(p->model, ring_elevations, table, &unsupported))
       return fail(unsupported ? SRRG2_E_UNSUPPORTED : SRRG2_E_INVALID, who + why);
   }
-  int rc;
-  if ((rc = clip_begin(full, clipped))) return rc;
   float Linv[12], Sinv[12];
   dm::se3_inverse(robot_in_local_map, Linv);
   dm::se3_inverse(p->sensor_in_robot, Sinv);
-  const Xf L = load_transform(3, Linv), S = load_transform(3, Sinv);
-  const sph::Geom geom = sph::geom_of(p->model);
-  const float margin   = p->occlusion_margin;
+  const float margin = p->occlusion_margin;
+  const LidarView view{{load_transform(3, Linv), load_transform(3, Sinv)}, sph::geom_of(p->model), margin};
   const bool occlusion = margin >= 0.f;
-  const int n          = full->n;
-  // (arrays even for an empty result, as srrg2_scene_set leaves them: srrg2_scene_device_arrays then shows the normals' presence)
-  if ((rc = scene_reserve(clipped, 1, 0)) || (rc = clipped->gidx.reserve(1))) return rc;
-  if (out) {
-    std::memset(out, 0, sizeof(*out));
-    out->status = n == 0 ? SRRG2_CLIPPER_READY : SRRG2_CLIPPER_SUCCESSFUL;
-  }
-  if (n == 0) return 0;
-  hipStream_t st = full->stream;
-  if ((rc = full->flags.reserve((size_t) n + 1))) return rc;
-  int* const counters = full->dscalars.p;  // (compact_into brings them to the host with the scan's total)
-  HIP_TRY(hipMemsetAsync(counters, 0, CLIP_TOTAL * sizeof(int), st));
-  const dim3 grid(blocks_for(n));
-  if (occlusion) {
-    const size_t npix = (size_t) geom.rows * (size_t) geom.cols;
-    if ((rc = full->rmin.reserve(npix))) return rc;
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) full->rmin.p, 0x7f800000, npix, st));  // +inf
-    if (ring_elevations) {
-      if ((rc = full->sph_stage.reserve((size_t) n))) return rc;
-      hipLaunchKernelGGL(k_spclip_rings_rmin, grid, dim3(256), 0, st, L, S, geom, table, full->pts.p, n, full->rmin.p,
-                         full->sph_stage.p, counters);
-      hipLaunchKernelGGL(k_spclip_flag_staged, grid, dim3(256), 0, st, full->sph_stage.p, n, full->rmin.p, margin, full->flags.p);
-    } else {
-#ifndef SRRG2_SPCLIP_RECOMPUTE
-    if ((rc = full->sph_stage.reserve((size_t) n))) return rc;
-    hipLaunchKernelGGL(k_spclip_rmin, grid, dim3(256), 0, st, L, S, geom, full->pts.p, n, full->rmin.p, full->sph_stage.p, counters);
-    hipLaunchKernelGGL(k_spclip_flag_staged, grid, dim3(256), 0, st, full->sph_stage.p, n, full->rmin.p, margin, full->flags.p);
-#else
-    hipLaunchKernelGGL(k_spclip_rmin, grid, dim3(256), 0, st, L, S, geom, full->pts.p, n, full->rmin.p, (uint2*) nullptr, counters);
-    hipLaunchKernelGGL(k_spclip_flag<true>, grid, dim3(256), 0, st, L, S, geom, margin, full->pts.p, n, full->rmin.p, full->flags.p,
-                       counters);
-#endif
+  // the lidar's passes over either view: staged minimum -> staged flag, or one projecting flag
+  const auto passes = [&](const auto& v, dim3 grid, int* counters) {
+    using V        = std::decay_t<decltype(v)>;
+    hipStream_t st = full->stream;
+    const int n    = full->n;
+    if (!occlusion) {
+      hipLaunchKernelGGL((k_view_flag<V, false>), grid, dim3(256), 0, st, v, full->pts.p, n, (const unsigned*) nullptr, full->flags.p,
+                         counters);
+      return 0;
     }
-  } else if (ring_elevations) {
-    hipLaunchKernelGGL(k_spclip_rings_flag, grid, dim3(256), 0, st, L, S, geom, table, full->pts.p, n, full->flags.p, counters);
-  } else {
-    hipLaunchKernelGGL(k_spclip_flag<false>, grid, dim3(256), 0, st, L, S, geom, margin, full->pts.p, n, (const unsigned*) nullptr,
-                       full->flags.p, counters);
-  }
-  if ((rc = compact_into(full, clipped, L, n))) return rc;
-  if (out) {
-    out->num_valid   = full->scalars[CLIP_VALID];
-    out->num_in_view = full->scalars[CLIP_IN_VIEW];
-    out->num_kept    = full->scalars[CLIP_TOTAL];
-  }
-  return 0;
+    if (int rc = full->sph_stage.reserve((size_t) n)) return rc;
+    hipLaunchKernelGGL(k_view_min_staged<V>, grid, dim3(256), 0, st, v, full->pts.p, n, full->rmin.p, full->sph_stage.p, counters);
+    hipLaunchKernelGGL(k_spclip_flag_staged, grid, dim3(256), 0, st, full->sph_stage.p, n, full->rmin.p, margin, full->flags.p);
+    return 0;
+  };
+  return clip_view(full, clipped, view.L, occlusion ? &full->rmin : nullptr, (size_t) p->model.rows * (size_t) p->model.cols, out,
+                   [&](dim3 grid, int* counters) {
+                     return ring_elevations ? passes(RingLidarView{view, table}, grid, counters) : passes(view, grid, counters);
+                   });
 }
 
 extern "C" {

@@ -298,12 +298,11 @@ class Scene:
         return c, (m if m else None), n.value
 
 
-class SceneClipperBall:
-    """setFullScene / setClippedSceneInRobot / setRobotInLocalMap / compute / status / globalIndices."""
+class _ClipperBase:
+    """what the four clippers share: the full scene, the clipped scene, the pose, status() and global_indices()."""
 
-    def __init__(self, binding, range_max=10.0):
+    def __init__(self, binding):
         self._b = binding
-        self.range_max = float(range_max)
         self._full = self._clipped = None
         self._robot_in_local_map = None
         self._status = CLIPPER_ERROR
@@ -317,143 +316,96 @@ class SceneClipperBall:
     def set_robot_in_local_map(self, T):
         self._robot_in_local_map = _f32(T)
 
-    def compute(self):
+    def _ready(self):
         if self._full is None or self._clipped is None or self._robot_in_local_map is None:
-            raise RuntimeError("SceneClipperBall::compute|scene, output or pose not set")
+            raise RuntimeError("%s::compute|scene, output or pose not set" % type(self).__name__)
+
+    def status(self):
+        return self._status
+
+    def global_indices(self):
+        return self._clipped.global_indices()
+
+
+class SceneClipperBall(_ClipperBase):
+    """setFullScene / setClippedSceneInRobot / setRobotInLocalMap / compute / status / globalIndices."""
+
+    def __init__(self, binding, range_max=10.0):
+        super().__init__(binding)
+        self.range_max = float(range_max)
+
+    def compute(self):
+        self._ready()
         st = C.c_int(0)
         self._b.check(self._b.fn("clip_ball")(self._full._h, _fp(self._robot_in_local_map), C.c_float(self.range_max),
                                               self._clipped._h, C.byref(st)))
         self._status = st.value
 
-    def status(self):
-        return self._status
 
-    def global_indices(self):
-        return self._clipped.global_indices()
+class _ViewClipperBase(_ClipperBase):
+    """the clippers with a sensor: ``params`` (its sensor_in_robot has ``_SENSOR_FLOATS`` floats), ``last`` and the frame of
+    compute(); a subclass makes the call in ``_clip(out)``, ``out`` being the result struct by reference or None."""
+
+    def __init__(self, binding, params):
+        super().__init__(binding)
+        self.params = params
+        self.last = None
+
+    def set_sensor_in_robot(self, T):
+        for i, v in enumerate(_f32(T).reshape(self._SENSOR_FLOATS)):
+            self.params.sensor_in_robot[i] = float(v)
+
+    def compute(self, want_result=True):
+        self._ready()
+        out = ClipResult()
+        self._status = CLIPPER_ERROR
+        self._b.check(self._clip(C.byref(out) if want_result else None))
+        if want_result:
+            self._status, self.last = out.status, out.as_dict()
+        else:
+            self._status, self.last = (CLIPPER_SUCCESSFUL if self._full.size() else CLIPPER_READY), None
+        return self.last
 
 
-class SceneClipperProjective:
+class SceneClipperProjective(_ViewClipperBase):
     """setFullScene / setClippedSceneInRobot / setRobotInLocalMap / setSensorInRobot / setCameraMatrix / compute / status /
     globalIndices.  ``params``: ProjectiveClipParams (image size, depth range, occlusion_margin); ``last``: the counts of the
     last compute() (``want_result=False`` passes no result struct: ``last`` is then None)."""
+    _SENSOR_FLOATS = 12
 
     def __init__(self, binding, params=None):
-        self._b = binding
-        self.params = params or default_projective_clip_params()
-        self._full = self._clipped = None
-        self._robot_in_local_map = None
-        self._status = CLIPPER_ERROR
-        self.last = None
-
-    def set_full_scene(self, scene):
-        self._full = scene
-
-    def set_clipped_scene_in_robot(self, scene):
-        self._clipped = scene
-
-    def set_robot_in_local_map(self, T):
-        self._robot_in_local_map = _f32(T)
-
-    def set_sensor_in_robot(self, T):
-        for i, v in enumerate(_f32(T).reshape(12)):
-            self.params.sensor_in_robot[i] = float(v)
+        super().__init__(binding, params or default_projective_clip_params())
 
     def set_camera_matrix(self, K):
         for i, v in enumerate(_f32(K).reshape(9)):
             self.params.camera_matrix[i] = float(v)
 
-    def compute(self, want_result=True):
-        if self._full is None or self._clipped is None or self._robot_in_local_map is None:
-            raise RuntimeError("SceneClipperProjective::compute|scene, output or pose not set")
-        out = ClipResult()
-        self._status = CLIPPER_ERROR
-        self._b.check(self._b.fn("clip_projective")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params),
-                                                    self._clipped._h, C.byref(out) if want_result else None))
-        if want_result:
-            self._status, self.last = out.status, out.as_dict()
-        else:
-            self._status, self.last = (CLIPPER_SUCCESSFUL if self._full.size() else CLIPPER_READY), None
-        return self.last
-
-    def status(self):
-        return self._status
-
-    def global_indices(self):
-        return self._clipped.global_indices()
+    def _clip(self, out):
+        return self._b.fn("clip_projective")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params), self._clipped._h, out)
 
 
-class SceneClipperScan:
+class SceneClipperScan(_ViewClipperBase):
     """setFullScene / setClippedSceneInRobot / setRobotInLocalMap / setSensorInRobot / compute / status / globalIndices for 2-D
     scenes.  ``params``: ScanClipParams (angle_min, angle_increment, num_beams, range interval, occlusion_margin); ``last``: the
     counts of the last compute() (``want_result=False`` passes no result struct: ``last`` is then None)."""
+    _SENSOR_FLOATS = 9
 
     def __init__(self, binding, params=None):
-        self._b = binding
-        self.params = params or default_scan_clip_params()
-        self._full = self._clipped = None
-        self._robot_in_local_map = None
-        self._status = CLIPPER_ERROR
-        self.last = None
+        super().__init__(binding, params or default_scan_clip_params())
 
-    def set_full_scene(self, scene):
-        self._full = scene
-
-    def set_clipped_scene_in_robot(self, scene):
-        self._clipped = scene
-
-    def set_robot_in_local_map(self, T):
-        self._robot_in_local_map = _f32(T)
-
-    def set_sensor_in_robot(self, T):
-        for i, v in enumerate(_f32(T).reshape(9)):
-            self.params.sensor_in_robot[i] = float(v)
-
-    def compute(self, want_result=True):
-        if self._full is None or self._clipped is None or self._robot_in_local_map is None:
-            raise RuntimeError("SceneClipperScan::compute|scene, output or pose not set")
-        out = ClipResult()
-        self._status = CLIPPER_ERROR
-        self._b.check(self._b.fn("clip_scan")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params),
-                                              self._clipped._h, C.byref(out) if want_result else None))
-        if want_result:
-            self._status, self.last = out.status, out.as_dict()
-        else:
-            self._status, self.last = (CLIPPER_SUCCESSFUL if self._full.size() else CLIPPER_READY), None
-        return self.last
-
-    def status(self):
-        return self._status
-
-    def global_indices(self):
-        return self._clipped.global_indices()
+    def _clip(self, out):
+        return self._b.fn("clip_scan")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params), self._clipped._h, out)
 
 
-class SceneClipperSpherical:
+class SceneClipperSpherical(_ViewClipperBase):
     """setFullScene / setClippedSceneInRobot / setRobotInLocalMap / setSensorInRobot / compute / status / globalIndices for 3-D
     scenes seen by a spinning lidar.  ``params``: SphericalClipParams (model, occlusion_margin); ``last``: the counts of the last
     compute() (``want_result=False`` passes no result struct: ``last`` is then None)."""
+    _SENSOR_FLOATS = 12
 
     def __init__(self, binding, params=None):
-        self._b = binding
-        self.params = params or default_spherical_clip_params()
-        self._full = self._clipped = None
-        self._robot_in_local_map = None
+        super().__init__(binding, params or default_spherical_clip_params())
         self._rings = None
-        self._status = CLIPPER_ERROR
-        self.last = None
-
-    def set_full_scene(self, scene):
-        self._full = scene
-
-    def set_clipped_scene_in_robot(self, scene):
-        self._clipped = scene
-
-    def set_robot_in_local_map(self, T):
-        self._robot_in_local_map = _f32(T)
-
-    def set_sensor_in_robot(self, T):
-        for i, v in enumerate(_f32(T).reshape(12)):
-            self.params.sensor_in_robot[i] = float(v)
 
     def set_model(self, model):
         C.memmove(C.byref(self.params.model), C.byref(model), C.sizeof(SphericalModel))
@@ -464,31 +416,14 @@ class SceneClipperSpherical:
         A copy is kept; its length must be ``params.model.rows`` at compute()."""
         self._rings = None if elevations is None else np.array(elevations, dtype=np.float64).reshape(-1)
 
-    def compute(self, want_result=True):
-        if self._full is None or self._clipped is None or self._robot_in_local_map is None:
-            raise RuntimeError("SceneClipperSpherical::compute|scene, output or pose not set")
-        out = ClipResult()
-        self._status = CLIPPER_ERROR
+    def _clip(self, out):
         if self._rings is None:
-            self._b.check(self._b.fn("clip_spherical")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params),
-                                                       self._clipped._h, C.byref(out) if want_result else None))
-        else:
-            if self._rings.shape[0] != self.params.model.rows:
-                raise ValueError("ring elevations: %d entries for %d rows" % (self._rings.shape[0], self.params.model.rows))
-            self._b.check(self._b.fn("clip_spherical_rings")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params),
-                                                             self._rings.ctypes.data_as(C.POINTER(C.c_double)), self._clipped._h,
-                                                             C.byref(out) if want_result else None))
-        if want_result:
-            self._status, self.last = out.status, out.as_dict()
-        else:
-            self._status, self.last = (CLIPPER_SUCCESSFUL if self._full.size() else CLIPPER_READY), None
-        return self.last
-
-    def status(self):
-        return self._status
-
-    def global_indices(self):
-        return self._clipped.global_indices()
+            return self._b.fn("clip_spherical")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params), self._clipped._h,
+                                                out)
+        if self._rings.shape[0] != self.params.model.rows:
+            raise ValueError("ring elevations: %d entries for %d rows" % (self._rings.shape[0], self.params.model.rows))
+        return self._b.fn("clip_spherical_rings")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params),
+                                                  self._rings.ctypes.data_as(C.POINTER(C.c_double)), self._clipped._h, out)
 
 
 class MergerCorrespondenceHomo:

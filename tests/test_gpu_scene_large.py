@@ -156,7 +156,7 @@ def _check_clip(clipped, r, res, c, same_bits, what):
 
 
 def test_projective_clip_past_the_cap_with_features(product):
-    """occlusion on (k_pclip_zmin, k_pclip_flag<true>), then off, into one clipped scene"""
+    """occlusion on (k_view_min, k_view_flag<PinholeView, true>), then off, into one clipped scene"""
     clock = _Clock("B projective")
     c = lc.clip_case(3)
     b, full, clipped = _full_scene(product, c, 3)
@@ -180,7 +180,7 @@ def test_projective_clip_past_the_cap_with_features(product):
 
 
 def test_scan_clip_past_the_cap_with_features(product):
-    """occlusion with the per-beam minimum in LDS tables (k_sclip_rmin_lds), in global memory (k_sclip_rmin: 100 000 beams), and
+    """occlusion with the per-beam minimum in LDS tables (k_view_min_lds), in global memory (k_view_min: 100 000 beams), and
     off, into one clipped scene"""
     clock = _Clock("B scan")
     c = lc.clip_case(2)

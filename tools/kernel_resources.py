@@ -18,7 +18,7 @@ for b, d in zip(blocks, dem):
     def g(k):
         m = re.search(k + r": (\d+)", b)
         return int(m.group(1)) if m else -1
-    d = re.sub(r"^void ", "", d)
+    d = re.sub(r"^void ", "", d).replace("(anonymous namespace)::", "")
     d = re.sub(r"\(.*", "", d)[:78]
     if want and not any(w in d for w in want):
         continue
