@@ -1012,6 +1012,63 @@ int srrg2_adapt_lidar_sweep_ex(srrg2_scene_h dst /* dim 3 */, const float* point
                                const srrg2_lidar_adaptor_params* p, const srrg2_lidar_sweep_extras* x /* NULL = plain */,
                                srrg2_adapt_result* out /* may be NULL */);
 
+/* Image features: an 8-bit intensity image (+ optional depth image) -> a compact scene of keypoints, each with a 3-D point, a
+ * 256-bit descriptor and an intensity -- the producer of the PointIntensityDescriptor3f clouds that srrg2_scene_set_features,
+ * the merger and srrg2_descriptor_db_add_scene / match_scene carry (S/mapping/merger_correspondence_homo.h:36-40,
+ * multi_loop_detector_hbst_impl.cpp:84-85, :131-136).  No reference counterpart; DESIGN.md section 4 "Image features" is the
+ * contract, all image arithmetic is integer, tests/features_restatement.py restates it and the library gives the same bits.
+ *   score     FAST on the 16-pixel circle of radius 3: the largest t below which 9 contiguous circle pixels are all brighter
+ *             than centre + t or all darker than centre - t; 0 within 3 pixels of a border.
+ *   maxima    keypoint: score > fast_threshold, at least 16 pixels from every border, score strictly above the 4 of its 8
+ *             neighbours that precede it in raster order and not below the 4 that follow.
+ *   cap       max_features > 0 and more keypoints than that: those above the cut score s* stay, of those at s* the first in
+ *             raster order, max_features in all (256-bin histogram, no sort).  Output order: ascending pixel index.
+ *   angle     oriented: the bin k of 32 that maximises m10 * C_k + m01 * S_k (lowest k of equals), m10 / m01 the first moments
+ *             of the intensity over the disc of radius 15, C_k / S_k = round(16384 cos / sin (2 pi k / 32)); else bin 0.
+ *   bits      bit i = B(a_i) < B(b_i): B the 5x5 box sum, (a_i, b_i) pair i of srrg2_feature_pattern(angle_bin); bit i lies in
+ *             byte i / 8, bit i % 8.
+ *   point     with a depth image (U16 / F32 as srrg2_adapt_depth_image): a keypoint is kept iff its own depth pixel is in range,
+ *             its coordinates are what srrg2_adapt_depth_image stores for that pixel; without (depth NULL, depth_type NONE):
+ *             the unprojection at z = 1.  The cap comes before the depth gate.
+ *   cam       read: camera_matrix, rows, cols, depth_scale, depth_min, depth_max; the normal and compact fields are not read.
+ *   scene     dst (dim 3) holds the kept keypoints in pixel order: no normals, both features (the intensity is the pixel's value
+ *             as float), srrg2_scene_global_indices(dst) = pixel indices r*cols + c.  keypoints_out (host) receives up to
+ *             keypoint_capacity records in the same order.
+ *   refused   SRRG2_E_INVALID, dst unchanged: wrong dim, null params, a null intensity image of more than zero pixels, rows or
+ *             cols < 0 or rows*cols beyond int32, a stride smaller than a row, a depth image not aligned to its element, bad
+ *             mem, fast_threshold outside 0 .. 254, max_features < 0, oriented not 0 / 1, reserved != 0, keypoint_capacity < 0,
+ *             a depth image with depth_type NONE or U8 (or a depth_type without an image), fx or fy zero / not finite.
+ *             SRRG2_E_UNSUPPORTED: intensity_type U16 or F32, K[0][1] != 0.
+ *   status    zero pixels: an empty scene, INITIALIZING.  Either side below 33 (no admissible pixel): an empty scene, READY.
+ *   waits     ONE host wait in the middle, for the number of kept keypoints (it sizes dst); the call returns when dst, and
+ *             keypoints_out, are complete.  SRRG2_MEM_HOST images are consumed before the call returns. */
+typedef struct srrg2_feature_params {
+  int32_t fast_threshold; /* 0 .. 254, default 20 */
+  int32_t max_features;   /* 0 = no cap, default 1000 */
+  int32_t oriented;       /* 0 | 1, default 1 */
+  int32_t reserved;       /* 0 */
+} srrg2_feature_params;
+typedef struct srrg2_keypoint {
+  int32_t pixel, score, angle_bin, reserved;
+} srrg2_keypoint;
+typedef struct srrg2_feature_result {
+  int32_t status;         /* srrg2_adaptor_status */
+  int32_t num_pixels;
+  int32_t num_candidates; /* score > fast_threshold inside the margin */
+  int32_t num_maxima;
+  int32_t num_selected;   /* after the cap */
+  int32_t num_with_depth;
+  int32_t scene_size;
+} srrg2_feature_result;
+void srrg2_adapt_default_feature_params(srrg2_feature_params* p);
+int srrg2_adapt_image_features(srrg2_scene_h dst /* dim 3 */, const void* intensity, int intensity_type /* U8 */,
+                               int intensity_row_stride_bytes, const void* depth /* may be NULL */, int depth_type,
+                               int depth_row_stride_bytes, int mem, const srrg2_depth_adaptor_params* cam,
+                               const srrg2_feature_params* p, srrg2_keypoint* keypoints_out /* host, may be NULL */,
+                               int keypoint_capacity, srrg2_feature_result* out /* may be NULL */);
+/* the 256 point pairs (ax, ay, bx, by) of orientation bin 0 .. 31, rotated: 1024 values.  Needs no device. */
+int srrg2_feature_pattern(int angle_bin, int8_t* pairs_out);
+
 /* ---- strategy knobs (no reference counterpart) ----------------------------------------------------------------
  * Every setting gives the SAME results (indices, estimates, statistics bit for bit): the knobs choose between exact
  * strategies of the finder / reduction / control step.  A handle starts from srrg2_aligner_default_tuning() overridden

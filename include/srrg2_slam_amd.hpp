@@ -680,6 +680,7 @@ private:
 //   DepthImageAdaptor   depth image (+ intensity image) -> Scene<3>, organised or compact, with normals
 //   LaserScanAdaptor    ranges -> Scene<2> with normals
 //   LidarSweepAdaptor   3-D lidar sweep (point list, + intensity) -> Scene<3>, organised or compact, with normals
+//   ImageFeatureAdaptor 8-bit intensity image (+ depth image) -> Scene<3> of keypoints with descriptors and intensity
 // setRawData / setMeas / compute / status / reset; status() is Error after setRawData until compute() (:67-72).  The raw
 // data is borrowed until compute() has run.  compute(false) asks for no counts: an organised adapt then only queues its work.
 class AdaptorBase_ {
@@ -822,6 +823,64 @@ private:
   bool _has_raw = false;
   srrg2_lidar_sweep_extras _extras;
   std::vector<double> _rings;
+};
+
+// 8-bit intensity image (+ optional depth image) -> Scene<3> of keypoints: point, 256-bit descriptor, intensity, no normals;
+// globalIndices() = pixel indices (srrg2_adapt_image_features).  camera: camera_matrix, rows, cols and the depth scale / gates
+// are read.  last() keeps status and scene_size; features() has every counter, keypoints() the records in the scene's order.
+class ImageFeatureAdaptor : public AdaptorBase_ {
+public:
+  using MeasurementType = Scene<3>;
+  srrg2_feature_params param;
+  srrg2_depth_adaptor_params camera;
+  ImageFeatureAdaptor() {
+    srrg2_adapt_default_feature_params(&param);
+    srrg2_adapt_default_depth_params(&camera);
+  }
+  // images with a row stride in bytes; depth may be nullptr with SRRG2_IMAGE_NONE; camera.rows / cols say the size
+  void setRawData(const uint8_t* intensity, int intensity_row_stride_bytes, const void* depth = nullptr,
+                  int depth_type = SRRG2_IMAGE_NONE, int depth_row_stride_bytes = 0, int mem = SRRG2_MEM_HOST) {
+    _inten = intensity, _inten_stride = intensity_row_stride_bytes;
+    _depth = depth, _depth_type = depth_type, _depth_stride = depth_row_stride_bytes;
+    _mem = mem, _has_raw = true;
+    _status = Error;
+  }
+  void setMeas(MeasurementType* meas) { _meas = meas; }
+  void reset() {
+    _has_raw = false;
+    _status  = Initializing;
+    _keypoints.clear();
+  }
+  void compute() {
+    if (!_meas || !_has_raw) throw std::runtime_error("ImageFeatureAdaptor::compute|raw data or measurement not set");
+    // every selected keypoint fits: the cap, or every admissible pixel
+    const long long inner = (long long) (camera.rows > 32 ? camera.rows - 32 : 0) * (long long) (camera.cols > 32 ? camera.cols - 32 : 0);
+    const long long want  = param.max_features > 0 && param.max_features < inner ? param.max_features : inner;
+    _keypoints.assign((size_t) (want > 0 ? want : 0), srrg2_keypoint{});
+    _features = srrg2_feature_result{};
+    const int rc = srrg2_adapt_image_features(_meas->handle(), _inten, SRRG2_IMAGE_U8, _inten_stride, _depth, _depth_type,
+                                              _depth_stride, _mem, &camera, &param, _keypoints.empty() ? nullptr : _keypoints.data(),
+                                              (int) _keypoints.size(), &_features);
+    if (rc != 0) _keypoints.clear();
+    _last            = srrg2_adapt_result{};
+    _last.status     = _features.status;
+    _last.num_raw    = _features.num_pixels;
+    _last.num_valid  = _features.scene_size;
+    _last.scene_size = _features.scene_size;
+    finish(rc, true);
+    _keypoints.resize((size_t) _features.scene_size < _keypoints.size() ? (size_t) _features.scene_size : _keypoints.size());
+  }
+  const srrg2_feature_result& features() const { return _features; }
+  const std::vector<srrg2_keypoint>& keypoints() const { return _keypoints; }
+
+private:
+  MeasurementType* _meas = nullptr;
+  const uint8_t* _inten  = nullptr;
+  const void* _depth     = nullptr;
+  int _inten_stride = 0, _depth_type = SRRG2_IMAGE_NONE, _depth_stride = 0, _mem = SRRG2_MEM_HOST;
+  bool _has_raw = false;
+  srrg2_feature_result _features{};
+  std::vector<srrg2_keypoint> _keypoints;
 };
 
 // ---- binary descriptor database: the matching half of MultiLoopDetectorHBST_ --------------------------------------

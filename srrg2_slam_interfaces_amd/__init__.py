@@ -55,3 +55,10 @@ def MeasurementAdaptorLidarSweep(params=None):
     from .adaptors import MeasurementAdaptorLidarSweep as _A
 
     return _A(params)
+
+
+def MeasurementAdaptorImageFeatures(params=None, camera=None):
+    """8-bit intensity image (+ optional depth image) -> scene of keypoints with descriptors on the device; see ``adaptors``."""
+    from .adaptors import MeasurementAdaptorImageFeatures as _A
+
+    return _A(params, camera)

@@ -210,6 +210,25 @@ class AdaptResult(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class FeatureParams(C.Structure):
+    """srrg2_feature_params"""
+    _fields_ = [("fast_threshold", C.c_int32), ("max_features", C.c_int32), ("oriented", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Keypoint(C.Structure):
+    """srrg2_keypoint"""
+    _fields_ = [("pixel", C.c_int32), ("score", C.c_int32), ("angle_bin", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FeatureResult(C.Structure):
+    """srrg2_feature_result"""
+    _fields_ = [("status", C.c_int32), ("num_pixels", C.c_int32), ("num_candidates", C.c_int32), ("num_maxima", C.c_int32),
+                ("num_selected", C.c_int32), ("num_with_depth", C.c_int32), ("scene_size", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class NormalsParams(C.Structure):
     """srrg2_normals_params"""
     _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_int32), ("max_curvature", C.c_float), ("viewpoint", C.c_float * 3),

@@ -67,6 +67,13 @@ def lib():
         _LIB.srrg2_adapt_lidar_sweep_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                     C.POINTER(abi.LidarAdaptorParams), C.POINTER(abi.LidarSweepExtras),
                                                     C.POINTER(abi.AdaptResult)]
+        # srrg2_adapt_image_features (adaptors.MeasurementAdaptorImageFeatures), srrg2_feature_pattern
+        _LIB.srrg2_adapt_default_feature_params.argtypes = [C.POINTER(abi.FeatureParams)]
+        _LIB.srrg2_adapt_default_feature_params.restype = None
+        _LIB.srrg2_adapt_image_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                    C.POINTER(abi.DepthAdaptorParams), C.POINTER(abi.FeatureParams),
+                                                    C.POINTER(abi.Keypoint), C.c_int, C.POINTER(abi.FeatureResult)]
+        _LIB.srrg2_feature_pattern.argtypes = [C.c_int, C.POINTER(C.c_int8)]
         # srrg2_scene_clip_projective (mapping.SceneClipperProjective)
         from . import mapping
 

@@ -5,11 +5,13 @@
 ``MeasurementAdaptorLaserScan``    ranges -> 2-D scene with normals
 ``MeasurementAdaptorLidarSweep``   3-D lidar sweep (a list of points, + optional intensity) -> organised or compact 3-D scene
                                    with normals, through the range image of a spherical sensor model
+``MeasurementAdaptorImageFeatures`` 8-bit intensity image (+ optional depth image) -> compact 3-D scene of keypoints, each with
+                                   a 256-bit descriptor and an intensity (FAST corners, rotated-pair descriptors)
 
 Method names follow ``RawDataPreprocessor_`` (S/raw_data_preprocessors/raw_data_preprocessor.h:13-88), snake_case:
 ``set_raw_data``, ``set_meas``, ``compute``, ``status``, ``reset``; ``status()`` is ERROR after ``set_raw_data`` until
 ``compute()`` (:67-72).  Thin marshalling only; product library only (the oracle has no adaptor: the parity target is
-tests/adaptor_restatement.py and tests/lidar_restatement.py).
+tests/adaptor_restatement.py, tests/lidar_restatement.py and tests/features_restatement.py).
 """
 import ctypes as C
 
@@ -307,3 +309,84 @@ class MeasurementAdaptorLidarSweep(_AdaptorBase):
                                                       C.byref(x), res)
         self._check(rc)
         return self._finish(out, want_result)
+
+
+def default_feature_params():
+    """srrg2_feature_params: fast_threshold 20, max_features 1000, oriented 1"""
+    from . import _capi
+
+    p = abi.FeatureParams()
+    _capi.lib().srrg2_adapt_default_feature_params(C.byref(p))
+    return p
+
+
+def feature_pattern(angle_bin):
+    """srrg2_feature_pattern: the (256, 4) int8 point pairs (ax, ay, bx, by) of an orientation bin; needs no device"""
+    from . import _capi
+
+    out = np.zeros((256, 4), np.int8)
+    lib = _capi.lib()
+    if lib.srrg2_feature_pattern(int(angle_bin), out.ctypes.data_as(C.POINTER(C.c_int8))) != 0:
+        msg = lib.srrg2_amd_last_error()
+        raise ValueError(msg.decode() if msg else "feature_pattern")
+    return out
+
+
+class MeasurementAdaptorImageFeatures(_AdaptorBase):
+    """params: abi.FeatureParams (fast_threshold, max_features, oriented); camera: abi.DepthAdaptorParams, of which the
+    camera matrix and the depth scale / gates are read (rows / cols are taken from a numpy image).  compute() leaves a compact
+    scene of keypoints: point, 256-bit descriptor, intensity; global indices = pixel indices."""
+
+    def __init__(self, params=None, camera=None):
+        super().__init__()
+        self.params = params or default_feature_params()
+        self.camera = camera or default_depth_params()
+        self._raw = self._depth = None
+        self._keypoints = np.zeros((0, 4), np.int32)
+
+    def set_camera_matrix(self, K):
+        for i, v in enumerate(np.asarray(K, np.float32).reshape(9)):
+            self.camera.camera_matrix[i] = float(v)
+
+    def set_raw_data(self, intensity, depth=None, intensity_type=None, depth_type=None):
+        """intensity (uint8) and optionally depth (uint16 counts / float32 metres): 2-D numpy arrays, or
+        (device_pointer, row_stride_bytes) pairs with their abi.IMAGE_* type (then camera.rows / cols say the size)"""
+        raw = _image(intensity, intensity_type, "intensity")
+        dep = None if depth is None else _image(depth, depth_type, "depth")
+        if dep is not None and (dep[4] != raw[4] or (raw[5] is not None and dep[5] != raw[5])):
+            raise ValueError("depth: same memory space and shape as the intensity image expected")
+        self._raw, self._depth = raw, dep
+        if raw[5] is not None:
+            self.camera.rows, self.camera.cols = raw[5]
+        self._status = abi.ADAPTOR_ERROR
+
+    def reset(self):
+        self._raw = self._depth = None
+        self._status = abi.ADAPTOR_INITIALIZING
+        self.last = None
+        self._keypoints = np.zeros((0, 4), np.int32)
+
+    def compute(self, want_keypoints=True):
+        """fills the measurement scene; returns the counters of srrg2_feature_result (dict)"""
+        self._ready()
+        out = abi.FeatureResult()
+        _, iptr, itype, istride, mem, _ = self._raw
+        if self._depth is None:
+            dptr, dtype, dstride = None, abi.IMAGE_NONE, 0
+        else:
+            _, dptr, dtype, dstride, _, _ = self._depth
+        cap = 0
+        if want_keypoints:  # every selected keypoint fits: the cap, or every admissible pixel
+            inner = max(self.camera.rows - 32, 0) * max(self.camera.cols - 32, 0)
+            cap = min(inner, self.params.max_features) if self.params.max_features > 0 else inner
+        buf = np.zeros((max(cap, 1), 4), np.int32)
+        self._check(self._lib.srrg2_adapt_image_features(self._meas._h, iptr, itype, istride, dptr, dtype, dstride, mem,
+                                                         C.byref(self.camera), C.byref(self.params),
+                                                         buf.ctypes.data_as(C.POINTER(abi.Keypoint)) if cap > 0 else None, cap,
+                                                         C.byref(out)))
+        self._keypoints = buf[:min(out.scene_size, cap)]
+        return self._finish(out, True)
+
+    def keypoints(self):
+        """(n, 4) int32 rows of pixel, score, angle_bin, 0 of the last compute(), aligned with the scene's points"""
+        return self._keypoints

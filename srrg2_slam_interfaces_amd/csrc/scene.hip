@@ -824,6 +824,7 @@ int srrg2_scene_destroy(srrg2_scene_h s) {
   s->alt_pts.release(); s->alt_nrm.release(); s->nrm_sorted.release(); s->nrm_tmp.release(); s->alt_desc.release(); s->alt_inten.release();
   s->nrm_curv.release(); s->alt_gidx.release(); s->nrm_idx.release(); s->nrm_ctr.release(); s->nrm_keys.release();
   s->vox_acc.release(); s->vox_rep.release(); s->vox_rank.release(); s->vox_cnt.release(); s->vox_counts.release(); s->vox_pts.release(); s->vox_nrm.release();
+  s->feat_score.release(); s->feat_max.release(); s->feat_box.release(); s->feat_tie.release(); s->feat_ctr.release(); s->feat_pattern.release(); s->feat_kp.release();
   if (s->scalars) (void) hipHostFree(s->scalars);
   if (s->stream) (void) hipStreamDestroy(s->stream);
   delete s;

@@ -49,6 +49,15 @@ struct srrg2_scene {
   srrg2amd::DevBuf<long long> vox_acc;
   srrg2amd::DevBuf<int> vox_rep, vox_rank, vox_cnt, vox_counts;
   srrg2amd::DevBuf<float4> vox_pts, vox_nrm;
+  // adapt_image_features (features.hip): the U8 score and U16 box-sum images (padded to whole tiles), per pixel the maxima
+  // flag and the rank among the keypoints of the cut score, the counters + score histogram block, the 32 rotated patterns
+  // (uploaded once), per kept keypoint its record
+  srrg2amd::DevBuf<unsigned char> feat_score, feat_max;
+  srrg2amd::DevBuf<unsigned short> feat_box;
+  srrg2amd::DevBuf<int> feat_tie, feat_ctr;
+  srrg2amd::DevBuf<unsigned> feat_pattern;
+  srrg2amd::DevBuf<srrg2_keypoint> feat_kp;
+  bool feat_pattern_ready = false;
   int* scalars = nullptr;  // pinned host mirror of dscalars
   // device: [1] num_merged, [2] error flag, [3] duplicates seen, [4] ncorr (merge); [0] Valid, [1] in view, [2] scan total (clip);
   // [8] in range, [9] Valid (adapt)
