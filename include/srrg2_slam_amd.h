@@ -1108,8 +1108,12 @@ typedef struct srrg2_aligner_tuning {
   int32_t search_lists;         /* SRRG2_AMD_SEARCH_LISTS: search passes walk per-cell lists of occupied neighbour cells built
                                    once per fixed cloud (k_icp_step_cnl): 0 = never, 1 = batches of more than 4 alignments,
                                    2 = every alignment; -1 = automatic (carved out of reserved_: same struct size)        */
-  int32_t search_team;          /* SRRG2_AMD_SEARCH_TEAM: lanes per moving point of that kernel, 1 or 4; 0 = automatic (4 for up
-                                   to four alignments per launch, 1 for batches)                                         */
+  int32_t search_team;          /* SRRG2_AMD_SEARCH_TEAM: low byte = lanes per moving point of that kernel: 0 = automatic, 1, 2 or
+                                   4 = the most a point gets.  Launches of up to four alignments deal their points over
+                                   tiles of 4, 2 and 1 lanes per point so that the launch fits the workgroups that are
+                                   resident together (as many points as fit at the higher counts); larger batches take 4 or
+                                   1 for every point.  Bits 8 and up, when not zero: the number of resident workgroups
+                                   that plan assumes instead of the device's own (a sweep and test knob).  < 0: refused  */
   int32_t batch_pipeline;       /* SRRG2_AMD_BATCH_PIPELINE: compute_batch runs its alignments as P parts on P streams (one
                                    part's control steps and sort under the other parts' passes): 0 = never, 1 = two halves
                                    for every batch, 2 .. 8 = that many parts, -1 = automatic                             */

@@ -133,6 +133,7 @@ struct srrg2_aligner_s {
   static constexpr int MAX_PARTS = 8;
   hipStream_t pstream[MAX_PARTS]{};  // pstream[0] == stream
   int cu_count          = 256;       // compute units of the device (FusedCtl::first_round)
+  srrg2amd::SearchCapacity search_capacity;  // resident workgroups of the planned search passes, per instantiation (asked on first use)
   int fused_grid_max    = 130000;    // SRRG2_AMD_FUSED_GRID_MAX (read at create): largest cloud whose grid search passes drop the
                                      // deferred-search queue for the fused kernel (run_compute)
   hipEvent_t ev_staged  = nullptr;   // the staging copies of a batch upload (stream) before the other parts' sorts
@@ -1004,9 +1005,26 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   // lanes per moving point of that kernel: 1 = throughput, 4 = latency (a single alignment leaves the chip half empty and
   // its first pass, where every point searches without a bound, is a chain of dependent round trips: four lanes share a
   // point's headers and candidates: C2 55.7 -> 29.7 us; the passes with priors, where a fraction of the points search, are
-  // better off with one lane: 14.3 vs 18.3 us on the third pass); 0 = automatic: 4 on the first pass of up to four
-  // alignments per launch, 1 otherwise
-  const int search_team_knob = tn.search_team;
+  // better off with one lane: 14.3 vs 18.3 us on the third pass).  Launches of up to four alignments take more than one lane
+  // per point on the tiles of a launch plan (search_plan.h), so that the launch fits the workgroups resident together: 2 or 4 is
+  // then the CEILING, and the field's bits 8 and up, when not zero, are the workgroups the plan assumes instead of what the device
+  // reports (the sweep knob of the A/B).  0 = automatic, per pass what was measured fastest on a 100 k-point alignment (DESIGN
+  // section 5, "TEAM lanes per point"; profiles/r11): the most lanes EVERY point can have in one round, up to four on the first
+  // pass and two on the second -- at 100 k points two lanes on both, 782 workgroups: 25.7 us against 28.4 for four lanes on 1564
+  // workgroups in two rounds and 41 for a plan that mixes four-lane and one-lane tiles, whose one-lane tiles outlast everything
+  // else; 21.2 against 22.3-23.0 for one lane on the second pass.  The third pass alone is best off with one lane (16.3 against
+  // 16.9 us), but not behind a two-lane pass of a cloud whose first pass had two lanes as well: the tiles of consecutive passes
+  // then differ in size, a point's neighbour state is read by another workgroup than the one that wrote it, and the pass takes
+  // 18.6 us -- so it keeps the two lanes of the passes before it (all three on 782 tiles: 25.7 + 21.2 + 16.9 against the
+  // parent's 28.4 + 23.0 + 16.3).  One lane on every later search pass and for every launch of more than four alignments; a cloud
+  // too large for two lanes in one round keeps its uniform tiles, in rounds.
+  const int search_lanes_knob          = tn.search_team & 0xff;
+  const long long search_capacity_knob = tn.search_team >> 8;
+  int first_pass_lanes = 0;  // lanes per point the plan gave this compute()'s first pass (0: uniform tiles)
+  auto search_lanes_auto = [&](int run, int it) {
+    if (K > 4 || run != 0) return 1;
+    return it == 0 ? 4 : (it == 1 || (it == 2 && first_pass_lanes == 2)) ? 2 : 1;
+  };
   std::vector<char> cnl((size_t) std::max(nslices, 1), 0);
   std::vector<SliceDev> sdev((size_t) nslices);
   int first_cue = -1;
@@ -1618,10 +1636,19 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
             else if (fast)
               srrg2amd::launch_icp_step_fast(a->dim, plane, sd, pt, a->states.p, Kh, nm_max, fast_ppt_of(Kh), fast_gather, hs);
             else if (cnl[(size_t) si] && !sd.queue)
-              srrg2amd::launch_icp_step_cnl(a->dim, plane, sd, s->lists_host, pt, a->states.p, Kh, nm_max,
-                                            search_team_knob > 0 ? search_team_knob : ((K <= 4 && slot0 == 0 && it == 0) ? 4 : 1), hs,
-                                            first_pass_init ? &Ch[h] : nullptr, first_pass_init ? &fold_inl : nullptr,
-                                            first_pass_init && !fold_bat.empty() ? &fold_bat[(size_t) h] : nullptr);
+            {
+              // (up to four alignments: more than one lane per point only on the tiles of a launch plan, so that the launch fits
+              // the workgroups that are resident together; more alignments: uniform tiles as ever)
+              const int lanes = search_lanes_knob > 0 ? search_lanes_knob : search_lanes_auto(slot0, it);
+              const int plan_lanes = (K <= 4 && lanes > 1) ? (lanes >= 4 ? 4 : 2) : 0;
+              // (uniform tiles, where the plan does not apply: four lanes or one, as ever)
+              const int used = srrg2amd::launch_icp_step_cnl(
+                a->dim, plane, sd, s->lists_host, pt, a->states.p, Kh, nm_max, lanes >= 4 ? 4 : 1, hs,
+                first_pass_init ? &Ch[h] : nullptr, first_pass_init ? &fold_inl : nullptr,
+                first_pass_init && !fold_bat.empty() ? &fold_bat[(size_t) h] : nullptr, plan_lanes, search_lanes_knob == 0,
+                search_capacity_knob, &a->search_capacity);
+              if (slot0 == 0 && it == 0) first_pass_lanes = used;
+            }
             else if (!sd.queue && lds_tile > 0 && !small)
               srrg2amd::launch_icp_step_tile(a->dim, plane, sd, pt, a->states.p, Kh, nm_max, lds_tile == 2 ? 504 : 416, hs);
             else
@@ -1965,6 +1992,7 @@ int srrg2_aligner_create(int variable_kind, int device, srrg2_aligner_h* out) {
     (void) hipGetLastError();
     a->cu_count = 256;
   }
+  a->search_capacity.cu_count = a->cu_count;
   if (!ok) {
     for (int p = 0; p < srrg2_aligner::MAX_PARTS; ++p)
       if (a->pstream[p]) (void) hipStreamDestroy(a->pstream[p]);

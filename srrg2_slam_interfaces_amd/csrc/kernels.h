@@ -26,9 +26,19 @@ void launch_cnl_build(const GridDev& g, const GridLists& L, const int4* offs, in
 // search pass over the cell neighbour lists (any number of alignments per launch; no deferred-search queue)
 // (init_C / init_inl != null: the FIRST pass of a single alignment's compute() with the prologue inside -- no k_icp_init launch;
 // K == 1, fused control steps, the slot sets left zeroed by the previous compute()'s final step: run_compute decides)
-void launch_icp_step_cnl(int dim, bool plane, const SliceDev& S, const GridLists& GL, const ProblemDev* probs,
-                         ProblemState* states, int K, int max_nm, int team, hipStream_t s, const CtlParams* init_C = nullptr,
-                         const InitInline* init_inl = nullptr, const InitBatch* init_bat = nullptr);
+// (plan_lanes > 1, launches of up to four alignments: the tiles of a launch plan, search_plan.h, with at most that many lanes per
+// point, laid out for plan_capacity workgroups resident together -- 0: what the device holds of the instantiation, asked once
+// per handle and kept in `cap`; plan_whole: the automatic policy -- the most lanes every point can have in ONE round, and the
+// uniform tiles of `team` when not even two fit)
+struct SearchCapacity {
+  int cu_count = 256;
+  int blocks_per_cu[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};  // [plane][kind of pass kernel]; -1: not asked yet
+};
+// returns the most lanes per point of a planned launch, 0 for uniform tiles
+int launch_icp_step_cnl(int dim, bool plane, const SliceDev& S, const GridLists& GL, const ProblemDev* probs,
+                        ProblemState* states, int K, int max_nm, int team, hipStream_t s, const CtlParams* init_C = nullptr,
+                        const InitInline* init_inl = nullptr, const InitBatch* init_bat = nullptr, int plan_lanes = 0,
+                        bool plan_whole = false, long long plan_capacity = 0, SearchCapacity* cap = nullptr);
 // Morton sort of K moving clouds (counts/cursor: (K << kbits) + 1 ints; bb: K*6 keys initialised to
 // {0xffffffff x3, 0 x3}; counts zeroed)
 // kbits = total key bits (2^kbits cells per cloud); aniso != 0: bits dealt to the axes by extent (kernels_prep.hip: KeySpec);

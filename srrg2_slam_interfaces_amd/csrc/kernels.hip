@@ -14,10 +14,12 @@
 // order without FMA contraction (-ffp-contract=off), products widened to double, sums carried as
 // exact 64-bit fixed point so that the reduction order (lanes, waves, blocks, GPUs) cannot change
 // a single bit of H, b or the statistics.
+#include <climits>
 #include <cstdlib>
 #include <algorithm>
 
 #include "kernels.h"
+#include "search_plan.h"
 
 #include <type_traits>
 
@@ -2085,24 +2087,25 @@ __global__ __launch_bounds__(256) void k_icp_step_tile(SliceDev S, const Problem
 // its end: one plain store each (atomics on shared words serialise and stretch a 12-us launch to 85 us).  Compiled out of the
 // product build.
 #ifdef SRRG2_PASS_TIMELINE
-__device__ unsigned long long g_pass_ts[16 * 512 * 8];  // [epoch][workgroup (tile)][stamp]: plain stores, reduced on the host
+#define PASS_TS_WGS 2048  // (every workgroup of a 100 k-point search pass at four lanes per point: 1564; the last slot is the census')
+__device__ unsigned long long g_pass_ts[16 * PASS_TS_WGS * 8];  // [epoch][workgroup (tile)][stamp]: plain stores, reduced on the host
 #define PASS_TS_ANY(epoch, k) /* (by lane 0 of any wave: the last writer wins) */                      \
   do {                                                                                                 \
-    if ((threadIdx.x & 63) == 0 && (epoch) >= 0 && (epoch) < 16 && blockIdx.y < 512 && blockIdx.x == 0) \
-      g_pass_ts[(((epoch) * 512) + blockIdx.y) * 8 + (k)] = wall_clock64();                            \
+    if ((threadIdx.x & 63) == 0 && (epoch) >= 0 && (epoch) < 16 && blockIdx.y < PASS_TS_WGS - 1 && blockIdx.x == 0) \
+      g_pass_ts[(((epoch) * PASS_TS_WGS) + blockIdx.y) * 8 + (k)] = wall_clock64();                            \
   } while (0)
 #define PASS_TS_W(epoch, k, dep) /* (inside wave_control: after `dep` has been computed) */             \
   do {                                                                                                 \
     if (threadIdx.x == 0 && (epoch) >= 0 && (epoch) < 16 && blockIdx.x == 0) {                         \
       unsigned long long t_ = wall_clock64();                                                          \
       if ((dep) != (dep)) t_ = 0; /* (a data dependence: the stamp cannot be scheduled ahead) */        \
-      g_pass_ts[(((epoch) * 512) + 0) * 8 + (k)] = t_;                                                  \
+      g_pass_ts[(((epoch) * PASS_TS_WGS) + 0) * 8 + (k)] = t_;                                                  \
     }                                                                                                  \
   } while (0)
 #define PASS_TS(epoch, k)                                                                              \
   do {                                                                                                 \
-    if (threadIdx.x == 0 && (epoch) >= 0 && (epoch) < 16 && blockIdx.y < 512 && blockIdx.x == 0)       \
-      g_pass_ts[(((epoch) * 512) + blockIdx.y) * 8 + (k)] = wall_clock64();                            \
+    if (threadIdx.x == 0 && (epoch) >= 0 && (epoch) < 16 && blockIdx.y < PASS_TS_WGS - 1 && blockIdx.x == 0)       \
+      g_pass_ts[(((epoch) * PASS_TS_WGS) + blockIdx.y) * 8 + (k)] = wall_clock64();                            \
   } while (0)
 #else
 #define PASS_TS(epoch, k) do { } while (0)
@@ -3549,8 +3552,8 @@ __device__ __forceinline__ void icp_step_fast_body(const SliceDev& S, const Prob
 #ifdef SRRG2_PASS_TIMELINE
     if constexpr (FUSED) {
       if (active && !have && S.fc.epoch >= 0 && S.fc.epoch < 16 && blockIdx.x == 0) {
-        // census of the failed certificates: [epoch][499..511][5..7] of the stamp array are never stamped
-        unsigned long long* c = &g_pass_ts[((size_t) S.fc.epoch * 512 + 500) * 8];
+        // census of the failed certificates: the last workgroup slot of the epoch is never stamped
+        unsigned long long* c = &g_pass_ts[((size_t) S.fc.epoch * PASS_TS_WGS + PASS_TS_WGS - 1) * 8];
         const float gap = (pm[k] - d1) / g.h;  // margin left, in cells
         atomicAdd(&c[0], 1ull);
         if (!hasp) atomicAdd(&c[1], 1ull);
@@ -3718,10 +3721,14 @@ __global__ __launch_bounds__(256) void k_icp_step_fast_pairs(SliceDev S, const G
 // ============================================================================================
 // (FUSED: as k_icp_step_fast; 3 = the FIRST pass of a single alignment's compute() with the prologue inside, k_icp_step_cnl_init:
 // Ci / inl = the kernel's extra arguments, pass_view_init / fused_init_tail)
-template <int DIM, bool PLANE, int TEAM, int FUSED>
+// PLANNED: the waves' pools, the workgroup's tile and its first moving point come with the call (TilePlan: the tile's class
+// decides TEAM, the three bodies of a kernel share the pools); uniform tiles declare and derive them where they always did
+// (tile * 256 / TEAM: those kernels stay what they were).
+template <int DIM, bool PLANE, int TEAM, int FUSED, bool PLANNED = false>
 __device__ __forceinline__ void cnl_pass_body(const SliceDev& S, const GridLists& GL, const ProblemDev* __restrict__ probs,
                                               ProblemState* __restrict__ states, const CtlParams* Ci = nullptr,
-                                              const InitInline* inl = nullptr, const InitBatch* bat = nullptr) {
+                                              const InitInline* inl = nullptr, const InitBatch* bat = nullptr,
+                                              CnlWave* plan_wlds = nullptr, const int plan_tile = 0, const int plan_first = 0) {
   constexpr int NW  = 4;
   constexpr int PPB = NW * 64 / TEAM;  // moving points per workgroup
   const int prob    = (FUSED ? blockIdx.x : blockIdx.y) + S.prob0;  // (a launch may cover a sub-range of the batch: SliceDev::prob0)
@@ -3732,6 +3739,8 @@ __device__ __forceinline__ void cnl_pass_body(const SliceDev& S, const GridLists
   } else if constexpr (FUSED != 3) {
     PASS_TS(S.fc.epoch, 0);
     fused_control_if_due<DIM, FUSED == 2>(S, states, prob);
+  } else {
+    PASS_TS(S.fc.epoch, 0);
   }
   ProblemDev pd;
   if constexpr (FUSED == 3) {
@@ -3742,13 +3751,14 @@ __device__ __forceinline__ void cnl_pass_body(const SliceDev& S, const GridLists
   } else {
     pd = probs[prob];
   }
-  const int tile      = FUSED ? blockIdx.y : blockIdx.x;
+  const int tile      = PLANNED ? plan_tile : (int) (FUSED ? blockIdx.y : blockIdx.x);
+  const auto first_of = [&]() { return PLANNED ? plan_first : tile * PPB; };  // first moving point of the workgroup
   // (batches of unequal clouds; fused control steps: workgroup (0, problem) carries the control step of the previous
   // iteration whatever its share of the points.  FUSED = 3: no step is due; the launch has ONE workgroup more than tiles, which
   // holds no point and writes the rest of the prologue while the others run -- on workgroup 0 that tail sat on the launch's
   // critical path, ~3 us)
   const bool tail_wg = FUSED == 3 && tile == (int) gridDim.y - 1;
-  if (tile * PPB >= pd.nm && (!FUSED || (FUSED == 3 ? !tail_wg : tile != 0))) return;
+  if (first_of() >= pd.nm &&(!FUSED || (FUSED == 3 ? !tail_wg : tile != 0))) return;
   float T[12], Tprev[12];
   double scale;
   int rk;
@@ -3767,9 +3777,15 @@ __device__ __forceinline__ void cnl_pass_body(const SliceDev& S, const GridLists
   const GridDev& g   = S.grid;
   const float gfar = use_prior ? g.gate2_ext : g.gate2;
 
-  __shared__ CnlWave wlds[NW];
+  CnlWave* wlds;
+  if constexpr (PLANNED) {
+    wlds = plan_wlds;
+  } else {
+    __shared__ CnlWave own_wlds[NW];
+    wlds = own_wlds;
+  }
 
-  const int i        = tile * PPB + (int) threadIdx.x / TEAM;
+  const int i        = first_of() + (int) threadIdx.x / TEAM;
   const int lane     = threadIdx.x & 63;
   const int wid      = threadIdx.x >> 6;
   const bool leader  = (threadIdx.x & (TEAM - 1)) == 0;
@@ -3805,7 +3821,7 @@ __device__ __forceinline__ void cnl_pass_body(const SliceDev& S, const GridLists
     } else {
       pass_view_fused<DIM, FUSED == 2>(S, states, prob, pv);
     }
-    if (pv.stop || tile * PPB >= pd.nm) return;
+    if (pv.stop || first_of() >= pd.nm) return;
     load_T(pv.T, T);
     load_T(pv.Tprev, Tprev);
     scale = dm::pow2(pv.kexp);
@@ -3987,6 +4003,27 @@ __device__ __forceinline__ void cnl_pass_body(const SliceDev& S, const GridLists
   block_reduce_store_biased<NW>(acc, S.partials, prob, tile, 1);
   if constexpr (FUSED) PASS_TS(S.fc.epoch, 3);
 }
+// Launches of up to four alignments run on the tiles of a launch plan (search_plan.h) instead of uniform ones (TEAM = 1 | 4: 256 / TEAM
+// points per workgroup): the class of a tile, and with it the lanes per point, follows from the tile index, a workgroup-
+// uniform branch into the three bodies, which share one set of wave pools.  The slot sets, the control step's workgroup (problem,
+// tile 0) and the prologue's workgroup behind the last tile go by the tile index as before; everything per point goes by `first`.
+struct TilePlan {
+  int t4, t2;  // tiles [0, t4): 64 points at four lanes; [t4, t4 + t2): 128 points at two lanes; the rest: 256 points at one lane
+};
+template <int DIM, bool PLANE, int FUSED>
+__device__ __forceinline__ void cnl_pass_tiles(const SliceDev& S, const GridLists& GL, const ProblemDev* __restrict__ probs,
+                                               ProblemState* __restrict__ states, const TilePlan& plan, const CtlParams* Ci = nullptr,
+                                               const InitInline* inl = nullptr, const InitBatch* bat = nullptr) {
+  __shared__ CnlWave wlds[4];
+  const int tile = FUSED ? blockIdx.y : blockIdx.x;
+  const int t4 = plan.t4, t2 = plan.t2;
+  if (tile < t4)
+    cnl_pass_body<DIM, PLANE, 4, FUSED, true>(S, GL, probs, states, Ci, inl, bat, wlds, tile, tile * 64);
+  else if (tile < t4 + t2)
+    cnl_pass_body<DIM, PLANE, 2, FUSED, true>(S, GL, probs, states, Ci, inl, bat, wlds, tile, t4 * 64 + (tile - t4) * 128);
+  else
+    cnl_pass_body<DIM, PLANE, 1, FUSED, true>(S, GL, probs, states, Ci, inl, bat, wlds, tile, t4 * 64 + t2 * 128 + (tile - t4 - t2) * 256);
+}
 template <int DIM, bool PLANE, int TEAM, int FUSED>
 __global__ __launch_bounds__(256) void k_icp_step_cnl(SliceDev S, GridLists GL, const ProblemDev* __restrict__ probs,
                                                       ProblemState* __restrict__ states) {
@@ -4005,6 +4042,20 @@ __global__ __launch_bounds__(256) void k_icp_step_cnl_init_batch(SliceDev S, Gri
   const InitInline none{};
   cnl_pass_body<DIM, PLANE, TEAM, 3>(S, GL, probs, states, &C, &none, &B);
 }
+// ... the first two on the tiles of a launch plan (the boundaries arrive with the launch)
+template <int DIM, bool PLANE, int FUSED>
+__global__ __launch_bounds__(256) void k_icp_step_cnl_plan(SliceDev S, GridLists GL, const ProblemDev* __restrict__ probs,
+                                                           ProblemState* __restrict__ states, TilePlan plan) {
+  cnl_pass_tiles<DIM, PLANE, FUSED>(S, GL, probs, states, plan);
+}
+template <int DIM, bool PLANE>
+__global__ __launch_bounds__(256) void k_icp_step_cnl_init_plan(SliceDev S, GridLists GL, CtlParams C, InitInline inl,
+                                                                ProblemDev* __restrict__ probs, ProblemState* __restrict__ states,
+                                                                TilePlan plan) {
+  cnl_pass_tiles<DIM, PLANE, 3>(S, GL, probs, states, plan, &C, &inl);
+}
+// (k_icp_step_cnl_init_batch has no planned form: with the three bodies inside, the compiler copies the launch's table of guesses
+// to the stack, 1020 bytes of scratch per lane -- a part of a batch with the prologue in its first pass keeps its uniform tiles)
 
 // The correspondence records of the nearest-neighbour passes, on demand (get_correspondences, factor status, the scene
 // merger): slice->correspondences() and the factor statistics of the last linearisation (multi_aligner_impl.cpp:215,244)
@@ -5747,14 +5798,86 @@ void launch_icp_step_tile(int dim, bool plane, const SliceDev& S, const ProblemD
   });
 }
 
-// the search pass over the cell neighbour lists of the grid (S.grid.list_R > 0); team = lanes per moving point (1 or 4)
-void launch_icp_step_cnl(int dim, bool plane, const SliceDev& S, const GridLists& GL, const ProblemDev* probs,
-                         ProblemState* states, int K, int max_nm, int team, hipStream_t s, const CtlParams* init_C,
-                         const InitInline* init_inl, const InitBatch* init_bat) {
-  if (K <= 0) return;
+// Workgroups of a planned search pass that are resident together: the occupancy query per instantiation, once per handle
+// (SearchCapacity caches it), times the compute units.  kind: 0 .. 2 = k_icp_step_cnl_plan<.., FUSED>, 3 = k_icp_step_cnl_init_plan.
+// The query knows nothing of the scalar register file, which admits
+// floor(800 / (ceil(sgprs / 16) * 16 + 16)) workgroups of 256 threads per compute unit: one fewer than the query's answer for a
+// kernel of 82 to 98 scalar registers, never fewer than six.  The runtime does not tell a kernel's scalar registers, so an answer
+// above six is taken as one fewer: a plan that assumes too few resident workgroups only gives a few tiles fewer lanes per point,
+// one that assumes too many brings the second round back.
+static long long cnl_plan_capacity(int dim, bool plane, int kind, SearchCapacity& cap) {
+  int& per_cu = cap.blocks_per_cu[plane ? 1 : 0][kind];
+  if (per_cu < 0) {
+    int n = 0;
+    hipError_t e = hipErrorUnknown;
+    with_dim_plane(dim, plane, [&](auto D, auto P) {
+      if (kind == 3)
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_icp_step_cnl_init_plan<D(), P()>, 256, 0);
+      else if (kind == 2)
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_icp_step_cnl_plan<D(), P(), 2>, 256, 0);
+      else if (kind == 1)
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_icp_step_cnl_plan<D(), P(), 1>, 256, 0);
+      else
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_icp_step_cnl_plan<D(), P(), 0>, 256, 0);
+    });
+    if (e != hipSuccess) {
+      (void) hipGetLastError();
+      n = 0;  // (no answer: no plan, the one-lane layout)
+    }
+    per_cu = n > 6 ? n - 1 : n;
+  }
+  return (long long) per_cu * cap.cu_count;
+}
+
+// the search pass over the cell neighbour lists of the grid (S.grid.list_R > 0); team = lanes per moving point (1 or 4) on uniform
+// tiles; plan_lanes > 1 (launches of up to four alignments): the tiles of a launch plan with at most that many lanes per point
+// (search_plan.h) for plan_capacity resident workgroups (0: the device's, `cap`); plan_whole: only a plan that gives every point
+// the same lanes, else the uniform tiles
+int launch_icp_step_cnl(int dim, bool plane, const SliceDev& S, const GridLists& GL, const ProblemDev* probs,
+                        ProblemState* states, int K, int max_nm, int team, hipStream_t s, const CtlParams* init_C,
+                        const InitInline* init_inl, const InitBatch* init_bat, int plan_lanes, bool plan_whole,
+                        long long plan_capacity, SearchCapacity* cap) {
+  if (K <= 0) return 0;
   ProblemDev* pw = const_cast<ProblemDev*>(probs);  // (a pass with the prologue inside writes the problems)
   auto tiles_of = [&](auto TEAM) { return (max_nm * TEAM() + 255) / 256; };
-  if (S.fc.pub && init_C && init_bat) {  // a part of a batch (K <= INIT_BATCH_MAX alignments) with the prologue in its first pass
+  const bool init_b = S.fc.pub && init_C && init_bat, init_1 = S.fc.pub && init_C && !init_bat;
+  if (plan_lanes > 1 && cap && !init_b && (init_1 || max_nm > 0)) {
+    const int kind = init_1 ? 3 : (S.fc.pub && S.fc.prior_mask) ? 2 : S.fc.pub ? 1 : 0;
+    const long long resident = plan_capacity > 0 ? plan_capacity : cnl_plan_capacity(dim, plane, kind, *cap);
+    // (a first pass with the prologue inside has one workgroup more per alignment, which holds no tile; the tile index is
+    // gridDim.y <= 65535)
+    const long long room = std::min(resident - (kind == 3 ? K : 0), 65534ll * K);
+    SearchTiles t{0, 0, 0};
+    bool planned = true;
+    if (plan_whole) {
+      // (the automatic policy: the most lanes, up to plan_lanes, that EVERY point can have in one round -- a launch that mixes
+      // classes is as slow as its one-lane tiles, 41 us against 28 on the first pass of 100 k points; when not even two lanes fit,
+      // the uniform tiles of `team` below, in rounds, as ever)
+      planned = false;
+      for (int l = plan_lanes >= 4 ? 4 : 2; l > 1 && !planned; l >>= 1) {
+        t       = plan_search_tiles(max_nm, K, room, l);
+        planned = (l == 4 ? t.t2 + t.t1 : t.t4 + t.t1) == 0;
+      }
+    } else {
+      t = plan_search_tiles(max_nm, K, room, plan_lanes);
+    }
+    const TilePlan tp{t.t4, t.t2};
+    SliceDev Sp = S;
+    if (resident > 0 && resident < (long long) INT_MAX) Sp.fc.first_round = (int) resident;
+    if (planned) with_dim_plane(dim, plane, [&](auto D, auto P) {
+      if (kind == 3)
+        hipLaunchKernelGGL((k_icp_step_cnl_init_plan<D(), P()>), dim3(K, t.tiles() + 1), dim3(256), 0, s, Sp, GL, *init_C,
+                           *init_inl, pw, states, tp);
+      else if (kind == 2)
+        hipLaunchKernelGGL((k_icp_step_cnl_plan<D(), P(), 2>), dim3(K, t.tiles()), dim3(256), 0, s, Sp, GL, probs, states, tp);
+      else if (kind == 1)
+        hipLaunchKernelGGL((k_icp_step_cnl_plan<D(), P(), 1>), dim3(K, t.tiles()), dim3(256), 0, s, Sp, GL, probs, states, tp);
+      else
+        hipLaunchKernelGGL((k_icp_step_cnl_plan<D(), P(), 0>), dim3(t.tiles(), K), dim3(256), 0, s, Sp, GL, probs, states, tp);
+    });
+    if (planned) return t.t4 ? 4 : t.t2 ? 2 : 1;  // (the most lanes a point of the launch has)
+  }
+  if (init_b) {  // a part of a batch (K <= INIT_BATCH_MAX alignments) with the prologue in its first pass
     with_value<4, 1>(team >= 4, [&](auto TEAM) {
       const dim3 grid(K, tiles_of(TEAM) + 1);
       with_dim_plane(dim, plane, [&](auto D, auto P) {
@@ -5762,9 +5885,9 @@ void launch_icp_step_cnl(int dim, bool plane, const SliceDev& S, const GridLists
                            states);
       });
     });
-    return;
+    return 0;
   }
-  if (S.fc.pub && init_C) {  // the first pass of a single alignment with compute()'s prologue inside (even for an empty cloud)
+  if (init_1) {  // the first pass of a single alignment with compute()'s prologue inside (even for an empty cloud)
     with_value<4, 1>(team >= 4, [&](auto TEAM) {
       const dim3 grid(K, tiles_of(TEAM) + 1);  // (+ the workgroup that writes the rest of the prologue)
       with_dim_plane(dim, plane, [&](auto D, auto P) {
@@ -5772,9 +5895,9 @@ void launch_icp_step_cnl(int dim, bool plane, const SliceDev& S, const GridLists
                            states);
       });
     });
-    return;
+    return 0;
   }
-  if (max_nm <= 0) return;
+  if (max_nm <= 0) return 0;
   auto pass = [&](auto FUSED) __attribute__((always_inline)) {
     with_value<4, 1>(team >= 4, [&](auto TEAM) {
       const dim3 grid = FUSED() ? dim3(K, tiles_of(TEAM)) : dim3(tiles_of(TEAM), K);  // (fused: x = problem, y = tile)
@@ -5790,6 +5913,7 @@ void launch_icp_step_cnl(int dim, bool plane, const SliceDev& S, const GridLists
     pass(int_c<1>{});
   else
     pass(int_c<0>{});
+  return 0;
 }
 
 // the pass of a converged alignment; ppt = moving points per thread

@@ -3,7 +3,8 @@
   make -C srrg2_slam_interfaces_amd/csrc OUT=../lib/libsrrg2_slam_amd_timeline.so EXTRA=-DSRRG2_PASS_TIMELINE
   SRRG2_AMD_LIB=srrg2_slam_interfaces_amd/lib/libsrrg2_slam_amd_timeline.so python tools/pass_timeline.py [n]
 Per launch epoch: first / last workgroup start, control step done, record seen (first / last workgroup), first / last end,
-in microseconds after the end of the previous launch (100 MHz constant-rate clock: 10 ns steps)."""
+in microseconds after the end of the previous launch (100 MHz constant-rate clock: 10 ns steps), and how many workgroups
+started only after the first one had ended: the launch's second round, workgroups that were not resident at its start."""
 import ctypes as C
 import os
 import sys
@@ -32,7 +33,8 @@ c.robustifier, c.robustifier_chi_threshold = abi.ROBUST_CAUCHY, 0.05
 al.add_slice(c)
 al.set_fixed(0, pr["fixed"], pr.get("fixed_normals"))
 al.set_moving(0, pr["moving"], pr.get("moving_normals"))
-buf = (C.c_uint64 * (16 * 512 * 8))()
+WGS = 2048  # (PASS_TS_WGS of kernels.hip: every workgroup of the launch; the last slot holds the census)
+buf = (C.c_uint64 * (16 * WGS * 8))()
 for rep in range(4):  # (the second compute() builds the lists; the later ones run on them)
     if scan2d:
         al.set_fixed(0, pr["fixed"], pr.get("fixed_normals"))
@@ -40,24 +42,29 @@ for rep in range(4):  # (the second compute() builds the lists; the later ones r
     lib.srrg2_amd_debug_pass_timeline(buf, 1)
     al.compute()
 lib.srrg2_amd_debug_pass_timeline(buf, 0)
-ts = np.frombuffer(buf, dtype=np.uint64).reshape(16, 512, 8).astype(np.int64)
+ts = np.frombuffer(buf, dtype=np.uint64).reshape(16, WGS, 8).astype(np.int64)
 prev_end = None
 print("epoch | workgroups | start: first  last | control done | record seen: first  median  last | end: first  median  last | launch   [us after the end of the previous launch]")
 for e in range(16):
     used = ts[e, :, 0] > 0
-    used[500] = False
-    census = ts[e, 500, :7].copy()
+    used[WGS - 1] = False
+    census = ts[e, WGS - 1, :7].copy()
     if not used.any():
         continue
     st, ctl, seen, end = ts[e, used, 0], ts[e, 0, 1], ts[e, used, 2], ts[e, used, 3]
     seen, end = seen[seen > 0], end[end > 0]
     if not len(end):
         continue
+    if not len(seen):  # (a first pass with the prologue inside derives its record from the kernel arguments: no such stamp)
+        seen = st
     t0 = prev_end if prev_end is not None else st.min()
     f = lambda x: "%6.2f" % ((x - t0) / 100.0)
     print("%5d | %10d | %s  %s | %s | %s  %s  %s | %s  %s  %s | %6.2f" % (
         e, used.sum(), f(st.min()), f(st.max()), f(ctl) if ctl else "     -", f(seen.min()), f(np.median(seen)), f(seen.max()),
         f(end.min()), f(np.median(end)), f(end.max()), (end.max() - st.min()) / 100.0))
+    ended = ts[e, used, 3]
+    late = int((st > ended[ended > 0].min()).sum())
+    print("      %d of %d workgroups started after the first one had ended%s" % (late, used.sum(), " (a second round)" if late else ""))
     if ts[e, 0, 5] and ctl:
         print("      control step: sums and H / b in the lanes at %s, dx solved at %s, X and the transforms at %s, published at %s" % (f(ts[e, 0, 5]), f(ts[e, 0, 6]), f(ts[e, 0, 7]), f(ctl)))
     if census[0]:
