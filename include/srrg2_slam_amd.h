@@ -1069,6 +1069,65 @@ int srrg2_adapt_image_features(srrg2_scene_h dst /* dim 3 */, const void* intens
 /* the 256 point pairs (ax, ay, bx, by) of orientation bin 0 .. 31, rotated: 1024 values.  Needs no device. */
 int srrg2_feature_pattern(int angle_bin, int8_t* pairs_out);
 
+/* Stereo features: a rectified pair of 8-bit images -> a compact scene of matched, triangulated, described keypoints (the
+ * clouds of the reference's stereo pipeline, initializers/initializer_camera.h InitializerStereoCamera_).  No reference
+ * counterpart; DESIGN.md section 4 "Stereo features" is the contract, tests/stereo_restatement.py restates it and the library
+ * gives the same bits.
+ *   extract   each image alone goes through score, maxima, cap, angle and bits of srrg2_adapt_image_features with fp.  cam: rows,
+ *             cols, camera_matrix, depth_min, depth_max are read; both images have that shape and lie in `mem`.
+ *   candidates  of a left keypoint (r, cl): the right keypoints (rr, cr) with |rr - r| <= row_tolerance and d = cl - cr in
+ *             [min_disparity, max_disparity].
+ *   best      the candidate of smallest (Hamming distance h, right pixel index rr*cols + cr); accepted iff h <= max_distance.
+ *   cross     cross_check: the same rule from the right (candidates: left keypoints in the band with d in range, smallest
+ *             (h, left pixel index)); a left keypoint stays iff its best right keypoint's best is that left keypoint.
+ *   subpixel  integer costs cost(k) = sum over the 7x7 window of |L(r+dy, cl+dx) - R(rr+dy, cr+k+dx)|, k = -1, 0, 1;
+ *             D = cost(-1) - 2 cost(0) + cost(1); cost(0) <= both neighbours and D > 0: off = (float)(cost(-1) - cost(1)) /
+ *             (float)(2 D), else 0; disparity = (float) d - off.  subpixel 0: disparity = (float) d.
+ *   point     z = (fx * baseline) / disparity in float32; kept iff z is finite and depth_min <= z <= depth_max; the coordinates
+ *             are those of srrg2_adapt_image_features for the left pixel under an F32 depth image holding z there.
+ *   scene     dst (dim 3): the kept left keypoints in left pixel order, no normals, the left descriptor and the left pixel's
+ *             intensity as features, srrg2_scene_global_indices(dst) = left pixel indices.  keypoints_out / matches_out (host,
+ *             may be NULL) receive up to their capacity of records in the same order.
+ *   refused   what srrg2_adapt_image_features refuses for either image, with its codes; SRRG2_E_INVALID: a null sp, baseline
+ *             not finite or <= 0, min_disparity < 1, max_disparity < min_disparity, row_tolerance outside 0 .. 8, max_distance
+ *             outside 0 .. 256, cross_check or subpixel not 0 / 1, reserved != 0, a negative capacity.  dst is unchanged.
+ *   status    zero pixels: an empty scene, INITIALIZING.  Either side below 33: an empty scene, READY.
+ *   waits     TWO host waits in the middle: for both images' keypoint counts (both pipelines are queued before it) and for the
+ *             number of kept keypoints (it sizes dst); the call returns when dst and the records are complete.
+ * max_distance 48 and max_disparity 128 are UNTUNED defaults: nobody has derived or measured them. */
+typedef struct srrg2_stereo_params {
+  float baseline;        /* metres, finite, > 0: the right camera sits at +baseline along the left camera's x axis */
+  int32_t min_disparity; /* >= 1, default 1 */
+  int32_t max_disparity; /* >= min_disparity, default 128 (untuned) */
+  int32_t row_tolerance; /* 0 .. 8, default 1: |row_right - row_left| allowed (rectified pair) */
+  int32_t max_distance;  /* 0 .. 256, default 48 (untuned): largest accepted Hamming distance */
+  int32_t cross_check;   /* 0 | 1, default 1 */
+  int32_t subpixel;      /* 0 | 1, default 1 */
+  int32_t reserved;      /* 0 */
+} srrg2_stereo_params;
+typedef struct srrg2_stereo_match {
+  int32_t left_pixel, right_pixel, distance;
+  float disparity;
+} srrg2_stereo_match;
+typedef struct srrg2_stereo_result {
+  int32_t status;       /* srrg2_adaptor_status */
+  int32_t num_pixels;
+  int32_t num_left;     /* keypoints selected (after the cap) in the left image */
+  int32_t num_right;    /* ... in the right image */
+  int32_t num_matched;  /* left keypoints with a best right candidate inside all three gates */
+  int32_t num_mutual;   /* ... that survive the cross check (= num_matched when it is off) */
+  int32_t num_in_range; /* ... whose z lies in [depth_min, depth_max] */
+  int32_t scene_size;
+} srrg2_stereo_result;
+/* baseline 0 (the caller must set it), disparity 1 .. 128, row_tolerance 1, max_distance 48, cross_check 1, subpixel 1 */
+void srrg2_adapt_default_stereo_params(srrg2_stereo_params* p);
+int srrg2_adapt_stereo_features(srrg2_scene_h dst /* dim 3 */, const void* left, int left_row_stride_bytes, const void* right,
+                                int right_row_stride_bytes, int mem, const srrg2_depth_adaptor_params* cam,
+                                const srrg2_feature_params* fp, const srrg2_stereo_params* sp,
+                                srrg2_keypoint* keypoints_out /* host, may be NULL */, int keypoint_capacity,
+                                srrg2_stereo_match* matches_out /* host, may be NULL */, int match_capacity,
+                                srrg2_stereo_result* out /* may be NULL */);
+
 /* ---- strategy knobs (no reference counterpart) ----------------------------------------------------------------
  * Every setting gives the SAME results (indices, estimates, statistics bit for bit): the knobs choose between exact
  * strategies of the finder / reduction / control step.  A handle starts from srrg2_aligner_default_tuning() overridden

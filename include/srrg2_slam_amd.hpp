@@ -681,6 +681,7 @@ private:
 //   LaserScanAdaptor    ranges -> Scene<2> with normals
 //   LidarSweepAdaptor   3-D lidar sweep (point list, + intensity) -> Scene<3>, organised or compact, with normals
 //   ImageFeatureAdaptor 8-bit intensity image (+ depth image) -> Scene<3> of keypoints with descriptors and intensity
+//   StereoFeatureAdaptor rectified pair of 8-bit images -> Scene<3> of matched, triangulated keypoints with descriptors
 // setRawData / setMeas / compute / status / reset; status() is Error after setRawData until compute() (:67-72).  The raw
 // data is borrowed until compute() has run.  compute(false) asks for no counts: an organised adapt then only queues its work.
 class AdaptorBase_ {
@@ -881,6 +882,74 @@ private:
   bool _has_raw = false;
   srrg2_feature_result _features{};
   std::vector<srrg2_keypoint> _keypoints;
+};
+
+// a rectified pair of 8-bit images -> Scene<3> of the left image's keypoints that found their partner in the right image:
+// triangulated point, left descriptor, left intensity, no normals; globalIndices() = left pixel indices
+// (srrg2_adapt_stereo_features).  param: the per-image extraction; stereo: baseline (set it: the default 0 is refused), disparity
+// range, row tolerance, gates; camera: camera_matrix, rows, cols, depth_min, depth_max are read.  last() keeps status and
+// scene_size; result() has every counter, keypoints() and matches() the records in the scene's order.
+class StereoFeatureAdaptor : public AdaptorBase_ {
+public:
+  using MeasurementType = Scene<3>;
+  srrg2_feature_params param;
+  srrg2_stereo_params stereo;
+  srrg2_depth_adaptor_params camera;
+  StereoFeatureAdaptor() {
+    srrg2_adapt_default_feature_params(&param);
+    srrg2_adapt_default_stereo_params(&stereo);
+    srrg2_adapt_default_depth_params(&camera);
+  }
+  // images with a row stride in bytes, both of camera.rows x camera.cols and in the same memory
+  void setRawData(const uint8_t* left, int left_row_stride_bytes, const uint8_t* right, int right_row_stride_bytes,
+                  int mem = SRRG2_MEM_HOST) {
+    _left = left, _left_stride = left_row_stride_bytes;
+    _right = right, _right_stride = right_row_stride_bytes;
+    _mem = mem, _has_raw = true;
+    _status = Error;
+  }
+  void setMeas(MeasurementType* meas) { _meas = meas; }
+  void reset() {
+    _has_raw = false;
+    _status  = Initializing;
+    _keypoints.clear();
+    _matches.clear();
+  }
+  void compute() {
+    if (!_meas || !_has_raw) throw std::runtime_error("StereoFeatureAdaptor::compute|raw data or measurement not set");
+    // every left keypoint fits: the cap, or every admissible pixel
+    const long long inner = (long long) (camera.rows > 32 ? camera.rows - 32 : 0) * (long long) (camera.cols > 32 ? camera.cols - 32 : 0);
+    const long long want  = param.max_features > 0 && param.max_features < inner ? param.max_features : inner;
+    _keypoints.assign((size_t) (want > 0 ? want : 0), srrg2_keypoint{});
+    _matches.assign(_keypoints.size(), srrg2_stereo_match{});
+    _result = srrg2_stereo_result{};
+    const int rc = srrg2_adapt_stereo_features(_meas->handle(), _left, _left_stride, _right, _right_stride, _mem, &camera, &param,
+                                               &stereo, _keypoints.empty() ? nullptr : _keypoints.data(), (int) _keypoints.size(),
+                                               _matches.empty() ? nullptr : _matches.data(), (int) _matches.size(), &_result);
+    if (rc != 0) _keypoints.clear(), _matches.clear();
+    _last            = srrg2_adapt_result{};
+    _last.status     = _result.status;
+    _last.num_raw    = _result.num_pixels;
+    _last.num_valid  = _result.scene_size;
+    _last.scene_size = _result.scene_size;
+    finish(rc, true);
+    const size_t got = (size_t) _result.scene_size < _keypoints.size() ? (size_t) _result.scene_size : _keypoints.size();
+    _keypoints.resize(got);
+    _matches.resize(got);
+  }
+  const srrg2_stereo_result& result() const { return _result; }
+  const std::vector<srrg2_keypoint>& keypoints() const { return _keypoints; }
+  const std::vector<srrg2_stereo_match>& matches() const { return _matches; }
+
+private:
+  MeasurementType* _meas = nullptr;
+  const uint8_t* _left   = nullptr;
+  const uint8_t* _right  = nullptr;
+  int _left_stride = 0, _right_stride = 0, _mem = SRRG2_MEM_HOST;
+  bool _has_raw = false;
+  srrg2_stereo_result _result{};
+  std::vector<srrg2_keypoint> _keypoints;
+  std::vector<srrg2_stereo_match> _matches;
 };
 
 // ---- binary descriptor database: the matching half of MultiLoopDetectorHBST_ --------------------------------------

@@ -62,3 +62,11 @@ def MeasurementAdaptorImageFeatures(params=None, camera=None):
     from .adaptors import MeasurementAdaptorImageFeatures as _A
 
     return _A(params, camera)
+
+
+def MeasurementAdaptorStereoFeatures(params=None, stereo=None, camera=None):
+    """Rectified pair of 8-bit images -> scene of matched, triangulated keypoints with descriptors on the device; see
+    ``adaptors``."""
+    from .adaptors import MeasurementAdaptorStereoFeatures as _A
+
+    return _A(params, stereo, camera)

@@ -229,6 +229,26 @@ class FeatureResult(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class StereoParams(C.Structure):
+    """srrg2_stereo_params"""
+    _fields_ = [("baseline", C.c_float), ("min_disparity", C.c_int32), ("max_disparity", C.c_int32), ("row_tolerance", C.c_int32),
+                ("max_distance", C.c_int32), ("cross_check", C.c_int32), ("subpixel", C.c_int32), ("reserved", C.c_int32)]
+
+
+class StereoMatch(C.Structure):
+    """srrg2_stereo_match"""
+    _fields_ = [("left_pixel", C.c_int32), ("right_pixel", C.c_int32), ("distance", C.c_int32), ("disparity", C.c_float)]
+
+
+class StereoResult(C.Structure):
+    """srrg2_stereo_result"""
+    _fields_ = [("status", C.c_int32), ("num_pixels", C.c_int32), ("num_left", C.c_int32), ("num_right", C.c_int32),
+                ("num_matched", C.c_int32), ("num_mutual", C.c_int32), ("num_in_range", C.c_int32), ("scene_size", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class NormalsParams(C.Structure):
     """srrg2_normals_params"""
     _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_int32), ("max_curvature", C.c_float), ("viewpoint", C.c_float * 3),

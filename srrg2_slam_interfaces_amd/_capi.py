@@ -74,6 +74,13 @@ def lib():
                                                     C.POINTER(abi.DepthAdaptorParams), C.POINTER(abi.FeatureParams),
                                                     C.POINTER(abi.Keypoint), C.c_int, C.POINTER(abi.FeatureResult)]
         _LIB.srrg2_feature_pattern.argtypes = [C.c_int, C.POINTER(C.c_int8)]
+        # srrg2_adapt_stereo_features (adaptors.MeasurementAdaptorStereoFeatures)
+        _LIB.srrg2_adapt_default_stereo_params.argtypes = [C.POINTER(abi.StereoParams)]
+        _LIB.srrg2_adapt_default_stereo_params.restype = None
+        _LIB.srrg2_adapt_stereo_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                     C.POINTER(abi.DepthAdaptorParams), C.POINTER(abi.FeatureParams),
+                                                     C.POINTER(abi.StereoParams), C.POINTER(abi.Keypoint), C.c_int,
+                                                     C.POINTER(abi.StereoMatch), C.c_int, C.POINTER(abi.StereoResult)]
         # srrg2_scene_clip_projective (mapping.SceneClipperProjective)
         from . import mapping
 

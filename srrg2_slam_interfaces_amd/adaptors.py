@@ -7,11 +7,13 @@
                                    with normals, through the range image of a spherical sensor model
 ``MeasurementAdaptorImageFeatures`` 8-bit intensity image (+ optional depth image) -> compact 3-D scene of keypoints, each with
                                    a 256-bit descriptor and an intensity (FAST corners, rotated-pair descriptors)
+``MeasurementAdaptorStereoFeatures`` rectified pair of 8-bit images -> compact 3-D scene of the left image's keypoints that were
+                                   matched in the right image, triangulated (z = fx * baseline / disparity)
 
 Method names follow ``RawDataPreprocessor_`` (S/raw_data_preprocessors/raw_data_preprocessor.h:13-88), snake_case:
 ``set_raw_data``, ``set_meas``, ``compute``, ``status``, ``reset``; ``status()`` is ERROR after ``set_raw_data`` until
 ``compute()`` (:67-72).  Thin marshalling only; product library only (the oracle has no adaptor: the parity target is
-tests/adaptor_restatement.py, tests/lidar_restatement.py and tests/features_restatement.py).
+tests/adaptor_restatement.py, tests/lidar_restatement.py, tests/features_restatement.py and tests/stereo_restatement.py).
 """
 import ctypes as C
 
@@ -390,3 +392,85 @@ class MeasurementAdaptorImageFeatures(_AdaptorBase):
     def keypoints(self):
         """(n, 4) int32 rows of pixel, score, angle_bin, 0 of the last compute(), aligned with the scene's points"""
         return self._keypoints
+
+
+def default_stereo_params():
+    """srrg2_stereo_params: baseline 0 (set it), disparity 1 .. 128, row_tolerance 1, max_distance 48, cross_check 1, subpixel 1"""
+    from . import _capi
+
+    p = abi.StereoParams()
+    _capi.lib().srrg2_adapt_default_stereo_params(C.byref(p))
+    return p
+
+
+MATCH_DTYPE = np.dtype([("left_pixel", np.int32), ("right_pixel", np.int32), ("distance", np.int32), ("disparity", np.float32)])
+
+
+class MeasurementAdaptorStereoFeatures(_AdaptorBase):
+    """params: abi.FeatureParams (per image); stereo: abi.StereoParams (baseline, disparity range, row tolerance, gates);
+    camera: abi.DepthAdaptorParams, of which the camera matrix and depth_min / depth_max are read (rows / cols are taken from
+    numpy images).  compute() leaves a compact scene of the left image's matched keypoints: triangulated point, left
+    descriptor, left intensity; global indices = left pixel indices."""
+
+    def __init__(self, params=None, stereo=None, camera=None):
+        super().__init__()
+        self.params = params or default_feature_params()
+        self.stereo = stereo or default_stereo_params()
+        self.camera = camera or default_depth_params()
+        self._raw = self._right = None
+        self._keypoints = np.zeros((0, 4), np.int32)
+        self._matches = np.zeros(0, MATCH_DTYPE)
+
+    def set_camera_matrix(self, K):
+        for i, v in enumerate(np.asarray(K, np.float32).reshape(9)):
+            self.camera.camera_matrix[i] = float(v)
+
+    def set_raw_data(self, left, right):
+        """the rectified pair (uint8): 2-D numpy arrays of one shape, or (device_pointer, row_stride_bytes) pairs (then
+        camera.rows / cols say the size)"""
+        raw = _image(left, abi.IMAGE_U8, "left")
+        other = _image(right, abi.IMAGE_U8, "right")
+        if raw[2] != abi.IMAGE_U8 or other[2] != abi.IMAGE_U8:
+            raise ValueError("left / right: uint8 images expected")
+        if other[4] != raw[4] or other[5] != raw[5]:
+            raise ValueError("right: same memory space and shape as the left image expected")
+        self._raw, self._right = raw, other
+        if raw[5] is not None:
+            self.camera.rows, self.camera.cols = raw[5]
+        self._status = abi.ADAPTOR_ERROR
+
+    def reset(self):
+        self._raw = self._right = None
+        self._status = abi.ADAPTOR_INITIALIZING
+        self.last = None
+        self._keypoints = np.zeros((0, 4), np.int32)
+        self._matches = np.zeros(0, MATCH_DTYPE)
+
+    def compute(self, want_records=True):
+        """fills the measurement scene; returns the counters of srrg2_stereo_result (dict)"""
+        self._ready()
+        out = abi.StereoResult()
+        _, lptr, _, lstride, mem, _ = self._raw
+        _, rptr, _, rstride, _, _ = self._right
+        cap = 0
+        if want_records:  # every left keypoint fits: the cap, or every admissible pixel
+            inner = max(self.camera.rows - 32, 0) * max(self.camera.cols - 32, 0)
+            cap = min(inner, self.params.max_features) if self.params.max_features > 0 else inner
+        kps = np.zeros((max(cap, 1), 4), np.int32)
+        ms = np.zeros(max(cap, 1), MATCH_DTYPE)
+        self._check(self._lib.srrg2_adapt_stereo_features(self._meas._h, lptr, lstride, rptr, rstride, mem, C.byref(self.camera),
+                                                          C.byref(self.params), C.byref(self.stereo),
+                                                          kps.ctypes.data_as(C.POINTER(abi.Keypoint)) if cap > 0 else None, cap,
+                                                          ms.ctypes.data_as(C.POINTER(abi.StereoMatch)) if cap > 0 else None, cap,
+                                                          C.byref(out)))
+        got = min(out.scene_size, cap)
+        self._keypoints, self._matches = kps[:got], ms[:got]
+        return self._finish(out, True)
+
+    def keypoints(self):
+        """(n, 4) int32 rows of left pixel, score, angle_bin, 0 of the last compute(), aligned with the scene's points"""
+        return self._keypoints
+
+    def matches(self):
+        """(n,) structured array (left_pixel, right_pixel, distance, disparity) of the last compute(), in the scene's order"""
+        return self._matches

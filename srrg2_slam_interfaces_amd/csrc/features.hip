@@ -14,6 +14,8 @@
 //   k_feat_scatter     kept pixel -> its slot's global index
 //   k_feat_describe    one wave per keypoint: disc moments lane-strided + wave reduction, 32 projections on 32 lanes + argmax,
 //                      4 x 64 comparisons assembled with __ballot; lane 0 writes point, intensity and the keypoint record
+// The pipeline is queued in two halves (features_pipeline.h: select, describe) on buffers the caller names, so that stereo.hip
+// runs it on two images behind one wait; srrg2_adapt_image_features hands it the scene's own arrays.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -21,6 +23,7 @@
 #include <cstring>
 #include <string>
 
+#include "features_pipeline.h"
 #include "host_util.h"
 #include "kernels.h"
 #include "scene_state.h"
@@ -29,10 +32,11 @@ using srrg2amd::fail;
 
 namespace {
 
-enum { MARGIN = 16, TILE_W = 64, TILE_H = 16, LDS_ROWS = TILE_H + 6, LDS_WORDS = (TILE_W + 8) / 4 };
-// counters block (ints): [0] candidates, [1] maxima, [2] selected, [3] s*, [4] ties kept, [5] ties seen (the scan's total);
-// the score histogram of the keypoints behind them
-enum { C_CANDIDATES = 0, C_MAXIMA = 1, C_SELECTED = 2, C_CUT = 3, C_QUOTA = 4, C_TIES = 5, C_HIST = 16, C_WORDS = C_HIST + 256 };
+enum { MARGIN = srrg2amd::FEAT_MARGIN, TILE_W = 64, TILE_H = 16, LDS_ROWS = TILE_H + 6, LDS_WORDS = (TILE_W + 8) / 4 };
+// counters block (features_pipeline.h)
+enum { C_CANDIDATES = srrg2amd::FEAT_C_CANDIDATES, C_MAXIMA = srrg2amd::FEAT_C_MAXIMA, C_SELECTED = srrg2amd::FEAT_C_SELECTED,
+       C_CUT = srrg2amd::FEAT_C_CUT, C_QUOTA = srrg2amd::FEAT_C_QUOTA, C_TIES = srrg2amd::FEAT_C_TIES, C_HIST = srrg2amd::FEAT_C_HIST,
+       C_WORDS = srrg2amd::FEAT_C_WORDS };
 
 // round(16384 cos(2 pi k / 32)); the sine is the cosine a quarter turn back
 #define FEAT_COS_TABLE                                                                                                         \
@@ -41,38 +45,8 @@ enum { C_CANDIDATES = 0, C_MAXIMA = 1, C_SELECTED = 2, C_CUT = 3, C_QUOTA = 4, C
 __constant__ int kCos[32] = FEAT_COS_TABLE;  // the kernels' copy
 const int kCosHost[32]    = FEAT_COS_TABLE;  // the pattern's (host)
 
-struct Image {
-  const unsigned char* p;
-  long long stride;  // bytes per row
-  int rows, cols;
-};
-
-// the keypoint's own depth pixel and the pinhole model (the arithmetic of DepthSource in adaptor.hip, expression for expression)
-struct DepthView {
-  const unsigned char* p;  // null: no depth image, z = 1
-  long long stride;
-  int f32;  // F32 metres (else U16 counts)
-  float ifx, ify, cx, cy, scale, zmin, zmax;
-
-  __device__ __forceinline__ bool depth_at(int r, int c, float& z) const {
-    if (!p) {
-      z = 1.f;
-      return true;
-    }
-    const unsigned char* at = p + (long long) r * stride;
-    if (f32) {
-      z = reinterpret_cast<const float*>(at)[c];
-    } else {
-      const uint16_t raw = reinterpret_cast<const uint16_t*>(at)[c];
-      if (raw == (uint16_t) 0) return false;
-      z = (float) raw * scale;
-    }
-    return isfinite(z) && zmin <= z && z <= zmax;
-  }
-  __device__ __forceinline__ float3 point_at(int r, int c, float z) const {
-    return make_float3((((float) c - cx) * ifx) * z, (((float) r - cy) * ify) * z, z);
-  }
-};
+using Image     = srrg2amd::FeatImage;
+using DepthView = srrg2amd::FeatDepth;
 
 // byte `off` (-4 .. 7, relative to the thread's first pixel) of a 12-byte row held in three words; off is a constant after unrolling
 __device__ __forceinline__ int row_byte(const unsigned (&w)[3], int off) {
@@ -314,12 +288,14 @@ __global__ __launch_bounds__(256) void k_feat_describe(Image I, const unsigned c
   }
   if (lane < 4) desc[(size_t) k * 4 + lane] = word;
   if (lane == 0) {
-    float z = 1.f;
-    D.depth_at(r, c, z);  // (in range: k_feat_select kept the pixel)
-    const float3 q = D.point_at(r, c, z);
-    pts[k]   = make_float4(q.x, q.y, q.z, 0.f);
-    nrm[k]   = make_float4(0.f, 0.f, 0.f, 0.f);
-    inten[k] = (float) I.p[(long long) r * I.stride + c];
+    if (pts) {  // (null: the caller makes the point itself, stereo.hip)
+      float z = 1.f;
+      D.depth_at(r, c, z);  // (in range: k_feat_select kept the pixel)
+      const float3 q = D.point_at(r, c, z);
+      pts[k]   = make_float4(q.x, q.y, q.z, 0.f);
+      nrm[k]   = make_float4(0.f, 0.f, 0.f, 0.f);
+      inten[k] = (float) I.p[(long long) r * I.stride + c];
+    }
     srrg2_keypoint kp;
     kp.pixel = pixel, kp.score = score[(size_t) r * pitch + c], kp.angle_bin = bin, kp.reserved = 0;
     kps[k] = kp;
@@ -377,8 +353,10 @@ bool aligned_to(const void* p, long long stride, int elem) {
   return reinterpret_cast<uintptr_t>(p) % (uintptr_t) elem == 0 && stride % elem == 0;
 }
 
+}  // namespace
+
 // dst becomes an empty feature scene (arrays for one point, as the adaptors leave them)
-int empty_scene(srrg2_scene* s) {
+int srrg2amd::feat_empty_scene(srrg2_scene* s) {
   int rc;
   s->has_desc = s->has_inten = true;
   if ((rc = srrg2amd::scene_make_room(s, 1, 0)) || (rc = s->gidx.reserve(1))) return rc;
@@ -387,7 +365,70 @@ int empty_scene(srrg2_scene* s) {
   return 0;
 }
 
-}  // namespace
+int srrg2amd::feat_check_params(const std::string& who, const srrg2_depth_adaptor_params* cam, const srrg2_feature_params* p,
+                                int keypoint_capacity) {
+  if (cam->rows < 0 || cam->cols < 0 || (long long) cam->rows * (long long) cam->cols > 0x7fffffffLL)
+    return fail(SRRG2_E_INVALID, who + "rows, cols >= 0 and rows*cols within int32");
+  if (p->fast_threshold < 0 || p->fast_threshold > 254) return fail(SRRG2_E_INVALID, who + "fast_threshold 0 .. 254");
+  if (p->max_features < 0) return fail(SRRG2_E_INVALID, who + "max_features >= 0");
+  if (p->oriented != 0 && p->oriented != 1) return fail(SRRG2_E_INVALID, who + "oriented must be 0 or 1");
+  if (p->reserved != 0) return fail(SRRG2_E_INVALID, who + "reserved must be 0");
+  if (keypoint_capacity < 0) return fail(SRRG2_E_INVALID, who + "keypoint_capacity >= 0");
+  const float fx = cam->camera_matrix[0], fy = cam->camera_matrix[4];
+  if (!std::isfinite(fx) || !std::isfinite(fy) || fx == 0.f || fy == 0.f)
+    return fail(SRRG2_E_INVALID, who + "fx and fy must be finite and non-zero");
+  if (cam->camera_matrix[1] != 0.f) return fail(SRRG2_E_UNSUPPORTED, who + "a camera matrix with skew (K[0][1] != 0)");
+  return 0;
+}
+
+size_t srrg2amd::feat_padded_pixels(int rows, int cols) {
+  const int tiles_x = (cols + TILE_W - 1) / TILE_W, tiles_y = (rows + TILE_H - 1) / TILE_H;
+  return (size_t) (tiles_x * TILE_W) * (size_t) (tiles_y * TILE_H);
+}
+
+int srrg2amd::feat_pattern_upload(srrg2_scene* s) {
+  if (s->feat_pattern_ready) return 0;
+  int rc;
+  if ((rc = s->feat_pattern.reserve(32 * 256))) return rc;
+  int8_t all[32][1024];
+  for (int b = 0; b < 32; ++b) pattern().rotated(b, all[b]);
+  HIP_TRY(hipMemcpyAsync(s->feat_pattern.p, all, sizeof(all), hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));  // (`all` leaves the stack)
+  s->feat_pattern_ready = true;
+  return 0;
+}
+
+int srrg2amd::feat_queue_select(const FeatImage& I, const FeatDepth& D, int fast_threshold, int max_features, const FeatWork& w,
+                                hipStream_t st) {
+  const int rows = I.rows, cols = I.cols, n = rows * cols;
+  const int tiles_x = (cols + TILE_W - 1) / TILE_W, tiles_y = (rows + TILE_H - 1) / TILE_H;
+  const int pitch = tiles_x * TILE_W;
+  int* const ctr  = w.ctr;
+  HIP_TRY(hipMemsetAsync(ctr, 0, C_WORDS * sizeof(int), st));
+  const int word_reads = reinterpret_cast<uintptr_t>(I.p) % 4 == 0 && I.stride % 4 == 0;
+  hipLaunchKernelGGL(k_feat_score_box, dim3(tiles_x, tiles_y), dim3(256), 0, st, I, word_reads, reinterpret_cast<unsigned*>(w.score),
+                     reinterpret_cast<uint2*>(w.box), pitch);
+  hipLaunchKernelGGL(k_feat_maxima, dim3((unsigned) (((long long) n + 255) / 256)), dim3(256), 0, st, w.score, pitch, rows, cols,
+                     fast_threshold, w.is_max, ctr);
+  hipLaunchKernelGGL(k_feat_cut, dim3(1), dim3(64), 0, st, max_features, ctr);
+  const dim3 grid(blocks_of(n)), block(256);
+  hipLaunchKernelGGL(k_feat_tie, grid, block, 0, st, w.score, pitch, cols, n, w.is_max, ctr, w.tie);
+  srrg2amd::launch_exclusive_scan(w.tie, n, w.scan_sums, ctr + C_TIES, st);
+  hipLaunchKernelGGL(k_feat_select, grid, block, 0, st, w.score, pitch, cols, n, w.is_max, w.tie, D, w.flags, ctr);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int srrg2amd::feat_queue_describe(const FeatImage& I, const FeatDepth& D, int oriented, const FeatWork& w, const unsigned* pattern,
+                                  int total, const FeatOut& o, hipStream_t st) {
+  const int n     = I.rows * I.cols;
+  const int pitch = (I.cols + TILE_W - 1) / TILE_W * TILE_W;
+  hipLaunchKernelGGL(k_feat_scatter, dim3(blocks_of(n)), dim3(256), 0, st, n, w.flags, total, o.gidx);
+  hipLaunchKernelGGL(k_feat_describe, dim3((total + 3) / 4), dim3(256), 0, st, I, w.score, w.box, pitch, pattern, D, oriented, o.gidx,
+                     total, o.pts, o.nrm, o.inten, o.desc, o.kps);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
 
 extern "C" void srrg2_adapt_default_feature_params(srrg2_feature_params* p) {
   if (!p) return;
@@ -408,6 +449,7 @@ extern "C" int srrg2_adapt_image_features(srrg2_scene_h dst, const void* intensi
                                           const srrg2_depth_adaptor_params* cam, const srrg2_feature_params* p,
                                           srrg2_keypoint* keypoints_out, int keypoint_capacity, srrg2_feature_result* out) {
   const std::string who = "adapt_image_features: ";
+  int rc;
   if (!dst || !cam || !p) return fail(SRRG2_E_INVALID, who + "null scene or params");
   if (dst->dim != 3) return fail(SRRG2_E_INVALID, who + "the scene must have dim 3");
   if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, who + "bad mem");
@@ -418,17 +460,8 @@ extern "C" int srrg2_adapt_image_features(srrg2_scene_h dst, const void* intensi
     return fail(SRRG2_E_INVALID, who + "depth_type must be NONE, U16 or F32");
   if ((depth != nullptr) != (depth_type != SRRG2_IMAGE_NONE) && (depth || cam->rows * (long long) cam->cols > 0))
     return fail(SRRG2_E_INVALID, who + "a depth image needs depth_type U16 or F32, and a depth_type its image");
-  if (cam->rows < 0 || cam->cols < 0 || (long long) cam->rows * (long long) cam->cols > 0x7fffffffLL)
-    return fail(SRRG2_E_INVALID, who + "rows, cols >= 0 and rows*cols within int32");
-  if (p->fast_threshold < 0 || p->fast_threshold > 254) return fail(SRRG2_E_INVALID, who + "fast_threshold 0 .. 254");
-  if (p->max_features < 0) return fail(SRRG2_E_INVALID, who + "max_features >= 0");
-  if (p->oriented != 0 && p->oriented != 1) return fail(SRRG2_E_INVALID, who + "oriented must be 0 or 1");
-  if (p->reserved != 0) return fail(SRRG2_E_INVALID, who + "reserved must be 0");
-  if (keypoint_capacity < 0) return fail(SRRG2_E_INVALID, who + "keypoint_capacity >= 0");
+  if ((rc = srrg2amd::feat_check_params(who, cam, p, keypoint_capacity))) return rc;
   const float fx = cam->camera_matrix[0], fy = cam->camera_matrix[4];
-  if (!std::isfinite(fx) || !std::isfinite(fy) || fx == 0.f || fy == 0.f)
-    return fail(SRRG2_E_INVALID, who + "fx and fy must be finite and non-zero");
-  if (cam->camera_matrix[1] != 0.f) return fail(SRRG2_E_UNSUPPORTED, who + "a camera matrix with skew (K[0][1] != 0)");
   const int rows = cam->rows, cols = cam->cols;
   const int n = rows * cols;
   const bool with_depth = depth != nullptr;
@@ -439,7 +472,6 @@ extern "C" int srrg2_adapt_image_features(srrg2_scene_h dst, const void* intensi
     if (with_depth && ((long long) depth_stride < (long long) cols * de || !aligned_to(depth, depth_stride, de)))
       return fail(SRRG2_E_INVALID, who + "depth row stride smaller than a row, or image not aligned to its element");
   }
-  int rc;
   srrg2_scene* const s = dst;
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = s->stream;
@@ -452,7 +484,7 @@ extern "C" int srrg2_adapt_image_features(srrg2_scene_h dst, const void* intensi
     out->status     = n == 0 ? SRRG2_ADAPTOR_INITIALIZING : SRRG2_ADAPTOR_READY;
     out->num_pixels = n;
   }
-  if (rows <= 2 * MARGIN || cols <= 2 * MARGIN) return empty_scene(s);  // no pixel 16 away from every border
+  if (rows <= 2 * MARGIN || cols <= 2 * MARGIN) return srrg2amd::feat_empty_scene(s);  // no pixel 16 away from every border
 
   Image I{static_cast<const unsigned char*>(intensity), (long long) intensity_stride, rows, cols};
   DepthView D;
@@ -475,35 +507,15 @@ extern "C" int srrg2_adapt_image_features(srrg2_scene_h dst, const void* intensi
       D.p = reinterpret_cast<const unsigned char*>(s->staging.p + off_d);
     }
   }
-  const int tiles_x = (cols + TILE_W - 1) / TILE_W, tiles_y = (rows + TILE_H - 1) / TILE_H;
-  const int pitch    = tiles_x * TILE_W;
-  const size_t padded = (size_t) pitch * (size_t) (tiles_y * TILE_H);
+  const size_t padded = srrg2amd::feat_padded_pixels(rows, cols);
   if ((rc = s->feat_score.reserve(padded)) || (rc = s->feat_box.reserve(padded))) return rc;
   if ((rc = s->feat_max.reserve((size_t) n)) || (rc = s->feat_tie.reserve((size_t) n + 1))) return rc;
   if ((rc = s->flags.reserve((size_t) n + 1)) || (rc = s->feat_ctr.reserve(C_WORDS))) return rc;
   if ((rc = s->scan_sums.reserve((size_t) srrg2amd::scan_num_blocks(n) + 2))) return rc;
-  if (!s->feat_pattern_ready) {  // the 32 rotated patterns, once per scene
-    if ((rc = s->feat_pattern.reserve(32 * 256))) return rc;
-    int8_t all[32][1024];
-    for (int b = 0; b < 32; ++b) pattern().rotated(b, all[b]);
-    HIP_TRY(hipMemcpyAsync(s->feat_pattern.p, all, sizeof(all), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));  // (`all` leaves the stack)
-    s->feat_pattern_ready = true;
-  }
+  if ((rc = srrg2amd::feat_pattern_upload(s))) return rc;  // the 32 rotated patterns, once per scene
+  const srrg2amd::FeatWork work{s->feat_score.p, s->feat_box.p, s->feat_max.p, s->feat_tie.p, s->feat_ctr.p, s->flags.p, s->scan_sums.p};
   int* const ctr = s->feat_ctr.p;
-  HIP_TRY(hipMemsetAsync(ctr, 0, C_WORDS * sizeof(int), st));
-  const int word_reads = reinterpret_cast<uintptr_t>(I.p) % 4 == 0 && I.stride % 4 == 0;
-  hipLaunchKernelGGL(k_feat_score_box, dim3(tiles_x, tiles_y), dim3(256), 0, st, I, word_reads,
-                     reinterpret_cast<unsigned*>(s->feat_score.p), reinterpret_cast<uint2*>(s->feat_box.p), pitch);
-  hipLaunchKernelGGL(k_feat_maxima, dim3((unsigned) (((long long) n + 255) / 256)), dim3(256), 0, st, s->feat_score.p, pitch, rows, cols, p->fast_threshold,
-                     s->feat_max.p, ctr);
-  hipLaunchKernelGGL(k_feat_cut, dim3(1), dim3(64), 0, st, p->max_features, ctr);
-  const dim3 grid(blocks_of(n)), block(256);
-  hipLaunchKernelGGL(k_feat_tie, grid, block, 0, st, s->feat_score.p, pitch, cols, n, s->feat_max.p, ctr, s->feat_tie.p);
-  srrg2amd::launch_exclusive_scan(s->feat_tie.p, n, s->scan_sums.p, ctr + C_TIES, st);
-  hipLaunchKernelGGL(k_feat_select, grid, block, 0, st, s->feat_score.p, pitch, cols, n, s->feat_max.p, s->feat_tie.p, D, s->flags.p,
-                     ctr);
-  HIP_TRY(hipGetLastError());
+  if ((rc = srrg2amd::feat_queue_select(I, D, p->fast_threshold, p->max_features, work, st))) return rc;
   HIP_TRY(hipMemcpyAsync(s->scalars + 8, ctr, 4 * sizeof(int), hipMemcpyDeviceToHost, st));  // (rides on the scan's wait)
   int total = 0;
   if ((rc = srrg2amd::scene_scan_flags(s, n, &total))) return rc;
@@ -515,11 +527,8 @@ extern "C" int srrg2_adapt_image_features(srrg2_scene_h dst, const void* intensi
   s->n = s->ng = total;
   s->has_normals = false;
   if (total > 0) {
-    hipLaunchKernelGGL(k_feat_scatter, grid, block, 0, st, n, s->flags.p, total, s->gidx.p);
-    hipLaunchKernelGGL(k_feat_describe, dim3((total + 3) / 4), dim3(256), 0, st, I, s->feat_score.p, s->feat_box.p, pitch,
-                       s->feat_pattern.p, D, p->oriented, s->gidx.p, total, s->pts.p, s->nrm.p, s->inten.p,
-                       reinterpret_cast<unsigned long long*>(s->desc.p), s->feat_kp.p);
-    HIP_TRY(hipGetLastError());
+    const srrg2amd::FeatOut o{s->gidx.p, reinterpret_cast<unsigned long long*>(s->desc.p), s->feat_kp.p, s->pts.p, s->nrm.p, s->inten.p};
+    if ((rc = srrg2amd::feat_queue_describe(I, D, p->oriented, work, s->feat_pattern.p, total, o, st))) return rc;
     const int copied = keypoints_out ? (total < keypoint_capacity ? total : keypoint_capacity) : 0;
     if (copied > 0)
       HIP_TRY(hipMemcpyAsync(keypoints_out, s->feat_kp.p, sizeof(srrg2_keypoint) * (size_t) copied, hipMemcpyDeviceToHost, st));

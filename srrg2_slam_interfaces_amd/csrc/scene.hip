@@ -825,6 +825,11 @@ int srrg2_scene_destroy(srrg2_scene_h s) {
   s->nrm_curv.release(); s->alt_gidx.release(); s->nrm_idx.release(); s->nrm_ctr.release(); s->nrm_keys.release();
   s->vox_acc.release(); s->vox_rep.release(); s->vox_rank.release(); s->vox_cnt.release(); s->vox_counts.release(); s->vox_pts.release(); s->vox_nrm.release();
   s->feat_score.release(); s->feat_max.release(); s->feat_box.release(); s->feat_tie.release(); s->feat_ctr.release(); s->feat_pattern.release(); s->feat_kp.release();
+  s->st_score.release(); s->st_max.release(); s->st_box.release(); s->st_tie.release(); s->st_ctr.release(); s->st_flags.release(); s->st_sums.release();
+  s->st_counts.release(); s->st_match.release(); s->st_match_out.release(); s->st_z.release();
+  for (int i = 0; i < 2; ++i) {
+    s->st_pixel[i].release(); s->st_rows[i].release(); s->st_desc[i].release(); s->st_kp[i].release(); s->st_best[i].release();
+  }
   if (s->scalars) (void) hipHostFree(s->scalars);
   if (s->stream) (void) hipStreamDestroy(s->stream);
   delete s;

@@ -58,6 +58,19 @@ struct srrg2_scene {
   srrg2amd::DevBuf<unsigned> feat_pattern;
   srrg2amd::DevBuf<srrg2_keypoint> feat_kp;
   bool feat_pattern_ready = false;
+  // adapt_stereo_features (stereo.hip): the right image's copy of the pipeline scratch above (the left image uses feat_* with
+  // flags / scan_sums); per image [left, right] and selected keypoint its pixel, descriptor and record, per image row + 1 the
+  // first keypoint at or below it, per keypoint its best candidate (distance << 32 | candidate index, all ones = none); per left
+  // keypoint its match record and depth; the counters; the compacted match records
+  srrg2amd::DevBuf<unsigned char> st_score, st_max;
+  srrg2amd::DevBuf<unsigned short> st_box;
+  srrg2amd::DevBuf<int> st_tie, st_ctr, st_flags, st_sums;
+  srrg2amd::DevBuf<int> st_pixel[2], st_rows[2], st_counts;
+  srrg2amd::DevBuf<uint4> st_desc[2];
+  srrg2amd::DevBuf<srrg2_keypoint> st_kp[2];
+  srrg2amd::DevBuf<unsigned long long> st_best[2];
+  srrg2amd::DevBuf<srrg2_stereo_match> st_match, st_match_out;
+  srrg2amd::DevBuf<float> st_z;
   int* scalars = nullptr;  // pinned host mirror of dscalars
   // device: [1] num_merged, [2] error flag, [3] duplicates seen, [4] ncorr (merge); [0] Valid, [1] in view, [2] scan total (clip);
   // [8] in range, [9] Valid (adapt)

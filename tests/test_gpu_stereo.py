@@ -1,0 +1,338 @@
+"""GPU: the stereo-feature adaptor (srrg2_adapt_stereo_features, csrc/stereo.hip) against the numpy restatement of its contract
+(tests/stereo_restatement.py), BIT FOR BIT: points, descriptors, intensities, global indices, keypoint records, match records
+(the float disparity's bits included) and every counter; against the image-feature adaptor on the device under the depth image of
+the returned matches; misuse leaves the scene as it was; and through the stack: the descriptor database fed from a stereo scene
+matches as one fed the restatement's descriptors from the host, and the ball clipper carries the descriptors of the points it
+keeps.  tests/test_stereo_restatement.py pins what the cases exercise."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import adaptor_restatement as ar
+import features_cases as fc
+import stereo_cases as sc
+import stereo_restatement as sr
+from srrg2_slam_interfaces_amd import _abi as abi
+from srrg2_slam_interfaces_amd import adaptors, mapping
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+PAIR_NAMES = [n for n, _, _ in sc.pairs()]
+FEATURE_KEYS = ("fast_threshold", "max_features", "oriented")
+
+
+def _padded(img, pad):
+    """the same image inside rows that are `pad` elements longer (a row stride larger than the row)"""
+    if not pad:
+        return img
+    big = np.full((img.shape[0], img.shape[1] + pad), 7, img.dtype)
+    big[:, :img.shape[1]] = img
+    return big[:, :img.shape[1]]
+
+
+def _to_device(img):
+    """(tensor kept alive, (pointer, row stride in bytes)): the image's rows at their stride in device memory"""
+    import torch
+
+    rows, cols = img.shape
+    stride = img.strides[0]
+    buf = np.zeros((rows, stride), np.uint8)
+    buf[:, :cols] = img
+    t = torch.from_numpy(buf).cuda()
+    torch.cuda.synchronize()
+    return t, (t.data_ptr(), stride)
+
+
+def _adaptor(**kw):
+    ad = adaptors.MeasurementAdaptorStereoFeatures()
+    ad.set_camera_matrix(sc.CAMERA)
+    ad.stereo.baseline = sc.BASELINE
+    ad.params.max_features = 0
+    for k, v in kw.items():
+        setattr(ad.params if k in FEATURE_KEYS else ad.stereo, k, int(v))
+    return ad
+
+
+def _run(scene, left, right, device=False, pad=0, **kw):
+    ad = _adaptor(**kw)
+    ad.set_meas(scene)
+    lp, rp = _padded(left, pad), _padded(right, pad + (3 if pad else 0))  # (the two strides differ)
+    keep = []
+    if device and left.size:
+        tl, lpair = _to_device(lp)
+        tr, rpair = _to_device(rp)
+        keep += [tl, tr]
+        ad.camera.rows, ad.camera.cols = left.shape
+        ad.set_raw_data(lpair, rpair)
+    else:
+        ad.set_raw_data(lp, rp)
+    assert ad.status() == abi.ADAPTOR_ERROR  # not computed yet
+    res = ad.compute()
+    assert ad.status() == (abi.ADAPTOR_READY if left.size else abi.ADAPTOR_INITIALIZING)
+    return ad, res
+
+
+def _check(scene, ad, res, want, what):
+    n = want["scene_size"]
+    assert res == {k: want[k] for k in sr.COUNTERS}, (what, res)
+    assert scene.size() == n, what
+    pts, _ = scene.get()
+    assert ar.same_bits(pts, want["points"]), what
+    assert scene.device_arrays()[1] is None, what  # no normals
+    assert scene.has_features() == (True, True), what
+    desc, inten = scene.features()
+    assert desc.tobytes() == want["descriptors"].tobytes(), what
+    assert inten.tobytes() == want["intensity"].tobytes(), what
+    assert np.array_equal(scene.global_indices(), want["global_indices"]), what
+    kp = ad.keypoints()
+    assert kp.shape == (n, 4) and np.array_equal(kp[:, :3], want["keypoints"]) and not kp[:, 3].any(), what
+    ms = ad.matches()
+    assert ms.dtype == sr.MATCH_DTYPE and ms.tobytes() == want["matches"].tobytes(), what  # (the disparity's bits too)
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("name", PAIR_NAMES)
+def test_pairs_bit_for_bit(product, name, device):
+    """every size plain and rotated under every variant (each switch both ways, row tolerances 0 / 1 / 8, max_distance 0 and
+    256, a narrow disparity gate); the defaults also with rows at a larger stride"""
+    left, right = sc.named(name)
+    scene = mapping.Scene(product.scene_binding(0), 3)
+    for kw in sc.VARIANTS:
+        for pad in ((0, 5) if not kw else (0,)):
+            ad, res = _run(scene, left, right, device=device, pad=pad, **kw)
+            _check(scene, ad, res, sc.want(name, **kw), (name, device, kw, pad))
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_dense_keypoints_long_bands_and_ties(product, device):
+    """threshold 0, uncapped: about a thousand keypoints per image, row bands of more than 64 candidates (several passes of the
+    search wave), Hamming ties; then the tiled pair, where two candidates tie at distance 0"""
+    scene = mapping.Scene(product.scene_binding(0), 3)
+    left, right = sc.named(sc.DENSE_PAIR)
+    for kw in sc.DENSE:
+        want = sc.want(sc.DENSE_PAIR, **kw)
+        assert (want["details"]["band_size"] > 64).any()
+        ad, res = _run(scene, left, right, device=device, **kw)
+        _check(scene, ad, res, want, (device, kw))
+    left, right = sc.named("tiled")
+    for kw in sc.TILED:
+        ad, res = _run(scene, left, right, device=device, **kw)
+        _check(scene, ad, res, sc.want("tiled", **kw), (device, kw))
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_cap_cuts_inside_a_class_of_equal_scores(product, device):
+    left, right = sc.named("tiled")
+    _, caps = fc.tie_caps(left)
+    scene = mapping.Scene(product.scene_binding(0), 3)
+    for which in ("inside", "boundary", "above"):
+        kw = dict(max_features=caps[which], max_disparity=20)
+        ad, res = _run(scene, left, right, device=device, **kw)
+        want = sc.want("tiled", **kw)
+        _check(scene, ad, res, want, which)
+        assert res["num_left"] == min(caps[which], sc.want("tiled", max_disparity=20)["num_left"])
+
+
+@pytest.mark.parametrize("name", ["120x160", "96x128_rot", "tiled"])
+def test_scene_equals_the_image_features_under_the_depth_of_the_matches(product, name):
+    """(6) of the contract on the device: srrg2_adapt_image_features on the left image with the F32 depth image built from the
+    returned matches gives the same scene"""
+    left, right = sc.named(name)
+    b = product.scene_binding(0)
+    scene, other = mapping.Scene(b, 3), mapping.Scene(b, 3)
+    for kw in (dict(), dict(subpixel=False, cross_check=False, max_distance=256)):
+        ad, res = _run(scene, left, right, **kw)
+        assert res["scene_size"] > 10
+        depth = sr.depth_image_of(ad.matches(), left.shape[0], left.shape[1], sc.CAMERA, sc.BASELINE)
+        fa = adaptors.MeasurementAdaptorImageFeatures()
+        fa.set_camera_matrix(sc.CAMERA)
+        fa.params.max_features = 0
+        fa.set_meas(other)
+        fa.set_raw_data(left, depth)
+        fres = fa.compute()
+        assert fres["scene_size"] == res["scene_size"] and fres["num_selected"] == res["num_left"]
+        assert ar.same_bits(other.get()[0], scene.get()[0])
+        assert other.features()[0].tobytes() == scene.features()[0].tobytes()
+        assert other.features()[1].tobytes() == scene.features()[1].tobytes()
+        assert np.array_equal(other.global_indices(), scene.global_indices())
+        assert np.array_equal(fa.keypoints(), ad.keypoints())
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_degenerate_pairs(product, device):
+    """no pixel: INITIALIZING; a side of 32: empty, READY; a flat right image: keypoints on the left, none on the right, nothing
+    matched, READY -- and the scene is usable again afterwards"""
+    scene = mapping.Scene(product.scene_binding(0), 3)
+    left, right = sc.named("48x64")
+    ad, res = _run(scene, left, right, device=device)
+    _check(scene, ad, res, sc.want("48x64"), "48x64")
+    assert scene.size() > 0
+    for name, status in (("0x0", abi.ADAPTOR_INITIALIZING), ("32x40", abi.ADAPTOR_READY), ("blank", abi.ADAPTOR_READY)):
+        ad, res = _run(scene, *sc.named(name), device=device)
+        _check(scene, ad, res, sc.want(name), name)
+        assert scene.size() == 0 and res["status"] == status and res["num_matched"] == 0
+        assert len(ad.keypoints()) == 0 and len(ad.matches()) == 0
+    assert sc.want("blank")["num_left"] > 0
+    ad, res = _run(scene, left, right, device=device, subpixel=False)
+    _check(scene, ad, res, sc.want("48x64", subpixel=False), "48x64 again")
+
+
+def test_record_capacities(product):
+    """keypoints_out and matches_out take what fits, each by its own capacity; without them and without a result the scene is
+    complete all the same"""
+    from srrg2_slam_interfaces_amd import _capi
+
+    lib = _capi.lib()
+    left, right = sc.named("120x160")
+    want = sc.want("120x160")
+    n = want["scene_size"]
+    scene = mapping.Scene(product.scene_binding(0), 3)
+    ad = _adaptor()
+    ad.camera.rows, ad.camera.cols = left.shape
+
+    def call(kps, kcap, ms, mcap, out):
+        return lib.srrg2_adapt_stereo_features(scene._h, C.c_void_p(left.ctypes.data), left.strides[0], C.c_void_p(right.ctypes.data),
+                                               right.strides[0], abi.MEM_HOST, C.byref(ad.camera), C.byref(ad.params),
+                                               C.byref(ad.stereo), kps, kcap, ms, mcap, out)
+
+    for kcap, mcap in ((0, 0), (5, 2), (n, n + 9), (n + 9, 1)):
+        kps = np.full((max(kcap, 1) + 1, 4), -7, np.int32)
+        ms = np.full((max(mcap, 1) + 1, 4), -7, np.int32)
+        out = abi.StereoResult()
+        assert call(kps.ctypes.data_as(C.POINTER(abi.Keypoint)), kcap, ms.ctypes.data_as(C.POINTER(abi.StereoMatch)), mcap,
+                    C.byref(out)) == 0
+        gk, gm = min(kcap, n), min(mcap, n)
+        assert np.array_equal(kps[:gk, :3], want["keypoints"][:gk]) and (kps[gk:] == -7).all()
+        assert ms[:gm].tobytes() == want["matches"][:gm].tobytes() and (ms[gm:] == -7).all()
+        assert out.scene_size == n
+    assert call(None, 0, None, 0, None) == 0
+    assert scene.features()[0].tobytes() == want["descriptors"].tobytes()
+
+
+def _snapshot(scene):
+    pts, nrm = scene.get()
+    desc, inten = scene.features()
+    return (scene.size(), pts.tobytes(), nrm.tobytes(), scene.has_features(), None if desc is None else desc.tobytes(),
+            None if inten is None else inten.tobytes(), scene.global_indices().tobytes())
+
+
+def test_misuse_leaves_the_scene_unchanged(product):
+    from srrg2_slam_interfaces_amd import _capi
+
+    lib = _capi.lib()
+    left, right = sc.named("48x64")
+    b = product.scene_binding(0)
+    s3, s2 = mapping.Scene(b, 3), mapping.Scene(b, 2)
+    _run(s3, left, right)
+    s2.set(np.random.default_rng(1).uniform(-1, 1, (40, 2)).astype(F))
+    before3, before2 = _snapshot(s3), _snapshot(s2)
+    assert before3[0] > 0
+    lp, rp = C.c_void_p(left.ctypes.data), C.c_void_p(right.ctypes.data)
+    stride = left.strides[0]
+    kp = (abi.Keypoint * 64)()
+    ms = (abi.StereoMatch * 64)()
+
+    def call(scene=s3, lptr=lp, lst=stride, rptr=rp, rst=stride, mem=abi.MEM_HOST, cam=None, par=None, ste=None, kcap=64, mcap=64,
+             null=None):
+        ad = _adaptor()
+        ad.camera.rows, ad.camera.cols = left.shape
+        if cam:
+            cam(ad.camera)
+        for k, v in (par or {}).items():
+            setattr(ad.params, k, v)
+        for k, v in (ste or {}).items():
+            setattr(ad.stereo, k, v)
+        return lib.srrg2_adapt_stereo_features(scene._h, lptr, lst, rptr, rst, mem, None if null == "cam" else C.byref(ad.camera),
+                                               None if null == "fp" else C.byref(ad.params),
+                                               None if null == "sp" else C.byref(ad.stereo), kp, kcap, ms, mcap, None)
+
+    def setter(**kw):
+        def edit(p):
+            for k, v in kw.items():
+                setattr(p, k, v)
+        return edit
+
+    def matrix(i, v):
+        def edit(p):
+            p.camera_matrix[i] = v
+        return edit
+
+    assert call() == 0  # (the call itself is good)
+    assert _snapshot(s3) == before3
+    bad = [dict(scene=s2), dict(null="cam"), dict(null="fp"), dict(null="sp"), dict(lptr=None), dict(rptr=None),
+           dict(cam=setter(rows=-1)), dict(cam=setter(cols=-1)), dict(cam=setter(rows=70000, cols=70000)), dict(lst=stride - 1),
+           dict(rst=stride - 1), dict(lst=0), dict(rst=0), dict(mem=abi.MEM_DEVICE_KEPT), dict(mem=7),
+           dict(par=dict(fast_threshold=-1)), dict(par=dict(fast_threshold=255)), dict(par=dict(max_features=-1)),
+           dict(par=dict(oriented=2)), dict(par=dict(oriented=-1)), dict(par=dict(reserved=1)), dict(kcap=-1), dict(mcap=-1),
+           dict(cam=matrix(0, 0.0)), dict(cam=matrix(4, 0.0)), dict(cam=matrix(0, float("nan"))), dict(cam=matrix(4, float("inf"))),
+           dict(ste=dict(baseline=0.0)), dict(ste=dict(baseline=-0.1)), dict(ste=dict(baseline=float("nan"))),
+           dict(ste=dict(baseline=float("inf"))), dict(ste=dict(min_disparity=0)), dict(ste=dict(min_disparity=-3)),
+           dict(ste=dict(min_disparity=9, max_disparity=8)), dict(ste=dict(row_tolerance=-1)), dict(ste=dict(row_tolerance=9)),
+           dict(ste=dict(max_distance=-1)), dict(ste=dict(max_distance=257)), dict(ste=dict(cross_check=2)),
+           dict(ste=dict(cross_check=-1)), dict(ste=dict(subpixel=2)), dict(ste=dict(subpixel=-1)), dict(ste=dict(reserved=1))]
+    for kw in bad:
+        assert call(**kw) == -1, kw  # SRRG2_E_INVALID
+        assert b"adapt_stereo_features" in lib.srrg2_amd_last_error()
+    assert call(cam=matrix(1, 0.5)) == -4  # SRRG2_E_UNSUPPORTED: skew
+    assert _snapshot(s3) == before3 and _snapshot(s2) == before2
+    assert call(ste=dict(min_disparity=9, max_disparity=9)) == 0 and s3.size() < before3[0]
+
+
+def test_one_handle_across_shapes_and_behind_a_queued_adapt(product):
+    """the same scene reused larger then smaller then larger; and a call that follows an organised srrg2_adapt_depth_image that
+    only queued its work on the same scene"""
+    scene = mapping.Scene(product.scene_binding(0), 3)
+    for name in ("120x160", "48x64", "96x128_rot", "67x101", "120x160_rot"):
+        ad, res = _run(scene, *sc.named(name))
+        _check(scene, ad, res, sc.want(name), name)
+    left, right = sc.named("96x128")
+    dp = adaptors.MeasurementAdaptorDepthImage()
+    dp.set_camera_matrix(sc.CAMERA)
+    dp.params.compact = 0
+    dp.set_meas(scene)
+    dp.set_raw_data(fc.depth_for(left, "u16"))
+    assert dp.compute(want_result=False) is None  # queued, not waited for
+    ad, res = _run(scene, left, right)
+    _check(scene, ad, res, sc.want("96x128"), "behind a queued adapt")
+
+
+def _same_match(a, b):
+    assert np.array_equal(a.indices, b.indices) and np.array_equal(a.num_matches, b.num_matches)
+    assert np.array_equal(a.map_counts, b.map_counts) and len(a.correspondences) == len(b.correspondences)
+    for x, y in zip(a.correspondences, b.correspondences):
+        assert x.tobytes() == y.tobytes()
+
+
+def test_through_the_stack(product):
+    """the descriptor database fed from stereo scenes answers as one fed the restatement's descriptors from the host; the ball
+    clipper moves a keypoint's descriptor and intensity with its point"""
+    b = product.scene_binding(0)
+    sa, sb = mapping.Scene(b, 3), mapping.Scene(b, 3)
+    kw = dict(min_disparity=6, max_disparity=15)
+    _run(sa, *sc.named("120x160"), **kw)
+    _run(sb, *sc.named("120x160"), cross_check=False, **kw)
+    wa, wb = sc.want("120x160", **kw), sc.want("120x160", cross_check=False, **kw)
+    assert wa["scene_size"] >= 40
+    dev, host = product.DescriptorDatabase(0), product.DescriptorDatabase(0)
+    ones = lambda w: np.ones(w["scene_size"], np.uint8)  # noqa: E731  (every keypoint's point is finite)
+    assert dev.add_scene(sa) == host.add(wa["descriptors"], ones(wa)) == 0
+    for mkw in (dict(query_index=1), dict(query_index=1, max_distance=12.5, min_matches=10)):
+        got, want = dev.match_scene(sb, **mkw), host.match(wb["descriptors"], ones(wb), **mkw)
+        _same_match(got, want)
+    assert want.indices.tolist() == [0] and int(want.num_matches[0]) >= 40
+    # clip_ball around the scene's first point
+    pts = sa.get()[0]
+    clipped = mapping.Scene(b, 3)
+    cl = mapping.SceneClipperBall(b, range_max=0.5)
+    cl.set_full_scene(sa)
+    cl.set_clipped_scene_in_robot(clipped)
+    pose = np.eye(3, 4, dtype=F)
+    pose[:, 3] = pts[0]
+    cl.set_robot_in_local_map(pose)
+    cl.compute()
+    g = cl.global_indices()
+    assert 0 < len(g) < sa.size()
+    d, i = sa.features()
+    cd, ci = clipped.features()
+    assert cd.tobytes() == d[g].tobytes() and ci.tobytes() == i[g].tobytes()
