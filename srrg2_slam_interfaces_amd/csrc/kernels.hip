@@ -479,10 +479,14 @@ __device__ __forceinline__ void transform_point(const float* T, const float4 p, 
 // The team's lanes fetch all row ranges of the cube together, prefix-sum the counts, take equal contiguous shares of
 // the flattened candidate list and reduce to the lexicographic minimum of (d2, fixed index).  Every lane of the team
 // returns the same (best, idx, pos); idx == NO_MATCH when the cube is empty.  lds: 4*TW + 8 ints per team.
-template <int DIM, int TW>
+// STAGE: the front half alone -- the candidates are not tested but kept, in the order of the flattened list, in the team's
+// `stage` (LDS, STAGE_CAP entries), for a query that is not known yet (icp_step_fast_body: staged neighbours); widx returns
+// how many the ball holds, and nothing is kept of a ball that holds more than STAGE_CAP.
+constexpr int STAGE_CAP = 64;
+template <int DIM, int TW, bool STAGE = false>
 __device__ __forceinline__ void coop_scan(const GridDev& g, int lane, int* lds_wave, float sqx, float sqy, float sqz,
                                           int scx, int scy, int scz, int sr, float sr2, float& wbest, int& widx,
-                                          int& wpos, float& wexcl2) {
+                                          int& wpos, float& wexcl2, float4* stage = nullptr) {
   constexpr int ROWS_PER_CHUNK = 2 * TW;
   const int lt   = lane & (TW - 1);
   const int team = lane / TW;
@@ -531,6 +535,7 @@ __device__ __forceinline__ void coop_scan(const GridDev& g, int lane, int* lds_w
 #pragma unroll
     for (int off = TW; off < 64; off <<= 1) max_rows = max(max_rows, __shfl_xor(max_rows, off));
   }
+  [[maybe_unused]] int staged = 0;  // (STAGE: candidates of the chunks before this one)
   for (int row0 = 0; row0 < max_rows; row0 += ROWS_PER_CHUNK) {
     // (1) every lane fetches the [start, end) ranges of two rows: all row fetches of the chunk in flight at once
     int sA = 0, eA = 0, sB = 0, eB = 0;
@@ -576,11 +581,21 @@ __device__ __forceinline__ void coop_scan(const GridDev& g, int lane, int* lds_w
         }
         const int j   = first[r] + (t - flat[r]);
         const int run = min(next, tend) - t;  // candidates of this row in my share: consecutive in memory
-        scan_range2<DIM>(g.pts, j, j + run, sqx, sqy, sqz, key, lb2);
+        if constexpr (STAGE) {
+          if (staged + total <= STAGE_CAP)
+            for (int c = 0; c < run; ++c) stage[staged + t + c] = g.pts[j + c];
+        } else {
+          scan_range2<DIM>(g.pts, j, j + run, sqx, sqy, sqz, key, lb2);
+        }
         t += run;
       }
     }
+    if constexpr (STAGE) staged += total;
     wave_lds_sync();
+  }
+  if constexpr (STAGE) {
+    wbest = INFINITY; widx = staged; wpos = 0; wexcl2 = 0.f;
+    return;
   }
   // team minimum of the 64-bit key (d2 bits, index): d2 >= 0 so the float bit pattern orders like the value
   unsigned long long kmin = key;
@@ -2087,11 +2102,11 @@ __global__ __launch_bounds__(256) void k_icp_step_tile(SliceDev S, const Problem
 // its end: one plain store each (atomics on shared words serialise and stretch a 12-us launch to 85 us).  Compiled out of the
 // product build.
 #ifdef SRRG2_PASS_TIMELINE
-#define PASS_TS_WGS 2048  // (every workgroup of a 100 k-point search pass at four lanes per point: 1564; the last slot is the census')
+#define PASS_TS_WGS 2048  // (every workgroup of a 100 k-point search pass at four lanes per point: 1564; the last two slots are the censuses')
 __device__ unsigned long long g_pass_ts[16 * PASS_TS_WGS * 8];  // [epoch][workgroup (tile)][stamp]: plain stores, reduced on the host
 #define PASS_TS_ANY(epoch, k) /* (by lane 0 of any wave: the last writer wins) */                      \
   do {                                                                                                 \
-    if ((threadIdx.x & 63) == 0 && (epoch) >= 0 && (epoch) < 16 && blockIdx.y < PASS_TS_WGS - 1 && blockIdx.x == 0) \
+    if ((threadIdx.x & 63) == 0 && (epoch) >= 0 && (epoch) < 16 && blockIdx.y < PASS_TS_WGS - 2 && blockIdx.x == 0) \
       g_pass_ts[(((epoch) * PASS_TS_WGS) + blockIdx.y) * 8 + (k)] = wall_clock64();                            \
   } while (0)
 #define PASS_TS_W(epoch, k, dep) /* (inside wave_control: after `dep` has been computed) */             \
@@ -2104,7 +2119,7 @@ __device__ unsigned long long g_pass_ts[16 * PASS_TS_WGS * 8];  // [epoch][workg
   } while (0)
 #define PASS_TS(epoch, k)                                                                              \
   do {                                                                                                 \
-    if (threadIdx.x == 0 && (epoch) >= 0 && (epoch) < 16 && blockIdx.y < PASS_TS_WGS - 1 && blockIdx.x == 0)       \
+    if (threadIdx.x == 0 && (epoch) >= 0 && (epoch) < 16 && blockIdx.y < PASS_TS_WGS - 2 && blockIdx.x == 0)       \
       g_pass_ts[(((epoch) * PASS_TS_WGS) + blockIdx.y) * 8 + (k)] = wall_clock64();                            \
   } while (0)
 #else
@@ -2746,9 +2761,48 @@ extern "C" int srrg2_amd_debug_fused_fallbacks(unsigned long long* out, int rese
   do {                                                                             \
     if ((threadIdx.x & 63) == 0) atomicAdd(&g_fused_fallbacks, 1ull);              \
   } while (0)
+// ... and what became of the staged neighbours of the converged passes (icp_step_fast_body): [0] thin lanes staged, [1] staged and
+// decided, [2] staged and rejected: more than STAGE_CAP candidates, [3] ... the new query not covered, [4] certificates that failed
+// without having been staged, [5] waves with more than four thin lanes (nothing staged)
+__device__ unsigned long long g_stage_counts[6];
+extern "C" int srrg2_amd_debug_staged_neighbours(unsigned long long* out6, int reset) {
+  if (out6 && hipMemcpyFromSymbol(out6, HIP_SYMBOL(g_stage_counts), 6 * sizeof(unsigned long long)) != hipSuccess) return -1;
+  if (reset) {
+    const unsigned long long zero[6] = {0, 0, 0, 0, 0, 0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stage_counts), zero, sizeof(zero)) != hipSuccess) return -1;
+  }
+  return 0;
+}
+#define STAGE_COUNT(k, n) /* (n: wave-uniform) */                                  \
+  do {                                                                             \
+    const unsigned long long n_ = (unsigned long long) (n);                        \
+    if ((threadIdx.x & 63) == 0 && n_) atomicAdd(&g_stage_counts[k], n_);          \
+  } while (0)
 #else
 #define FUSED_STALL() do { } while (0)
 #define FUSED_FALLBACK_COUNT() do { } while (0)
+#ifdef SRRG2_PASS_TIMELINE  // (the same six counts per epoch, in the second census slot of the timeline: tools/pass_timeline.py)
+#define STAGE_COUNT(k, n)                                                                                        \
+  do {                                                                                                           \
+    const unsigned long long n_ = (unsigned long long) (n);                                                      \
+    if ((threadIdx.x & 63) == 0 && n_ && S.fc.epoch >= 0 && S.fc.epoch < 16 && blockIdx.x == 0)                  \
+      atomicAdd(&g_pass_ts[((size_t) S.fc.epoch * PASS_TS_WGS + PASS_TS_WGS - 2) * 8 + (k)], n_);                \
+  } while (0)
+#else
+#define STAGE_COUNT(k, n) do { } while (0)
+#endif
+#endif
+// a lane's margin is thin -- its ball is staged -- when what is left of it is less than STAGE_THIN_A of the point's last step plus
+// STAGE_THIN_B cells.  A certificate fails when the margin left is below ~2 |q - q0| (the neighbour recedes by the step, the margin
+// shrinks by it): 2 covers every step no longer than the last one, the cells cover a step that grows.  C2, converged passes
+// (profiles/r12/r12_pass_timeline_thresholds.txt): 1e-4 cells stage 165 - 178 lanes per pass for the 9 - 15 that fail and the last
+// stager is done at 6.3 - 7.0 us, 1 us after the record; 1e-5 cells stage 24 - 38, done at 5.4 - 6.0 us, and still no failed
+// certificate was left unstaged.
+#ifndef STAGE_THIN_A
+#define STAGE_THIN_A 2.0f
+#endif
+#ifndef STAGE_THIN_B
+#define STAGE_THIN_B 1e-5f
 #endif
 
 template <int DIM, bool PRIORS = false>
@@ -2763,10 +2817,32 @@ __device__ __forceinline__ void fused_control_if_due(const SliceDev& S, ProblemS
   PASS_TS(S.fc.epoch, 1);
 }
 
-template <int DIM, bool PRIORS = false>
-__device__ __forceinline__ void pass_view_fused(const SliceDev& S, ProblemState* __restrict__ states, int prob, PassView& v) {
+// WHILE_WAITING (a callable, icp_step_fast_body's staging): the copy of the record that wave 0 loads before it polls goes to all
+// waves first, behind a barrier of its own -- stale[0 .. 23]: the two transforms of that copy, stale[24]: whether it stands whole at
+// the previous epoch (it does not in the workgroup that has just published, in a later round, or in the middle of a publication) --,
+// and every wave calls while_waiting(stale) before wave 0 starts polling.  No further agent-scope load: the waves would queue up on
+// the record's lines.
+struct NoStaging {};
+template <int DIM, bool PRIORS = false, class WhileWaiting = NoStaging>
+__device__ __forceinline__ void pass_view_fused(const SliceDev& S, ProblemState* __restrict__ states, int prob, PassView& v,
+                                                WhileWaiting while_waiting = WhileWaiting{}) {
+  constexpr bool STAGING = !std::is_same<WhileWaiting, NoStaging>::value;
   __shared__ unsigned rec_lds[PUB_SLICE_GRANULES];
+  [[maybe_unused]] __shared__ unsigned stale_lds[STAGING ? 25 : 1];
   const int lane = threadIdx.x & 63;
+  [[maybe_unused]] unsigned long long g_first = 0;
+  if constexpr (STAGING) {
+    if (threadIdx.x < 64) {
+      const unsigned long long* rec = S.fc.pub + ((size_t) prob * SRRG2_MAX_SLICES + S.slice_idx) * PUB_SLICE_GRANULES + lane;
+      const bool late = (int) (blockIdx.y * gridDim.x + blockIdx.x) >= S.fc.first_round;
+      g_first         = late ? *rec : pub_load(rec);
+      const bool whole_prev = __all((unsigned) (g_first >> 32) == (unsigned) (S.fc.epoch - 1));
+      if (lane < 24) stale_lds[lane] = (unsigned) g_first;
+      if (lane == 24) stale_lds[24] = whole_prev ? 1u : 0u;
+    }
+    __syncthreads();
+    while_waiting(stale_lds);
+  }
   if (threadIdx.x < 64) {
     const unsigned long long* rec = S.fc.pub + ((size_t) prob * SRRG2_MAX_SLICES + S.slice_idx) * PUB_SLICE_GRANULES + lane;
     // A workgroup of the first round of the launch starts before the control steps have published: agent-scope load
@@ -2774,7 +2850,8 @@ __device__ __forceinline__ void pass_view_fused(const SliceDev& S, ProblemState*
     // i.e. after the control steps (they all run in the first K workgroups of the launch): an ordinary cached load finds the
     // new record -- and if it ever does not, the tags say so and the agent-scope path below takes over.
     const bool late      = (int) (blockIdx.y * gridDim.x + blockIdx.x) >= S.fc.first_round;
-    unsigned long long g = late ? *rec : pub_load(rec);
+    unsigned long long g;
+    if constexpr (STAGING) g = g_first; else g = late ? *rec : pub_load(rec);
     if (!__all((unsigned) (g >> 32) == (unsigned) S.fc.epoch)) {
       // (workgroup (0, problem) applied the control step at its very top -- fused_control_if_due -- before it came here)
       const unsigned* ep = S.fc.pub_epoch + ((size_t) prob * PUB_EPOCH_REPLICAS + (blockIdx.y & (PUB_EPOCH_REPLICAS - 1))) * PUB_EPOCH_STRIDE;
@@ -3350,10 +3427,17 @@ __device__ __forceinline__ void icp_step_fast_body(const SliceDev& S, const Prob
   const int wid      = threadIdx.x >> 6;
   // (the row tables of the cooperative grid scans -- 64-lane scans need 264 ints, four 16-lane teams 4 x 72 -- or, when the
   // grid has cell neighbour lists, the wave's pool of cnl_search: never live together)
+  // (... or, between the top of the kernel and the searches, the staged candidates of up to four thin-margin points -- below)
+  struct StageWave {
+    int coop[288];
+    float4 cand[4][STAGE_CAP];
+  };
   union FastWaveLds {
     CnlWave cnl;
     int coop[288];
+    StageWave stage;
   };
+  static_assert(sizeof(StageWave) <= sizeof(CnlWave), "the staged candidates live in the idle pool of the list search");
   __shared__ FastWaveLds fast_lds[4];
   int* const coop_lds_w = fast_lds[wid].coop;
 
@@ -3410,8 +3494,73 @@ __device__ __forceinline__ void icp_step_fast_body(const SliceDev& S, const Prob
       if (PLANE || ngate) pn[k] = g.nrm[ppos];
     }
   }
+  // Staged neighbours (single alignments with fused control steps and kept neighbours).  While the record is waited for, the only
+  // thing a converged pass does not know is the new transform; which fixed points can matter to a point whose margin is nearly used
+  // up is known: the ones inside the ball of radius R = d0 + PAD_MIN cells about its PREVIOUS query q0 -- the ball the search behind
+  // a failed certificate would enumerate.  So the lanes whose margin is thin (a tie, or a margin that a step like the last one uses
+  // up) gather that ball into LDS now, four at a time by 16-lane teams (the front half of coop_scan), and when the record is there
+  // choose among the kept candidates at the new query q (search_open): no memory round trip at the tail of the launch.  Every fixed
+  // point outside the set is farther than R from q0, hence farther than R - |q - q0| from q: the winner of the set is the nearest
+  // neighbour when it is closer than that, and what is not decided this way -- not predicted, more than STAGE_CAP candidates, a step
+  // that leaves the ball -- is searched as before.  The prediction is never a condition of correctness.
+  constexpr bool STAGE = PPT == 1 && FUSED == 1 && !GATHER;
+  [[maybe_unused]] unsigned long long st_mask = 0;  // the lanes whose ball is staged: team t holds the t-th of them
+  [[maybe_unused]] int st_n = 0;                    // candidates in this lane's team's set (> STAGE_CAP: none kept)
+  [[maybe_unused]] float st_R2 = 0.f;               // squared radius of this lane's ball
+  [[maybe_unused]] float Tst[12];                   // the transform the balls were centred with
+  [[maybe_unused]] auto stage_thin = [&](const unsigned* stale) {
+    if (!__builtin_amdgcn_readfirstlane((int) stale[24])) return;
+    float Tpp[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) Tst[i] = __int_as_float(__builtin_amdgcn_readfirstlane((int) stale[i]));
+#pragma unroll
+    for (int i = 0; i < 12; ++i) Tpp[i] = __int_as_float(__builtin_amdgcn_readfirstlane((int) stale[12 + i]));
+    float ax, ay, az, bx, by, bz;
+    transform_point<DIM>(Tst, p[0], ax, ay, az);
+    transform_point<DIM>(Tpp, p[0], bx, by, bz);
+    const float ex = ax - bx, ey = ay - by, ez = az - bz;
+    const float dlp = __builtin_amdgcn_sqrtf((ex * ex + ey * ey) + ez * ez);  // the last step of this point
+    unsigned long long k0 = NO_KEY;
+    test_candidate<DIM>(pf[0], ax, ay, az, true, k0);
+    const float d0 = __builtin_amdgcn_sqrtf(key_best(k0));
+    const float rr = (d0 + PAD_MIN * g.h) * 1.00001f;
+    const float R2 = fminf(rr * rr, gfar);
+    const bool thin = inr[0] && finite3(p[0].x, p[0].y, p[0].z) && __float_as_int(pf[0].w) != NO_MATCH &&
+                      R2 <= bound2_of(2, g.h) && pm[0] * 0.99999f - d0 * 1.00001f < STAGE_THIN_A * dlp + STAGE_THIN_B * g.h;
+    unsigned long long m = __ballot(thin);
+    const int nthin      = __popcll(m);
+    if (nthin == 0) return;
+    if (nthin > 4) {  // (a pass that still moves: it has the pooled search)
+      STAGE_COUNT(5, 1);
+      return;
+    }
+    st_mask = m;
+    st_R2   = R2;
+    int src[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      src[t] = m ? __ffsll((long long) m) - 1 : -1;
+      m &= m - 1;
+    }
+    const int team = lane >> 4;
+    const int mine = team == 0 ? src[0] : (team == 1 ? src[1] : (team == 2 ? src[2] : src[3]));
+    const int from = mine >= 0 ? mine : lane;
+    const float sqx = __shfl(ax, from), sqy = __shfl(ay, from), sqz = __shfl(az, from), sball = __shfl(R2, from);
+    const int scx = cell_coord(sqx, g.ox, g.inv_h), scy = cell_coord(sqy, g.oy, g.inv_h);
+    const int scz = DIM == 3 ? cell_coord(sqz, g.oz, g.inv_h) : 0;
+    float wbest, wexcl2;
+    int wpos, count;
+    coop_scan<DIM, 16, true>(g, lane, fast_lds[wid].stage.coop, sqx, sqy, sqz, scx, scy, scz, mine >= 0 ? 2 : -1, sball, wbest,
+                             count, wpos, wexcl2, fast_lds[wid].stage.cand[team]);
+    st_n = mine >= 0 ? count : 0;
+    STAGE_COUNT(0, nthin);
+    PASS_TS_ANY(S.fc.epoch, 5);  // (staging done: the last wave that staged)
+  };
   if constexpr (FUSED) {  // (the points are on their way: now the record, or the control step it still waits for)
-    pass_view_fused<DIM, FUSED == 2>(S, states, prob, pv);
+    if constexpr (STAGE)
+      pass_view_fused<DIM, false>(S, states, prob, pv, stage_thin);
+    else
+      pass_view_fused<DIM, FUSED == 2>(S, states, prob, pv);
     if (pv.stop || tile * (256 * PPT) >= pd.nm) return;
     load_T(pv.T, T);
     load_T(pv.Tprev, Tprev);
@@ -3426,10 +3575,72 @@ __device__ __forceinline__ void icp_step_fast_body(const SliceDev& S, const Prob
   #pragma unroll
     for (int k = 0; k < PPT; ++k) {
       sbest[k] = INFINITY; sexcl[k] = 0.f; sidx[k] = NO_MATCH; spos[k] = 0;
-      const bool open = open_ball2[k] >= 0.f;
+      bool open = open_ball2[k] >= 0.f;
       if (!__ballot(open)) continue;
       float qx = 0.f, qy = 0.f, qz = 0.f;
       if (open) transform_point<DIM>(T, p[k], qx, qy, qz);
+      if constexpr (STAGE) {
+        // the staged balls of the lanes whose certificate did fail: the team that gathered a ball tests its candidates at the new
+        // query (the key of every other path: ties break the same way) and the owner accepts the winner if no fixed point outside
+        // the ball can be as close; its open flag is cleared for the searches below, the caller treats the result like theirs
+        const unsigned long long due = st_mask & __ballot(open);
+        STAGE_COUNT(4, __popcll(__ballot(open) & ~st_mask));
+        if (due) {
+          int src[4];
+          unsigned long long m = st_mask;
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            src[t] = m ? __ffsll((long long) m) - 1 : -1;
+            m &= m - 1;
+          }
+          const int team = lane >> 4, lt = lane & 15;
+          const int mine = team == 0 ? src[0] : (team == 1 ? src[1] : (team == 2 ? src[2] : src[3]));
+          const int from = mine >= 0 ? mine : lane;
+          const float sqx = __shfl(qx, from), sqy = __shfl(qy, from), sqz = __shfl(qz, from);
+          const bool work = mine >= 0 && ((due >> (mine & 63)) & 1ull) && st_n <= STAGE_CAP;
+          unsigned long long key = NO_KEY;
+          float lb2 = INFINITY;
+          if (work) {
+            const float4* cand = fast_lds[wid].stage.cand[team];
+            for (int c = lt; c < st_n; c += 16) test_candidate2<DIM>(cand[c], sqx, sqy, sqz, true, key, lb2);
+          }
+          unsigned long long kmin = key;
+#pragma unroll
+          for (int off = 8; off >= 1; off >>= 1) {
+            const unsigned long long o = __shfl_xor(kmin, off);
+            kmin = o < kmin ? o : kmin;
+          }
+          float v = key == kmin ? lb2 : fminf(lb2, key_best(key));  // (the runner-up of the set, as coop_scan's)
+#pragma unroll
+          for (int off = 8; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off));
+          bool decided = false, overflow = false;
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const unsigned long long rk_ = __shfl(kmin, 16 * t);
+            const float rv = __shfl(v, 16 * t);
+            const int rn   = __shfl(st_n, 16 * t);
+            if (lane == src[t] && open) {
+              float ax, ay, az;
+              transform_point<DIM>(Tst, p[k], ax, ay, az);
+              const float ex = qx - ax, ey = qy - ay, ez = qz - az;
+              const float dls = sqrtf((ex * ex + ey * ey) + ez * ez);
+              const float rin = sqrtf(st_R2) * 0.99999f - dls * 1.00001f;  // no fixed point outside the set is closer than this
+              overflow = rn > STAGE_CAP;
+              if (!overflow && key_idx(rk_) != NO_MATCH && sqrtf(key_best(rk_)) * 1.00001f < rin) {
+                sbest[k] = key_best(rk_);
+                sidx[k]  = key_idx(rk_);
+                sexcl[k] = sqrtf(fminf(rv, rin * rin)) * 0.99999f;
+                decided  = true;
+              }
+            }
+          }
+          STAGE_COUNT(1, __popcll(__ballot(decided)));
+          STAGE_COUNT(2, __popcll(__ballot(overflow)));
+          STAGE_COUNT(3, __popcll(due) - __popcll(__ballot(decided || overflow)));
+          open = open && !decided;
+          if (!__ballot(open)) continue;
+        }
+      }
       // The grid has cell neighbour lists and the wave has more than a few open points (a pass before convergence, a partial
       // overlap: C2 at 60 % overlap 24.9 -> 43.0 k it/s): all of them in one pooled search.  A settled pass leaves a wave one
       // or two: the 16-lane cooperative scans below finish those in fewer dependent round trips (C2 converged pass 8.6 us

@@ -47,8 +47,9 @@ prev_end = None
 print("epoch | workgroups | start: first  last | control done | record seen: first  median  last | end: first  median  last | launch   [us after the end of the previous launch]")
 for e in range(16):
     used = ts[e, :, 0] > 0
-    used[WGS - 1] = False
+    used[WGS - 2:] = False  # (the last two slots hold the censuses)
     census = ts[e, WGS - 1, :7].copy()
+    staged = ts[e, WGS - 2, :6].copy()
     if not used.any():
         continue
     st, ctl, seen, end = ts[e, used, 0], ts[e, 0, 1], ts[e, used, 2], ts[e, used, 3]
@@ -69,6 +70,16 @@ for e in range(16):
         print("      control step: sums and H / b in the lanes at %s, dx solved at %s, X and the transforms at %s, published at %s" % (f(ts[e, 0, 5]), f(ts[e, 0, 6]), f(ts[e, 0, 7]), f(ctl)))
     if census[0]:
         print("      failed certificates: %d points (no previous neighbour %d; margin < 1e-4 cells %d, < 0.0202 cells %d, larger %d; moved > 1e-3 cells %d; no radius %d)" % tuple(census))
+    if staged.any():
+        print("      staged neighbours: %d thin lanes staged, %d decided, rejected %d (more than the cap) + %d (not covered), "
+              "%d certificates failed unstaged, %d waves with more than four thin lanes" % tuple(staged))
+    rest = used.copy()
+    rest[0] = False  # (workgroup 0 keeps the control step's stamps in these slots)
+    sdone = ts[e, rest, 5]
+    sdone = sdone[sdone > 0]
+    if len(sdone):
+        print("      staging done in %d workgroups: first %s, median %s, last %s (record seen: median %s)" % (
+            len(sdone), f(sdone.min()), f(np.median(sdone)), f(sdone.max()), f(np.median(seen))))
     p2 = ts[e, used, 4]
     p2 = p2[p2 > 0]
     if len(p2):
