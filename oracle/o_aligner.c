@@ -295,7 +295,8 @@ typedef struct {
   float prior_Z[12];
   int has_prior;
   int64_t acc[ACC_N];
-  int k;
+  int k;  /* fixed-point exponent of the b and chi terms ... */
+  int kh; /* ... and of the H terms: the same, except on given-correspondences slices (slice_exponent) */
   double prior_H[36], prior_b[6], prior_chi;
   int prior_status;
   int shares; /* 1 + index of the slice whose clouds this one reads (srrg2_aligner_share_clouds); 0: its own */
@@ -414,6 +415,10 @@ int oracle_aligner_add_slice(o_aligner* h, const srrg2_slice_config* c, int* idx
         !(c->camera_matrix[0] > 0.f) || !(c->camera_matrix[4] > 0.f))
       return fail(SRRG2_E_INVALID, "projective slice: bad camera / image / depth range");
   }
+  /* the gate bounds the residual of the fixed-point exponent: a negative one would search within |gate| and bound with gate */
+  if (c->kind != SRRG2_SLICE_PRIOR && (c->finder == SRRG2_FINDER_NN_GATED || c->finder == SRRG2_FINDER_PROJECTIVE) &&
+      !(isfinite(c->finder_max_distance) && c->finder_max_distance >= 0.f))
+    return fail(SRRG2_E_INVALID, "finder_max_distance must be finite and not negative");
   o_slice* s = &h->slices[h->nslices];
   memset(s, 0, sizeof(*s));
   s->cfg         = *c;
@@ -776,7 +781,7 @@ static float proj_extent(int n, float c) {
   return fmaxf(fmaxf((float) n, fabsf(c + 0.5f)), fabsf(((float) n - 0.5f) - c));
 }
 
-static int slice_exponent(const o_aligner* a, const o_slice* s) {
+static int slice_exponent(const o_aligner* a, const o_slice* s, int* kh_out) {
   const int plane = s->cfg.kind == SRRG2_SLICE_P2PLANE;
   const int repro = s->cfg.kind == SRRG2_SLICE_REPROJECTION;
   const int proj  = s->cfg.finder == SRRG2_FINDER_PROJECTIVE;
@@ -797,20 +802,27 @@ static int slice_exponent(const o_aligner* a, const o_slice* s) {
   if (repro) eb = (double) PIX_BOUND * 1.01;
   int n_terms = s->nm;
   if (s->cfg.finder == SRRG2_FINDER_CORRESPONDENCES) {
-    /* no gate bounds the residual: |e_r| <= sqrt3 (sqrt3 |p|inf + |t|inf + |f|inf) with the CURRENT estimate */
-    const float* X = a->X;
-    double tmax    = 0.0;
+    /* no gate bounds the residual: |e_r| <= sqrt3 (sqrt3 |p|inf + |t|inf + |f|inf), t the translation of the finder transform
+     * T = robot_in_sensor * X of the CURRENT estimate -- the transform the residual is formed with (the estimate's own
+     * translation misses the sensor's offset) */
+    float T[12];
+    finder_transform(a, s, T);
+    double tmax = 0.0;
     if (a->dim == 3) {
-      for (int r = 0; r < 3; ++r) tmax = fabs((double) X[r * 4 + 3]) > tmax ? fabs((double) X[r * 4 + 3]) : tmax;
+      for (int r = 0; r < 3; ++r) tmax = fabs((double) T[r * 4 + 3]) > tmax ? fabs((double) T[r * 4 + 3]) : tmax;
     } else {
-      for (int r = 0; r < 2; ++r) tmax = fabs((double) X[r * 3 + 2]) > tmax ? fabs((double) X[r * 3 + 2]) : tmax;
+      for (int r = 0; r < 2; ++r) tmax = fabs((double) T[r * 3 + 2]) > tmax ? fabs((double) T[r * 3 + 2]) : tmax;
     }
     eb      = ((mb * 1.7320508075688772) * ((1.7320508075688772 * (double) s->pinf + tmax) + (double) s->finf)) * 1.01;
     n_terms = s->ngiven > 1 ? s->ngiven : 1;
   }
   double mx       = jb > eb ? jb : eb;
   double B        = (double) rows * (mx * mx);
-  return o_fixed_point_exponent(n_terms, B);
+  const int k     = o_fixed_point_exponent(n_terms, B);
+  /* The H terms do not hold the residual.  Where no gate bounds it (given correspondences) a far-off estimate would otherwise
+   * coarsen the grid of H with it: those slices scale H by its own bound rows * J_b^2. */
+  *kh_out = s->cfg.finder == SRRG2_FINDER_CORRESPONDENCES ? o_fixed_point_exponent(n_terms, (double) rows * (jb * jb)) : k;
+  return k;
 }
 
 /* Fixed-point terms: every product (w 2^k J_ra) * J_rb is rounded ONCE, to nearest-even, onto the
@@ -834,8 +846,10 @@ static int slice_linearize(o_aligner* a, o_slice* s) {
   const int repro = s->cfg.kind == SRRG2_SLICE_REPROJECTION;
   if (plane && !s->fixed_n) return fail(SRRG2_E_STATE, "point-to-plane slice without fixed normals");
   const float kk = a->kind == SRRG2_SE3_QUAT_RIGHT ? 2.f : 1.f;
-  const int k    = slice_exponent(a, s);
+  int kh;
+  const int k    = slice_exponent(a, s, &kh);
   s->k           = k;
+  s->kh          = kh;
   memset(s->acc, 0, sizeof(s->acc));
   float T[12];
   finder_transform(a, s, T);
@@ -943,12 +957,14 @@ static int slice_linearize(o_aligner* a, o_slice* s) {
     }
     if (w == 0.f) continue;
     const double ws = (double) w * scale; /* exact */
+    const double wh = (double) w * ldexp(1.0, kh);
     for (int aa = 0; aa < D; ++aa) {
-      double wj[3];
+      double wj[3], wjh[3];
       for (int r = 0; r < rows; ++r) wj[r] = ws * (double) J[r][aa]; /* exact: 24 x 24 bits */
+      for (int r = 0; r < rows; ++r) wjh[r] = wh * (double) J[r][aa];
       for (int bb = aa; bb < D; ++bb) {
         double t = FX_MAGIC;
-        for (int r = 0; r < rows; ++r) t = fma(wj[r], (double) J[r][bb], t);
+        for (int r = 0; r < rows; ++r) t = fma(wjh[r], (double) J[r][bb], t);
         s->acc[hidx(aa, bb)] += fx_bits(t);
       }
       double t = FX_MAGIC;
@@ -1109,7 +1125,7 @@ static int solver_compute(o_aligner* a) {
     if (rc) return rc;
     for (int aa = 0; aa < D; ++aa) {
       for (int bb = aa; bb < D; ++bb) {
-        double v       = ldexp((double) s->acc[hidx(aa, bb)], -s->k);
+        double v       = ldexp((double) s->acc[hidx(aa, bb)], -s->kh);
         H[aa * D + bb] = H[aa * D + bb] + v;
         if (bb != aa) H[bb * D + aa] = H[bb * D + aa] + v;
       }

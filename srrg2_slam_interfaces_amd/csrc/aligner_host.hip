@@ -2071,6 +2071,10 @@ int srrg2_aligner_add_slice(srrg2_aligner_h a, const srrg2_slice_config* c, int*
         !(c->camera_matrix[0] > 0.f) || !(c->camera_matrix[4] > 0.f))
       return fail(SRRG2_E_INVALID, "add_slice: projective slice with bad camera / image / depth range");
   }
+  // the gate bounds the residual of the fixed-point exponent: a negative one would search within |gate| and bound with gate
+  if (c->kind != SRRG2_SLICE_PRIOR && (c->finder == SRRG2_FINDER_NN_GATED || c->finder == SRRG2_FINDER_PROJECTIVE) &&
+      !(std::isfinite(c->finder_max_distance) && c->finder_max_distance >= 0.f))
+    return fail(SRRG2_E_INVALID, "add_slice: finder_max_distance must be finite and not negative");
   if (c->kind == SRRG2_SLICE_PRIOR && a->kind == SRRG2_SE3_EULER_RIGHT)
     return fail(SRRG2_E_UNSUPPORTED, "add_slice: SE3 prior factors exist for the quaternion variable only "
                                      "(SE3PriorErrorFactorAD, aligner_slice_odometry_prior.h:33)");

@@ -184,6 +184,9 @@ struct ProblemState {
   int w_count;
   double w_corr[TERM_WINDOW_MAX], w_inl[TERM_WINDOW_MAX], w_out[TERM_WINDOW_MAX], w_chi[TERM_WINDOW_MAX];
   double last_H[36], last_b[6], last_dx[6];
+  // fixed-point exponent of the H terms per slice: kexp, except on given-correspondences slices, whose residual no gate bounds
+  // (slice_exponent).  (Last: every other field keeps its offset.)
+  int kexp_h[SRRG2_MAX_SLICES];
 };
 
 // what the host reads back after compute()

@@ -352,9 +352,11 @@ __device__ __forceinline__ long long wave_transpose_reduce(long long (&v)[ACC_N]
 
 // per-correspondence factor arithmetic shared by every cue slice: chi, robustifier, the 27 (9 in 2D) fixed-point
 // terms of w J^T J and w J^T e, and the statistics.  Returns the srrg2_factor_status of the correspondence.
-template <int D, int ROWS>
+// (OWN_H: the H terms are scaled by scale_h instead of scale -- given correspondences, slice_exponent)
+template <int D, int ROWS, bool OWN_H = false>
 __device__ __forceinline__ uint8_t factor_accumulate(const float (&J)[ROWS][D], const float (&e)[ROWS], bool invalid,
-                                                     int rk, float thr, double scale, long long (&acc)[ACC_N]) {
+                                                     int rk, float thr, double scale, long long (&acc)[ACC_N],
+                                                     double scale_h = 0.0) {
   float chi = e[0] * e[0];
 #pragma unroll
   for (int r = 1; r < ROWS; ++r) chi = chi + e[r] * e[r];
@@ -375,16 +377,19 @@ __device__ __forceinline__ uint8_t factor_accumulate(const float (&J)[ROWS][D], 
   if (w != 0.f) {
     // (w * 2^k) is exact, (w * 2^k) * J is exact (24 x 24 bits); the fma rounds each product once onto the grid
     const double ws = (double) w * scale;
+    const double wh = OWN_H ? (double) w * scale_h : ws;
 #pragma unroll
     for (int a = 0; a < D; ++a) {
-      double wj[ROWS];
+      double wj[ROWS], wjh[ROWS];
 #pragma unroll
       for (int r = 0; r < ROWS; ++r) wj[r] = ws * (double) J[r][a];
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) wjh[r] = OWN_H ? wh * (double) J[r][a] : wj[r];
 #pragma unroll
       for (int b = a; b < D; ++b) {
         double t = FX_MAGIC;
 #pragma unroll
-        for (int r = 0; r < ROWS; ++r) t = __fma_rn(wj[r], (double) J[r][b], t);
+        for (int r = 0; r < ROWS; ++r) t = __fma_rn(wjh[r], (double) J[r][b], t);
         acc[hidx(a, b)] += fx_bits(t);
       }
       double t = FX_MAGIC;
@@ -2131,8 +2136,10 @@ namespace {
 
 __device__ float robust_weight(int kind, float thr, float chi, bool& kernelized);  // (defined with the control kernels below)
 // (PAIRS: a pair batch, srrg2_align_pairs -- every problem's fixed cloud has its own normals' norm, s.ninf_bits[prob * PAIR_ROW_WORDS])
-template <bool PAIRS = false>
-__device__ __forceinline__ int slice_exponent(const CtlParams& C, const SliceCtl& s, int prob, int nm, const float* X);
+// (GIVEN = false: the caller's slice cannot be a given-correspondences slice -- their branch, the only reader of T, is left out)
+template <bool PAIRS = false, bool GIVEN = true>
+__device__ __forceinline__ int slice_exponent(const CtlParams& C, const SliceCtl& s, int prob, int nm, const float* T,
+                                              int* kh_out = nullptr);
 template <bool ONLY_INLINE, bool PAIRS = false>
 __device__ __forceinline__ void init_problem_thread0(const CtlParams& C, int prob, const ProblemDev* probs_host, ProblemDev* probs,
                                                      ProblemState* states, const float* guesses_host, int tsize,
@@ -2917,7 +2924,9 @@ __device__ __forceinline__ void pass_view_init(const SliceDev& S, const CtlParam
     for (int i = 0; i < 12; ++i) X[i] = inl.guess[i];  // (run_compute: a prior slice's override of the guess already applied)
   }
   const int nm_of = sc.nm_global > 0 ? sc.nm_global : nm;
-  v.kexp = slice_exponent(C, sc, prob, nm_of, X);
+  // (a pass kernel with this prologue serves a nearest-neighbour or a projective slice: k_icp_step_corr, the only kernel of the
+  // given-correspondences slices, has none -- so the exponent does not read the finder transform here)
+  v.kexp = slice_exponent<false, false>(C, sc, prob, nm_of, nullptr);
   float T[12];
   finder_transform_of(sc.Sinv, DIM, X, T);
 #pragma unroll
@@ -4505,7 +4514,8 @@ __global__ __launch_bounds__(256) void k_icp_step_corr(SliceDev S, const Problem
   const ProblemDev pd = probs[prob];
   float T[12];
   load_T(st->Tf[S.slice_idx], T);
-  const double scale = dm::pow2(st->kexp[S.slice_idx]);
+  const double scale   = dm::pow2(st->kexp[S.slice_idx]);
+  const double scale_h = dm::pow2(st->kexp_h[S.slice_idx]);  // (the H terms' own exponent: slice_exponent)
   const int rk       = (st->phase == 1 && S.robust_kind != SRRG2_ROBUST_NONE) ? (int) SRRG2_ROBUST_CLAMP : S.robust_kind;
   const float kk     = S.variable_kind == SRRG2_SE3_QUAT_RIGHT ? 2.f : 1.f;
   long long acc[ACC_N];
@@ -4574,7 +4584,7 @@ __global__ __launch_bounds__(256) void k_icp_step_corr(SliceDev S, const Problem
       }
     }
     // (a pair with a non-finite point gives a non-finite chi: Suppressed)
-    S.gcorr_stat[c] = factor_accumulate<D, ROWS>(J, e, false, rk, S.robust_thr, scale, acc);
+    S.gcorr_stat[c] = factor_accumulate<D, ROWS, true>(J, e, false, rk, S.robust_thr, scale, acc, scale_h);
   }
   block_reduce_store<4>(acc, S.partials, prob, blockIdx.x);
 }
@@ -5048,8 +5058,8 @@ __global__ __launch_bounds__(256) void k_icp_step_proj_pack(SlicePack P, Problem
 // ============================================================================================
 namespace {
 
-template <bool PAIRS>
-__device__ __forceinline__ int slice_exponent(const CtlParams& C, const SliceCtl& s, int prob, int nm, const float* X) {
+template <bool PAIRS, bool GIVEN>
+__device__ __forceinline__ int slice_exponent(const CtlParams& C, const SliceCtl& s, int prob, int nm, const float* T, int* kh_out) {
   const bool plane = s.kind == SRRG2_SLICE_P2PLANE;
   const bool repro = s.kind == SRRG2_SLICE_REPROJECTION;
   const bool proj  = s.finder == SRRG2_FINDER_PROJECTIVE;
@@ -5071,14 +5081,14 @@ __device__ __forceinline__ int slice_exponent(const CtlParams& C, const SliceCtl
   if (proj) eb = (mb * (2.0 * (double) s.gate)) * 1.01;
   if (repro) eb = (double) PIX_BOUND * 1.01;
   int n_terms = nm;
-  if (s.finder == SRRG2_FINDER_CORRESPONDENCES) {
-    // no gate bounds the residual: |e_r| <= sqrt3 (sqrt3 |p|inf + |t|inf + |f|inf) with the CURRENT estimate
+  if (GIVEN && s.finder == SRRG2_FINDER_CORRESPONDENCES) {
+    // no gate bounds the residual: |e_r| <= sqrt3 (sqrt3 |p|inf + |t|inf + |f|inf), t the translation of the slice's finder
+    // transform T = robot_in_sensor * X of the CURRENT estimate -- the transform the residual is formed with (the estimate's own
+    // translation misses the sensor's offset)
+    // (T in the kernels' 3x4 slots, where an SE(2) transform has t_z = 0: finder_transform_of)
     double tmax = 0.0;
-    if (dim == 3) {
-      for (int r = 0; r < 3; ++r) tmax = fabs((double) X[r * 4 + 3]) > tmax ? fabs((double) X[r * 4 + 3]) : tmax;
-    } else {
-      for (int r = 0; r < 2; ++r) tmax = fabs((double) X[r * 3 + 2]) > tmax ? fabs((double) X[r * 3 + 2]) : tmax;
-    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) tmax = fabs((double) T[r * 4 + 3]) > tmax ? fabs((double) T[r * 4 + 3]) : tmax;
     const float finf = __uint_as_float(s.finf_bits[0]);
     eb          = ((mb * 1.7320508075688772) * ((1.7320508075688772 * (double) pinf + tmax) + (double) finf)) * 1.01;
     const int ng = s.gcorr_off[prob + 1] - s.gcorr_off[prob];
@@ -5086,6 +5096,9 @@ __device__ __forceinline__ int slice_exponent(const CtlParams& C, const SliceCtl
   }
   double mx = jb > eb ? jb : eb;
   double B  = (double) rows * (mx * mx);
+  // The H terms do not hold the residual.  Where no gate bounds it (given correspondences) a far-off estimate would otherwise
+  // coarsen the grid of H with it: those slices scale H by its own bound rows * J_b^2 (ProblemState::kexp_h).
+  if (GIVEN && kh_out && s.finder == SRRG2_FINDER_CORRESPONDENCES) *kh_out = dm::fixed_point_exponent(n_terms, (double) rows * (jb * jb));
   return dm::fixed_point_exponent(n_terms, B);
 }
 
@@ -5296,9 +5309,10 @@ __device__ void control_body(const CtlParams& C, ProblemState* st, srrg2_iterati
     for (int i = 0; i < 12; ++i) st->Tfprev[s][i] = st->Tf[s][i];
     if (!bad) finder_transform_of(C.slices[s].Sinv, C.variable_kind == SRRG2_SE2_RIGHT ? 2 : 3, st->X, st->Tf[s]);
   }
-  for (int s = 0; s < C.nslices; ++s)  // the fixed-point scale of given-correspondences slices follows the estimate
+  for (int s = 0; s < C.nslices; ++s)  // the fixed-point scale of given-correspondences slices follows the estimate: the
+                                       // translation of the slice's finder transform, updated just above
     if (C.slices[s].finder == SRRG2_FINDER_CORRESPONDENCES && C.slices[s].kind != SRRG2_SLICE_PRIOR)
-      st->kexp[s] = slice_exponent(C, C.slices[s], prob, 0, st->X);
+      st->kexp[s] = slice_exponent(C, C.slices[s], prob, 0, st->Tf[s], &st->kexp_h[s]);
   if (st->nstats < C.max_stats) stats[(size_t) prob * C.max_stats + st->nstats] = cur;
   st->nstats++;
   if (C.has_term && has_to_stop(C, st, cur)) st->done = 1;  // :124-126
@@ -5365,9 +5379,11 @@ __device__ __forceinline__ void init_problem_thread0(const CtlParams& C, int pro
     if (C.slices[s].kind == SRRG2_SLICE_PRIOR) continue;
     float Xloc[12], Tloc[12];
     for (int i = 0; i < 12; ++i) Xloc[i] = st->X[i];
-    const int kx = slice_exponent<PAIRS>(C, C.slices[s], prob, nm_of[s], Xloc);
     finder_transform_of(C.slices[s].Sinv, C.variable_kind == SRRG2_SE2_RIGHT ? 2 : 3, Xloc, Tloc);
-    st->kexp[s] = kx;
+    int kh       = 0;  // (read on given-correspondences slices only)
+    const int kx = slice_exponent<PAIRS>(C, C.slices[s], prob, nm_of[s], Tloc, &kh);
+    st->kexp[s]   = kx;
+    st->kexp_h[s] = kh;
     for (int i = 0; i < 12; ++i) st->Tf[s][i] = st->Tfprev[s][i] = Tloc[i];
     if (C.pub) {  // fused control steps: the record of epoch 0, staged for the wave (from the registers: read back from the
                   // state just stored, 64 dependent loads took the kernel from 7 to 17 us)
@@ -5504,7 +5520,8 @@ __device__ void icp_control_block(const CtlParams& C, ProblemState* st, srrg2_it
 #pragma unroll
       for (int k = 0; k < 8; ++k) t += part[k][threadIdx.x];
       sums[s][threadIdx.x]   = t;
-      scaled[s][threadIdx.x] = (double) t * dm::pow2(-st->kexp[s]);
+      const bool own_h       = sc.finder == SRRG2_FINDER_CORRESPONDENCES && threadIdx.x < ACC_B;  // (H of given pairs: kexp_h)
+      scaled[s][threadIdx.x] = (double) t * dm::pow2(-(own_h ? st->kexp_h[s] : st->kexp[s]));
     }
     __syncthreads();
   }
