@@ -1128,6 +1128,66 @@ int srrg2_adapt_stereo_features(srrg2_scene_h dst /* dim 3 */, const void* left,
                                 srrg2_stereo_match* matches_out /* host, may be NULL */, int match_capacity,
                                 srrg2_stereo_result* out /* may be NULL */);
 
+/* Feature tracking: which keypoint of the measurement is which landmark of the clipped local map -- the per-frame data
+ * association of a visual tracker, a projective window plus the Hamming distance of the 256-bit descriptors.  The reference
+ * declares the slot and leaves it empty (CorrespondenceFinder_::compute() is pure virtual, S/registration/correspondence_finder.h:56;
+ * its inputs are setFixed, setMoving and setLocalMapInSensor, :80-114).  DESIGN.md section 4 "Feature tracking" is the contract,
+ * tests/tracking_restatement.py restates it and the library gives the same bits.
+ *   fixed     the measurement: a dim-3 scene with descriptors whose srrg2_scene_global_indices are pixel indices r*cols + c in
+ *             strictly ascending order (what srrg2_adapt_image_features / _stereo_features write, or a clip of such a scene).
+ *             Keypoint j is fixed point j, its pixel its global index.  Its coordinates are NOT read: a keypoint with a non-finite
+ *             point still matches (the aligner reports such a given pair as Suppressed).
+ *   moving    the clipped local map: a dim-3 scene with descriptors, in any order.
+ *   project   a landmark with a non-finite coordinate is not in view; else c = moving_in_sensor * p (rows as ((m0 x + m1 y) + m2 z)
+ *             + m3, float32, no FMA) and the steps of srrg2_scene_clip_projective: depth_min <= c.z <= depth_max,
+ *             u = (K0 c.x) / c.z + K2, v = (K4 c.y) / c.z + K5, in view iff 0 <= u + 0.5 < cols and 0 <= v + 0.5 < rows,
+ *             cu = floor(u + 0.5), rv = floor(v + 0.5).
+ *   candidates  of landmark i: the keypoints j with |r_j - rv| <= search_radius and |c_j - cu| <= search_radius.
+ *   best      the candidate of smallest (Hamming distance h, j); accepted iff h <= max_distance and -- min_margin > 0 --
+ *             h2 - h >= min_margin, h2 being the smallest distance among the OTHER candidates (a lone candidate passes).
+ *   cross     cross_check: per keypoint j, of the landmarks that have j as a candidate, the one of smallest (h, i); landmark i stays
+ *             iff its best keypoint's best is i.  No gate is applied in that direction (as in the stereo matcher).
+ *   output    the surviving pairs in ascending i as {fixed_idx = j, moving_idx = i, response = (float) h}: the aligner's
+ *             convention for srrg2_aligner_set_correspondences (measurement fixed, clipped map moving).  moving_idx is the index
+ *             in `moving`; srrg2_scene_global_indices(moving) leads to the map.  correspondences_out (host, may be NULL) receives
+ *             min(capacity, num_correspondences) records; num_correspondences is not limited by capacity.
+ *   refused   nothing is written.  SRRG2_E_INVALID: a null handle, pose or params; moving == fixed; different devices; a dim other
+ *             than 3; rows or cols <= 0 or rows*cols beyond int32; fx or fy zero or not finite; !(depth_min > 0) or
+ *             !(depth_max >= depth_min); search_radius outside 0 .. 255; max_distance or min_margin outside 0 .. 256; cross_check
+ *             not 0 / 1; reserved != 0; capacity < 0; a non-finite moving_in_sensor; fixed global indices that do not ascend
+ *             strictly inside [0, rows*cols) (found on the device, reported at the call's host wait).  SRRG2_E_UNSUPPORTED: K with
+ *             skew (K[0][1] != 0), as the clipper.  SRRG2_E_STATE: a non-empty scene without descriptors; a non-empty fixed scene
+ *             whose global indices do not cover its points (srrg2_scene_set leaves none).
+ *   empty     an empty scene on either side: 0, no correspondences, the counters filled (an empty `moving` returns before the
+ *             device is asked: fixed's indices are then not looked at).
+ *   waits     ONE host wait: the counters, the error word, the number of pairs and the capacity-bounded records come back in one
+ *             copy.  Both scenes are left as they were; the workspaces live on `moving`, a steady-state call allocates nothing.
+ * search_radius 16 and max_distance 48 are UNTUNED defaults: nobody has derived or measured them. */
+typedef struct srrg2_track_params {
+  float   camera_matrix[9];      /* row-major K; K[0][1] != 0 -> SRRG2_E_UNSUPPORTED (as the clipper) */
+  int32_t image_rows, image_cols;
+  float   depth_min, depth_max;  /* gate on the landmark's c.z, as srrg2_scene_clip_projective; default 0.4, 8 */
+  int32_t search_radius;         /* pixels, 0 .. 255, default 16 (untuned): the window is the square |dr| <= R, |dc| <= R */
+  int32_t max_distance;          /* 0 .. 256, default 48 (untuned): largest accepted Hamming distance */
+  int32_t min_margin;            /* 0 .. 256, default 0 = off; else second-best distance - best distance >= min_margin */
+  int32_t cross_check;           /* 0 | 1, default 1 */
+  int32_t reserved;              /* 0 */
+} srrg2_track_params;            /* 72 bytes */
+typedef struct srrg2_track_result {
+  int32_t num_moving, num_fixed;
+  int32_t num_in_view;           /* landmarks that project into the image inside the depth gate */
+  int32_t num_with_candidate;    /* ... with at least one keypoint in their window */
+  int32_t num_accepted;          /* ... whose best passes max_distance and min_margin */
+  int32_t num_mutual;            /* ... that survive the cross check (= num_accepted when it is off) */
+  int32_t num_correspondences;   /* == num_mutual; NOT limited by capacity */
+  int32_t reserved;
+} srrg2_track_result;            /* 32 bytes */
+/* K, rows and cols zero (the caller must set them), depth 0.4 .. 8, search_radius 16, max_distance 48, min_margin 0, cross_check 1 */
+void srrg2_track_default_params(srrg2_track_params* p);
+int srrg2_scene_track_features(srrg2_scene_h moving, srrg2_scene_h fixed, const float* moving_in_sensor /* 3x4 */,
+                               const srrg2_track_params* p, srrg2_correspondence* correspondences_out /* host, may be NULL */,
+                               int capacity, srrg2_track_result* out /* may be NULL */);
+
 /* ---- strategy knobs (no reference counterpart) ----------------------------------------------------------------
  * Every setting gives the SAME results (indices, estimates, statistics bit for bit): the knobs choose between exact
  * strategies of the finder / reduction / control step.  A handle starts from srrg2_aligner_default_tuning() overridden

@@ -676,6 +676,46 @@ private:
   Status _status = Error;
 };
 
+// the per-frame data association of a visual tracker (srrg2_scene_track_features): which keypoint of the measurement (fixed) is
+// which landmark of the clipped local map (moving), by projective window and Hamming distance -- a concrete
+// CorrespondenceFinder_ (S/registration/correspondence_finder.h:56-114: setFixed / setMoving / setLocalMapInSensor / compute).
+// param: camera matrix, image size, depth range, search_radius, max_distance, min_margin, cross_check.  correspondences() is
+// what MultiAligner_::setCorrespondences takes; toMerger() flips and globalises it for MergerCorrespondenceHomo.
+class FeatureTracker {
+public:
+  srrg2_track_params param;
+  FeatureTracker() { srrg2_track_default_params(&param); }
+  void setCameraMatrix(const float* K_row_major) { std::memcpy(param.camera_matrix, K_row_major, sizeof(param.camera_matrix)); }
+  void setFixed(const Scene<3>* measurement) { _fixed = measurement; }
+  void setMoving(Scene<3>* clipped_map) { _moving = clipped_map; }
+  void setMovingInSensor(const Isometry3f& T) { _T = T; }
+  void compute() {
+    if (!_fixed || !_moving) throw std::runtime_error("FeatureTracker::compute|fixed or moving not set");
+    _corr.assign((size_t) _moving->size(), Correspondence{});  // (at most one pair per landmark)
+    _result = srrg2_track_result{};
+    check(srrg2_scene_track_features(_moving->handle(), _fixed->handle(), _T.data(), &param, _corr.data(), (int) _corr.size(),
+                                     &_result));
+    _corr.resize((size_t) _result.num_correspondences);
+  }
+  const CorrespondenceVector& correspondences() const { return _corr; }
+  const srrg2_track_result& result() const { return _result; }
+  // {fixed_idx = map point, moving_idx = measurement point}: the pairs as the merger reads them
+  // (TrackerSliceProcessor_::merge(), tracker_slice_processor_impl.cpp:160-186); moving_global_indices = the clipped map's
+  static CorrespondenceVector toMerger(const CorrespondenceVector& corr, const std::vector<int>& moving_global_indices) {
+    CorrespondenceVector out(corr.size());
+    for (size_t k = 0; k < corr.size(); ++k)
+      out[k] = Correspondence{moving_global_indices.at((size_t) corr[k].moving_idx), corr[k].fixed_idx, corr[k].response};
+    return out;
+  }
+
+private:
+  const Scene<3>* _fixed = nullptr;
+  Scene<3>* _moving      = nullptr;
+  Isometry3f _T          = Isometry3f::Identity();
+  CorrespondenceVector _corr;
+  srrg2_track_result _result{};
+};
+
 // ---- measurement adaptors: RawDataPreprocessor_ (S/raw_data_preprocessors/raw_data_preprocessor.h:13-88) -------------
 //   DepthImageAdaptor   depth image (+ intensity image) -> Scene<3>, organised or compact, with normals
 //   LaserScanAdaptor    ranges -> Scene<2> with normals

@@ -28,6 +28,14 @@ def scene_binding(device=0):
     return _Binding(l, "srrg2_scene_", l.srrg2_amd_last_error, device)
 
 
+def FeatureTracker(params=None, device=0):
+    """Per-frame data association of a visual tracker on the HIP library: keypoints of the measurement against the landmarks of
+    the clipped local map, by projective window and descriptor distance; see ``mapping.FeatureTracker``."""
+    from .mapping import FeatureTracker as _FT
+
+    return _FT(scene_binding(device), params)
+
+
 def DescriptorDatabase(device=0):
     """Device-resident database of 256-bit binary descriptors with exact matching (the matching half of the HBST loop
     detector; raises if the library or a HIP device is missing)."""

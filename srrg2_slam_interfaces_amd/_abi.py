@@ -249,6 +249,22 @@ class StereoResult(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class TrackParams(C.Structure):
+    """srrg2_track_params"""
+    _fields_ = [("camera_matrix", C.c_float * 9), ("image_rows", C.c_int32), ("image_cols", C.c_int32), ("depth_min", C.c_float),
+                ("depth_max", C.c_float), ("search_radius", C.c_int32), ("max_distance", C.c_int32), ("min_margin", C.c_int32),
+                ("cross_check", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TrackResult(C.Structure):
+    """srrg2_track_result"""
+    _fields_ = [("num_moving", C.c_int32), ("num_fixed", C.c_int32), ("num_in_view", C.c_int32), ("num_with_candidate", C.c_int32),
+                ("num_accepted", C.c_int32), ("num_mutual", C.c_int32), ("num_correspondences", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class NormalsParams(C.Structure):
     """srrg2_normals_params"""
     _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_int32), ("max_curvature", C.c_float), ("viewpoint", C.c_float * 3),

@@ -81,6 +81,11 @@ def lib():
                                                      C.POINTER(abi.DepthAdaptorParams), C.POINTER(abi.FeatureParams),
                                                      C.POINTER(abi.StereoParams), C.POINTER(abi.Keypoint), C.c_int,
                                                      C.POINTER(abi.StereoMatch), C.c_int, C.POINTER(abi.StereoResult)]
+        # srrg2_scene_track_features (mapping.FeatureTracker)
+        _LIB.srrg2_track_default_params.argtypes = [C.POINTER(abi.TrackParams)]
+        _LIB.srrg2_track_default_params.restype = None
+        _LIB.srrg2_scene_track_features.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(abi.TrackParams),
+                                                    C.c_void_p, C.c_int, C.POINTER(abi.TrackResult)]
         # srrg2_scene_clip_projective (mapping.SceneClipperProjective)
         from . import mapping
 

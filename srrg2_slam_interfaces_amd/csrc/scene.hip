@@ -830,6 +830,9 @@ int srrg2_scene_destroy(srrg2_scene_h s) {
   for (int i = 0; i < 2; ++i) {
     s->st_pixel[i].release(); s->st_rows[i].release(); s->st_desc[i].release(); s->st_kp[i].release(); s->st_best[i].release();
   }
+  s->trk_pix.release(); s->trk_rows.release(); s->trk_second.release(); s->trk_best.release(); s->trk_best_fixed.release();
+  s->trk_rec.release(); s->trk_out.release();
+  if (s->trk_host) (void) hipHostFree(s->trk_host);
   if (s->scalars) (void) hipHostFree(s->scalars);
   if (s->stream) (void) hipStreamDestroy(s->stream);
   delete s;

@@ -71,6 +71,18 @@ struct srrg2_scene {
   srrg2amd::DevBuf<unsigned long long> st_best[2];
   srrg2amd::DevBuf<srrg2_stereo_match> st_match, st_match_out;
   srrg2amd::DevBuf<float> st_z;
+  // track_features (tracking.hip; on the MOVING scene, whose flags / scan_sums hold the keep flags and their scan): per landmark
+  // its projected pixel (-1 = not in view), its best keypoint (distance << 32 | keypoint index, all ones = none), the smallest
+  // distance among its other candidates and its record; per image row + 1 the first keypoint at or below it; per keypoint the
+  // best landmark (distance << 32 | landmark index); the counters + error word with the capacity-bounded compacted records
+  // behind them in ONE block, and that block's pinned host mirror
+  srrg2amd::DevBuf<int> trk_pix, trk_rows;
+  srrg2amd::DevBuf<unsigned> trk_second;
+  srrg2amd::DevBuf<unsigned long long> trk_best, trk_best_fixed;
+  srrg2amd::DevBuf<srrg2_correspondence> trk_rec;
+  srrg2amd::DevBuf<int> trk_out;
+  int* trk_host       = nullptr;
+  size_t trk_host_cap = 0;  // words
   int* scalars = nullptr;  // pinned host mirror of dscalars
   // device: [1] num_merged, [2] error flag, [3] duplicates seen, [4] ncorr (merge); [0] Valid, [1] in view, [2] scan total (clip);
   // [8] in range, [9] Valid (adapt)

@@ -1,0 +1,303 @@
+// tracking.hip -- srrg2_scene_track_features: which keypoint of the measurement is which landmark of the clipped local map, on
+// the device.  The reference declares this slot and leaves it empty (CorrespondenceFinder_::compute() is pure virtual,
+// S/registration/correspondence_finder.h:56); DESIGN.md section 4 "Feature tracking" is the contract and
+// tests/tracking_restatement.py its executable form.  The projection is that of srrg2_scene_clip_projective, operation for
+// operation, in float32; everything behind it is integer arithmetic: the result is a function of the two scenes, the pose and the
+// parameters alone, bit for bit.
+//   k_track_project   one thread per landmark: its pixel rv * cols + cu, or -1 when it is not in view
+//   k_track_rows      row_begin[rows + 1] from the keypoints' pixels (as stereo.hip's k_stereo_rows); the same pass checks that
+//                     the pixels ascend strictly inside the image and raises the error word otherwise
+//   k_track_best      one wave per landmark: the lanes stride over the keypoints of rows rv - R .. rv + R (one contiguous range),
+//                     gate the column, take the Hamming distance (two 16-byte loads per side, four popcounts) and keep the
+//                     smallest (distance << 32 | keypoint index) and the smallest distance of any other candidate; a shuffle
+//                     reduction merges the (best, second) pairs.  With the cross check every evaluated pair also sends ONE 64-bit
+//                     atomicMin (distance << 32 | landmark index) to its keypoint's word: a minimum does not depend on the order
+//   k_track_resolve   one thread per landmark: the gates, the cross check, the record and the keep flag; the four counters are
+//                     block sums with one atomic per block and counter
+//   (exclusive scan of the keep flags: srrg2amd::launch_exclusive_scan, what srrg2amd::scene_scan_flags runs -- its total rides
+//   on the call's one wait)
+//   k_track_scatter   kept landmark -> its slot of the capacity-bounded output, behind the counters in one block
+// No launch is capped: every kernel has one thread (or wave) per element and no loop behind a cap.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+
+#include "host_util.h"
+#include "kernels.h"
+#include "scene_state.h"
+
+using srrg2amd::fail;
+
+namespace {
+
+// words of the output block (srrg2_scene::trk_out): the counters, the error word, the scan's total; the records from T_WORDS on
+enum { T_IN_VIEW = 0, T_CANDIDATE = 1, T_ACCEPTED = 2, T_MUTUAL = 3, T_ERROR = 4, T_TOTAL = 5, T_WORDS = 8 };
+constexpr unsigned long long NO_CANDIDATE = ~0ull;
+constexpr unsigned NO_SECOND              = 0xffffffffu;  // (= the distance field of NO_CANDIDATE)
+
+struct TrackCam {
+  float m[12];  // rows of moving_in_sensor
+  float K0, K2, K4, K5, depth_min, depth_max;
+  int rows, cols;
+};
+
+// srrg2_scene_clip_projective's steps behind its two transforms (scene.hip pclip_project): the same operations in the same order
+__global__ __launch_bounds__(256) void k_track_project(TrackCam C, const float4* __restrict__ pts, int n, int* __restrict__ pix) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = pts[i];
+  int out = -1;
+  if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
+    const float cx = ((C.m[0] * p.x + C.m[1] * p.y) + C.m[2] * p.z) + C.m[3];
+    const float cy = ((C.m[4] * p.x + C.m[5] * p.y) + C.m[6] * p.z) + C.m[7];
+    const float cz = ((C.m[8] * p.x + C.m[9] * p.y) + C.m[10] * p.z) + C.m[11];
+    if (isfinite(cx) && isfinite(cy) && isfinite(cz) && cz >= C.depth_min && cz <= C.depth_max) {
+      const float u  = (C.K0 * cx) / cz + C.K2;
+      const float v  = (C.K4 * cy) / cz + C.K5;
+      const float uf = u + 0.5f, vf = v + 0.5f;
+      if (uf >= 0.f && uf < (float) C.cols && vf >= 0.f && vf < (float) C.rows) out = (int) floorf(vf) * C.cols + (int) floorf(uf);
+    }
+  }
+  pix[i] = out;
+}
+
+// pixel: n keypoints' pixel indices.  row_begin[r] = the first keypoint in row r or below it, row_begin[rows] = n.  A pixel
+// outside [0, rows * cols) or not above its predecessor raises *error; the rows are clamped into the image first, so that every
+// write stays inside row_begin whatever the pixels are (the kernels behind this one do nothing once *error is set).
+__global__ __launch_bounds__(256) void k_track_rows(const int* __restrict__ pixel, int n, int rows, int cols, int* __restrict__ row_begin,
+                                                    int* __restrict__ error) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n) return;
+  int cur = rows, prev = -1;
+  if (i < n) {
+    const int p = pixel[i];
+    if (p < 0 || p >= rows * cols || (i > 0 && pixel[i - 1] >= p)) *error = 1;
+    cur = min(max(p / cols, 0), rows - 1);
+  }
+  if (i > 0) prev = min(max(pixel[i - 1] / cols, 0), rows - 1);
+  for (int r = prev + 1; r <= cur; ++r) row_begin[r] = i;
+}
+
+__device__ __forceinline__ int hamming(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
+  const unsigned long long w0 = (unsigned long long) (a0.x ^ b0.x) | ((unsigned long long) (a0.y ^ b0.y) << 32);
+  const unsigned long long w1 = (unsigned long long) (a0.z ^ b0.z) | ((unsigned long long) (a0.w ^ b0.w) << 32);
+  const unsigned long long w2 = (unsigned long long) (a1.x ^ b1.x) | ((unsigned long long) (a1.y ^ b1.y) << 32);
+  const unsigned long long w3 = (unsigned long long) (a1.z ^ b1.z) | ((unsigned long long) (a1.w ^ b1.w) << 32);
+  return (__popcll(w0) + __popcll(w1)) + (__popcll(w2) + __popcll(w3));
+}
+
+// (best, second) of two disjoint candidate sets -> of their union: the smaller key wins; the loser's distance is a distance of
+// "another candidate", as both seconds are.  NO_CANDIDATE's distance field is NO_SECOND: an empty side adds nothing.
+__device__ __forceinline__ void merge_best(unsigned long long& key, unsigned& second, unsigned long long k, unsigned s) {
+  const unsigned long long loser = k < key ? key : k;
+  key                            = k < key ? k : key;
+  second                         = min(min(second, s), (unsigned) (loser >> 32));
+}
+
+// One wave per landmark (4 per workgroup).  best_fixed null: no cross check, no atomics.
+__global__ __launch_bounds__(256) void k_track_best(int nm, const int* __restrict__ m_pix, const uint4* __restrict__ m_desc,
+                                                    const int* __restrict__ f_pixel, const uint4* __restrict__ f_desc,
+                                                    const int* __restrict__ row_begin, int rows, int cols, int radius,
+                                                    const int* __restrict__ error, unsigned long long* __restrict__ best,
+                                                    unsigned* __restrict__ second, unsigned long long* __restrict__ best_fixed) {
+  const int lane = threadIdx.x & 63;
+  const int i    = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= nm) return;  // (the whole wave)
+  unsigned long long key = NO_CANDIDATE;
+  unsigned sec           = NO_SECOND;
+  const int pixel        = m_pix[i];
+  if (pixel >= 0 && *error == 0) {  // (the same for every lane)
+    const int rv = pixel / cols, cu = pixel - rv * cols;
+    const int begin = row_begin[max(rv - radius, 0)], end = row_begin[min(rv + radius, rows - 1) + 1];
+    const uint4 a0 = m_desc[2 * (size_t) i], a1 = m_desc[2 * (size_t) i + 1];
+    for (int j = begin + lane; j < end; j += 64) {
+      const int fp = f_pixel[j];
+      const int dc = (fp - (fp / cols) * cols) - cu;
+      if (dc >= -radius && dc <= radius) {
+        const unsigned h = (unsigned) hamming(a0, a1, f_desc[2 * (size_t) j], f_desc[2 * (size_t) j + 1]);
+        merge_best(key, sec, ((unsigned long long) h << 32) | (unsigned) j, NO_SECOND);
+        if (best_fixed) atomicMin(&best_fixed[j], ((unsigned long long) h << 32) | (unsigned) i);
+      }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const unsigned long long k = __shfl_xor(key, off);
+      const unsigned s           = __shfl_xor(sec, off);
+      merge_best(key, sec, k, s);
+    }
+  }
+  if (lane == 0) {
+    best[i]   = key;
+    second[i] = sec;
+  }
+}
+
+// block sum -> ONE atomic per block (blockDim = 256)
+__device__ __forceinline__ void block_add(int v, int* target, int* red) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int t = (red[0] + red[1]) + (red[2] + red[3]);
+    if (t) atomicAdd(target, t);
+  }
+}
+
+// One thread per landmark; cross = 0: best_fixed is not read.  counters: the output block's first words.
+__global__ __launch_bounds__(256) void k_track_resolve(int nm, const int* __restrict__ m_pix, const unsigned long long* __restrict__ best,
+                                                       const unsigned* __restrict__ second,
+                                                       const unsigned long long* __restrict__ best_fixed, int max_distance,
+                                                       int min_margin, int cross, srrg2_correspondence* __restrict__ rec,
+                                                       int* __restrict__ flags, int* __restrict__ counters) {
+  __shared__ int red[4][4];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  int in_view = 0, candidate = 0, accepted = 0, mutual = 0;
+  if (i < nm && counters[T_ERROR] == 0) {
+    in_view                    = m_pix[i] >= 0 ? 1 : 0;
+    const unsigned long long k = best[i];
+    const unsigned h = (unsigned) (k >> 32), s = second[i];
+    const int j = (int) (unsigned) (k & 0xffffffffull);
+    candidate   = k != NO_CANDIDATE ? 1 : 0;
+    accepted    = candidate && (int) h <= max_distance && (min_margin == 0 || s == NO_SECOND || (int) (s - h) >= min_margin) ? 1 : 0;
+    mutual      = accepted && (!cross || (int) (unsigned) (best_fixed[j] & 0xffffffffull) == i) ? 1 : 0;
+    srrg2_correspondence c;
+    c.fixed_idx = mutual ? j : -1, c.moving_idx = i, c.response = mutual ? (float) h : 0.f;
+    rec[i] = c;
+  }
+  if (i < nm) flags[i] = mutual;
+  block_add(in_view, &counters[T_IN_VIEW], red[0]);
+  block_add(candidate, &counters[T_CANDIDATE], red[1]);
+  block_add(accepted, &counters[T_ACCEPTED], red[2]);
+  block_add(mutual, &counters[T_MUTUAL], red[3]);
+}
+
+// offset: the exclusive scan of the keep flags (nm + 1 words); out holds cap records
+__global__ __launch_bounds__(256) void k_track_scatter(int nm, const int* __restrict__ offset, const srrg2_correspondence* __restrict__ rec,
+                                                       srrg2_correspondence* __restrict__ out, int cap) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nm) return;
+  const int k = offset[i];
+  if (offset[i + 1] == k || k < 0 || k >= cap) return;
+  out[k] = rec[i];
+}
+
+unsigned blocks_of(long long threads) { return (unsigned) ((threads + 255) / 256); }
+
+}  // namespace
+
+extern "C" void srrg2_track_default_params(srrg2_track_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->depth_min     = 0.4f;  // (the projective clipper's interval)
+  p->depth_max     = 8.f;
+  p->search_radius = 16;  // untuned
+  p->max_distance  = 48;  // untuned, as the stereo matcher's
+  p->min_margin    = 0;
+  p->cross_check   = 1;
+}
+
+extern "C" int srrg2_scene_track_features(srrg2_scene_h moving, srrg2_scene_h fixed, const float* moving_in_sensor,
+                                          const srrg2_track_params* p, srrg2_correspondence* correspondences_out, int capacity,
+                                          srrg2_track_result* out) {
+  const std::string who = "scene_track_features: ";
+  if (!moving || !fixed || !moving_in_sensor || !p) return fail(SRRG2_E_INVALID, who + "null scene, pose or params");
+  if (moving == fixed || moving->device != fixed->device)
+    return fail(SRRG2_E_INVALID, who + "moving and fixed must be two scenes on one device");
+  if (moving->dim != 3 || fixed->dim != 3) return fail(SRRG2_E_INVALID, who + "both scenes must have dim 3");
+  if (p->image_rows <= 0 || p->image_cols <= 0 || (long long) p->image_rows * (long long) p->image_cols > 0x7fffffffLL)
+    return fail(SRRG2_E_INVALID, who + "image_rows, image_cols > 0 and rows*cols within int32");
+  const float fx = p->camera_matrix[0], fy = p->camera_matrix[4];
+  if (!std::isfinite(fx) || !std::isfinite(fy) || fx == 0.f || fy == 0.f)
+    return fail(SRRG2_E_INVALID, who + "fx and fy must be finite and non-zero");
+  if (!(p->depth_min > 0.f) || !(p->depth_max >= p->depth_min)) return fail(SRRG2_E_INVALID, who + "0 < depth_min <= depth_max");
+  if (p->search_radius < 0 || p->search_radius > 255) return fail(SRRG2_E_INVALID, who + "search_radius 0 .. 255");
+  if (p->max_distance < 0 || p->max_distance > 256) return fail(SRRG2_E_INVALID, who + "max_distance 0 .. 256");
+  if (p->min_margin < 0 || p->min_margin > 256) return fail(SRRG2_E_INVALID, who + "min_margin 0 .. 256");
+  if (p->cross_check != 0 && p->cross_check != 1) return fail(SRRG2_E_INVALID, who + "cross_check must be 0 or 1");
+  if (p->reserved != 0) return fail(SRRG2_E_INVALID, who + "reserved must be 0");
+  if (capacity < 0) return fail(SRRG2_E_INVALID, who + "capacity >= 0");
+  for (int k = 0; k < 12; ++k)
+    if (!std::isfinite(moving_in_sensor[k])) return fail(SRRG2_E_INVALID, who + "moving_in_sensor is not finite");
+  if (p->camera_matrix[1] != 0.f) return fail(SRRG2_E_UNSUPPORTED, who + "a camera matrix with skew (K[0][1] != 0)");
+  srrg2_scene* const s = moving;
+  HIP_TRY(hipSetDevice(s->device));
+  for (srrg2_scene* q : {moving, fixed})
+    if (q->pending) {  // an adaptor's queued write
+      HIP_TRY(hipStreamSynchronize(q->stream));
+      q->pending = false;
+    }
+  const int nm = moving->n, nf = fixed->n;
+  if ((nm > 0 && !moving->has_desc) || (nf > 0 && !fixed->has_desc)) return fail(SRRG2_E_STATE, who + "a scene without descriptors");
+  if (nf > 0 && fixed->ng != nf)
+    return fail(SRRG2_E_STATE, who + "the fixed scene has no global indices (an adaptor's or a clipper's output has)");
+  srrg2_track_result res;
+  std::memset(&res, 0, sizeof(res));
+  res.num_moving = nm, res.num_fixed = nf;
+  if (nm == 0) {  // nothing to project: the device is not asked (fixed's pixels stay unchecked)
+    if (out) *out = res;
+    return 0;
+  }
+
+  int rc;
+  hipStream_t st = s->stream;
+  const int rows = p->image_rows, cols = p->image_cols;
+  const int cap       = capacity < nm ? capacity : nm;  // (records the output block has room for)
+  const size_t words  = (size_t) T_WORDS + 3 * (size_t) cap;
+  static_assert(sizeof(srrg2_correspondence) == 12, "three words per record");
+  if ((rc = s->trk_pix.reserve((size_t) nm)) || (rc = s->trk_best.reserve((size_t) nm)) || (rc = s->trk_second.reserve((size_t) nm)) ||
+      (rc = s->trk_rec.reserve((size_t) nm)) || (rc = s->trk_rows.reserve((size_t) rows + 1)) ||
+      (rc = s->trk_best_fixed.reserve((size_t) nf + 1)) || (rc = s->trk_out.reserve(words)) ||
+      (rc = s->flags.reserve((size_t) nm + 1)) || (rc = s->scan_sums.reserve((size_t) srrg2amd::scan_num_blocks(nm) + 2)))
+    return rc;
+  if (s->trk_host_cap < words) {
+    if (s->trk_host) (void) hipHostFree(s->trk_host);
+    s->trk_host     = nullptr;
+    s->trk_host_cap = 0;
+    const size_t want = words + words / 8 + 64;
+    HIP_TRY(hipHostMalloc((void**) &s->trk_host, want * sizeof(int), hipHostMallocDefault));
+    s->trk_host_cap = want;
+  }
+  TrackCam C;
+  std::memcpy(C.m, moving_in_sensor, sizeof(C.m));
+  C.K0 = fx, C.K2 = p->camera_matrix[2], C.K4 = fy, C.K5 = p->camera_matrix[5];
+  C.depth_min = p->depth_min, C.depth_max = p->depth_max;
+  C.rows = rows, C.cols = cols;
+  int* const block                   = s->trk_out.p;
+  srrg2_correspondence* const d_recs = reinterpret_cast<srrg2_correspondence*>(block + T_WORDS);
+  unsigned long long* const reverse  = p->cross_check ? s->trk_best_fixed.p : nullptr;
+
+  HIP_TRY(hipMemsetAsync(block, 0, T_WORDS * sizeof(int), st));
+  if (reverse) HIP_TRY(hipMemsetAsync(reverse, 0xff, sizeof(unsigned long long) * (size_t) (nf + 1), st));
+  hipLaunchKernelGGL(k_track_project, dim3(blocks_of(nm)), dim3(256), 0, st, C, moving->pts.p, nm, s->trk_pix.p);
+  hipLaunchKernelGGL(k_track_rows, dim3(blocks_of((long long) nf + 1)), dim3(256), 0, st, fixed->gidx.p, nf, rows, cols, s->trk_rows.p,
+                     block + T_ERROR);
+  hipLaunchKernelGGL(k_track_best, dim3((unsigned) ((nm + 3) / 4)), dim3(256), 0, st, nm, s->trk_pix.p, moving->desc.p, fixed->gidx.p,
+                     fixed->desc.p, s->trk_rows.p, rows, cols, p->search_radius, block + T_ERROR, s->trk_best.p, s->trk_second.p,
+                     reverse);
+  hipLaunchKernelGGL(k_track_resolve, dim3(blocks_of(nm)), dim3(256), 0, st, nm, s->trk_pix.p, s->trk_best.p, s->trk_second.p, reverse,
+                     p->max_distance, p->min_margin, p->cross_check, s->trk_rec.p, s->flags.p, block);
+  srrg2amd::launch_exclusive_scan(s->flags.p, nm, s->scan_sums.p, block + T_TOTAL, st);
+  if (cap > 0) hipLaunchKernelGGL(k_track_scatter, dim3(blocks_of(nm)), dim3(256), 0, st, nm, s->flags.p, s->trk_rec.p, d_recs, cap);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(s->trk_host, block, words * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));  // the call's one host wait: counters, error word, total and records together
+
+  const int* const h = s->trk_host;
+  if (h[T_ERROR])
+    return fail(SRRG2_E_INVALID, who + "the fixed scene's global indices must ascend strictly inside [0, rows*cols)");
+  const int total = h[T_TOTAL];
+  if (total < 0 || total > nm || total != h[T_MUTUAL]) return fail(SRRG2_E_HIP, who + "the compaction scan returned a total out of range");
+  const int give = correspondences_out ? (total < cap ? total : cap) : 0;
+  if (give > 0) std::memcpy(correspondences_out, h + T_WORDS, sizeof(srrg2_correspondence) * (size_t) give);
+  res.num_in_view         = h[T_IN_VIEW];
+  res.num_with_candidate  = h[T_CANDIDATE];
+  res.num_accepted        = h[T_ACCEPTED];
+  res.num_mutual          = h[T_MUTUAL];
+  res.num_correspondences = total;
+  if (out) *out = res;
+  return 0;
+}

@@ -7,6 +7,8 @@
 ``SceneClipperProjective``     the same interface with the projective policy: what a pinhole camera sees (3-D, product library)
 ``SceneClipperScan``           the same interface with the scan policy: what a planar laser scanner sees (2-D, product library)
 ``SceneClipperSpherical``      the same interface with the spherical policy: what a spinning 3-D lidar sees (3-D, product library)
+``FeatureTracker``             a concrete ``CorrespondenceFinder_``: keypoints of the measurement against the landmarks of the clipped
+                               map by projective window and descriptor distance (3-D, product library); ``to_merger`` flips its pairs
 ``MergerCorrespondenceHomo``   ``MergerCorrespondenceHomo_`` (S/mapping/merger_correspondence_homo_impl.cpp:11-125)
 
 Method names follow the reference setters (snake_case).  Thin marshalling only; parametrised by
@@ -424,6 +426,83 @@ class SceneClipperSpherical(_ViewClipperBase):
             raise ValueError("ring elevations: %d entries for %d rows" % (self._rings.shape[0], self.params.model.rows))
         return self._b.fn("clip_spherical_rings")(self._full._h, _fp(self._robot_in_local_map), C.byref(self.params),
                                                   self._rings.ctypes.data_as(C.POINTER(C.c_double)), self._clipped._h, out)
+
+
+TrackParams, TrackResult = abi.TrackParams, abi.TrackResult
+CORR_DTYPE = np.dtype([("fixed_idx", np.int32), ("moving_idx", np.int32), ("response", np.float32)])
+
+
+def default_track_params():
+    """depth 0.4 .. 8 m, search_radius 16, max_distance 48, min_margin 0 (off), cross_check 1; camera matrix / rows / cols are
+    the caller's"""
+    from . import _capi
+
+    p = TrackParams()
+    _capi.lib().srrg2_track_default_params(C.byref(p))
+    return p
+
+
+def to_merger(corr, moving_global_indices):
+    """a FeatureTracker result (fixed_idx = measurement point, moving_idx = point of the clipped map) flipped and globalised on
+    the host, as TrackerSliceProcessor_::merge() does (tracker_slice_processor_impl.cpp:160-186): fixed_idx = map point
+    (``moving_global_indices`` = the clipped scene's global_indices()), moving_idx = measurement point, response kept.  What
+    ``MergerCorrespondenceHomo.set_correspondences`` takes."""
+    g = np.asarray(moving_global_indices, np.int32).reshape(-1)
+    out = np.zeros(len(corr), CORR_DTYPE)
+    out["fixed_idx"] = g[np.asarray(corr["moving_idx"], np.int64)]
+    out["moving_idx"] = corr["fixed_idx"]
+    out["response"] = corr["response"]
+    return out
+
+
+class FeatureTracker:
+    """setFixed / setMoving / setLocalMapInSensor / compute of the reference's CorrespondenceFinder_
+    (S/registration/correspondence_finder.h:56-114), made concrete for clouds with descriptors (srrg2_scene_track_features;
+    product library only).  ``fixed``: the measurement, a scene of keypoints whose global indices are pixel indices (an image
+    or stereo adaptor's output); ``moving``: the clipped local map, landmarks with descriptors; ``moving_in_sensor``: the pose
+    guess (3 x 4).  ``params``: TrackParams (camera matrix, image size, depth range, search_radius, max_distance, min_margin,
+    cross_check).  compute() returns the pairs as a CORR_DTYPE array in ascending moving_idx -- what
+    ``MultiAligner.set_correspondences`` takes for a FINDER_CORRESPONDENCES slice; ``result``: the counters of the last call."""
+
+    def __init__(self, binding, params=None):
+        self._b = binding
+        self.params = params or default_track_params()
+        self._fixed = self._moving = None
+        self._T = _f32(np.eye(3, 4))
+        self.result = None
+
+    def set_camera_matrix(self, K):
+        for i, v in enumerate(_f32(K).reshape(9)):
+            self.params.camera_matrix[i] = float(v)
+
+    def set_fixed(self, scene):
+        self._fixed = scene
+
+    def set_moving(self, scene):
+        self._moving = scene
+
+    def set_moving_in_sensor(self, T):
+        self._T = _f32(T).reshape(12)
+
+    def compute(self, capacity=None, want_result=True):
+        """``capacity``: at most that many pairs are returned (``result["num_correspondences"]`` still counts all); None:
+        room for every landmark.  ``want_result=False`` passes no result struct: ``result`` is then None and the array has
+        ``capacity`` rows, of which the caller cannot tell how many are pairs."""
+        if self._fixed is None or self._moving is None:
+            raise RuntimeError("FeatureTracker::compute|fixed or moving not set")
+        f = getattr(self._b.lib, self._b.prefix + "track_features", None)
+        if f is None:
+            raise NotImplementedError("%strack_features: this binding has no feature tracker (product library only)" % self._b.prefix)
+        cap = self._moving.size() if capacity is None else int(capacity)
+        buf = np.zeros(max(cap, 1), CORR_DTYPE)
+        out = TrackResult()
+        self.result = None
+        self._b.check(f(self._moving._h, self._fixed._h, _fp(self._T), C.byref(self.params), C.c_void_p(buf.ctypes.data) if cap > 0 else None,
+                        C.c_int(cap), C.byref(out) if want_result else None))
+        if not want_result:
+            return buf[:max(cap, 0)]
+        self.result = out.as_dict()
+        return buf[:min(max(cap, 0), out.num_correspondences)]
 
 
 class MergerCorrespondenceHomo:
