@@ -1188,6 +1188,77 @@ int srrg2_scene_track_features(srrg2_scene_h moving, srrg2_scene_h fixed, const 
                                const srrg2_track_params* p, srrg2_correspondence* correspondences_out /* host, may be NULL */,
                                int capacity, srrg2_track_result* out /* may be NULL */);
 
+/* Consensus pose: geometric verification of descriptor matches -- K candidates x H minimal-sample hypotheses x N matches of
+ * transform-and-compare (RANSAC with a fixed hypothesis count), in one call.  The reference has no such step: its HBST detector
+ * hands the raw matches to the locked Gauss-Newton solve (multi_loop_detector_hbst_impl.cpp:257-377).  DESIGN.md section 4
+ * "Consensus pose" is the contract, tests/consensus_restatement.py restates it and the library gives the same bits.
+ *   clouds    `fixed` is the query cloud, `moving` the K candidates' clouds one behind the other (moving_offsets: K + 1 point
+ *             indices); both in `mem` = SRRG2_MEM_HOST | SRRG2_MEM_DEVICE (srrg2_scene_device_arrays: stride 16), borrowed for
+ *             the call only.  Strides: multiples of 4, >= dim * 4 (12 and 16 among them).
+ *   pairs     candidate k's records are correspondences[corr_offsets[k] .. corr_offsets[k+1]) (host), in the aligner's
+ *             convention: fixed_idx indexes the query, moving_idx the candidate's OWN cloud.  A pair is valid iff both indices
+ *             are in range and all `dim` coordinates of both points are finite; an invalid pair is never an inlier and is no error.
+ *   sampling  s = 3 (dim 3) | 2 (dim 2).  mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *             (uint32).  base = mix32(mix32(seed) + h); index j of hypothesis h: for attempt a = 0 .. 3, r = mix32(base + 4 j + a),
+ *             i = ((uint64) r * N) >> 32, the first i that differs from the hypothesis's earlier indices.  None, a sampled invalid
+ *             pair or N < s: the hypothesis is DEGENERATE.  The candidate's index is not in the hash: result k of a batch is bit
+ *             for bit the result of a K = 1 call on candidate k alone.
+ *   solver    float64 from the float32 points, + - * / sqrt only (csrc/consensus_math.h).  dim 3: the orthonormal frames of the
+ *             moving and the fixed triple (a = p1 - p0, b = p2 - p0, n = a x b, e1 = a / |a|, e3 = n / |n|, e2 = e3 x e1;
+ *             degenerate iff |a|^2 < msd^2 or |n|^2 < msd^2 |a|^2), R = Ef Em^T, t = cf - R cm on the centroids.  dim 2: angle
+ *             between the two segments, t on the midpoints.  A non-finite entry: degenerate.
+ *   length    length_check: REJECTED iff for some two sample points | |m_i - m_j| - |f_i - f_j| | > 2 inlier_distance.
+ *   score     float32, on the pose cast to float32 -- which is the pose returned: r_i = ((R_i0 x + R_i1 y) + R_i2 z) + t_i - f_i,
+ *             e = (r0^2 + r1^2) + r2^2, inlier iff e <= tau * tau (float32).  cost = the int64 sum over the inliers of
+ *             trunc((double) e * 2^cost_exponent): order-independent.
+ *   best      largest count, then smallest cost, then smallest h, over the scored hypotheses; all H are always evaluated.
+ *             status NO_HYPOTHESIS: none was scored (pose all zero, best_hypothesis -1); TOO_FEW_INLIERS: count <
+ *             max(min_inliers, s), pose and counters still written; FOUND otherwise.
+ *   inliers   the records of the best hypothesis's inliers in input order (response carried through), for FOUND candidates only,
+ *             concatenated over the candidates: inliers_out (host, may be NULL) receives the first inlier_capacity of them,
+ *             inlier_offsets_out (K + 1, may be NULL) is NOT limited by inlier_capacity.
+ *   refused   SRRG2_E_INVALID, nothing written: a null handle, params or results (K > 0); K < 0; decreasing or negative offsets;
+ *             null clouds or records where points / records exist; bad strides; num_hypotheses outside 1 .. 65536; inlier_distance
+ *             not finite or <= 0; min_sample_distance not finite or < 0; min_inliers < 0; length_check not 0 / 1; reserved != 0;
+ *             inlier_capacity < 0; a mem other than HOST | DEVICE (SRRG2_MEM_DEVICE_KEPT among them).  K = 0 returns 0.  A candidate
+ *             without pairs gets NO_HYPOTHESIS.
+ *   waits     ONE host wait: results, offsets and the capacity-bounded records come back in one copy.  The handle owns a stream
+ *             and the workspaces; a steady-state call allocates nothing.  The number of launches does not depend on K, H or N.
+ * inlier_distance 0.05, min_sample_distance 0.1 and num_hypotheses 256 are UNTUNED defaults: nobody has derived or measured them. */
+typedef struct srrg2_consensus_s* srrg2_consensus_h;
+enum srrg2_consensus_status { SRRG2_CONSENSUS_FOUND = 0, SRRG2_CONSENSUS_NO_HYPOTHESIS = 1, SRRG2_CONSENSUS_TOO_FEW_INLIERS = 2 };
+typedef struct srrg2_consensus_params {
+  int32_t  num_hypotheses;      /* 1 .. 65536, default 256 (untuned) */
+  float    inlier_distance;     /* m, > 0 and finite, default 0.05 (untuned) */
+  float    min_sample_distance; /* m, >= 0 and finite, default 0.1 (untuned): sample points closer than this, or a triangle
+                                   flatter than this, are degenerate */
+  int32_t  min_inliers;         /* >= 0, default 0: FOUND needs max(min_inliers, s) inliers */
+  uint32_t seed;                /* default 0 */
+  int32_t  length_check;        /* 0 | 1, default 1 */
+  int32_t  reserved[2];         /* 0 */
+} srrg2_consensus_params;       /* 32 bytes */
+typedef struct srrg2_consensus_result {
+  float   moving_in_fixed[12];  /* row-major 3 x 4; SE(2): the first 9, a row-major 3 x 3 */
+  int32_t status;               /* srrg2_consensus_status */
+  int32_t best_hypothesis;      /* -1 when none was scored */
+  int32_t num_inliers;
+  int32_t num_pairs, num_valid_pairs;
+  int32_t num_degenerate, num_rejected, num_scored; /* sum to num_hypotheses */
+  int32_t cost_exponent;
+  int32_t reserved;
+  int64_t cost;                 /* fixed point: sum of trunc(e * 2^cost_exponent) over the inliers */
+} srrg2_consensus_result;       /* 96 bytes */
+int  srrg2_consensus_create(int dim /* 2 | 3 */, int device, srrg2_consensus_h* out);
+int  srrg2_consensus_destroy(srrg2_consensus_h h);
+void srrg2_consensus_default_params(srrg2_consensus_params* p);
+int  srrg2_consensus_compute(srrg2_consensus_h h, const float* fixed, int fixed_stride_bytes, int num_fixed, int K,
+                             const float* moving, int moving_stride_bytes, const int32_t* moving_offsets /* K + 1 */,
+                             int mem /* of both clouds: SRRG2_MEM_HOST | SRRG2_MEM_DEVICE */,
+                             const srrg2_correspondence* correspondences /* host */, const int32_t* corr_offsets /* K + 1 */,
+                             const srrg2_consensus_params* p, srrg2_consensus_result* results /* [K] */,
+                             srrg2_correspondence* inliers_out /* host, may be NULL */, int64_t inlier_capacity,
+                             int64_t* inlier_offsets_out /* [K + 1], may be NULL */);
+
 /* ---- strategy knobs (no reference counterpart) ----------------------------------------------------------------
  * Every setting gives the SAME results (indices, estimates, statistics bit for bit): the knobs choose between exact
  * strategies of the finder / reduction / control step.  A handle starts from srrg2_aligner_default_tuning() overridden

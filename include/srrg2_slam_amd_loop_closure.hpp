@@ -11,6 +11,7 @@
 //   MultiRelocalizer                 MultiRelocalizer_                          multi_relocalizer.h:29-43, _impl.cpp:12-145
 //   PoseGraph                        the global Solver + FactorGraph of MultiGraphSLAM_   system/multi_graph_slam.h:50-54
 //   GraphSLAMLifecycle               MultiGraphSLAM_::makeNewMap / loopValidate / optimize  system/multi_graph_slam_impl.cpp:52-90,227-317
+//   ConsensusVerifier                (no reference counterpart) consensus pose + inlier matches per candidate, before the locked solve
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -603,6 +604,81 @@ private:
   float _default_info[D * D] = {};
   int _current_local_map     = -1;
   int _num_valid_closures    = 0;
+};
+
+// ---- geometric verification of descriptor matches (srrg2_consensus_compute) ------------------------------------------------
+// A consensus pose and its inlier matches per candidate: K candidates x num_hypotheses minimal samples x N matches, one call,
+// one host wait.  The reference has no such step (multi_loop_detector_hbst_impl.cpp:257-377 hands raw matches to the locked
+// solve); include/srrg2_slam_amd.h states the contract.  The pose of a FOUND candidate is the guess and inliers(k) the
+// correspondences of the locked solve that follows (MultiAligner_::computeBatchCorrespondences).  fixed = the query cloud,
+// moving = the candidates' clouds one behind the other; records: fixed_idx = query point, moving_idx = point of the candidate's
+// OWN cloud.  The clouds are borrowed until compute() has run.
+template <int DIM>
+class ConsensusVerifier {
+public:
+  using EstimateType = Isometry<DIM>;
+  srrg2_consensus_params param;  // num_hypotheses 256, inlier_distance 0.05, min_sample_distance 0.1: untuned defaults
+  explicit ConsensusVerifier(int device = 0) {
+    srrg2_consensus_default_params(&param);
+    check(srrg2_consensus_create(DIM, device, &_h));
+  }
+  ~ConsensusVerifier() { srrg2_consensus_destroy(_h); }
+  ConsensusVerifier(const ConsensusVerifier&)            = delete;
+  ConsensusVerifier& operator=(const ConsensusVerifier&) = delete;
+  void setNumHypotheses(int n) { param.num_hypotheses = n; }
+  void setInlierDistance(float d) { param.inlier_distance = d; }
+  void setMinSampleDistance(float d) { param.min_sample_distance = d; }
+  void setMinInliers(int n) { param.min_inliers = n; }
+  void setSeed(uint32_t s) { param.seed = s; }
+  void setLengthCheck(bool on) { param.length_check = on ? 1 : 0; }
+  // mem (SRRG2_MEM_HOST | SRRG2_MEM_DEVICE) holds for both clouds
+  void setFixed(const float* coords, int n, int stride_bytes = DIM * 4, int mem = SRRG2_MEM_HOST) {
+    _fixed = coords, _nfixed = n, _fixed_stride = stride_bytes, _mem = mem;
+  }
+  // offsets: K + 1 point indices into coords
+  void setMoving(const float* coords, const std::vector<int32_t>& offsets, int stride_bytes = DIM * 4) {
+    _moving = coords, _moving_offsets = offsets, _moving_stride = stride_bytes;
+  }
+  void setCorrespondences(const std::vector<CorrespondenceVector>& per_candidate) {
+    _corr.clear();
+    _corr_offsets.assign(1, 0);
+    for (const CorrespondenceVector& c : per_candidate) {
+      _corr.insert(_corr.end(), c.begin(), c.end());
+      _corr_offsets.push_back((int32_t) _corr.size());
+    }
+  }
+  void compute() {
+    const int K = (int) _corr_offsets.size() - 1;
+    if (K < 0 || (int) _moving_offsets.size() != K + 1)
+      throw std::runtime_error("ConsensusVerifier::compute|moving offsets and correspondences disagree on the candidates");
+    _results.assign((size_t) K, srrg2_consensus_result{});
+    _inliers.assign(_corr.size(), Correspondence{});
+    _inlier_offsets.assign((size_t) K + 1, 0);
+    check(srrg2_consensus_compute(_h, _fixed, _fixed_stride, _nfixed, K, _moving, _moving_stride, _moving_offsets.data(), _mem,
+                                  _corr.data(), _corr_offsets.data(), &param, _results.data(), _inliers.data(),
+                                  (int64_t) _inliers.size(), _inlier_offsets.data()));
+    _inliers.resize((size_t) _inlier_offsets[(size_t) K]);
+  }
+  const std::vector<srrg2_consensus_result>& results() const { return _results; }
+  EstimateType movingInFixed(int k) const {
+    EstimateType X;
+    std::memcpy(X.data(), _results.at((size_t) k).moving_in_fixed, sizeof(float) * EstimateType::N);
+    return X;
+  }
+  // the best pose's inlier records in input order; empty unless results()[k].status == SRRG2_CONSENSUS_FOUND
+  CorrespondenceVector inliers(int k) const {
+    return CorrespondenceVector(_inliers.begin() + _inlier_offsets.at((size_t) k), _inliers.begin() + _inlier_offsets.at((size_t) k + 1));
+  }
+
+private:
+  srrg2_consensus_h _h = nullptr;
+  const float* _fixed  = nullptr;
+  const float* _moving = nullptr;
+  int _nfixed = 0, _fixed_stride = DIM * 4, _moving_stride = DIM * 4, _mem = SRRG2_MEM_HOST;
+  std::vector<int32_t> _moving_offsets, _corr_offsets{0};
+  CorrespondenceVector _corr, _inliers;
+  std::vector<int64_t> _inlier_offsets;
+  std::vector<srrg2_consensus_result> _results;
 };
 
 }  // namespace srrg2_slam_amd

@@ -44,6 +44,14 @@ def DescriptorDatabase(device=0):
     return _DD(device=device)
 
 
+def ConsensusVerifier(dim=3, device=0):
+    """Geometric verification of descriptor matches on the HIP library: a consensus pose and its inlier matches per candidate
+    (batched RANSAC with a fixed hypothesis count); see ``consensus.ConsensusVerifier``."""
+    from .consensus import ConsensusVerifier as _CV
+
+    return _CV(dim, device)
+
+
 def MeasurementAdaptorDepthImage(params=None):
     """Depth image -> measurement scene on the device (the adapt step of a tracker's frame); see ``adaptors``."""
     from .adaptors import MeasurementAdaptorDepthImage as _A

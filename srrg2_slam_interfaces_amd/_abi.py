@@ -265,6 +265,26 @@ class TrackResult(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# enum srrg2_consensus_status
+CONSENSUS_FOUND, CONSENSUS_NO_HYPOTHESIS, CONSENSUS_TOO_FEW_INLIERS = 0, 1, 2
+
+
+class ConsensusParams(C.Structure):
+    """srrg2_consensus_params (32 bytes)"""
+    _fields_ = [("num_hypotheses", C.c_int32), ("inlier_distance", C.c_float), ("min_sample_distance", C.c_float),
+                ("min_inliers", C.c_int32), ("seed", C.c_uint32), ("length_check", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class ConsensusResult(C.Structure):
+    """srrg2_consensus_result (96 bytes)"""
+    _fields_ = [("moving_in_fixed", C.c_float * 12), ("status", C.c_int32), ("best_hypothesis", C.c_int32), ("num_inliers", C.c_int32),
+                ("num_pairs", C.c_int32), ("num_valid_pairs", C.c_int32), ("num_degenerate", C.c_int32), ("num_rejected", C.c_int32),
+                ("num_scored", C.c_int32), ("cost_exponent", C.c_int32), ("reserved", C.c_int32), ("cost", C.c_int64)]
+
+
+assert C.sizeof(ConsensusParams) == 32 and C.sizeof(ConsensusResult) == 96
+
+
 class NormalsParams(C.Structure):
     """srrg2_normals_params"""
     _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_int32), ("max_curvature", C.c_float), ("viewpoint", C.c_float * 3),

@@ -86,6 +86,15 @@ def lib():
         _LIB.srrg2_track_default_params.restype = None
         _LIB.srrg2_scene_track_features.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(abi.TrackParams),
                                                     C.c_void_p, C.c_int, C.POINTER(abi.TrackResult)]
+        # srrg2_consensus_* (consensus.ConsensusVerifier)
+        _LIB.srrg2_consensus_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        _LIB.srrg2_consensus_destroy.argtypes = [C.c_void_p]
+        _LIB.srrg2_consensus_default_params.argtypes = [C.POINTER(abi.ConsensusParams)]
+        _LIB.srrg2_consensus_default_params.restype = None
+        _LIB.srrg2_consensus_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                 C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.POINTER(C.c_int32),
+                                                 C.POINTER(abi.ConsensusParams), C.c_void_p, C.c_void_p, C.c_int64,
+                                                 C.POINTER(C.c_int64)]
         # srrg2_scene_clip_projective (mapping.SceneClipperProjective)
         from . import mapping
 

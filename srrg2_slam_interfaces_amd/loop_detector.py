@@ -288,12 +288,21 @@ class MultiLoopDetectorHBST:
     the local map's cloud the reference reads its descriptors from (:84-85, :131-136).  Then nothing but counts, matches
     and results crosses to the host: the database matches and adds the scene on the device (valid = finite coordinates),
     the detector remembers the scene by graph id, and the alignments bind the scenes' device arrays.  A remembered scene
-    must stay alive and unchanged while it can be a candidate, as the reference's local maps do."""
+    must stay alive and unchanged while it can be a candidate, as the reference's local maps do.
+
+    ``consensus`` (not in the reference): None keeps exactly the behaviour above.  A dict of srrg2_consensus_params fields (it
+    may be empty: the defaults, untuned) puts a geometric verification in front of the solve: ONE srrg2_consensus_compute
+    (``consensus.ConsensusVerifier``) over the candidates that pass the match-count gate; a candidate without a consensus pose or
+    with fewer than relocalize_min_inliers inliers is dropped as "CONSENSUS DROP [code: n]" (n: srrg2_consensus_status), the rest
+    go through the same ONE batched locked solve, from the consensus poses and on the inlier lists.  The exhaustive matcher
+    returns more wrong matches than a tree would, and the robustifier alone does not survive a majority of them from the
+    identity.  relocalize_min_inliers_ratio is still taken against the ORIGINAL match count (``num_matches`` of the closure
+    record): the verification loosens no gate."""
 
     def __init__(self, relocalize_aligner, relocalize_min_inliers=500, relocalize_max_chi_inliers=0.005,
                  relocalize_min_inliers_ratio=0.7, maximum_descriptor_distance=25.0, maximum_leaf_size=100,
                  maximum_partitioning=0.1, maximum_depth=16, maximum_distance_for_merge=0.0,
-                 minimum_age_difference_to_candidates=0, database=None, device=0):
+                 minimum_age_difference_to_candidates=0, database=None, device=0, consensus=None):
         if relocalize_aligner is None:
             raise RuntimeError("MultiLoopDetectorHBST::computeAlignments|ERROR: aligner not set")  # :264-268
         if maximum_distance_for_merge != 0:
@@ -314,6 +323,9 @@ class MultiLoopDetectorHBST:
         self.minimum_age_difference_to_candidates = minimum_age_difference_to_candidates
         self.database = database
         self.device = device
+        self.consensus = None if consensus is None else dict(consensus)
+        self._verifier = None
+        self.last_consensus = None  # the ConsensusVerifier results of the last compute_alignments(), per verified candidate
         self.detected_closures = []
         self.drops = []
         self._graph_id_to_database_index = {}
@@ -428,7 +440,28 @@ class MultiLoopDetectorHBST:
                                "correspondences": self._correspondences_per_reference[r]})
         return self.compute_alignments(graph_id, points, normals, candidates, pose_in_query)
 
-    def _align_scenes(self, fixed, todo):
+    def _verify(self, fixed, todo):
+        """the consensus poses of the candidates in ONE call; returns (the candidates that keep going, with their inlier lists as
+        ``correspondences`` and the original count as ``num_matches``; their consensus poses)"""
+        if self._verifier is None:
+            from .consensus import ConsensusVerifier
+
+            self._verifier = ConsensusVerifier(self.relocalize_aligner.dim, self.device)
+        params = dict(self.consensus)
+        params.setdefault("min_inliers", int(self.relocalize_min_inliers))
+        results = self._verifier.compute(fixed, [c["moving"] for c in todo], [c["correspondences"] for c in todo], **params)
+        self.last_consensus = results
+        kept, guesses = [], []
+        for c, r in zip(todo, results):
+            if r["status"] != abi.CONSENSUS_FOUND or r["num_inliers"] < self.relocalize_min_inliers:
+                code = r["status"] if r["status"] != abi.CONSENSUS_FOUND else abi.CONSENSUS_TOO_FEW_INLIERS
+                self.drops.append((c["reference"], "CONSENSUS DROP [code: %d]" % code))
+                continue
+            kept.append(dict(c, correspondences=r["inliers"], num_matches=len(c["correspondences"])))
+            guesses.append(r["moving_in_fixed"])
+        return kept, guesses
+
+    def _align_scenes(self, fixed, todo, guesses):
         """the batched locked solve on device-resident clouds: the query scene's arrays are the fixed cloud, the candidates'
         (float4 records, stride 16) are concatenated device to device into one buffer for the call"""
         import ctypes as C
@@ -462,7 +495,7 @@ class MultiLoopDetectorHBST:
                         raise RuntimeError("srrg2_amd_memcpy (device -> device) failed")
             return al.compute_batch_correspondences_device(
                 bufs[0], 16, bufs[1] if with_normals else None, 16, offsets, [c["correspondences"] for c in todo],
-                [sl.identity(al.dim)] * len(todo))  # :335
+                guesses)
         finally:
             for b in bufs:
                 lib.srrg2_amd_device_free(C.c_void_p(b))
@@ -483,15 +516,22 @@ class MultiLoopDetectorHBST:
             todo.append(c)
         if not todo:
             return self.detected_closures
-        if self._is_scene(fixed) or any(self._is_scene(c["moving"]) for c in todo):
-            if not (self._is_scene(fixed) and all(self._is_scene(c["moving"]) for c in todo)):
-                raise ValueError("compute_alignments: scenes and host arrays cannot be mixed")
-            results = self._align_scenes(fixed, todo)
+        scenes = self._is_scene(fixed) or any(self._is_scene(c["moving"]) for c in todo)
+        if scenes and not (self._is_scene(fixed) and all(self._is_scene(c["moving"]) for c in todo)):
+            raise ValueError("compute_alignments: scenes and host arrays cannot be mixed")
+        guesses = [sl.identity(dim)] * len(todo)  # :335
+        self.last_consensus = None
+        if self.consensus is not None:
+            todo, guesses = self._verify(fixed, todo)
+            if not todo:
+                return self.detected_closures
+        if scenes:
+            results = self._align_scenes(fixed, todo, guesses)
         else:
             al.set_fixed(0, fixed, fixed_normals)
             normals = [c.get("moving_normals") for c in todo]
             results = al.compute_batch_correspondences(
-                [c["moving"] for c in todo], [c["correspondences"] for c in todo], [sl.identity(dim)] * len(todo),  # :335
+                [c["moving"] for c in todo], [c["correspondences"] for c in todo], guesses,
                 normals if all(n is not None for n in normals) else None)
         for c, r in zip(todo, results):
             if r["status"] != abi.SUCCESS:  # :346-356
@@ -507,7 +547,10 @@ class MultiLoopDetectorHBST:
             if chi_inliers > np.float32(self.relocalize_max_chi_inliers):  # :400-404
                 self.drops.append((c["reference"], "MAX_CHI_INLIERS DROP"))
                 continue
-            if np.float32(num_inliers) / np.float32(num_correspondences) < np.float32(self.relocalize_min_inliers_ratio):
+            # (behind a consensus verification the ratio is still taken against the ORIGINAL match count)
+            num_matches = int(c.get("num_matches", len(c["correspondences"])))
+            ratio_base = num_matches if self.consensus is not None else num_correspondences
+            if np.float32(num_inliers) / np.float32(ratio_base) < np.float32(self.relocalize_min_inliers_ratio):
                 self.drops.append((c["reference"], "MIN_INLIERS_RATIO DROP"))  # :406-413
                 continue
             reference_in_query = r["moving_in_fixed"]
@@ -518,5 +561,6 @@ class MultiLoopDetectorHBST:
                 "source": query_id, "target": c["reference"], "measurement": reference_in_query, "information": info,
                 "pose_in_target": sl.compose(sl.inverse(reference_in_query), pose_in_query),  # :420
                 "chi_inliers": float(chi_inliers), "num_inliers": int(num_inliers),
-                "num_correspondences": int(num_correspondences), "correspondences": c["correspondences"]})
+                "num_correspondences": int(num_correspondences), "correspondences": c["correspondences"],
+                "num_matches": num_matches})
         return self.detected_closures
