@@ -23,6 +23,7 @@
 #include <utility>
 
 #include "det_math.h"
+#include "device_util.h"
 #include "host_util.h"
 #include "kernels.h"
 #include "scene_state.h"
@@ -308,19 +309,9 @@ struct LidarSource {
 };
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------
-// both counts of a workgroup in one word (low: in range, high: Valid), ONE atomic per workgroup (blockDim = 256): same-address
-// atomics serialise
-__device__ __forceinline__ void block_add_counts(int flags_seen_in_range, int flags_seen_valid, unsigned long long* target) {
-  __shared__ unsigned long long red[4];
-  unsigned long long v = (unsigned long long) (unsigned) flags_seen_in_range | ((unsigned long long) (unsigned) flags_seen_valid << 32);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long t = (red[0] + red[1]) + (red[2] + red[3]);
-    if (t) atomicAdd(target, t);
-  }
+// both counts of a workgroup in one word (low: in range, high: Valid): ONE block_add, so one atomic per workgroup
+__device__ __forceinline__ unsigned long long pack_counts(int in_range, int valid) {
+  return (unsigned long long) (unsigned) in_range | ((unsigned long long) (unsigned) valid << 32);
 }
 
 template <typename S>
@@ -336,7 +327,7 @@ __global__ __launch_bounds__(256) void k_adapt_organised(S src, int n, float4* _
     in_range += f & 1;
     valid += f >> 1;
   }
-  block_add_counts(in_range, valid, counters);
+  block_add(pack_counts(in_range, valid), counters);
 }
 
 template <typename S>
@@ -349,7 +340,7 @@ __global__ __launch_bounds__(256) void k_adapt_flag(S src, int n, int* __restric
     in_range += f & 1;
     valid += f >> 1;
   }
-  block_add_counts(in_range, valid, counters);
+  block_add(pack_counts(in_range, valid), counters);
 }
 
 template <typename S>

@@ -1,4 +1,5 @@
-// device_util.h -- small device helpers shared by kernels_prep.hip (ingest, grid, sort) and kernels.hip (ICP passes).
+// device_util.h -- small device helpers shared by kernels_prep.hip (ingest, grid, sort) and kernels.hip (ICP passes); block_add
+// also by scene.hip, adaptor.hip and tracking.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +30,21 @@ __device__ __forceinline__ long long wave_sum(long long v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
   return v;
+}
+
+// block sum -> ONE atomic per block (same-address atomics serialise at tens of ns each; blockDim = 256, every thread calls)
+template <typename T>
+__device__ __forceinline__ void block_add(T v, T* target) {
+  __shared__ T red[4];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  __syncthreads();  // (a call right after another: thread 0 must have read red[] before the wave leaders overwrite it)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const T t = (red[0] + red[1]) + (red[2] + red[3]);
+    if (t) atomicAdd(target, t);
+  }
 }
 
 }  // namespace

@@ -17,6 +17,20 @@ void launch_grid_count(const GridDev& g, const float4* pts, int n, int* counts, 
 void launch_count_nonzero(const int* counts, int n, int* out, hipStream_t s);
 int scan_num_blocks(int n);
 void launch_exclusive_scan(int* data, int n, int* block_sums, int* grand_total, hipStream_t s, int* copy = nullptr);
+// desc_band.hip: the best 256-bit descriptor inside a band of image rows (stereo.hip, tracking.hip).  A best word is
+// (Hamming distance << 32 | index), NO_CANDIDATE when nothing was inside the gate; second: the smallest distance of any other
+// candidate, NO_SECOND (= the distance field of NO_CANDIDATE) when there was none.
+constexpr unsigned long long NO_CANDIDATE = ~0ull;
+constexpr unsigned NO_SECOND              = 0xffffffffu;
+// row_begin[rows + 1] from n ascending pixel indices.  error not null: raised on a pixel outside [0, rows * cols) or not above
+// its predecessor; null: the caller vouches for the pixels.
+void launch_band_rows(const int* pixel, int n, int rows, int cols, int* row_begin, int* error, hipStream_t s);
+// best[q] over the candidates of rows r - radius .. r + radius with lo <= candidate column - query column <= hi; q_pixel[q] < 0
+// skips the query, a set error word (may be null) all of them.  second (may be null): the runner-up's distance; reverse (may be
+// null, needs second): per candidate the atomicMin of (distance << 32 | query index), set to NO_CANDIDATE by the caller.
+void launch_band_search(int nq, const int* q_pixel, const uint4* q_desc, const int* c_pixel, const uint4* c_desc, const int* c_rows,
+                        int rows, int cols, int radius, int lo, int hi, const int* error, unsigned long long* best, unsigned* second,
+                        unsigned long long* reverse, hipStream_t s);
 void launch_grid_scatter(const GridDev& g, const float4* pts, const float4* nrm, int n, int* cursor, float4* out_pts,
                          float4* out_nrm, int* pos_of, hipStream_t s);
 // cell neighbour lists of the grid (GridDev::list_*): ent == null counts the entries per cell into list_start, else fills

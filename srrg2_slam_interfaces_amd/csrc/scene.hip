@@ -30,6 +30,7 @@
 
 #include "det_math.h"
 #include "device_types.h"
+#include "device_util.h"
 #include "host_util.h"
 #include "kernels.h"
 #include "scene_device.h"
@@ -130,20 +131,6 @@ __global__ void k_scatter_kept(int dim, Xf L, const float4* __restrict__ pts, co
     scatter_kept<FEAT, 2>(L, pts, nrm, n, offset, out_pts, out_nrm, gidx, cap, f);
 }
 
-// block sum -> ONE atomic per block (same-address atomics serialise at tens of ns each; blockDim = 256)
-__device__ __forceinline__ void block_add(int v, int* target) {
-  __shared__ int red[4];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();  // (a call right after another: thread 0 must have read red[] before the wave leaders overwrite it)
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int t = (red[0] + red[1]) + (red[2] + red[3]);
-    if (t) atomicAdd(target, t);
-  }
-}
-
 // ---- view clips (no reference counterpart: SceneClipper_ is an interface; DESIGN.md section 4 "Projective clipping", "Scan
 // clipping", "Lidar sweeps") --------------------------------------------------------------------------------------------------
 // keep the Valid points a sensor at sensor_in_robot sees: inside its depth / range interval and its image or sector, and --
@@ -195,7 +182,7 @@ struct PinholeView : ViewBase {
 
 // -- planar laser scanner (2-D): the bins are the beams of its angular sector.
 // A scan has ~10^3 beams, a map 10^5..10^6 points: hundreds of points per word, and same-address global atomics serialise
-// (block_add above).  So with occlusion every workgroup takes the minimum in a private LDS table of num_beams words first
+// (block_add, device_util.h).  So with occlusion every workgroup takes the minimum in a private LDS table of num_beams words first
 // (k_view_min_lds: ds atomics, no return value) and sends ONE global atomicMin per bin it touched.  k_view_min, straight into
 // global memory, remains for tables beyond SRRG2_SCLIP_LDS_BINS and maps too small to give SRRG2_SCLIP_LDS_MIN_WORKGROUPS
 // workgroups their share.  A minimum does not depend on who took it: both give the same bits.

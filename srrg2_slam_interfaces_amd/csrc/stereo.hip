@@ -5,12 +5,9 @@
 // sub-pixel costs are integer arithmetic, the depth is two float32 operations in a fixed order: the result is a function of the
 // pixels and the parameters alone, bit for bit.
 //   (per image: the pipeline of features.hip through features_pipeline.h -- both queued before the call's first host wait)
-//   k_stereo_rows      per image row_begin[rows + 1] from the keypoints' pixels, which are in raster order: thread i writes the
-//                      rows that keypoint i opens (boundary detection, no sort)
-//   k_stereo_best      one wave per query keypoint, once per direction: the lanes stride over the row band's keypoints (one
-//                      contiguous range), gate the disparity, take the Hamming distance (two 16-byte loads, four popcounts) and
-//                      keep the smallest (distance << 32 | candidate index); a shuffle-min gives the wave's
-//   k_stereo_resolve   one wave per left keypoint: distance gate, cross check, the three 7x7 costs (lane = window pixel, wave
+//   (per image the row table, then once per direction the banded descriptor search of desc_band.hip: srrg2amd::launch_band_rows,
+//   launch_band_search -- the disparity gate is an interval on candidate column - query column)
+//   k_stereo_resolve  one wave per left keypoint: distance gate, cross check, the three 7x7 costs (lane = window pixel, wave
 //                      reduction); lane 0 computes the offset, the depth, its gate, the keep flag and the keypoint's record
 //   k_stereo_count     num_matched and num_mutual from the records: grid-stride sums, two atomics per wave
 //   (exclusive scan of the keep flags: srrg2amd::scene_scan_flags -- the second host wait)
@@ -35,56 +32,7 @@ using srrg2amd::FeatImage;
 namespace {
 
 enum { S_MATCHED = 0, S_MUTUAL = 1, S_WORDS = 2 };
-constexpr unsigned long long NO_CANDIDATE = ~0ull;
-
-// pixel: n keypoints' pixel indices, ascending.  row_begin[r] = the first keypoint in row r or below it, row_begin[rows] = n
-__global__ __launch_bounds__(256) void k_stereo_rows(const int* __restrict__ pixel, int n, int rows, int cols, int* __restrict__ row_begin) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += gridDim.x * blockDim.x) {
-    const int cur  = i < n ? pixel[i] / cols : rows;
-    const int prev = i > 0 ? pixel[i - 1] / cols : -1;
-    for (int r = prev + 1; r <= cur; ++r) row_begin[r] = i;  // (0 <= r <= rows: a pixel lies inside the image)
-  }
-}
-
-__device__ __forceinline__ int hamming(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
-  const unsigned long long w0 = (unsigned long long) (a0.x ^ b0.x) | ((unsigned long long) (a0.y ^ b0.y) << 32);
-  const unsigned long long w1 = (unsigned long long) (a0.z ^ b0.z) | ((unsigned long long) (a0.w ^ b0.w) << 32);
-  const unsigned long long w2 = (unsigned long long) (a1.x ^ b1.x) | ((unsigned long long) (a1.y ^ b1.y) << 32);
-  const unsigned long long w3 = (unsigned long long) (a1.z ^ b1.z) | ((unsigned long long) (a1.w ^ b1.w) << 32);
-  return (__popcll(w0) + __popcll(w1)) + (__popcll(w2) + __popcll(w3));
-}
-
-// One wave per query keypoint (4 per workgroup).  sign = +1: the queries are left keypoints and d = c_query - c_candidate;
-// -1: right keypoints, d = c_candidate - c_query.  The candidates are in raster order, so the smaller candidate index is the
-// smaller pixel index: best[q] = min (distance << 32 | candidate index) over the band's keypoints inside the disparity gate.
-__global__ __launch_bounds__(256) void k_stereo_best(int nq, const int* __restrict__ q_pixel, const uint4* __restrict__ q_desc,
-                                                     const int* __restrict__ c_pixel, const uint4* __restrict__ c_desc,
-                                                     const int* __restrict__ c_rows, int rows, int cols, int tolerance, int dmin,
-                                                     int dmax, int sign, unsigned long long* __restrict__ best) {
-  const int lane = threadIdx.x & 63;
-  const int q    = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (q >= nq) return;  // (the whole wave)
-  const int pixel = q_pixel[q];
-  const int r = pixel / cols, c = pixel - r * cols;
-  const int begin = c_rows[max(r - tolerance, 0)], end = c_rows[min(r + tolerance, rows - 1) + 1];
-  const uint4 a0 = q_desc[2 * (size_t) q], a1 = q_desc[2 * (size_t) q + 1];
-  unsigned long long key = NO_CANDIDATE;
-  for (int j = begin + lane; j < end; j += 64) {
-    const int cp = c_pixel[j];
-    const int d  = sign * (c - (cp - (cp / cols) * cols));
-    if (d >= dmin && d <= dmax) {
-      const int h = hamming(a0, a1, c_desc[2 * (size_t) j], c_desc[2 * (size_t) j + 1]);
-      const unsigned long long k = ((unsigned long long) h << 32) | (unsigned) j;
-      key = k < key ? k : key;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const unsigned long long k = __shfl_xor(key, off);
-    key = k < key ? k : key;
-  }
-  if (lane == 0) best[q] = key;
-}
+using srrg2amd::NO_CANDIDATE;
 
 // One wave per left keypoint (4 per workgroup).  best_r null: no cross check.  fb = fx * baseline.  Every read stays inside the
 // images: a keypoint is >= 16 pixels from the borders, the window reaches 3 and the shifted one 4.
@@ -292,16 +240,15 @@ extern "C" int srrg2_adapt_stereo_features(srrg2_scene_h dst, const void* left, 
     const srrg2amd::FeatOut o{s->st_pixel[e].p, reinterpret_cast<unsigned long long*>(s->st_desc[e].p), s->st_kp[e].p, nullptr, nullptr,
                               nullptr};
     if ((rc = srrg2amd::feat_queue_describe(I[e], D, fp->oriented, work[e], s->feat_pattern.p, count[e], o, st))) return rc;
-    hipLaunchKernelGGL(k_stereo_rows, dim3(blocks_for(count[e] + 1)), dim3(256), 0, st, s->st_pixel[e].p, count[e], rows, cols,
-                       s->st_rows[e].p);
+    srrg2amd::launch_band_rows(s->st_pixel[e].p, count[e], rows, cols, s->st_rows[e].p, nullptr, st);  // (the extractor's pixels)
   }
-  hipLaunchKernelGGL(k_stereo_best, dim3((nl + 3) / 4), dim3(256), 0, st, nl, s->st_pixel[0].p, s->st_desc[0].p, s->st_pixel[1].p,
-                     s->st_desc[1].p, s->st_rows[1].p, rows, cols, sp->row_tolerance, sp->min_disparity, sp->max_disparity, 1,
-                     s->st_best[0].p);
+  // the disparity d = left column - right column in [min, max], as an interval on candidate column - query column:
+  // left -> right [-max, -min], right -> left [min, max]
+  srrg2amd::launch_band_search(nl, s->st_pixel[0].p, s->st_desc[0].p, s->st_pixel[1].p, s->st_desc[1].p, s->st_rows[1].p, rows, cols,
+                               sp->row_tolerance, -sp->max_disparity, -sp->min_disparity, nullptr, s->st_best[0].p, nullptr, nullptr, st);
   if (sp->cross_check)
-    hipLaunchKernelGGL(k_stereo_best, dim3((nr + 3) / 4), dim3(256), 0, st, nr, s->st_pixel[1].p, s->st_desc[1].p, s->st_pixel[0].p,
-                       s->st_desc[0].p, s->st_rows[0].p, rows, cols, sp->row_tolerance, sp->min_disparity, sp->max_disparity, -1,
-                       s->st_best[1].p);
+    srrg2amd::launch_band_search(nr, s->st_pixel[1].p, s->st_desc[1].p, s->st_pixel[0].p, s->st_desc[0].p, s->st_rows[0].p, rows, cols,
+                                 sp->row_tolerance, sp->min_disparity, sp->max_disparity, nullptr, s->st_best[1].p, nullptr, nullptr, st);
   HIP_TRY(hipMemsetAsync(s->st_counts.p, 0, S_WORDS * sizeof(int), st));
   // (the left image's keep flags are consumed: s->flags takes the matches')
   hipLaunchKernelGGL(k_stereo_resolve, dim3((nl + 3) / 4), dim3(256), 0, st, I[0], I[1], nl, s->st_pixel[0].p, s->st_pixel[1].p,

@@ -5,14 +5,10 @@
 // operation, in float32; everything behind it is integer arithmetic: the result is a function of the two scenes, the pose and the
 // parameters alone, bit for bit.
 //   k_track_project   one thread per landmark: its pixel rv * cols + cu, or -1 when it is not in view
-//   k_track_rows      row_begin[rows + 1] from the keypoints' pixels (as stereo.hip's k_stereo_rows); the same pass checks that
-//                     the pixels ascend strictly inside the image and raises the error word otherwise
-//   k_track_best      one wave per landmark: the lanes stride over the keypoints of rows rv - R .. rv + R (one contiguous range),
-//                     gate the column, take the Hamming distance (two 16-byte loads per side, four popcounts) and keep the
-//                     smallest (distance << 32 | keypoint index) and the smallest distance of any other candidate; a shuffle
-//                     reduction merges the (best, second) pairs.  With the cross check every evaluated pair also sends ONE 64-bit
-//                     atomicMin (distance << 32 | landmark index) to its keypoint's word: a minimum does not depend on the order
-//   k_track_resolve   one thread per landmark: the gates, the cross check, the record and the keep flag; the four counters are
+//   (the keypoints' row table, which checks that their pixels ascend strictly inside the image and raises the error word
+//   otherwise, then the banded descriptor search of desc_band.hip with the runner-up's distance and, with the cross check, the
+//   reverse atomicMin table: srrg2amd::launch_band_rows, launch_band_search -- the column gate is [-R, R])
+//   k_track_resolve  one thread per landmark: the gates, the cross check, the record and the keep flag; the four counters are
 //                     block sums with one atomic per block and counter
 //   (exclusive scan of the keep flags: srrg2amd::launch_exclusive_scan, what srrg2amd::scene_scan_flags runs -- its total rides
 //   on the call's one wait)
@@ -25,6 +21,7 @@
 #include <cstring>
 #include <string>
 
+#include "device_util.h"
 #include "host_util.h"
 #include "kernels.h"
 #include "scene_state.h"
@@ -35,8 +32,8 @@ namespace {
 
 // words of the output block (srrg2_scene::trk_out): the counters, the error word, the scan's total; the records from T_WORDS on
 enum { T_IN_VIEW = 0, T_CANDIDATE = 1, T_ACCEPTED = 2, T_MUTUAL = 3, T_ERROR = 4, T_TOTAL = 5, T_WORDS = 8 };
-constexpr unsigned long long NO_CANDIDATE = ~0ull;
-constexpr unsigned NO_SECOND              = 0xffffffffu;  // (= the distance field of NO_CANDIDATE)
+using srrg2amd::NO_CANDIDATE;
+using srrg2amd::NO_SECOND;
 
 struct TrackCam {
   float m[12];  // rows of moving_in_sensor
@@ -64,96 +61,12 @@ __global__ __launch_bounds__(256) void k_track_project(TrackCam C, const float4*
   pix[i] = out;
 }
 
-// pixel: n keypoints' pixel indices.  row_begin[r] = the first keypoint in row r or below it, row_begin[rows] = n.  A pixel
-// outside [0, rows * cols) or not above its predecessor raises *error; the rows are clamped into the image first, so that every
-// write stays inside row_begin whatever the pixels are (the kernels behind this one do nothing once *error is set).
-__global__ __launch_bounds__(256) void k_track_rows(const int* __restrict__ pixel, int n, int rows, int cols, int* __restrict__ row_begin,
-                                                    int* __restrict__ error) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > n) return;
-  int cur = rows, prev = -1;
-  if (i < n) {
-    const int p = pixel[i];
-    if (p < 0 || p >= rows * cols || (i > 0 && pixel[i - 1] >= p)) *error = 1;
-    cur = min(max(p / cols, 0), rows - 1);
-  }
-  if (i > 0) prev = min(max(pixel[i - 1] / cols, 0), rows - 1);
-  for (int r = prev + 1; r <= cur; ++r) row_begin[r] = i;
-}
-
-__device__ __forceinline__ int hamming(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
-  const unsigned long long w0 = (unsigned long long) (a0.x ^ b0.x) | ((unsigned long long) (a0.y ^ b0.y) << 32);
-  const unsigned long long w1 = (unsigned long long) (a0.z ^ b0.z) | ((unsigned long long) (a0.w ^ b0.w) << 32);
-  const unsigned long long w2 = (unsigned long long) (a1.x ^ b1.x) | ((unsigned long long) (a1.y ^ b1.y) << 32);
-  const unsigned long long w3 = (unsigned long long) (a1.z ^ b1.z) | ((unsigned long long) (a1.w ^ b1.w) << 32);
-  return (__popcll(w0) + __popcll(w1)) + (__popcll(w2) + __popcll(w3));
-}
-
-// (best, second) of two disjoint candidate sets -> of their union: the smaller key wins; the loser's distance is a distance of
-// "another candidate", as both seconds are.  NO_CANDIDATE's distance field is NO_SECOND: an empty side adds nothing.
-__device__ __forceinline__ void merge_best(unsigned long long& key, unsigned& second, unsigned long long k, unsigned s) {
-  const unsigned long long loser = k < key ? key : k;
-  key                            = k < key ? k : key;
-  second                         = min(min(second, s), (unsigned) (loser >> 32));
-}
-
-// One wave per landmark (4 per workgroup).  best_fixed null: no cross check, no atomics.
-__global__ __launch_bounds__(256) void k_track_best(int nm, const int* __restrict__ m_pix, const uint4* __restrict__ m_desc,
-                                                    const int* __restrict__ f_pixel, const uint4* __restrict__ f_desc,
-                                                    const int* __restrict__ row_begin, int rows, int cols, int radius,
-                                                    const int* __restrict__ error, unsigned long long* __restrict__ best,
-                                                    unsigned* __restrict__ second, unsigned long long* __restrict__ best_fixed) {
-  const int lane = threadIdx.x & 63;
-  const int i    = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= nm) return;  // (the whole wave)
-  unsigned long long key = NO_CANDIDATE;
-  unsigned sec           = NO_SECOND;
-  const int pixel        = m_pix[i];
-  if (pixel >= 0 && *error == 0) {  // (the same for every lane)
-    const int rv = pixel / cols, cu = pixel - rv * cols;
-    const int begin = row_begin[max(rv - radius, 0)], end = row_begin[min(rv + radius, rows - 1) + 1];
-    const uint4 a0 = m_desc[2 * (size_t) i], a1 = m_desc[2 * (size_t) i + 1];
-    for (int j = begin + lane; j < end; j += 64) {
-      const int fp = f_pixel[j];
-      const int dc = (fp - (fp / cols) * cols) - cu;
-      if (dc >= -radius && dc <= radius) {
-        const unsigned h = (unsigned) hamming(a0, a1, f_desc[2 * (size_t) j], f_desc[2 * (size_t) j + 1]);
-        merge_best(key, sec, ((unsigned long long) h << 32) | (unsigned) j, NO_SECOND);
-        if (best_fixed) atomicMin(&best_fixed[j], ((unsigned long long) h << 32) | (unsigned) i);
-      }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const unsigned long long k = __shfl_xor(key, off);
-      const unsigned s           = __shfl_xor(sec, off);
-      merge_best(key, sec, k, s);
-    }
-  }
-  if (lane == 0) {
-    best[i]   = key;
-    second[i] = sec;
-  }
-}
-
-// block sum -> ONE atomic per block (blockDim = 256)
-__device__ __forceinline__ void block_add(int v, int* target, int* red) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int t = (red[0] + red[1]) + (red[2] + red[3]);
-    if (t) atomicAdd(target, t);
-  }
-}
-
 // One thread per landmark; cross = 0: best_fixed is not read.  counters: the output block's first words.
 __global__ __launch_bounds__(256) void k_track_resolve(int nm, const int* __restrict__ m_pix, const unsigned long long* __restrict__ best,
                                                        const unsigned* __restrict__ second,
                                                        const unsigned long long* __restrict__ best_fixed, int max_distance,
                                                        int min_margin, int cross, srrg2_correspondence* __restrict__ rec,
                                                        int* __restrict__ flags, int* __restrict__ counters) {
-  __shared__ int red[4][4];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   int in_view = 0, candidate = 0, accepted = 0, mutual = 0;
   if (i < nm && counters[T_ERROR] == 0) {
@@ -169,10 +82,10 @@ __global__ __launch_bounds__(256) void k_track_resolve(int nm, const int* __rest
     rec[i] = c;
   }
   if (i < nm) flags[i] = mutual;
-  block_add(in_view, &counters[T_IN_VIEW], red[0]);
-  block_add(candidate, &counters[T_CANDIDATE], red[1]);
-  block_add(accepted, &counters[T_ACCEPTED], red[2]);
-  block_add(mutual, &counters[T_MUTUAL], red[3]);
+  block_add(in_view, &counters[T_IN_VIEW]);
+  block_add(candidate, &counters[T_CANDIDATE]);
+  block_add(accepted, &counters[T_ACCEPTED]);
+  block_add(mutual, &counters[T_MUTUAL]);
 }
 
 // offset: the exclusive scan of the keep flags (nm + 1 words); out holds cap records
@@ -273,11 +186,10 @@ extern "C" int srrg2_scene_track_features(srrg2_scene_h moving, srrg2_scene_h fi
   HIP_TRY(hipMemsetAsync(block, 0, T_WORDS * sizeof(int), st));
   if (reverse) HIP_TRY(hipMemsetAsync(reverse, 0xff, sizeof(unsigned long long) * (size_t) (nf + 1), st));
   hipLaunchKernelGGL(k_track_project, dim3(blocks_of(nm)), dim3(256), 0, st, C, moving->pts.p, nm, s->trk_pix.p);
-  hipLaunchKernelGGL(k_track_rows, dim3(blocks_of((long long) nf + 1)), dim3(256), 0, st, fixed->gidx.p, nf, rows, cols, s->trk_rows.p,
-                     block + T_ERROR);
-  hipLaunchKernelGGL(k_track_best, dim3((unsigned) ((nm + 3) / 4)), dim3(256), 0, st, nm, s->trk_pix.p, moving->desc.p, fixed->gidx.p,
-                     fixed->desc.p, s->trk_rows.p, rows, cols, p->search_radius, block + T_ERROR, s->trk_best.p, s->trk_second.p,
-                     reverse);
+  srrg2amd::launch_band_rows(fixed->gidx.p, nf, rows, cols, s->trk_rows.p, block + T_ERROR, st);
+  srrg2amd::launch_band_search(nm, s->trk_pix.p, moving->desc.p, fixed->gidx.p, fixed->desc.p, s->trk_rows.p, rows, cols,
+                               p->search_radius, -p->search_radius, p->search_radius, block + T_ERROR, s->trk_best.p,
+                               s->trk_second.p, reverse, st);
   hipLaunchKernelGGL(k_track_resolve, dim3(blocks_of(nm)), dim3(256), 0, st, nm, s->trk_pix.p, s->trk_best.p, s->trk_second.p, reverse,
                      p->max_distance, p->min_margin, p->cross_check, s->trk_rec.p, s->flags.p, block);
   srrg2amd::launch_exclusive_scan(s->flags.p, nm, s->scan_sums.p, block + T_TOTAL, st);

@@ -10,8 +10,9 @@ of 16 pixels keeps them out of the last 16 rows.
 STEREO_COUNT_CAP: srrg2_adapt_stereo_features (csrc/stereo.hip) launches k_stereo_count with at most 64 workgroups of 256 threads;
 more left keypoints than that send it round its loop again.
 
-Not built here: k_stereo_rows and k_stereo_scatter go through `blocks_for()` (csrc/scene_device.h), whose cap of 2048 * 256 =
-524 288 threads would need that many keypoints in one image; and the exclusive scan's second level needs more than 4 194 304
+Not built here: k_stereo_scatter goes through `blocks_for()` (csrc/scene_device.h), whose cap of 2048 * 256 = 524 288 threads
+would need that many keypoints in one image (the row table and the band search, csrc/desc_band.hip, have one thread or wave per
+element and no capped launch: there is no loop to reach); and the exclusive scan's second level needs more than 4 194 304
 pixels (tests/test_gpu_scene_large.py drives the same launch_exclusive_scan there).
 """
 import numpy as np

@@ -75,6 +75,14 @@ DENSE_PAIR = "120x160"
 TILED_DISPARITY = 10
 TILED = (dict(max_disparity=40, cross_check=False), dict(max_disparity=40), dict(max_disparity=20))
 
+# a gate of ONE column (min_disparity == max_disparity), in both directions: left -> right it admits the column c - 12 only,
+# right -> left the column c + 12 only.  The wide row band and the open distance gate give the right keypoints several left
+# keypoints to choose from, so that the cross check has something to reject (tests/test_stereo_restatement.py pins it)
+ONE_COLUMN_PAIR = "120x160"
+ONE_COLUMN_DISPARITY = 12
+ONE_COLUMN = tuple(dict(min_disparity=ONE_COLUMN_DISPARITY, max_disparity=ONE_COLUMN_DISPARITY, row_tolerance=8, max_distance=256,
+                        cross_check=cross) for cross in (True, False))
+
 _PAIRS = {}
 _EXTRACTED = {}
 _WANT = {}
@@ -113,5 +121,5 @@ def want(name, **kw):
 def all_cases():
     """[(pair name, parameters)]: everything the GPU test compares bit for bit and the CPU test draws its pins from"""
     out = [(n, v) for n, _, _ in pairs() for v in VARIANTS]
-    out += [(DENSE_PAIR, v) for v in DENSE] + [("tiled", v) for v in TILED]
+    out += [(DENSE_PAIR, v) for v in DENSE] + [("tiled", v) for v in TILED] + [(ONE_COLUMN_PAIR, v) for v in ONE_COLUMN]
     return out

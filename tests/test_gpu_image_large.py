@@ -10,8 +10,9 @@ that each case reaches the path it is here for:
   more left keypoints than k_stereo_count's grid has threads             test_stereo_bit_for_bit[odd_dense*]
   pitch != cols, partial tiles on both edges, hundreds of keypoint rows  the odd and hd cases of both
 
-Not reached, on purpose: the 524 288-thread cap of blocks_for() in k_stereo_rows and k_stereo_scatter (that many keypoints in one
-image) and the exclusive scan's second level (more than 4 194 304 pixels; tests/test_gpu_scene_large.py drives it).
+Not reached, on purpose: the 524 288-thread cap of blocks_for() in k_stereo_scatter (that many keypoints in one image; the row
+table of csrc/desc_band.hip is launched without a cap) and the exclusive scan's second level (more than 4 194 304 pixels;
+tests/test_gpu_scene_large.py drives it).
 
 The device's share of every test is milliseconds; the time is the CPU restatements', computed once per case and parameter set in
 image_large_cases and shared by the tests of a session (seconds on one core of the development machine: an extraction 0.3 to 0.9,

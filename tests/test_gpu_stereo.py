@@ -122,6 +122,19 @@ def test_dense_keypoints_long_bands_and_ties(product, device):
 
 
 @pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_one_column_disparity_gate(product, device):
+    """min_disparity == max_disparity with the cross check on and off: the gate is one column wide in each direction, and the
+    right -> left one rejects some left -> right bests (tests/test_stereo_restatement.py pins that)"""
+    scene = mapping.Scene(product.scene_binding(0), 3)
+    left, right = sc.named(sc.ONE_COLUMN_PAIR)
+    for kw in sc.ONE_COLUMN:
+        want = sc.want(sc.ONE_COLUMN_PAIR, **kw)
+        assert want["num_mutual"] >= 1
+        ad, res = _run(scene, left, right, device=device, **kw)
+        _check(scene, ad, res, want, (device, kw))
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
 def test_cap_cuts_inside_a_class_of_equal_scores(product, device):
     left, right = sc.named("tiled")
     _, caps = fc.tie_caps(left)

@@ -140,7 +140,7 @@ def test_match_banded_equals_the_all_pairs_restatement():
     assert a["matches"].tobytes() == b["matches"].tobytes() and a["num_left"] == b["num_left"] > 0
 
 
-# Row bands of more than 64 candidates (a second pass of k_stereo_best's wave) need the keypoints for it: `hd` under its cap of
+# Row bands of more than 64 candidates (a second pass of the band search's wave) need the keypoints for it: `hd` under its cap of
 # 1000 has fewer than two per row and cannot; `vga` and `odd` must.
 @pytest.mark.parametrize("name,kw", lc.STEREO_CASES, ids=["vga", "odd_dense", "odd_dense_one_way", "hd_1000"])
 def test_stereo_cases_discriminate(name, kw):

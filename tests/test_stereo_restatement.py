@@ -54,6 +54,21 @@ def test_a_tie_goes_to_the_smaller_pixel_index():
     assert (d2["left_pixel"][both] % cols - d2["right_pixel"][d2["best"][both]] % cols == sc.TILED_DISPARITY).all()
 
 
+def test_the_one_column_gate_is_used_in_both_directions():
+    """min_disparity == max_disparity: with the cross check there are mutual matches (right -> left finds the column c + d),
+    and left keypoints whose best is taken by another left keypoint (right -> left decides, not left -> right alone); every
+    candidate lies in exactly that column, and without the cross check exactly the rejected ones come back"""
+    on, off = (sc.want(sc.ONE_COLUMN_PAIR, **kw) for kw in sc.ONE_COLUMN)
+    assert sc.ONE_COLUMN[0]["cross_check"] and not sc.ONE_COLUMN[1]["cross_check"]
+    d = on["details"]
+    rejected = d["matched"] & ~d["mutual"]
+    assert on["num_mutual"] >= 1 and rejected.sum() >= 1, (on["num_mutual"], int(rejected.sum()))
+    cols = sc.named(sc.ONE_COLUMN_PAIR)[0].shape[1]
+    has = d["best"] >= 0
+    assert (d["left_pixel"][has] % cols - d["right_pixel"][d["best"][has]] % cols == sc.ONE_COLUMN_DISPARITY).all()
+    assert off["num_matched"] == on["num_matched"] and off["num_mutual"] == on["num_mutual"] + int(rejected.sum())
+
+
 def test_interior_matches_recover_the_band_disparity():
     """a left keypoint whose 31 x 31 window lies in one band and whose partner lies inside the right image's margin: distance 0,
     the band's disparity -- exactly without the sub-pixel step, within half a pixel with it"""

@@ -83,8 +83,14 @@ def test_the_cases_exercise_what_they_claim():
     w = tc.want(c)
     assert len(c["points"]) > tc.SCAN_TILE and 0 < w["num_mutual"] < w["num_accepted"] < w["num_with_candidate"] < w["num_in_view"] < len(c["points"])
     assert w["correspondences"]["moving_idx"].max() >= tc.SCAN_TILE  # (pairs behind the scan's first tile)
-    d = tc.want(tc.case("borders"))["details"]
+    c = tc.case("borders")
+    d = tc.want(c)["details"]
     assert d["in_view"].all() and (d["num_candidates"] >= 1).all()
+    # keypoints in the first and the last image row, and landmarks whose row band reaches each of them (and is cut there)
+    kp_rows, R, last = c["fixed_pixels"] // c["cols"], c["params"]["search_radius"], c["rows"] - 1
+    assert (kp_rows == 0).any() and (kp_rows == last).any()
+    assert (d["rv"] - R < 0).any() and (d["rv"] + R > last).any() and (d["rv"] == 0).any() and (d["rv"] == last).any()
+    assert c["rows"] == 40 and [v["params"]["search_radius"] for v in tc.variants("borders")[2:]] == [255, 0, 39, 40]
     for name in ("image_48x64", "image_67x101"):
         w = tc.want(tc.case(name))
         assert w["num_mutual"] >= 5, name

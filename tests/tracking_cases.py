@@ -9,7 +9,7 @@ its first bits.  What each case is for stands in its builder; tests/test_trackin
 really sees it (candidate counts, lanes, ties).
 
 SCAN_TILE: the exclusive scan (csrc/kernels_prep.hip) takes SCAN_THREADS * SCAN_ITEMS = 256 * 8 keep flags per workgroup; more
-landmarks than that go through its second level.  The tracker's own kernels (csrc/tracking.hip) have one thread or wave per
+landmarks than that go through its second level.  The tracker's own kernels (csrc/tracking.hip, csrc/desc_band.hip) have one thread or wave per
 element and no capped launch, so there is no other loop to reach; `large` also spans several workgroups of each of them.
 """
 import numpy as np
@@ -277,7 +277,9 @@ EXTRA = {
     "ties": [dict(min_margin=1), dict(min_margin=4), dict(min_margin=5), dict(min_margin=256), dict(min_margin=4, cross_check=False)],
     "gates": [dict(search_radius=0), dict(max_distance=0), dict(max_distance=256), dict(search_radius=255),
               dict(search_radius=0, max_distance=0, cross_check=False), dict(search_radius=1, max_distance=48)],
-    "borders": [dict(search_radius=255), dict(search_radius=0)],
+    # (keypoints in rows 0 and rows - 1: 39 is the radius at which a band from one extreme row ends exactly on the other --
+    # max(r - R, 0) and min(r + R, rows - 1) hit their limits unclamped -- and 40 the first that is cut there)
+    "borders": [dict(search_radius=255), dict(search_radius=0), dict(search_radius=39), dict(search_radius=40, cross_check=False)],
     "image_48x64": [dict(min_margin=0), dict(search_radius=20, max_distance=256)],
 }
 # (name, k) of every variant, without building a case
