@@ -300,7 +300,9 @@ int srrg2_aligner_set_correspondences(srrg2_aligner_h h, int slice_idx, const sr
                                       int n);
 /* K such alignments against the fixed cloud already set (the loop over _correspondences_per_reference,
  * :296-374): moving clouds concatenated with offsets[K+1], correspondences concatenated with
- * corr_offsets[K+1] (moving_idx relative to its own cloud).  Host pointers for the correspondences. */
+ * corr_offsets[K+1] (moving_idx relative to its own cloud).  Host pointers for the correspondences.
+ * Neither table needs to start at 0 (the clouds and the records of a pooled array); a negative first entry or a
+ * decreasing table is SRRG2_E_INVALID, refused before the handle is touched. */
 int srrg2_aligner_compute_batch_correspondences(srrg2_aligner_h h, int K, const float* coords, int coord_stride_bytes,
                                                 const float* normals, int normal_stride_bytes, const int32_t* offsets,
                                                 int mem, const srrg2_correspondence* correspondences,

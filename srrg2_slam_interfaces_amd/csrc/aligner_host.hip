@@ -2558,9 +2558,16 @@ int srrg2_aligner_compute_batch_correspondences(srrg2_aligner_h a, int K, const 
   if (K == 0) return 0;
   if (a->slices.empty() || a->slices[0]->cfg.finder != SRRG2_FINDER_CORRESPONDENCES)
     return fail(SRRG2_E_STATE, "compute_batch_correspondences: slice 0 must be a given-correspondences slice");
+  // (a negative first offset would copy records from in front of the caller's array: refused before the handle is touched)
+  if (corr_offsets[0] < 0) return fail(SRRG2_E_INVALID, "compute_batch_correspondences: negative offset");
   for (int k = 0; k < K; ++k)
     if (corr_offsets[k + 1] < corr_offsets[k]) return fail(SRRG2_E_INVALID, "compute_batch_correspondences: bad offsets");
   if (corr_offsets[K] > corr_offsets[0] && !corr) return fail(SRRG2_E_INVALID, "compute_batch_correspondences: null pairs");
+  // (compute_batch's own refusals of the cloud table, made here so that they leave the slice's pairs as they were)
+  if (K > 65535) return fail(SRRG2_E_INVALID, "compute_batch_correspondences: at most 65535 alignments per call (grid.y)");
+  if (offsets[0] < 0) return fail(SRRG2_E_INVALID, "compute_batch_correspondences: negative offset");
+  for (int k = 0; k < K; ++k)
+    if (offsets[k + 1] < offsets[k]) return fail(SRRG2_E_INVALID, "compute_batch_correspondences: offsets must not decrease");
   Slice* s = a->slices[0];
   s->h_gcorr.assign(corr + corr_offsets[0], corr + corr_offsets[K]);
   s->h_gcorr_off.resize((size_t) K + 1);
