@@ -418,12 +418,12 @@ int run_adapt(srrg2_scene* s, const S& src, int n, bool normals, bool intensity,
                          intensity ? s->inten.p : nullptr, s->gidx.p);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipMemcpyAsync(&s->scalars[8], counters, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&s->scalars.p[8], counters, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   s->pending = false;
   if (out) {
-    out->num_in_range = s->scalars[8];
-    out->num_valid    = s->scalars[9];
+    out->num_in_range = s->scalars.p[8];
+    out->num_valid    = s->scalars.p[9];
     out->scene_size   = s->n;
   }
   return 0;

@@ -32,6 +32,7 @@ namespace {
 using srrg2amd::DevBuf;
 using srrg2amd::fail;
 
+// (owned by its aligner, which has quiesced its streams before it deletes one: ~srrg2_aligner_s, clear_slices)
 struct Slice {
   srrg2_slice_config cfg;
   // fixed cloud + search grid
@@ -75,8 +76,8 @@ struct Slice {
   DevBuf<uint8_t> gcorr_stat;
   std::vector<srrg2_correspondence> h_gcorr;
   std::vector<int> h_gcorr_off;  // [K + 1]; empty: none set
-  int* qprobe_host = nullptr; size_t qprobe_cap = 0;  // pinned: deferred counts of the last finished iteration
-  ProblemDev* ms_probs_host = nullptr; size_t ms_probs_host_cap = 0;  // pinned: problem table of the last moving batch
+  srrg2amd::PinnedBuf<int> qprobe_host;  // pinned: deferred counts of the last finished iteration
+  srrg2amd::PinnedBuf<ProblemDev> ms_probs_host;  // pinned: problem table of the last moving batch
   bool ms_pending = false;  // a sort that reads ms_probs_host may still be in flight
   bool fast_queue_only = false;  // the queue exists for the converged pass of a batch only (k_icp_step does not use it)
   DevBuf<float4> prev_f;
@@ -92,7 +93,7 @@ struct Slice {
   const void* slots_zeroed_at = nullptr;
   int slots_zeroed = 0;
   // set_fixed's bounding box: written into pinned memory by the last block of k_ingest_bbox, word 8 = the sequence number polled for
-  unsigned* bbox_host = nullptr; size_t bbox_host_cap = 0;
+  srrg2amd::PinnedBuf<unsigned> bbox_host;
   unsigned bbox_seq = 0;
   bool scalars_self_init = false;  // the last set_fixed's k_ingest_bbox left the scalars as the next one needs them
   DevBuf<unsigned> bbox_rows;  // [INGEST_BBOX_MAX_BLOCKS][8]: the blocks' partial results of k_ingest_bbox
@@ -102,24 +103,6 @@ struct Slice {
   // prior
   float prior_Z[12]{};
   bool has_prior = false;
-  void release() {
-    if (qprobe_host) (void) hipHostFree(qprobe_host);
-    qprobe_host = nullptr;
-    qprobe_cap  = 0;
-    if (bbox_host) (void) hipHostFree(bbox_host);
-    bbox_host     = nullptr;
-    bbox_host_cap = 0;
-    if (ms_probs_host) (void) hipHostFree(ms_probs_host);
-    ms_probs_host     = nullptr;
-    ms_probs_host_cap = 0;
-    fixed_raw.release(); fixed_nrm_raw.release(); fixed_sorted.release(); fixed_nrm_sorted.release();
-    cell_start.release(); cursor.release(); scan_sums.release(); scalars.release(); pos_of.release();
-    list_start.release(); list_sums.release(); list_ent.release(); list_box.release(); list_offs.release(); list_hdr.release();
-    moving.release(); moving_nrm.release(); pinf.release();
-    moving_raw.release(); moving_nrm_raw.release(); ms_counts.release(); ms_cursor.release(); ms_sums.release();
-    ms_bb.release(); ms_probs.release();
-    corr_fixed.release(); gcorr.release(); gcorr_off.release(); gcorr_stat.release(); prev_n.release(); prev_pos.release(); prev_f.release(); prev_m.release(); corr_resp.release(); corr_stat.release(); partials.release(); zbuf.release(); queue.release(); qcount.release(); bbox_rows.release();
-  }
 };
 
 }  // namespace
@@ -149,7 +132,7 @@ struct srrg2_aligner_s {
   long long shard_total     = 0;
   bool has_term = false;
   srrg2_termination_params term{5, 20, 20, 20, 0.2f};
-  std::vector<Slice*> slices;
+  std::vector<Slice*> slices;  // owned: deleted by clear_slices and the destructor
   float X[12]{};
   int status = SRRG2_FAIL;
   // problems of the current batch (K = 1 for compute())
@@ -173,17 +156,17 @@ struct srrg2_aligner_s {
   DevBuf<ProblemDev> pair_fprobs;  // [K] {offset, count} of the fixed clouds
   DevBuf<GridDev> pair_grids;      // [K]
   DevBuf<char> pair_staging;       // the fixed clouds staged (host input; the moving ones use `staging`)
-  unsigned* pair_rows_host = nullptr; size_t pair_rows_host_cap = 0;  // pinned: the rows, read back once per call
-  ProblemDev* pair_fprobs_host = nullptr; size_t pair_fprobs_host_cap = 0;
-  GridDev* pair_grids_host = nullptr; size_t pair_grids_host_cap = 0;
+  srrg2amd::PinnedBuf<unsigned> pair_rows_host;  // pinned: the rows, read back once per call
+  srrg2amd::PinnedBuf<ProblemDev> pair_fprobs_host;
+  srrg2amd::PinnedBuf<GridDev> pair_grids_host;
   bool pair_normals  = false;         // the fixed clouds of the pair batch at hand have normals
   bool pairs_computed = false;        // the last compute was a pair batch: it left no correspondence records
   // pinned host mirrors
-  ProblemOut* outs_host = nullptr; size_t outs_host_cap = 0;
+  srrg2amd::PinnedBuf<ProblemOut> outs_host;
   int seq = 0;  // sequence number of the last compute() (completion flags in outs_host)
-  srrg2_iteration_stats* stats_host = nullptr; size_t stats_host_cap = 0;
-  float* guesses_host = nullptr; size_t guesses_host_cap = 0;
-  ProblemDev* probs_host = nullptr; size_t probs_host_cap = 0;
+  srrg2amd::PinnedBuf<srrg2_iteration_stats> stats_host;
+  srrg2amd::PinnedBuf<float> guesses_host;
+  srrg2amd::PinnedBuf<ProblemDev> probs_host;
   int max_stats = 0;
   std::vector<srrg2_iteration_stats> last_stats;  // of problem K-1 (== the only one for compute())
   int last_ncorr[SRRG2_MAX_SLICES]{};
@@ -206,6 +189,22 @@ struct srrg2_aligner_s {
   int64_t prof_launches = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
   size_t prof_used = 0;
+  // The ordering is what this destructor is for: every stream retires before any buffer above, the slices' included, is
+  // freed (the members free themselves after this body).
+  ~srrg2_aligner_s() {
+    (void) hipSetDevice(device);
+    for (int p = 0; p < MAX_PARTS; ++p)
+      if (pstream[p]) (void) hipStreamSynchronize(pstream[p]);
+    for (Slice* s : slices) delete s;
+    for (auto& ev : prof_events) {
+      (void) hipEventDestroy(ev.first);
+      (void) hipEventDestroy(ev.second);
+    }
+    if (ev_staged) (void) hipEventDestroy(ev_staged);
+    if (ev_records) (void) hipEventDestroy(ev_records);
+    for (int p = MAX_PARTS - 1; p >= 0; --p)
+      if (pstream[p]) (void) hipStreamDestroy(pstream[p]);
+  }
 };
 
 namespace {
@@ -239,17 +238,6 @@ int quiesce_stream2(srrg2_aligner* a) {
   const int n    = a->parts_dirty;
   a->parts_dirty = 0;
   for (int p = 1; p < n; ++p) HIP_TRY(hipStreamSynchronize(a->pstream[p]));
-  return 0;
-}
-
-template <typename T>
-int ensure_pinned(T*& p, size_t& cap, size_t n) {
-  if (n <= cap) return 0;
-  if (p) (void) hipHostFree(p);
-  p = nullptr;
-  cap = 0;
-  HIP_TRY(hipHostMalloc((void**) &p, (n + 16) * sizeof(T), hipHostMallocDefault));
-  cap = n + 16;
   return 0;
 }
 
@@ -314,7 +302,7 @@ int build_grid(srrg2_aligner* a, Slice* s, float force_h = 0.f, bool have_bbox =
   unsigned back[8];
   bool polled = false;
   if (have_bbox) {  // (set_fixed: the last block of k_ingest_bbox has left box and count in pinned memory)
-    volatile unsigned* flag = s->bbox_host + 8;
+    volatile unsigned* flag = s->bbox_host.p + 8;
     int spins = 0;
     polled    = true;
     while (*flag != s->bbox_seq)
@@ -323,7 +311,7 @@ int build_grid(srrg2_aligner* a, Slice* s, float force_h = 0.f, bool have_bbox =
         break;
       }
     if (polled)
-      for (int i = 0; i < 7; ++i) back[i] = s->bbox_host[i];
+      for (int i = 0; i < 7; ++i) back[i] = s->bbox_host.p[i];
   }
   if (!polled) {
     HIP_TRY(hipMemcpyAsync(back, s->scalars.p, 8 * sizeof(unsigned), hipMemcpyDeviceToHost, a->stream));
@@ -743,10 +731,10 @@ int upload_moving(srrg2_aligner* a, int si, const float* coords, int cs, const f
   // table read from pinned host memory (no copies, memsets or waits on the stream); the ingest-order copy of the
   // clouds, which this path does not produce, is only read by given-correspondences slices
   if (kbits <= 15 && s->cfg.finder != SRRG2_FINDER_CORRESPONDENCES) {
-    if ((rc = ensure_pinned(s->ms_probs_host, s->ms_probs_host_cap, (size_t) K))) return rc;
+    if ((rc = s->ms_probs_host.reserve((size_t) K, 16))) return rc;
     if (s->ms_pending) HIP_TRY(hipStreamSynchronize(a->stream));  // (set_moving twice without a compute() in between)
     s->ms_pending = false;
-    std::memcpy(s->ms_probs_host, pd.data(), (size_t) K * sizeof(ProblemDev));
+    std::memcpy(s->ms_probs_host.p, pd.data(), (size_t) K * sizeof(ProblemDev));
     bool sorted = false;
     if (nparts >= 2 && nparts <= srrg2_aligner::MAX_PARTS && pbegin) {
       // pipelined batch: every part is sorted on its own stream (behind the staging copies of this call), the later parts
@@ -759,7 +747,7 @@ int upload_moving(srrg2_aligner* a, int si, const float* coords, int cs, const f
       for (int p = 0; p < nparts && sorted; ++p) {
         int nmp = 0;
         for (int k = pbegin[p]; k < pbegin[p + 1]; ++k) nmp = std::max(nmp, pd[k].nm);
-        sorted = srrg2amd::launch_msort_local(dsrc, sf, nsrc, nsf, s->ms_probs_host + pbegin[p], pbegin[p + 1] - pbegin[p], a->dim,
+        sorted = srrg2amd::launch_msort_local(dsrc, sf, nsrc, nsf, s->ms_probs_host.p + pbegin[p], pbegin[p + 1] - pbegin[p], a->dim,
                                               kbits, aniso, a->tuning.msort_segments, nmp, s->moving.p,
                                               normals ? s->moving_nrm.p : nullptr, s->pinf.p + pbegin[p], a->pstream[p]);
         if (p > 0) a->parts_dirty = std::max(a->parts_dirty, p + 1);
@@ -769,7 +757,7 @@ int upload_moving(srrg2_aligner* a, int si, const float* coords, int cs, const f
         for (int p = 0; p <= nparts; ++p) a->part_begin[p] = pbegin[p];
       }
     } else {
-      sorted = srrg2amd::launch_msort_local(dsrc, sf, nsrc, nsf, s->ms_probs_host, K, a->dim, kbits, aniso, a->tuning.msort_segments,
+      sorted = srrg2amd::launch_msort_local(dsrc, sf, nsrc, nsf, s->ms_probs_host.p, K, a->dim, kbits, aniso, a->tuning.msort_segments,
                                             max_nm, s->moving.p, normals ? s->moving_nrm.p : nullptr, s->pinf.p, a->stream);
     }
     if (sorted) {
@@ -884,13 +872,13 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   if ((rc = a->outs.reserve((size_t) K))) return rc;
   if ((rc = a->stats.reserve((size_t) K * slots))) return rc;
   if ((rc = a->guesses.reserve((size_t) K * a->tsize))) return rc;
-  if ((rc = ensure_pinned(a->outs_host, a->outs_host_cap, (size_t) K))) return rc;
-  if ((rc = ensure_pinned(a->stats_host, a->stats_host_cap, (size_t) K * slots))) return rc;
-  if ((rc = ensure_pinned(a->guesses_host, a->guesses_host_cap, (size_t) K * a->tsize))) return rc;
+  if ((rc = a->outs_host.reserve((size_t) K, 16))) return rc;
+  if ((rc = a->stats_host.reserve((size_t) K * slots, 16))) return rc;
+  if ((rc = a->guesses_host.reserve((size_t) K * a->tsize, 16))) return rc;
   // guesses and problem tables go through pinned host memory that k_icp_init reads directly (no copies on the stream;
   // the previous compute() has been waited for, so the buffers are free)
-  std::memcpy(a->guesses_host, guesses, (size_t) K * a->tsize * sizeof(float));
-  if ((rc = ensure_pinned(a->probs_host, a->probs_host_cap, (size_t) K * std::max(nslices, 1)))) return rc;
+  std::memcpy(a->guesses_host.p, guesses, (size_t) K * a->tsize * sizeof(float));
+  if ((rc = a->probs_host.reserve((size_t) K * std::max(nslices, 1), 16))) return rc;
   // per-slice problem tables live back to back in a->probs: [slice][K]
   std::vector<ProblemDev> all((size_t) K * std::max(nslices, 1));
   for (int si = 0; si < nslices; ++si) {
@@ -911,7 +899,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
       all[(size_t) si * K + k] = pd;
     }
   }
-  std::memcpy(a->probs_host, all.data(), all.size() * sizeof(ProblemDev));
+  std::memcpy(a->probs_host.p, all.data(), all.size() * sizeof(ProblemDev));
 
   CtlParams C{};
   C.variable_kind = a->kind;
@@ -923,7 +911,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   C.max_stats     = slots;
   C.seq           = ++a->seq;
   if (C.seq <= 0) C.seq = a->seq = 1;
-  for (int k = 0; k < K; ++k) a->outs_host[k].seq = 0;  // (never a sequence number: fresh pinned memory is not zeroed)
+  for (int k = 0; k < K; ++k) a->outs_host.p[k].seq = 0;  // (never a sequence number: fresh pinned memory is not zeroed)
   const srrg2_aligner_tuning& tn = a->tuning;  // (read once at create / set_tuning: no environment look-ups in compute())
   C.probe_it      = tn.queue_probe_iteration;
   if (a->params.max_iterations <= C.probe_it + 3 || K > 4) C.probe_it = -1;
@@ -1086,9 +1074,9 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     sc.qprobe_host = nullptr;
     sc.probs       = nullptr;
     if (use_queue) {
-      if ((rc = ensure_pinned(s->qprobe_host, s->qprobe_cap, (size_t) 2 * K))) return rc;
-      std::memset(s->qprobe_host, 0x7f, sizeof(int) * (size_t) 2 * K);  // "large" until the device reports
-      sc.qprobe_host = s->qprobe_host;
+      if ((rc = s->qprobe_host.reserve((size_t) 2 * K, 16))) return rc;
+      std::memset(s->qprobe_host.p, 0x7f, sizeof(int) * (size_t) 2 * K);  // "large" until the device reports
+      sc.qprobe_host = s->qprobe_host.p;
       sc.probs       = a->probs.p + (size_t) si * K;
     }
     // (k_icp_init zeroes the slot sets and the queue counters; afterwards the control kernel resets them each iteration)
@@ -1364,7 +1352,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     const Slice* s = a->slices[first_cue];
     fold_init = s->slots_zeroed >= 3 * K && s->slots_zeroed_at == (const void*) s->partials.p;
     if (fold_init) {
-      const bool single = srrg2amd::make_init_inline(Ch[0], a->probs_host, a->guesses_host, a->tsize, &fold_inl);
+      const bool single = srrg2amd::make_init_inline(Ch[0], a->probs_host.p, a->guesses_host.p, a->tsize, &fold_inl);
       for (int si = 0; si < nslices && fold_init; ++si)  // (a prior slice that sets the initial guess: k_icp_init's override, here)
         if (C.slices[si].kind == SRRG2_SLICE_PRIOR && C.slices[si].prior_sets_initial_guess) {
           if (single)
@@ -1378,8 +1366,8 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
           InitBatch& B = fold_bat[(size_t) h];
           B.cue_slice  = first_cue;
           for (int k = 0; k < hn[h]; ++k) {
-            for (int i = 0; i < 12; ++i) B.guess[k][i] = i < a->tsize ? a->guesses_host[(size_t) (h0[h] + k) * a->tsize + i] : 0.f;
-            B.pd[k] = a->probs_host[(size_t) first_cue * K + h0[h] + k];
+            for (int i = 0; i < 12; ++i) B.guess[k][i] = i < a->tsize ? a->guesses_host.p[(size_t) (h0[h] + k) * a->tsize + i] : 0.f;
+            B.pd[k] = a->probs_host.p[(size_t) first_cue * K + h0[h] + k];
           }
         }
       }
@@ -1393,7 +1381,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
       fold_init = fold_init && s->slots_zeroed >= 3 * K && s->slots_zeroed_at == (const void*) s->partials.p;
     }
     if (fold_init) {
-      fold_init = srrg2amd::make_init_inline(Ch[0], a->probs_host, a->guesses_host, a->tsize, &fold_inl);
+      fold_init = srrg2amd::make_init_inline(Ch[0], a->probs_host.p, a->guesses_host.p, a->tsize, &fold_inl);
       for (int si = 0; si < nslices && fold_init; ++si)
         if (C.slices[si].kind == SRRG2_SLICE_PRIOR && C.slices[si].prior_sets_initial_guess)
           for (int i = 0; i < a->tsize; ++i) fold_inl.guess[i] = C.slices[si].prior_Z[i];
@@ -1402,18 +1390,18 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   for (Slice* sl : a->slices) sl->slots_zeroed = 0;  // (until this compute() has ended the same way)
   if (!fold_init)
     for (int h = 0; h < nhalves; ++h)
-      srrg2amd::launch_icp_init(Ch[h], a->probs_host, a->probs.p, a->states.p, a->guesses_host, a->tsize, hstream[h], pairs);
+      srrg2amd::launch_icp_init(Ch[h], a->probs_host.p, a->probs.p, a->states.p, a->guesses_host.p, a->tsize, hstream[h], pairs);
   auto t_init = std::chrono::steady_clock::now();
 
   if (small) {
     Slice* s = a->slices[first_cue];
     if (pairs)
       srrg2amd::launch_icp_small_pairs(a->dim, s->cfg.kind == SRRG2_SLICE_P2PLANE, sdev[first_cue], pair_grids, C,
-                                       a->probs.p + (size_t) first_cue * K, a->states.p, a->stats.p, a->outs_host, a->stats_host,
+                                       a->probs.p + (size_t) first_cue * K, a->states.p, a->stats.p, a->outs_host.p, a->stats_host.p,
                                        a->stream);
     else
       srrg2amd::launch_icp_small(a->dim, s->cfg.kind == SRRG2_SLICE_P2PLANE, sdev[first_cue], C,
-                                 a->probs.p + (size_t) first_cue * K, a->states.p, a->stats.p, a->outs_host, a->stats_host,
+                                 a->probs.p + (size_t) first_cue * K, a->states.p, a->stats.p, a->outs_host.p, a->stats_host.p,
                                  a->stream);
   }
   // Adaptive use of the deferred-search kernel.  After iteration `probe_it` the control kernel looks at what that
@@ -1432,7 +1420,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
     probed = true;
     for (int si = 0; si < nslices; ++si) {
       if (!sdev[si].queue) continue;
-      volatile int* mirror = a->slices[si]->qprobe_host;
+      volatile int* mirror = a->slices[si]->qprobe_host.p;
       bool small           = true;
       for (int k = 0; k < K; ++k) {
         int spins = 0;
@@ -1498,7 +1486,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
           pack[z].fc.prev_partials = slot_buffer(sz, pround);
           pack[z].fc.zero_partials = slot_buffer(sz, pround + 2);
         }
-        srrg2amd::launch_icp_final_wave_pack(pack, pp, (int) proj_group.size(), a->states.p, a->stats.p, a->outs_host, a->stats_host,
+        srrg2amd::launch_icp_final_wave_pack(pack, pp, (int) proj_group.size(), a->states.p, a->stats.p, a->outs_host.p, a->stats_host.p,
                                              !a->params.enable_inlier_only_runs, hstream[h]);
       } else if (fuse) {
         SliceDev sd          = sdev[first_cue];
@@ -1507,10 +1495,10 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
         sd.fc.epoch          = epoch + 1;
         sd.fc.prev_partials  = slot_buffer(a->slices[first_cue], pround);
         sd.fc.zero_partials  = slot_buffer(a->slices[first_cue], pround + 2);
-        srrg2amd::launch_icp_final_wave(Ch[h], sd, a->states.p, a->stats.p, a->outs_host, a->stats_host,
+        srrg2amd::launch_icp_final_wave(Ch[h], sd, a->states.p, a->stats.p, a->outs_host.p, a->stats_host.p,
                                         !a->params.enable_inlier_only_runs, hstream[h]);
       } else {
-        srrg2amd::launch_icp_control_final(Ch[h], a->states.p, a->stats.p, a->outs_host, a->stats_host,
+        srrg2amd::launch_icp_control_final(Ch[h], a->states.p, a->stats.p, a->outs_host.p, a->stats_host.p,
                                            !a->params.enable_inlier_only_runs /* post step inside */, hstream[h]);
       }
       final_launched = true;
@@ -1682,7 +1670,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   // the launches is this wait
   if (!final_launched)  // (max_iterations < 1)
     for (int h = 0; h < nhalves; ++h)
-      srrg2amd::launch_icp_finalize(Ch[h], a->states.p, a->stats.p, a->outs_host, a->stats_host,
+      srrg2amd::launch_icp_finalize(Ch[h], a->states.p, a->stats.p, a->outs_host.p, a->stats_host.p,
                                     !a->params.enable_inlier_only_runs /* post step inside */, hstream[h]);
   if (split) a->parts_dirty = std::max(a->parts_dirty, split);
   HIP_TRY(hipGetLastError());
@@ -1694,7 +1682,7 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   // when something else needs it idle (event timing, the timeline dump) or when it reports an error.
   bool seen = true;
   for (int k = 0; k < K && seen; ++k) {
-    volatile int* flag = &a->outs_host[k].seq;
+    volatile int* flag = &a->outs_host.p[k].seq;
     int spins          = 0;
     hipStream_t qs = a->stream;
     for (int h = 1; h < nhalves; ++h)
@@ -1746,11 +1734,11 @@ int run_compute(srrg2_aligner* a, int K, const int32_t* offsets /* K+1 or null f
   for (Slice* sl : a->slices) sl->ms_pending = false;  // (the stream has drained)
   a->K = K;
   // the handle's observable state is that of the last alignment (sequential semantics)
-  const ProblemOut& o = a->outs_host[K - 1];
+  const ProblemOut& o = a->outs_host.p[K - 1];
   std::memcpy(a->X, o.X, sizeof(float) * a->tsize);
   a->status = o.status;
   int ns    = std::min(o.nstats, slots);
-  a->last_stats.assign(a->stats_host + (size_t) (K - 1) * slots, a->stats_host + (size_t) (K - 1) * slots + ns);
+  a->last_stats.assign(a->stats_host.p + (size_t) (K - 1) * slots, a->stats_host.p + (size_t) (K - 1) * slots + ns);
   for (int si = 0; si < SRRG2_MAX_SLICES; ++si) a->last_ncorr[si] = o.ncorr[si];
   std::memcpy(a->last_H, o.H, sizeof(a->last_H));
   a->computed = true;
@@ -1812,12 +1800,12 @@ int plan_batch_parts(srrg2_aligner* a, int K, const int32_t* offsets, int* pbegi
 void fill_batch_results(const srrg2_aligner* a, int K, srrg2_batch_result* results) {
   const int slots = a->max_stats;
   for (int k = 0; k < K; ++k) {
-    const ProblemOut& o = a->outs_host[k];
+    const ProblemOut& o = a->outs_host.p[k];
     std::memset(&results[k], 0, sizeof(results[k]));
     std::memcpy(results[k].moving_in_fixed, o.X, sizeof(float) * a->tsize);
     results[k].status         = o.status;
     results[k].num_iterations = o.nstats;
-    if (o.nstats > 0) results[k].last = a->stats_host[(size_t) k * slots + std::min(o.nstats, slots) - 1];
+    if (o.nstats > 0) results[k].last = a->stats_host.p[(size_t) k * slots + std::min(o.nstats, slots) - 1];
     int tot = 0;  // multi_aligner_impl.cpp:275-285, after pruning (k_icp_finalize)
     for (size_t si = 0; si < a->slices.size(); ++si) {
       const int c = a->slices[si]->cfg.kind == SRRG2_SLICE_PRIOR ? 1 : o.ncorr[si];
@@ -1973,7 +1961,8 @@ int srrg2_aligner_create(int variable_kind, int device, srrg2_aligner_h* out) {
   if (e != hipSuccess || n <= 0)
     return fail(SRRG2_E_NO_DEVICE, "create: no HIP device visible (this library has no CPU fallback)");
   if (device < 0 || device >= n) return fail(SRRG2_E_INVALID, "create: bad device ordinal");
-  srrg2_aligner* a = new srrg2_aligner();
+  std::unique_ptr<srrg2_aligner> owner(new srrg2_aligner());  // (a failure below deletes it: streams and events go with it)
+  srrg2_aligner* const a = owner.get();
   a->kind   = variable_kind;
   a->dim    = variable_kind == SRRG2_SE2_RIGHT ? 2 : 3;
   a->dof    = variable_kind == SRRG2_SE2_RIGHT ? 3 : 6;
@@ -1993,47 +1982,13 @@ int srrg2_aligner_create(int variable_kind, int device, srrg2_aligner_h* out) {
     a->cu_count = 256;
   }
   a->search_capacity.cu_count = a->cu_count;
-  if (!ok) {
-    for (int p = 0; p < srrg2_aligner::MAX_PARTS; ++p)
-      if (a->pstream[p]) (void) hipStreamDestroy(a->pstream[p]);
-    delete a;
-    return fail(SRRG2_E_HIP, "create: cannot create stream");
-  }
-  *out = a;
+  if (!ok) return fail(SRRG2_E_HIP, "create: cannot create stream");
+  *out = owner.release();
   return 0;
 }
 
 int srrg2_aligner_destroy(srrg2_aligner_h a) {
-  if (!a) return 0;
-  (void) hipSetDevice(a->device);
-  for (int p = 0; p < srrg2_aligner::MAX_PARTS; ++p)
-    if (a->pstream[p]) (void) hipStreamSynchronize(a->pstream[p]);
-  for (Slice* s : a->slices) {
-    s->release();
-    delete s;
-  }
-  a->probs.release(); a->states.release(); a->outs.release(); a->stats.release(); a->guesses.release();
-  a->pub.release(); a->pub_epoch.release(); a->ctl_dev.release();
-  a->staging.release();
-  a->pair_raw.release(); a->pair_nrm_raw.release(); a->pair_sorted.release(); a->pair_nrm_sorted.release();
-  a->pair_cell_start.release(); a->pair_cursor.release(); a->pair_scan_sums.release(); a->pair_pos_of.release();
-  a->pair_rows.release(); a->pair_fprobs.release(); a->pair_grids.release(); a->pair_staging.release();
-  if (a->pair_rows_host) (void) hipHostFree(a->pair_rows_host);
-  if (a->pair_fprobs_host) (void) hipHostFree(a->pair_fprobs_host);
-  if (a->pair_grids_host) (void) hipHostFree(a->pair_grids_host);
-  if (a->outs_host) (void) hipHostFree(a->outs_host);
-  if (a->stats_host) (void) hipHostFree(a->stats_host);
-  if (a->guesses_host) (void) hipHostFree(a->guesses_host);
-  if (a->probs_host) (void) hipHostFree(a->probs_host);
-  for (auto& ev : a->prof_events) {
-    (void) hipEventDestroy(ev.first);
-    (void) hipEventDestroy(ev.second);
-  }
-  if (a->ev_staged) (void) hipEventDestroy(a->ev_staged);
-  if (a->ev_records) (void) hipEventDestroy(a->ev_records);
-  for (int p = srrg2_aligner::MAX_PARTS - 1; p >= 0; --p)
-    if (a->pstream[p]) (void) hipStreamDestroy(a->pstream[p]);
-  delete a;
+  delete a;  // (null: nothing to do)
   return 0;
 }
 
@@ -2089,10 +2044,7 @@ int srrg2_aligner_clear_slices(srrg2_aligner_h a) {
   if (!a) return fail(SRRG2_E_INVALID, "clear_slices: null handle");
   (void) hipSetDevice(a->device);
   (void) hipStreamSynchronize(a->stream);
-  for (Slice* s : a->slices) {
-    s->release();
-    delete s;
-  }
+  for (Slice* s : a->slices) delete s;
   a->slices.clear();
   return 0;
 }
@@ -2136,12 +2088,12 @@ int srrg2_aligner_set_fixed(srrg2_aligner_h a, int si, const float* coords, int 
   if ((rc = stage_input(a, coords, cs, n, a->dim, mem, &dsrc, &sf, 0))) return rc;
   if (nn) {
     // (the box comes back through pinned memory: word 8 = this call's sequence number, never 0; scalars[11] = the blocks' ticket)
-    if ((rc = ensure_pinned(s->bbox_host, s->bbox_host_cap, (size_t) 16))) return rc;
+    if ((rc = s->bbox_host.reserve((size_t) 16, 16))) return rc;
     if ((rc = s->bbox_rows.reserve((size_t) INGEST_BBOX_MAX_BLOCKS * 8))) return rc;
     if (++s->bbox_seq == 0) s->bbox_seq = 1;
-    s->bbox_host[8] = 0;
+    s->bbox_host.p[8] = 0;
     srrg2amd::launch_ingest_bbox(dsrc, sf, n, a->dim, s->fixed_raw.p, s->scalars.p + 10, s->scalars.p, s->scalars.p + 3,
-                                 (int*) (s->scalars.p + 6), a->stream, s->scalars.p + 11, s->bbox_host, s->bbox_seq, s->bbox_rows.p,
+                                 (int*) (s->scalars.p + 6), a->stream, s->scalars.p + 11, s->bbox_host.p, s->bbox_seq, s->bbox_rows.p,
                                  s->scalars.p + 7);
     s->scalars_self_init = n > 0;
   }
@@ -2178,6 +2130,13 @@ int srrg2_aligner_set_moving(srrg2_aligner_h a, int si, const float* coords, int
   return upload_moving(a, si, coords, cs, normals, ns, offsets, 1, mem, /*wait=*/mem != SRRG2_MEM_DEVICE_KEPT);
 }
 
+// Not ownership bookkeeping (the buffers free themselves): the clouds a sharing slice views in place of its own -- the arrays
+// run_compute borrows -- dropped early when sharing begins (its own copies) and when it ends (the views)
+static void drop_shared_clouds(Slice* s) {
+  s->fixed_raw.release(); s->fixed_nrm_raw.release(); s->moving.release(); s->moving_nrm.release();
+  s->moving_raw.release(); s->moving_nrm_raw.release(); s->pinf.release(); s->scalars.release();
+}
+
 int srrg2_aligner_share_clouds(srrg2_aligner_h a, int si, int source) {
   int rc = check_slice(a, si, "share_clouds");
   if (rc) return rc;
@@ -2185,8 +2144,7 @@ int srrg2_aligner_share_clouds(srrg2_aligner_h a, int si, int source) {
     Slice* s = a->slices[si];
     if (s->alias_of >= 0) {
       s->alias_of = -1;
-      s->fixed_raw.release(); s->fixed_nrm_raw.release(); s->moving.release(); s->moving_nrm.release();
-      s->moving_raw.release(); s->moving_nrm_raw.release(); s->pinf.release(); s->scalars.release();
+      drop_shared_clouds(s);
       s->has_fixed = s->has_moving = false;
       s->nf = s->nm_total = 0;
     }
@@ -2205,8 +2163,7 @@ int srrg2_aligner_share_clouds(srrg2_aligner_h a, int si, int source) {
   HIP_TRY(hipStreamSynchronize(a->stream));
   s->alias_of = source;
   // (its own copies, if any, are dropped: from now on it views the source's buffers, re-borrowed at every compute())
-  s->fixed_raw.release(); s->fixed_nrm_raw.release(); s->moving.release(); s->moving_nrm.release();
-  s->moving_raw.release(); s->moving_nrm_raw.release(); s->pinf.release(); s->scalars.release();
+  drop_shared_clouds(s);
   if (a->computed) a->records_state = 2;
   return 0;
 }
@@ -2245,7 +2202,7 @@ int srrg2_amd_device_malloc(size_t bytes, void** out) {
 }
 
 int srrg2_amd_device_free(void* p) {
-  if (p) HIP_TRY(hipFree(p));
+  if (p) HIP_TRY(srrg2amd::device_free(p));
   return 0;
 }
 
@@ -2626,13 +2583,13 @@ int srrg2_align_pairs(srrg2_aligner_h a, int K, const float* fixed_coords, int f
   // 1. the fixed clouds: one ingest for all of them, with the per-pair rows, read back with ONE copy and one wait
   const size_t nfa = (size_t) std::max(nf_all, 1);
   int max_nf = 0;
-  if ((rc = ensure_pinned(a->pair_fprobs_host, a->pair_fprobs_host_cap, (size_t) K)) ||
-      (rc = ensure_pinned(a->pair_rows_host, a->pair_rows_host_cap, (size_t) K * PAIR_ROW_WORDS)) ||
-      (rc = ensure_pinned(a->pair_grids_host, a->pair_grids_host_cap, (size_t) K)))
+  if ((rc = a->pair_fprobs_host.reserve((size_t) K, 16)) ||
+      (rc = a->pair_rows_host.reserve((size_t) K * PAIR_ROW_WORDS, 16)) ||
+      (rc = a->pair_grids_host.reserve((size_t) K, 16)))
     return rc;
   for (int k = 0; k < K; ++k) {
-    a->pair_fprobs_host[k] = ProblemDev{fixed_offsets[k] - fixed_offsets[0], fixed_offsets[k + 1] - fixed_offsets[k]};
-    max_nf                 = std::max(max_nf, a->pair_fprobs_host[k].nm);
+    a->pair_fprobs_host.p[k] = ProblemDev{fixed_offsets[k] - fixed_offsets[0], fixed_offsets[k + 1] - fixed_offsets[k]};
+    max_nf                 = std::max(max_nf, a->pair_fprobs_host.p[k].nm);
   }
   if ((rc = a->pair_raw.reserve(nfa)) || (fixed_normals && (rc = a->pair_nrm_raw.reserve(nfa))) ||
       (rc = a->pair_rows.reserve((size_t) K * PAIR_ROW_WORDS)) || (rc = a->pair_fprobs.reserve((size_t) K)) ||
@@ -2656,11 +2613,11 @@ int srrg2_align_pairs(srrg2_aligner_h a, int K, const float* fixed_coords, int f
     if ((rc = stage_input(a, nbase, fns, nf_all, dim, mem, &nsrc, &nsf, (bytes_c + 63) / 64 * 64, &a->pair_staging)))
       return drain(rc);
   }
-  PAIRS_TRY(hipMemcpyAsync(a->pair_fprobs.p, a->pair_fprobs_host, sizeof(ProblemDev) * (size_t) K, hipMemcpyHostToDevice, a->stream));
+  PAIRS_TRY(hipMemcpyAsync(a->pair_fprobs.p, a->pair_fprobs_host.p, sizeof(ProblemDev) * (size_t) K, hipMemcpyHostToDevice, a->stream));
   PAIRS_TRY(hipMemsetAsync(a->pair_rows.p, 0, sizeof(unsigned) * (size_t) K * PAIR_ROW_WORDS, a->stream));
   srrg2amd::launch_pairs_ingest(fsrc, fsf, nsrc, nsf, a->pair_fprobs.p, K, max_nf, dim, a->pair_raw.p,
                                 fixed_normals ? a->pair_nrm_raw.p : nullptr, a->pair_rows.p, a->stream);
-  PAIRS_TRY(hipMemcpyAsync(a->pair_rows_host, a->pair_rows.p, sizeof(unsigned) * (size_t) K * PAIR_ROW_WORDS, hipMemcpyDeviceToHost,
+  PAIRS_TRY(hipMemcpyAsync(a->pair_rows_host.p, a->pair_rows.p, sizeof(unsigned) * (size_t) K * PAIR_ROW_WORDS, hipMemcpyDeviceToHost,
                            a->stream));
   PAIRS_TRY(hipStreamSynchronize(a->stream));
   // 2. the grids' records on the host from the rows (before the slice's moving cloud is touched: a batch whose grids do not fit
@@ -2669,8 +2626,8 @@ int srrg2_align_pairs(srrg2_aligner_h a, int K, const float* fixed_coords, int f
   int max_cells   = 0;
   std::vector<long long> coff((size_t) K);
   for (int k = 0; k < K; ++k) {
-    const long long nc = pair_grid_of(a, s, a->pair_rows_host + (size_t) k * PAIR_ROW_WORDS, a->pair_fprobs_host[k].nm,
-                                      a->pair_grids_host[k]);
+    const long long nc = pair_grid_of(a, s, a->pair_rows_host.p + (size_t) k * PAIR_ROW_WORDS, a->pair_fprobs_host.p[k].nm,
+                                      a->pair_grids_host.p[k]);
     coff[(size_t) k] = total;
     total += nc + 1;  // (+ the cell of the non-finite points)
     max_cells = (int) std::max((long long) max_cells, nc);
@@ -2682,8 +2639,8 @@ int srrg2_align_pairs(srrg2_aligner_h a, int K, const float* fixed_coords, int f
       (fixed_normals && (rc = a->pair_nrm_sorted.reserve(nfa + 8))) || (rc = a->pair_pos_of.reserve(nfa)))
     return rc;
   for (int k = 0; k < K; ++k) {
-    GridDev& g     = a->pair_grids_host[k];
-    const int foff = a->pair_fprobs_host[k].moff;
+    GridDev& g     = a->pair_grids_host.p[k];
+    const int foff = a->pair_fprobs_host.p[k].moff;
     g.cell_start   = a->pair_cell_start.p + coff[(size_t) k];
     g.pts          = a->pair_sorted.p + foff;
     g.nrm          = fixed_normals ? a->pair_nrm_sorted.p + foff : nullptr;
@@ -2695,7 +2652,7 @@ int srrg2_align_pairs(srrg2_aligner_h a, int K, const float* fixed_coords, int f
   if ((rc = upload_moving(a, 0, moving_coords, mcs, moving_normals, mns, moving_offsets, K, mem, /*wait=*/false, nparts, pbegin)))
     return drain(rc);
   // 4. the segmented grid build (count, scan, localise, scatter) in one launch each
-  PAIRS_TRY(hipMemcpyAsync(a->pair_grids.p, a->pair_grids_host, sizeof(GridDev) * (size_t) K, hipMemcpyHostToDevice, a->stream));
+  PAIRS_TRY(hipMemcpyAsync(a->pair_grids.p, a->pair_grids_host.p, sizeof(GridDev) * (size_t) K, hipMemcpyHostToDevice, a->stream));
   PAIRS_TRY(hipMemsetAsync(a->pair_cell_start.p, 0, sizeof(int) * ((size_t) total + 1), a->stream));
   srrg2amd::launch_pairs_grid_build(a->pair_grids.p, a->pair_fprobs.p, K, max_nf, max_cells, (int) total, a->pair_raw.p,
                                     fixed_normals ? a->pair_nrm_raw.p : nullptr, a->pair_cell_start.p, a->pair_cursor.p,
@@ -2815,7 +2772,7 @@ int srrg2_multi_gpu_init(int local_rank, int* device_out) {
   if (local_rank < 0) return fail(SRRG2_E_INVALID, "multi_gpu_init: negative local rank");
   const int dev = local_rank % n;
   HIP_TRY(hipSetDevice(dev));
-  HIP_TRY(hipFree(nullptr));  // (creates the context: a broken device fails here, not in the first kernel)
+  HIP_TRY(srrg2amd::device_free(nullptr));  // (creates the context: a broken device fails here, not in the first kernel)
   if (device_out) *device_out = dev;
   return 0;
 }

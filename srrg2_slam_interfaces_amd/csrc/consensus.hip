@@ -321,25 +321,15 @@ struct srrg2_consensus_s {
   DevBuf<float> pose, best;    // 12 floats per (candidate, slot); 16 per candidate
   DevBuf<int> hyp_id, flags, scan_sums;
   DevBuf<long long> acc;       // zeroed per call: cost (K H words), count (K H ints), nsurv (K), ctr (3 K)
-  char* host_in = nullptr;     // pinned
-  char* host_out = nullptr;
-  size_t host_in_cap = 0, host_out_cap = 0;
+  srrg2amd::PinnedBuf<char> host_in, host_out;  // their pinned mirrors
+  // The ordering is what this destructor is for: the stream retires before any buffer above is freed (the members free
+  // themselves after this body).
+  ~srrg2_consensus_s() {
+    (void) hipSetDevice(device);
+    if (stream) (void) hipStreamSynchronize(stream);
+    if (stream) (void) hipStreamDestroy(stream);
+  }
 };
-
-namespace {
-
-int pinned_reserve(char** p, size_t* cap, size_t n) {
-  if (n <= *cap) return 0;
-  if (*p) (void) hipHostFree(*p);
-  *p   = nullptr;
-  *cap = 0;
-  const size_t want = n + n / 8 + 256;
-  HIP_TRY(hipHostMalloc((void**) p, want, hipHostMallocDefault));
-  *cap = want;
-  return 0;
-}
-
-}  // namespace
 
 extern "C" void srrg2_consensus_default_params(srrg2_consensus_params* p) {
   if (!p) return;
@@ -358,27 +348,15 @@ extern "C" int srrg2_consensus_create(int dim, int device, srrg2_consensus_h* ou
     return fail(SRRG2_E_NO_DEVICE, "consensus_create: no HIP device (this library has no CPU fallback)");
   if (device < 0 || device >= ndev) return fail(SRRG2_E_INVALID, "consensus_create: bad device index");
   HIP_TRY(hipSetDevice(device));
-  srrg2_consensus_s* h = new srrg2_consensus_s();
+  std::unique_ptr<srrg2_consensus_s> h(new srrg2_consensus_s());  // (a failure below deletes it)
   h->dim = dim, h->device = device;
-  const hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete h;
-    return fail(SRRG2_E_HIP, std::string("consensus_create: ") + hipGetErrorString(e));
-  }
-  *out = h;
+  HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  *out = h.release();
   return 0;
 }
 
 extern "C" int srrg2_consensus_destroy(srrg2_consensus_h h) {
-  if (!h) return 0;
-  (void) hipSetDevice(h->device);
-  if (h->stream) (void) hipStreamSynchronize(h->stream);
-  h->in.release(); h->out.release(); h->pf.release(); h->pm.release(); h->pose.release(); h->best.release();
-  h->hyp_id.release(); h->flags.release(); h->scan_sums.release(); h->acc.release();
-  if (h->host_in) (void) hipHostFree(h->host_in);
-  if (h->host_out) (void) hipHostFree(h->host_out);
-  if (h->stream) (void) hipStreamDestroy(h->stream);
-  delete h;
+  delete h;  // (null: nothing to do)
   return 0;
 }
 
@@ -440,14 +418,14 @@ extern "C" int srrg2_consensus_compute(srrg2_consensus_h h, const float* fixed, 
   const size_t KH        = (size_t) K * (size_t) H;
   const size_t acc_words = KH + (KH + 1) / 2 + ((size_t) 4 * K + 1) / 2;
   int rc;
-  if ((rc = pinned_reserve(&h->host_in, &h->host_in_cap, in_bytes)) || (rc = pinned_reserve(&h->host_out, &h->host_out_cap, out_bytes)) ||
+  if ((rc = h->host_in.reserve(in_bytes, in_bytes / 8 + 256)) || (rc = h->host_out.reserve(out_bytes, out_bytes / 8 + 256)) ||
       (rc = h->in.reserve(in_bytes)) || (rc = h->out.reserve(out_bytes)) || (rc = h->pf.reserve((size_t) P + 1)) ||
       (rc = h->pm.reserve((size_t) P + 1)) || (rc = h->pose.reserve(KH * 12)) || (rc = h->best.reserve((size_t) K * 16)) ||
       (rc = h->hyp_id.reserve(KH)) || (rc = h->flags.reserve((size_t) P + 1)) ||
       (rc = h->scan_sums.reserve((size_t) srrg2amd::scan_num_blocks(P) + 2)) || (rc = h->acc.reserve(acc_words)))
     return rc;
   const double tau = (double) p->inlier_distance, msd = (double) p->min_sample_distance;
-  CandMeta* const hc = reinterpret_cast<CandMeta*>(h->host_in + off_cand);
+  CandMeta* const hc = reinterpret_cast<CandMeta*>(h->host_in.p + off_cand);
   for (int k = 0; k < K; ++k) {
     CandMeta& c = hc[k];
     c.corr_begin = corr_offsets[k] - c0, c.n = corr_offsets[k + 1] - corr_offsets[k];
@@ -456,16 +434,16 @@ extern "C" int srrg2_consensus_compute(srrg2_consensus_h h, const float* fixed, 
     c.scale         = dm::pow2(c.cost_exponent);
     c.pad           = 0;
   }
-  if (P > 0) std::memcpy(h->host_in + off_corr, correspondences + c0, sizeof(srrg2_correspondence) * (size_t) P);
+  if (P > 0) std::memcpy(h->host_in.p + off_corr, correspondences + c0, sizeof(srrg2_correspondence) * (size_t) P);
   const char* const moving0 = reinterpret_cast<const char*>(moving) + (size_t) m0 * (size_t) moving_stride_bytes;
   const char *d_fixed = reinterpret_cast<const char*>(fixed), *d_moving = moving0;
   if (mem == SRRG2_MEM_HOST) {
-    if (fixed_bytes) std::memcpy(h->host_in + off_fixed, fixed, fixed_bytes);
-    if (moving_bytes) std::memcpy(h->host_in + off_moving, moving0, moving_bytes);
+    if (fixed_bytes) std::memcpy(h->host_in.p + off_fixed, fixed, fixed_bytes);
+    if (moving_bytes) std::memcpy(h->host_in.p + off_moving, moving0, moving_bytes);
     d_fixed = h->in.p + off_fixed, d_moving = h->in.p + off_moving;
   }
   hipStream_t st = h->stream;
-  HIP_TRY(hipMemcpyAsync(h->in.p, h->host_in, in_bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(h->in.p, h->host_in.p, in_bytes, hipMemcpyHostToDevice, st));
   const CandMeta* const d_cand             = reinterpret_cast<const CandMeta*>(h->in.p + off_cand);
   const srrg2_correspondence* const d_corr = reinterpret_cast<const srrg2_correspondence*>(h->in.p + off_corr);
   long long* const d_cost = h->acc.p;
@@ -503,15 +481,15 @@ extern "C" int srrg2_consensus_compute(srrg2_consensus_h h, const float* fixed, 
   hipLaunchKernelGGL(k_cns_scatter, dim3((unsigned) ((scatter_threads + 255) / 256)), dim3(256), 0, st, P, K, d_cand, h->flags.p, d_corr, d_recs,
                      cap, d_offsets);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->host_out, h->out.p, out_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h->host_out.p, h->out.p, out_bytes, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));  // the call's one host wait: results, offsets and records together
 
-  const long long* const offs = reinterpret_cast<const long long*>(h->host_out + out_off);
+  const long long* const offs = reinterpret_cast<const long long*>(h->host_out.p + out_off);
   const long long total       = offs[K];
   if (total < 0 || total > P) return fail(SRRG2_E_HIP, who + "the compaction scan returned a total out of range");
-  std::memcpy(results, h->host_out + out_res, sizeof(srrg2_consensus_result) * (size_t) K);
+  std::memcpy(results, h->host_out.p + out_res, sizeof(srrg2_consensus_result) * (size_t) K);
   if (inlier_offsets_out) std::memcpy(inlier_offsets_out, offs, sizeof(long long) * ((size_t) K + 1));
   const long long give = std::min(total, cap);
-  if (give > 0) std::memcpy(inliers_out, h->host_out + out_rec, sizeof(srrg2_correspondence) * (size_t) give);
+  if (give > 0) std::memcpy(inliers_out, h->host_out.p + out_rec, sizeof(srrg2_correspondence) * (size_t) give);
   return 0;
 }

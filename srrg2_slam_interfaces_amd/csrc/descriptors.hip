@@ -215,39 +215,16 @@ __global__ void k_scene_stage(int dim, const float4* __restrict__ pts, const uin
   }
 }
 
-// a device buffer that keeps its first `used` elements when it grows (capacity doubles)
+// a device buffer that keeps its first `used` elements when it grows: the capacity doubles, from 1024 on
 template <typename T>
 int grow_keep(DevBuf<T>& buf, size_t need, size_t used, hipStream_t s) {
   if (need <= buf.cap) return 0;
-  size_t cap = std::max<size_t>(buf.cap * 2, std::max<size_t>(need, 1024));
-  T* p       = nullptr;
-  hipError_t e = hipMalloc((void**) &p, cap * sizeof(T));
-  if (e != hipSuccess) return fail(SRRG2_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-  if (used && buf.p) {
-    e = hipMemcpyAsync(p, buf.p, used * sizeof(T), hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-      (void) hipFree(p);
-      return fail(SRRG2_E_HIP, std::string("grow: ") + hipGetErrorString(e));
-    }
-  }
-  buf.release();
-  buf.p   = p;
-  buf.cap = cap;
-  return 0;
+  return buf.grow(std::max<size_t>(buf.cap * 2, std::max<size_t>(need, 1024)), used, s);
 }
 
-// pinned host staging that grows
-int host_reserve(void** p, size_t* cap, size_t bytes) {
-  if (bytes <= *cap) return 0;
-  if (*p) (void) hipHostFree(*p);
-  *p       = nullptr;
-  *cap     = 0;
-  size_t want = std::max<size_t>(bytes + bytes / 2, 4096);
-  hipError_t e = hipHostMalloc(p, want, hipHostMallocDefault);
-  if (e != hipSuccess) return fail(SRRG2_E_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-  *cap = want;
-  return 0;
+// pinned host staging that grows by half, from 4096 bytes on
+int host_reserve(srrg2amd::PinnedBuf<char>& buf, size_t bytes) {
+  return buf.reserve(bytes, std::max<size_t>(bytes + bytes / 2, 4096) - bytes);
 }
 
 // d < t for an integer distance d in 0 .. 256  <=>  d < L
@@ -275,8 +252,7 @@ struct srrg2_descriptor_db {
   DevBuf<MapStat> stats;
   DevBuf<Candidate> cands;
   DevBuf<srrg2_correspondence> corr;
-  void* staging = nullptr;  // pinned
-  size_t staging_cap = 0;
+  srrg2amd::PinnedBuf<char> staging;
   // staging from a scene: flags -> offsets, the scan's block sums, the event that orders this stream behind the scene's
   DevBuf<int> sflags, sscan;
   hipEvent_t ev_scene = nullptr;
@@ -287,6 +263,15 @@ struct srrg2_descriptor_db {
   std::vector<int64_t> cand_count, cand_off{0};
   std::vector<srrg2_correspondence> h_corr;
   double last_ms = 0.0;
+  // The ordering is what this destructor is for: the stream retires before any buffer above is freed (the members free
+  // themselves after this body).
+  ~srrg2_descriptor_db() {
+    (void) hipSetDevice(device);
+    if (stream) (void) hipStreamSynchronize(stream);
+    for (hipEvent_t ev : {ev_scene, ev0, ev1})
+      if (ev) (void) hipEventDestroy(ev);
+    if (stream) (void) hipStreamDestroy(stream);
+  }
 };
 
 namespace {
@@ -302,8 +287,8 @@ int stage(srrg2_descriptor_db* h, const uint8_t* d, const uint8_t* valid, int n,
   for (int i = 0; i < n; ++i) nv += (!valid || valid[i]) ? 1 : 0;
   const size_t off = ((size_t) nv * SRRG2_DESCRIPTOR_BYTES + 15) / 16 * 16;
   int rc;
-  if ((rc = host_reserve(&h->staging, &h->staging_cap, off + (size_t) nv * 4 + 16))) return rc;
-  uint8_t* rows  = (uint8_t*) h->staging;
+  if ((rc = host_reserve(h->staging, off + (size_t) nv * 4 + 16))) return rc;
+  uint8_t* rows  = (uint8_t*) h->staging.p;
   int32_t* idx   = (int32_t*) (rows + off);
   int k          = 0;
   for (int i = 0; i < n; ++i) {
@@ -343,14 +328,14 @@ int scene_count(srrg2_descriptor_db* h, const srrg2amd::SceneFeatureView& v, int
   HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_scene, 0));
   if ((rc = h->sflags.reserve((size_t) v.n + 1))) return rc;
   if ((rc = h->sscan.reserve((size_t) srrg2amd::scan_num_blocks(v.n) + 2))) return rc;
-  if ((rc = host_reserve(&h->staging, &h->staging_cap, 64))) return rc;
+  if ((rc = host_reserve(h->staging, 64))) return rc;
   hipLaunchKernelGGL(k_scene_flag, dim3(scene_blocks(v.n)), dim3(THREADS), 0, h->stream, v.dim, v.pts, v.n, h->sflags.p);
   int* dtotal = h->sscan.p + h->sscan.cap - 1;
   srrg2amd::launch_exclusive_scan(h->sflags.p, v.n, h->sscan.p, dtotal, h->stream);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->staging, dtotal, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->staging.p, dtotal, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  *nv_out = *(const int*) h->staging;
+  *nv_out = *(const int*) h->staging.p;
   return 0;
 }
 
@@ -368,39 +353,20 @@ int srrg2_descriptor_db_create(int device, srrg2_descriptor_db_h* out) {
     return fail(SRRG2_E_NO_DEVICE, "descriptor_db_create: no HIP device (this library has no CPU fallback)");
   if (device < 0 || device >= ndev) return fail(SRRG2_E_INVALID, "descriptor_db_create: bad device index");
   HIP_TRY(hipSetDevice(device));
-  srrg2_descriptor_db* h = new srrg2_descriptor_db();
-  h->device              = device;
-  hipError_t e           = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreate(&h->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&h->ev1);
-  int rc = 0;
-  if (e != hipSuccess) rc = fail(SRRG2_E_HIP, std::string("descriptor_db_create: ") + hipGetErrorString(e));
-  if (!rc) rc = grow_keep(h->starts, 1024, 0, h->stream);
-  if (!rc) {
-    e = hipMemsetAsync(h->starts.p, 0, sizeof(long long), h->stream);
-    if (e != hipSuccess) rc = fail(SRRG2_E_HIP, std::string("descriptor_db_create: ") + hipGetErrorString(e));
-  }
-  if (rc) {
-    srrg2_descriptor_db_destroy(h);
-    return rc;
-  }
-  *out = h;
+  std::unique_ptr<srrg2_descriptor_db> h(new srrg2_descriptor_db());  // (a failure below deletes it)
+  h->device = device;
+  HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  HIP_TRY(hipEventCreate(&h->ev0));
+  HIP_TRY(hipEventCreate(&h->ev1));
+  int rc;
+  if ((rc = grow_keep(h->starts, 1024, 0, h->stream))) return rc;
+  HIP_TRY(hipMemsetAsync(h->starts.p, 0, sizeof(long long), h->stream));
+  *out = h.release();
   return 0;
 }
 
 int srrg2_descriptor_db_destroy(srrg2_descriptor_db_h h) {
-  if (!h) return 0;
-  (void) hipSetDevice(h->device);
-  if (h->stream) (void) hipStreamSynchronize(h->stream);
-  h->desc.release(); h->ref_idx.release(); h->starts.release(); h->best.release(); h->count.release();
-  h->query.release(); h->query_idx.release(); h->stats.release(); h->cands.release(); h->corr.release();
-  h->sflags.release(); h->sscan.release();
-  if (h->staging) (void) hipHostFree(h->staging);
-  if (h->ev_scene) (void) hipEventDestroy(h->ev_scene);
-  if (h->ev0) (void) hipEventDestroy(h->ev0);
-  if (h->ev1) (void) hipEventDestroy(h->ev1);
-  if (h->stream) (void) hipStreamDestroy(h->stream);
-  delete h;
+  delete h;  // (null: nothing to do)
   return 0;
 }
 
@@ -430,9 +396,9 @@ int add_impl(srrg2_descriptor_db* h, const uint8_t* d, const uint8_t* valid, int
     scene_scatter(h, *sv, nv, h->desc.p + 2 * old, h->ref_idx.p + old);
     HIP_TRY(hipGetLastError());
   } else {
-    HIP_TRY(hipMemcpyAsync(h->desc.p + 2 * old, h->staging, (size_t) nv * SRRG2_DESCRIPTOR_BYTES, hipMemcpyHostToDevice,
+    HIP_TRY(hipMemcpyAsync(h->desc.p + 2 * old, h->staging.p, (size_t) nv * SRRG2_DESCRIPTOR_BYTES, hipMemcpyHostToDevice,
                            h->stream));
-    HIP_TRY(hipMemcpyAsync(h->ref_idx.p + old, (uint8_t*) h->staging + off, (size_t) nv * 4, hipMemcpyHostToDevice,
+    HIP_TRY(hipMemcpyAsync(h->ref_idx.p + old, (uint8_t*) h->staging.p + off, (size_t) nv * 4, hipMemcpyHostToDevice,
                            h->stream));
   }
   HIP_TRY(hipMemcpyAsync(h->starts.p + maps + 1, &h->h_starts.back(), sizeof(long long), hipMemcpyHostToDevice,
@@ -506,8 +472,8 @@ int match_impl(srrg2_descriptor_db* h, const uint8_t* d, const uint8_t* valid, i
     scene_scatter(h, *sv, nv, h->query.p, h->query_idx.p);
     HIP_TRY(hipGetLastError());
   } else {
-    HIP_TRY(hipMemcpyAsync(h->query.p, h->staging, (size_t) nv * SRRG2_DESCRIPTOR_BYTES, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->query_idx.p, (uint8_t*) h->staging + off, (size_t) nv * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->query.p, h->staging.p, (size_t) nv * SRRG2_DESCRIPTOR_BYTES, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->query_idx.p, (uint8_t*) h->staging.p + off, (size_t) nv * 4, hipMemcpyHostToDevice, h->stream));
   }
   const long long blocks = (nactive + THREADS * DPT - 1) / (THREADS * DPT);
   hipLaunchKernelGGL(k_desc_match, dim3((unsigned) blocks), dim3(THREADS), 0, h->stream, h->desc.p, lo, skip, nactive,
@@ -537,9 +503,9 @@ int match_impl(srrg2_descriptor_db* h, const uint8_t* d, const uint8_t* valid, i
   if (K > 0 && total > 0) {
     if ((rc = grow_keep(h->cands, (size_t) K, 0, h->stream))) return rc;
     if ((rc = grow_keep(h->corr, (size_t) total, 0, h->stream))) return rc;
-    if ((rc = host_reserve(&h->staging, &h->staging_cap, (size_t) K * sizeof(Candidate)))) return rc;
-    std::memcpy(h->staging, cands.data(), (size_t) K * sizeof(Candidate));
-    HIP_TRY(hipMemcpyAsync(h->cands.p, h->staging, (size_t) K * sizeof(Candidate), hipMemcpyHostToDevice, h->stream));
+    if ((rc = host_reserve(h->staging, (size_t) K * sizeof(Candidate)))) return rc;
+    std::memcpy(h->staging.p, cands.data(), (size_t) K * sizeof(Candidate));
+    HIP_TRY(hipMemcpyAsync(h->cands.p, h->staging.p, (size_t) K * sizeof(Candidate), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(k_desc_emit, dim3(K), dim3(THREADS), 0, h->stream, h->cands.p, h->best.p, h->ref_idx.p,
                        h->query_idx.p, L, h->corr.p);
     HIP_TRY(hipGetLastError());

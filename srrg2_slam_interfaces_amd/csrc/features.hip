@@ -516,7 +516,7 @@ extern "C" int srrg2_adapt_image_features(srrg2_scene_h dst, const void* intensi
   const srrg2amd::FeatWork work{s->feat_score.p, s->feat_box.p, s->feat_max.p, s->feat_tie.p, s->feat_ctr.p, s->flags.p, s->scan_sums.p};
   int* const ctr = s->feat_ctr.p;
   if ((rc = srrg2amd::feat_queue_select(I, D, p->fast_threshold, p->max_features, work, st))) return rc;
-  HIP_TRY(hipMemcpyAsync(s->scalars + 8, ctr, 4 * sizeof(int), hipMemcpyDeviceToHost, st));  // (rides on the scan's wait)
+  HIP_TRY(hipMemcpyAsync(s->scalars.p + 8, ctr, 4 * sizeof(int), hipMemcpyDeviceToHost, st));  // (rides on the scan's wait)
   int total = 0;
   if ((rc = srrg2amd::scene_scan_flags(s, n, &total))) return rc;
   if (total < 0 || total > n) return fail(SRRG2_E_HIP, who + "the compaction scan returned a total out of range");
@@ -535,9 +535,9 @@ extern "C" int srrg2_adapt_image_features(srrg2_scene_h dst, const void* intensi
     HIP_TRY(hipStreamSynchronize(st));  // dst, and the caller's images, are done with
   }
   if (out) {
-    out->num_candidates = s->scalars[8 + C_CANDIDATES];
-    out->num_maxima     = s->scalars[8 + C_MAXIMA];
-    out->num_selected   = s->scalars[8 + C_SELECTED];
+    out->num_candidates = s->scalars.p[8 + C_CANDIDATES];
+    out->num_maxima     = s->scalars.p[8 + C_MAXIMA];
+    out->num_selected   = s->scalars.p[8 + C_SELECTED];
     out->num_with_depth = total;
     out->scene_size     = total;
   }

@@ -312,13 +312,6 @@ int ceil_log2(int n) {
   return l;
 }
 
-template <typename T>
-void swap_buf(srrg2amd::DevBuf<T>& a, srrg2amd::DevBuf<T>& b) {
-  std::swap(a.p, b.p);
-  std::swap(a.cap, b.cap);
-  std::swap(a.borrowed, b.borrowed);
-}
-
 }  // namespace
 
 // the two exponents of the fixed-point moments: radius < 2^E, n <= 2^L;
@@ -434,7 +427,7 @@ extern "C" int srrg2_scene_estimate_normals(srrg2_scene_h s, const srrg2_normals
     hipLaunchKernelGGL(k_nrm_neigh<2>, ngrid, dim3(64), 0, st, spec, skeys, s->nrm_sorted.p, n, A, computed, s->nrm_curv.p, ctr);
   HIP_TRY(hipGetLastError());
   if (queued) {  // (an extent beyond the key range cannot be reported from here: the kernel has written NaN normals instead)
-    swap_buf(s->nrm, s->alt_nrm);
+    std::swap(s->nrm, s->alt_nrm);
     s->has_normals = true;
     s->pending     = true;
     return 0;
@@ -452,32 +445,32 @@ extern "C" int srrg2_scene_estimate_normals(srrg2_scene_h s, const srrg2_normals
       hipLaunchKernelGGL(k_nrm_scatter<false>, grid, block, 0, st, spec, s->pts.p, computed, n, s->flags.p, s->alt_pts.p,
                          s->alt_nrm.p, s->alt_gidx.p, f);
   }
-  HIP_TRY(hipMemcpyAsync(s->scalars, ctr, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(s->scalars.p, ctr, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
   if (curvature_out) HIP_TRY(hipMemcpyAsync(curvature_out, s->nrm_curv.p, sizeof(float) * (size_t) n, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
-  if (s->scalars[C_UNSUP])
+  if (s->scalars.p[C_UNSUP])
     return fail(SRRG2_E_UNSUPPORTED,
                 "scene_estimate_normals: the cloud spans more cells of one radius than the 63-bit cell key holds (2^30 per axis, "
                 "63 bits over the axes)");
-  swap_buf(s->nrm, s->alt_nrm);
+  std::swap(s->nrm, s->alt_nrm);
   s->has_normals = true;
   if (drop) {
-    const int total = s->scalars[C_TOTAL];
+    const int total = s->scalars.p[C_TOTAL];
     if (total < 0 || total > n) return fail(SRRG2_E_HIP, "scene_estimate_normals: the compaction scan returned a total out of range");
-    swap_buf(s->pts, s->alt_pts);
-    if (s->has_desc) swap_buf(s->desc, s->alt_desc);
-    if (s->has_inten) swap_buf(s->inten, s->alt_inten);
-    swap_buf(s->gidx, s->alt_gidx);
+    std::swap(s->pts, s->alt_pts);
+    if (s->has_desc) std::swap(s->desc, s->alt_desc);
+    if (s->has_inten) std::swap(s->inten, s->alt_inten);
+    std::swap(s->gidx, s->alt_gidx);
     s->n = s->ng = total;
   }
   if (out) {
     out->num_points      = n;
-    out->num_finite      = s->scalars[C_FINITE];
-    out->num_with_normal = s->scalars[C_NORMAL];
-    out->num_too_few     = s->scalars[C_FEW];
-    out->num_degenerate  = s->scalars[C_DEGEN];
-    out->num_too_curved  = s->scalars[C_CURVED];
+    out->num_finite      = s->scalars.p[C_FINITE];
+    out->num_with_normal = s->scalars.p[C_NORMAL];
+    out->num_too_few     = s->scalars.p[C_FEW];
+    out->num_degenerate  = s->scalars.p[C_DEGEN];
+    out->num_too_curved  = s->scalars.p[C_CURVED];
     out->scene_size      = s->n;
   }
   return 0;

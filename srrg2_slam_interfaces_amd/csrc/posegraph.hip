@@ -1848,14 +1848,6 @@ struct MgLevelBufs {
   DevBuf<unsigned long long> qp_list, gp_list;  // (int2 {x, y} = the low and the high word)
   DevBuf<int> qp_start, gp_start, qdiag;
   long long nqp = 0, ngp = 0;                   // products of Q = H Ps / of the coarse edges
-  void release() {
-    qp_list.release(); gp_list.release(); qp_start.release(); gp_start.release(); qdiag.release();
-    eij.release(); inc_start.release(); inc_adj.release(); agg.release(); rep0.release(); prow_start.release();
-    pcol.release(); prow_of.release(); pcsc_start.release(); pcsc_ent.release(); qrow_start.release(); qcol.release();
-    qrow_of.release(); Hd.release(); Ho.release(); P.release(); Ps.release(); Q.release(); Dinv.release(); x.release();
-    r.release(); res.release(); Hdf.release(); Hof.release(); Dinvf.release(); Psf.release(); Qf.release();
-    qcsc_start.release(); qcsc_ent.release(); pcsc2.release(); qcsc2.release();
-  }
 };
 
 struct srrg2_posegraph_s {
@@ -1872,7 +1864,7 @@ struct srrg2_posegraph_s {
   // multigrid hierarchy
   std::vector<MgLevelBufs*> levels;      // the current hierarchy: the first levels of the pool
   std::set<int> pg_force_tentative;      // levels whose smoothed interpolation exceeded the fill limit (this build)
-  std::vector<MgLevelBufs*> level_pool;  // level objects with their device buffers, kept across rebuilds
+  std::vector<std::unique_ptr<MgLevelBufs>> level_pool;  // level objects with their device buffers, kept across rebuilds
   DevBuf<MgLevel> levels_dev;
   std::vector<MgLevel> level_views;      // host copies of the records in levels_dev (kernel arguments: MgPair)
   DevBuf<double> coarse_A, coarse_inv;
@@ -1923,6 +1915,13 @@ struct srrg2_posegraph_s {
   bool robust_dirty = false;
   DevBuf<PgRobust> robust;
   DevBuf<float> eval_out;    // k_pg_factor_eval: E chi, then E weights
+  // The ordering is what this destructor is for: the stream retires before any buffer above, the levels' included, is freed
+  // (the members free themselves after this body).
+  ~srrg2_posegraph_s() {
+    (void) hipSetDevice(device);
+    if (stream) (void) hipStreamSynchronize(stream);
+    if (stream) (void) hipStreamDestroy(stream);
+  }
 };
 
 namespace {
@@ -2614,8 +2613,8 @@ int build_hierarchy(srrg2_posegraph_s* g) {
   const int match_passes = g->sw.match_passes;
   for (int level = 0; level < MG_MAX_LEVELS; ++level) {
     const int ne = (int) (eij.size() / 2);
-    if ((size_t) level >= g->level_pool.size()) g->level_pool.push_back(new MgLevelBufs());
-    MgLevelBufs* L = g->level_pool[(size_t) level];
+    if ((size_t) level >= g->level_pool.size()) g->level_pool.emplace_back(new MgLevelBufs());
+    MgLevelBufs* L = g->level_pool[(size_t) level].get();
     g->levels.push_back(L);
     L->nc = L->nce = L->np = L->nq = 0;
     L->row_parts = L->col_parts = L->prow_parts = 1;
@@ -3407,17 +3406,11 @@ void srrg2_posegraph_default_params(srrg2_posegraph_params* p) {
 
 }  // extern "C" (reopened below)
 namespace {
-// grow a device array keeping its first `keep` elements (DevBuf::reserve drops the content)
+// grow a device array by half keeping its first `keep` elements (DevBuf::reserve drops the content); a blocking copy
 template <typename T>
 int grow_keep(DevBuf<T>& b, size_t keep, size_t want) {
   if (want <= b.cap) return 0;
-  DevBuf<T> nb;
-  int rc;
-  if ((rc = nb.reserve(want + want / 2 + 64))) return rc;
-  if (keep > 0) HIP_TRY(hipMemcpy(nb.p, b.p, sizeof(T) * keep, hipMemcpyDeviceToDevice));
-  b.release();
-  b = nb;
-  return 0;
+  return b.grow(want + want / 2 + 64, keep, nullptr);
 }
 
 // incidence lists in (vertex, edge id) order: fixed summation order of the diagonal blocks
@@ -3503,7 +3496,8 @@ int srrg2_posegraph_create(int variable_kind, int device, srrg2_posegraph_h* out
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
     return fail(SRRG2_E_NO_DEVICE, "posegraph_create: no HIP device visible (this library has no CPU fallback)");
   if (device < 0 || device >= n) return fail(SRRG2_E_INVALID, "posegraph_create: bad device ordinal");
-  srrg2_posegraph_s* g = new srrg2_posegraph_s();
+  std::unique_ptr<srrg2_posegraph_s> owner(new srrg2_posegraph_s());  // (a failure below deletes it)
+  srrg2_posegraph_s* const g = owner.get();
   g->kind   = variable_kind;
   g->D      = variable_kind == SRRG2_SE2_RIGHT ? 3 : 6;
   g->T      = variable_kind == SRRG2_SE2_RIGHT ? 9 : 12;
@@ -3526,38 +3520,14 @@ int srrg2_posegraph_create(int variable_kind, int device, srrg2_posegraph_h* out
     if (t.match_passes < 1) t.match_passes = 1;
     apply_tuning(g, t);
   }
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete g;
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess)
     return fail(SRRG2_E_HIP, "posegraph_create: cannot create stream");
-  }
-  *out = g;
+  *out = owner.release();
   return 0;
 }
 
 int srrg2_posegraph_destroy(srrg2_posegraph_h g) {
-  if (!g) return 0;
-  (void) hipSetDevice(g->device);
-  if (g->stream) (void) hipStreamSynchronize(g->stream);
-  g->poses.release(); g->Z.release(); g->fixed.release(); g->enabled.release(); g->ij.release(); g->omega.release();
-  g->Hd.release(); g->Ho.release(); g->b.release(); g->Minv.release(); g->x.release(); g->r.release();
-  g->p.release(); g->Ap.release(); g->contrib.release(); g->part_rz.release(); g->part_rz_new.release();
-  g->part_pAp.release(); g->part_rr.release(); g->part_bb.release(); g->part_chi.release(); g->part_n.release();
-  g->inc_start.release(); g->inc_edge.release(); g->sc.release(); g->act_edge.release(); g->levels_dev.release();
-  g->coarse_A.release(); g->coarse_inv.release();
-  g->bottom_acc.release(); g->bottom_G.release(); g->bottom_W.release(); g->bottom_B.release();
-  g->tail_parent.release(); g->tail_ecode.release(); g->tail_K.release(); g->tail_c.release();
-  g->st_keys_a.release(); g->st_keys_b.release(); g->st_cnt.release(); g->st_off.release(); g->st_slot.release();
-  g->st_ia.release(); g->st_ib.release(); g->st_counts.release(); g->st_total.release(); g->st_temp.release();
-  g->st_vals.release(); g->st_rle.release();
-  g->robust.release(); g->eval_out.release();
-  for (MgLevelBufs* L : g->level_pool) {
-    L->release();
-    delete L;
-  }
-  g->level_pool.clear();
-  g->levels.clear();
-  if (g->stream) (void) hipStreamDestroy(g->stream);
-  delete g;
+  delete g;  // (null: nothing to do)
   return 0;
 }
 

@@ -549,19 +549,7 @@ bool moves_features(const Feat& f) { return f.dst_desc || f.dst_inten; }
 // a feature array follows the capacity of the point arrays (per_point elements each), keeping the first `keep` points' entries
 template <typename T>
 int grow_feature(srrg2_scene* s, DevBuf<T>& buf, size_t per_point, int keep) {
-  const size_t want = s->pts.cap * per_point;
-  if (want <= buf.cap) return 0;
-  DevBuf<T> nb;
-  int rc;
-  if ((rc = nb.reserve(want))) return rc;
-  const size_t kept = std::min((size_t) (keep > 0 ? keep : 0) * per_point, buf.cap);
-  if (kept > 0) {
-    HIP_TRY(hipMemcpyAsync(nb.p, buf.p, sizeof(T) * kept, hipMemcpyDeviceToDevice, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-  }
-  buf.release();
-  buf = nb;
-  return 0;
+  return buf.grow(s->pts.cap * per_point, std::min((size_t) (keep > 0 ? keep : 0) * per_point, buf.cap), s->stream);
 }
 
 int features_reserve(srrg2_scene* s, int keep) {
@@ -588,20 +576,9 @@ int bind_features(srrg2_scene* scene, const srrg2_scene* meas, const char* who) 
 // grow the point arrays (and the feature arrays that are present) to hold n points, keeping the first `keep`
 int scene_reserve(srrg2_scene* s, int n, int keep) {
   if ((size_t) n <= s->pts.cap && (size_t) n <= s->nrm.cap) return features_reserve(s, keep);
-  DevBuf<float4> np, nn;
   int rc;
-  const size_t want = (size_t) n + (size_t) n / 2 + 1024;
-  if ((rc = np.reserve(want))) return rc;
-  if ((rc = nn.reserve(want))) return rc;
-  if (keep > 0) {
-    HIP_TRY(hipMemcpyAsync(np.p, s->pts.p, sizeof(float4) * (size_t) keep, hipMemcpyDeviceToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(nn.p, s->nrm.p, sizeof(float4) * (size_t) keep, hipMemcpyDeviceToDevice, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-  }
-  s->pts.release();
-  s->nrm.release();
-  s->pts = np;
-  s->nrm = nn;
+  const size_t want = (size_t) n + (size_t) n / 2 + 1024, kept = (size_t) (keep > 0 ? keep : 0);
+  if ((rc = s->pts.grow(want, kept, s->stream)) || (rc = s->nrm.grow(want, kept, s->stream))) return rc;
   return features_reserve(s, keep);
 }
 
@@ -610,14 +587,14 @@ int scan_flags(srrg2_scene* s, int n, int* total) {
   int rc;
   if ((rc = s->scan_sums.reserve((size_t) srrg2amd::scan_num_blocks(n) + 2))) return rc;
   srrg2amd::launch_exclusive_scan(s->flags.p, n, s->scan_sums.p, s->scan_sums.p + s->scan_sums.cap - 1, s->stream);
-  HIP_TRY(hipMemcpyAsync(&s->scalars[0], s->scan_sums.p + s->scan_sums.cap - 1, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(&s->scalars.p[0], s->scan_sums.p + s->scan_sums.cap - 1, sizeof(int), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
-  *total = s->scalars[0];
+  *total = s->scalars.p[0];
   return 0;
 }
 
 int read_scalars(srrg2_scene* s, const int* from = nullptr) {
-  HIP_TRY(hipMemcpyAsync(s->scalars, from ? from : s->dscalars.p, 16 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->scalars.p, from ? from : s->dscalars.p, 16 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return 0;
 }
@@ -660,10 +637,10 @@ int compact_scatter(srrg2_scene* full, srrg2_scene* clipped, int n, const std::f
   const int room = (int) std::min({clipped->pts.cap, clipped->nrm.cap, clipped->gidx.cap});
   if (room > 0) scatter(room);
   if (before_wait && (rc = before_wait())) return rc;
-  HIP_TRY(hipMemcpyAsync(full->scalars, full->dscalars.p, (CLIP_TOTAL + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(full->scalars.p, full->dscalars.p, (CLIP_TOTAL + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
-  const int total = full->scalars[CLIP_TOTAL];
+  const int total = full->scalars.p[CLIP_TOTAL];
   if (total > room) {
     if ((rc = scene_reserve(clipped, total, 0)) || (rc = clipped->gidx.reserve((size_t) total))) return rc;
     scatter(total);
@@ -705,9 +682,9 @@ int clip_view(srrg2_scene* full, srrg2_scene* clipped, const Xf& L, DevBuf<unsig
   if ((rc = passes(dim3(blocks_for(n)), counters))) return rc;
   if ((rc = compact_into(full, clipped, L, n))) return rc;
   if (out) {
-    out->num_valid   = full->scalars[CLIP_VALID];
-    out->num_in_view = full->scalars[CLIP_IN_VIEW];
-    out->num_kept    = full->scalars[CLIP_TOTAL];
+    out->num_valid   = full->scalars.p[CLIP_VALID];
+    out->num_in_view = full->scalars.p[CLIP_IN_VIEW];
+    out->num_kept    = full->scalars.p[CLIP_TOTAL];
   }
   return 0;
 }
@@ -736,12 +713,12 @@ int finish_merge(srrg2_scene* scene, srrg2_scene* meas, const Xf& M, bool have_c
   const int n_meas = meas->n;
   int num_merged   = 0;
   if (counted) {
-    num_merged = scene->scalars[1];
+    num_merged = scene->scalars.p[1];
   } else if (have_corr && n_meas > 0) {
     hipLaunchKernelGGL(k_count_merged, dim3(std::min(blocks_for(n_meas), 64)), dim3(256), 0, scene->stream, scene->merged.p, n_meas,
                        scene->dscalars.p);
     if ((rc = read_scalars(scene))) return rc;
-    num_merged = scene->scalars[1];
+    num_merged = scene->scalars.p[1];
   }
   out->num_merged = num_merged;
   if (!have_corr || (unsigned) num_merged < (unsigned) p->target_number_of_merges) {  // :92
@@ -788,41 +765,22 @@ int srrg2_scene_create(int dim, int device, srrg2_scene_h* out) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(SRRG2_E_NO_DEVICE, "scene_create: no HIP device (this library has no CPU fallback)");
   if (device < 0 || device >= ndev) return fail(SRRG2_E_INVALID, "scene_create: bad device index");
-  srrg2_scene* s = new srrg2_scene();
-  s->dim         = dim;
-  s->device      = device;
+  std::unique_ptr<srrg2_scene> s(new srrg2_scene());  // (a failure below deletes it: stream and buffers go with it)
+  s->dim    = dim;
+  s->device = device;
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  HIP_TRY(hipHostMalloc((void**) &s->scalars, 16 * sizeof(int), hipHostMallocDefault));
-  std::memset(s->scalars, 0, 16 * sizeof(int));
   int rc;
+  if ((rc = s->scalars.reserve(16))) return rc;
+  std::memset(s->scalars.p, 0, 16 * sizeof(int));
   if ((rc = s->dscalars.reserve(16))) return rc;
   HIP_TRY(hipMemset(s->dscalars.p, 0, 16 * sizeof(int)));
-  *out = s;
+  *out = s.release();
   return 0;
 }
 
 int srrg2_scene_destroy(srrg2_scene_h s) {
-  if (!s) return 0;
-  (void) hipSetDevice(s->device);
-  if (s->stream) (void) hipStreamSynchronize(s->stream);
-  s->pts.release(); s->nrm.release(); s->desc.release(); s->inten.release(); s->gidx.release(); s->flags.release(); s->scan_sums.release();
-  s->counts.release(); s->dup_list.release(); s->dup_keys.release(); s->sort_tmp.release(); s->merged.release(); s->corr.release(); s->staging.release(); s->zmin.release(); s->rmin.release(); s->dscalars.release();
-  s->alt_pts.release(); s->alt_nrm.release(); s->nrm_sorted.release(); s->nrm_tmp.release(); s->alt_desc.release(); s->alt_inten.release();
-  s->nrm_curv.release(); s->alt_gidx.release(); s->nrm_idx.release(); s->nrm_ctr.release(); s->nrm_keys.release();
-  s->vox_acc.release(); s->vox_rep.release(); s->vox_rank.release(); s->vox_cnt.release(); s->vox_counts.release(); s->vox_pts.release(); s->vox_nrm.release();
-  s->feat_score.release(); s->feat_max.release(); s->feat_box.release(); s->feat_tie.release(); s->feat_ctr.release(); s->feat_pattern.release(); s->feat_kp.release();
-  s->st_score.release(); s->st_max.release(); s->st_box.release(); s->st_tie.release(); s->st_ctr.release(); s->st_flags.release(); s->st_sums.release();
-  s->st_counts.release(); s->st_match.release(); s->st_match_out.release(); s->st_z.release();
-  for (int i = 0; i < 2; ++i) {
-    s->st_pixel[i].release(); s->st_rows[i].release(); s->st_desc[i].release(); s->st_kp[i].release(); s->st_best[i].release();
-  }
-  s->trk_pix.release(); s->trk_rows.release(); s->trk_second.release(); s->trk_best.release(); s->trk_best_fixed.release();
-  s->trk_rec.release(); s->trk_out.release();
-  if (s->trk_host) (void) hipHostFree(s->trk_host);
-  if (s->scalars) (void) hipHostFree(s->scalars);
-  if (s->stream) (void) hipStreamDestroy(s->stream);
-  delete s;
+  delete s;  // (null: nothing to do)
   return 0;
 }
 
@@ -1204,8 +1162,8 @@ int srrg2_scene_merge(srrg2_scene_h scene, srrg2_scene_h meas, const float* meas
       hipLaunchKernelGGL(k_merge_count, dim3(blocks_for(ncorr)), dim3(256), 0, st, scene->corr.p, ncorr, n_scene, n_meas,
                          scene->counts.p, scene->dscalars.p);
       if ((rc = read_scalars(scene))) return rc;
-      if (scene->scalars[2]) return fail(SRRG2_E_INVALID, "scene_merge: correspondence index out of range");
-      const bool dups = scene->scalars[3] != 0;
+      if (scene->scalars.p[2]) return fail(SRRG2_E_INVALID, "scene_merge: correspondence index out of range");
+      const bool dups = scene->scalars.p[3] != 0;
       if (dups && (rc = scene->flags.reserve((size_t) ncorr + 1))) return rc;
       float4* snrm       = scene->nrm.p;  // (always allocated; written like the oracle's)
       const float4* mnrm = meas->has_normals ? meas->nrm.p : nullptr;
@@ -1274,11 +1232,11 @@ int srrg2_scene_merge_from_aligner(srrg2_scene_h scene, srrg2_scene_h meas, cons
                 v.corr_stat, v.prune ? 1 : 0, v.nm, clipped->gidx.p, n_scene, n_meas, scene->pts.p, scene->nrm.p, meas->pts.p,
                 meas->has_normals ? meas->nrm.p : nullptr, flags_, counters, f);
     if ((rc = read_scalars(scene, counters))) return rc;
-    if (scene->scalars[2]) return fail(SRRG2_E_STATE, "scene_merge_from_aligner: index out of range");
+    if (scene->scalars.p[2]) return fail(SRRG2_E_STATE, "scene_merge_from_aligner: index out of range");
   }
   else if ((rc = read_scalars(scene, counters)))
     return rc;
-  out->num_correspondences = scene->scalars[4];
+  out->num_correspondences = scene->scalars.p[4];
   return finish_merge(scene, meas, M, true, p, out, /*counted=*/true, flags_);
 }
 

@@ -81,12 +81,18 @@ struct srrg2_scene {
   srrg2amd::DevBuf<unsigned long long> trk_best, trk_best_fixed;
   srrg2amd::DevBuf<srrg2_correspondence> trk_rec;
   srrg2amd::DevBuf<int> trk_out;
-  int* trk_host       = nullptr;
-  size_t trk_host_cap = 0;  // words
-  int* scalars = nullptr;  // pinned host mirror of dscalars
+  srrg2amd::PinnedBuf<int> trk_host;  // words
+  srrg2amd::PinnedBuf<int> scalars;   // pinned host mirror of dscalars
   // device: [1] num_merged, [2] error flag, [3] duplicates seen, [4] ncorr (merge); [0] Valid, [1] in view, [2] scan total (clip);
   // [8] in range, [9] Valid (adapt)
   srrg2amd::DevBuf<int> dscalars;
+  // The ordering is what this destructor is for: the stream retires before any buffer above is freed (the members free
+  // themselves after this body).  A new scratch buffer is one member line and nothing else.
+  ~srrg2_scene() {
+    (void) hipSetDevice(device);
+    if (stream) (void) hipStreamSynchronize(stream);
+    if (stream) (void) hipStreamDestroy(stream);
+  }
 };
 
 namespace srrg2amd {

@@ -219,10 +219,10 @@ extern "C" int srrg2_adapt_stereo_features(srrg2_scene_h dst, const void* left, 
     if ((rc = srrg2amd::feat_queue_select(I[e], D, fp->fast_threshold, fp->max_features, work[e], st))) return rc;
     srrg2amd::launch_exclusive_scan(work[e].flags, n, work[e].scan_sums, work[e].ctr + srrg2amd::FEAT_C_KEPT, st);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(s->scalars + 8 * e, work[e].ctr, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(s->scalars.p + 8 * e, work[e].ctr, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(hipStreamSynchronize(st));
-  const int count[2] = {s->scalars[srrg2amd::FEAT_C_KEPT], s->scalars[8 + srrg2amd::FEAT_C_KEPT]};
+  const int count[2] = {s->scalars.p[srrg2amd::FEAT_C_KEPT], s->scalars.p[8 + srrg2amd::FEAT_C_KEPT]};
   if (count[0] < 0 || count[0] > n || count[1] < 0 || count[1] > n)
     return fail(SRRG2_E_HIP, who + "the compaction scan returned a total out of range");
   if (out) out->num_left = count[0], out->num_right = count[1];
@@ -257,7 +257,7 @@ extern "C" int srrg2_adapt_stereo_features(srrg2_scene_h dst, const void* left, 
   const int count_blocks = (nl + 255) / 256;
   hipLaunchKernelGGL(k_stereo_count, dim3(count_blocks < 64 ? count_blocks : 64), dim3(256), 0, st, s->st_match.p, nl, s->st_counts.p);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(s->scalars + 8, s->st_counts.p, S_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));  // (rides on the scan's wait)
+  HIP_TRY(hipMemcpyAsync(s->scalars.p + 8, s->st_counts.p, S_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));  // (rides on the scan's wait)
   int total = 0;
   if ((rc = srrg2amd::scene_scan_flags(s, nl, &total))) return rc;
   if (total < 0 || total > nl) return fail(SRRG2_E_HIP, who + "the compaction scan returned a total out of range");
@@ -281,8 +281,8 @@ extern "C" int srrg2_adapt_stereo_features(srrg2_scene_h dst, const void* left, 
     HIP_TRY(hipStreamSynchronize(st));  // dst, the records and the caller's images are done with
   }
   if (out) {
-    out->num_matched  = s->scalars[8 + S_MATCHED];
-    out->num_mutual   = s->scalars[8 + S_MUTUAL];
+    out->num_matched  = s->scalars.p[8 + S_MATCHED];
+    out->num_mutual   = s->scalars.p[8 + S_MUTUAL];
     out->num_in_range = total;
     out->scene_size   = total;
   }

@@ -166,14 +166,7 @@ extern "C" int srrg2_scene_track_features(srrg2_scene_h moving, srrg2_scene_h fi
       (rc = s->trk_best_fixed.reserve((size_t) nf + 1)) || (rc = s->trk_out.reserve(words)) ||
       (rc = s->flags.reserve((size_t) nm + 1)) || (rc = s->scan_sums.reserve((size_t) srrg2amd::scan_num_blocks(nm) + 2)))
     return rc;
-  if (s->trk_host_cap < words) {
-    if (s->trk_host) (void) hipHostFree(s->trk_host);
-    s->trk_host     = nullptr;
-    s->trk_host_cap = 0;
-    const size_t want = words + words / 8 + 64;
-    HIP_TRY(hipHostMalloc((void**) &s->trk_host, want * sizeof(int), hipHostMallocDefault));
-    s->trk_host_cap = want;
-  }
+  if ((rc = s->trk_host.reserve(words, words / 8 + 64))) return rc;
   TrackCam C;
   std::memcpy(C.m, moving_in_sensor, sizeof(C.m));
   C.K0 = fx, C.K2 = p->camera_matrix[2], C.K4 = fy, C.K5 = p->camera_matrix[5];
@@ -195,10 +188,10 @@ extern "C" int srrg2_scene_track_features(srrg2_scene_h moving, srrg2_scene_h fi
   srrg2amd::launch_exclusive_scan(s->flags.p, nm, s->scan_sums.p, block + T_TOTAL, st);
   if (cap > 0) hipLaunchKernelGGL(k_track_scatter, dim3(blocks_of(nm)), dim3(256), 0, st, nm, s->flags.p, s->trk_rec.p, d_recs, cap);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(s->trk_host, block, words * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(s->trk_host.p, block, words * sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));  // the call's one host wait: counters, error word, total and records together
 
-  const int* const h = s->trk_host;
+  const int* const h = s->trk_host.p;
   if (h[T_ERROR])
     return fail(SRRG2_E_INVALID, who + "the fixed scene's global indices must ascend strictly inside [0, rows*cols)");
   const int total = h[T_TOTAL];

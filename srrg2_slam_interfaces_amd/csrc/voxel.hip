@@ -375,12 +375,12 @@ extern "C" int srrg2_scene_voxelize(srrg2_scene_h src, const srrg2_voxel_params*
                          dst->nrm.p, dst->gidx.p, s->vox_counts.p, cap, g);
   };
   const auto before_wait = [&]() -> int {
-    HIP_TRY(hipMemcpyAsync(s->scalars + 8, ctr, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(s->scalars.p + 8, ctr, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
     if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, s->vox_counts.p, sizeof(int) * (size_t) n, hipMemcpyDeviceToHost, st));
     return 0;
   };
   rc = srrg2amd::scene_compact_into(s, dst, n, scatter, before_wait);
-  const int* const got = s->scalars + 8;
+  const int* const got = s->scalars.p + 8;
   if (rc || got[V_UNSUP]) {
     dst->n = dst_n, dst->ng = dst_ng;
     dst->has_normals = dst_normals, dst->has_desc = dst_desc, dst->has_inten = dst_inten;
