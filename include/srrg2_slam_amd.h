@@ -1071,6 +1071,68 @@ int srrg2_adapt_image_features(srrg2_scene_h dst /* dim 3 */, const void* intens
 /* the 256 point pairs (ax, ay, bx, by) of orientation bin 0 .. 31, rotated: 1024 values.  Needs no device. */
 int srrg2_feature_pattern(int angle_bin, int8_t* pairs_out);
 
+/* Image features over a scale pyramid: srrg2_adapt_image_features on every level of an integer-resampled pyramid of the image,
+ * into ONE ordinary feature scene -- a landmark seen from another distance finds its descriptor on another level.  No reference
+ * counterpart; DESIGN.md section 4 "Image features: scale pyramid" is the contract, all image arithmetic is integer,
+ * tests/pyramid_restatement.py restates it and the library gives the same bits.
+ *   levels    level 0 is the caller's image; rows_l = rows_{l-1} * den / num, cols_l = cols_{l-1} * den / num (floor), each level
+ *             resampled from the level before it.  The first level with a side <= 32 (no admissible pixel) ends the pyramid: it
+ *             and all later levels are not built.
+ *   resample  bilinear with 8 fractional bits at pixel centres.  Destination column c: X = ((2c+1) * num * 256) / (2 * den) - 128
+ *             (floor; never negative), x0 = min(X >> 8, cols_{l-1} - 1), x1 = min((X >> 8) + 1, cols_{l-1} - 1), fx = X & 255;
+ *             rows likewise.  Value: (I00 (256-fx)(256-fy) + I01 fx (256-fy) + I10 (256-fx) fy + I11 fx fy + 32768) >> 16.  A
+ *             constant image stays constant; at 2/1 the value is (a + b + c + d + 2) >> 2 of the 2x2 block.  No blur.
+ *   per level score, maxima, angle and bits are exactly those of srrg2_adapt_image_features on the level's image (same
+ *             thresholds, margin and pattern).
+ *   cap       max_features > 0: with A_l = rows_l * cols_l over the built levels, level l keeps at most q_l = max_features * A_l
+ *             / sum A (floor, 64 bits), level 0 also the remainder max_features - sum q; inside a level the cap of
+ *             srrg2_adapt_image_features.  A quota of 0 keeps nothing on that level.  Unused quota is not handed on.
+ *             max_features == 0: no cap on any level.
+ *   position  of (r, c) on level l: u_q8 = ((2c+1) * num^l * 128) / den^l - 128 (floor, 64 bits; 256 c at level 0), v_q8 from r;
+ *             the nearest level-0 pixel is c0 = min((u_q8 + 128) >> 8, cols_0 - 1), r0 likewise.
+ *   point     the depth gate reads depth pixel (r0, c0) with the rule of srrg2_adapt_image_features; the point is
+ *             (((u - cx) * (1/fx)) * z, ((v - cy) * (1/fy)) * z, z) with u = (float) u_q8 * (1/256), that call's expression
+ *             order, so at level 0 it is that call's point bit for bit.  Without a depth image z = 1.  The cap comes before the depth gate.
+ *   scene     dst (dim 3) holds the kept keypoints level-major, in raster order within a level: no normals, both features (the
+ *             intensity is the LEVEL image's pixel value as float).  srrg2_scene_global_indices(dst) = `pixel`, the nearest
+ *             level-0 pixel: NOT ascending across levels, and the same pixel may appear once per level -- keypoints of different
+ *             levels on one corner are all kept (as ORB does), there is no cross-level suppression.  The descriptor database, the
+ *             consensus pose, the clippers and the merger take the scene as it is; srrg2_scene_track_features takes it as `moving`
+ *             and, as long as dst is as this call left it, as `fixed` (it searches the levels one by one).
+ *   refused   (dst unchanged) everything srrg2_adapt_image_features refuses, with its codes; SRRG2_E_INVALID: a null pyr,
+ *             num_levels outside 1 .. 8, a ratio outside 1 <= den < num <= 2 den, num <= 8, reserved != 0; SRRG2_E_UNSUPPORTED:
+ *             rows or cols above 4194304 (u_q8 / v_q8 would leave int32).
+ *   status    as srrg2_adapt_image_features; level 0 with a side below 33: an empty scene, READY, num_levels_built 0.
+ *   result    rows / cols / counters per built level (0 beyond); quota[l] = q_l (0 when max_features == 0).
+ *   waits     ONE host wait in the middle, for all levels' kept counts together (they size dst and place the levels in it); the
+ *             call returns when dst and keypoints_out are complete.  SRRG2_MEM_HOST images are consumed before the call returns.
+ *   identity  num_levels = 1: the scene, the counters and the records' first three fields are those of
+ *             srrg2_adapt_image_features. */
+typedef struct srrg2_pyramid_params {
+  int32_t num_levels; /* 1 .. 8, default 4 */
+  int32_t scale_num;  /* default 6 */
+  int32_t scale_den;  /* default 5;  1 <= den < num <= 2*den, num <= 8 */
+  int32_t reserved;   /* 0 */
+} srrg2_pyramid_params;
+typedef struct srrg2_pyramid_keypoint { /* 32 bytes */
+  int32_t pixel;       /* nearest level-0 pixel r0*cols + c0 (also the scene's global index) */
+  int32_t score, angle_bin, level;
+  int32_t level_pixel; /* r*cols_l + c in the level's own image */
+  int32_t u_q8, v_q8;  /* level-0 position of the keypoint's centre, 1/256 pixel */
+  int32_t reserved;
+} srrg2_pyramid_keypoint;
+typedef struct srrg2_pyramid_result {
+  int32_t status, num_levels_built, scene_size, reserved;
+  int32_t rows[8], cols[8], num_candidates[8], num_maxima[8], num_selected[8], num_with_depth[8], quota[8];
+} srrg2_pyramid_result;
+void srrg2_adapt_default_pyramid_params(srrg2_pyramid_params* p);
+int srrg2_adapt_image_features_pyramid(srrg2_scene_h dst /* dim 3 */, const void* intensity, int intensity_type /* U8 */,
+                                       int intensity_row_stride_bytes, const void* depth /* may be NULL */, int depth_type,
+                                       int depth_row_stride_bytes, int mem, const srrg2_depth_adaptor_params* cam,
+                                       const srrg2_feature_params* p, const srrg2_pyramid_params* pyr,
+                                       srrg2_pyramid_keypoint* keypoints_out /* host, may be NULL */, int keypoint_capacity,
+                                       srrg2_pyramid_result* out /* may be NULL */);
+
 /* Stereo features: a rectified pair of 8-bit images -> a compact scene of matched, triangulated, described keypoints (the
  * clouds of the reference's stereo pipeline, initializers/initializer_camera.h InitializerStereoCamera_).  No reference
  * counterpart; DESIGN.md section 4 "Stereo features" is the contract, tests/stereo_restatement.py restates it and the library
@@ -1137,6 +1199,9 @@ int srrg2_adapt_stereo_features(srrg2_scene_h dst /* dim 3 */, const void* left,
  * tests/tracking_restatement.py restates it and the library gives the same bits.
  *   fixed     the measurement: a dim-3 scene with descriptors whose srrg2_scene_global_indices are pixel indices r*cols + c in
  *             strictly ascending order (what srrg2_adapt_image_features / _stereo_features write, or a clip of such a scene).
+ *             A scene as srrg2_adapt_image_features_pyramid left it is taken too: level-major, its pixels (the nearest level-0
+ *             pixels) ascend strictly inside each level and may repeat across levels; the levels are searched one by one and
+ *             merged, the result is that of the rules below on all keypoints (the window is in level-0 pixels on every level).
  *             Keypoint j is fixed point j, its pixel its global index.  Its coordinates are NOT read: a keypoint with a non-finite
  *             point still matches (the aligner reports such a given pair as Suppressed).
  *   moving    the clipped local map: a dim-3 scene with descriptors, in any order.
@@ -1157,7 +1222,7 @@ int srrg2_adapt_stereo_features(srrg2_scene_h dst /* dim 3 */, const void* left,
  *             than 3; rows or cols <= 0 or rows*cols beyond int32; fx or fy zero or not finite; !(depth_min > 0) or
  *             !(depth_max >= depth_min); search_radius outside 0 .. 255; max_distance or min_margin outside 0 .. 256; cross_check
  *             not 0 / 1; reserved != 0; capacity < 0; a non-finite moving_in_sensor; fixed global indices that do not ascend
- *             strictly inside [0, rows*cols) (found on the device, reported at the call's host wait).  SRRG2_E_UNSUPPORTED: K with
+ *             strictly (a pyramid scene: inside each level) inside [0, rows*cols) (found on the device, reported at the call's host wait).  SRRG2_E_UNSUPPORTED: K with
  *             skew (K[0][1] != 0), as the clipper.  SRRG2_E_STATE: a non-empty scene without descriptors; a non-empty fixed scene
  *             whose global indices do not cover its points (srrg2_scene_set leaves none).
  *   empty     an empty scene on either side: 0, no correspondences, the counters filled (an empty `moving` returns before the

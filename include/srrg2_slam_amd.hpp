@@ -721,6 +721,7 @@ private:
 //   LaserScanAdaptor    ranges -> Scene<2> with normals
 //   LidarSweepAdaptor   3-D lidar sweep (point list, + intensity) -> Scene<3>, organised or compact, with normals
 //   ImageFeatureAdaptor 8-bit intensity image (+ depth image) -> Scene<3> of keypoints with descriptors and intensity
+//   PyramidFeatureAdaptor the same on every level of a scale pyramid of the image -> ONE Scene<3>, level-major
 //   StereoFeatureAdaptor rectified pair of 8-bit images -> Scene<3> of matched, triangulated keypoints with descriptors
 // setRawData / setMeas / compute / status / reset; status() is Error after setRawData until compute() (:67-72).  The raw
 // data is borrowed until compute() has run.  compute(false) asks for no counts: an organised adapt then only queues its work.
@@ -922,6 +923,70 @@ private:
   bool _has_raw = false;
   srrg2_feature_result _features{};
   std::vector<srrg2_keypoint> _keypoints;
+};
+
+// ImageFeatureAdaptor over a scale pyramid (srrg2_adapt_image_features_pyramid): ONE Scene<3> with the keypoints of every level,
+// level-major, at their level-0 positions; globalIndices() = the nearest level-0 pixel (it may repeat across levels).  pyramid:
+// num_levels and the ratio scale_num / scale_den.  last() keeps status and scene_size; result() has every per-level counter,
+// keypoints() the records in the scene's order.
+class PyramidFeatureAdaptor : public AdaptorBase_ {
+public:
+  using MeasurementType = Scene<3>;
+  srrg2_feature_params param;
+  srrg2_pyramid_params pyramid;
+  srrg2_depth_adaptor_params camera;
+  PyramidFeatureAdaptor() {
+    srrg2_adapt_default_feature_params(&param);
+    srrg2_adapt_default_pyramid_params(&pyramid);
+    srrg2_adapt_default_depth_params(&camera);
+  }
+  // images with a row stride in bytes; depth may be nullptr with SRRG2_IMAGE_NONE; camera.rows / cols say the size
+  void setRawData(const uint8_t* intensity, int intensity_row_stride_bytes, const void* depth = nullptr,
+                  int depth_type = SRRG2_IMAGE_NONE, int depth_row_stride_bytes = 0, int mem = SRRG2_MEM_HOST) {
+    _inten = intensity, _inten_stride = intensity_row_stride_bytes;
+    _depth = depth, _depth_type = depth_type, _depth_stride = depth_row_stride_bytes;
+    _mem = mem, _has_raw = true;
+    _status = Error;
+  }
+  void setMeas(MeasurementType* meas) { _meas = meas; }
+  void reset() {
+    _has_raw = false;
+    _status  = Initializing;
+    _keypoints.clear();
+  }
+  void compute() {
+    if (!_meas || !_has_raw) throw std::runtime_error("PyramidFeatureAdaptor::compute|raw data or measurement not set");
+    // every selected keypoint fits: the cap, or every admissible pixel of every level
+    long long want = param.max_features > 0 ? param.max_features : 0;
+    if (param.max_features <= 0 && pyramid.scale_num > 0)
+      for (int l = 0, rows = camera.rows, cols = camera.cols; l < pyramid.num_levels && rows > 32 && cols > 32;
+           ++l, rows = rows * pyramid.scale_den / pyramid.scale_num, cols = cols * pyramid.scale_den / pyramid.scale_num)
+        want += (long long) (rows - 32) * (long long) (cols - 32);
+    _keypoints.assign((size_t) want, srrg2_pyramid_keypoint{});
+    _result = srrg2_pyramid_result{};
+    const int rc = srrg2_adapt_image_features_pyramid(_meas->handle(), _inten, SRRG2_IMAGE_U8, _inten_stride, _depth, _depth_type,
+                                                      _depth_stride, _mem, &camera, &param, &pyramid,
+                                                      _keypoints.empty() ? nullptr : _keypoints.data(), (int) _keypoints.size(), &_result);
+    if (rc != 0) _keypoints.clear();
+    _last            = srrg2_adapt_result{};
+    _last.status     = _result.status;
+    _last.num_raw    = camera.rows * camera.cols;
+    _last.num_valid  = _result.scene_size;
+    _last.scene_size = _result.scene_size;
+    finish(rc, true);
+    _keypoints.resize((size_t) _result.scene_size < _keypoints.size() ? (size_t) _result.scene_size : _keypoints.size());
+  }
+  const srrg2_pyramid_result& result() const { return _result; }
+  const std::vector<srrg2_pyramid_keypoint>& keypoints() const { return _keypoints; }
+
+private:
+  MeasurementType* _meas = nullptr;
+  const uint8_t* _inten  = nullptr;
+  const void* _depth     = nullptr;
+  int _inten_stride = 0, _depth_type = SRRG2_IMAGE_NONE, _depth_stride = 0, _mem = SRRG2_MEM_HOST;
+  bool _has_raw = false;
+  srrg2_pyramid_result _result{};
+  std::vector<srrg2_pyramid_keypoint> _keypoints;
 };
 
 // a rectified pair of 8-bit images -> Scene<3> of the left image's keypoints that found their partner in the right image:

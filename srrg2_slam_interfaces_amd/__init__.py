@@ -80,6 +80,13 @@ def MeasurementAdaptorImageFeatures(params=None, camera=None):
     return _A(params, camera)
 
 
+def MeasurementAdaptorImageFeaturesPyramid(params=None, camera=None, pyramid=None):
+    """MeasurementAdaptorImageFeatures on every level of a scale pyramid, into one scene; see ``adaptors``."""
+    from .adaptors import MeasurementAdaptorImageFeaturesPyramid as _A
+
+    return _A(params, camera, pyramid)
+
+
 def MeasurementAdaptorStereoFeatures(params=None, stereo=None, camera=None):
     """Rectified pair of 8-bit images -> scene of matched, triangulated keypoints with descriptors on the device; see
     ``adaptors``."""

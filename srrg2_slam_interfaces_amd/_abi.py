@@ -229,6 +229,33 @@ class FeatureResult(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class PyramidParams(C.Structure):
+    """srrg2_pyramid_params"""
+    _fields_ = [("num_levels", C.c_int32), ("scale_num", C.c_int32), ("scale_den", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PyramidKeypoint(C.Structure):
+    """srrg2_pyramid_keypoint"""
+    _fields_ = [("pixel", C.c_int32), ("score", C.c_int32), ("angle_bin", C.c_int32), ("level", C.c_int32),
+                ("level_pixel", C.c_int32), ("u_q8", C.c_int32), ("v_q8", C.c_int32), ("reserved", C.c_int32)]
+
+
+PYRAMID_MAX_LEVELS = 8
+
+
+class PyramidResult(C.Structure):
+    """srrg2_pyramid_result"""
+    _fields_ = [("status", C.c_int32), ("num_levels_built", C.c_int32), ("scene_size", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, C.c_int32 * PYRAMID_MAX_LEVELS) for n in ("rows", "cols", "num_candidates", "num_maxima", "num_selected",
+                                                              "num_with_depth", "quota")]
+
+    def as_dict(self):
+        """the scalars as they are, the per-level arrays as lists of num_levels_built entries"""
+        out = {n: getattr(self, n) for n, _ in self._fields_[:4]}
+        out.update({n: list(getattr(self, n))[:self.num_levels_built] for n, _ in self._fields_[4:]})
+        return out
+
+
 class StereoParams(C.Structure):
     """srrg2_stereo_params"""
     _fields_ = [("baseline", C.c_float), ("min_disparity", C.c_int32), ("max_disparity", C.c_int32), ("row_tolerance", C.c_int32),

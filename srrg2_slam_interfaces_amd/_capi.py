@@ -74,6 +74,13 @@ def lib():
                                                     C.POINTER(abi.DepthAdaptorParams), C.POINTER(abi.FeatureParams),
                                                     C.POINTER(abi.Keypoint), C.c_int, C.POINTER(abi.FeatureResult)]
         _LIB.srrg2_feature_pattern.argtypes = [C.c_int, C.POINTER(C.c_int8)]
+        # srrg2_adapt_image_features_pyramid (adaptors.MeasurementAdaptorImageFeaturesPyramid)
+        _LIB.srrg2_adapt_default_pyramid_params.argtypes = [C.POINTER(abi.PyramidParams)]
+        _LIB.srrg2_adapt_default_pyramid_params.restype = None
+        _LIB.srrg2_adapt_image_features_pyramid.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                            C.c_int, C.POINTER(abi.DepthAdaptorParams), C.POINTER(abi.FeatureParams),
+                                                            C.POINTER(abi.PyramidParams), C.POINTER(abi.PyramidKeypoint), C.c_int,
+                                                            C.POINTER(abi.PyramidResult)]
         # srrg2_adapt_stereo_features (adaptors.MeasurementAdaptorStereoFeatures)
         _LIB.srrg2_adapt_default_stereo_params.argtypes = [C.POINTER(abi.StereoParams)]
         _LIB.srrg2_adapt_default_stereo_params.restype = None

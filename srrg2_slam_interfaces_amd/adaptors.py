@@ -7,13 +7,15 @@
                                    with normals, through the range image of a spherical sensor model
 ``MeasurementAdaptorImageFeatures`` 8-bit intensity image (+ optional depth image) -> compact 3-D scene of keypoints, each with
                                    a 256-bit descriptor and an intensity (FAST corners, rotated-pair descriptors)
+``MeasurementAdaptorImageFeaturesPyramid`` the same on every level of a scale pyramid of the image -> ONE compact scene,
+                                   level-major, points at the keypoints' level-0 positions
 ``MeasurementAdaptorStereoFeatures`` rectified pair of 8-bit images -> compact 3-D scene of the left image's keypoints that were
                                    matched in the right image, triangulated (z = fx * baseline / disparity)
 
 Method names follow ``RawDataPreprocessor_`` (S/raw_data_preprocessors/raw_data_preprocessor.h:13-88), snake_case:
 ``set_raw_data``, ``set_meas``, ``compute``, ``status``, ``reset``; ``status()`` is ERROR after ``set_raw_data`` until
 ``compute()`` (:67-72).  Thin marshalling only; product library only (the oracle has no adaptor: the parity target is
-tests/adaptor_restatement.py, tests/lidar_restatement.py, tests/features_restatement.py and tests/stereo_restatement.py).
+tests/adaptor_restatement.py, tests/lidar_restatement.py, tests/features_restatement.py, tests/pyramid_restatement.py and tests/stereo_restatement.py).
 """
 import ctypes as C
 
@@ -391,6 +393,64 @@ class MeasurementAdaptorImageFeatures(_AdaptorBase):
 
     def keypoints(self):
         """(n, 4) int32 rows of pixel, score, angle_bin, 0 of the last compute(), aligned with the scene's points"""
+        return self._keypoints
+
+
+def default_pyramid_params():
+    """srrg2_pyramid_params: 4 levels at 6/5"""
+    from . import _capi
+
+    p = abi.PyramidParams()
+    _capi.lib().srrg2_adapt_default_pyramid_params(C.byref(p))
+    return p
+
+
+PYRAMID_KEYPOINT_DTYPE = np.dtype([(n, np.int32) for n, _ in abi.PyramidKeypoint._fields_])
+
+
+class MeasurementAdaptorImageFeaturesPyramid(MeasurementAdaptorImageFeatures):
+    """MeasurementAdaptorImageFeatures over a scale pyramid (pyramid: abi.PyramidParams -- num_levels, scale_num / scale_den):
+    compute() leaves ONE compact scene of the keypoints of every level, level-major; the points lie at the keypoints' level-0
+    positions, global indices = nearest level-0 pixel (the same pixel may appear once per level)."""
+
+    def __init__(self, params=None, camera=None, pyramid=None):
+        super().__init__(params, camera)
+        self.pyramid = pyramid or default_pyramid_params()
+        self._keypoints = np.zeros(0, PYRAMID_KEYPOINT_DTYPE)
+
+    def reset(self):
+        super().reset()
+        self._keypoints = np.zeros(0, PYRAMID_KEYPOINT_DTYPE)
+
+    def compute(self, want_keypoints=True):
+        """fills the measurement scene; returns the counters of srrg2_pyramid_result (dict, per-level lists)"""
+        self._ready()
+        out = abi.PyramidResult()
+        _, iptr, itype, istride, mem, _ = self._raw
+        if self._depth is None:
+            dptr, dtype, dstride = None, abi.IMAGE_NONE, 0
+        else:
+            _, dptr, dtype, dstride, _, _ = self._depth
+        cap = 0
+        if want_keypoints:  # every selected keypoint fits: the cap, or every admissible pixel of every level
+            if self.params.max_features > 0:
+                cap = self.params.max_features
+            else:
+                rows, cols = self.camera.rows, self.camera.cols
+                for _ in range(max(self.pyramid.num_levels, 0)):
+                    cap += max(rows - 32, 0) * max(cols - 32, 0)
+                    rows = rows * self.pyramid.scale_den // max(self.pyramid.scale_num, 1)
+                    cols = cols * self.pyramid.scale_den // max(self.pyramid.scale_num, 1)
+        buf = np.zeros(max(cap, 1), PYRAMID_KEYPOINT_DTYPE)
+        self._check(self._lib.srrg2_adapt_image_features_pyramid(
+            self._meas._h, iptr, itype, istride, dptr, dtype, dstride, mem, C.byref(self.camera), C.byref(self.params),
+            C.byref(self.pyramid), buf.ctypes.data_as(C.POINTER(abi.PyramidKeypoint)) if cap > 0 else None, cap, C.byref(out)))
+        self._keypoints = buf[:min(out.scene_size, cap)]
+        return self._finish(out, True)
+
+    def keypoints(self):
+        """(n,) structured array (pixel, score, angle_bin, level, level_pixel, u_q8, v_q8, reserved) of the last compute(),
+        aligned with the scene's points"""
         return self._keypoints
 
 

@@ -15,7 +15,9 @@
 //   k_feat_describe    one wave per keypoint: disc moments lane-strided + wave reduction, 32 projections on 32 lanes + argmax,
 //                      4 x 64 comparisons assembled with __ballot; lane 0 writes point, intensity and the keypoint record
 // The pipeline is queued in two halves (features_pipeline.h: select, describe) on buffers the caller names, so that stereo.hip
-// runs it on two images behind one wait; srrg2_adapt_image_features hands it the scene's own arrays.
+// runs it on two images behind one wait; srrg2_adapt_image_features hands it the scene's own arrays.  pyramid.hip runs it on
+// every level of a scale pyramid: k_feat_select and k_feat_describe are templates on LEVEL, and only the <true> instantiations
+// read the level map (features_pipeline.h: FeatLevel) -- the single-scale and stereo paths launch <false>, the code as it was.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -47,6 +49,7 @@ const int kCosHost[32]    = FEAT_COS_TABLE;  // the pattern's (host)
 
 using Image     = srrg2amd::FeatImage;
 using DepthView = srrg2amd::FeatDepth;
+using LevelMap  = srrg2amd::FeatLevel;
 
 // byte `off` (-4 .. 7, relative to the thread's first pixel) of a 12-byte row held in three words; off is a constant after unrolling
 __device__ __forceinline__ int row_byte(const unsigned (&w)[3], int off) {
@@ -203,10 +206,12 @@ __global__ __launch_bounds__(256) void k_feat_tie(const unsigned char* __restric
   }
 }
 
-// tie: the exclusive scan of k_feat_tie's flags (n + 1 words)
+// tie: the exclusive scan of k_feat_tie's flags (n + 1 words).  LEVEL (a pyramid level, L its map): the depth pixel is the
+// keypoint's nearest level-0 pixel, and a level whose quota is 0 selects nothing; else L is not read.
+template <bool LEVEL>
 __global__ __launch_bounds__(256) void k_feat_select(const unsigned char* __restrict__ score, int pitch, int cols, int n,
                                                      const unsigned char* __restrict__ is_max, const int* __restrict__ tie,
-                                                     DepthView D, int* __restrict__ flags, int* __restrict__ ctr) {
+                                                     DepthView D, LevelMap L, int* __restrict__ flags, int* __restrict__ ctr) {
   const int cut = ctr[C_CUT], quota = ctr[C_QUOTA];
   int selected = 0;
   for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long) gridDim.x * blockDim.x) {
@@ -214,10 +219,13 @@ __global__ __launch_bounds__(256) void k_feat_select(const unsigned char* __rest
     if (is_max[i]) {
       const int r = (int) i / cols, c = (int) i - r * cols;  // (i < n: 32 bits)
       const int s = score[(size_t) r * pitch + c];
-      if (s > cut || (s == cut && tie[i] < quota)) {
+      if ((!LEVEL || !L.keep_none) && (s > cut || (s == cut && tie[i] < quota))) {
         ++selected;
         float z;
-        keep = D.depth_at(r, c, z) ? 1 : 0;
+        if (LEVEL)
+          keep = D.depth_at(LevelMap::nearest(L.q8(r), L.rows0), LevelMap::nearest(L.q8(c), L.cols0), z) ? 1 : 0;
+        else
+          keep = D.depth_at(r, c, z) ? 1 : 0;
       }
     }
     flags[i] = keep;
@@ -237,13 +245,17 @@ __global__ __launch_bounds__(256) void k_feat_scatter(int n, const int* __restri
 
 // One wave per keypoint (4 per workgroup).  pattern: 32 bins x 256 pairs, one word each (ax, ay, bx, by as int8, low byte first).
 // Every read stays inside the image: the keypoint is >= 16 pixels from the borders, the disc reaches 15, the rotated pattern 12
-// and a box sum there is valid from 2 pixels inside.
+// and a box sum there is valid from 2 pixels inside.  LEVEL (a pyramid level, L its map): gidx holds LEVEL pixels; the point is
+// taken at the keypoint's level-0 position, pixel0 gets its nearest level-0 pixel and rec the pyramid record (kps is not written);
+// else L, pixel0 and rec are not read.
+template <bool LEVEL>
 __global__ __launch_bounds__(256) void k_feat_describe(Image I, const unsigned char* __restrict__ score,
                                                        const unsigned short* __restrict__ box, int pitch,
-                                                       const unsigned* __restrict__ pattern, DepthView D, int oriented,
+                                                       const unsigned* __restrict__ pattern, DepthView D, LevelMap L, int oriented,
                                                        const int* __restrict__ gidx, int total, float4* __restrict__ pts,
                                                        float4* __restrict__ nrm, float* __restrict__ inten,
-                                                       unsigned long long* __restrict__ desc, srrg2_keypoint* __restrict__ kps) {
+                                                       unsigned long long* __restrict__ desc, srrg2_keypoint* __restrict__ kps,
+                                                       int* __restrict__ pixel0, srrg2_pyramid_keypoint* __restrict__ rec) {
   const int lane = threadIdx.x & 63;
   const int k    = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (k >= total) return;  // (the whole wave)
@@ -287,6 +299,24 @@ __global__ __launch_bounds__(256) void k_feat_describe(Image I, const unsigned c
     if (lane == w) word = m;
   }
   if (lane < 4) desc[(size_t) k * 4 + lane] = word;
+  if (LEVEL) {
+    if (lane == 0) {
+      const int u = L.q8(c), v = L.q8(r);
+      const int r0 = LevelMap::nearest(v, L.rows0), c0 = LevelMap::nearest(u, L.cols0);
+      float z = 1.f;
+      D.depth_at(r0, c0, z);  // (in range: k_feat_select kept the pixel)
+      const float3 q = LevelMap::point_at(D, u, v, z);
+      pts[k]   = make_float4(q.x, q.y, q.z, 0.f);
+      nrm[k]   = make_float4(0.f, 0.f, 0.f, 0.f);
+      inten[k] = (float) I.p[(long long) r * I.stride + c];
+      srrg2_pyramid_keypoint kp;
+      kp.pixel = r0 * L.cols0 + c0, kp.score = score[(size_t) r * pitch + c], kp.angle_bin = bin, kp.level = L.level;
+      kp.level_pixel = pixel, kp.u_q8 = u, kp.v_q8 = v, kp.reserved = 0;
+      pixel0[k] = kp.pixel;
+      rec[k]    = kp;
+    }
+    return;
+  }
   if (lane == 0) {
     if (pts) {  // (null: the caller makes the point itself, stereo.hip)
       float z = 1.f;
@@ -381,6 +411,63 @@ int srrg2amd::feat_check_params(const std::string& who, const srrg2_depth_adapto
   return 0;
 }
 
+int srrg2amd::feat_check_images(const std::string& who, srrg2_scene* dst, const void* intensity, int intensity_type,
+                                int intensity_stride, const void* depth, int depth_type, int depth_stride, int mem,
+                                const srrg2_depth_adaptor_params* cam, const srrg2_feature_params* p, int keypoint_capacity) {
+  int rc;
+  if (!dst || !cam || !p) return fail(SRRG2_E_INVALID, who + "null scene or params");
+  if (dst->dim != 3) return fail(SRRG2_E_INVALID, who + "the scene must have dim 3");
+  if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, who + "bad mem");
+  if (intensity_type == SRRG2_IMAGE_U16 || intensity_type == SRRG2_IMAGE_F32)
+    return fail(SRRG2_E_UNSUPPORTED, who + "the intensity image must be U8 (U16 and F32 are not supported)");
+  if (intensity_type != SRRG2_IMAGE_U8) return fail(SRRG2_E_INVALID, who + "intensity_type must be SRRG2_IMAGE_U8");
+  if (depth_type != SRRG2_IMAGE_NONE && depth_type != SRRG2_IMAGE_U16 && depth_type != SRRG2_IMAGE_F32)
+    return fail(SRRG2_E_INVALID, who + "depth_type must be NONE, U16 or F32");
+  if ((depth != nullptr) != (depth_type != SRRG2_IMAGE_NONE) && (depth || cam->rows * (long long) cam->cols > 0))
+    return fail(SRRG2_E_INVALID, who + "a depth image needs depth_type U16 or F32, and a depth_type its image");
+  if ((rc = srrg2amd::feat_check_params(who, cam, p, keypoint_capacity))) return rc;
+  const int de = depth_type == SRRG2_IMAGE_U16 ? 2 : 4;
+  if (cam->rows * cam->cols > 0) {
+    if (!intensity) return fail(SRRG2_E_INVALID, who + "null image");
+    if ((long long) intensity_stride < (long long) cam->cols) return fail(SRRG2_E_INVALID, who + "intensity row stride smaller than a row");
+    if (depth && ((long long) depth_stride < (long long) cam->cols * de || !aligned_to(depth, depth_stride, de)))
+      return fail(SRRG2_E_INVALID, who + "depth row stride smaller than a row, or image not aligned to its element");
+  }
+  return 0;
+}
+
+int srrg2amd::feat_stage_images(srrg2_scene* s, const void* intensity, int intensity_stride, const void* depth, int depth_type,
+                                int depth_stride, int mem, const srrg2_depth_adaptor_params* cam, FeatImage* image, FeatDepth* view) {
+  const int rows = cam->rows, cols = cam->cols;
+  const bool with_depth = depth != nullptr;
+  const int de = depth_type == SRRG2_IMAGE_U16 ? 2 : 4;
+  hipStream_t st = s->stream;
+  int rc;
+  Image I{static_cast<const unsigned char*>(intensity), (long long) intensity_stride, rows, cols};
+  DepthView D;
+  std::memset(&D, 0, sizeof(D));
+  D.p      = static_cast<const unsigned char*>(depth);
+  D.stride = depth_stride;
+  D.f32    = depth_type == SRRG2_IMAGE_F32;
+  D.ifx = 1.0f / cam->camera_matrix[0], D.ify = 1.0f / cam->camera_matrix[4];
+  D.cx = cam->camera_matrix[2], D.cy = cam->camera_matrix[5];
+  D.scale = cam->depth_scale, D.zmin = cam->depth_min, D.zmax = cam->depth_max;
+  if (mem == SRRG2_MEM_HOST) {  // rows up to the last pixel of the last row, as they lie
+    const size_t bi    = (size_t) (rows - 1) * (size_t) intensity_stride + (size_t) cols;
+    const size_t bd    = with_depth ? (size_t) (rows - 1) * (size_t) depth_stride + (size_t) cols * de : 0;
+    const size_t off_d = (bi + 63) / 64 * 64;
+    if ((rc = s->staging.reserve(off_d + bd + 64))) return rc;
+    HIP_TRY(hipMemcpyAsync(s->staging.p, intensity, bi, hipMemcpyHostToDevice, st));
+    I.p = reinterpret_cast<const unsigned char*>(s->staging.p);
+    if (with_depth) {
+      HIP_TRY(hipMemcpyAsync(s->staging.p + off_d, depth, bd, hipMemcpyHostToDevice, st));
+      D.p = reinterpret_cast<const unsigned char*>(s->staging.p + off_d);
+    }
+  }
+  *image = I, *view = D;
+  return 0;
+}
+
 size_t srrg2amd::feat_padded_pixels(int rows, int cols) {
   const int tiles_x = (cols + TILE_W - 1) / TILE_W, tiles_y = (rows + TILE_H - 1) / TILE_H;
   return (size_t) (tiles_x * TILE_W) * (size_t) (tiles_y * TILE_H);
@@ -398,8 +485,11 @@ int srrg2amd::feat_pattern_upload(srrg2_scene* s) {
   return 0;
 }
 
-int srrg2amd::feat_queue_select(const FeatImage& I, const FeatDepth& D, int fast_threshold, int max_features, const FeatWork& w,
-                                hipStream_t st) {
+namespace {
+
+// both halves, for the single-scale callers (level null: the identity map, not read) and for a pyramid level
+int queue_select(const Image& I, const DepthView& D, const LevelMap* level, int fast_threshold, int max_features,
+                 const srrg2amd::FeatWork& w, hipStream_t st) {
   const int rows = I.rows, cols = I.cols, n = rows * cols;
   const int tiles_x = (cols + TILE_W - 1) / TILE_W, tiles_y = (rows + TILE_H - 1) / TILE_H;
   const int pitch = tiles_x * TILE_W;
@@ -414,9 +504,24 @@ int srrg2amd::feat_queue_select(const FeatImage& I, const FeatDepth& D, int fast
   const dim3 grid(blocks_of(n)), block(256);
   hipLaunchKernelGGL(k_feat_tie, grid, block, 0, st, w.score, pitch, cols, n, w.is_max, ctr, w.tie);
   srrg2amd::launch_exclusive_scan(w.tie, n, w.scan_sums, ctr + C_TIES, st);
-  hipLaunchKernelGGL(k_feat_select, grid, block, 0, st, w.score, pitch, cols, n, w.is_max, w.tie, D, w.flags, ctr);
+  if (level)
+    hipLaunchKernelGGL(k_feat_select<true>, grid, block, 0, st, w.score, pitch, cols, n, w.is_max, w.tie, D, *level, w.flags, ctr);
+  else
+    hipLaunchKernelGGL(k_feat_select<false>, grid, block, 0, st, w.score, pitch, cols, n, w.is_max, w.tie, D, LevelMap{}, w.flags, ctr);
   HIP_TRY(hipGetLastError());
   return 0;
+}
+
+}  // namespace
+
+int srrg2amd::feat_queue_select(const FeatImage& I, const FeatDepth& D, int fast_threshold, int max_features, const FeatWork& w,
+                                hipStream_t st) {
+  return queue_select(I, D, nullptr, fast_threshold, max_features, w, st);
+}
+
+int srrg2amd::feat_queue_select_level(const FeatImage& I, const FeatDepth& D, const FeatLevel& L, int fast_threshold,
+                                      int max_features, const FeatWork& w, hipStream_t st) {
+  return queue_select(I, D, &L, fast_threshold, max_features, w, st);
 }
 
 int srrg2amd::feat_queue_describe(const FeatImage& I, const FeatDepth& D, int oriented, const FeatWork& w, const unsigned* pattern,
@@ -424,8 +529,20 @@ int srrg2amd::feat_queue_describe(const FeatImage& I, const FeatDepth& D, int or
   const int n     = I.rows * I.cols;
   const int pitch = (I.cols + TILE_W - 1) / TILE_W * TILE_W;
   hipLaunchKernelGGL(k_feat_scatter, dim3(blocks_of(n)), dim3(256), 0, st, n, w.flags, total, o.gidx);
-  hipLaunchKernelGGL(k_feat_describe, dim3((total + 3) / 4), dim3(256), 0, st, I, w.score, w.box, pitch, pattern, D, oriented, o.gidx,
-                     total, o.pts, o.nrm, o.inten, o.desc, o.kps);
+  hipLaunchKernelGGL(k_feat_describe<false>, dim3((total + 3) / 4), dim3(256), 0, st, I, w.score, w.box, pitch, pattern, D, LevelMap{},
+                     oriented, o.gidx, total, o.pts, o.nrm, o.inten, o.desc, o.kps, nullptr, nullptr);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int srrg2amd::feat_queue_describe_level(const FeatImage& I, const FeatDepth& D, const FeatLevel& L, int oriented, const FeatWork& w,
+                                        const unsigned* pattern, int total, int* lpix, const FeatOut& o, srrg2_pyramid_keypoint* rec,
+                                        hipStream_t st) {
+  const int n     = I.rows * I.cols;
+  const int pitch = (I.cols + TILE_W - 1) / TILE_W * TILE_W;
+  hipLaunchKernelGGL(k_feat_scatter, dim3(blocks_of(n)), dim3(256), 0, st, n, w.flags, total, lpix);
+  hipLaunchKernelGGL(k_feat_describe<true>, dim3((total + 3) / 4), dim3(256), 0, st, I, w.score, w.box, pitch, pattern, D, L, oriented,
+                     lpix, total, o.pts, o.nrm, o.inten, o.desc, nullptr, o.gidx, rec);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -450,28 +567,11 @@ extern "C" int srrg2_adapt_image_features(srrg2_scene_h dst, const void* intensi
                                           srrg2_keypoint* keypoints_out, int keypoint_capacity, srrg2_feature_result* out) {
   const std::string who = "adapt_image_features: ";
   int rc;
-  if (!dst || !cam || !p) return fail(SRRG2_E_INVALID, who + "null scene or params");
-  if (dst->dim != 3) return fail(SRRG2_E_INVALID, who + "the scene must have dim 3");
-  if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, who + "bad mem");
-  if (intensity_type == SRRG2_IMAGE_U16 || intensity_type == SRRG2_IMAGE_F32)
-    return fail(SRRG2_E_UNSUPPORTED, who + "the intensity image must be U8 (U16 and F32 are not supported)");
-  if (intensity_type != SRRG2_IMAGE_U8) return fail(SRRG2_E_INVALID, who + "intensity_type must be SRRG2_IMAGE_U8");
-  if (depth_type != SRRG2_IMAGE_NONE && depth_type != SRRG2_IMAGE_U16 && depth_type != SRRG2_IMAGE_F32)
-    return fail(SRRG2_E_INVALID, who + "depth_type must be NONE, U16 or F32");
-  if ((depth != nullptr) != (depth_type != SRRG2_IMAGE_NONE) && (depth || cam->rows * (long long) cam->cols > 0))
-    return fail(SRRG2_E_INVALID, who + "a depth image needs depth_type U16 or F32, and a depth_type its image");
-  if ((rc = srrg2amd::feat_check_params(who, cam, p, keypoint_capacity))) return rc;
-  const float fx = cam->camera_matrix[0], fy = cam->camera_matrix[4];
+  if ((rc = srrg2amd::feat_check_images(who, dst, intensity, intensity_type, intensity_stride, depth, depth_type, depth_stride, mem,
+                                        cam, p, keypoint_capacity)))
+    return rc;
   const int rows = cam->rows, cols = cam->cols;
   const int n = rows * cols;
-  const bool with_depth = depth != nullptr;
-  const int de = depth_type == SRRG2_IMAGE_U16 ? 2 : 4;
-  if (n > 0) {
-    if (!intensity) return fail(SRRG2_E_INVALID, who + "null image");
-    if ((long long) intensity_stride < (long long) cols) return fail(SRRG2_E_INVALID, who + "intensity row stride smaller than a row");
-    if (with_depth && ((long long) depth_stride < (long long) cols * de || !aligned_to(depth, depth_stride, de)))
-      return fail(SRRG2_E_INVALID, who + "depth row stride smaller than a row, or image not aligned to its element");
-  }
   srrg2_scene* const s = dst;
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = s->stream;
@@ -486,27 +586,9 @@ extern "C" int srrg2_adapt_image_features(srrg2_scene_h dst, const void* intensi
   }
   if (rows <= 2 * MARGIN || cols <= 2 * MARGIN) return srrg2amd::feat_empty_scene(s);  // no pixel 16 away from every border
 
-  Image I{static_cast<const unsigned char*>(intensity), (long long) intensity_stride, rows, cols};
+  Image I;
   DepthView D;
-  std::memset(&D, 0, sizeof(D));
-  D.p      = static_cast<const unsigned char*>(depth);
-  D.stride = depth_stride;
-  D.f32    = depth_type == SRRG2_IMAGE_F32;
-  D.ifx = 1.0f / fx, D.ify = 1.0f / fy;
-  D.cx = cam->camera_matrix[2], D.cy = cam->camera_matrix[5];
-  D.scale = cam->depth_scale, D.zmin = cam->depth_min, D.zmax = cam->depth_max;
-  if (mem == SRRG2_MEM_HOST) {  // rows up to the last pixel of the last row, as they lie
-    const size_t bi    = (size_t) (rows - 1) * (size_t) intensity_stride + (size_t) cols;
-    const size_t bd    = with_depth ? (size_t) (rows - 1) * (size_t) depth_stride + (size_t) cols * de : 0;
-    const size_t off_d = (bi + 63) / 64 * 64;
-    if ((rc = s->staging.reserve(off_d + bd + 64))) return rc;
-    HIP_TRY(hipMemcpyAsync(s->staging.p, intensity, bi, hipMemcpyHostToDevice, st));
-    I.p = reinterpret_cast<const unsigned char*>(s->staging.p);
-    if (with_depth) {
-      HIP_TRY(hipMemcpyAsync(s->staging.p + off_d, depth, bd, hipMemcpyHostToDevice, st));
-      D.p = reinterpret_cast<const unsigned char*>(s->staging.p + off_d);
-    }
-  }
+  if ((rc = srrg2amd::feat_stage_images(s, intensity, intensity_stride, depth, depth_type, depth_stride, mem, cam, &I, &D))) return rc;
   const size_t padded = srrg2amd::feat_padded_pixels(rows, cols);
   if ((rc = s->feat_score.reserve(padded)) || (rc = s->feat_box.reserve(padded))) return rc;
   if ((rc = s->feat_max.reserve((size_t) n)) || (rc = s->feat_tie.reserve((size_t) n + 1))) return rc;

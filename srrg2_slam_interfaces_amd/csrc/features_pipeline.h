@@ -49,6 +49,24 @@ struct FeatDepth {
   }
 };
 
+// Where level l of a scale pyramid (pyramid.hip) sits over level 0: a level pixel's centre lies at (2c+1) num / (2 den) - 1/2 level-0
+// pixels, num = scale_num^l, den = scale_den^l.  The depth gate and the point are taken there; the identity map (level 0) gives
+// 256 c, c and the arithmetic of the single-scale extractor, bit for bit.
+struct FeatLevel {
+  long long num, den;
+  int rows0, cols0;  // level 0's size
+  int level;
+  int keep_none;  // the level's quota under the cap is 0: nothing is selected (inside the cap proper, 0 means "no cap")
+
+  __device__ __forceinline__ int q8(int c) const { return (int) (((long long) (2 * c + 1) * num * 128) / den - 128); }
+  __device__ __forceinline__ static int nearest(int q8, int size0) { return min((q8 + 128) >> 8, size0 - 1); }
+  // FeatDepth::point_at with u = u_q8 / 256 in place of (float) c
+  __device__ __forceinline__ static float3 point_at(const FeatDepth& D, int u_q8, int v_q8, float z) {
+    const float u = (float) u_q8 * (1.0f / 256.0f), v = (float) v_q8 * (1.0f / 256.0f);
+    return make_float3(((u - D.cx) * D.ifx) * z, ((v - D.cy) * D.ify) * z, z);
+  }
+};
+
 // one image's scratch: score / box of feat_padded_pixels(rows, cols) elements, is_max of n = rows * cols, tie and flags of
 // n + 1, ctr of FEAT_C_WORDS, scan_sums of scan_num_blocks(n) + 2
 struct FeatWork {
@@ -74,6 +92,13 @@ struct FeatOut {
 // the refusals that depend on the camera, the feature parameters and the capacity alone (0, or the error code with the text set)
 int feat_check_params(const std::string& who, const srrg2_depth_adaptor_params* cam, const srrg2_feature_params* p,
                       int keypoint_capacity);
+// every refusal of srrg2_adapt_image_features, in its order (0, or the error code with the text set)
+int feat_check_images(const std::string& who, srrg2_scene* dst, const void* intensity, int intensity_type, int intensity_stride,
+                      const void* depth, int depth_type, int depth_stride, int mem, const srrg2_depth_adaptor_params* cam,
+                      const srrg2_feature_params* p, int keypoint_capacity);
+// the views of the checked images and camera; SRRG2_MEM_HOST images are copied into s->staging, queued on s->stream
+int feat_stage_images(srrg2_scene* s, const void* intensity, int intensity_stride, const void* depth, int depth_type, int depth_stride,
+                      int mem, const srrg2_depth_adaptor_params* cam, FeatImage* image, FeatDepth* view);
 // dst becomes an empty feature scene (arrays for one point, as the adaptors leave them)
 int feat_empty_scene(srrg2_scene* s);
 size_t feat_padded_pixels(int rows, int cols);
@@ -85,5 +110,13 @@ int feat_queue_select(const FeatImage& I, const FeatDepth& D, int fast_threshold
 // description
 int feat_queue_describe(const FeatImage& I, const FeatDepth& D, int oriented, const FeatWork& w, const unsigned* pattern, int total,
                         const FeatOut& o, hipStream_t st);
+// The same two halves on level L of a pyramid.  select: the depth gate reads D at the keypoint's nearest level-0 pixel.  describe:
+// the kept LEVEL pixels go to lpix[0 .. total), o.gidx takes the nearest level-0 pixel, o.pts the point at the level-0 position,
+// rec the pyramid records; o.kps is not written
+int feat_queue_select_level(const FeatImage& I, const FeatDepth& D, const FeatLevel& L, int fast_threshold, int max_features,
+                            const FeatWork& w, hipStream_t st);
+int feat_queue_describe_level(const FeatImage& I, const FeatDepth& D, const FeatLevel& L, int oriented, const FeatWork& w,
+                              const unsigned* pattern, int total, int* lpix, const FeatOut& o, srrg2_pyramid_keypoint* rec,
+                              hipStream_t st);
 
 }  // namespace srrg2amd

@@ -575,6 +575,7 @@ int bind_features(srrg2_scene* scene, const srrg2_scene* meas, const char* who) 
 
 // grow the point arrays (and the feature arrays that are present) to hold n points, keeping the first `keep`
 int scene_reserve(srrg2_scene* s, int n, int keep) {
+  s->pyr_levels = 0;  // (the content is about to be rewritten: it is no pyramid adaptor's any more)
   if ((size_t) n <= s->pts.cap && (size_t) n <= s->nrm.cap) return features_reserve(s, keep);
   int rc;
   const size_t want = (size_t) n + (size_t) n / 2 + 1024, kept = (size_t) (keep > 0 ? keep : 0);

@@ -71,6 +71,19 @@ struct srrg2_scene {
   srrg2amd::DevBuf<unsigned long long> st_best[2];
   srrg2amd::DevBuf<srrg2_stereo_match> st_match, st_match_out;
   srrg2amd::DevBuf<float> st_z;
+  // adapt_image_features_pyramid (pyramid.hip): levels 1 .. of the image at pitches that are multiples of 4; the pipeline scratch
+  // of ALL levels, each array one block with a slice per level (score / box padded to whole tiles, maxima flags, tie ranks, keep
+  // flags, scan sums, counters); per kept keypoint its level pixel and its record; the pinned mirror of the levels' counters
+  srrg2amd::DevBuf<unsigned char> pyr_img, pyr_score, pyr_max;
+  srrg2amd::DevBuf<unsigned short> pyr_box;
+  srrg2amd::DevBuf<int> pyr_tie, pyr_flags, pyr_sums, pyr_ctr, pyr_lpix;
+  srrg2amd::DevBuf<srrg2_pyramid_keypoint> pyr_kp;
+  srrg2amd::PinnedBuf<int> pyr_host;
+  // ... and, while the content is that call's: the number of built levels and where each level's keypoints begin (level l is
+  // points pyr_offset[l] .. pyr_offset[l + 1]).  scene_make_room and every other rewrite of the content clear pyr_levels; the
+  // tracker reads it to search a level-major `fixed` scene level by level
+  int pyr_levels = 0;
+  int pyr_offset[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   // track_features (tracking.hip; on the MOVING scene, whose flags / scan_sums hold the keep flags and their scan): per landmark
   // its projected pixel (-1 = not in view), its best keypoint (distance << 32 | keypoint index, all ones = none), the smallest
   // distance among its other candidates and its record; per image row + 1 the first keypoint at or below it; per keypoint the
@@ -79,6 +92,9 @@ struct srrg2_scene {
   srrg2amd::DevBuf<int> trk_pix, trk_rows;
   srrg2amd::DevBuf<unsigned> trk_second;
   srrg2amd::DevBuf<unsigned long long> trk_best, trk_best_fixed;
+  // ... `fixed` a pyramid scene of several levels: per level and landmark the level's best keypoint and runner-up distance
+  srrg2amd::DevBuf<unsigned long long> trk_best_level;
+  srrg2amd::DevBuf<unsigned> trk_second_level;
   srrg2amd::DevBuf<srrg2_correspondence> trk_rec;
   srrg2amd::DevBuf<int> trk_out;
   srrg2amd::PinnedBuf<int> trk_host;  // words

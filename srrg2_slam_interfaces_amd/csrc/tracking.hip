@@ -8,6 +8,10 @@
 //   (the keypoints' row table, which checks that their pixels ascend strictly inside the image and raises the error word
 //   otherwise, then the banded descriptor search of desc_band.hip with the runner-up's distance and, with the cross check, the
 //   reverse atomicMin table: srrg2amd::launch_band_rows, launch_band_search -- the column gate is [-R, R])
+//   (`fixed` a pyramid scene of several levels -- level-major, its pixels ascend inside a level only: row table and search once per
+//   level on the level's slice of the keypoints, then)
+//   k_track_merge    one thread per landmark: the levels' (best, runner-up) pairs -> those of all keypoints, the keypoint index
+//                     made global; the same merge the search runs across its lanes, so the result is that of one search
 //   k_track_resolve  one thread per landmark: the gates, the cross check, the record and the keep flag; the four counters are
 //                     block sums with one atomic per block and counter
 //   (exclusive scan of the keep flags: srrg2amd::launch_exclusive_scan, what srrg2amd::scene_scan_flags runs -- its total rides
@@ -40,6 +44,32 @@ struct TrackCam {
   float K0, K2, K4, K5, depth_min, depth_max;
   int rows, cols;
 };
+
+// the non-empty levels of a pyramid scene as `fixed`: level s holds keypoints offset[s] .. offset[s + 1]
+struct TrackLevels {
+  int n;
+  int offset[9];
+};
+
+// best_level / second_level: per level s and landmark q (at s * nm + q) what the banded search found among that level's keypoints,
+// the index counted inside the level.  Disjoint candidate sets: the smaller key wins, the loser's distance is a distance of
+// "another candidate" as both runner-ups are (merge_best of desc_band.hip).
+__global__ __launch_bounds__(256) void k_track_merge(int nm, TrackLevels L, const unsigned long long* __restrict__ best_level,
+                                                     const unsigned* __restrict__ second_level, unsigned long long* __restrict__ best,
+                                                     unsigned* __restrict__ second) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nm) return;
+  unsigned long long key = NO_CANDIDATE;
+  unsigned sec           = NO_SECOND;
+  for (int s = 0; s < L.n; ++s) {
+    unsigned long long k = best_level[(size_t) s * nm + q];
+    if (k != NO_CANDIDATE) k += (unsigned) L.offset[s];  // (index + offset < the scene's size: no carry into the distance)
+    sec = min(min(sec, second_level[(size_t) s * nm + q]), (unsigned) ((k < key ? key : k) >> 32));
+    key = k < key ? k : key;
+  }
+  best[q]   = key;
+  second[q] = sec;
+}
 
 // srrg2_scene_clip_projective's steps behind its two transforms (scene.hip pclip_project): the same operations in the same order
 __global__ __launch_bounds__(256) void k_track_project(TrackCam C, const float4* __restrict__ pts, int n, int* __restrict__ pix) {
@@ -167,6 +197,18 @@ extern "C" int srrg2_scene_track_features(srrg2_scene_h moving, srrg2_scene_h fi
       (rc = s->flags.reserve((size_t) nm + 1)) || (rc = s->scan_sums.reserve((size_t) srrg2amd::scan_num_blocks(nm) + 2)))
     return rc;
   if ((rc = s->trk_host.reserve(words, words / 8 + 64))) return rc;
+  // `fixed` written by srrg2_adapt_image_features_pyramid and untouched since: its non-empty levels
+  TrackLevels levels;
+  std::memset(&levels, 0, sizeof(levels));
+  if (fixed->pyr_levels > 1 && fixed->pyr_offset[fixed->pyr_levels] == nf)
+    for (int l = 0; l < fixed->pyr_levels; ++l)
+      if (fixed->pyr_offset[l + 1] > fixed->pyr_offset[l]) {
+        levels.offset[levels.n]     = fixed->pyr_offset[l];
+        levels.offset[++levels.n]   = fixed->pyr_offset[l + 1];
+      }
+  if (levels.n > 1 && ((rc = s->trk_rows.reserve((size_t) levels.n * ((size_t) rows + 1))) ||
+                       (rc = s->trk_best_level.reserve((size_t) levels.n * nm)) || (rc = s->trk_second_level.reserve((size_t) levels.n * nm))))
+    return rc;
   TrackCam C;
   std::memcpy(C.m, moving_in_sensor, sizeof(C.m));
   C.K0 = fx, C.K2 = p->camera_matrix[2], C.K4 = fy, C.K5 = p->camera_matrix[5];
@@ -179,10 +221,24 @@ extern "C" int srrg2_scene_track_features(srrg2_scene_h moving, srrg2_scene_h fi
   HIP_TRY(hipMemsetAsync(block, 0, T_WORDS * sizeof(int), st));
   if (reverse) HIP_TRY(hipMemsetAsync(reverse, 0xff, sizeof(unsigned long long) * (size_t) (nf + 1), st));
   hipLaunchKernelGGL(k_track_project, dim3(blocks_of(nm)), dim3(256), 0, st, C, moving->pts.p, nm, s->trk_pix.p);
-  srrg2amd::launch_band_rows(fixed->gidx.p, nf, rows, cols, s->trk_rows.p, block + T_ERROR, st);
-  srrg2amd::launch_band_search(nm, s->trk_pix.p, moving->desc.p, fixed->gidx.p, fixed->desc.p, s->trk_rows.p, rows, cols,
-                               p->search_radius, -p->search_radius, p->search_radius, block + T_ERROR, s->trk_best.p,
-                               s->trk_second.p, reverse, st);
+  if (levels.n <= 1) {
+    srrg2amd::launch_band_rows(fixed->gidx.p, nf, rows, cols, s->trk_rows.p, block + T_ERROR, st);
+    srrg2amd::launch_band_search(nm, s->trk_pix.p, moving->desc.p, fixed->gidx.p, fixed->desc.p, s->trk_rows.p, rows, cols,
+                                 p->search_radius, -p->search_radius, p->search_radius, block + T_ERROR, s->trk_best.p,
+                                 s->trk_second.p, reverse, st);
+  } else {  // a pyramid scene: level by level (the pixels must ascend strictly inside every level), then one merge
+    for (int l = 0; l < levels.n; ++l) {
+      const int at = levels.offset[l], count = levels.offset[l + 1] - at;
+      int* const table = s->trk_rows.p + (size_t) l * ((size_t) rows + 1);
+      srrg2amd::launch_band_rows(fixed->gidx.p + at, count, rows, cols, table, block + T_ERROR, st);
+      srrg2amd::launch_band_search(nm, s->trk_pix.p, moving->desc.p, fixed->gidx.p + at, fixed->desc.p + 2 * (size_t) at, table, rows, cols,
+                                   p->search_radius, -p->search_radius, p->search_radius, block + T_ERROR,
+                                   s->trk_best_level.p + (size_t) l * nm, s->trk_second_level.p + (size_t) l * nm,
+                                   reverse ? reverse + at : nullptr, st);
+    }
+    hipLaunchKernelGGL(k_track_merge, dim3(blocks_of(nm)), dim3(256), 0, st, nm, levels, s->trk_best_level.p, s->trk_second_level.p,
+                       s->trk_best.p, s->trk_second.p);
+  }
   hipLaunchKernelGGL(k_track_resolve, dim3(blocks_of(nm)), dim3(256), 0, st, nm, s->trk_pix.p, s->trk_best.p, s->trk_second.p, reverse,
                      p->max_distance, p->min_margin, p->cross_check, s->trk_rec.p, s->flags.p, block);
   srrg2amd::launch_exclusive_scan(s->flags.p, nm, s->scan_sums.p, block + T_TOTAL, st);

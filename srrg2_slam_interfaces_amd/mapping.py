@@ -458,8 +458,8 @@ def to_merger(corr, moving_global_indices):
 class FeatureTracker:
     """setFixed / setMoving / setLocalMapInSensor / compute of the reference's CorrespondenceFinder_
     (S/registration/correspondence_finder.h:56-114), made concrete for clouds with descriptors (srrg2_scene_track_features;
-    product library only).  ``fixed``: the measurement, a scene of keypoints whose global indices are pixel indices (an image
-    or stereo adaptor's output); ``moving``: the clipped local map, landmarks with descriptors; ``moving_in_sensor``: the pose
+    product library only).  ``fixed``: the measurement, a scene of keypoints whose global indices are pixel indices (an image,
+    stereo or pyramid adaptor's output); ``moving``: the clipped local map, landmarks with descriptors; ``moving_in_sensor``: the pose
     guess (3 x 4).  ``params``: TrackParams (camera matrix, image size, depth range, search_radius, max_distance, min_margin,
     cross_check).  compute() returns the pairs as a CORR_DTYPE array in ascending moving_idx -- what
     ``MultiAligner.set_correspondences`` takes for a FINDER_CORRESPONDENCES slice; ``result``: the counters of the last call."""
