@@ -1192,6 +1192,68 @@ int srrg2_adapt_stereo_features(srrg2_scene_h dst /* dim 3 */, const void* left,
                                 srrg2_stereo_match* matches_out /* host, may be NULL */, int match_capacity,
                                 srrg2_stereo_result* out /* may be NULL */);
 
+/* Dense stereo: a rectified pair of 8-bit images -> a disparity for every pixel that earns one -> depth -> the scene
+ * srrg2_adapt_depth_image leaves for that depth image with the left image as its intensity, without leaving the device.  No
+ * reference counterpart; DESIGN.md section 4 "Dense stereo" is the contract, tests/stereo_dense_restatement.py restates it and
+ * the library gives the same bits.  cam: rows, cols (both images have that shape and lie in `mem`) and everything the depth
+ * adaptor reads.  The right camera sits at +baseline along the left camera's x axis.
+ *   census    62 bits per pixel with 3 <= r < rows-3, 4 <= c < cols-4: one per (dy, dx) in [-3,3] x [-4,4] but (0,0), set iff
+ *             I(r+dy, c+dx) < I(r, c).
+ *   rectangle rows 3 .. rows-4, columns 4 + max_disparity .. cols-5: every disparity of the range is defined for each of its
+ *             pixels; pixels outside never get a disparity.  Empty (rows < 7 or cols < max_disparity + 9): no disparities, READY.
+ *   cost      C(p, d) = popcount(censusL(r, c) ^ censusR(r, c-d)), 0 .. 62.
+ *   paths     4: for e in (0,+1), (0,-1), (+1,0), (-1,0): L_e(p,d) = C(p,d) when p-e lies outside the rectangle, else C(p,d) +
+ *             min(L_e(p-e,d), L_e(p-e,d-1)+p1, L_e(p-e,d+1)+p1, M+p2) - M with M = min_k L_e(p-e,k), terms beyond the range
+ *             omitted; S = sum of the four.  0: S = C.
+ *   best      d* = argmin_d S(p,d), the smallest d on ties.
+ *   unique    uniqueness_ratio u > 0: with S2 the minimum of S over |d - d*| > 1, the pixel passes iff there is no such d or
+ *             S2 (100-u) > 100 S(p,d*) (strict: a flat image is rejected everywhere).
+ *   lr_check  dR(r,x) = argmin over d with (r, x+d) in the rectangle of S((r,x+d), d), the smallest d on ties -- the left
+ *             volume read along its diagonal; the pixel passes iff |dR(r, c-d*) - d*| <= lr_tolerance.
+ *   subpixel  for min < d* < max, with a = S(d*-1), b = S(d*), cc = S(d*+1), D = a - 2b + cc > 0:
+ *             disparity = (float) d* + (float)(a - cc) / (float)(2 D); otherwise (float) d*.
+ *   scene     Z = (fx * baseline) / disparity in float32, NaN without a disparity; dst is bit for bit what
+ *             srrg2_adapt_depth_image(dst, Z, F32, ..., left, U8, ..., cam, ...) leaves (the same code runs).
+ *   disparity_out  rows x cols floats in `mem` (may be NULL), 0.0f where there is no disparity; bytes between rows are not written.
+ *   refused   dst and disparity_out untouched, nothing read from the images.  Everything srrg2_adapt_depth_image refuses for
+ *             cam, the images' strides and mem, with its codes.  SRRG2_E_INVALID: a null sp, baseline not finite or <= 0,
+ *             min_disparity < 1, max_disparity < min_disparity, paths not 0 / 4, not 0 <= p1 <= p2 <= 255, uniqueness_ratio
+ *             outside 0 .. 99, lr_check or subpixel not 0 / 1, lr_tolerance outside 0 .. 16, reserved != 0, dst and
+ *             disparity_out both NULL, a disparity stride below 4 cols or no multiple of 4 (or a misaligned disparity_out).
+ *             SRRG2_E_UNSUPPORTED: more than 256 disparities, a volume of more than 2^31 - 1 elements.
+ *   status    zero pixels: an empty scene, INITIALIZING; otherwise READY.
+ *   waits     none in the middle: every size follows from the shapes.  Organised mode, out == NULL and disparity_out NULL or in
+ *             device memory: the call queues its work on the scene's stream and returns, like the depth adaptor.  Otherwise ONE
+ *             wait at the end (compact mode: the depth adaptor's own wait for the scene's size comes before it).  dst == NULL:
+ *             the call works on a scene of its own on the current device and returns when that scene has retired.
+ * p1 8, p2 48 and uniqueness_ratio 10 are UNTUNED defaults: nobody has derived or measured them. */
+typedef struct srrg2_dense_stereo_params {
+  float   baseline;         /* metres, finite, > 0 (default 0: the caller must set it) */
+  int32_t min_disparity;    /* >= 1, default 1 */
+  int32_t max_disparity;    /* >= min_disparity; max - min + 1 <= 256 (else SRRG2_E_UNSUPPORTED); default 64 */
+  int32_t paths;            /* 0: per-pixel census cost only; 4: aggregation along the four axis directions; default 4 */
+  int32_t p1, p2;           /* 0 <= p1 <= p2 <= 255; defaults 8 / 48 (untuned) */
+  int32_t uniqueness_ratio; /* 0 .. 99 per cent, 0 = no test; default 10 (untuned) */
+  int32_t lr_check;         /* 0 | 1, default 1 */
+  int32_t lr_tolerance;     /* 0 .. 16, default 1 */
+  int32_t subpixel;         /* 0 | 1, default 1 */
+  int32_t reserved;         /* 0 */
+} srrg2_dense_stereo_params;
+typedef struct srrg2_dense_stereo_result {
+  int32_t status;           /* srrg2_adaptor_status */
+  int32_t num_pixels;       /* rows * cols */
+  int32_t num_evaluated;    /* pixels of the processed rectangle */
+  int32_t num_unique;       /* ... that pass the uniqueness test */
+  int32_t num_consistent;   /* ... and the left-right check: the pixels that carry a disparity */
+  int32_t num_in_range, num_valid, scene_size; /* srrg2_adapt_result's, 0 when dst is NULL */
+} srrg2_dense_stereo_result;
+void srrg2_adapt_default_dense_stereo_params(srrg2_dense_stereo_params* p);
+int srrg2_adapt_stereo_dense(srrg2_scene_h dst /* dim 3; may be NULL if disparity_out is not */, const void* left,
+                             int left_row_stride_bytes, const void* right, int right_row_stride_bytes, int mem,
+                             const srrg2_depth_adaptor_params* cam, const srrg2_dense_stereo_params* sp,
+                             float* disparity_out /* rows x cols, in `mem`, may be NULL */, int disparity_row_stride_bytes,
+                             srrg2_dense_stereo_result* out /* may be NULL */);
+
 /* Feature tracking: which keypoint of the measurement is which landmark of the clipped local map -- the per-frame data
  * association of a visual tracker, a projective window plus the Hamming distance of the 256-bit descriptors.  The reference
  * declares the slot and leaves it empty (CorrespondenceFinder_::compute() is pure virtual, S/registration/correspondence_finder.h:56;

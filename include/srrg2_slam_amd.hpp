@@ -1057,6 +1057,75 @@ private:
   std::vector<srrg2_stereo_match> _matches;
 };
 
+// a rectified pair of 8-bit images -> a disparity per pixel -> depth -> the Scene<3> that DepthImageAdaptor leaves for that
+// depth with the left image as its intensity (srrg2_adapt_stereo_dense).  stereo: baseline (set it: the default 0 is refused),
+// disparity range, paths, penalties, uniqueness, left-right check, sub-pixel; camera: all of it, as for DepthImageAdaptor.
+// setMeas(nullptr) (or never): only the disparity image is computed.  compute(want_result, want_disparity): without the result
+// an organised adapt whose disparity stays on the device only queues its work; with host images want_disparity fills
+// disparity() (rows x cols floats, 0 = none); device images take setDisparityOut(device pointer, stride) instead.
+class StereoDenseAdaptor : public AdaptorBase_ {
+public:
+  using MeasurementType = Scene<3>;
+  srrg2_dense_stereo_params stereo;
+  srrg2_depth_adaptor_params camera;
+  StereoDenseAdaptor() {
+    srrg2_adapt_default_dense_stereo_params(&stereo);
+    srrg2_adapt_default_depth_params(&camera);
+  }
+  // images with a row stride in bytes, both of camera.rows x camera.cols and in the same memory
+  void setRawData(const uint8_t* left, int left_row_stride_bytes, const uint8_t* right, int right_row_stride_bytes,
+                  int mem = SRRG2_MEM_HOST) {
+    _left = left, _left_stride = left_row_stride_bytes;
+    _right = right, _right_stride = right_row_stride_bytes;
+    _mem = mem, _has_raw = true;
+    _status = Error;
+  }
+  void setMeas(MeasurementType* meas) { _meas = meas; }
+  // where compute() writes the disparity image when the images are in device memory (nullptr: nowhere)
+  void setDisparityOut(float* device_pointer, int row_stride_bytes) { _dev_out = device_pointer, _dev_out_stride = row_stride_bytes; }
+  void reset() {
+    _has_raw = false;
+    _status  = Initializing;
+    _disparity.clear();
+  }
+  void compute(bool want_result = true, bool want_disparity = false) {
+    if (!_has_raw) throw std::runtime_error("StereoDenseAdaptor::compute|raw data not set");
+    float* out_ptr = nullptr;
+    int out_stride = 0;
+    _disparity.clear();
+    if (_mem == SRRG2_MEM_DEVICE) {
+      out_ptr = _dev_out, out_stride = _dev_out_stride;
+    } else if (want_disparity) {
+      _disparity.assign((size_t) (camera.rows > 0 ? camera.rows : 0) * (size_t) (camera.cols > 0 ? camera.cols : 0), 0.f);
+      out_ptr = _disparity.empty() ? nullptr : _disparity.data(), out_stride = 4 * camera.cols;
+    }
+    _result = srrg2_dense_stereo_result{};
+    const int rc = srrg2_adapt_stereo_dense(_meas ? _meas->handle() : nullptr, _left, _left_stride, _right, _right_stride, _mem, &camera,
+                                            &stereo, out_ptr, out_stride, want_result ? &_result : nullptr);
+    if (rc != 0) _disparity.clear();
+    _last              = srrg2_adapt_result{};
+    _last.status       = _result.status;
+    _last.num_raw      = _result.num_pixels;
+    _last.num_in_range = _result.num_in_range;
+    _last.num_valid    = _result.num_valid;
+    _last.scene_size   = _result.scene_size;
+    finish(rc, want_result);
+  }
+  const srrg2_dense_stereo_result& result() const { return _result; }
+  const std::vector<float>& disparity() const { return _disparity; }
+
+private:
+  MeasurementType* _meas = nullptr;
+  const uint8_t* _left   = nullptr;
+  const uint8_t* _right  = nullptr;
+  int _left_stride = 0, _right_stride = 0, _mem = SRRG2_MEM_HOST;
+  bool _has_raw    = false;
+  float* _dev_out  = nullptr;
+  int _dev_out_stride = 0;
+  srrg2_dense_stereo_result _result{};
+  std::vector<float> _disparity;
+};
+
 // ---- binary descriptor database: the matching half of MultiLoopDetectorHBST_ --------------------------------------
 // (S/registration/loop_detector/multi_loop_detector_hbst_impl.cpp:41-197; it stands where the reference keeps its
 // srrg_hbst::BinaryTree256<uint64_t>).  Exact, exhaustive matching on the device; semantics: srrg2_slam_amd.h.

@@ -93,3 +93,10 @@ def MeasurementAdaptorStereoFeatures(params=None, stereo=None, camera=None):
     from .adaptors import MeasurementAdaptorStereoFeatures as _A
 
     return _A(params, stereo, camera)
+
+
+def MeasurementAdaptorStereoDense(stereo=None, camera=None):
+    """Rectified pair of 8-bit images -> per-pixel disparity -> the depth adaptor's scene, on the device; see ``adaptors``."""
+    from .adaptors import MeasurementAdaptorStereoDense as _A
+
+    return _A(stereo, camera)

@@ -262,6 +262,22 @@ class StereoParams(C.Structure):
                 ("max_distance", C.c_int32), ("cross_check", C.c_int32), ("subpixel", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DenseStereoParams(C.Structure):
+    """srrg2_dense_stereo_params"""
+    _fields_ = [("baseline", C.c_float), ("min_disparity", C.c_int32), ("max_disparity", C.c_int32), ("paths", C.c_int32),
+                ("p1", C.c_int32), ("p2", C.c_int32), ("uniqueness_ratio", C.c_int32), ("lr_check", C.c_int32),
+                ("lr_tolerance", C.c_int32), ("subpixel", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DenseStereoResult(C.Structure):
+    """srrg2_dense_stereo_result"""
+    _fields_ = [("status", C.c_int32), ("num_pixels", C.c_int32), ("num_evaluated", C.c_int32), ("num_unique", C.c_int32),
+                ("num_consistent", C.c_int32), ("num_in_range", C.c_int32), ("num_valid", C.c_int32), ("scene_size", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class StereoMatch(C.Structure):
     """srrg2_stereo_match"""
     _fields_ = [("left_pixel", C.c_int32), ("right_pixel", C.c_int32), ("distance", C.c_int32), ("disparity", C.c_float)]

@@ -88,6 +88,12 @@ def lib():
                                                      C.POINTER(abi.DepthAdaptorParams), C.POINTER(abi.FeatureParams),
                                                      C.POINTER(abi.StereoParams), C.POINTER(abi.Keypoint), C.c_int,
                                                      C.POINTER(abi.StereoMatch), C.c_int, C.POINTER(abi.StereoResult)]
+        # srrg2_adapt_stereo_dense (adaptors.MeasurementAdaptorStereoDense)
+        _LIB.srrg2_adapt_default_dense_stereo_params.argtypes = [C.POINTER(abi.DenseStereoParams)]
+        _LIB.srrg2_adapt_default_dense_stereo_params.restype = None
+        _LIB.srrg2_adapt_stereo_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                  C.POINTER(abi.DepthAdaptorParams), C.POINTER(abi.DenseStereoParams), C.c_void_p,
+                                                  C.c_int, C.POINTER(abi.DenseStereoResult)]
         # srrg2_scene_track_features (mapping.FeatureTracker)
         _LIB.srrg2_track_default_params.argtypes = [C.POINTER(abi.TrackParams)]
         _LIB.srrg2_track_default_params.restype = None

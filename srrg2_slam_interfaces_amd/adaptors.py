@@ -11,11 +11,13 @@
                                    level-major, points at the keypoints' level-0 positions
 ``MeasurementAdaptorStereoFeatures`` rectified pair of 8-bit images -> compact 3-D scene of the left image's keypoints that were
                                    matched in the right image, triangulated (z = fx * baseline / disparity)
+``MeasurementAdaptorStereoDense``  rectified pair of 8-bit images -> a disparity per pixel (census cost, four-path semi-global
+                                   aggregation) -> depth -> the scene of MeasurementAdaptorDepthImage, organised or compact
 
 Method names follow ``RawDataPreprocessor_`` (S/raw_data_preprocessors/raw_data_preprocessor.h:13-88), snake_case:
 ``set_raw_data``, ``set_meas``, ``compute``, ``status``, ``reset``; ``status()`` is ERROR after ``set_raw_data`` until
 ``compute()`` (:67-72).  Thin marshalling only; product library only (the oracle has no adaptor: the parity target is
-tests/adaptor_restatement.py, tests/lidar_restatement.py, tests/features_restatement.py, tests/pyramid_restatement.py and tests/stereo_restatement.py).
+tests/adaptor_restatement.py, tests/lidar_restatement.py, tests/features_restatement.py, tests/pyramid_restatement.py, tests/stereo_restatement.py and tests/stereo_dense_restatement.py).
 """
 import ctypes as C
 
@@ -534,3 +536,92 @@ class MeasurementAdaptorStereoFeatures(_AdaptorBase):
     def matches(self):
         """(n,) structured array (left_pixel, right_pixel, distance, disparity) of the last compute(), in the scene's order"""
         return self._matches
+
+
+def default_dense_stereo_params():
+    """srrg2_dense_stereo_params: baseline 0 (set it), disparity 1 .. 64, paths 4, p1 8, p2 48, uniqueness_ratio 10, lr_check 1,
+    lr_tolerance 1, subpixel 1"""
+    from . import _capi
+
+    p = abi.DenseStereoParams()
+    _capi.lib().srrg2_adapt_default_dense_stereo_params(C.byref(p))
+    return p
+
+
+class MeasurementAdaptorStereoDense(_AdaptorBase):
+    """stereo: abi.DenseStereoParams (baseline, disparity range, paths, penalties, uniqueness, left-right check, sub-pixel);
+    camera: abi.DepthAdaptorParams, all of it (rows / cols are taken from numpy images): compute() leaves the scene that
+    MeasurementAdaptorDepthImage leaves for the depth fx * baseline / disparity with the left image as its intensity --
+    organised or compact, with normals by the gaps.  Without a measurement scene (``set_meas`` never called, or with None) only
+    the disparity image is computed."""
+
+    def __init__(self, stereo=None, camera=None):
+        super().__init__()
+        self.stereo = stereo or default_dense_stereo_params()
+        self.camera = camera or default_depth_params()
+        self._raw = self._right = None
+        self._disparity = None
+
+    def set_camera_matrix(self, K):
+        for i, v in enumerate(np.asarray(K, np.float32).reshape(9)):
+            self.camera.camera_matrix[i] = float(v)
+
+    def set_raw_data(self, left, right):
+        """the rectified pair (uint8): 2-D numpy arrays of one shape, or (device_pointer, row_stride_bytes) pairs (then
+        camera.rows / cols say the size)"""
+        raw = _image(left, abi.IMAGE_U8, "left")
+        other = _image(right, abi.IMAGE_U8, "right")
+        if raw[2] != abi.IMAGE_U8 or other[2] != abi.IMAGE_U8:
+            raise ValueError("left / right: uint8 images expected")
+        if other[4] != raw[4] or other[5] != raw[5]:
+            raise ValueError("right: same memory space and shape as the left image expected")
+        self._raw, self._right = raw, other
+        if raw[5] is not None:
+            self.camera.rows, self.camera.cols = raw[5]
+        self._status = abi.ADAPTOR_ERROR
+
+    def reset(self):
+        self._raw = self._right = None
+        self._status = abi.ADAPTOR_INITIALIZING
+        self.last = None
+        self._disparity = None
+
+    def compute(self, want_result=True, want_disparity=False):
+        """fills the measurement scene; returns the counters of srrg2_dense_stereo_result (dict), or None with
+        ``want_result=False`` -- an organised adapt whose disparity stays on the device then only queues its work.
+        want_disparity: True with numpy images (``disparity()`` then gives the (rows, cols) float32 image), or the float32 array
+        that shall receive it (its bytes between rows are left alone); with device images a (device_pointer, row_stride_bytes)
+        pair that receives it."""
+        if self._raw is None:
+            raise RuntimeError("%s::compute|raw data not set" % type(self).__name__)
+        out = abi.DenseStereoResult()
+        _, lptr, _, lstride, mem, _ = self._raw
+        _, rptr, _, rstride, _, _ = self._right
+        self._disparity = None
+        dptr, dstride = None, 0
+        if isinstance(want_disparity, tuple):
+            if mem != abi.MEM_DEVICE:
+                raise ValueError("want_disparity: a (device_pointer, stride) pair goes with device images")
+            dptr, dstride = C.c_void_p(int(want_disparity[0])), int(want_disparity[1])
+            self._disparity = want_disparity
+        elif isinstance(want_disparity, np.ndarray):  # the caller's own image, rows at its stride
+            a = want_disparity
+            if mem != abi.MEM_HOST or a.dtype != np.float32 or a.shape != (self.camera.rows, self.camera.cols) or \
+                    (a.size and a.strides[1] != 4):
+                raise ValueError("want_disparity: a (rows, cols) float32 array with unit column stride goes with numpy images")
+            self._disparity = a
+            dptr, dstride = C.c_void_p(a.ctypes.data), int(a.strides[0]) if a.shape[0] > 1 else 4 * self.camera.cols
+        elif want_disparity:
+            if mem != abi.MEM_HOST:
+                raise ValueError("want_disparity: device images need a (device_pointer, stride) pair")
+            self._disparity = np.zeros((self.camera.rows, self.camera.cols), np.float32)
+            dptr, dstride = C.c_void_p(self._disparity.ctypes.data), 4 * self.camera.cols
+        self._check(self._lib.srrg2_adapt_stereo_dense(None if self._meas is None else self._meas._h, lptr, lstride, rptr, rstride,
+                                                       mem, C.byref(self.camera), C.byref(self.stereo), dptr, dstride,
+                                                       C.byref(out) if want_result else None))
+        return self._finish(out, want_result)
+
+    def disparity(self):
+        """the disparity image of the last compute() that asked for it: a (rows, cols) float32 array, 0 where a pixel has none
+        (or the device pair that was handed in); None otherwise"""
+        return self._disparity

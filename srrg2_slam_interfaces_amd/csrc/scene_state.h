@@ -71,6 +71,16 @@ struct srrg2_scene {
   srrg2amd::DevBuf<unsigned long long> st_best[2];
   srrg2amd::DevBuf<srrg2_stereo_match> st_match, st_match_out;
   srrg2amd::DevBuf<float> st_z;
+  // adapt_stereo_dense (stereo_dense.hip): both images' census words [left, right][rows*cols]; the aggregated cost volume S,
+  // [row][col][d] over the processed rectangle, 16 bits per element; per rectangle pixel its best-disparity record (index |
+  // unique << 16) and its sub-pixel disparity; per row of the rectangle and right-image column the diagonal's best index; per
+  // image pixel the depth Z the depth adaptor then reads, the flag byte the counters are summed from and (a host disparity_out
+  // only) the disparity; the three counters
+  srrg2amd::DevBuf<unsigned long long> sd_census;
+  srrg2amd::DevBuf<unsigned short> sd_vol, sd_right;
+  srrg2amd::DevBuf<int> sd_best, sd_counts;
+  srrg2amd::DevBuf<float> sd_sub, sd_z, sd_disp;
+  srrg2amd::DevBuf<unsigned char> sd_flags;
   // adapt_image_features_pyramid (pyramid.hip): levels 1 .. of the image at pitches that are multiples of 4; the pipeline scratch
   // of ALL levels, each array one block with a slice per level (score / box padded to whole tiles, maxima flags, tie ranks, keep
   // flags, scan sums, counters); per kept keypoint its level pixel and its record; the pinned mirror of the levels' counters
@@ -101,6 +111,7 @@ struct srrg2_scene {
   srrg2amd::PinnedBuf<int> scalars;   // pinned host mirror of dscalars
   // device: [1] num_merged, [2] error flag, [3] duplicates seen, [4] ncorr (merge); [0] Valid, [1] in view, [2] scan total (clip);
   // [8] in range, [9] Valid (adapt)
+  // (host mirror only) [12] evaluated, [13] unique, [14] consistent (adapt_stereo_dense)
   srrg2amd::DevBuf<int> dscalars;
   // The ordering is what this destructor is for: the stream retires before any buffer above is freed (the members free
   // themselves after this body).  A new scratch buffer is one member line and nothing else.
