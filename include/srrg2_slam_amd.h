@@ -1254,6 +1254,83 @@ int srrg2_adapt_stereo_dense(srrg2_scene_h dst /* dim 3; may be NULL if disparit
                              float* disparity_out /* rows x cols, in `mem`, may be NULL */, int disparity_row_stride_bytes,
                              srrg2_dense_stereo_result* out /* may be NULL */);
 
+/* Rectification: lens undistortion and stereo rectification of raw images on the device -- the stage in front of the image
+ * adaptors above, which all assume an ideal pinhole image (the stereo calls: a rectified pair).  No reference counterpart;
+ * DESIGN.md section 4 "Rectification" is the contract, tests/rectify_restatement.py restates it and the library gives the same
+ * bits.  A rectifier holds one camera and one target: a map with one entry per pixel of the target, built on the device.
+ *   model     float64 throughout.  Pixel (r, c) of the target, integer coordinates being pixel centres:
+ *               x = (c - cx') / fx', y = (r - cy') / fy';  (X, Y, W) = R^T (x, y, 1), each as (a x + b y) + c;
+ *               xn = X / W, yn = Y / W;  r2 = xn xn + yn yn;
+ *               num = 1 + r2 (k1 + r2 (k2 + r2 k3)), den = 1 + r2 (k4 + r2 (k5 + r2 k6)), rad = num / den;  xy = xn yn;
+ *               xd = xn rad + ((2 p1) xy + p2 (r2 + 2 (xn xn))),  yd = yn rad + (p1 (r2 + 2 (yn yn)) + (2 p2) xy);
+ *               u = fx xd + cx, v = fy yd + cy;  U = floor(u 256 + 0.5), V = floor(v 256 + 0.5)
+ *             (Brown-Conrady with the rational denominator, OpenCV's order of the coefficients; R: X_rect = R X_src).
+ *   map       entry (U, V), int32 with 8 fractional bits, valid iff W > 0, den > 0, u and v finite, 0 <= U <= 256 (src_cols - 1)
+ *             and 0 <= V <= 256 (src_rows - 1); otherwise both words are INT32_MIN.
+ *   U8        bilinear, the pyramid's formula: x0 = U >> 8, x1 = min(x0 + 1, src_cols - 1), fx = U & 255, rows likewise;
+ *             (I00 (256-fx)(256-fy) + I01 fx (256-fy) + I10 (256-fx) fy + I11 fx fy + 32768) >> 16.  Invalid entry: `border`.
+ *   U16, F32  depth images, never blended: the pixel ((V + 128) >> 8, (U + 128) >> 8) copied bit for bit (NaN payloads
+ *             survive).  Invalid entry: 0 (U16), the quiet NaN 0x7fc00000 (F32).  A rotation that is not exactly the identity:
+ *             SRRG2_E_UNSUPPORTED (z along the optical axis would change).
+ *   dst       dst_rows x dst_cols at its stride; bytes between rows are never written.  Zero pixels: accepted, nothing written.
+ *   waits     order_on != NULL and dst in device memory: the work is queued on that scene's stream and the call returns; a
+ *             following srrg2_adapt_* on that scene with SRRG2_MEM_DEVICE images is ordered behind it (a pageable host source
+ *             is consumed before the call returns, as for any upload).  order_on == NULL, or a host destination: the work runs on
+ *             the rectifier's stream and the call returns when dst is complete.  srrg2_rectifier_destroy (and _set) wait for
+ *             work queued with the handle's map.
+ *   refused   dst untouched, nothing read from src.  SRRG2_E_INVALID: a null handle, params or image of more than zero pixels;
+ *             a handle without srrg2_rectifier_set; a shape < 0 or rows*cols beyond int32; a stride below a row or misaligned (or
+ *             such a pointer); bad mem or type; border outside 0 .. 255; fx, fy, fx', fy' zero; any parameter that is not
+ *             finite; order_on on another device; the pair: targets of different shape, one handle twice.  SRRG2_E_UNSUPPORTED:
+ *             skew in either camera matrix; a source side above 4194304 (U would leave int32); U16 / F32 under a rotation.
+ *             srrg2_rectifier_set checks its parameters before its handle.
+ * Not built: the fisheye (equidistant) model -- it needs atan, which is not bit-reproducible between hosts and the device; the
+ * scaled / cropped target of OpenCV's alpha (pass any new_camera_matrix instead). */
+typedef struct srrg2_rectifier_s* srrg2_rectifier_h;
+typedef struct srrg2_rectifier_params {
+  double  camera_matrix[9];     /* row-major K of the source: fx, fy finite and non-zero; K[0][1] != 0 -> SRRG2_E_UNSUPPORTED */
+  double  distortion[8];        /* k1, k2, p1, p2, k3, k4, k5, k6; all zero = none */
+  double  rotation[9];          /* row-major R, X_rect = R X_src; identity = plain undistortion */
+  double  new_camera_matrix[9]; /* row-major K' of the target: fx', fy', cx', cy' as above */
+  int32_t src_rows, src_cols, dst_rows, dst_cols;
+} srrg2_rectifier_params;
+typedef struct srrg2_rectifier_info {
+  int32_t num_pixels;           /* dst_rows * dst_cols */
+  int32_t num_valid;            /* entries that are valid */
+  int32_t first_row, last_row;  /* the first and last target row, and */
+  int32_t first_col, last_col;  /* column, that hold a valid entry; -1 when none does */
+} srrg2_rectifier_info;
+/* a rectifier on `device`: its own non-blocking stream, its map in device memory */
+int srrg2_rectifier_create(int device, srrg2_rectifier_h* out);
+int srrg2_rectifier_destroy(srrg2_rectifier_h h);
+/* zeros, identity rotation */
+void srrg2_rectifier_default_params(srrg2_rectifier_params* p);
+/* builds the map on the device (one thread per target pixel); one wait */
+int srrg2_rectifier_set(srrg2_rectifier_h h, const srrg2_rectifier_params* p, srrg2_rectifier_info* info_out /* may be NULL */);
+/* the map on the host: dst_rows x dst_cols entries (U, V), row-major; capacity in int32 words */
+int srrg2_rectifier_get_map(srrg2_rectifier_h h, int32_t* uv_out, int64_t capacity);
+/* writes the target's camera matrix (as float), dst_rows and dst_cols into an adaptor's params; nothing else of them */
+int srrg2_rectifier_camera(srrg2_rectifier_h h, srrg2_depth_adaptor_params* cam);
+/* src: src_rows x src_cols of `type` (srrg2_image_type) in src_mem; dst: dst_rows x dst_cols of the same type in dst_mem */
+int srrg2_rectify_image(srrg2_rectifier_h h, srrg2_scene_h order_on /* may be NULL */, const void* src, int type,
+                        int src_row_stride_bytes, int src_mem, void* dst, int dst_row_stride_bytes, int dst_mem,
+                        int border /* 0 .. 255, U8 only */);
+/* both U8 images of a stereo pair in ONE launch; the two targets have one shape (the sources need not) */
+int srrg2_rectify_pair(srrg2_rectifier_h left_h, srrg2_rectifier_h right_h, srrg2_scene_h order_on /* may be NULL */,
+                       const void* left, int left_row_stride_bytes, const void* right, int right_row_stride_bytes, int mem,
+                       void* dst_left, int dst_left_row_stride_bytes, void* dst_right, int dst_right_row_stride_bytes,
+                       int dst_mem, int border);
+/* Stereo calibration -> the two rectifying rotations; host only, float64, + - * / sqrt alone (bit for bit against the
+ * restatement).  KL, KR: row-major camera matrices; R, t: X_right = R X_left + t.
+ *   c = -R^T t (the right camera's centre in the left frame), baseline = |c|, e1 = c / |c|;
+ *   zm = ((0,0,1) + row 3 of R) / 2;  e2 = (zm x e1) / |zm x e1|;  e3 = e1 x e2;  R1 = rows e1, e2, e3;  R2 = R1 R^T;
+ *   Knew: fx' = fy' = (fyL + fyR) / 2, cx' = (cxL + cxR) / 2, cy' = (cyL + cyR) / 2.
+ * The right camera then sits at +baseline along the rectified x axis, the convention of srrg2_adapt_stereo_dense.  Sums of
+ * three products are (a + b) + c.  |c| = 0 or |zm x e1| = 0 (or an input that is not finite): SRRG2_E_INVALID.  Every output
+ * may be NULL. */
+int srrg2_stereo_rectify(const double* KL /* 9 */, const double* KR /* 9 */, const double* R /* 9 */, const double* t /* 3 */,
+                         double* R1_out /* 9 */, double* R2_out /* 9 */, double* Knew_out /* 9 */, double* baseline_out);
+
 /* Feature tracking: which keypoint of the measurement is which landmark of the clipped local map -- the per-frame data
  * association of a visual tracker, a projective window plus the Hamming distance of the 256-bit descriptors.  The reference
  * declares the slot and leaves it empty (CorrespondenceFinder_::compute() is pure virtual, S/registration/correspondence_finder.h:56;

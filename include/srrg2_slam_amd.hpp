@@ -1126,6 +1126,87 @@ private:
   std::vector<float> _disparity;
 };
 
+// ---- rectification: lens undistortion and stereo rectification in front of the image adaptors ----------------------------
+// (srrg2_rectifier_*, srrg2_rectify_image / _pair, srrg2_stereo_rectify; no reference counterpart, semantics: srrg2_slam_amd.h)
+//   ImageRectifier   one camera and one target: params (camera_matrix, distortion, rotation, new_camera_matrix, shapes) -> set()
+//                    builds the map on the device; rectify() remaps an image through it.  With order_on = scene.handle() and a
+//                    device destination the call only queues on that scene's stream: the adaptor that then fills the scene from
+//                    the rectified device image runs behind it without a host wait.
+//   StereoRectifier  two of them set from a calibration (KL, KR, R, t with X_right = R X_left + t); rectify() remaps both images
+//                    in one launch.  baseline goes into srrg2_dense_stereo_params, camera() into the adaptor's camera.
+class ImageRectifier {
+public:
+  srrg2_rectifier_params params;
+  explicit ImageRectifier(int device = 0) {
+    srrg2_rectifier_default_params(&params);
+    check(srrg2_rectifier_create(device, &_h));
+  }
+  ~ImageRectifier() { srrg2_rectifier_destroy(_h); }  // (waits for work queued with this map)
+  ImageRectifier(const ImageRectifier&)            = delete;
+  ImageRectifier& operator=(const ImageRectifier&) = delete;
+  // builds the map from `params`; the counts of the map
+  const srrg2_rectifier_info& set() {
+    check(srrg2_rectifier_set(_h, &params, &_info));
+    return _info;
+  }
+  const srrg2_rectifier_info& info() const { return _info; }
+  // dst_rows x dst_cols entries (U, V) in 1/256 source pixel, INT32_MIN twice = invalid
+  std::vector<int32_t> map() const {
+    std::vector<int32_t> uv((size_t) 2 * (size_t) params.dst_rows * (size_t) params.dst_cols);
+    check(srrg2_rectifier_get_map(_h, uv.empty() ? nullptr : uv.data(), (int64_t) uv.size()));
+    return uv;
+  }
+  // the target's camera matrix, rows and cols into an adaptor's camera params
+  void camera(srrg2_depth_adaptor_params& cam) const { check(srrg2_rectifier_camera(_h, &cam)); }
+  // src: src_rows x src_cols of `type` (SRRG2_IMAGE_U8 / U16 / F32); dst: dst_rows x dst_cols of the same type; strides in bytes
+  void rectify(const void* src, int type, int src_row_stride_bytes, void* dst, int dst_row_stride_bytes, int src_mem = SRRG2_MEM_HOST,
+               int dst_mem = SRRG2_MEM_HOST, srrg2_scene_h order_on = nullptr, int border = 0) {
+    check(srrg2_rectify_image(_h, order_on, src, type, src_row_stride_bytes, src_mem, dst, dst_row_stride_bytes, dst_mem, border));
+  }
+  srrg2_rectifier_h handle() const { return _h; }
+
+private:
+  srrg2_rectifier_h _h = nullptr;
+  srrg2_rectifier_info _info{};
+};
+
+class StereoRectifier {
+public:
+  ImageRectifier left, right;
+  double R1[9] = {0}, R2[9] = {0}, new_camera_matrix[9] = {0}, baseline = 0.0;
+  explicit StereoRectifier(int device = 0) : left(device), right(device) {}
+  // the rotations and the shared target camera of a calibration alone (host only)
+  static void rotations(const double* KL, const double* KR, const double* R, const double* t, double* R1_out, double* R2_out,
+                        double* Knew_out, double* baseline_out) {
+    check(srrg2_stereo_rectify(KL, KR, R, t, R1_out, R2_out, Knew_out, baseline_out));
+  }
+  // distortion: 8 coefficients per camera; both sources of one shape, both targets dst_rows x dst_cols under the shared camera
+  void setCalibration(const double* KL, const double* dist_left, const double* KR, const double* dist_right, const double* R,
+                      const double* t, int src_rows, int src_cols, int dst_rows, int dst_cols) {
+    rotations(KL, KR, R, t, R1, R2, new_camera_matrix, &baseline);
+    fill(left.params, KL, dist_left, R1, src_rows, src_cols, dst_rows, dst_cols);
+    fill(right.params, KR, dist_right, R2, src_rows, src_cols, dst_rows, dst_cols);
+    left.set();
+    right.set();
+  }
+  void camera(srrg2_depth_adaptor_params& cam) const { left.camera(cam); }
+  // both U8 images in one launch; sources in `mem`, destinations in `dst_mem`
+  void rectify(const uint8_t* left_src, int left_row_stride_bytes, const uint8_t* right_src, int right_row_stride_bytes, uint8_t* left_dst,
+               int left_dst_row_stride_bytes, uint8_t* right_dst, int right_dst_row_stride_bytes, int mem = SRRG2_MEM_HOST,
+               int dst_mem = SRRG2_MEM_HOST, srrg2_scene_h order_on = nullptr, int border = 0) {
+    check(srrg2_rectify_pair(left.handle(), right.handle(), order_on, left_src, left_row_stride_bytes, right_src, right_row_stride_bytes,
+                             mem, left_dst, left_dst_row_stride_bytes, right_dst, right_dst_row_stride_bytes, dst_mem, border));
+  }
+
+private:
+  void fill(srrg2_rectifier_params& p, const double* K, const double* dist, const double* R, int src_rows, int src_cols, int dst_rows,
+            int dst_cols) const {
+    for (int i = 0; i < 9; ++i) p.camera_matrix[i] = K[i], p.rotation[i] = R[i], p.new_camera_matrix[i] = new_camera_matrix[i];
+    for (int i = 0; i < 8; ++i) p.distortion[i] = dist ? dist[i] : 0.0;
+    p.src_rows = src_rows, p.src_cols = src_cols, p.dst_rows = dst_rows, p.dst_cols = dst_cols;
+  }
+};
+
 // ---- binary descriptor database: the matching half of MultiLoopDetectorHBST_ --------------------------------------
 // (S/registration/loop_detector/multi_loop_detector_hbst_impl.cpp:41-197; it stands where the reference keeps its
 // srrg_hbst::BinaryTree256<uint64_t>).  Exact, exhaustive matching on the device; semantics: srrg2_slam_amd.h.

@@ -100,3 +100,17 @@ def MeasurementAdaptorStereoDense(stereo=None, camera=None):
     from .adaptors import MeasurementAdaptorStereoDense as _A
 
     return _A(stereo, camera)
+
+
+def ImageRectifier(device=0):
+    """Lens undistortion / rectification of raw images on the device, the stage in front of the image adaptors; see ``rectify``."""
+    from .rectify import ImageRectifier as _R
+
+    return _R(device)
+
+
+def StereoRectifier(device=0):
+    """Two ``ImageRectifier``s set from a stereo calibration; both images of a pair rectified in one launch; see ``rectify``."""
+    from .rectify import StereoRectifier as _R
+
+    return _R(device)

@@ -278,6 +278,22 @@ class DenseStereoResult(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RectifierParams(C.Structure):
+    """srrg2_rectifier_params"""
+    _fields_ = [("camera_matrix", C.c_double * 9), ("distortion", C.c_double * 8), ("rotation", C.c_double * 9),
+                ("new_camera_matrix", C.c_double * 9), ("src_rows", C.c_int32), ("src_cols", C.c_int32), ("dst_rows", C.c_int32),
+                ("dst_cols", C.c_int32)]
+
+
+class RectifierInfo(C.Structure):
+    """srrg2_rectifier_info"""
+    _fields_ = [("num_pixels", C.c_int32), ("num_valid", C.c_int32), ("first_row", C.c_int32), ("last_row", C.c_int32),
+                ("first_col", C.c_int32), ("last_col", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class StereoMatch(C.Structure):
     """srrg2_stereo_match"""
     _fields_ = [("left_pixel", C.c_int32), ("right_pixel", C.c_int32), ("distance", C.c_int32), ("disparity", C.c_float)]

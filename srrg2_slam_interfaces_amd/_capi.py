@@ -94,6 +94,20 @@ def lib():
         _LIB.srrg2_adapt_stereo_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                                   C.POINTER(abi.DepthAdaptorParams), C.POINTER(abi.DenseStereoParams), C.c_void_p,
                                                   C.c_int, C.POINTER(abi.DenseStereoResult)]
+        # srrg2_rectifier_*, srrg2_rectify_*, srrg2_stereo_rectify (rectify.ImageRectifier / StereoRectifier)
+        dp = C.POINTER(C.c_double)
+        _LIB.srrg2_rectifier_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        _LIB.srrg2_rectifier_destroy.argtypes = [C.c_void_p]
+        _LIB.srrg2_rectifier_default_params.argtypes = [C.POINTER(abi.RectifierParams)]
+        _LIB.srrg2_rectifier_default_params.restype = None
+        _LIB.srrg2_rectifier_set.argtypes = [C.c_void_p, C.POINTER(abi.RectifierParams), C.POINTER(abi.RectifierInfo)]
+        _LIB.srrg2_rectifier_get_map.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int64]
+        _LIB.srrg2_rectifier_camera.argtypes = [C.c_void_p, C.POINTER(abi.DepthAdaptorParams)]
+        _LIB.srrg2_rectify_image.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_int, C.c_int]
+        _LIB.srrg2_rectify_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        _LIB.srrg2_stereo_rectify.argtypes = [dp, dp, dp, dp, dp, dp, dp, dp]
         # srrg2_scene_track_features (mapping.FeatureTracker)
         _LIB.srrg2_track_default_params.argtypes = [C.POINTER(abi.TrackParams)]
         _LIB.srrg2_track_default_params.restype = None
