@@ -486,12 +486,19 @@ __device__ __forceinline__ void transform_point(const float* T, const float4 p, 
 // returns the same (best, idx, pos); idx == NO_MATCH when the cube is empty.  lds: 4*TW + 8 ints per team.
 // STAGE: the front half alone -- the candidates are not tested but kept, in the order of the flattened list, in the team's
 // `stage` (LDS, STAGE_CAP entries), for a query that is not known yet (icp_step_fast_body: staged neighbours); widx returns
-// how many the ball holds, and nothing is kept of a ball that holds more than STAGE_CAP.
+// how many the ball holds, and nothing is kept of a ball that holds more than STAGE_CAP.  The set is what the rows of cells hold
+// that the ball touches; the candidates inside the ball itself are kept a second time, apart (`near`: up to STAGE_NEAR per team,
+// in any order, and their number, which the caller has set to zero).
 constexpr int STAGE_CAP = 64;
+constexpr int STAGE_NEAR = 5;
+struct StageNear {
+  int n[4];
+  float4 f[4][STAGE_NEAR];
+};
 template <int DIM, int TW, bool STAGE = false>
 __device__ __forceinline__ void coop_scan(const GridDev& g, int lane, int* lds_wave, float sqx, float sqy, float sqz,
                                           int scx, int scy, int scz, int sr, float sr2, float& wbest, int& widx,
-                                          int& wpos, float& wexcl2, float4* stage = nullptr) {
+                                          int& wpos, float& wexcl2, float4* stage = nullptr, StageNear* near = nullptr) {
   constexpr int ROWS_PER_CHUNK = 2 * TW;
   const int lt   = lane & (TW - 1);
   const int team = lane / TW;
@@ -588,7 +595,14 @@ __device__ __forceinline__ void coop_scan(const GridDev& g, int lane, int* lds_w
         const int run = min(next, tend) - t;  // candidates of this row in my share: consecutive in memory
         if constexpr (STAGE) {
           if (staged + total <= STAGE_CAP)
-            for (int c = 0; c < run; ++c) stage[staged + t + c] = g.pts[j + c];
+            for (int c = 0; c < run; ++c) {
+              const float4 f        = g.pts[j + c];
+              stage[staged + t + c] = f;
+              if (!(cand_d2<DIM>(f, sqx, sqy, sqz) > sr2 * 1.000001f)) {  // inside the ball itself (a NaN distance stays in)
+                const int at = atomicAdd(&near->n[team], 1);
+                if (at < STAGE_NEAR) near->f[team][at] = f;
+              }
+            }
         } else {
           scan_range2<DIM>(g.pts, j, j + run, sqx, sqy, sqz, key, lb2);
         }
@@ -2107,11 +2121,11 @@ __global__ __launch_bounds__(256) void k_icp_step_tile(SliceDev S, const Problem
 // its end: one plain store each (atomics on shared words serialise and stretch a 12-us launch to 85 us).  Compiled out of the
 // product build.
 #ifdef SRRG2_PASS_TIMELINE
-#define PASS_TS_WGS 2048  // (every workgroup of a 100 k-point search pass at four lanes per point: 1564; the last two slots are the censuses')
+#define PASS_TS_WGS 2048  // (every workgroup of a 100 k-point search pass at four lanes per point: 1564; the last three slots are the censuses')
 __device__ unsigned long long g_pass_ts[16 * PASS_TS_WGS * 8];  // [epoch][workgroup (tile)][stamp]: plain stores, reduced on the host
 #define PASS_TS_ANY(epoch, k) /* (by lane 0 of any wave: the last writer wins) */                      \
   do {                                                                                                 \
-    if ((threadIdx.x & 63) == 0 && (epoch) >= 0 && (epoch) < 16 && blockIdx.y < PASS_TS_WGS - 2 && blockIdx.x == 0) \
+    if ((threadIdx.x & 63) == 0 && (epoch) >= 0 && (epoch) < 16 && blockIdx.y < PASS_TS_WGS - 3 && blockIdx.x == 0) \
       g_pass_ts[(((epoch) * PASS_TS_WGS) + blockIdx.y) * 8 + (k)] = wall_clock64();                            \
   } while (0)
 #define PASS_TS_W(epoch, k, dep) /* (inside wave_control: after `dep` has been computed) */             \
@@ -2124,7 +2138,7 @@ __device__ unsigned long long g_pass_ts[16 * PASS_TS_WGS * 8];  // [epoch][workg
   } while (0)
 #define PASS_TS(epoch, k)                                                                              \
   do {                                                                                                 \
-    if (threadIdx.x == 0 && (epoch) >= 0 && (epoch) < 16 && blockIdx.y < PASS_TS_WGS - 2 && blockIdx.x == 0)       \
+    if (threadIdx.x == 0 && (epoch) >= 0 && (epoch) < 16 && blockIdx.y < PASS_TS_WGS - 3 && blockIdx.x == 0)       \
       g_pass_ts[(((epoch) * PASS_TS_WGS) + blockIdx.y) * 8 + (k)] = wall_clock64();                            \
   } while (0)
 #else
@@ -2770,7 +2784,7 @@ extern "C" int srrg2_amd_debug_fused_fallbacks(unsigned long long* out, int rese
   } while (0)
 // ... and what became of the staged neighbours of the converged passes (icp_step_fast_body): [0] thin lanes staged, [1] staged and
 // decided, [2] staged and rejected: more than STAGE_CAP candidates, [3] ... the new query not covered, [4] certificates that failed
-// without having been staged, [5] waves with more than four thin lanes (nothing staged)
+// without having been staged, [5] waves with more than four thin lanes (whether their near-ties alone were then staged or not)
 __device__ unsigned long long g_stage_counts[6];
 extern "C" int srrg2_amd_debug_staged_neighbours(unsigned long long* out6, int reset) {
   if (out6 && hipMemcpyFromSymbol(out6, HIP_SYMBOL(g_stage_counts), 6 * sizeof(unsigned long long)) != hipSuccess) return -1;
@@ -2785,6 +2799,24 @@ extern "C" int srrg2_amd_debug_staged_neighbours(unsigned long long* out6, int r
     const unsigned long long n_ = (unsigned long long) (n);                        \
     if ((threadIdx.x & 63) == 0 && n_) atomicAdd(&g_stage_counts[k], n_);          \
   } while (0)
+// ... and of the decided points: [0] neighbour kept, [1] neighbour changed and served from the staged set (never: a changed neighbour
+// and its normal are fetched; none changes in a converged pass of C2, profiles/r13), [2] neighbour changed, fetched, [3] lanes staged
+// under the near-tie-only rule (a wave with more than four thin lanes, one to four of them thin without the motion term), [4] decided
+// by the owner alone, among the candidates inside its ball
+__device__ unsigned long long g_stage_winners[5];
+extern "C" int srrg2_amd_debug_staged_winners(unsigned long long* out5, int reset) {
+  if (out5 && hipMemcpyFromSymbol(out5, HIP_SYMBOL(g_stage_winners), 5 * sizeof(unsigned long long)) != hipSuccess) return -1;
+  if (reset) {
+    const unsigned long long zero[5] = {0, 0, 0, 0, 0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_stage_winners), zero, sizeof(zero)) != hipSuccess) return -1;
+  }
+  return 0;
+}
+#define STAGE_WIN(k, n) /* (n: wave-uniform) */                                    \
+  do {                                                                             \
+    const unsigned long long n_ = (unsigned long long) (n);                        \
+    if ((threadIdx.x & 63) == 0 && n_) atomicAdd(&g_stage_winners[k], n_);         \
+  } while (0)
 #else
 #define FUSED_STALL() do { } while (0)
 #define FUSED_FALLBACK_COUNT() do { } while (0)
@@ -2795,8 +2827,15 @@ extern "C" int srrg2_amd_debug_staged_neighbours(unsigned long long* out6, int r
     if ((threadIdx.x & 63) == 0 && n_ && S.fc.epoch >= 0 && S.fc.epoch < 16 && blockIdx.x == 0)                  \
       atomicAdd(&g_pass_ts[((size_t) S.fc.epoch * PASS_TS_WGS + PASS_TS_WGS - 2) * 8 + (k)], n_);                \
   } while (0)
+#define STAGE_WIN(k, n) /* (the five counts of srrg2_amd_debug_staged_winners, in the third census slot) */      \
+  do {                                                                                                           \
+    const unsigned long long n_ = (unsigned long long) (n);                                                      \
+    if ((threadIdx.x & 63) == 0 && n_ && S.fc.epoch >= 0 && S.fc.epoch < 16 && blockIdx.x == 0)                  \
+      atomicAdd(&g_pass_ts[((size_t) S.fc.epoch * PASS_TS_WGS + PASS_TS_WGS - 3) * 8 + (k)], n_);                \
+  } while (0)
 #else
 #define STAGE_COUNT(k, n) do { } while (0)
+#define STAGE_WIN(k, n) do { } while (0)
 #endif
 #endif
 // a lane's margin is thin -- its ball is staged -- when what is left of it is less than STAGE_THIN_A of the point's last step plus
@@ -2804,7 +2843,8 @@ extern "C" int srrg2_amd_debug_staged_neighbours(unsigned long long* out6, int r
 // shrinks by it): 2 covers every step no longer than the last one, the cells cover a step that grows.  C2, converged passes
 // (profiles/r12/r12_pass_timeline_thresholds.txt): 1e-4 cells stage 165 - 178 lanes per pass for the 9 - 15 that fail and the last
 // stager is done at 6.3 - 7.0 us, 1 us after the record; 1e-5 cells stage 24 - 38, done at 5.4 - 6.0 us, and still no failed
-// certificate was left unstaged.
+// certificate was left unstaged.  A wave with more than four thin lanes (the estimate still moves: the first converged pass)
+// drops the motion term and stages the lanes that are thin by the cells alone, if one to four are.
 #ifndef STAGE_THIN_A
 #define STAGE_THIN_A 2.0f
 #endif
@@ -3437,9 +3477,11 @@ __device__ __forceinline__ void icp_step_fast_body(const SliceDev& S, const Prob
   // (the row tables of the cooperative grid scans -- 64-lane scans need 264 ints, four 16-lane teams 4 x 72 -- or, when the
   // grid has cell neighbour lists, the wave's pool of cnl_search: never live together)
   // (... or, between the top of the kernel and the searches, the staged candidates of up to four thin-margin points -- below)
+  // (... and of each set the few that lie inside the point's ball: StageNear, in the slack the pool leaves)
   struct StageWave {
     int coop[288];
     float4 cand[4][STAGE_CAP];
+    StageNear near;
   };
   union FastWaveLds {
     CnlWave cnl;
@@ -3512,11 +3554,19 @@ __device__ __forceinline__ void icp_step_fast_body(const SliceDev& S, const Prob
   // point outside the set is farther than R from q0, hence farther than R - |q - q0| from q: the winner of the set is the nearest
   // neighbour when it is closer than that, and what is not decided this way -- not predicted, more than STAGE_CAP candidates, a step
   // that leaves the ball -- is searched as before.  The prediction is never a condition of correctness.
+  // The set is what the ROWS of cells that the ball touches hold, a few dozen candidates; the ball itself holds the neighbour, the
+  // point it ties with and seldom more.  A candidate farther than R from q0 is farther than R - |q - q0| from q, like every point
+  // outside the set: it can neither win nor be the runner-up of a decision.  So the scan that stages the set also keeps the
+  // candidates within R of q0 apart (StageWave::near, up to STAGE_NEAR), and the lane that owns the point decides among those
+  // ALONE, in a straight line: the team's pass over the whole set with its two cross-lane reductions -- some thirty dependent LDS
+  // round trips of a lone wave, ~2.3 us at the very tail of the launch (profiles/r13) -- is left to the sets whose ball holds more.
   constexpr bool STAGE = PPT == 1 && FUSED == 1 && !GATHER;
+  [[maybe_unused]] int st_near = -1;                // this lane owns a staged point: the team that holds its set
   [[maybe_unused]] unsigned long long st_mask = 0;  // the lanes whose ball is staged: team t holds the t-th of them
   [[maybe_unused]] int st_n = 0;                    // candidates in this lane's team's set (> STAGE_CAP: none kept)
   [[maybe_unused]] float st_R2 = 0.f;               // squared radius of this lane's ball
   [[maybe_unused]] float Tst[12];                   // the transform the balls were centred with
+  [[maybe_unused]] bool st_dec = false, st_own = false;  // (the builds that count: this lane's point was decided from its set, by its owner alone)
   [[maybe_unused]] auto stage_thin = [&](const unsigned* stale) {
     if (!__builtin_amdgcn_readfirstlane((int) stale[24])) return;
     float Tpp[12];
@@ -3537,14 +3587,20 @@ __device__ __forceinline__ void icp_step_fast_body(const SliceDev& S, const Prob
     const bool thin = inr[0] && finite3(p[0].x, p[0].y, p[0].z) && __float_as_int(pf[0].w) != NO_MATCH &&
                       R2 <= bound2_of(2, g.h) && pm[0] * 0.99999f - d0 * 1.00001f < STAGE_THIN_A * dlp + STAGE_THIN_B * g.h;
     unsigned long long m = __ballot(thin);
-    const int nthin      = __popcll(m);
+    int nthin            = __popcll(m);
     if (nthin == 0) return;
-    if (nthin > 4) {  // (a pass that still moves: it has the pooled search)
+    if (nthin > 4) {
+      // a pass that still moves: it has the pooled search for the margins its motion uses up.  Its true near-ties -- thin without
+      // the motion term -- fail whatever the step is and are few: they are staged if there are one to four of them
       STAGE_COUNT(5, 1);
-      return;
+      m     = __ballot(thin && pm[0] * 0.99999f - d0 * 1.00001f < STAGE_THIN_B * g.h);
+      nthin = __popcll(m);
+      if (nthin == 0 || nthin > 4) return;
+      STAGE_WIN(3, nthin);
     }
     st_mask = m;
     st_R2   = R2;
+    if ((m >> lane) & 1ull) st_near = __popcll(m & ((1ull << lane) - 1ull));
     int src[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -3559,10 +3615,13 @@ __device__ __forceinline__ void icp_step_fast_body(const SliceDev& S, const Prob
     const int scz = DIM == 3 ? cell_coord(sqz, g.oz, g.inv_h) : 0;
     float wbest, wexcl2;
     int wpos, count;
+    if ((lane & 15) == 0) fast_lds[wid].stage.near.n[team] = 0;  // (the scan's first LDS fence orders it before the candidates)
     coop_scan<DIM, 16, true>(g, lane, fast_lds[wid].stage.coop, sqx, sqy, sqz, scx, scy, scz, mine >= 0 ? 2 : -1, sball, wbest,
-                             count, wpos, wexcl2, fast_lds[wid].stage.cand[team]);
+                             count, wpos, wexcl2, fast_lds[wid].stage.cand[team], &fast_lds[wid].stage.near);
     st_n = mine >= 0 ? count : 0;
     STAGE_COUNT(0, nthin);
+    // (a ball that holds more than a team keeps: its owner must not take the candidates kept apart for the whole of it)
+    if ((lane & 15) == 0 && count > STAGE_CAP) fast_lds[wid].stage.near.n[team] = STAGE_NEAR + 1;
     PASS_TS_ANY(S.fc.epoch, 5);  // (staging done: the last wave that staged)
   };
   if constexpr (FUSED) {  // (the points are on their way: now the record, or the control step it still waits for)
@@ -3595,51 +3654,79 @@ __device__ __forceinline__ void icp_step_fast_body(const SliceDev& S, const Prob
         const unsigned long long due = st_mask & __ballot(open);
         STAGE_COUNT(4, __popcll(__ballot(open) & ~st_mask));
         if (due) {
-          int src[4];
-          unsigned long long m = st_mask;
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            src[t] = m ? __ffsll((long long) m) - 1 : -1;
-            m &= m - 1;
-          }
-          const int team = lane >> 4, lt = lane & 15;
-          const int mine = team == 0 ? src[0] : (team == 1 ? src[1] : (team == 2 ? src[2] : src[3]));
-          const int from = mine >= 0 ? mine : lane;
-          const float sqx = __shfl(qx, from), sqy = __shfl(qy, from), sqz = __shfl(qz, from);
-          const bool work = mine >= 0 && ((due >> (mine & 63)) & 1ull) && st_n <= STAGE_CAP;
-          unsigned long long key = NO_KEY;
-          float lb2 = INFINITY;
-          if (work) {
-            const float4* cand = fast_lds[wid].stage.cand[team];
-            for (int c = lt; c < st_n; c += 16) test_candidate2<DIM>(cand[c], sqx, sqy, sqz, true, key, lb2);
-          }
-          unsigned long long kmin = key;
-#pragma unroll
-          for (int off = 8; off >= 1; off >>= 1) {
-            const unsigned long long o = __shfl_xor(kmin, off);
-            kmin = o < kmin ? o : kmin;
-          }
-          float v = key == kmin ? lb2 : fminf(lb2, key_best(key));  // (the runner-up of the set, as coop_scan's)
-#pragma unroll
-          for (int off = 8; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off));
           bool decided = false, overflow = false;
+          // the owner accepts (key, runner-up) if no fixed point outside the ball can be as close
+          auto accept = [&](unsigned long long wk, float wv) {
+            float ax, ay, az;
+            transform_point<DIM>(Tst, p[k], ax, ay, az);
+            const float ex = qx - ax, ey = qy - ay, ez = qz - az;
+            const float dls = sqrtf((ex * ex + ey * ey) + ez * ez);
+            const float rin = sqrtf(st_R2) * 0.99999f - dls * 1.00001f;  // no fixed point outside the set is closer than this
+            if (key_idx(wk) != NO_MATCH && sqrtf(key_best(wk)) * 1.00001f < rin) {
+              sbest[k] = key_best(wk);
+              sidx[k]  = key_idx(wk);
+              sexcl[k] = sqrtf(fminf(wv, rin * rin)) * 0.99999f;
+              decided  = true;
+              st_dec   = true;
+            }
+          };
+          // a ball of a few candidates: its owner alone, among the ones kept apart.  What was left out of them is farther than
+          // rin from q: the same winner, and the same runner-up wherever it is below rin, which is all sexcl takes of it
+          bool quick = false;
+          if (open && st_near >= 0) {  // (its number and the candidates themselves: one LDS round trip)
+            const StageNear& near = fast_lds[wid].stage.near;
+            const int n_near      = near.n[st_near];
+            float4 nf[STAGE_NEAR];
 #pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            const unsigned long long rk_ = __shfl(kmin, 16 * t);
-            const float rv = __shfl(v, 16 * t);
-            const int rn   = __shfl(st_n, 16 * t);
-            if (lane == src[t] && open) {
-              float ax, ay, az;
-              transform_point<DIM>(Tst, p[k], ax, ay, az);
-              const float ex = qx - ax, ey = qy - ay, ez = qz - az;
-              const float dls = sqrtf((ex * ex + ey * ey) + ez * ez);
-              const float rin = sqrtf(st_R2) * 0.99999f - dls * 1.00001f;  // no fixed point outside the set is closer than this
-              overflow = rn > STAGE_CAP;
-              if (!overflow && key_idx(rk_) != NO_MATCH && sqrtf(key_best(rk_)) * 1.00001f < rin) {
-                sbest[k] = key_best(rk_);
-                sidx[k]  = key_idx(rk_);
-                sexcl[k] = sqrtf(fminf(rv, rin * rin)) * 0.99999f;
-                decided  = true;
+            for (int i = 0; i < STAGE_NEAR; ++i) nf[i] = near.f[st_near][i];
+            quick = n_near <= STAGE_NEAR;
+            if (quick) {
+              unsigned long long key = NO_KEY;
+              float lb2 = INFINITY;
+#pragma unroll
+              for (int i = 0; i < STAGE_NEAR; ++i) test_candidate2<DIM>(nf[i], qx, qy, qz, i < n_near, key, lb2);
+              accept(key, lb2);
+              st_own = decided;
+            }
+          }
+          STAGE_WIN(4, __popcll(__ballot(quick && decided)));
+          const unsigned long long due_team = due & ~__ballot(quick);
+          if (due_team) {
+            int src[4];
+            unsigned long long m = st_mask;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+              src[t] = m ? __ffsll((long long) m) - 1 : -1;
+              m &= m - 1;
+            }
+            const int team = lane >> 4, lt = lane & 15;
+            const int mine = team == 0 ? src[0] : (team == 1 ? src[1] : (team == 2 ? src[2] : src[3]));
+            const int from = mine >= 0 ? mine : lane;
+            const float sqx = __shfl(qx, from), sqy = __shfl(qy, from), sqz = __shfl(qz, from);
+            const bool work = mine >= 0 && ((due_team >> (mine & 63)) & 1ull) && st_n <= STAGE_CAP;
+            unsigned long long key = NO_KEY;
+            float lb2 = INFINITY;
+            if (work) {
+              const float4* cand = fast_lds[wid].stage.cand[team];
+              for (int c = lt; c < st_n; c += 16) test_candidate2<DIM>(cand[c], sqx, sqy, sqz, true, key, lb2);
+            }
+            unsigned long long kmin = key;
+#pragma unroll
+            for (int off = 8; off >= 1; off >>= 1) {
+              const unsigned long long o = __shfl_xor(kmin, off);
+              kmin = o < kmin ? o : kmin;
+            }
+            float v = key == kmin ? lb2 : fminf(lb2, key_best(key));  // (the runner-up of the set, as coop_scan's)
+#pragma unroll
+            for (int off = 8; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off));
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+              const unsigned long long rk_ = __shfl(kmin, 16 * t);
+              const float rv = __shfl(v, 16 * t);
+              const int rn   = __shfl(st_n, 16 * t);
+              if (lane == src[t] && open && !quick) {
+                overflow = rn > STAGE_CAP;
+                if (!overflow) accept(rk_, rv);
               }
             }
           }
@@ -3800,10 +3887,12 @@ __device__ __forceinline__ void icp_step_fast_body(const SliceDev& S, const Prob
       // ONE linearisation of all 64 lanes -- kept and newly found neighbours alike -- and one reduction.  A settled pass
       // still has a handful of near-ties to search for (C2: 8 - 15 of 100 000 points, profiles/r6e); as a second phase with
       // its own linearisation, wave reduction and atomics they kept ten lone waves busy ~4 us after their siblings.
+      [[maybe_unused]] int stamp_w = 0;
       if (__any(any_open)) {
         float sbest[PPT], sexcl[PPT];
         int sidx[PPT], spos[PPT];
         search_open(sbest, sidx, sexcl, spos);
+        if constexpr (STAGE) PASS_TS_ANY(S.fc.epoch, 4);  // (timeline: the searches of a wave with failed certificates are done)
         const bool open = open_ball2[0] >= 0.f;
         // (a near-tie searched again mostly finds the neighbour it had: coordinates, normal and position are in place)
         const bool same = open && sidx[0] != NO_MATCH && sidx[0] == __float_as_int(pf[0].w);
@@ -3826,9 +3915,20 @@ __device__ __forceinline__ void icp_step_fast_body(const SliceDev& S, const Prob
           d_best  = sbest[0];
           d_valid = true;
         }
+        if constexpr (STAGE) {  // (the census of the stall and the timeline builds)
+          STAGE_WIN(0, __popcll(__ballot(st_dec && same)));
+          STAGE_WIN(2, __popcll(__ballot(st_dec && !same)));
+          stamp_w = (__ballot(open && !same) ? 1 : 0) | (__ballot(st_own) ? 2 : 0);
+        }
       }
       linearize(std::true_type{}, acc, d_valid, p[0], pf[0], pn[0], pnm[0], d_qx, d_qy, d_qz, d_best);
       block_reduce_store_biased<4>(acc, S.partials, prob, tile, PPT);
+      // (timeline: a wave that changed a neighbour -- and fetched it -- stamps [6] behind the reduction, one with a point that its
+      // owner decided alone [7])
+      if constexpr (STAGE) {
+        if (stamp_w & 1) PASS_TS_ANY(S.fc.epoch, 6);
+        if (stamp_w & 2) PASS_TS_ANY(S.fc.epoch, 7);
+      }
       if constexpr (FUSED) PASS_TS(S.fc.epoch, 3);
       return;
     }

@@ -4,7 +4,10 @@
   SRRG2_AMD_LIB=srrg2_slam_interfaces_amd/lib/libsrrg2_slam_amd_timeline.so python tools/pass_timeline.py [n]
 Per launch epoch: first / last workgroup start, control step done, record seen (first / last workgroup), first / last end,
 in microseconds after the end of the previous launch (100 MHz constant-rate clock: 10 ns steps), and how many workgroups
-started only after the first one had ended: the launch's second round, workgroups that were not resident at its start."""
+started only after the first one had ended: the launch's second round, workgroups that were not resident at its start.
+Converged passes: the censuses of the failed certificates, of the staged neighbours and of the staged winners (kept / changed
+neighbours, near-tie-only staging, points decided by their owner alone), when the workgroups with a changed neighbour or an
+owner's decision end, and what the workgroups are that end more than 1 us after the median one."""
 import ctypes as C
 import os
 import sys
@@ -47,9 +50,10 @@ prev_end = None
 print("epoch | workgroups | start: first  last | control done | record seen: first  median  last | end: first  median  last | launch   [us after the end of the previous launch]")
 for e in range(16):
     used = ts[e, :, 0] > 0
-    used[WGS - 2:] = False  # (the last two slots hold the censuses)
+    used[WGS - 3:] = False  # (the last three slots hold the censuses)
     census = ts[e, WGS - 1, :7].copy()
     staged = ts[e, WGS - 2, :6].copy()
+    winners = ts[e, WGS - 3, :5].copy()
     if not used.any():
         continue
     st, ctl, seen, end = ts[e, used, 0], ts[e, 0, 1], ts[e, used, 2], ts[e, used, 3]
@@ -73,8 +77,23 @@ for e in range(16):
     if staged.any():
         print("      staged neighbours: %d thin lanes staged, %d decided, rejected %d (more than the cap) + %d (not covered), "
               "%d certificates failed unstaged, %d waves with more than four thin lanes" % tuple(staged))
+    if winners.any():
+        print("      staged winners: %d kept their neighbour, %d changed it and were served from the staged set, %d changed it and fetched; "
+              "%d lanes staged under the near-tie-only rule; %d decided by their owner alone" % tuple(winners))
     rest = used.copy()
     rest[0] = False  # (workgroup 0 keeps the control step's stamps in these slots)
+    # behind the reduction a wave that changed a neighbour (and fetched it) stamps slot 6, one with a point its owner decided alone slot 7
+    wend = ts[e, :, 3]
+    for slot, what in ((6, "a changed neighbour"), (7, "a point decided by its owner alone")):
+        ch = rest & (ts[e, :, slot] > 0) & (wend > 0)
+        if ch.any():
+            print("      workgroups with %s: %d, end first / median / last %s / %s / %s" % (
+                what, ch.sum(), f(wend[ch].min()), f(np.median(wend[ch])), f(wend[ch].max())))
+    tail = rest & (wend > np.median(end) + 100)  # (more than 1 us behind the median workgroup)
+    if tail.any():
+        print("      workgroups that end more than 1 us after the median: %d (first at %s), of them %d fetched a changed neighbour, "
+              "%d had a point decided by its owner alone, %d staged" % (tail.sum(), f(wend[tail].min()), (tail & (ts[e, :, 6] > 0)).sum(),
+                                                                        (tail & (ts[e, :, 7] > 0)).sum(), (tail & (ts[e, :, 5] > 0)).sum()))
     sdone = ts[e, rest, 5]
     sdone = sdone[sdone > 0]
     if len(sdone):
@@ -82,7 +101,11 @@ for e in range(16):
             len(sdone), f(sdone.min()), f(np.median(sdone)), f(sdone.max()), f(np.median(seen))))
     p2 = ts[e, used, 4]
     p2 = p2[p2 > 0]
-    if len(p2):
+    if len(p2) and staged.any():  # (a kernel that stages has no second phase: its waves with failed certificates stamp their searches' end)
+        print("      failed certificates settled (staged decisions and searches) in %d workgroups: first %s, median %s, last %s" % (
+            len(p2), f(p2.min()), f(np.median(p2)), f(p2.max())))
+        prev_end = end.max()
+    elif len(p2):
         print("      second phase (failed certificates) in %d workgroups, last one done at %s" % (len(p2), f(p2.max())))
         prev_end = max(end.max(), p2.max())
     else:
