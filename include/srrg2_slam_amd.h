@@ -1331,6 +1331,89 @@ int srrg2_rectify_pair(srrg2_rectifier_h left_h, srrg2_rectifier_h right_h, srrg
 int srrg2_stereo_rectify(const double* KL /* 9 */, const double* KR /* 9 */, const double* R /* 9 */, const double* t /* 3 */,
                          double* R1_out /* 9 */, double* R2_out /* 9 */, double* Knew_out /* 9 */, double* baseline_out);
 
+/* Occupancy grid: laser scans and the poses they were taken from -> which cells of a 2-D grid are free, occupied or never seen,
+ * on the device -- the map product of the 2-D laser pipeline (adapt_laser_scan, clip_scan, the aligner, merge, the SE(2) pose
+ * graph).  No reference counterpart; DESIGN.md section 4 "Occupancy grid" is the contract, tests/gridmap_restatement.py restates
+ * it and the library gives the same bits: behind the beam's end point everything is integer.
+ *   grid      cols x rows cells of `resolution` metres; origin = world position of the corner of cell (0, 0); cell (ix, iy) lives
+ *             at plane index iy*cols + ix, its centre is (ox + ((float) ix + 0.5f) res, oy + ((float) iy + 0.5f) res) in float32.
+ *             The state is two int32 planes, hits and misses.
+ *   beam      beam k with range r: the sensor-frame point b of srrg2_adapt_laser_scan (bearing angle_min + k angle_increment in
+ *             float64, dm::sincos, (float) c * r, (float) s * r); T = dm::se2_compose(robot_in_world, sensor_in_robot); end point
+ *             (T0 bx + T1 by) + T2, (T3 bx + T4 by) + T5 in float32; the ray starts at (T2, T5).
+ *   cell      u = floorf((x - ox) / resolution) in float32, ix = (int) u; likewise iy.  A u that is NaN or outside
+ *             [-2^30, 2^30) is never converted: a beam with such a start or end cell adds nothing (sides are at most 32768 and
+ *             rays at most 32767 cells, so such a beam is nowhere near the grid).
+ *   ray       (x0, y0) -> (x1, y1), dx = x1 - x0, dy = y1 - y0, n = max(|dx|, |dy|); step i = 0 .. n is the cell
+ *             (x0 + sgn(dx) ((2 i |dx| + n) / (2 n)), y0 + sgn(dy) ((2 i |dy| + n) / (2 n))), integer division, 32-bit (n <= 32767
+ *             keeps 2 n^2 + n inside int32; a beam with n > 32767 -- no rigid pose gives one -- adds nothing).  Steps 0 .. n-1
+ *             add `weight` to misses, step n adds `weight` to hits and not to misses; n = 0 is a hit in the sensor's own cell.
+ *             A cell outside the grid is skipped on its own: the ray may start outside, leave and re-enter.
+ *   classes   a finite range inside [range_min, range_max]: a return, traced as above.  A range above range_max (+inf too):
+ *             clear_beyond_max = 1 traces steps 0 .. n-1 towards the point at range_max as misses, no hit ("cleared only");
+ *             = 0 skips the beam.  NaN, -inf, <= 0 or below range_min: skipped.
+ *   counts    per beam, not per scan: a cell crossed by 300 beams of one scan gets 300 misses.  Integer adds commute: the
+ *             planes do not depend on scheduling, scan order or batch split, and a batch with weight +1 followed by the same
+ *             batch with -1 restores them bit for bit (take a scan out, put it back at its optimised pose).  No saturation: an
+ *             int32 plane wraps after 2^31 adds to one cell, about 2^31 / num_beams scans through it (1.9 million of 1 081 beams).
+ *   result    num_beams_total = num_scans * num_beams = num_returns + num_cleared_only + num_skipped (the classes above, whatever
+ *             the geometry); num_hits_in_grid / num_miss_updates: the adds this call made to the two planes.
+ *   render    per cell n = hits + misses: n < max(min_observations, 1), or a negative hits or misses (only a removal that was
+ *             never integrated leaves one): 255 = unknown; else (100 hits + n / 2) / n in 64-bit integers, 0 .. 100.
+ *   to_scene  every cell that renders into [occupied_percent, 100] becomes a point at its centre in a 2-D scene, in plane-index
+ *             order, without normals or features; srrg2_scene_global_indices(dst) gives the plane indices.  The scene aligns
+ *             like any other (set_fixed of its device arrays): scan-to-map tracking, relocalisation.
+ *   waits     every call runs on the grid's stream, in order.  srrg2_gridmap_integrate_scans with out == NULL only queues and
+ *             returns (host `ranges` / poses are consumed before it returns; device ones must stay untouched until a later call
+ *             of this handle has waited); with `out` it waits once.  The other calls return when their output is complete.
+ *   refused   every destination and the planes unchanged.  SRRG2_E_INVALID: a null handle, params or (where there is data) data
+ *             pointer; a handle without srrg2_gridmap_reset; rows or cols outside 0 .. 32768; a resolution that is not finite or
+ *             <= 0; an origin or sensor_in_robot that is not finite; num_scans or num_beams < 0; bad mem; a weight other than +1 /
+ *             -1; clear_beyond_max other than 0 / 1; the scan-model refusals of srrg2_scene_clip_scan (increment zero or not
+ *             finite, |angle_min| > 2 pi, |angle_increment| * num_beams beyond 2 pi plus one increment, !(range_min > 0),
+ *             !(range_max >= range_min)), except that num_beams = 0 is accepted; range_max / resolution (float32) beyond 32000 or
+ *             NaN; occupied_percent outside 0 .. 100; a stride below a row; a `dst` scene that is not 2-D or lives on another
+ *             device.  SRRG2_E_UNSUPPORTED: num_scans * num_beams beyond int32.  Parameters are checked before the handle.
+ *             num_scans = 0, num_beams = 0 and rows * cols = 0 are accepted and do nothing. */
+typedef struct srrg2_gridmap_s* srrg2_gridmap_h;
+typedef struct srrg2_gridmap_params {
+  int32_t rows, cols;   /* 0 .. 32768 each */
+  float   resolution;   /* metres per cell */
+  float   origin[2];    /* world position of the corner of cell (0, 0) */
+} srrg2_gridmap_params;
+typedef struct srrg2_gridmap_scan_params {
+  double  angle_min, angle_increment;   /* as srrg2_scan_adaptor_params: bearing of beam k = angle_min + k*angle_increment */
+  int32_t num_beams;
+  float   range_min, range_max;         /* a return lies inside, both inclusive */
+  float   sensor_in_robot[9];           /* SE(2), row-major 3x3 */
+  int32_t clear_beyond_max;             /* 1: a range above range_max clears the ray up to range_max; 0: it is skipped */
+} srrg2_gridmap_scan_params;
+typedef struct srrg2_gridmap_result {
+  int64_t num_beams_total, num_returns, num_cleared_only, num_skipped;
+  int64_t num_hits_in_grid, num_miss_updates;
+} srrg2_gridmap_result;
+/* a grid on `device`: its own non-blocking stream, its planes in device memory */
+int srrg2_gridmap_create(int device, srrg2_gridmap_h* out);
+int srrg2_gridmap_destroy(srrg2_gridmap_h h);
+/* an empty grid (rows = cols = 0) of 0.05 m cells at the origin */
+void srrg2_gridmap_default_params(srrg2_gridmap_params* p);
+/* identity sensor, range 0.05 .. 30 m (the scan adaptor's), clear_beyond_max = 1; bearings / num_beams (0) are the caller's */
+void srrg2_gridmap_default_scan_params(srrg2_gridmap_scan_params* p);
+/* allocates and zeroes both planes */
+int srrg2_gridmap_reset(srrg2_gridmap_h h, const srrg2_gridmap_params* p);
+/* ranges: num_scans x num_beams floats, robot_in_world: num_scans x 9 floats (SE(2), row-major), both in `mem` = SRRG2_MEM_HOST |
+ * SRRG2_MEM_DEVICE.  One upload, one kernel, whatever num_scans and num_beams are. */
+int srrg2_gridmap_integrate_scans(srrg2_gridmap_h h, const float* ranges, int num_scans, const float* robot_in_world, int mem,
+                                  const srrg2_gridmap_scan_params* p, int weight /* +1 | -1 */,
+                                  srrg2_gridmap_result* out /* may be NULL: queue only */);
+/* rows*cols words each, to `mem`; either pointer may be NULL */
+int srrg2_gridmap_get_counts(srrg2_gridmap_h h, int32_t* hits, int32_t* misses, int mem);
+/* the planes in device memory (valid until the next reset or destroy); waits for the grid's stream, as srrg2_scene_device_arrays */
+int srrg2_gridmap_device_arrays(srrg2_gridmap_h h, const int32_t** hits, const int32_t** misses);
+/* rows x cols bytes (0 .. 100, 255 = unknown) to dst in `mem`; bytes between rows are never written */
+int srrg2_gridmap_render(srrg2_gridmap_h h, int min_observations, uint8_t* dst, int row_stride_bytes, int mem);
+int srrg2_gridmap_to_scene(srrg2_gridmap_h h, int min_observations, int occupied_percent /* 0 .. 100 */, srrg2_scene_h dst);
+
 /* Feature tracking: which keypoint of the measurement is which landmark of the clipped local map -- the per-frame data
  * association of a visual tracker, a projective window plus the Hamming distance of the 256-bit descriptors.  The reference
  * declares the slot and leaves it empty (CorrespondenceFinder_::compute() is pure virtual, S/registration/correspondence_finder.h:56;

@@ -1207,6 +1207,64 @@ private:
   }
 };
 
+// ---- occupancy grid: laser scans and their poses -> free / occupied / unknown cells ---------------------------------------
+// (srrg2_gridmap_*; no reference counterpart, semantics: srrg2_slam_amd.h)
+//   GridMap   reset() allocates the two count planes from `params`; integrate() traces a batch of scans taken with the scanner of
+//             `scan` from the given poses (one scan = the per-frame update), remove() takes the same scans out again bit for bit
+//             -- after a pose-graph optimisation only the scans whose pose moved are re-drawn; counts() / render() read the map;
+//             toScene() exports the occupied cells as a 2-D scene an aligner takes as it is.
+class GridMap {
+public:
+  srrg2_gridmap_params params;
+  srrg2_gridmap_scan_params scan;
+  explicit GridMap(int device = 0) {
+    srrg2_gridmap_default_params(&params);
+    srrg2_gridmap_default_scan_params(&scan);
+    check(srrg2_gridmap_create(device, &_h));
+  }
+  ~GridMap() { srrg2_gridmap_destroy(_h); }  // (waits for queued work)
+  GridMap(const GridMap&)            = delete;
+  GridMap& operator=(const GridMap&) = delete;
+  // a new, empty map from `params`
+  void reset() { check(srrg2_gridmap_reset(_h, &params)); }
+  // ranges: num_scans x scan.num_beams, robot_in_world: num_scans x 9 (row-major SE(2)), both in `mem`
+  const srrg2_gridmap_result& integrate(const float* ranges, int num_scans, const float* robot_in_world, int mem = SRRG2_MEM_HOST,
+                                        int weight = 1) {
+    check(srrg2_gridmap_integrate_scans(_h, ranges, num_scans, robot_in_world, mem, &scan, weight, &_result));
+    return _result;
+  }
+  const srrg2_gridmap_result& remove(const float* ranges, int num_scans, const float* robot_in_world, int mem = SRRG2_MEM_HOST) {
+    return integrate(ranges, num_scans, robot_in_world, mem, -1);
+  }
+  // queues the work on the grid's stream and returns without waiting; no counters
+  void integrateQueued(const float* ranges, int num_scans, const float* robot_in_world, int mem = SRRG2_MEM_HOST, int weight = 1) {
+    check(srrg2_gridmap_integrate_scans(_h, ranges, num_scans, robot_in_world, mem, &scan, weight, nullptr));
+  }
+  const srrg2_gridmap_result& result() const { return _result; }
+  size_t cells() const { return (size_t) params.rows * (size_t) params.cols; }
+  // rows*cols words each, plane index iy*cols + ix
+  void counts(std::vector<int32_t>& hits, std::vector<int32_t>& misses) const {
+    hits.assign(cells(), 0);
+    misses.assign(cells(), 0);
+    check(srrg2_gridmap_get_counts(_h, hits.data(), misses.data(), SRRG2_MEM_HOST));
+  }
+  // rows x cols bytes: 0 .. 100, 255 = unknown
+  std::vector<uint8_t> render(int min_observations = 1) const {
+    std::vector<uint8_t> img(cells());
+    check(srrg2_gridmap_render(_h, min_observations, img.data(), params.cols, SRRG2_MEM_HOST));
+    return img;
+  }
+  // the cells that render into [occupied_percent, 100] as points at their centres; dst.globalIndices() are the plane indices
+  void toScene(Scene<2>& dst, int min_observations = 1, int occupied_percent = 50) const {
+    check(srrg2_gridmap_to_scene(_h, min_observations, occupied_percent, dst.handle()));
+  }
+  srrg2_gridmap_h handle() const { return _h; }
+
+private:
+  srrg2_gridmap_h _h = nullptr;
+  srrg2_gridmap_result _result{};
+};
+
 // ---- binary descriptor database: the matching half of MultiLoopDetectorHBST_ --------------------------------------
 // (S/registration/loop_detector/multi_loop_detector_hbst_impl.cpp:41-197; it stands where the reference keeps its
 // srrg_hbst::BinaryTree256<uint64_t>).  Exact, exhaustive matching on the device; semantics: srrg2_slam_amd.h.

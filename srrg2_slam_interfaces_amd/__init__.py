@@ -109,6 +109,14 @@ def ImageRectifier(device=0):
     return _R(device)
 
 
+def OccupancyGrid(device=0):
+    """Occupancy grid map from laser scans and poses on the device: integrate / remove scans, read the counts, render the
+    image, export the occupied cells as a 2-D scene; see ``gridmap``."""
+    from .gridmap import OccupancyGrid as _G
+
+    return _G(device)
+
+
 def StereoRectifier(device=0):
     """Two ``ImageRectifier``s set from a stereo calibration; both images of a pair rectified in one launch; see ``rectify``."""
     from .rectify import StereoRectifier as _R

@@ -294,6 +294,26 @@ class RectifierInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class GridMapParams(C.Structure):
+    """srrg2_gridmap_params"""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("resolution", C.c_float), ("origin", C.c_float * 2)]
+
+
+class GridMapScanParams(C.Structure):
+    """srrg2_gridmap_scan_params"""
+    _fields_ = [("angle_min", C.c_double), ("angle_increment", C.c_double), ("num_beams", C.c_int32), ("range_min", C.c_float),
+                ("range_max", C.c_float), ("sensor_in_robot", C.c_float * 9), ("clear_beyond_max", C.c_int32)]
+
+
+class GridMapResult(C.Structure):
+    """srrg2_gridmap_result"""
+    _fields_ = [("num_beams_total", C.c_int64), ("num_returns", C.c_int64), ("num_cleared_only", C.c_int64),
+                ("num_skipped", C.c_int64), ("num_hits_in_grid", C.c_int64), ("num_miss_updates", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class StereoMatch(C.Structure):
     """srrg2_stereo_match"""
     _fields_ = [("left_pixel", C.c_int32), ("right_pixel", C.c_int32), ("distance", C.c_int32), ("disparity", C.c_float)]

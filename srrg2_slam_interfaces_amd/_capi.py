@@ -108,6 +108,21 @@ def lib():
         _LIB.srrg2_rectify_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                             C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
         _LIB.srrg2_stereo_rectify.argtypes = [dp, dp, dp, dp, dp, dp, dp, dp]
+        # srrg2_gridmap_* (gridmap.OccupancyGrid)
+        i32p = C.POINTER(C.c_int32)
+        _LIB.srrg2_gridmap_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        _LIB.srrg2_gridmap_destroy.argtypes = [C.c_void_p]
+        _LIB.srrg2_gridmap_default_params.argtypes = [C.POINTER(abi.GridMapParams)]
+        _LIB.srrg2_gridmap_default_params.restype = None
+        _LIB.srrg2_gridmap_default_scan_params.argtypes = [C.POINTER(abi.GridMapScanParams)]
+        _LIB.srrg2_gridmap_default_scan_params.restype = None
+        _LIB.srrg2_gridmap_reset.argtypes = [C.c_void_p, C.POINTER(abi.GridMapParams)]
+        _LIB.srrg2_gridmap_integrate_scans.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                       C.POINTER(abi.GridMapScanParams), C.c_int, C.POINTER(abi.GridMapResult)]
+        _LIB.srrg2_gridmap_get_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        _LIB.srrg2_gridmap_device_arrays.argtypes = [C.c_void_p, C.POINTER(i32p), C.POINTER(i32p)]
+        _LIB.srrg2_gridmap_render.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        _LIB.srrg2_gridmap_to_scene.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         # srrg2_scene_track_features (mapping.FeatureTracker)
         _LIB.srrg2_track_default_params.argtypes = [C.POINTER(abi.TrackParams)]
         _LIB.srrg2_track_default_params.restype = None

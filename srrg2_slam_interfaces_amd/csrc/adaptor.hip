@@ -26,6 +26,7 @@
 #include "device_util.h"
 #include "host_util.h"
 #include "kernels.h"
+#include "scan_beam.h"
 #include "scene_state.h"
 #include "spherical.h"
 
@@ -133,12 +134,7 @@ struct ScanSource {
     r = ranges[k];
     return isfinite(r) && rmin <= r && r <= rmax;
   }
-  __device__ __forceinline__ float2 point_at(int k, float r) const {
-    double s, c;
-    dm::sincos(amin + (double) k * ainc, s, c);
-    const float cf = (float) c, sf = (float) s;
-    return make_float2(cf * r, sf * r);
-  }
+  __device__ __forceinline__ float2 point_at(int k, float r) const { return scan_beam_point(amin, ainc, k, r); }
   __device__ __forceinline__ int eval(int k, float4& p, float4& nrm) const {
     const float qn = quiet_nan();
     p   = make_float4(qn, qn, 0.f, 0.f);
