@@ -1414,6 +1414,64 @@ int srrg2_gridmap_device_arrays(srrg2_gridmap_h h, const int32_t** hits, const i
 int srrg2_gridmap_render(srrg2_gridmap_h h, int min_observations, uint8_t* dst, int row_stride_bytes, int mem);
 int srrg2_gridmap_to_scene(srrg2_gridmap_h h, int min_observations, int occupied_percent /* 0 .. 100 */, srrg2_scene_h dst);
 
+/* Correlative scan matching against the grid: a pose for a scan whose guess is too far off for ICP (Olson 2009) -- every pose of
+ * a window (x, y, theta) around the guess is scored against a smoothed likelihood field of the map, the best one wins.  No
+ * reference counterpart; DESIGN.md section 4 "Correlative scan matching" is the contract, tests/scan_match_restatement.py restates
+ * it and the library gives the same bits: behind a beam's end cell everything is integer.
+ *   field     a third plane of the grid, rows x cols bytes.  A cell is occupied when srrg2_gridmap_render(min_observations)
+ *             gives it a value in [occupied_percent, 100] (unknown, 255, is not occupied).  field(c) = the maximum of
+ *             lut[dx^2 + dy^2] over the occupied cells c + (dx, dy) inside the grid with dx^2 + dy^2 <= R^2, 0 if there is none.
+ *             lut: R^2 + 1 bytes of the caller's in host memory; it need not be monotone, the maximum decides.  R = 0 .. 16.
+ *             srrg2_gridmap_default_likelihood_lut: lut[d2] = (255 (R^2 + 1 - d2)) / (R^2 + 1), integer division.
+ *   fresh     srrg2_gridmap_reset and every accepted srrg2_gridmap_integrate_scans (one that adds nothing too) make the field
+ *             stale; srrg2_gridmap_get_likelihood and srrg2_gridmap_match_scans refuse a stale or never-built field
+ *             (SRRG2_E_INVALID, "stale"): build it again.
+ *   window    candidates (j, dy, dx), j in [-half_steps_theta, half_steps_theta], dy in [-half_window_y, half_window_y], dx in
+ *             [-half_window_x, half_window_x]; flat index ((j + ht) Ny + (dy + wy)) Nx + (dx + wx), Ny = 2 wy + 1, Nx = 2 wx + 1.
+ *   rotation  Rj = the SE(2) matrix of dm::sincos((double) j * theta_step) (0 when half_steps_theta = 0), float64 rounded to
+ *             float32; Pj = dm::se2_compose(guess, Rj); T = dm::se2_compose(Pj, sensor_in_robot).
+ *   beams     only returns (a finite range inside [range_min, range_max]) are scored, and at rotation j only those the grid
+ *             would trace from T: the end cell (x1, y1) is the one srrg2_gridmap_integrate_scans adds its hit to (the same
+ *             float32 expressions, divide and floorf; start and end inside the 2^30 guard, a ray of at most 32767 cells).
+ *   score     of (j, dy, dx): the int32 sum over those beams of field(x1 + dx, y1 + dy), 0 for a cell outside the grid -- the
+ *             translation is a shift of whole cells.  At most 255 num_beams.
+ *   best      the highest score; among equals the guess (0, 0, 0) if it is one of them, else the lowest flat index.  A scan
+ *             without returns, an empty field or an empty grid hand the guess back; nothing depends on scheduling.
+ *   result    robot_in_world = Pj with (float) dx * resolution added to entry 2 and (float) dy * resolution to entry 5 (float32);
+ *             dx, dy, jtheta; score, score_at_guess; num_scored_beams = the returns of the scan (whatever the rotation: an
+ *             upper bound of the beams summed at the winning one, so score <= 255 num_scored_beams).
+ *   volume    scores_out, if not NULL: num_scans * Ntheta * Ny * Nx int32 in flat-index order, to scores_mem.
+ *   effort    one upload, one host wait, and a launch count that depends neither on num_scans nor on the window.
+ *   refused   every destination, the planes and the field unchanged; parameters are checked before the handle.
+ *             SRRG2_E_INVALID: R outside 0 .. 16; occupied_percent outside 0 .. 100; a null lut; a null destination; a stride
+ *             below a row; bad mem; a negative half window or half_steps_theta; with half_steps_theta > 0 a theta_step that is
+ *             not finite or not > 0; null results with num_scans > 0; null or misaligned guesses with num_scans > 0 (whatever
+ *             num_beams is: the guesses are always read, ranges only when there are beams); a misaligned scores_out; everything
+ *             srrg2_gridmap_integrate_scans refuses of ranges, poses and the scan model; a stale field.  SRRG2_E_UNSUPPORTED:
+ *             Ntheta * Ny * Nx beyond int32; with scores_out, num_scans * Ntheta * Ny * Nx beyond int32.  num_scans = 0 writes
+ *             nothing; num_beams = 0 and an empty grid score 0 everywhere. */
+typedef struct srrg2_gridmap_match_params {
+  int32_t half_window_x, half_window_y;   /* cells, >= 0 */
+  int32_t half_steps_theta;               /* >= 0 */
+  int32_t reserved;                       /* 0 */
+  double  theta_step;                     /* radians per step */
+} srrg2_gridmap_match_params;
+typedef struct srrg2_gridmap_match_result {
+  float   robot_in_world[9];              /* SE(2), row-major 3x3 */
+  int32_t dx, dy, jtheta;
+  int32_t score, score_at_guess, num_scored_beams;
+} srrg2_gridmap_match_result;
+/* R*R + 1 bytes */
+int srrg2_gridmap_default_likelihood_lut(int radius_cells, uint8_t* lut);
+int srrg2_gridmap_build_likelihood(srrg2_gridmap_h h, int min_observations, int occupied_percent, int radius_cells, const uint8_t* lut);
+/* rows x cols bytes to dst in `mem`; the stride as in srrg2_gridmap_render */
+int srrg2_gridmap_get_likelihood(srrg2_gridmap_h h, uint8_t* dst, int row_stride_bytes, int mem);
+/* ranges: num_scans x num_beams floats, guess_robot_in_world: num_scans x 9 floats, both in `mem`; results: num_scans structs in
+ * host memory; scores_out: NULL or the volume in `scores_mem` */
+int srrg2_gridmap_match_scans(srrg2_gridmap_h h, const float* ranges, int num_scans, const float* guess_robot_in_world, int mem,
+                              const srrg2_gridmap_scan_params* scan_params, const srrg2_gridmap_match_params* match_params,
+                              srrg2_gridmap_match_result* results, int32_t* scores_out, int scores_mem);
+
 /* Feature tracking: which keypoint of the measurement is which landmark of the clipped local map -- the per-frame data
  * association of a visual tracker, a projective window plus the Hamming distance of the 256-bit descriptors.  The reference
  * declares the slot and leaves it empty (CorrespondenceFinder_::compute() is pure virtual, S/registration/correspondence_finder.h:56;

@@ -1212,7 +1212,8 @@ private:
 //   GridMap   reset() allocates the two count planes from `params`; integrate() traces a batch of scans taken with the scanner of
 //             `scan` from the given poses (one scan = the per-frame update), remove() takes the same scans out again bit for bit
 //             -- after a pose-graph optimisation only the scans whose pose moved are re-drawn; counts() / render() read the map;
-//             toScene() exports the occupied cells as a 2-D scene an aligner takes as it is.
+//             toScene() exports the occupied cells as a 2-D scene an aligner takes as it is.  buildLikelihood() / matchScans():
+//             correlative scan matching against the map, a pose for a scan whose guess is too far off for ICP.
 class GridMap {
 public:
   srrg2_gridmap_params params;
@@ -1257,6 +1258,43 @@ public:
   // the cells that render into [occupied_percent, 100] as points at their centres; dst.globalIndices() are the plane indices
   void toScene(Scene<2>& dst, int min_observations = 1, int occupied_percent = 50) const {
     check(srrg2_gridmap_to_scene(_h, min_observations, occupied_percent, dst.handle()));
+  }
+  // correlative scan matching (srrg2_slam_amd.h "Correlative scan matching"): the likelihood field of the map as it is now, from
+  // the default table of `radius_cells` or from the caller's radius_cells^2 + 1 bytes; every integrate / remove / reset makes it
+  // stale and a match against a stale field throws
+  static std::vector<uint8_t> defaultLikelihoodLut(int radius_cells) {
+    std::vector<uint8_t> lut((size_t) (radius_cells > 0 ? radius_cells * radius_cells : 0) + 1);
+    check(srrg2_gridmap_default_likelihood_lut(radius_cells, lut.data()));
+    return lut;
+  }
+  void buildLikelihood(int min_observations = 1, int occupied_percent = 50, int radius_cells = 4) {
+    buildLikelihood(min_observations, occupied_percent, radius_cells, defaultLikelihoodLut(radius_cells));
+  }
+  void buildLikelihood(int min_observations, int occupied_percent, int radius_cells, const std::vector<uint8_t>& lut) {
+    if (radius_cells >= 0 && radius_cells <= 16 && lut.size() != (size_t) radius_cells * radius_cells + 1)
+      throw std::runtime_error("GridMap::buildLikelihood: radius_cells^2 + 1 bytes of lut expected");
+    check(srrg2_gridmap_build_likelihood(_h, min_observations, occupied_percent, radius_cells, lut.data()));
+  }
+  // rows x cols bytes
+  std::vector<uint8_t> likelihood() const {
+    std::vector<uint8_t> img(cells());
+    check(srrg2_gridmap_get_likelihood(_h, img.data(), params.cols, SRRG2_MEM_HOST));
+    return img;
+  }
+  // the best pose of the window around each scan's guess; ranges / guesses (num_scans x 9) in `mem`.  scores: if not null, the
+  // whole volume num_scans x Ntheta x Ny x Nx in flat-index order (what a covariance or an ambiguity test is derived from)
+  std::vector<srrg2_gridmap_match_result> matchScans(const float* ranges, int num_scans, const float* guess_robot_in_world,
+                                                     const srrg2_gridmap_match_params& window, int mem = SRRG2_MEM_HOST,
+                                                     std::vector<int32_t>* scores = nullptr) {
+    std::vector<srrg2_gridmap_match_result> out((size_t) (num_scans > 0 ? num_scans : 0));
+    if (scores) {
+      const double n = (2.0 * window.half_window_x + 1) * (2.0 * window.half_window_y + 1) * (2.0 * window.half_steps_theta + 1) *
+                       (double) out.size();
+      scores->assign(n >= 0 && n <= 2147483647.0 ? (size_t) n : 0, 0);  // (beyond int32 the call refuses and writes nothing)
+    }
+    check(srrg2_gridmap_match_scans(_h, ranges, num_scans, guess_robot_in_world, mem, &scan, &window, out.data(),
+                                    scores ? scores->data() : nullptr, SRRG2_MEM_HOST));
+    return out;
   }
   srrg2_gridmap_h handle() const { return _h; }
 

@@ -111,7 +111,8 @@ def ImageRectifier(device=0):
 
 def OccupancyGrid(device=0):
     """Occupancy grid map from laser scans and poses on the device: integrate / remove scans, read the counts, render the
-    image, export the occupied cells as a 2-D scene; see ``gridmap``."""
+    image, export the occupied cells as a 2-D scene, match scans against its likelihood field over a window of poses; see
+    ``gridmap``."""
     from .gridmap import OccupancyGrid as _G
 
     return _G(device)

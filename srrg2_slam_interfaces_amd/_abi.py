@@ -314,6 +314,18 @@ class GridMapResult(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class GridMapMatchParams(C.Structure):
+    """srrg2_gridmap_match_params"""
+    _fields_ = [("half_window_x", C.c_int32), ("half_window_y", C.c_int32), ("half_steps_theta", C.c_int32), ("reserved", C.c_int32),
+                ("theta_step", C.c_double)]
+
+
+class GridMapMatchResult(C.Structure):
+    """srrg2_gridmap_match_result"""
+    _fields_ = [("robot_in_world", C.c_float * 9), ("dx", C.c_int32), ("dy", C.c_int32), ("jtheta", C.c_int32), ("score", C.c_int32),
+                ("score_at_guess", C.c_int32), ("num_scored_beams", C.c_int32)]
+
+
 class StereoMatch(C.Structure):
     """srrg2_stereo_match"""
     _fields_ = [("left_pixel", C.c_int32), ("right_pixel", C.c_int32), ("distance", C.c_int32), ("disparity", C.c_float)]

@@ -123,6 +123,12 @@ def lib():
         _LIB.srrg2_gridmap_device_arrays.argtypes = [C.c_void_p, C.POINTER(i32p), C.POINTER(i32p)]
         _LIB.srrg2_gridmap_render.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
         _LIB.srrg2_gridmap_to_scene.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _LIB.srrg2_gridmap_default_likelihood_lut.argtypes = [C.c_int, C.c_void_p]
+        _LIB.srrg2_gridmap_build_likelihood.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        _LIB.srrg2_gridmap_get_likelihood.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        _LIB.srrg2_gridmap_match_scans.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(abi.GridMapScanParams),
+                                                   C.POINTER(abi.GridMapMatchParams), C.POINTER(abi.GridMapMatchResult), C.c_void_p,
+                                                   C.c_int]
         # srrg2_scene_track_features (mapping.FeatureTracker)
         _LIB.srrg2_track_default_params.argtypes = [C.POINTER(abi.TrackParams)]
         _LIB.srrg2_track_default_params.restype = None

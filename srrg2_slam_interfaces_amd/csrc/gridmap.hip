@@ -25,43 +25,19 @@
 
 #include "det_math.h"
 #include "device_util.h"
+#include "gridmap_state.h"
 #include "host_util.h"
 #include "scan_beam.h"
 #include "scene_state.h"
 
 using srrg2amd::fail;
-
-struct srrg2_gridmap_s {
-  int device = 0;
-  // the grid's stream is this scratch scene's: the scene export hands it to scene_compact_into as the source of the compaction
-  // (its flags, scan sums and counters are the scratch of that path); it never holds points
-  srrg2_scene* work = nullptr;
-  hipEvent_t uploaded = nullptr;  // recorded behind the upload out of host_stage: the next call waits for it before it refills
-  bool upload_pending = false;
-  bool is_set         = false;
-  srrg2_gridmap_params p;
-  srrg2amd::DevBuf<int> planes;  // hits, then misses: rows*cols words each
-  srrg2amd::DevBuf<char> stage;  // a host call's ranges, then its poses
-  srrg2amd::PinnedBuf<char> host_stage;
-  srrg2amd::DevBuf<unsigned long long> ctr;
-  srrg2amd::PinnedBuf<unsigned long long> ctr_host;
-  srrg2amd::DevBuf<unsigned char> image;  // a host render's packed rows
-  long long cells() const { return (long long) p.rows * p.cols; }
-  hipStream_t stream() const { return work->stream; }
-  ~srrg2_gridmap_s() {
-    (void) hipSetDevice(device);
-    if (work) (void) hipStreamSynchronize(work->stream);
-    if (uploaded) (void) hipEventDestroy(uploaded);
-    if (work) (void) srrg2_scene_destroy(work);
-  }
-};
+using srrg2amd::gridmap_check_scan_call;
+using srrg2amd::gridmap_ready;
 
 namespace {
 
-enum { MAX_SIDE = 32768, MAX_RAY = 32767, MAX_BLOCKS = 1024 };
+enum { MAX_SIDE = 32768, MAX_RAY = GRIDMAP_MAX_RAY, MAX_BLOCKS = 1024 };
 enum { C_RETURNS = 0, C_CLEARED, C_HITS, C_MISSES, C_WORDS };
-#define GRIDMAP_MAX_STEPS 32000.f          /* range_max / resolution beyond this is refused */
-#define GRIDMAP_CELL_GUARD 1073741824.f    /* 2^30 */
 
 struct GridArgs {
   int* hits;
@@ -80,14 +56,6 @@ struct BeamArgs {
   float S[9];
   int clear, weight;
 };
-
-// the cell coordinate of the contract; false: never converted
-__device__ __forceinline__ bool cell_of(float x, float o, float res, int& c) {
-  const float u = floorf((x - o) / res);
-  if (!(u >= -GRIDMAP_CELL_GUARD && u < GRIDMAP_CELL_GUARD)) return false;  // (a NaN fails both)
-  c = (int) u;
-  return true;
-}
 
 // a beam ready to be walked: start cell, direction, 2|dx|, 2|dy|, n (-1: the beam adds nothing), and whether step n is a hit
 struct Ray {
@@ -208,14 +176,6 @@ __global__ __launch_bounds__(256) void k_gridmap_integrate(GridArgs G, BeamArgs 
   block_add(misses, &ctr[C_MISSES]);
 }
 
-// 0 .. 100, or 255 = unknown
-__device__ __forceinline__ unsigned cell_value(int h, int m, long long need) {
-  if (h < 0 || m < 0) return 255u;
-  const unsigned long long n = (unsigned long long) h + (unsigned long long) m;
-  if ((long long) n < need) return 255u;  // (need >= 1: n > 0 below)
-  return (unsigned) ((100ull * (unsigned long long) h + n / 2) / n);
-}
-
 // a thread: cells (r, c .. c + 3); quads = ceil(cols / 4)
 __global__ __launch_bounds__(256) void k_gridmap_render(GridArgs G, long long need, int quads, unsigned char* __restrict__ dst,
                                                         long long stride) {
@@ -276,9 +236,11 @@ int check_grid_params(const std::string& who, const srrg2_gridmap_params* p) {
   return 0;
 }
 
-// what srrg2_gridmap_integrate_scans refuses without looking at its handle
-int check_scan_call(const std::string& who, const float* ranges, int num_scans, const float* poses, int mem,
-                    const srrg2_gridmap_scan_params* p, int weight) {
+}  // namespace
+
+// what srrg2_gridmap_integrate_scans refuses without looking at its handle (srrg2_gridmap_match_scans refuses the same)
+int srrg2amd::gridmap_check_scan_call(const std::string& who, const float* ranges, int num_scans, const float* poses, int mem,
+                                      const srrg2_gridmap_scan_params* p, int weight) {
   if (!p) return fail(SRRG2_E_INVALID, who + "null params");
   if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, who + "bad mem");
   if (weight != 1 && weight != -1) return fail(SRRG2_E_INVALID, who + "weight must be +1 or -1");
@@ -303,13 +265,11 @@ int check_scan_call(const std::string& who, const float* ranges, int num_scans, 
   return 0;
 }
 
-int ready(const std::string& who, srrg2_gridmap_s* h) {
+int srrg2amd::gridmap_ready(const std::string& who, srrg2_gridmap_s* h) {
   if (!h) return fail(SRRG2_E_INVALID, who + "null handle");
   if (!h->is_set) return fail(SRRG2_E_INVALID, who + "no grid (srrg2_gridmap_reset)");
   return 0;
 }
-
-}  // namespace
 
 extern "C" int srrg2_gridmap_create(int device, srrg2_gridmap_h* out) {
   if (!out) return fail(SRRG2_E_INVALID, "gridmap_create: out is NULL");
@@ -357,7 +317,7 @@ extern "C" int srrg2_gridmap_reset(srrg2_gridmap_h h, const srrg2_gridmap_params
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t) p->rows * (size_t) p->cols;
   HIP_TRY(hipStreamSynchronize(h->stream()));  // (queued work still adds into the old planes)
-  h->is_set = false;
+  h->is_set = false, h->field_fresh = false;  // (the likelihood field of the old planes is nobody's)
   if ((rc = h->planes.reserve(2 * n + 4))) return rc;
   if (n > 0) HIP_TRY(hipMemsetAsync(h->planes.p, 0, 2 * n * sizeof(int), h->stream()));
   h->p      = *p;
@@ -369,11 +329,12 @@ extern "C" int srrg2_gridmap_integrate_scans(srrg2_gridmap_h h, const float* ran
                                              const srrg2_gridmap_scan_params* p, int weight, srrg2_gridmap_result* out) {
   const std::string who = "gridmap_integrate_scans: ";
   int rc;
-  if ((rc = check_scan_call(who, ranges, num_scans, robot_in_world, mem, p, weight))) return rc;
-  if ((rc = ready(who, h))) return rc;
+  if ((rc = gridmap_check_scan_call(who, ranges, num_scans, robot_in_world, mem, p, weight))) return rc;
+  if ((rc = gridmap_ready(who, h))) return rc;
   // (float32, as the rays are: NaN -- an infinite range_max -- is refused too)
   if (!(p->range_max / h->p.resolution <= GRIDMAP_MAX_STEPS))
     return fail(SRRG2_E_INVALID, who + "range_max / resolution beyond 32000 cells");
+  h->field_fresh = false;  // every accepted call: the likelihood field has to be built again before the next match
   const long long total = (long long) num_scans * p->num_beams;
   srrg2_gridmap_result res;
   std::memset(&res, 0, sizeof(res));
@@ -429,7 +390,7 @@ extern "C" int srrg2_gridmap_get_counts(srrg2_gridmap_h h, int32_t* hits, int32_
   const std::string who = "gridmap_get_counts: ";
   if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, who + "bad mem");
   int rc;
-  if ((rc = ready(who, h))) return rc;
+  if ((rc = gridmap_ready(who, h))) return rc;
   const size_t n = (size_t) h->cells();
   if (n == 0 || (!hits && !misses)) return 0;
   HIP_TRY(hipSetDevice(h->device));
@@ -445,7 +406,7 @@ extern "C" int srrg2_gridmap_device_arrays(srrg2_gridmap_h h, const int32_t** hi
   const std::string who = "gridmap_device_arrays: ";
   if (!hits || !misses) return fail(SRRG2_E_INVALID, who + "null output");
   int rc;
-  if ((rc = ready(who, h))) return rc;
+  if ((rc = gridmap_ready(who, h))) return rc;
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipStreamSynchronize(h->stream()));  // (the arrays go to another stream: queued work has to be done)
   h->upload_pending = false;
@@ -458,7 +419,7 @@ extern "C" int srrg2_gridmap_render(srrg2_gridmap_h h, int min_observations, uin
   const std::string who = "gridmap_render: ";
   if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, who + "bad mem");
   int rc;
-  if ((rc = ready(who, h))) return rc;
+  if ((rc = gridmap_ready(who, h))) return rc;
   const int rows = h->p.rows, cols = h->p.cols;
   if (h->cells() == 0) return 0;
   if (!dst) return fail(SRRG2_E_INVALID, who + "null image");
@@ -488,7 +449,7 @@ extern "C" int srrg2_gridmap_to_scene(srrg2_gridmap_h h, int min_observations, i
   const std::string who = "gridmap_to_scene: ";
   if (occupied_percent < 0 || occupied_percent > 100) return fail(SRRG2_E_INVALID, who + "occupied_percent 0 .. 100");
   int rc;
-  if ((rc = ready(who, h))) return rc;
+  if ((rc = gridmap_ready(who, h))) return rc;
   if (!dst) return fail(SRRG2_E_INVALID, who + "null scene");
   if (!srrg2amd::scene_clip_pair(h->work, dst)) return fail(SRRG2_E_INVALID, who + "dst must be a 2-D scene on the grid's device");
   srrg2_scene* const s = h->work;

@@ -6,8 +6,12 @@ which cells of a 2-D grid are free, occupied or never seen, on the device.
                    same scans out again (weight -1: after a pose-graph optimisation only the scans whose pose moved are re-drawn);
                    ``counts()`` / ``render()`` read the map, ``to_scene(scene)`` exports the occupied cells as a 2-D scene the
                    aligner takes as it is (scan-to-map tracking).
+                   ``build_likelihood()`` smooths the occupied cells into a likelihood field, ``match_scans(ranges, guesses, ...)``
+                   scores every pose of a window around each guess against it and returns the best (a pose for a scan whose
+                   guess is too far off for ICP); ``likelihood()`` reads the field.
 
-Thin marshalling only; the contract is DESIGN.md section 4 "Occupancy grid", its restatement tests/gridmap_restatement.py.
+Thin marshalling only; the contract is DESIGN.md section 4 "Occupancy grid" and "Correlative scan matching", its restatements
+tests/gridmap_restatement.py and tests/scan_match_restatement.py.
 """
 import ctypes as C
 
@@ -143,3 +147,82 @@ class OccupancyGrid:
         plane-index order; ``scene.global_indices()`` are the plane indices iy*cols + ix.  Returns the number of points."""
         self._check(self._lib.srrg2_gridmap_to_scene(self._h, int(min_observations), int(occupied_percent), scene._h))
         return scene.size()
+
+    # ---- correlative scan matching (DESIGN.md section 4 "Correlative scan matching", tests/scan_match_restatement.py) ----------
+
+    def build_likelihood(self, min_observations=1, occupied_percent=50, radius_cells=4, lut=None):
+        """the likelihood field of the map as it is now: per cell the maximum of lut[dx^2 + dy^2] over the occupied cells within
+        radius_cells.  lut: radius_cells^2 + 1 bytes (None: ``default_likelihood_lut``).  Every integrate / remove / reset makes
+        the field stale: build it again before the next match."""
+        lut = default_likelihood_lut(radius_cells) if lut is None else np.ascontiguousarray(lut, np.uint8)
+        if 0 <= int(radius_cells) <= 16 and lut.size != int(radius_cells) ** 2 + 1:
+            raise ValueError("lut: radius_cells^2 + 1 bytes expected")
+        self._check(self._lib.srrg2_gridmap_build_likelihood(self._h, int(min_observations), int(occupied_percent), int(radius_cells),
+                                                             C.c_void_p(lut.ctypes.data)))
+
+    def likelihood(self, out=None):
+        """(rows, cols) uint8, the field; out: as in ``render``"""
+        rows, cols = self.shape
+        if isinstance(out, tuple):
+            self._check(self._lib.srrg2_gridmap_get_likelihood(self._h, C.c_void_p(int(out[0])), int(out[1]), abi.MEM_DEVICE))
+            return out
+        if out is None:
+            out = np.zeros((rows, cols), np.uint8)
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.shape != (rows, cols) or (out.size and out.strides[1] != 1):
+            raise ValueError("out: a (rows, cols) uint8 array with unit column stride expected")
+        stride = int(out.strides[0]) if rows > 1 else cols
+        self._check(self._lib.srrg2_gridmap_get_likelihood(self._h, C.c_void_p(out.ctypes.data), stride, abi.MEM_HOST))
+        return out
+
+    def match_scans(self, ranges, guesses, half_window=(0, 0), half_steps_theta=0, theta_step=0.0, want_scores=False):
+        """every pose of the window around each scan's guess scored against the likelihood field, the best one per scan.
+        ranges: (K, num_beams) float32, guesses: (K, 3, 3) robot_in_world -- numpy arrays, or torch tensors on the device (both).
+        half_window: (wx, wy) cells; the rotations are j * theta_step, |j| <= half_steps_theta.  Returns a dict of arrays over
+        the K scans: robot_in_world (K, 3, 3), dx, dy, jtheta, score, score_at_guess, num_scored_beams; with want_scores also
+        scores, the whole volume (K, Ntheta, Ny, Nx) int32 -- want_scores may be a contiguous int32 torch tensor of that many
+        elements on the device, which is then filled and returned as it is."""
+        nb = self.scan.num_beams
+        rk, rptr, rmem, rshape = _floats(ranges, "ranges")
+        pk, pptr, pmem, pshape = _floats(guesses, "guesses")
+        if rmem != pmem:
+            raise ValueError("ranges and guesses must live in one memory space")
+        n_ranges, n_poses = int(np.prod(rshape)), int(np.prod(pshape))
+        K = n_poses // 9
+        if n_poses != 9 * K or n_ranges != K * nb:
+            raise ValueError("ranges: (K, %d) and guesses: (K, 3, 3) expected, got %s and %s" % (nb, rshape, pshape))
+        mp = abi.GridMapMatchParams()
+        mp.half_window_x, mp.half_window_y, mp.half_steps_theta = int(half_window[0]), int(half_window[1]), int(half_steps_theta)
+        mp.theta_step = float(theta_step)
+        shape = (K, 2 * mp.half_steps_theta + 1, 2 * mp.half_window_y + 1, 2 * mp.half_window_x + 1)
+        res = (abi.GridMapMatchResult * max(K, 1))()
+        scores, sptr, smem = None, None, abi.MEM_HOST
+        if hasattr(want_scores, "data_ptr"):
+            import torch
+
+            if want_scores.dtype != torch.int32 or not want_scores.is_contiguous() or not want_scores.is_cuda or \
+                    want_scores.numel() != int(np.prod(shape)):
+                raise ValueError("want_scores: a contiguous int32 device tensor of %d elements expected" % int(np.prod(shape)))
+            scores, sptr, smem = want_scores, C.c_void_p(want_scores.data_ptr()), abi.MEM_DEVICE
+        elif want_scores:
+            refused = min(shape[1:]) < 1 or shape[0] * shape[1] * shape[2] * shape[3] > 2 ** 31 - 1
+            scores = np.zeros((1, 1, 1, 1) if refused else shape, np.int32)  # (refused: the call says why and writes nothing)
+            sptr = C.c_void_p(scores.ctypes.data)
+        self._check(self._lib.srrg2_gridmap_match_scans(self._h, rptr, K, pptr, rmem, C.byref(self.scan), C.byref(mp), res, sptr, smem))
+        raw = np.frombuffer(res, np.uint8).reshape(max(K, 1), C.sizeof(abi.GridMapMatchResult))[:K]
+        out = {"robot_in_world": raw[:, :36].copy().view(np.float32).reshape(K, 3, 3)}
+        for i, name in enumerate(("dx", "dy", "jtheta", "score", "score_at_guess", "num_scored_beams")):
+            out[name] = raw[:, 36 + 4 * i:40 + 4 * i].copy().view(np.int32).reshape(K)
+        if scores is not None:
+            out["scores"] = scores
+        return out
+
+
+def default_likelihood_lut(radius_cells):
+    """lut[d2] = (255 (R^2 + 1 - d2)) / (R^2 + 1), integer division: 255 on an occupied cell, falling linearly in the squared distance"""
+    from . import _capi
+
+    lib = _capi.lib()
+    lut = np.zeros(max(int(radius_cells), 0) ** 2 + 1, np.uint8)
+    if lib.srrg2_gridmap_default_likelihood_lut(int(radius_cells), C.c_void_p(lut.ctypes.data)) != 0:
+        raise RuntimeError((lib.srrg2_amd_last_error() or b"").decode())
+    return lut
