@@ -1472,6 +1472,63 @@ int srrg2_gridmap_match_scans(srrg2_gridmap_h h, const float* ranges, int num_sc
                               const srrg2_gridmap_scan_params* scan_params, const srrg2_gridmap_match_params* match_params,
                               srrg2_gridmap_match_result* results, int32_t* scores_out, int scores_mem);
 
+/* Pruned scan matching: the window of srrg2_gridmap_match_scans searched through a pyramid of upper bounds, so that a scan with
+ * no usable guess can be placed against the whole map (relocalisation, a 2-D loop closure against the map).  The result is bit
+ * for bit that of srrg2_gridmap_match_scans on the same inputs, ties included.  DESIGN.md section 4 "Pruned scan matching" is the
+ * contract, tests/scan_match_pruned_restatement.py restates it; everything behind a beam's end cell is integer.
+ *   planes    levels l = 1 .. L <= 6, a block of level l has side s = 2^l.  P_l(x, y) = the maximum of the field over the cells
+ *             [x, x + s) x [y, y + s) inside the grid, 0 if there is none: defined for x in [-(s - 1), cols - 1] and y in
+ *             [-(s - 1), rows - 1], 0 elsewhere; P_0 is the field and P_l a 2 x 2 maximum of P_(l-1) at offset s / 2.
+ *             srrg2_gridmap_build_bounds builds P_1 .. P_num_levels from a fresh field (a stale one is refused);
+ *             srrg2_gridmap_get_bounds hands out the (rows + s - 1) x (cols + s - 1) bytes of one level, row (y + s - 1), column
+ *             (x + s - 1), to dst in `mem` (the stride as in srrg2_gridmap_render).  srrg2_gridmap_reset, every accepted
+ *             srrg2_gridmap_integrate_scans and srrg2_gridmap_build_likelihood make the planes stale.
+ *   blocks    window, rotations, scored beams, end cells (x1, y1) and flat candidate index are those of srrg2_gridmap_match_scans.
+ *             At level l the Nx x Ny shifts are tiled by NBx x NBy blocks, NBx = ceil(Nx / s); block (j, by, bx) covers the shift
+ *             indices [bx s, bx s + s) x [by s, by s + s) inside the window, its flat index is (j NBy + by) NBx + bx, its bound
+ *             U_l = the sum of P_l(x1 + bx s - wx, y1 + by s - wy) over the beams scored at rotation j whose end cell some shift
+ *             of the window brings inside the grid.  U_l >= the score of every candidate of the block, and U_(l+1) of the
+ *             parent >= U_l of the child.
+ *   search    per scan.  Every block of level L is bounded; the seed block is the one with the highest bound, among equals the
+ *             lowest flat block index.  The guess and every candidate of the seed block are scored; floor = the highest of these
+ *             scores, fixed from here on.  A block survives iff U >= floor, and iff U > floor when floor = score_at_guess (then
+ *             nothing beats the guess under the tie rule).  Level by level, the children inside the window of a level's survivors
+ *             are evaluated: bounds above level 0, scores at level 0.  The result is the best (the tie rule of
+ *             srrg2_gridmap_match_scans) of everything scored: the guess, the seed block, the children at level 0.
+ *   lists     the blocks of one scan to evaluate at one level below L are at most max_list_entries (0 = 2^20); a scan with more
+ *             falls back: its whole window is scored exhaustively, fell_back = 1, the result is the same.  The limit is per scan,
+ *             so that falling back depends on the inputs alone.
+ *   stats     per scan, NULL or num_scans structs in host memory, a function of the inputs alone: num_evaluated[l] = the blocks
+ *             bounded at level l = 1 .. L and, at l = 0, the candidates scored in the descent (seed block and guess are not
+ *             counted); num_survivors[l], l = 1 .. L; floor_score; seed_block; fell_back.  After a fall-back the levels above
+ *             the one whose list overflowed keep their counts, that level and those below have 0, and num_evaluated[0] =
+ *             num_candidates.
+ *   effort    one upload, one host wait, a launch count that depends on num_levels alone.  Device memory: 4 bytes per block of
+ *             level L and, per scan, 8 bytes per entry of min(limit, num_candidates).
+ *   refused   what srrg2_gridmap_match_scans refuses, and SRRG2_E_INVALID: null prune params; num_levels outside 1 .. 6 or above
+ *             the number built; stale planes; a negative max_list_entries.  Parameters are checked before the handle; every
+ *             destination stays as it was.  There is no score volume: srrg2_gridmap_match_scans has it. */
+typedef struct srrg2_gridmap_prune_params {
+  int32_t num_levels;                     /* L, 1 .. 6 and <= the levels built */
+  int32_t max_list_entries;               /* per scan and level; 0 = 2^20 */
+} srrg2_gridmap_prune_params;
+typedef struct srrg2_gridmap_prune_stats {
+  int32_t num_candidates;
+  int32_t num_evaluated[7];               /* [l], l = 0 .. 6 */
+  int32_t num_survivors[7];               /* [l], l = 1 .. 6; [0] = 0 */
+  int32_t floor_score;
+  int32_t seed_block;                     /* flat block index at level L */
+  int32_t fell_back;
+} srrg2_gridmap_prune_stats;
+/* num_levels = 4, max_list_entries = 0 */
+void srrg2_gridmap_default_prune_params(srrg2_gridmap_prune_params* p);
+int srrg2_gridmap_build_bounds(srrg2_gridmap_h h, int num_levels /* 1 .. 6 */);
+int srrg2_gridmap_get_bounds(srrg2_gridmap_h h, int level /* 1 .. the levels built */, uint8_t* dst, int row_stride_bytes, int mem);
+int srrg2_gridmap_match_scans_pruned(srrg2_gridmap_h h, const float* ranges, int num_scans, const float* guess_robot_in_world, int mem,
+                                     const srrg2_gridmap_scan_params* scan_params, const srrg2_gridmap_match_params* match_params,
+                                     const srrg2_gridmap_prune_params* prune_params, srrg2_gridmap_match_result* results,
+                                     srrg2_gridmap_prune_stats* stats /* NULL ok */);
+
 /* Feature tracking: which keypoint of the measurement is which landmark of the clipped local map -- the per-frame data
  * association of a visual tracker, a projective window plus the Hamming distance of the 256-bit descriptors.  The reference
  * declares the slot and leaves it empty (CorrespondenceFinder_::compute() is pure virtual, S/registration/correspondence_finder.h:56;

@@ -16,6 +16,7 @@
 #pragma once
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstring>
 #include <deque>
 #include <stdexcept>
@@ -1213,7 +1214,9 @@ private:
 //             `scan` from the given poses (one scan = the per-frame update), remove() takes the same scans out again bit for bit
 //             -- after a pose-graph optimisation only the scans whose pose moved are re-drawn; counts() / render() read the map;
 //             toScene() exports the occupied cells as a 2-D scene an aligner takes as it is.  buildLikelihood() / matchScans():
-//             correlative scan matching against the map, a pose for a scan whose guess is too far off for ICP.
+//             correlative scan matching against the map, a pose for a scan whose guess is too far off for ICP.  buildBounds() /
+//             matchScansPruned() / localize(): the same search through a pyramid of upper bounds, cheap enough for the whole map
+//             -- a pose for a scan that has no guess at all.
 class GridMap {
 public:
   srrg2_gridmap_params params;
@@ -1227,11 +1230,15 @@ public:
   GridMap(const GridMap&)            = delete;
   GridMap& operator=(const GridMap&) = delete;
   // a new, empty map from `params`
-  void reset() { check(srrg2_gridmap_reset(_h, &params)); }
+  void reset() {
+    check(srrg2_gridmap_reset(_h, &params));
+    _bounds_levels = 0;
+  }
   // ranges: num_scans x scan.num_beams, robot_in_world: num_scans x 9 (row-major SE(2)), both in `mem`
   const srrg2_gridmap_result& integrate(const float* ranges, int num_scans, const float* robot_in_world, int mem = SRRG2_MEM_HOST,
                                         int weight = 1) {
     check(srrg2_gridmap_integrate_scans(_h, ranges, num_scans, robot_in_world, mem, &scan, weight, &_result));
+    _bounds_levels = 0;
     return _result;
   }
   const srrg2_gridmap_result& remove(const float* ranges, int num_scans, const float* robot_in_world, int mem = SRRG2_MEM_HOST) {
@@ -1240,6 +1247,7 @@ public:
   // queues the work on the grid's stream and returns without waiting; no counters
   void integrateQueued(const float* ranges, int num_scans, const float* robot_in_world, int mem = SRRG2_MEM_HOST, int weight = 1) {
     check(srrg2_gridmap_integrate_scans(_h, ranges, num_scans, robot_in_world, mem, &scan, weight, nullptr));
+    _bounds_levels = 0;
   }
   const srrg2_gridmap_result& result() const { return _result; }
   size_t cells() const { return (size_t) params.rows * (size_t) params.cols; }
@@ -1273,6 +1281,7 @@ public:
   void buildLikelihood(int min_observations, int occupied_percent, int radius_cells, const std::vector<uint8_t>& lut) {
     if (radius_cells >= 0 && radius_cells <= 16 && lut.size() != (size_t) radius_cells * radius_cells + 1)
       throw std::runtime_error("GridMap::buildLikelihood: radius_cells^2 + 1 bytes of lut expected");
+    _bounds_levels = 0;
     check(srrg2_gridmap_build_likelihood(_h, min_observations, occupied_percent, radius_cells, lut.data()));
   }
   // rows x cols bytes
@@ -1296,11 +1305,60 @@ public:
                                     scores ? scores->data() : nullptr, SRRG2_MEM_HOST));
     return out;
   }
+  // pruned scan matching (srrg2_slam_amd.h "Pruned scan matching"): the bound planes P_1 .. P_levels of the field as it is now;
+  // whatever makes the field stale -- buildLikelihood too -- makes them stale
+  void buildBounds(int levels = 4) {
+    check(srrg2_gridmap_build_bounds(_h, levels));
+    _bounds_levels = levels;
+  }
+  // (rows + s - 1) x (cols + s - 1) bytes, s = 2^level: row y + s - 1, column x + s - 1 hold the maximum of the field over the
+  // cells [x, x + s) x [y, y + s) inside the grid
+  std::vector<uint8_t> bounds(int level) const {
+    const size_t s = (size_t) 1 << (level < 0 ? 0 : level > 6 ? 6 : level);
+    std::vector<uint8_t> img(((size_t) params.rows + s - 1) * ((size_t) params.cols + s - 1));
+    check(srrg2_gridmap_get_bounds(_h, level, img.data(), (int) ((size_t) params.cols + s - 1), SRRG2_MEM_HOST));
+    return img;
+  }
+  // matchScans through the bound planes: the same window, bit for bit the same results, without scoring most of it.  levels = 0:
+  // all that were built; max_list_entries = 0: 2^20 blocks per scan and level before a scan falls back to the exhaustive search.
+  // stats: if not null, one srrg2_gridmap_prune_stats per scan
+  std::vector<srrg2_gridmap_match_result> matchScansPruned(const float* ranges, int num_scans, const float* guess_robot_in_world,
+                                                           const srrg2_gridmap_match_params& window, int levels = 0, int max_list_entries = 0,
+                                                           int mem = SRRG2_MEM_HOST, std::vector<srrg2_gridmap_prune_stats>* stats = nullptr) {
+    std::vector<srrg2_gridmap_match_result> out((size_t) (num_scans > 0 ? num_scans : 0));
+    if (stats) stats->assign(out.size(), srrg2_gridmap_prune_stats{});
+    srrg2_gridmap_prune_params prune;
+    prune.num_levels = levels > 0 ? levels : _bounds_levels, prune.max_list_entries = max_list_entries;
+    check(srrg2_gridmap_match_scans_pruned(_h, ranges, num_scans, guess_robot_in_world, mem, &scan, &window, &prune, out.data(),
+                                           stats ? stats->data() : nullptr));
+    return out;
+  }
+  // the guess of localize(): the centre of cell (cols / 2, rows / 2) at heading 0, row-major SE(2)
+  void centrePose(float* robot_in_world) const {
+    const float P[9] = {1.f, 0.f, (float) ((double) params.origin[0] + (params.cols / 2 + 0.5) * (double) params.resolution),
+                        0.f, 1.f, (float) ((double) params.origin[1] + (params.rows / 2 + 0.5) * (double) params.resolution),
+                        0.f, 0.f, 1.f};
+    for (int i = 0; i < 9; ++i) robot_in_world[i] = P[i];
+  }
+  // scans without any guess against the whole map: the window is the grid around its centre cell and ceil(pi / theta_step) steps
+  // either way.  Builds the bound planes if they are stale (levels, or 4); the field must be fresh.  ranges in host memory
+  std::vector<srrg2_gridmap_match_result> localize(const float* ranges, int num_scans, double theta_step, int levels = 0,
+                                                   std::vector<srrg2_gridmap_prune_stats>* stats = nullptr) {
+    if (_bounds_levels < (levels > 0 ? levels : 1)) buildBounds(levels > 0 ? levels : 4);
+    std::vector<float> guesses((size_t) (num_scans > 0 ? num_scans : 0) * 9);
+    for (size_t k = 0; k * 9 < guesses.size(); ++k) centrePose(guesses.data() + 9 * k);
+    srrg2_gridmap_match_params window;
+    window.half_window_x = params.cols / 2, window.half_window_y = params.rows / 2;
+    window.half_steps_theta = (int) std::ceil(3.14159265358979323846 / theta_step);
+    window.reserved = 0, window.theta_step = theta_step;
+    return matchScansPruned(ranges, num_scans, guesses.data(), window, levels, 0, SRRG2_MEM_HOST, stats);
+  }
   srrg2_gridmap_h handle() const { return _h; }
 
 private:
   srrg2_gridmap_h _h = nullptr;
   srrg2_gridmap_result _result{};
+  int _bounds_levels = 0;  // the levels of bound planes built from the field as it is
 };
 
 // ---- binary descriptor database: the matching half of MultiLoopDetectorHBST_ --------------------------------------

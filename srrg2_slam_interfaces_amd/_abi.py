@@ -326,6 +326,21 @@ class GridMapMatchResult(C.Structure):
                 ("score_at_guess", C.c_int32), ("num_scored_beams", C.c_int32)]
 
 
+class GridMapPruneParams(C.Structure):
+    """srrg2_gridmap_prune_params"""
+    _fields_ = [("num_levels", C.c_int32), ("max_list_entries", C.c_int32)]
+
+
+class GridMapPruneStats(C.Structure):
+    """srrg2_gridmap_prune_stats"""
+    _fields_ = [("num_candidates", C.c_int32), ("num_evaluated", C.c_int32 * 7), ("num_survivors", C.c_int32 * 7),
+                ("floor_score", C.c_int32), ("seed_block", C.c_int32), ("fell_back", C.c_int32)]
+
+    def as_dict(self):
+        return {"num_candidates": self.num_candidates, "num_evaluated": list(self.num_evaluated), "num_survivors": list(self.num_survivors),
+                "floor_score": self.floor_score, "seed_block": self.seed_block, "fell_back": self.fell_back}
+
+
 class StereoMatch(C.Structure):
     """srrg2_stereo_match"""
     _fields_ = [("left_pixel", C.c_int32), ("right_pixel", C.c_int32), ("distance", C.c_int32), ("disparity", C.c_float)]

@@ -129,6 +129,14 @@ def lib():
         _LIB.srrg2_gridmap_match_scans.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(abi.GridMapScanParams),
                                                    C.POINTER(abi.GridMapMatchParams), C.POINTER(abi.GridMapMatchResult), C.c_void_p,
                                                    C.c_int]
+        _LIB.srrg2_gridmap_default_prune_params.argtypes = [C.POINTER(abi.GridMapPruneParams)]
+        _LIB.srrg2_gridmap_default_prune_params.restype = None
+        _LIB.srrg2_gridmap_build_bounds.argtypes = [C.c_void_p, C.c_int]
+        _LIB.srrg2_gridmap_get_bounds.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        _LIB.srrg2_gridmap_match_scans_pruned.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                          C.POINTER(abi.GridMapScanParams), C.POINTER(abi.GridMapMatchParams),
+                                                          C.POINTER(abi.GridMapPruneParams), C.POINTER(abi.GridMapMatchResult),
+                                                          C.POINTER(abi.GridMapPruneStats)]
         # srrg2_scene_track_features (mapping.FeatureTracker)
         _LIB.srrg2_track_default_params.argtypes = [C.POINTER(abi.TrackParams)]
         _LIB.srrg2_track_default_params.restype = None

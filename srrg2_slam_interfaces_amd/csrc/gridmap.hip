@@ -317,7 +317,7 @@ extern "C" int srrg2_gridmap_reset(srrg2_gridmap_h h, const srrg2_gridmap_params
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t) p->rows * (size_t) p->cols;
   HIP_TRY(hipStreamSynchronize(h->stream()));  // (queued work still adds into the old planes)
-  h->is_set = false, h->field_fresh = false;  // (the likelihood field of the old planes is nobody's)
+  h->is_set = false, h->stale_field();  // (the likelihood field of the old planes is nobody's, and so are its bound planes)
   if ((rc = h->planes.reserve(2 * n + 4))) return rc;
   if (n > 0) HIP_TRY(hipMemsetAsync(h->planes.p, 0, 2 * n * sizeof(int), h->stream()));
   h->p      = *p;
@@ -334,7 +334,7 @@ extern "C" int srrg2_gridmap_integrate_scans(srrg2_gridmap_h h, const float* ran
   // (float32, as the rays are: NaN -- an infinite range_max -- is refused too)
   if (!(p->range_max / h->p.resolution <= GRIDMAP_MAX_STEPS))
     return fail(SRRG2_E_INVALID, who + "range_max / resolution beyond 32000 cells");
-  h->field_fresh = false;  // every accepted call: the likelihood field has to be built again before the next match
+  h->stale_field();  // every accepted call: the likelihood field (and its bound planes) has to be built again before the next match
   const long long total = (long long) num_scans * p->num_beams;
   srrg2_gridmap_result res;
   std::memset(&res, 0, sizeof(res));

@@ -1,5 +1,5 @@
 // gridmap_state.h -- what the two translation units of the srrg2_gridmap_* family share: the handle (gridmap.hip draws the count
-// planes, scan_match.hip builds the likelihood field from them and matches scans against it), the cell coordinate and the
+// planes, scan_match.hip builds the likelihood field and its bound planes from them and matches scans against both), the cell coordinate and the
 // rendered value of the contract, and the checks both make of a batch of scans.  Internal to the library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +33,19 @@ struct srrg2_gridmap_s {
   srrg2amd::DevBuf<srrg2_gridmap_match_result> match_results;
   srrg2amd::PinnedBuf<srrg2_gridmap_match_result> match_results_host;
   srrg2amd::DevBuf<int> match_volume;
+  // pruned matching: the bound planes P_1 .. P_bounds_levels one behind the other (P_l: (rows + s - 1) * (cols + s - 1) bytes at
+  // bounds_at[l], s = 2^l) and ONE zero byte behind them at bounds_at[0]; bounds_levels = 0: stale or never built -- whatever
+  // clears field_fresh clears it too (stale_field()).  The top level's bounds, the two block lists a descent alternates
+  // between, the per-scan search state and the statistics
+  int bounds_levels = 0;
+  long long bounds_at[7] = {0, 0, 0, 0, 0, 0, 0};
+  srrg2amd::DevBuf<unsigned char> bounds;
+  srrg2amd::DevBuf<int> prune_top;
+  srrg2amd::DevBuf<int> prune_lists;
+  srrg2amd::DevBuf<int> prune_state;
+  srrg2amd::DevBuf<srrg2_gridmap_prune_stats> prune_stats;
+  srrg2amd::PinnedBuf<srrg2_gridmap_prune_stats> prune_stats_host;
+  void stale_field() { field_fresh = false, bounds_levels = 0; }
   long long cells() const { return (long long) p.rows * p.cols; }
   hipStream_t stream() const { return work->stream; }
   ~srrg2_gridmap_s() {

@@ -20,6 +20,7 @@
 //                   one is 3.6 times faster on 32 scans with a window of 81 x 81 cells x 81 rotations (DESIGN.md has both timings)
 //   k_match_finish  one lane per scan: key -> result
 // Everything runs on the grid's stream in order; one upload, one wait.
+// srrg2_gridmap_build_bounds / _get_bounds / _match_scans_pruned, the same search through upper bounds, are the second half of the file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -303,7 +304,7 @@ extern "C" int srrg2_gridmap_build_likelihood(srrg2_gridmap_h h, int min_observa
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st     = h->stream();
   const size_t cells = (size_t) h->cells();
-  h->field_fresh     = false;
+  h->stale_field();  // (the bound planes are of the old field)
   if ((rc = h->field.reserve(cells + 1))) return rc;
   HIP_TRY(hipMemsetAsync(h->field.p + cells, 0, 1, st));  // what a lookup outside the grid reads
   if (cells > 0) {
@@ -336,10 +337,11 @@ extern "C" int srrg2_gridmap_get_likelihood(srrg2_gridmap_h h, uint8_t* dst, int
   return 0;
 }
 
-extern "C" int srrg2_gridmap_match_scans(srrg2_gridmap_h h, const float* ranges, int num_scans, const float* guess_robot_in_world, int mem,
-                                         const srrg2_gridmap_scan_params* p, const srrg2_gridmap_match_params* mp,
-                                         srrg2_gridmap_match_result* results, int32_t* scores_out, int scores_mem) {
-  const std::string who = "gridmap_match_scans: ";
+namespace {
+
+// what srrg2_gridmap_match_scans and srrg2_gridmap_match_scans_pruned refuse without looking at their handle
+int check_match_call(const std::string& who, const float* ranges, int num_scans, const float* guess_robot_in_world, int mem,
+                     const srrg2_gridmap_scan_params* p, const srrg2_gridmap_match_params* mp, const void* results) {
   int rc;
   if (!mp) return fail(SRRG2_E_INVALID, who + "null match params");
   if (mp->half_window_x < 0 || mp->half_window_y < 0 || mp->half_steps_theta < 0)
@@ -351,53 +353,85 @@ extern "C" int srrg2_gridmap_match_scans(srrg2_gridmap_h h, const float* ranges,
   if (num_scans > 0 && (!guess_robot_in_world || reinterpret_cast<uintptr_t>(guess_robot_in_world) % 4 != 0))
     return fail(SRRG2_E_INVALID, who + "null or misaligned guesses");
   if (num_scans > 0 && !results) return fail(SRRG2_E_INVALID, who + "null results");
-  if (scores_out && scores_mem != SRRG2_MEM_HOST && scores_mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, who + "bad scores_mem");
-  if (reinterpret_cast<uintptr_t>(scores_out) % 4 != 0) return fail(SRRG2_E_INVALID, who + "misaligned scores_out");
+  return 0;
+}
+
+// ... and of the window's size, still without the handle
+int check_match_sizes(const std::string& who, const srrg2_gridmap_match_params* mp) {
   const long long nx = 2LL * mp->half_window_x + 1, ny = 2LL * mp->half_window_y + 1, nt = 2LL * mp->half_steps_theta + 1;
   // (three factors below 2^32: the product of two is tested before the third comes in)
   if (nx * ny > 0x7fffffffLL || nx * ny * nt > 0x7fffffffLL) return fail(SRRG2_E_UNSUPPORTED, who + "candidates per scan beyond int32");
-  const long long nc = nx * ny * nt;
-  if (scores_out && nc * num_scans > 0x7fffffffLL) return fail(SRRG2_E_UNSUPPORTED, who + "score volume beyond int32 elements");
-  // (one end cell per scan, rotation and beam is kept: 8 bytes each)
-  if ((long long) num_scans * p->num_beams * nt > 0x7fffffffLL)
+  return 0;
+}
+
+// (one end cell per scan, rotation and beam is kept: 8 bytes each)
+int check_match_cells(const std::string& who, int num_scans, const srrg2_gridmap_scan_params* p, const srrg2_gridmap_match_params* mp) {
+  if ((long long) num_scans * p->num_beams * (2LL * mp->half_steps_theta + 1) > 0x7fffffffLL)
     return fail(SRRG2_E_UNSUPPORTED, who + "num_scans * num_beams * rotations beyond int32");
-  if ((rc = srrg2amd::gridmap_ready(who, h))) return rc;
-  if (!(p->range_max / h->p.resolution <= GRIDMAP_MAX_STEPS)) return fail(SRRG2_E_INVALID, who + "range_max / resolution beyond 32000 cells");
-  if ((rc = fresh(who, h))) return rc;
-  if (num_scans == 0) return 0;
-  const int K = num_scans, nb = p->num_beams;
-  const long long beams = (long long) K * nb, prep_total = beams * nt;
-  HIP_TRY(hipSetDevice(h->device));
+  return 0;
+}
+
+// ONE upload: the ranges, then the guesses, through the pinned block (the protocol of srrg2_gridmap_integrate_scans); then what
+// the kernels need to know of the call
+int stage_match(srrg2_gridmap_s* h, const float* ranges, int K, const float* guess_robot_in_world, int mem, const srrg2_gridmap_scan_params* p,
+                const srrg2_gridmap_match_params* mp, MatchArgs& A) {
+  int rc;
   hipStream_t st = h->stream();
-  MatchArgs A;
+  const int nb   = p->num_beams;
   std::memset(&A, 0, sizeof(A));
   A.ranges = ranges, A.guesses = guess_robot_in_world;
-  {  // ONE upload: the ranges, then the guesses, through the pinned block (the protocol of srrg2_gridmap_integrate_scans)
-    const size_t br = (size_t) beams * 4, bp = (size_t) K * 36;
-    if (mem == SRRG2_MEM_HOST) {
-      if (h->upload_pending) {
-        HIP_TRY(hipEventSynchronize(h->uploaded));
-        h->upload_pending = false;
-      }
-      if ((rc = h->host_stage.reserve(br + bp, (br + bp) / 8)) || (rc = h->stage.reserve(br + bp))) return rc;
-      if (br) std::memcpy(h->host_stage.p, ranges, br);
-      std::memcpy(h->host_stage.p + br, guess_robot_in_world, bp);
-      HIP_TRY(hipMemcpyAsync(h->stage.p, h->host_stage.p, br + bp, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipEventRecord(h->uploaded, st));
-      h->upload_pending = true;
-      A.ranges  = reinterpret_cast<const float*>(h->stage.p);
-      A.guesses = reinterpret_cast<const float*>(h->stage.p + br);
+  const size_t br = (size_t) K * nb * 4, bp = (size_t) K * 36;
+  if (mem == SRRG2_MEM_HOST) {
+    if (h->upload_pending) {
+      HIP_TRY(hipEventSynchronize(h->uploaded));
+      h->upload_pending = false;
     }
+    if ((rc = h->host_stage.reserve(br + bp, (br + bp) / 8)) || (rc = h->stage.reserve(br + bp))) return rc;
+    if (br) std::memcpy(h->host_stage.p, ranges, br);
+    std::memcpy(h->host_stage.p + br, guess_robot_in_world, bp);
+    HIP_TRY(hipMemcpyAsync(h->stage.p, h->host_stage.p, br + bp, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(h->uploaded, st));
+    h->upload_pending = true;
+    A.ranges  = reinterpret_cast<const float*>(h->stage.p);
+    A.guesses = reinterpret_cast<const float*>(h->stage.p + br);
   }
   A.K = K, A.nb = nb;
   A.amin = p->angle_min, A.ainc = p->angle_increment;
   A.rmin = p->range_min, A.rmax = p->range_max;
   std::memcpy(A.S, p->sensor_in_robot, sizeof(A.S));
   A.wx = mp->half_window_x, A.wy = mp->half_window_y, A.ht = mp->half_steps_theta;
-  A.nx = (int) nx, A.ny = (int) ny, A.nt = (int) nt, A.nc = (int) nc;
+  A.nx = 2 * A.wx + 1, A.ny = 2 * A.wy + 1, A.nt = 2 * A.ht + 1, A.nc = A.nx * A.ny * A.nt;
   A.step = mp->theta_step;
   A.rows = h->p.rows, A.cols = h->p.cols;
   A.ox = h->p.origin[0], A.oy = h->p.origin[1], A.res = h->p.resolution;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int srrg2_gridmap_match_scans(srrg2_gridmap_h h, const float* ranges, int num_scans, const float* guess_robot_in_world, int mem,
+                                         const srrg2_gridmap_scan_params* p, const srrg2_gridmap_match_params* mp,
+                                         srrg2_gridmap_match_result* results, int32_t* scores_out, int scores_mem) {
+  const std::string who = "gridmap_match_scans: ";
+  int rc;
+  if ((rc = check_match_call(who, ranges, num_scans, guess_robot_in_world, mem, p, mp, results))) return rc;
+  if (scores_out && scores_mem != SRRG2_MEM_HOST && scores_mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, who + "bad scores_mem");
+  if (reinterpret_cast<uintptr_t>(scores_out) % 4 != 0) return fail(SRRG2_E_INVALID, who + "misaligned scores_out");
+  if ((rc = check_match_sizes(who, mp))) return rc;
+  const long long nx = 2LL * mp->half_window_x + 1, ny = 2LL * mp->half_window_y + 1, nt = 2LL * mp->half_steps_theta + 1;
+  const long long nc = nx * ny * nt;
+  if (scores_out && nc * num_scans > 0x7fffffffLL) return fail(SRRG2_E_UNSUPPORTED, who + "score volume beyond int32 elements");
+  if ((rc = check_match_cells(who, num_scans, p, mp))) return rc;
+  if ((rc = srrg2amd::gridmap_ready(who, h))) return rc;
+  if (!(p->range_max / h->p.resolution <= GRIDMAP_MAX_STEPS)) return fail(SRRG2_E_INVALID, who + "range_max / resolution beyond 32000 cells");
+  if ((rc = fresh(who, h))) return rc;
+  if (num_scans == 0) return 0;
+  const int K = num_scans;
+  const long long prep_total = (long long) K * p->num_beams * nt;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = h->stream();
+  MatchArgs A;
+  if ((rc = stage_match(h, ranges, K, guess_robot_in_world, mem, p, mp, A))) return rc;
   const bool to_host = scores_out && scores_mem == SRRG2_MEM_HOST;
   if ((rc = h->match_cells.reserve((size_t) prep_total + 1)) || (rc = h->match_words.reserve(2 * (size_t) K)) ||
       (rc = h->match_results.reserve((size_t) K)) || (rc = h->match_results_host.reserve((size_t) K, (size_t) K / 8)) ||
@@ -445,5 +479,466 @@ extern "C" int srrg2_gridmap_match_scans(srrg2_gridmap_h h, const float* ranges,
   HIP_TRY(hipStreamSynchronize(st));  // the one wait
   h->upload_pending = false;
   std::memcpy(results, h->match_results_host.p, (size_t) K * sizeof(srrg2_gridmap_match_result));
+  return 0;
+}
+
+// ---- pruned scan matching (DESIGN.md section 4 "Pruned scan matching", tests/scan_match_pruned_restatement.py) -------------------
+// The window of srrg2_gridmap_match_scans searched through bound planes: P_l holds per cell the maximum of the field over the block
+// of side 2^l that starts there, so the sum of P_l under a rotation's beam cells, moved to a block's first shift, bounds every
+// candidate of the block.  Level-synchronous, one launch per step, sized from counts in device memory:
+//   k_bounds_build     P_l from P_(l-1): one lane per byte, a 2 x 2 maximum at offset 2^(l-1)
+//   k_prune_top        the dense top level, the shape of k_match_score: a workgroup owns one (scan, rotation) and 256 blocks, the
+//                      live beam cells come through LDS; a wave's lookups for one beam are bytes 2^L apart.  Writes every bound
+//                      and, with one atomicMax per workgroup, the scan's seed (highest bound, lowest flat block index)
+//   k_prune_seed       the seed block's candidates and the guess, exactly: the floor is the score part of the scan's word
+//   k_prune_expand_top the top blocks against the floor; the children of the survivors go to the scan's list
+//   k_prune_level      one lane per listed block: its bound (beam cells from global memory), the survival test, its children
+//   k_prune_exact      one lane per listed candidate: its score, one atomicMax per workgroup
+//   k_prune_fallback   launched always: a scan whose list overflowed is scored exhaustively, one lane per candidate; without such
+//                      a scan every workgroup leaves after reading K flags
+//   k_prune_stats      one lane per scan
+// A list belongs to one scan (its segment of `cap` entries): a workgroup reserves room for its children with ONE atomicAdd on the
+// scan's counter, which goes on counting past the segment's end -- whether a scan falls back depends on its inputs alone.
+namespace {
+
+enum { MAX_LEVELS = 6, BOUNDS_BLOCKS = 2048, TOP_BLOCKS = 2048, SEED_BLOCKS = 1024, EXPAND_BLOCKS = 512, LIST_BLOCKS = 256, FALLBACK_BLOCKS = 2048 };
+enum { DEFAULT_LIST_ENTRIES = 1 << 20 };
+// per scan: the floor, whether the guess holds it, the seed block; per level the entries listed for it and its survivors
+enum { ST_FLOOR = 0, ST_STRICT = 1, ST_SEED = 2, ST_COUNT = 4, ST_SURV = ST_COUNT + MAX_LEVELS + 1, STATE_INTS = ST_SURV + MAX_LEVELS + 1 };
+
+// a bound plane (or the field: s = 1): P(x, y) = p[(y + s - 1) * W + x + s - 1] inside, p[zero] = 0 outside
+struct Plane {
+  const unsigned char* p;
+  long long zero;
+  int W, H, s;
+};
+
+__global__ __launch_bounds__(256) void k_bounds_build(const unsigned char* __restrict__ prev, int pw, int ph, unsigned char* __restrict__ out,
+                                                      int ow, int oh, int half) {
+  const long long total = (long long) ow * oh;
+  for (long long i = (long long) blockIdx.x * 256 + threadIdx.x; i < total; i += (long long) gridDim.x * 256) {
+    const int Y = (int) (i / ow), X = (int) (i - (long long) Y * ow);
+    unsigned best = 0;
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        const int y = Y - b * half, x = X - a * half;
+        if ((unsigned) y < (unsigned) ph && (unsigned) x < (unsigned) pw) best = max(best, (unsigned) prev[(long long) y * pw + x]);
+      }
+    out[i] = (unsigned char) best;
+  }
+}
+
+// the sum of P under the beam cells of one (scan, rotation), read from global memory, moved by (ox, oy) plane cells
+__device__ __forceinline__ int sum_under(const Plane& pl, const int2* __restrict__ mine, int nb, long long ox, long long oy) {
+  int acc = 0;
+  for (int b = 0; b < nb; ++b) {
+    const int2 c = mine[b];
+    if (c.x == DEAD) continue;
+    const long long X = c.x + ox, Y = c.y + oy;
+    const bool ok = X >= 0 && X < pl.W && Y >= 0 && Y < pl.H;
+    acc += (int) pl.p[ok ? Y * pl.W + X : pl.zero];
+  }
+  return acc;
+}
+
+// the greatest key of the workgroup, in thread 0 (red: 4 words of LDS; every thread calls)
+__device__ __forceinline__ unsigned long long block_max(unsigned long long v, unsigned long long* red) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = max(v, (unsigned long long) __shfl_xor((long long) v, o));
+  __syncthreads();  // (thread 0 has read red[] of the round before)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return max(max(red[0], red[1]), max(red[2], red[3]));
+}
+
+__global__ __launch_bounds__(256) void k_prune_top(MatchArgs A, Plane pl, int nbx, int nby, long long tiles, int chunks,
+                                                   const int2* __restrict__ cells, int* __restrict__ top, unsigned long long* __restrict__ seeds) {
+  __shared__ int2 sb[BEAM_CHUNK];
+  __shared__ int n_live;
+  __shared__ unsigned long long red[4];
+  const int t  = threadIdx.x;
+  const int NB = nbx * nby;  // (<= Nx Ny)
+  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int chunk = (int) (tile % chunks);
+    const long long rest = tile / chunks;
+    const int jj = (int) (rest % A.nt), scan = (int) (rest / A.nt);
+    const long long q = (long long) chunk * 256 + t;
+    const bool holds  = q < NB;
+    const int by = holds ? (int) (q / nbx) : 0, bx = holds ? (int) (q - (long long) by * nbx) : 0;
+    const long long ox = (long long) bx * pl.s - A.wx + pl.s - 1, oy = (long long) by * pl.s - A.wy + pl.s - 1;
+    const int2* const mine = cells + ((long long) scan * A.nt + jj) * A.nb;
+    int acc = 0;
+    for (int b0 = 0; b0 < A.nb; b0 += BEAM_CHUNK) {
+      __syncthreads();
+      if (t == 0) n_live = 0;
+      __syncthreads();
+      const int end = min(A.nb, b0 + BEAM_CHUNK);
+      for (int b = b0 + t; b < end; b += 256) {
+        const int2 c = mine[b];
+        if (c.x != DEAD) sb[atomicAdd(&n_live, 1)] = c;  // (integer adds commute: the order is free)
+      }
+      __syncthreads();
+      const int n = n_live;
+      for (int i = 0; holds && i < n; ++i) {
+        const int2 c = sb[i];
+        const long long X = c.x + ox, Y = c.y + oy;
+        const bool ok = X >= 0 && X < pl.W && Y >= 0 && Y < pl.H;
+        acc += (int) pl.p[ok ? Y * pl.W + X : pl.zero];
+      }
+    }
+    unsigned long long key = 0;
+    if (holds) {
+      top[((long long) scan * A.nt + jj) * NB + q] = acc;
+      key = ((unsigned long long) (unsigned) acc << 32) | (unsigned long long) (0x7fffffffu - (unsigned) ((long long) jj * NB + q));
+    }
+    const unsigned long long m = block_max(key, red);
+    if (t == 0 && m) atomicMax(&seeds[scan], m);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_prune_seed(MatchArgs A, Plane field, int L, int nbx, int nby, long long tiles, int parts,
+                                                    const int2* __restrict__ cells, const unsigned long long* __restrict__ seeds,
+                                                    unsigned long long* __restrict__ words, int* __restrict__ aux) {
+  __shared__ unsigned long long red[4];
+  const int t = threadIdx.x, s = 1 << L, NB = nbx * nby;
+  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int scan = (int) (tile / parts), part = (int) (tile - (long long) scan * parts);
+    const int block = (int) (0x7fffffffu - ((unsigned) seeds[scan] & 0x7fffffffu));
+    const int jb = block / NB, q = block - jb * NB;
+    const int by = q / nbx, bx = q - by * nbx;
+    const int i = part * 256 + t;  // a candidate of the seed block; the one behind them is the guess
+    long long dxi = (long long) bx * s + (i & (s - 1)), dyi = (long long) by * s + (i >> L);
+    int jj = jb;
+    if (i == s * s) dxi = A.wx, dyi = A.wy, jj = A.ht;
+    unsigned long long key = 0;
+    if (i <= s * s && dxi < A.nx && dyi < A.ny) {
+      const int score     = sum_under(field, cells + ((long long) scan * A.nt + jj) * A.nb, A.nb, dxi - A.wx, dyi - A.wy);
+      const bool is_guess = jj == A.ht && dyi == A.wy && dxi == A.wx;
+      if (is_guess) aux[2 * scan] = score;
+      key = key_of(score, is_guess, (int) (((long long) jj * A.ny + dyi) * A.nx + dxi));
+    }
+    const unsigned long long m = block_max(key, red);
+    if (t == 0 && m) atomicMax(&words[scan], m);
+  }
+}
+
+// the children inside the window of the workgroup's surviving blocks go to the scan's next list: ONE atomicAdd per workgroup
+// reserves their room (and one counts the survivors); what lies past the segment's end is counted, not written.  Every thread of
+// the workgroup calls; sh: 9 ints of LDS.
+__device__ __forceinline__ void emit_children(bool alive, int jj, int by, int bx, int half, int cnbx, int cnby, const MatchArgs& A, int cap,
+                                              int* __restrict__ count, int* __restrict__ survivors, int* __restrict__ out, int* sh) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int kx = alive ? 1 + ((2LL * bx + 1) * half < A.nx ? 1 : 0) : 0, ky = alive ? 1 + ((2LL * by + 1) * half < A.ny ? 1 : 0) : 0;
+  const int c  = kx * ky;
+  int inc      = c;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(inc, o);
+    if (lane >= o) inc += v;
+  }
+  const unsigned long long mask = __ballot(alive);
+  if (lane == 63) sh[w] = inc;
+  if (lane == 0) sh[4 + w] = __popcll(mask);
+  __syncthreads();
+  if (t == 0) {
+    const int total = sh[0] + sh[1] + sh[2] + sh[3], ns = sh[4] + sh[5] + sh[6] + sh[7];
+    sh[8] = total ? atomicAdd(count, total) : 0;
+    if (ns) atomicAdd(survivors, ns);
+  }
+  __syncthreads();
+  long long at = (long long) sh[8] + inc - c;
+  for (int u = 0; u < w; ++u) at += sh[u];
+  for (int b = 0; b < ky; ++b)
+    for (int a = 0; a < kx; ++a, ++at)
+      if (at < cap) out[at] = (int) (((long long) jj * cnby + 2 * by + b) * cnbx + 2 * bx + a);
+  __syncthreads();  // (sh is the next round's too)
+}
+
+// the workgroup's first chunk of a scan's entries: turned by the scan, so that short lists of many scans spread over the launch
+__device__ __forceinline__ long long first_chunk(int scan) {
+  return (long long) ((blockIdx.x + gridDim.x - (unsigned) scan % gridDim.x) % gridDim.x) * 256;
+}
+
+__global__ __launch_bounds__(256) void k_prune_expand_top(MatchArgs A, int L, int nbx, int nby, int cnbx, int cnby, int cap,
+                                                          const int* __restrict__ top, const unsigned long long* __restrict__ seeds,
+                                                          const unsigned long long* __restrict__ words, const int* __restrict__ aux,
+                                                          int* __restrict__ state, int* __restrict__ lists) {
+  __shared__ int sh[9];
+  const int t = threadIdx.x, NB = nbx * nby;
+  const long long n = (long long) A.nt * NB;
+  for (int scan = 0; scan < A.K; ++scan) {
+    int* const st     = state + (long long) scan * STATE_INTS;
+    const int floor   = (int) (words[scan] >> 32);
+    const bool strict = floor == aux[2 * scan];
+    const long long c1 = first_chunk(scan);
+    if (c1 == 0 && t == 0)
+      st[ST_FLOOR] = floor, st[ST_STRICT] = strict, st[ST_SEED] = (int) (0x7fffffffu - ((unsigned) seeds[scan] & 0x7fffffffu));
+    for (long long c0 = c1; c0 < n; c0 += (long long) gridDim.x * 256) {
+      const long long i = c0 + t;
+      bool alive = false;
+      int jj = 0, by = 0, bx = 0;
+      if (i < n) {
+        const int U = top[scan * n + i];
+        jj = (int) (i / NB);
+        const int q = (int) (i - (long long) jj * NB);
+        by = q / nbx, bx = q - by * nbx;
+        alive = strict ? U > floor : U >= floor;
+      }
+      emit_children(alive, jj, by, bx, 1 << (L - 1), cnbx, cnby, A, cap, st + ST_COUNT + L - 1, st + ST_SURV + L,
+                    lists + ((long long) ((L - 1) & 1) * A.K + scan) * cap, sh);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_prune_level(MatchArgs A, Plane pl, int l, int nbx, int nby, int cnbx, int cnby, int limit, int cap,
+                                                     const int2* __restrict__ cells, int* __restrict__ state, int* __restrict__ lists) {
+  __shared__ int sh[9];
+  const int t = threadIdx.x;
+  for (int scan = 0; scan < A.K; ++scan) {
+    int* const st = state + (long long) scan * STATE_INTS;
+    const int n   = st[ST_COUNT + l];
+    if (n == 0 || n > limit) continue;  // (over the limit: the scan falls back)
+    const int floor = st[ST_FLOOR];
+    const bool strict = st[ST_STRICT] != 0;
+    const int* const in = lists + ((long long) (l & 1) * A.K + scan) * cap;
+    for (long long c0 = first_chunk(scan); c0 < n; c0 += (long long) gridDim.x * 256) {
+      const long long i = c0 + t;
+      bool alive = false;
+      int jj = 0, by = 0, bx = 0;
+      if (i < n) {
+        const int flat = in[i];
+        const int rest = flat / nbx;
+        bx = flat - rest * nbx, jj = rest / nby, by = rest - jj * nby;
+        const int U = sum_under(pl, cells + ((long long) scan * A.nt + jj) * A.nb, A.nb, (long long) bx * pl.s - A.wx + pl.s - 1,
+                                (long long) by * pl.s - A.wy + pl.s - 1);
+        alive = strict ? U > floor : U >= floor;
+      }
+      emit_children(alive, jj, by, bx, pl.s >> 1, cnbx, cnby, A, cap, st + ST_COUNT + l - 1, st + ST_SURV + l,
+                    lists + ((long long) ((l - 1) & 1) * A.K + scan) * cap, sh);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_prune_exact(MatchArgs A, Plane field, int limit, int cap, const int2* __restrict__ cells,
+                                                     const int* __restrict__ state, const int* __restrict__ lists,
+                                                     unsigned long long* __restrict__ words) {
+  __shared__ unsigned long long red[4];
+  const int t = threadIdx.x;
+  for (int scan = 0; scan < A.K; ++scan) {
+    const int n = state[(long long) scan * STATE_INTS + ST_COUNT];
+    if (n == 0 || n > limit) continue;
+    const int* const in = lists + (long long) scan * cap;
+    unsigned long long key = 0;
+    for (long long i = first_chunk(scan) + t; i < n; i += (long long) gridDim.x * 256) {
+      const int flat = in[i];
+      const int dxi = flat % A.nx, rest = flat / A.nx;
+      const int dyi = rest % A.ny, jj = rest / A.ny;
+      const int score = sum_under(field, cells + ((long long) scan * A.nt + jj) * A.nb, A.nb, (long long) dxi - A.wx, (long long) dyi - A.wy);
+      key = max(key, key_of(score, jj == A.ht && dyi == A.wy && dxi == A.wx, flat));
+    }
+    const unsigned long long m = block_max(key, red);
+    if (t == 0 && m) atomicMax(&words[scan], m);
+  }
+}
+
+__device__ __forceinline__ bool fell_back(const int* st, int L, int limit) {
+  bool fell = false;
+  for (int l = 0; l < L; ++l) fell |= st[ST_COUNT + l] > limit;
+  return fell;
+}
+
+__global__ __launch_bounds__(256) void k_prune_fallback(MatchArgs A, Plane field, int L, int limit, const int2* __restrict__ cells,
+                                                        const int* __restrict__ state, unsigned long long* __restrict__ words) {
+  __shared__ unsigned long long red[4];
+  for (int scan = 0; scan < A.K; ++scan) {
+    if (!fell_back(state + (long long) scan * STATE_INTS, L, limit)) continue;
+    unsigned long long key = 0;
+    for (long long i = (long long) blockIdx.x * 256 + threadIdx.x; i < A.nc; i += (long long) gridDim.x * 256) {
+      const int flat = (int) i;
+      const int dxi = flat % A.nx, rest = flat / A.nx;
+      const int dyi = rest % A.ny, jj = rest / A.ny;
+      const int score = sum_under(field, cells + ((long long) scan * A.nt + jj) * A.nb, A.nb, (long long) dxi - A.wx, (long long) dyi - A.wy);
+      key = max(key, key_of(score, jj == A.ht && dyi == A.wy && dxi == A.wx, flat));
+    }
+    const unsigned long long m = block_max(key, red);
+    if (threadIdx.x == 0 && m) atomicMax(&words[scan], m);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_prune_stats(MatchArgs A, int L, int limit, int top_blocks, const int* __restrict__ state,
+                                                     srrg2_gridmap_prune_stats* __restrict__ out) {
+  const int scan = blockIdx.x * 256 + threadIdx.x;
+  if (scan >= A.K) return;
+  const int* const st = state + (long long) scan * STATE_INTS;
+  srrg2_gridmap_prune_stats* const o = out + scan;
+  int over = -1;  // the highest level whose list overflowed
+  for (int l = L - 1; l >= 0 && over < 0; --l)
+    if (st[ST_COUNT + l] > limit) over = l;
+  o->num_candidates = A.nc;
+  for (int l = 0; l <= MAX_LEVELS; ++l) {
+    o->num_evaluated[l] = l == L ? top_blocks : (l < L && l > over ? st[ST_COUNT + l] : 0);
+    o->num_survivors[l] = l >= 1 && l <= L && l > over ? st[ST_SURV + l] : 0;
+  }
+  if (over >= 0) o->num_evaluated[0] = A.nc;
+  o->floor_score = st[ST_FLOOR], o->seed_block = st[ST_SEED], o->fell_back = over >= 0;
+}
+
+int check_levels(const std::string& who, int num_levels) {
+  if (num_levels < 1 || num_levels > MAX_LEVELS) return fail(SRRG2_E_INVALID, who + "num_levels 1 .. 6");
+  return 0;
+}
+
+// level l of the planes as they are built (0: the field)
+Plane plane_of(const srrg2_gridmap_s* h, int l) {
+  Plane pl;
+  pl.s = 1 << l, pl.W = h->p.cols + pl.s - 1, pl.H = h->p.rows + pl.s - 1;
+  pl.p    = l == 0 ? h->field.p : h->bounds.p + h->bounds_at[l];
+  pl.zero = l == 0 ? h->cells() : h->bounds_at[0] - h->bounds_at[l];
+  return pl;
+}
+
+}  // namespace
+
+extern "C" void srrg2_gridmap_default_prune_params(srrg2_gridmap_prune_params* p) {
+  if (!p) return;
+  p->num_levels = 4, p->max_list_entries = 0;
+}
+
+extern "C" int srrg2_gridmap_build_bounds(srrg2_gridmap_h h, int num_levels) {
+  const std::string who = "gridmap_build_bounds: ";
+  int rc;
+  if ((rc = check_levels(who, num_levels)) || (rc = srrg2amd::gridmap_ready(who, h)) || (rc = fresh(who, h))) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st   = h->stream();
+  h->bounds_levels = 0;
+  long long at = 0;
+  for (int l = 1; l <= num_levels; ++l) {
+    h->bounds_at[l] = at;
+    at += (long long) (h->p.rows + (1 << l) - 1) * (h->p.cols + (1 << l) - 1);
+  }
+  h->bounds_at[0] = at;  // the zero byte
+  if ((rc = h->bounds.reserve((size_t) at + 1))) return rc;
+  HIP_TRY(hipMemsetAsync(h->bounds.p + at, 0, 1, st));
+  for (int l = 1; l <= num_levels; ++l) {
+    const int half = 1 << (l - 1);
+    const int pw = h->p.cols + half - 1, ph = h->p.rows + half - 1, ow = h->p.cols + 2 * half - 1, oh = h->p.rows + 2 * half - 1;
+    const int blocks = (int) std::min<long long>(((long long) ow * oh + 255) / 256, BOUNDS_BLOCKS);
+    hipLaunchKernelGGL(k_bounds_build, dim3(blocks), dim3(256), 0, st, l == 1 ? h->field.p : h->bounds.p + h->bounds_at[l - 1], pw, ph,
+                       h->bounds.p + h->bounds_at[l], ow, oh, half);
+    HIP_TRY(hipGetLastError());
+  }
+  h->bounds_levels = num_levels;
+  return 0;
+}
+
+extern "C" int srrg2_gridmap_get_bounds(srrg2_gridmap_h h, int level, uint8_t* dst, int row_stride_bytes, int mem) {
+  const std::string who = "gridmap_get_bounds: ";
+  if (mem != SRRG2_MEM_HOST && mem != SRRG2_MEM_DEVICE) return fail(SRRG2_E_INVALID, who + "bad mem");
+  if (level < 1 || level > MAX_LEVELS) return fail(SRRG2_E_INVALID, who + "level 1 .. 6");
+  int rc;
+  if ((rc = srrg2amd::gridmap_ready(who, h)) || (rc = fresh(who, h))) return rc;
+  if (h->bounds_levels == 0) return fail(SRRG2_E_INVALID, who + "the bound planes are stale or were never built (srrg2_gridmap_build_bounds)");
+  if (level > h->bounds_levels) return fail(SRRG2_E_INVALID, who + "level above the number of levels built");
+  const Plane pl = plane_of(h, level);
+  if (!dst) return fail(SRRG2_E_INVALID, who + "null image");
+  if (row_stride_bytes < pl.W) return fail(SRRG2_E_INVALID, who + "row stride smaller than a row");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipMemcpy2DAsync(dst, (size_t) row_stride_bytes, pl.p, (size_t) pl.W, (size_t) pl.W, (size_t) pl.H,
+                           mem == SRRG2_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream()));
+  HIP_TRY(hipStreamSynchronize(h->stream()));
+  h->upload_pending = false;
+  return 0;
+}
+
+extern "C" int srrg2_gridmap_match_scans_pruned(srrg2_gridmap_h h, const float* ranges, int num_scans, const float* guess_robot_in_world,
+                                                int mem, const srrg2_gridmap_scan_params* p, const srrg2_gridmap_match_params* mp,
+                                                const srrg2_gridmap_prune_params* pp, srrg2_gridmap_match_result* results,
+                                                srrg2_gridmap_prune_stats* stats) {
+  const std::string who = "gridmap_match_scans_pruned: ";
+  int rc;
+  if ((rc = check_match_call(who, ranges, num_scans, guess_robot_in_world, mem, p, mp, results))) return rc;
+  if (!pp) return fail(SRRG2_E_INVALID, who + "null prune params");
+  if ((rc = check_levels(who, pp->num_levels))) return rc;
+  if (pp->max_list_entries < 0) return fail(SRRG2_E_INVALID, who + "max_list_entries >= 0");
+  if ((rc = check_match_sizes(who, mp)) || (rc = check_match_cells(who, num_scans, p, mp))) return rc;
+  if ((rc = srrg2amd::gridmap_ready(who, h))) return rc;
+  if (!(p->range_max / h->p.resolution <= GRIDMAP_MAX_STEPS)) return fail(SRRG2_E_INVALID, who + "range_max / resolution beyond 32000 cells");
+  if ((rc = fresh(who, h))) return rc;
+  if (h->bounds_levels == 0) return fail(SRRG2_E_INVALID, who + "the bound planes are stale or were never built (srrg2_gridmap_build_bounds)");
+  if (pp->num_levels > h->bounds_levels) return fail(SRRG2_E_INVALID, who + "num_levels above the number of levels built");
+  if (num_scans == 0) return 0;
+  const int K = num_scans, L = pp->num_levels;
+  const int limit = pp->max_list_entries > 0 ? pp->max_list_entries : DEFAULT_LIST_ENTRIES;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = h->stream();
+  MatchArgs A;
+  if ((rc = stage_match(h, ranges, K, guess_robot_in_world, mem, p, mp, A))) return rc;
+  int nbx[MAX_LEVELS + 1], nby[MAX_LEVELS + 1];
+  for (int l = 0; l <= L; ++l) nbx[l] = (int) (((long long) A.nx + (1 << l) - 1) >> l), nby[l] = (int) (((long long) A.ny + (1 << l) - 1) >> l);
+  const long long prep_total = (long long) K * A.nb * A.nt;
+  const long long top_blocks = (long long) A.nt * nbx[L] * nby[L];  // per scan (<= the candidates)
+  const int cap              = std::min(limit, A.nc);                // entries of a scan's list
+  if ((rc = h->match_cells.reserve((size_t) prep_total + 1)) || (rc = h->match_words.reserve(3 * (size_t) K)) ||
+      (rc = h->match_results.reserve((size_t) K)) || (rc = h->match_results_host.reserve((size_t) K, (size_t) K / 8)) ||
+      (rc = h->prune_top.reserve((size_t) top_blocks * K)) || (rc = h->prune_lists.reserve(2 * (size_t) K * cap)) ||
+      (rc = h->prune_state.reserve((size_t) K * STATE_INTS)) || (rc = h->prune_stats.reserve((size_t) K)) ||
+      (rc = h->prune_stats_host.reserve((size_t) K, (size_t) K / 8)))
+    return rc;
+  unsigned long long* const words = h->match_words.p;
+  int* const aux                  = reinterpret_cast<int*>(words + K);
+  unsigned long long* const seeds = words + 2 * (size_t) K;
+  HIP_TRY(hipMemsetAsync(words, 0, 3 * (size_t) K * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(h->prune_state.p, 0, (size_t) K * STATE_INTS * sizeof(int), st));
+  if (prep_total > 0) {
+    const int blocks = (int) std::min<long long>((prep_total + 255) / 256, MAX_PREP_BLOCKS);
+    hipLaunchKernelGGL(k_match_prep, dim3(blocks), dim3(256), 0, st, A, prep_total, h->match_cells.p, aux);
+    HIP_TRY(hipGetLastError());
+  }
+  const Plane field = plane_of(h, 0);
+  {
+    const int chunks      = (int) (((long long) nbx[L] * nby[L] + 255) / 256);
+    const long long tiles = (long long) K * A.nt * chunks;
+    hipLaunchKernelGGL(k_prune_top, dim3((int) std::min<long long>(tiles, TOP_BLOCKS)), dim3(256), 0, st, A, plane_of(h, L), nbx[L], nby[L], tiles,
+                       chunks, h->match_cells.p, h->prune_top.p, seeds);
+    HIP_TRY(hipGetLastError());
+  }
+  {
+    const int parts       = ((1 << (2 * L)) + 1 + 255) / 256;
+    const long long tiles = (long long) K * parts;
+    hipLaunchKernelGGL(k_prune_seed, dim3((int) std::min<long long>(tiles, SEED_BLOCKS)), dim3(256), 0, st, A, field, L, nbx[L], nby[L], tiles,
+                       parts, h->match_cells.p, seeds, words, aux);
+    HIP_TRY(hipGetLastError());
+  }
+  {
+    const long long chunks = (top_blocks + 255) / 256;
+    hipLaunchKernelGGL(k_prune_expand_top, dim3((int) std::min<long long>(chunks, EXPAND_BLOCKS)), dim3(256), 0, st, A, L, nbx[L], nby[L],
+                       nbx[L - 1], nby[L - 1], cap, h->prune_top.p, seeds, words, aux, h->prune_state.p, h->prune_lists.p);
+    HIP_TRY(hipGetLastError());
+  }
+  // (a list holds at most `cap` entries: the launches below are sized for that and stride over what the counters say)
+  const int list_blocks = std::min((cap + 255) / 256, (int) LIST_BLOCKS);
+  for (int l = L - 1; l >= 1; --l) {
+    hipLaunchKernelGGL(k_prune_level, dim3(list_blocks), dim3(256), 0, st, A, plane_of(h, l), l, nbx[l], nby[l], nbx[l - 1], nby[l - 1], limit, cap,
+                       h->match_cells.p, h->prune_state.p, h->prune_lists.p);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_prune_exact, dim3(list_blocks), dim3(256), 0, st, A, field, limit, cap, h->match_cells.p, h->prune_state.p,
+                     h->prune_lists.p, words);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_prune_fallback, dim3((int) std::min<long long>(((long long) A.nc + 255) / 256, FALLBACK_BLOCKS)), dim3(256), 0, st, A, field,
+                     L, limit, h->match_cells.p, h->prune_state.p, words);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_match_finish, dim3((K + 255) / 256), dim3(256), 0, st, A, words, aux, h->match_results.p);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_prune_stats, dim3((K + 255) / 256), dim3(256), 0, st, A, L, limit, (int) top_blocks, h->prune_state.p, h->prune_stats.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h->match_results_host.p, h->match_results.p, (size_t) K * sizeof(srrg2_gridmap_match_result), hipMemcpyDeviceToHost, st));
+  if (stats) HIP_TRY(hipMemcpyAsync(h->prune_stats_host.p, h->prune_stats.p, (size_t) K * sizeof(srrg2_gridmap_prune_stats), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));  // the one wait
+  h->upload_pending = false;
+  std::memcpy(results, h->match_results_host.p, (size_t) K * sizeof(srrg2_gridmap_match_result));
+  if (stats) std::memcpy(stats, h->prune_stats_host.p, (size_t) K * sizeof(srrg2_gridmap_prune_stats));
   return 0;
 }

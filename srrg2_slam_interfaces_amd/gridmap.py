@@ -9,9 +9,12 @@ which cells of a 2-D grid are free, occupied or never seen, on the device.
                    ``build_likelihood()`` smooths the occupied cells into a likelihood field, ``match_scans(ranges, guesses, ...)``
                    scores every pose of a window around each guess against it and returns the best (a pose for a scan whose
                    guess is too far off for ICP); ``likelihood()`` reads the field.
+                   ``build_bounds()`` builds the pyramid of upper bounds over the field, ``match_scans_pruned`` searches the
+                   same window through it (the same answer without scoring most of it) and ``localize(ranges, theta_step)``
+                   places scans that have no guess at all against the whole map; ``bounds(level)`` reads a plane.
 
-Thin marshalling only; the contract is DESIGN.md section 4 "Occupancy grid" and "Correlative scan matching", its restatements
-tests/gridmap_restatement.py and tests/scan_match_restatement.py.
+Thin marshalling only; the contract is DESIGN.md section 4 "Occupancy grid", "Correlative scan matching" and "Pruned scan matching",
+its restatements tests/gridmap_restatement.py, tests/scan_match_restatement.py and tests/scan_match_pruned_restatement.py.
 """
 import ctypes as C
 
@@ -77,6 +80,7 @@ class OccupancyGrid:
         p.origin[0], p.origin[1] = float(origin[0]), float(origin[1])
         self._check(self._lib.srrg2_gridmap_reset(self._h, C.byref(p)))
         self.params = p
+        self._bounds_levels = 0  # (the levels of bound planes built from the field as it is: every call that makes it stale clears them)
 
     def set_scan_model(self, angle_min, angle_increment, num_beams, range_min=0.05, range_max=30.0, sensor_in_robot=None,
                        clear_beyond_max=True):
@@ -105,6 +109,7 @@ class OccupancyGrid:
         self._check(self._lib.srrg2_gridmap_integrate_scans(self._h, rptr, K, pptr, rmem, C.byref(self.scan), int(weight),
                                                             C.byref(out) if want_result else None))
         self._queued = (rk, pk)  # (device inputs of a queued call stay alive until the next call)
+        self._bounds_levels = 0
         return out.as_dict() if want_result else None
 
     def remove(self, ranges, poses, want_result=True):
@@ -157,6 +162,7 @@ class OccupancyGrid:
         lut = default_likelihood_lut(radius_cells) if lut is None else np.ascontiguousarray(lut, np.uint8)
         if 0 <= int(radius_cells) <= 16 and lut.size != int(radius_cells) ** 2 + 1:
             raise ValueError("lut: radius_cells^2 + 1 bytes expected")
+        self._bounds_levels = 0
         self._check(self._lib.srrg2_gridmap_build_likelihood(self._h, int(min_observations), int(occupied_percent), int(radius_cells),
                                                              C.c_void_p(lut.ctypes.data)))
 
@@ -174,13 +180,8 @@ class OccupancyGrid:
         self._check(self._lib.srrg2_gridmap_get_likelihood(self._h, C.c_void_p(out.ctypes.data), stride, abi.MEM_HOST))
         return out
 
-    def match_scans(self, ranges, guesses, half_window=(0, 0), half_steps_theta=0, theta_step=0.0, want_scores=False):
-        """every pose of the window around each scan's guess scored against the likelihood field, the best one per scan.
-        ranges: (K, num_beams) float32, guesses: (K, 3, 3) robot_in_world -- numpy arrays, or torch tensors on the device (both).
-        half_window: (wx, wy) cells; the rotations are j * theta_step, |j| <= half_steps_theta.  Returns a dict of arrays over
-        the K scans: robot_in_world (K, 3, 3), dx, dy, jtheta, score, score_at_guess, num_scored_beams; with want_scores also
-        scores, the whole volume (K, Ntheta, Ny, Nx) int32 -- want_scores may be a contiguous int32 torch tensor of that many
-        elements on the device, which is then filled and returned as it is."""
+    def _match_inputs(self, ranges, guesses, half_window, half_steps_theta, theta_step):
+        """what both matchers hand to the library: (keep-alives, ranges pointer, K, guesses pointer, mem, match params)"""
         nb = self.scan.num_beams
         rk, rptr, rmem, rshape = _floats(ranges, "ranges")
         pk, pptr, pmem, pshape = _floats(guesses, "guesses")
@@ -193,6 +194,24 @@ class OccupancyGrid:
         mp = abi.GridMapMatchParams()
         mp.half_window_x, mp.half_window_y, mp.half_steps_theta = int(half_window[0]), int(half_window[1]), int(half_steps_theta)
         mp.theta_step = float(theta_step)
+        return (rk, pk), rptr, K, pptr, rmem, mp
+
+    @staticmethod
+    def _match_results(res, K):
+        raw = np.frombuffer(res, np.uint8).reshape(max(K, 1), C.sizeof(abi.GridMapMatchResult))[:K]
+        out = {"robot_in_world": raw[:, :36].copy().view(np.float32).reshape(K, 3, 3)}
+        for i, name in enumerate(("dx", "dy", "jtheta", "score", "score_at_guess", "num_scored_beams")):
+            out[name] = raw[:, 36 + 4 * i:40 + 4 * i].copy().view(np.int32).reshape(K)
+        return out
+
+    def match_scans(self, ranges, guesses, half_window=(0, 0), half_steps_theta=0, theta_step=0.0, want_scores=False):
+        """every pose of the window around each scan's guess scored against the likelihood field, the best one per scan.
+        ranges: (K, num_beams) float32, guesses: (K, 3, 3) robot_in_world -- numpy arrays, or torch tensors on the device (both).
+        half_window: (wx, wy) cells; the rotations are j * theta_step, |j| <= half_steps_theta.  Returns a dict of arrays over
+        the K scans: robot_in_world (K, 3, 3), dx, dy, jtheta, score, score_at_guess, num_scored_beams; with want_scores also
+        scores, the whole volume (K, Ntheta, Ny, Nx) int32 -- want_scores may be a contiguous int32 torch tensor of that many
+        elements on the device, which is then filled and returned as it is."""
+        keep, rptr, K, pptr, rmem, mp = self._match_inputs(ranges, guesses, half_window, half_steps_theta, theta_step)
         shape = (K, 2 * mp.half_steps_theta + 1, 2 * mp.half_window_y + 1, 2 * mp.half_window_x + 1)
         res = (abi.GridMapMatchResult * max(K, 1))()
         scores, sptr, smem = None, None, abi.MEM_HOST
@@ -208,13 +227,73 @@ class OccupancyGrid:
             scores = np.zeros((1, 1, 1, 1) if refused else shape, np.int32)  # (refused: the call says why and writes nothing)
             sptr = C.c_void_p(scores.ctypes.data)
         self._check(self._lib.srrg2_gridmap_match_scans(self._h, rptr, K, pptr, rmem, C.byref(self.scan), C.byref(mp), res, sptr, smem))
-        raw = np.frombuffer(res, np.uint8).reshape(max(K, 1), C.sizeof(abi.GridMapMatchResult))[:K]
-        out = {"robot_in_world": raw[:, :36].copy().view(np.float32).reshape(K, 3, 3)}
-        for i, name in enumerate(("dx", "dy", "jtheta", "score", "score_at_guess", "num_scored_beams")):
-            out[name] = raw[:, 36 + 4 * i:40 + 4 * i].copy().view(np.int32).reshape(K)
+        out = self._match_results(res, K)
         if scores is not None:
             out["scores"] = scores
         return out
+
+    # ---- pruned scan matching (DESIGN.md section 4 "Pruned scan matching", tests/scan_match_pruned_restatement.py) -------------
+
+    def build_bounds(self, levels=4):
+        """the bound planes P_1 .. P_levels of the field as it is now (levels 1 .. 6): what ``match_scans_pruned`` and ``localize``
+        search through.  Whatever makes the field stale -- ``build_likelihood`` too -- makes them stale."""
+        self._check(self._lib.srrg2_gridmap_build_bounds(self._h, int(levels)))
+        self._bounds_levels = int(levels)
+
+    def bounds(self, level):
+        """(rows + s - 1, cols + s - 1) uint8, s = 2^level: [y + s - 1, x + s - 1] is the maximum of the field over the cells
+        [x, x + s) x [y, y + s) inside the grid"""
+        rows, cols = self.shape
+        s = 1 << max(0, min(int(level), 6))
+        out = np.zeros((rows + s - 1, cols + s - 1), np.uint8)
+        self._check(self._lib.srrg2_gridmap_get_bounds(self._h, int(level), C.c_void_p(out.ctypes.data), cols + s - 1, abi.MEM_HOST))
+        return out
+
+    def match_scans_pruned(self, ranges, guesses, half_window=(0, 0), half_steps_theta=0, theta_step=0.0, levels=None, max_list_entries=0,
+                           want_stats=False):
+        """``match_scans`` through the bound planes: the same inputs, bit for bit the same dict (there is no volume), without
+        scoring most of the window.  levels: how many of the built levels to use (None: all of them); max_list_entries: the
+        blocks one scan may have listed at one level before it falls back to the exhaustive search (0: 2^20).  With want_stats
+        the dict has "stats": one dict per scan (srrg2_gridmap_prune_stats)."""
+        keep, rptr, K, pptr, rmem, mp = self._match_inputs(ranges, guesses, half_window, half_steps_theta, theta_step)
+        pp = abi.GridMapPruneParams()
+        if levels is None and getattr(self, "_bounds_levels", 0) == 0:
+            raise RuntimeError("match_scans_pruned: the bound planes are stale or were never built (build_bounds)")
+        pp.num_levels = int(self._bounds_levels if levels is None else levels)
+        pp.max_list_entries = int(max_list_entries)
+        res = (abi.GridMapMatchResult * max(K, 1))()
+        stats = (abi.GridMapPruneStats * max(K, 1))() if want_stats else None
+        self._check(self._lib.srrg2_gridmap_match_scans_pruned(self._h, rptr, K, pptr, rmem, C.byref(self.scan), C.byref(mp), C.byref(pp),
+                                                               res, stats))
+        out = self._match_results(res, K)
+        if want_stats:
+            out["stats"] = [stats[k].as_dict() for k in range(K)]
+        return out
+
+    def centre_pose(self):
+        """(3, 3) float32: the centre of cell (cols // 2, rows // 2) at heading 0 (float64 arithmetic, rounded once)"""
+        rows, cols = self.shape
+        guess = np.eye(3, dtype=np.float32)
+        guess[0, 2] = float(self.params.origin[0]) + (cols // 2 + 0.5) * float(self.params.resolution)
+        guess[1, 2] = float(self.params.origin[1]) + (rows // 2 + 0.5) * float(self.params.resolution)
+        return guess
+
+    def localize(self, ranges, theta_step, levels=None, want_stats=False):
+        """scans without any guess against the whole map: ``match_scans_pruned`` from the centre of cell (cols // 2, rows // 2) at
+        heading 0 with the half window (cols // 2, rows // 2) and ceil(pi / theta_step) steps either way, so that every cell and
+        the full turn are covered.  Builds the bound planes if they are stale (levels, or 4); the field must be fresh."""
+        rows, cols = self.shape
+        if getattr(self, "_bounds_levels", 0) < (levels or 1):
+            self.build_bounds(levels or 4)
+        nb = self.scan.num_beams
+        K = int(np.prod(_floats(ranges, "ranges")[3])) // nb if nb > 0 else 0
+        guesses = np.tile(self.centre_pose(), (K, 1, 1))
+        if hasattr(ranges, "data_ptr") and ranges.is_cuda:
+            import torch
+
+            guesses = torch.from_numpy(guesses).to(ranges.device)
+        half_steps = int(np.ceil(np.pi / float(theta_step)))
+        return self.match_scans_pruned(ranges, guesses, (cols // 2, rows // 2), half_steps, theta_step, levels, 0, want_stats)
 
 
 def default_likelihood_lut(radius_cells):
