@@ -1529,6 +1529,109 @@ int srrg2_gridmap_match_scans_pruned(srrg2_gridmap_h h, const float* ranges, int
                                      const srrg2_gridmap_prune_params* prune_params, srrg2_gridmap_match_result* results,
                                      srrg2_gridmap_prune_stats* stats /* NULL ok */);
 
+/* TSDF volume: depth frames and the poses they were taken from -> one truncated signed-distance volume on the device, the dense
+ * model of the 3-D pipeline (rectify_pair, adapt_stereo_dense / an RGB-D depth image, adapt_depth_image, the projective aligner,
+ * the SE(3) pose graph).  A raycast from a pose gives an organised scene with normals -- set_fixed of the projective point-to-plane
+ * slice: frame-to-model tracking --, the export a 3-D cloud.  No reference counterpart; DESIGN.md section 4 "TSDF volume" is the
+ * contract, tests/tsdf_restatement.py restates it and the library gives the same bits.  All float work is float32 in the written
+ * order, no FMA.
+ *   volume    nx x ny x nz voxels of voxel_size metres; origin = world position of the corner of voxel (0, 0, 0); voxel (x, y, z)
+ *             lives at plane index (z ny + y) nx + x, its centre is origin + ((float) i + 0.5f) * voxel_size per axis.  The state
+ *             is two int32 planes, sum and weight, and -- with_intensity = 1 -- a third, isum.
+ *   frame     per frame and voxel: c = world_in_camera * centre, world_in_camera = the inverse of camera_in_world formed once on
+ *             the host (transposed rotation, the translation -((a + b) + c) in float64, rounded once), rows ((m0 x + m1 y) + m2 z)
+ *             + m3; the projection of srrg2_scene_clip_projective: c.z > 0, u = (K0 c.x) / c.z + K2, v = (K4 c.y) / c.z + K5, in
+ *             view iff 0 <= u + 0.5 < cols and 0 <= v + 0.5 < rows, pixel (floor(v + 0.5), floor(u + 0.5)); d = that pixel's U16
+ *             count * depth_scale, or its F32 value: skipped unless finite and inside [depth_min, depth_max]; s = d - c.z: skipped
+ *             if s < -mu; t = min(s, mu), q = (int32) floorf((t / mu) * 32767.0f + 0.5f); sum += weight q, weight plane += weight,
+ *             isum += weight I (U8, or F32 as floorf(x + 0.5f) clamped to 0 .. 255, NaN = 0).
+ *   adds      integers only: the planes do not depend on scheduling, frame order or batch split; a batch with weight -1 after
+ *             the same batch with +1 restores them bit for bit.  No saturation.
+ *   result    num_frames; num_pixels = num_frames rows cols; num_valid_depth: the pixels of all frames that pass the depth gate;
+ *             num_voxel_updates: the adds made to the weight plane.
+ *   raycast   voxel valid iff weight >= min_weight, F = (float) sum / (float) weight.  Sample at world point p: g = (p - origin) /
+ *             voxel_size - 0.5f per axis, i0 = floorf(g), f = g - i0; valid iff all eight corners i0 + {0, 1}^3 lie in the volume
+ *             and are valid; blended along x, then y, then z as a + f (b - a).  Pixel (r, c): z_i = depth_min + (float) i * step,
+ *             i = 0 .. floorf((depth_max - depth_min) / step); camera point ((((float) c - K2) / K0) z_i, (((float) r - K5) / K4)
+ *             z_i, z_i), world point camera_in_world * that (rows as above).  Surface at the first i >= 1 with samples i - 1 and i
+ *             valid, F_{i-1} > 0 and F_i <= 0: z* = z_{i-1} + (step F_{i-1}) / (F_{i-1} - F_i); no such i, or z* outside
+ *             [depth_min, depth_max]: depth 0.0f.  Intensity: the voxel (floorf((p* - origin) / voxel_size) per axis) that holds
+ *             the world point p* of z*; inside the volume and weight >= 1: (isum + weight / 2) / weight clamped to 0 .. 255, else 0.
+ *             The depth image (and the U8 intensity image of a volume that has one) then goes through srrg2_adapt_depth_image
+ *             into dst with the caller's params: organised or compact, normals and gates are the adaptor's.  skip_empty = 1
+ *             consults a mask of 8 x 8 x 8 blocks that hold a valid voxel before it fetches a sample's corners; the bits are those of
+ *             skip_empty = 0.
+ *   to_scene  per voxel v and axis a in (x, y, z) order: v and its +a neighbour both valid, F0 and F1 of opposite sign or exactly
+ *             one of them 0 -> the point at v's centre moved by (F0 / (F0 - F1)) voxel_size along a:
+ *             origin_a + (((float) i_a + 0.5f) + F0 / (F0 - F1)) * voxel_size.  Normal: (Fx+ - Fx-, Fy+ - Fy-, Fz+ - Fz-) of v's six
+ *             neighbours divided by sqrtf((gx gx + gy gy) + gz gz); NaN when a neighbour is missing or invalid or the gradient is
+ *             zero.  srrg2_scene_global_indices(dst) gives 3 (plane index) + a.
+ *   waits     every call runs on the volume's stream, in order.  srrg2_tsdf_integrate_frames with out == NULL only queues and
+ *             returns (host images are consumed before it returns; device images must stay untouched until a later call of
+ *             this handle has waited); with `out` it waits once.  The other calls return when their output is complete.
+ *   refused   every destination and the planes unchanged; parameters are checked before the handle.  SRRG2_E_INVALID: a null
+ *             handle, params or (where there is data) data pointer; a handle without srrg2_tsdf_reset; nx, ny or nz outside
+ *             0 .. 2048; with_intensity other than 0 / 1; a voxel_size, mu or step that is not finite or <= 0; an origin or pose
+ *             that is not finite; a weight other than +1 / -1; num_frames < 0; a depth type other than U16 / F32; an intensity
+ *             type other than U8 / F32 where the volume has the plane, other than NONE where it has not; a misaligned or too-small
+ *             stride; what srrg2_adapt_depth_image refuses of its params; min_weight < 1; skip_empty other than 0 / 1; (depth_max -
+ *             depth_min) / step NaN or beyond 2^20; a dst scene that is not 3-D or lives on another device; bad mem.
+ *             SRRG2_E_UNSUPPORTED: K[0][1] != 0; nx ny nz beyond int32 (srrg2_tsdf_to_scene: 3 nx ny nz beyond int32).
+ *             Zero frames, zero pixels and an empty volume are accepted and do nothing. */
+typedef struct srrg2_tsdf_s* srrg2_tsdf_h;
+typedef struct srrg2_tsdf_params {
+  int32_t nx, ny, nz;       /* 0 .. 2048 each */
+  float   voxel_size;       /* metres */
+  float   origin[3];        /* world position of the corner of voxel (0, 0, 0) */
+  int32_t with_intensity;   /* 1: the volume has the isum plane */
+} srrg2_tsdf_params;
+typedef struct srrg2_tsdf_frame_params {
+  float   mu;               /* truncation distance, metres, > 0 */
+  int32_t reserved;         /* 0 */
+} srrg2_tsdf_frame_params;
+typedef struct srrg2_tsdf_raycast_params {
+  float   step;             /* march step along the optical axis, metres, > 0 */
+  int32_t min_weight;       /* >= 1 */
+  int32_t skip_empty;       /* 1: consult the block mask; 0 (default): the plain march */
+  int32_t reserved;         /* 0 */
+} srrg2_tsdf_raycast_params;
+typedef struct srrg2_tsdf_result {
+  int64_t num_frames, num_pixels, num_valid_depth, num_voxel_updates;
+} srrg2_tsdf_result;
+typedef struct srrg2_tsdf_raycast_result {
+  int32_t num_pixels, num_surface;  /* rows cols; pixels with a depth other than 0 */
+  srrg2_adapt_result adapt;         /* what srrg2_adapt_depth_image reported (zeros when dst is NULL) */
+} srrg2_tsdf_raycast_result;
+typedef struct srrg2_tsdf_export_result {
+  int32_t num_points, reserved;
+} srrg2_tsdf_export_result;
+/* a volume on `device`: its own non-blocking stream, its planes in device memory */
+int srrg2_tsdf_create(int device, srrg2_tsdf_h* out);
+int srrg2_tsdf_destroy(srrg2_tsdf_h h);
+/* an empty volume (0 x 0 x 0) of 0.02 m voxels at the origin, no intensity; mu 0.06; step 0.02, min_weight 1, skip_empty 0 */
+void srrg2_tsdf_default_params(srrg2_tsdf_params* p);
+void srrg2_tsdf_default_frame_params(srrg2_tsdf_frame_params* p);
+void srrg2_tsdf_default_raycast_params(srrg2_tsdf_raycast_params* p);
+/* allocates (or re-uses) the planes and zeroes them */
+int srrg2_tsdf_reset(srrg2_tsdf_h h, const srrg2_tsdf_params* p);
+/* depth (and intensity): num_frames images of cam->rows rows, one behind the other (image k begins k rows row_stride bytes behind
+ * the first), in `mem` = SRRG2_MEM_HOST | SRRG2_MEM_DEVICE; camera_in_world: num_frames x 12 floats in HOST memory (the inverse is
+ * formed on the host).  cam: camera_matrix, rows, cols, depth_scale, depth_min, depth_max are read.  One upload; the number of
+ * launches does not depend on num_frames. */
+int srrg2_tsdf_integrate_frames(srrg2_tsdf_h h, const void* depth, int depth_type, int depth_row_stride_bytes, const void* intensity,
+                                int intensity_type, int intensity_row_stride_bytes, int num_frames, const float* camera_in_world,
+                                int mem, const srrg2_depth_adaptor_params* cam, const srrg2_tsdf_frame_params* fp,
+                                int weight /* +1 | -1 */, srrg2_tsdf_result* out /* may be NULL: queue only */);
+/* dst: a 3-D scene on the volume's device, or NULL; depth_out: cam->rows x cam->cols floats, packed, in depth_mem, or NULL */
+int srrg2_tsdf_raycast(srrg2_tsdf_h h, const float* camera_in_world /* 12, host */, const srrg2_depth_adaptor_params* cam,
+                       const srrg2_tsdf_raycast_params* rp, srrg2_scene_h dst, float* depth_out, int depth_mem,
+                       srrg2_tsdf_raycast_result* out /* may be NULL */);
+int srrg2_tsdf_to_scene(srrg2_tsdf_h h, int min_weight, srrg2_scene_h dst, srrg2_tsdf_export_result* out /* may be NULL */);
+/* nx ny nz int32 each to sum / weight / isum (isum: only a volume that has it) in `mem`; any pointer may be NULL */
+int srrg2_tsdf_get_planes(srrg2_tsdf_h h, int32_t* sum, int32_t* weight, int32_t* isum, int mem);
+/* the planes in device memory, valid until the next reset; isum receives NULL when the volume has none (isum itself may be NULL) */
+int srrg2_tsdf_device_arrays(srrg2_tsdf_h h, const int32_t** sum, const int32_t** weight, const int32_t** isum);
+
 /* Feature tracking: which keypoint of the measurement is which landmark of the clipped local map -- the per-frame data
  * association of a visual tracker, a projective window plus the Hamming distance of the 256-bit descriptors.  The reference
  * declares the slot and leaves it empty (CorrespondenceFinder_::compute() is pure virtual, S/registration/correspondence_finder.h:56;

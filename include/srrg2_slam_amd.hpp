@@ -1361,6 +1361,83 @@ private:
   int _bounds_levels = 0;  // the levels of bound planes built from the field as it is
 };
 
+// ---- TSDF volume: depth frames and their poses -> a truncated signed-distance volume -----------------------------------
+// (srrg2_tsdf_*; no reference counterpart, semantics: srrg2_slam_amd.h)
+//   TsdfVolume   reset() allocates the planes from `params`; integrate() fuses a batch of depth frames taken with `camera` from the
+//                given poses (one frame = the per-frame update), remove() takes the same frames out again bit for bit -- after a
+//                pose-graph optimisation only the frames whose pose moved are re-integrated; planes() reads the volume; raycast()
+//                renders it from a pose and runs the depth adaptor on the image: the scene is set_fixed of the projective
+//                point-to-plane slice (frame-to-model tracking); toScene() exports the surface as a cloud with normals.
+class TsdfVolume {
+public:
+  srrg2_tsdf_params params;
+  srrg2_tsdf_frame_params frame;
+  srrg2_tsdf_raycast_params ray;
+  srrg2_depth_adaptor_params camera;  // of the frames and of the raycast (which hands the adaptor's fields on)
+  explicit TsdfVolume(int device = 0) {
+    srrg2_tsdf_default_params(&params);
+    srrg2_tsdf_default_frame_params(&frame);
+    srrg2_tsdf_default_raycast_params(&ray);
+    srrg2_adapt_default_depth_params(&camera);
+    check(srrg2_tsdf_create(device, &_h));
+  }
+  ~TsdfVolume() { srrg2_tsdf_destroy(_h); }  // (waits for queued work)
+  TsdfVolume(const TsdfVolume&)            = delete;
+  TsdfVolume& operator=(const TsdfVolume&) = delete;
+  // a new, empty volume from `params`
+  void reset() { check(srrg2_tsdf_reset(_h, &params)); }
+  // depth (intensity: null for a volume without the plane): num_frames images one behind the other in `mem`;
+  // camera_in_world: num_frames x 12 on the host
+  const srrg2_tsdf_result& integrate(const void* depth, int depth_type, int depth_stride, int num_frames, const float* camera_in_world,
+                                     const void* intensity = nullptr, int intensity_type = SRRG2_IMAGE_NONE, int intensity_stride = 0,
+                                     int mem = SRRG2_MEM_HOST, int weight = 1) {
+    check(srrg2_tsdf_integrate_frames(_h, depth, depth_type, depth_stride, intensity, intensity_type, intensity_stride, num_frames,
+                                      camera_in_world, mem, &camera, &frame, weight, &_result));
+    return _result;
+  }
+  const srrg2_tsdf_result& remove(const void* depth, int depth_type, int depth_stride, int num_frames, const float* camera_in_world,
+                                  const void* intensity = nullptr, int intensity_type = SRRG2_IMAGE_NONE, int intensity_stride = 0,
+                                  int mem = SRRG2_MEM_HOST) {
+    return integrate(depth, depth_type, depth_stride, num_frames, camera_in_world, intensity, intensity_type, intensity_stride, mem, -1);
+  }
+  // queues the work on the volume's stream and returns without waiting; no counters
+  void integrateQueued(const void* depth, int depth_type, int depth_stride, int num_frames, const float* camera_in_world,
+                       const void* intensity = nullptr, int intensity_type = SRRG2_IMAGE_NONE, int intensity_stride = 0,
+                       int mem = SRRG2_MEM_HOST, int weight = 1) {
+    check(srrg2_tsdf_integrate_frames(_h, depth, depth_type, depth_stride, intensity, intensity_type, intensity_stride, num_frames,
+                                      camera_in_world, mem, &camera, &frame, weight, nullptr));
+  }
+  const srrg2_tsdf_result& result() const { return _result; }
+  size_t voxels() const { return (size_t) params.nx * (size_t) params.ny * (size_t) params.nz; }
+  // nx*ny*nz words each, plane index (z ny + y) nx + x; isum stays empty for a volume without the plane
+  void planes(std::vector<int32_t>& sum, std::vector<int32_t>& weight, std::vector<int32_t>& isum) const {
+    sum.assign(voxels(), 0);
+    weight.assign(voxels(), 0);
+    isum.assign(params.with_intensity ? voxels() : 0, 0);
+    check(srrg2_tsdf_get_planes(_h, sum.data(), weight.data(), params.with_intensity ? isum.data() : nullptr, SRRG2_MEM_HOST));
+  }
+  // the depth image a camera at camera_in_world (12 floats) would measure; dst (may be null) receives the depth adaptor's scene
+  std::vector<float> raycast(const float* camera_in_world, Scene<3>* dst = nullptr) {
+    std::vector<float> depth((size_t) (camera.rows > 0 ? camera.rows : 0) * (size_t) (camera.cols > 0 ? camera.cols : 0));
+    check(srrg2_tsdf_raycast(_h, camera_in_world, &camera, &ray, dst ? dst->handle() : nullptr, depth.empty() ? nullptr : depth.data(),
+                             SRRG2_MEM_HOST, &_raycast));
+    return depth;
+  }
+  const srrg2_tsdf_raycast_result& lastRaycast() const { return _raycast; }
+  // the zero crossings between neighbouring voxels as points with normals; dst.globalIndices() are 3 * plane index + axis
+  int toScene(Scene<3>& dst, int min_weight = 1) const {
+    srrg2_tsdf_export_result out{};
+    check(srrg2_tsdf_to_scene(_h, min_weight, dst.handle(), &out));
+    return out.num_points;
+  }
+  srrg2_tsdf_h handle() const { return _h; }
+
+private:
+  srrg2_tsdf_h _h = nullptr;
+  srrg2_tsdf_result _result{};
+  srrg2_tsdf_raycast_result _raycast{};
+};
+
 // ---- binary descriptor database: the matching half of MultiLoopDetectorHBST_ --------------------------------------
 // (S/registration/loop_detector/multi_loop_detector_hbst_impl.cpp:41-197; it stands where the reference keeps its
 // srrg_hbst::BinaryTree256<uint64_t>).  Exact, exhaustive matching on the device; semantics: srrg2_slam_amd.h.

@@ -118,6 +118,14 @@ def OccupancyGrid(device=0):
     return _G(device)
 
 
+def TsdfVolume(device=0):
+    """Truncated signed-distance volume from depth frames and poses on the device: integrate / remove frames, raycast an
+    organised scene with normals from a pose (frame-to-model tracking), export the surface as a 3-D scene; see ``tsdf``."""
+    from .tsdf import TsdfVolume as _T
+
+    return _T(device)
+
+
 def StereoRectifier(device=0):
     """Two ``ImageRectifier``s set from a stereo calibration; both images of a pair rectified in one launch; see ``rectify``."""
     from .rectify import StereoRectifier as _R

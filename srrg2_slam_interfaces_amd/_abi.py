@@ -341,6 +341,43 @@ class GridMapPruneStats(C.Structure):
                 "floor_score": self.floor_score, "seed_block": self.seed_block, "fell_back": self.fell_back}
 
 
+class TsdfParams(C.Structure):
+    """srrg2_tsdf_params"""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("voxel_size", C.c_float), ("origin", C.c_float * 3),
+                ("with_intensity", C.c_int32)]
+
+
+class TsdfFrameParams(C.Structure):
+    """srrg2_tsdf_frame_params"""
+    _fields_ = [("mu", C.c_float), ("reserved", C.c_int32)]
+
+
+class TsdfRaycastParams(C.Structure):
+    """srrg2_tsdf_raycast_params"""
+    _fields_ = [("step", C.c_float), ("min_weight", C.c_int32), ("skip_empty", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TsdfResult(C.Structure):
+    """srrg2_tsdf_result"""
+    _fields_ = [("num_frames", C.c_int64), ("num_pixels", C.c_int64), ("num_valid_depth", C.c_int64), ("num_voxel_updates", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class TsdfRaycastResult(C.Structure):
+    """srrg2_tsdf_raycast_result"""
+    _fields_ = [("num_pixels", C.c_int32), ("num_surface", C.c_int32), ("adapt", AdaptResult)]
+
+    def as_dict(self):
+        return {"num_pixels": self.num_pixels, "num_surface": self.num_surface, "adapt": self.adapt.as_dict()}
+
+
+class TsdfExportResult(C.Structure):
+    """srrg2_tsdf_export_result"""
+    _fields_ = [("num_points", C.c_int32), ("reserved", C.c_int32)]
+
+
 class StereoMatch(C.Structure):
     """srrg2_stereo_match"""
     _fields_ = [("left_pixel", C.c_int32), ("right_pixel", C.c_int32), ("distance", C.c_int32), ("disparity", C.c_float)]

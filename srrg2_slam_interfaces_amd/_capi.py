@@ -137,6 +137,24 @@ def lib():
                                                           C.POINTER(abi.GridMapScanParams), C.POINTER(abi.GridMapMatchParams),
                                                           C.POINTER(abi.GridMapPruneParams), C.POINTER(abi.GridMapMatchResult),
                                                           C.POINTER(abi.GridMapPruneStats)]
+        # srrg2_tsdf_* (tsdf.TsdfVolume)
+        _LIB.srrg2_tsdf_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        _LIB.srrg2_tsdf_destroy.argtypes = [C.c_void_p]
+        _LIB.srrg2_tsdf_default_params.argtypes = [C.POINTER(abi.TsdfParams)]
+        _LIB.srrg2_tsdf_default_params.restype = None
+        _LIB.srrg2_tsdf_default_frame_params.argtypes = [C.POINTER(abi.TsdfFrameParams)]
+        _LIB.srrg2_tsdf_default_frame_params.restype = None
+        _LIB.srrg2_tsdf_default_raycast_params.argtypes = [C.POINTER(abi.TsdfRaycastParams)]
+        _LIB.srrg2_tsdf_default_raycast_params.restype = None
+        _LIB.srrg2_tsdf_reset.argtypes = [C.c_void_p, C.POINTER(abi.TsdfParams)]
+        _LIB.srrg2_tsdf_integrate_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                     C.c_void_p, C.c_int, C.POINTER(abi.DepthAdaptorParams),
+                                                     C.POINTER(abi.TsdfFrameParams), C.c_int, C.POINTER(abi.TsdfResult)]
+        _LIB.srrg2_tsdf_raycast.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(abi.DepthAdaptorParams), C.POINTER(abi.TsdfRaycastParams),
+                                            C.c_void_p, C.c_void_p, C.c_int, C.POINTER(abi.TsdfRaycastResult)]
+        _LIB.srrg2_tsdf_to_scene.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(abi.TsdfExportResult)]
+        _LIB.srrg2_tsdf_get_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        _LIB.srrg2_tsdf_device_arrays.argtypes = [C.c_void_p, C.POINTER(i32p), C.POINTER(i32p), C.POINTER(i32p)]
         # srrg2_scene_track_features (mapping.FeatureTracker)
         _LIB.srrg2_track_default_params.argtypes = [C.POINTER(abi.TrackParams)]
         _LIB.srrg2_track_default_params.restype = None
